@@ -9,7 +9,7 @@ stream: la_gpu_lz4_decode() = block-checksum kernel, measure kernel, scan, expan
 frame-checksum kernel, summary.  Inputs (compressed stream + host-built block table) are
 resident in HBM before the timed region; outputs stay in HBM.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself
 (torch.distributed.run as a CHILD process, before anything here has touched a GPU).
@@ -23,8 +23,17 @@ separately and reported beside the sharded number.
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline      -- dominant kernel (lz4 expand): algorithmic bytes C+U per launch divided by
                    its average duration measured with HIP events on the work stream
+A plain run sets up, warms up, times the K steps, checks the step's own verdict (every checksum,
+the tiled output's period) and prints the line.  --full adds everything else the line can carry,
+each measured outside the timed steps:
   cpu_baseline  -- the CPU oracle (a port of the reference filter) on a bounded sample,
-                   1 thread, on this box's host cores
+                   1 thread, on the host's cores, and its bytes compared with the device's
+  api_level     -- the whole drop-in path (la_cat) as a child process
+  peak_measured_copy (in roofline) -- a device copy microbenchmark
+  secondary, tertiary -- the gzip C3 and zstd measurements
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64,
+about 17 MiB at the default size): the per-block results and the summary whole, the decoded bytes
+as a seeded sample of 4 KiB runs and as two sums per 64 KiB of output (plain and position-weighted).
 """
 import argparse
 import json
@@ -61,7 +70,57 @@ def parse():
                     help="N > 1: also time one gather of all decoded ranges to rank 0 (needs about N x 16 GiB free on GPU 0)")
     ap.add_argument("--workload", choices=["lz4", "gzip"], default="lz4",
                     help="lz4 = BASELINE configs[1] (the headline); gzip = configs[2] shape (64 KiB BGZF-style members)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines with the oracle comparison, the A-level (la_cat) run, the device copy "
+                         "microbenchmark and (lz4 at 16 GiB) the gzip C3 / zstd measurements; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="lz4: write what the last timed step computed to DIR/<name>.npy (float32 / float64, well under 64 MB)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload != "lz4":
+        ap.error("--dump-outputs covers the lz4 headline workload only")
+    return args
+
+
+DUMP_SEED = 0x4C414455
+DUMP_RUNS, DUMP_RUN_BYTES = 512, 4096
+
+
+def dump_outputs(torch, plan, U_bytes, out_dir, suffix=""):
+    """What the last timed step handed its caller, as .npy files in float32 / float64 (every value exact): the summary,
+    the per-block and per-frame results whole, and the decoded bytes twice reduced -- DUMP_RUNS runs of DUMP_RUN_BYTES at
+    offsets drawn from a fixed seed, and per 64 KiB of output the byte sum and the sum weighted by (offset % 251) + 1,
+    which together cover every byte.  Outside the timed region; reads only what the step wrote."""
+    os.makedirs(out_dir, exist_ok=True)
+    out_len, dst_off, bst, fst = plan.arrays()          # syncs the context's stream
+    sm = plan.summary()
+    arrays = {
+        "summary": np.array([float(sm[f]) for f in sm.dtype.names if f != "reserved"], dtype=np.float64),
+        "block_out_len": out_len.astype(np.float64),
+        "block_dst_off": dst_off[:plan.n_blocks + 1].astype(np.float64),
+        "block_status": bst.astype(np.float32),
+        "frame_status": fst.astype(np.float32),
+    }
+    dst = plan.d_dst[:U_bytes]
+    run = min(DUMP_RUN_BYTES, U_bytes)
+    rng = np.random.default_rng(DUMP_SEED)
+    offs = np.sort(rng.integers(0, U_bytes - run + 1, size=DUMP_RUNS, dtype=np.int64))
+    at = torch.from_numpy(offs).to(dst.device)[:, None] + torch.arange(run, device=dst.device)[None, :]
+    arrays["decoded_sample"] = dst[at].cpu().numpy().astype(np.float32)
+    arrays["decoded_sample_offsets"] = offs.astype(np.float64)
+    ch = BLOCK
+    w = torch.arange(ch, dtype=torch.int32, device=dst.device) % 251 + 1
+    sums = []
+    rows_per = 1024                                      # 64 MiB of output per reduction
+    for r0 in range(0, U_bytes // ch, rows_per):
+        x = dst[r0 * ch:min(U_bytes // ch, r0 + rows_per) * ch].view(-1, ch).to(torch.int32)
+        sums.append(torch.stack([x.sum(dim=1, dtype=torch.int64), (x * w).sum(dim=1, dtype=torch.int64)], dim=1))
+    if U_bytes % ch:
+        x = dst[U_bytes - U_bytes % ch:].to(torch.int32)
+        sums.append(torch.stack([x.sum(dtype=torch.int64), (x * w[:x.numel()]).sum(dtype=torch.int64)])[None, :])
+    arrays["decoded_sums_per_64k"] = (torch.cat(sums).cpu().numpy().astype(np.float64) if sums
+                                      else np.zeros((0, 2), dtype=np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def kernel_source_id():
@@ -399,7 +458,7 @@ def main_gzip(args, as_secondary=False):
     for t in range(1, tiles):
         ok = ok and bool(torch.equal(plan.d_dst[:plain.size], plan.d_dst[t * plain.size:(t + 1) * plain.size]))
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle_lib as O
         reps, el, t1 = 0, 0.0, time.time()
         while el < 10.0:
@@ -498,7 +557,7 @@ def main():
                  % (args.gpus, world, args.gpus, args.gpus))
     import streams as S
     api = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         api = api_level(S, args)      # child process, before this one initialises the GPU
     import torch
     import torch.distributed as dist
@@ -565,6 +624,9 @@ def main():
         n = min(tile_bytes, U_bytes - tile_bytes - o)
         ok = ok and bool(torch.equal(plan.d_dst[o:o + n], plan.d_dst[o + tile_bytes:o + tile_bytes + n]))
 
+    if args.dump_outputs:
+        dump_outputs(torch, plan, U_bytes, args.dump_outputs, "" if world == 1 else "_rank%d" % rank)
+
     # the only exchange: per-rank summaries (no decoded bytes move; outputs stay sharded)
     from libarchive_amd.shard import exchange_summaries
     dt_max, U_all, C_all, ok_all = exchange_summaries(dist, coll_device, dt, U_bytes, C_bytes, ok)
@@ -592,7 +654,7 @@ def main():
     if rank == 0:
         cpu = None
         sample_ok = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 measurement
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 measurement
             import oracle_lib as O  # checker / baseline only
             cpu, ref_out = cpu_baseline(S, O, img_u, idx_u, args.cpu_sample_mib)
             got = plan.d_dst[:len(ref_out)].cpu().numpy()
@@ -611,7 +673,7 @@ def main():
             else:
                 traffic_note = "profiles/r03_traffic.json was measured on another build of libla_gpu.so (%s, now %s): not quoted" % (
                     rec.get("library_sha16"), kernel_source_id())
-        copy_peak = measured_copy_peak(ctx, torch) if world == 1 else None
+        copy_peak = measured_copy_peak(ctx, torch) if world == 1 and args.full else None
         nl = 4 if (plan.n_blocks >= 32768 and not args.general_only) else 1   # slice launches of the expand kernel per step
         # per-launch algorithmic bytes / per-launch duration (the slices are equal, so this is the ratio of the sums)
         achieved = (C_bytes + U_bytes) / (exp_ms * 1e-3) / 1e9
@@ -667,7 +729,7 @@ def main():
             "api_level": api,
             "gather_mode": gather,
         }
-        if world == 1 and not args.no_secondary and not args.no_cpu_baseline and abs(args.gib - 16.0) < 1e-6:
+        if world == 1 and args.full and not args.no_secondary and not args.no_cpu_baseline and abs(args.gib - 16.0) < 1e-6:
             # BASELINE configs[2] (C3) in the same command: the lz4 buffers go first
             del plan, d_src
             torch.cuda.empty_cache()
