@@ -66,10 +66,10 @@ typedef struct la_lz4_resume {
 	uint32_t flags;		/* bit 0: block checksums, bit 1: content checksum, bit 2: dependent blocks */
 	uint32_t blocks_so_far;	/* blocks of the frame indexed in earlier windows */
 } la_lz4_resume;
-int  la_lz4_index_build2(const uint8_t *img, uint64_t len, int at_eof, la_lz4_resume *rs, la_lz4_index *idx);
-/* out_budget: stop indexing in front of the block that would take the window's decoded bytes (sum of
- * dst_cap) past it (0 = no bound); the rest of the stream is the next window's */
-int  la_lz4_index_build3(const uint8_t *img, uint64_t len, int at_eof, la_lz4_resume *rs, uint64_t out_budget,
+/* Full entry point (the filter's).  rs: resume record, NULL = none.  out_budget: stop indexing in front of the
+ * block that would take the window's decoded bytes (sum of dst_cap) past it (0 = no bound); the rest of the stream
+ * is the next window's.  la_lz4_index_build is this with rs NULL and no budget. */
+int  la_lz4_index_build_ex(const uint8_t *img, uint64_t len, int at_eof, la_lz4_resume *rs, uint64_t out_budget,
          la_lz4_index *idx);
 void la_lz4_index_free(la_lz4_index *idx);
 
@@ -99,23 +99,24 @@ typedef struct la_gz_index {
 size_t la_gz_header_parse(const uint8_t *p, size_t avail, la_gz_header *h);
 int    la_gz_bid_bytes(const uint8_t *p, size_t avail);
 /* Walk img[0..len): member table with per-member output slots (dst_off assigned back to
- * back from each member's ISIZE claim).  first_only: index just the first member. */
-uint64_t la_gz_span_limit(void);	/* 4 GiB - 1 (LA_GZ_TEST_SPAN_LIMIT lowers it for tests) */
+ * back from each member's ISIZE claim).  The plain entry point is la_gz_index_build_ex with
+ * no hints, no flags, no budget and the span limit LA_GZ_SPAN_LIMIT. */
 int    la_gz_index_build(const uint8_t *img, uint64_t len, int at_eof, la_gz_index *idx);
-/* first_skip: candidate boundaries to pass over for the first member (refuted by a decode);
- * first_cap: minimum output slot of the first member (its ISIZE claim proved too small) */
-int    la_gz_index_build2(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
-           uint32_t first_cap, la_gz_index *idx);
 /* flags: LA_GZ_INDEX_STRICT = a speculative boundary must also carry the XFL / OS bytes real writers emit
  * (XFL 0, 2 or 4; OS 0..13 or 255) -- a few thousand times fewer false boundaries inside deflate data.  A stream
  * whose headers do not look like that is still read correctly: the decode of the member in front ends early, the
  * filter sees a header there and goes on without the flag (la_filter_gzip.c). */
 #define LA_GZ_INDEX_STRICT 1u
-int    la_gz_index_build3(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
-           uint32_t first_cap, uint32_t flags, la_gz_index *idx);
-/* out_budget: stop indexing once the members taken ask for this many decoded bytes (0 = no bound) */
-int    la_gz_index_build4(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
-           uint32_t first_cap, uint32_t flags, uint64_t out_budget, la_gz_index *idx);
+/* Largest compressed span of ONE member the 32-bit member table can express */
+#define LA_GZ_SPAN_LIMIT 0xFFFFFFFFull
+/* Full entry point (the filter's).
+ * first_skip: candidate boundaries to pass over for the first member (refuted by a decode);
+ * first_cap: minimum output slot of the first member (its ISIZE claim proved too small);
+ * out_budget: stop indexing once the members taken ask for this many decoded bytes (0 = no bound);
+ * span_limit: a member whose compressed span passes it ends the walk with LA_END_GZ_TOO_LARGE
+ * (LA_GZ_SPAN_LIMIT, or lower in tests). */
+int    la_gz_index_build_ex(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
+           uint32_t first_cap, uint32_t flags, uint64_t out_budget, uint64_t span_limit, la_gz_index *idx);
 void   la_gz_index_free(la_gz_index *idx);
 
 /* ---- zstd (host/la_zstd_index.c) ---- */
@@ -141,6 +142,58 @@ const unsigned char *la_bid_peek(struct archive_read_filter *filter, size_t want
 int    la_bid_gzip_parallel(const unsigned char *p, size_t n, size_t hdr_len, size_t lookahead);
 int    la_bid_lz4_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead);
+
+/* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the lz4, gzip and zstd read filters ---- */
+/* LA_GPU_DEVICE: the device ordinal every filter, the ZIP reader and the hash drop-in open (default 0) */
+int  la_env_device(void);
+
+/* One filter's window: its device, its size (read once, at init) and whether upstream has ended */
+typedef struct la_window {
+	la_gpu_ctx *gpu;
+	const char *name;		/* "lz4", "gzip", "zstd": in the error strings */
+	size_t      batch_bytes;	/* compressed bytes of the next window: min(16 MiB, target), then ramped */
+	size_t      target_bytes;	/* LA_GPU_BATCH_MIB, default 64 */
+	size_t      max_batch_bytes;	/* LA_GPU_MAX_BATCH_MIB, default 2048: how far a window may widen */
+	uint64_t    out_budget;		/* LA_GPU_OUT_BUDGET_MIB, default 4096: decoded bytes one window may ask for */
+	int         upstream_eof;
+} la_window;
+/* Read the knobs and open the device; on failure "Can't initialize <name> GPU data plane ..." and ARCHIVE_FATAL */
+int  la_window_open(struct archive_read_filter *self, la_window *w, const char *name);
+/* batch = min(2 x batch, target) */
+void la_window_ramp(la_window *w);
+/* "<name> GPU data plane: <what> failed: <device error>"; returns ARCHIVE_FATAL */
+int  la_window_fail(struct archive_read_filter *self, const la_window *w, const char *what);
+
+/* A grown buffer: pinned host, device or malloc'ed host memory.  The growers start at 1 MiB and double;
+ * 0, or -1 when the allocation failed.  la_buf_pinned copies the first `keep` bytes over. */
+enum { LA_BUF_HOST = 0, LA_BUF_PINNED, LA_BUF_DEV };
+typedef struct la_buf {
+	uint8_t *p;
+	size_t   cap;
+	int      kind;	/* LA_BUF_*, set by the grower */
+} la_buf;
+int  la_buf_pinned(la_gpu_ctx *gpu, la_buf *b, size_t need, size_t keep);
+int  la_buf_dev(la_gpu_ctx *gpu, la_buf *b, size_t need);
+int  la_buf_host(la_buf *b, size_t need);
+void la_buf_release(la_gpu_ctx *gpu, la_buf *b);
+
+/* Append upstream bytes to the pinned stage[0..*len) until it holds a window (w->batch_bytes) or upstream
+ * ends (w->upstream_eof).  ARCHIVE_FATAL with upstream's error left in place, or after la_window_fail. */
+int  la_window_gather(struct archive_read_filter *self, la_window *w, la_buf *stage, size_t *len);
+
+/* A verdict reported after the bytes in front of it: rc (ARCHIVE_OK = none) and the message to set with it.
+ * fmt NULL: no message (upstream already set the error, or the reference returns ARCHIVE_FATAL without one). */
+typedef struct la_verdict {
+	int  rc;
+	int  has_msg;
+	char msg[256];
+} la_verdict;
+#if defined(__GNUC__)
+__attribute__((format(printf, 3, 4)))
+#endif
+void la_verdict_set(la_verdict *v, int rc, const char *fmt, ...);
+/* sets the message, if any, and returns rc */
+int  la_verdict_report(struct archive_read_filter *self, const la_verdict *v);
 
 /* ---- hash drop-ins (host/la_hash_dropin.c) ----
  * The 4-pointer table of libarchive/archive_xxhash.h:37-46 (defined as `__archive_xxhash` when built

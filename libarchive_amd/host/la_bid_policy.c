@@ -1,5 +1,8 @@
 /*
- * la_bid_policy.c -- should the GPU filter take this stream at all?
+ * la_bid_policy.c -- the host code the three read filters (la_filter_lz4.c, la_filter_gzip.c, la_filter_zstd.c)
+ * share: the bid policy, and below it the window plumbing.
+ *
+ * Bid policy: should the GPU filter take this stream at all?
  *
  * The device decodes INDEPENDENT units in parallel (lz4 frames / blocks, gzip members, zstd frames); ONE serial
  * unit -- a plain single-member .gz (gzip.c:431-511), a one-frame .zst (zstd.c:196-260), a single lz4 frame whose
@@ -18,6 +21,8 @@
  */
 #include "la_read_private.h"
 #include "la_host.h"
+#include <stdarg.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -106,4 +111,175 @@ int la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead)
 	if (la_zstd_index_build(p, n, 0, ~0ull, fr, 4, &r) != 0)
 		return 1;	/* let the filter report what is wrong with it */
 	return r.n_frames >= 1;
+}
+
+/*
+ * Window plumbing: the window configuration and its ramp, opening the device, the "GPU data plane" error strings,
+ * the buffer growers, the gather loop and the deferred verdict.  What differs between the filters -- the walker,
+ * the launch, the stream-order walk of the results -- stays in each filter.
+ */
+#define MIB ((size_t)1 << 20)
+
+int la_env_device(void)
+{
+	const char *d = getenv("LA_GPU_DEVICE");
+	return d ? atoi(d) : 0;
+}
+
+static size_t env_mib(const char *name, int dflt)
+{
+	const char *v = getenv(name);
+	return (size_t)(v && atoi(v) > 0 ? atoi(v) : dflt) << 20;
+}
+
+int la_window_open(struct archive_read_filter *self, la_window *w, const char *name)
+{
+	w->name = name;
+	/* The window RAMPS: the first one holds 16 MiB of the stream, the next 32, up to the target.  What a window
+	 * costs before its first byte comes back -- pinned staging and slab of its size (about half a millisecond
+	 * per MiB), the gather, the upload -- is paid before anything overlaps, so a stream of 1 GiB took 1.0 s
+	 * with fixed 256 MiB windows and 0.48 s with 16 MiB ones, and 16 GiB 1.70 s against 1.41 s at 64 MiB
+	 * (profiles/r03_alevel.txt): small streams want small windows, long ones 64-128 MiB. */
+	w->target_bytes = env_mib("LA_GPU_BATCH_MIB", 64);
+	w->batch_bytes = w->target_bytes < 16 * MIB ? w->target_bytes : 16 * MIB;
+	w->max_batch_bytes = env_mib("LA_GPU_MAX_BATCH_MIB", 2048);
+	w->out_budget = env_mib("LA_GPU_OUT_BUDGET_MIB", 4096);
+	const int rc = la_gpu_open(la_env_device(), &w->gpu);
+	if (rc != LA_OK) {
+		w->gpu = NULL;
+		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+		    "Can't initialize %s GPU data plane (la_gpu_open: %d); no CPU fallback is built", name, rc);
+		return ARCHIVE_FATAL;
+	}
+	return ARCHIVE_OK;
+}
+
+void la_window_ramp(la_window *w)
+{
+	if (w->batch_bytes < w->target_bytes)
+		w->batch_bytes = w->batch_bytes * 2 < w->target_bytes ? w->batch_bytes * 2 : w->target_bytes;
+}
+
+int la_window_fail(struct archive_read_filter *self, const la_window *w, const char *what)
+{
+	archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+	    "%s GPU data plane: %s failed: %s", w->name, what, w->gpu ? la_gpu_last_error(w->gpu) : "no device");
+	return ARCHIVE_FATAL;
+}
+
+/* Growers: the capacity starts at 1 MiB and doubles until it holds `need`.  0, or -1 when the allocation failed. */
+static size_t grown(size_t cap, size_t need)
+{
+	size_t nc = cap ? cap : MIB;
+	while (nc < need)
+		nc *= 2;
+	return nc;
+}
+
+int la_buf_pinned(la_gpu_ctx *gpu, la_buf *b, size_t need, size_t keep)
+{
+	if (b->cap >= need)
+		return 0;
+	const size_t nc = grown(b->cap, need);
+	void *np = NULL;
+	if (la_gpu_malloc_host(gpu, &np, nc) != LA_OK)
+		return -1;	/* (the old buffer stays) */
+	if (keep)
+		memcpy(np, b->p, keep);
+	if (b->p)
+		la_gpu_free_host(gpu, b->p);
+	b->p = np;
+	b->cap = nc;
+	b->kind = LA_BUF_PINNED;
+	return 0;
+}
+
+int la_buf_dev(la_gpu_ctx *gpu, la_buf *b, size_t need)
+{
+	if (b->cap >= need)
+		return 0;
+	const size_t nc = grown(b->cap, need);
+	la_buf_release(gpu, b);
+	void *np = NULL;
+	if (la_gpu_malloc(gpu, &np, nc) != LA_OK)
+		return -1;
+	b->p = np;
+	b->cap = nc;
+	b->kind = LA_BUF_DEV;
+	return 0;
+}
+
+int la_buf_host(la_buf *b, size_t need)
+{
+	if (b->cap >= need)
+		return 0;
+	const size_t nc = grown(b->cap, need);
+	la_buf_release(NULL, b);
+	if ((b->p = malloc(nc)) == NULL)
+		return -1;
+	b->cap = nc;
+	b->kind = LA_BUF_HOST;
+	return 0;
+}
+
+void la_buf_release(la_gpu_ctx *gpu, la_buf *b)
+{
+	if (b->p) {
+		if (b->kind == LA_BUF_PINNED)
+			la_gpu_free_host(gpu, b->p);
+		else if (b->kind == LA_BUF_DEV)
+			la_gpu_free(gpu, b->p);
+		else
+			free(b->p);
+	}
+	b->p = NULL;
+	b->cap = 0;
+}
+
+int la_window_gather(struct archive_read_filter *self, la_window *w, la_buf *stage, size_t *len)
+{
+	const size_t want = w->batch_bytes;
+	while (!w->upstream_eof && *len < want) {
+		ssize_t avail;
+		const void *up = __archive_read_filter_ahead(self->upstream, 1, &avail);
+		if (up == NULL) {
+			if (avail < 0)
+				return ARCHIVE_FATAL;	/* upstream already set the error */
+			w->upstream_eof = 1;
+			break;
+		}
+		size_t n = (size_t)avail;
+		if (n > want - *len)
+			n = want - *len;
+		/* a stream that has already filled 8 MiB gets the whole window at once instead of
+		 * five more rounds of pin-a-bigger-buffer-and-copy */
+		size_t need = *len + n;
+		if (need > 8 * MIB && need < want)
+			need = want;
+		if (la_buf_pinned(w->gpu, stage, need, *len) < 0)
+			return la_window_fail(self, w, "pinned staging allocation");
+		memcpy(stage->p + *len, up, n);
+		*len += n;
+		__archive_read_filter_consume(self->upstream, (int64_t)n);
+	}
+	return ARCHIVE_OK;
+}
+
+void la_verdict_set(la_verdict *v, int rc, const char *fmt, ...)
+{
+	v->rc = rc;
+	v->has_msg = fmt != NULL;
+	if (fmt) {
+		va_list ap;
+		va_start(ap, fmt);
+		vsnprintf(v->msg, sizeof(v->msg), fmt, ap);
+		va_end(ap);
+	}
+}
+
+int la_verdict_report(struct archive_read_filter *self, const la_verdict *v)
+{
+	if (v->has_msg)
+		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "%s", v->msg);
+	return v->rc;
 }

@@ -41,35 +41,29 @@ static double gz_now(void)
 #define OUT_BLOCK 65536u	/* gzip.c:314 */
 
 struct gzip_private {
-	la_gpu_ctx *gpu;
-	uint8_t *stage;
-	size_t stage_cap, stage_len, batch_bytes;
-	size_t target_bytes;	/* the window ramps up to this size (16, 32, 64 MiB ...: la_filter_lz4.c, init) */
-	int upstream_eof;
-	void *d_src, *d_dst, *d_tabs;
-	size_t d_src_cap, d_dst_cap, d_tabs_cap;
-	uint8_t *slab;		/* [carry | this batch's bytes] */
-	size_t slab_cap;
+	la_window w;
+	la_buf stage;		/* pinned */
+	size_t stage_len;
+	la_buf d_src, d_dst, d_tabs;
+	la_buf slab;		/* [carry | this batch's bytes] (pinned) */
 	/* The second slab: while the caller holds `slab`, the NEXT window's decoded bytes are already on their way into this
 	 * one (queued behind the decode by gz_prepare, at the offset the carry will take).  When the window turns out as
 	 * its index promised -- every member exactly as long as its ISIZE said, nothing refused -- the bytes are in place
 	 * when the next read() looks, the carry is put in front and the two slabs change roles; otherwise the copy is done
 	 * again the ordinary way.  (The lz4 and zstd filters have two whole slots; here one slab more is what was missing.) */
-	uint8_t *slab2;
-	size_t slab2_cap;
+	la_buf slab2;
 	int no_ahead;		/* LA_GZ_NO_COPY_AHEAD=1 (measurements: the single-slab behaviour of round 2) */
 	int ahead_ok;		/* a copy into slab2 is queued ... */
 	size_t ahead_rem;	/* ... behind this many carry bytes ... */
 	size_t ahead_len;	/* ... this long */
 	size_t carry_len;	/* decoded but not yet delivered (< 64 KiB) */
 	size_t last_ret;	/* bytes handed out by the previous read() */
-	la_gz_result *h_res;
-	size_t h_res_cap;
+	la_buf h_res;
 	uint64_t total_out;	/* bytes decoded so far (delivered + carry) */
 	uint32_t hint_skip, hint_cap;
-	uint64_t out_budget;	/* decoded bytes (output slots) one window may ask for: LA_GPU_OUT_BUDGET_MIB, default 4096 */
 	int strict;
 	uint32_t slot_limit;	/* an output slot cannot pass 2 GiB (32-bit positions on the device); LA_GZ_TEST_SLOT_LIMIT lowers it for tests */
+	uint64_t span_limit;	/* a member's compressed span cannot pass 4 GiB - 1 (32-bit table); LA_GZ_TEST_SPAN_LIMIT lowers it */
 	int trace;
 	int loose;		/* the stream's headers carry unusual XFL / OS bytes: index without LA_GZ_INDEX_STRICT */
 	/* header metadata (gzip.c:280-296) */
@@ -81,10 +75,7 @@ struct gzip_private {
 	la_gz_index idx;
 	int inflight;
 	size_t o_res;
-	int upstream_failed;	/* upstream reported an error while the next window was gathered ahead */
-	int pending_fatal;
-	int pending_has_msg;
-	char pending_msg[128];
+	la_verdict verdict;	/* what the next read() reports once the bytes in front of it are out */
 	int eof;
 };
 
@@ -163,13 +154,6 @@ static int gzip_bidder_bid(struct archive_read_filter_bidder *self, struct archi
 	}
 }
 
-static int gz_gpu_fail(struct archive_read_filter *self, struct gzip_private *st, const char *what)
-{
-	archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-	    "gzip GPU data plane: %s failed: %s", what, st->gpu ? la_gpu_last_error(st->gpu) : "no device");
-	return ARCHIVE_FATAL;
-}
-
 static int gzip_bidder_init(struct archive_read_filter *self)
 {
 	self->code = ARCHIVE_FILTER_GZIP;
@@ -179,9 +163,7 @@ static int gzip_bidder_init(struct archive_read_filter *self)
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
 		return ARCHIVE_FATAL;
 	}
-	const char *dev = getenv("LA_GPU_DEVICE"), *bm = getenv("LA_GPU_BATCH_MIB"), *sv = getenv("LA_GZIP_STRICT");
-	st->target_bytes = (size_t)(bm && atoi(bm) > 0 ? atoi(bm) : 64) << 20;
-	st->batch_bytes = st->target_bytes < ((size_t)16 << 20) ? st->target_bytes : (size_t)16 << 20;
+	const char *sv = getenv("LA_GZIP_STRICT");
 	st->strict = sv && atoi(sv) != 0;
 	st->slot_limit = 0x80000000u;
 	{
@@ -189,14 +171,15 @@ static int gzip_bidder_init(struct archive_read_filter *self)
 		if (sl != NULL && strtoul(sl, NULL, 10) >= 65536 && strtoul(sl, NULL, 10) < st->slot_limit)
 			st->slot_limit = (uint32_t)strtoul(sl, NULL, 10);
 	}
-	const char *ob = getenv("LA_GPU_OUT_BUDGET_MIB");
-	st->out_budget = (uint64_t)(ob && atoi(ob) > 0 ? atoi(ob) : 4096) << 20;
+	st->span_limit = LA_GZ_SPAN_LIMIT;
+	{
+		const char *v = getenv("LA_GZ_TEST_SPAN_LIMIT");
+		if (v != NULL && strtoull(v, NULL, 10) > 0 && strtoull(v, NULL, 10) < st->span_limit)
+			st->span_limit = strtoull(v, NULL, 10);
+	}
 	st->trace = getenv("LA_GPU_TRACE") != NULL && atoi(getenv("LA_GPU_TRACE")) != 0;
 	st->no_ahead = getenv("LA_GZ_NO_COPY_AHEAD") != NULL && atoi(getenv("LA_GZ_NO_COPY_AHEAD")) != 0;
-	int rc = la_gpu_open(dev ? atoi(dev) : 0, &st->gpu);
-	if (rc != LA_OK) {
-		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-		    "Can't initialize gzip GPU data plane (la_gpu_open: %d); no CPU fallback is built", rc);
+	if (la_window_open(self, &st->w, "gzip") != ARCHIVE_OK) {
 		free(st);
 		return ARCHIVE_FATAL;
 	}
@@ -215,51 +198,7 @@ static int gzip_read_header(struct archive_read_filter *self, struct archive_ent
 	return ARCHIVE_OK;
 }
 
-static int gz_grow_pinned(struct gzip_private *st, uint8_t **p, size_t *cap, size_t need, size_t keep)
-{
-	if (*cap >= need)
-		return 0;
-	size_t nc = *cap ? *cap : (1u << 20);
-	while (nc < need)
-		nc *= 2;
-	void *np = NULL;
-	if (la_gpu_malloc_host(st->gpu, &np, nc) != LA_OK)
-		return -1;
-	if (keep)
-		memcpy(np, *p, keep);
-	if (*p)
-		la_gpu_free_host(st->gpu, *p);
-	*p = np;
-	*cap = nc;
-	return 0;
-}
-
-static int gz_grow_dev(struct gzip_private *st, void **p, size_t *cap, size_t need)
-{
-	if (*cap >= need)
-		return 0;
-	size_t nc = *cap ? *cap : (1u << 20);
-	while (nc < need)
-		nc *= 2;
-	if (*p)
-		la_gpu_free(st->gpu, *p);
-	*p = NULL;
-	*cap = 0;
-	if (la_gpu_malloc(st->gpu, p, nc) != LA_OK)
-		return -1;
-	*cap = nc;
-	return 0;
-}
-
 #define ALIGN256(x) (((x) + 255) & ~(size_t)255)
-
-static void gz_set_fatal(struct gzip_private *st, const char *msg)
-{
-	st->pending_fatal = 1;
-	st->pending_has_msg = msg != NULL;
-	if (msg)
-		snprintf(st->pending_msg, sizeof(st->pending_msg), "%s", msg);
-}
 
 /*
  * One batch: decode every indexed member, then walk the results in stream
@@ -277,40 +216,37 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 	const size_t o_res = o; o += ALIGN256((size_t)n * sizeof(la_gz_result));
 	const size_t o_sum = o; o += 256;
 	size_t src_len = (size_t)x->consumed;
+	la_gpu_ctx *gpu = st->w.gpu;
 	if (phase == 0 &&
-	    (gz_grow_dev(st, &st->d_src, &st->d_src_cap, src_len + 64) < 0 ||
-	     gz_grow_dev(st, &st->d_dst, &st->d_dst_cap, (size_t)x->max_out + 64) < 0 ||
-	     gz_grow_dev(st, &st->d_tabs, &st->d_tabs_cap, o) < 0))
-		return gz_gpu_fail(self, st, "device allocation");
-	uint8_t *T = st->d_tabs;
+	    (la_buf_dev(gpu, &st->d_src, src_len + 64) < 0 ||
+	     la_buf_dev(gpu, &st->d_dst, (size_t)x->max_out + 64) < 0 ||
+	     la_buf_dev(gpu, &st->d_tabs, o) < 0))
+		return la_window_fail(self, &st->w, "device allocation");
+	uint8_t *T = st->d_tabs.p;
 	const double b0 = st->trace ? gz_now() : 0;
 	/* (the compressed bytes are already on their way: gz_prepare) */
-	if (phase == 0 && la_gpu_memcpy_h2d(st->gpu, T + o_mem, x->members, (size_t)n * sizeof(la_gz_member)) != LA_OK)
-		return gz_gpu_fail(self, st, "host to device copy");
+	if (phase == 0 && la_gpu_memcpy_h2d(gpu, T + o_mem, x->members, (size_t)n * sizeof(la_gz_member)) != LA_OK)
+		return la_window_fail(self, &st->w, "host to device copy");
 	la_gz_batch bt;
 	memset(&bt, 0, sizeof(bt));
-	bt.d_src = st->d_src; bt.src_bytes = src_len;
+	bt.d_src = st->d_src.p; bt.src_bytes = src_len;
 	bt.d_members = (const la_gz_member *)(T + o_mem); bt.n_members = n;
-	bt.d_dst = st->d_dst; bt.dst_cap = x->max_out;
+	bt.d_dst = st->d_dst.p; bt.dst_cap = x->max_out;
 	bt.d_results = (la_gz_result *)(T + o_res);
 	bt.d_summary = (la_batch_summary *)(T + o_sum);
 	if (phase == 0) {
-		if (la_gpu_gzip_decode(st->gpu, &bt) != LA_OK)
-			return gz_gpu_fail(self, st, "la_gpu_gzip_decode");
+		if (la_gpu_gzip_decode(gpu, &bt) != LA_OK)
+			return la_window_fail(self, &st->w, "la_gpu_gzip_decode");
 		return 0;
 	}
-	if (st->h_res_cap < n) {
-		free(st->h_res);
-		st->h_res = malloc((size_t)n * sizeof(la_gz_result));
-		st->h_res_cap = st->h_res ? n : 0;
-		if (!st->h_res) {
-			archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
-			return ARCHIVE_FATAL;
-		}
+	if (la_buf_host(&st->h_res, (size_t)n * sizeof(la_gz_result)) < 0) {
+		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
+		return ARCHIVE_FATAL;
 	}
-	if (la_gpu_memcpy_d2h(st->gpu, st->h_res, T + o_res, (size_t)n * sizeof(la_gz_result)) != LA_OK ||
-	    la_gpu_sync(st->gpu) != LA_OK)
-		return gz_gpu_fail(self, st, "result copy");
+	const la_gz_result *res = (const la_gz_result *)st->h_res.p;
+	if (la_gpu_memcpy_d2h(gpu, st->h_res.p, T + o_res, (size_t)n * sizeof(la_gz_result)) != LA_OK ||
+	    la_gpu_sync(gpu) != LA_OK)
+		return la_window_fail(self, &st->w, "result copy");
 	const double b1 = st->trace ? gz_now() : 0;
 
 	/* ---- stream-order walk ---- */
@@ -324,7 +260,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 	const uint32_t prev_skip = st->hint_skip, prev_cap = st->hint_cap;
 	st->hint_skip = st->hint_cap = 0;
 	for (uint32_t i = 0; i < n && !stop; i++) {
-		const la_gz_result *r = &st->h_res[i];
+		const la_gz_result *r = &res[i];
 		const la_gz_member *m = &x->members[i];
 		const la_gz_header *h = &x->headers[i];
 		const uint64_t member_start = h->off;
@@ -333,7 +269,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 		 * the boundary (a 1f 8b 08 guess, or a wrong BGZF size) was not the member's
 		 * end.  Decode this member again with the span extended past it. */
 		if ((r->status == LA_ST_GZ_TRUNCATED &&
-		    (m->src_off + m->src_len < st->stage_len || !st->upstream_eof)) ||
+		    (m->src_off + m->src_len < st->stage_len || !st->w.upstream_eof)) ||
 		    /* ... or it ended with fewer than 8 bytes left in a span that a BGZF size field or a
 		     * boundary guess cut short while the window holds more bytes: same cure */
 		    (r->status == LA_ST_GZ_NO_TRAILER && m->src_off + m->src_len < st->stage_len)) {
@@ -350,7 +286,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 			if (base >= st->slot_limit) {
 				/* the slot cannot grow any further (32-bit positions on the device): say so
 				 * instead of retrying for ever or delivering a wrapped slot */
-				gz_set_fatal(st, la_end_message(LA_END_GZ_TOO_LARGE, 1));
+				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
 				cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
 				stop = 1;
 				break;
@@ -360,7 +296,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 			stop = 1;
 			break;
 		}
-		if (r->status == LA_ST_GZ_NO_TRAILER && !st->upstream_eof) {
+		if (r->status == LA_ST_GZ_NO_TRAILER && !st->w.upstream_eof) {
 			/* the trailer lies beyond this window */
 			*used = (size_t)member_start;
 			stop = 1;
@@ -371,7 +307,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 			st->mtime = h->mtime;
 			if (h->name_off) {
 				free(st->name);
-				st->name = strdup((const char *)st->stage + h->off + h->name_off);
+				st->name = strdup((const char *)st->stage.p + h->off + h->name_off);
 			}
 		}
 		switch (r->status) {
@@ -379,7 +315,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 		case LA_ST_GZ_BAD_CRC:
 		case LA_ST_GZ_BAD_ISIZE:
 			if (st->strict && r->status != LA_ST_OK) {
-				gz_set_fatal(st, la_status_message(r->status));
+				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_status_message(r->status));
 				cutoff = total;	/* new behaviour: everything before the bad member, then the error */
 				stop = 1;
 				break;
@@ -398,7 +334,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 			}
 			if (x->speculative && !h->bgzf_size && (uint64_t)r->consumed + 8 < m->src_len) {
 				const uint64_t p = m->src_off + (uint64_t)r->consumed + 8;
-				const uint8_t *q = st->stage + p;
+				const uint8_t *q = st->stage.p + p;
 				const uint64_t rem = st->stage_len - p;
 				if (!st->loose && rem >= 4 && q[0] == 0x1f && q[1] == 0x8b && q[2] == 0x08 && (q[3] & 0xE0) == 0) {
 					/* a header the strict boundary search passed over (unusual XFL / OS): the
@@ -414,7 +350,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 			}
 			break;
 		case LA_ST_GZ_DATA:
-			gz_set_fatal(st, "gzip decompression failed");
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
 			cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
 			    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
 			last_out = r->out_len;
@@ -422,14 +358,14 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 			stop = 1;
 			break;
 		case LA_ST_GZ_TRUNCATED:
-			gz_set_fatal(st, "truncated gzip input");
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
 			cutoff = ((total + r->out_len) / OUT_BLOCK) * OUT_BLOCK;
 			last_out = r->out_len;
 			take = i + 1;
 			stop = 1;
 			break;
 		case LA_ST_GZ_NO_TRAILER:
-			gz_set_fatal(st, NULL);	/* ARCHIVE_FATAL without a message (gzip.c:419-421) */
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, NULL);	/* ARCHIVE_FATAL without a message (gzip.c:419-421) */
 			cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
 			    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
 			last_out = r->out_len;
@@ -437,7 +373,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 			stop = 1;
 			break;
 		default:
-			gz_set_fatal(st, "gzip decompression failed");
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
 			cutoff = total;
 			stop = 1;
 			break;
@@ -448,10 +384,10 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 		if (x->end_kind == LA_END_EOF)
 			st->eof = 1;
 		else if (x->end_kind == LA_END_TRUNCATED) {
-			gz_set_fatal(st, "truncated gzip input");
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
 			cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
 		} else if (x->end_kind == LA_END_GZ_TOO_LARGE) {
-			gz_set_fatal(st, la_end_message(LA_END_GZ_TOO_LARGE, 1));
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
 			cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
 		}
 	}
@@ -464,28 +400,27 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 	if (ahead) {
 		/* they came over while the caller was busy (the sync above covered the copy): carry in front, change slabs */
 		if (st->carry_len)
-			memcpy(st->slab2, st->slab, st->carry_len);
-		uint8_t *tp = st->slab; st->slab = st->slab2; st->slab2 = tp;
-		size_t tc = st->slab_cap; st->slab_cap = st->slab2_cap; st->slab2_cap = tc;
-	} else if (gz_grow_pinned(st, &st->slab, &st->slab_cap, st->carry_len + (size_t)new_bytes + 16, st->carry_len) < 0)
-		return gz_gpu_fail(self, st, "pinned slab allocation");
-	uint8_t *dstp = st->slab + st->carry_len;
+			memcpy(st->slab2.p, st->slab.p, st->carry_len);
+		const la_buf tb = st->slab; st->slab = st->slab2; st->slab2 = tb;
+	} else if (la_buf_pinned(gpu, &st->slab, st->carry_len + (size_t)new_bytes + 16, st->carry_len) < 0)
+		return la_window_fail(self, &st->w, "pinned slab allocation");
+	uint8_t *dstp = st->slab.p + st->carry_len;
 	const double b2 = st->trace ? gz_now() : 0;
 	if (take && !ahead) {
 		if (contiguous && last_out == 0) {
-			if (la_gpu_memcpy_d2h(st->gpu, dstp, st->d_dst, (size_t)new_bytes) != LA_OK)
-				return gz_gpu_fail(self, st, "device to host copy");
+			if (la_gpu_memcpy_d2h(gpu, dstp, st->d_dst.p, (size_t)new_bytes) != LA_OK)
+				return la_window_fail(self, &st->w, "device to host copy");
 		} else {
 			size_t w = 0;
 			for (uint32_t i = 0; i < take; i++) {
-				size_t len = st->h_res[i].out_len;
-				if (len && la_gpu_memcpy_d2h(st->gpu, dstp + w, (uint8_t *)st->d_dst + x->members[i].dst_off, len) != LA_OK)
-					return gz_gpu_fail(self, st, "device to host copy");
+				size_t len = res[i].out_len;
+				if (len && la_gpu_memcpy_d2h(gpu, dstp + w, st->d_dst.p + x->members[i].dst_off, len) != LA_OK)
+					return la_window_fail(self, &st->w, "device to host copy");
 				w += len;
 			}
 		}
-		if (la_gpu_sync(st->gpu) != LA_OK)
-			return gz_gpu_fail(self, st, "device to host copy");
+		if (la_gpu_sync(gpu) != LA_OK)
+			return la_window_fail(self, &st->w, "device to host copy");
 	}
 	if (st->trace)
 		fprintf(stderr, "la_gzip:   h2d+decode %.1f ms, walk+grow %.1f ms, d2h %.1f ms (%llu bytes, contiguous %d, copied ahead %d)\n",
@@ -517,62 +452,41 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 static int gz_prepare(struct archive_read_filter *self, struct gzip_private *st)
 {
 	const double t0 = st->trace ? gz_now() : 0;
-	while (!st->upstream_eof && st->stage_len < st->batch_bytes) {
-		ssize_t avail;
-		const void *up = __archive_read_filter_ahead(self->upstream, 1, &avail);
-		if (up == NULL) {
-			if (avail < 0)
-				return ARCHIVE_FATAL;
-			st->upstream_eof = 1;
-			break;
-		}
-		size_t n = (size_t)avail;
-		if (n > st->batch_bytes - st->stage_len)
-			n = st->batch_bytes - st->stage_len;
-		/* a stream that has already filled 8 MiB gets the whole window at once instead of
-		 * five more rounds of pin-a-bigger-buffer-and-copy */
-		size_t want = st->stage_len + n;
-		if (want > ((size_t)8 << 20) && want < st->batch_bytes)
-			want = st->batch_bytes;
-		if (gz_grow_pinned(st, &st->stage, &st->stage_cap, want, st->stage_len) < 0)
-			return gz_gpu_fail(self, st, "pinned staging allocation");
-		memcpy(st->stage + st->stage_len, up, n);
-		st->stage_len += n;
-		__archive_read_filter_consume(self->upstream, (int64_t)n);
-	}
+	if (la_window_gather(self, &st->w, &st->stage, &st->stage_len) != ARCHIVE_OK)
+		return ARCHIVE_FATAL;
 	const double t1 = st->trace ? gz_now() : 0;
 	/* the window goes to the device while the host looks for the member boundaries in it
 	 * (stream-ordered copy from the pinned window; nothing writes to [0, stage_len)
 	 * before the batch has been waited for) */
 	if (st->stage_len &&
-	    (gz_grow_dev(st, &st->d_src, &st->d_src_cap, st->stage_len + 64) < 0 ||
-	     la_gpu_memcpy_h2d(st->gpu, st->d_src, st->stage, st->stage_len) != LA_OK))
-		return gz_gpu_fail(self, st, "host to device copy");
-	if (la_gz_index_build4(st->stage, st->stage_len, st->upstream_eof, st->hint_skip, st->hint_cap,
-	    st->loose ? 0 : LA_GZ_INDEX_STRICT, st->out_budget, &st->idx) != 0) {
+	    (la_buf_dev(st->w.gpu, &st->d_src, st->stage_len + 64) < 0 ||
+	     la_gpu_memcpy_h2d(st->w.gpu, st->d_src.p, st->stage.p, st->stage_len) != LA_OK))
+		return la_window_fail(self, &st->w, "host to device copy");
+	if (la_gz_index_build_ex(st->stage.p, st->stage_len, st->w.upstream_eof, st->hint_skip, st->hint_cap,
+	    st->loose ? 0 : LA_GZ_INDEX_STRICT, st->w.out_budget, st->span_limit, &st->idx) != 0) {
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
 		return ARCHIVE_FATAL;
 	}
 	if (st->idx.n == 0) {
 		int kind = st->idx.end_kind;
 		la_gz_index_free(&st->idx);
-		if (la_gpu_sync(st->gpu) != LA_OK)	/* the upload above: the window may move now */
-			return gz_gpu_fail(self, st, "host to device copy");
+		if (la_gpu_sync(st->w.gpu) != LA_OK)	/* the upload above: the window may move now */
+			return la_window_fail(self, &st->w, "host to device copy");
 		if (kind == LA_END_NEED_MORE) {
-			if (st->upstream_eof) { st->eof = 1; return 0; }
+			if (st->w.upstream_eof) { st->eof = 1; return 0; }
 			if (!st->loose) {
 				/* no trusted boundary in the whole window: before widening it, look
 				 * with every 1f 8b 08 as a candidate (and keep doing so) */
 				st->loose = 1;
 				return 0;
 			}
-			st->batch_bytes *= 2;	/* one member larger than the window */
+			st->w.batch_bytes *= 2;	/* one member larger than the window */
 			return 0;
 		}
 		if (kind == LA_END_TRUNCATED)
-			gz_set_fatal(st, "truncated gzip input");
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
 		else if (kind == LA_END_GZ_TOO_LARGE)
-			gz_set_fatal(st, la_end_message(LA_END_GZ_TOO_LARGE, 1));
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
 		else
 			st->eof = 1;
 		return 0;
@@ -589,18 +503,17 @@ static int gz_prepare(struct archive_read_filter *self, struct gzip_private *st)
 	st->ahead_ok = 0;
 	/* (not before the window ramp has reached its target: a second pinned slab costs about half a millisecond per MiB, and one
 	 * that has to grow three times costs a short stream more than the copies it hides) */
-	if (!st->no_ahead && st->batch_bytes >= st->target_bytes && !st->idx.speculative && st->hint_skip == 0 && st->hint_cap == 0 && st->idx.max_out != 0 &&
+	if (!st->no_ahead && st->w.batch_bytes >= st->w.target_bytes && !st->idx.speculative && st->hint_skip == 0 && st->hint_cap == 0 && st->idx.max_out != 0 &&
 	    st->idx.max_out <= ((uint64_t)1 << 30) && st->carry_len >= st->last_ret) {
 		const size_t rem = st->carry_len - st->last_ret;
-		if (gz_grow_pinned(st, &st->slab2, &st->slab2_cap, rem + (size_t)st->idx.max_out + 16, 0) == 0 &&
-		    la_gpu_memcpy_d2h(st->gpu, st->slab2 + rem, st->d_dst, (size_t)st->idx.max_out) == LA_OK) {
+		if (la_buf_pinned(st->w.gpu, &st->slab2, rem + (size_t)st->idx.max_out + 16, 0) == 0 &&
+		    la_gpu_memcpy_d2h(st->w.gpu, st->slab2.p + rem, st->d_dst.p, (size_t)st->idx.max_out) == LA_OK) {
 			st->ahead_ok = 1;
 			st->ahead_rem = rem;
 			st->ahead_len = (size_t)st->idx.max_out;
 		}
 	}
-	if (st->batch_bytes < st->target_bytes)
-		st->batch_bytes = st->batch_bytes * 2 < st->target_bytes ? st->batch_bytes * 2 : st->target_bytes;
+	la_window_ramp(&st->w);
 	if (st->trace)
 		fprintf(stderr, "la_gzip: window %zu bytes, %u members queued: gather %.1f ms, index + launch %.1f ms\n",
 		    st->stage_len, st->idx.n, t1 - t0, gz_now() - t1);
@@ -614,27 +527,22 @@ static ssize_t gzip_filter_read(struct archive_read_filter *self, const void **p
 
 	/* the bytes handed out last time are released now: close the gap */
 	if (st->last_ret) {
-		memmove(st->slab, st->slab + st->last_ret, st->carry_len - st->last_ret);
+		memmove(st->slab.p, st->slab.p + st->last_ret, st->carry_len - st->last_ret);
 		st->carry_len -= st->last_ret;
 		st->last_ret = 0;
 	}
 	for (;;) {
-		if (st->pending_fatal) {
-			if (st->pending_has_msg)
-				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "%s", st->pending_msg);
-			return ARCHIVE_FATAL;
-		}
+		if (st->verdict.rc)
+			return la_verdict_report(self, &st->verdict);
 		if (st->eof) {
 			if (st->carry_len) {	/* the held-back tail of a clean stream */
 				st->last_ret = st->carry_len;
-				*p = st->slab;
+				*p = st->slab.p;
 				return (ssize_t)st->carry_len;
 			}
 			return 0;
 		}
 		if (!st->inflight) {
-			if (st->upstream_failed)
-				return ARCHIVE_FATAL;	/* upstream set the error when the window was gathered ahead */
 			int pr = gz_prepare(self, st);
 			if (pr < 0)
 				return pr;
@@ -653,24 +561,24 @@ static ssize_t gzip_filter_read(struct archive_read_filter *self, const void **p
 		if (rc < 0)
 			return rc;
 		if (used < st->stage_len)
-			memmove(st->stage, st->stage + used, st->stage_len - used);
+			memmove(st->stage.p, st->stage.p + used, st->stage_len - used);
 		st->stage_len -= used;
-		if (!made_progress && !st->pending_fatal && !st->eof && st->hint_skip == 0 && st->hint_cap == 0) {
+		if (!made_progress && !st->verdict.rc && !st->eof && st->hint_skip == 0 && st->hint_cap == 0) {
 			/* nothing could be finished in this window: it has to grow */
-			if (st->upstream_eof) { st->eof = 1; continue; }
-			st->batch_bytes *= 2;
+			if (st->w.upstream_eof) { st->eof = 1; continue; }
+			st->w.batch_bytes *= 2;
 		}
 		if (st->last_ret) {
 			/* Decode ahead: gather, upload, index and launch the NEXT window before handing this
 			 * slab out, so that the device works while the caller consumes it (the slab is not
 			 * touched until the next read()).  An outcome other than "in flight" is simply met
 			 * again by the next read(). */
-			if (!st->pending_fatal && !st->eof) {
+			if (!st->verdict.rc && !st->eof) {
 				int pr = gz_prepare(self, st);
-				if (pr < 0)
-					st->upstream_failed = 1;	/* reported by the next read(), after these bytes */
+				if (pr < 0)	/* reported by the next read(), after these bytes (the error is set) */
+					la_verdict_set(&st->verdict, pr, NULL);
 			}
-			*p = st->slab;
+			*p = st->slab.p;
 			return (ssize_t)st->last_ret;
 		}
 	}
@@ -681,19 +589,18 @@ static int gzip_filter_close(struct archive_read_filter *self)
 	struct gzip_private *st = (struct gzip_private *)self->data;
 	if (st == NULL)
 		return ARCHIVE_OK;
-	if (st->gpu) {
-		la_gpu_sync(st->gpu);
-		if (st->inflight)
-			la_gz_index_free(&st->idx);
-		if (st->stage) la_gpu_free_host(st->gpu, st->stage);
-		if (st->slab) la_gpu_free_host(st->gpu, st->slab);
-		if (st->slab2) la_gpu_free_host(st->gpu, st->slab2);
-		if (st->d_src) la_gpu_free(st->gpu, st->d_src);
-		if (st->d_dst) la_gpu_free(st->gpu, st->d_dst);
-		if (st->d_tabs) la_gpu_free(st->gpu, st->d_tabs);
-		la_gpu_close(st->gpu);
-	}
-	free(st->h_res);
+	la_gpu_ctx *gpu = st->w.gpu;
+	la_gpu_sync(gpu);
+	if (st->inflight)
+		la_gz_index_free(&st->idx);
+	la_buf_release(gpu, &st->stage);
+	la_buf_release(gpu, &st->slab);
+	la_buf_release(gpu, &st->slab2);
+	la_buf_release(gpu, &st->d_src);
+	la_buf_release(gpu, &st->d_dst);
+	la_buf_release(gpu, &st->d_tabs);
+	la_buf_release(gpu, &st->h_res);
+	la_gpu_close(gpu);
 	free(st->name);
 	free(st);
 	self->data = NULL;

@@ -18,14 +18,10 @@
 #include <string.h>
 
 struct zstd_private {
-	la_gpu_ctx *gpu;
-	size_t batch_bytes;		/* compressed bytes gathered per window */
-	size_t target_bytes;		/* the window ramps up to this size (16, 32, 64 MiB ...: la_filter_lz4.c, init) */
-	uint64_t out_budget;		/* decoded bytes asked for per window */
-	size_t max_batch_bytes;		/* how far the stage may grow for ONE frame larger than a window */
-	/* stage: compressed bytes not decoded yet */
+	la_window w;			/* (max_batch_bytes: how far the stage may grow for ONE frame larger than a window) */
+	uint32_t options;		/* la_zstd_batch.options: LA_ZSTD_LANE_KERNEL=1 */
+	/* stage: compressed bytes not decoded yet (pageable: its tail is moved right after its copy is queued) */
 	uint8_t *stage; size_t stage_len, stage_cap;
-	int upstream_eof;
 	uint64_t skip_left;		/* bytes of a skippable frame still to pass over before anything is staged (zstd.c skips
 					 * such frames in constant memory: so does this filter) */
 	/* Two windows in flight (round 3, as the lz4 filter does): while the caller consumes the slab of window n, window
@@ -37,16 +33,14 @@ struct zstd_private {
 	struct zstd_slot {
 		la_zstd_frame *frames; uint32_t frames_cap;
 		la_zstd_result *results;
-		uint8_t *out; size_t out_cap;		/* pinned */
+		la_buf out;				/* pinned */
 		uint32_t n, next;			/* frames of the window / next to hand out */
 		int end_kind;				/* what follows the window's last frame */
 		int launched;				/* the window has been prepared (and queued when n > 0) */
-		int rc;					/* ARCHIVE_OK, or what preparing it ended with (reported at its turn) */
-		char err[200];
+		la_verdict verdict;			/* what preparing it ended with (reported at its turn) */
 	} slot[2];
 	int cur;				/* the slot being handed out */
-	void *d_src, *d_dst, *d_frames, *d_results;
-	size_t d_src_cap, d_dst_cap, d_tab_cap;
+	la_buf d_src, d_dst, d_tabs;		/* d_tabs: the frame table, then the results */
 	int finished;				/* error or end already reported */
 	int64_t total_out;
 };
@@ -102,18 +96,9 @@ static int zstd_reader_init(struct archive_read_filter *self)
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for zstd decompression");
 		return ARCHIVE_FATAL;
 	}
-	const char *dev = getenv("LA_GPU_DEVICE");
-	const char *bm = getenv("LA_GPU_BATCH_MIB");
-	st->target_bytes = (size_t)(bm && atoi(bm) > 0 ? atoi(bm) : 64) << 20;
-	st->batch_bytes = st->target_bytes < ((size_t)16 << 20) ? st->target_bytes : (size_t)16 << 20;
-	const char *ob = getenv("LA_GPU_OUT_BUDGET_MIB");
-	st->out_budget = (uint64_t)(ob && atoi(ob) > 0 ? atoi(ob) : 4096) << 20;
-	const char *bmx = getenv("LA_GPU_MAX_BATCH_MIB");
-	st->max_batch_bytes = (size_t)(bmx && atoi(bmx) > 0 ? atoi(bmx) : 2048) << 20;
-	int rc = la_gpu_open(dev ? atoi(dev) : 0, &st->gpu);
-	if (rc != LA_OK) {
-		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-		    "Can't initialize zstd GPU data plane (la_gpu_open: %d); no CPU fallback is built", rc);
+	const char *lk = getenv("LA_ZSTD_LANE_KERNEL");
+	st->options = (lk && atoi(lk) > 0) ? LA_ZSTD_OPT_LANE_KERNEL : 0u;
+	if (la_window_open(self, &st->w, "zstd") != ARCHIVE_OK) {
 		free(st);
 		return ARCHIVE_FATAL;
 	}
@@ -124,37 +109,20 @@ static int zstd_reader_init(struct archive_read_filter *self)
 
 static int gpu_fail(struct archive_read_filter *self, struct zstd_private *st, const char *what)
 {
-	archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-	    "zstd GPU data plane: %s failed: %s", what, la_gpu_last_error(st->gpu));
 	st->finished = 1;
-	return ARCHIVE_FATAL;
-}
-
-static int grow_dev(struct zstd_private *st, void **p, size_t *cap, size_t need)
-{
-	if (need <= *cap)
-		return LA_OK;
-	if (*p)
-		la_gpu_free(st->gpu, *p);
-	*p = NULL;
-	*cap = 0;
-	need = (need + (need >> 2) + 0xFFFFFu) & ~(size_t)0xFFFFFu;
-	int rc = la_gpu_malloc(st->gpu, p, need);
-	if (rc == LA_OK)
-		*cap = need;
-	return rc;
+	return la_window_fail(self, &st->w, what);
 }
 
 /* Pull upstream into the stage until it holds a window's worth (or upstream ends). */
 static int zstd_fill(struct archive_read_filter *self, struct zstd_private *st, size_t want)
 {
-	while (!st->upstream_eof && st->stage_len < want) {
+	while (!st->w.upstream_eof && st->stage_len < want) {
 		ssize_t avail;
 		const void *up = __archive_read_filter_ahead(self->upstream, 1, &avail);
 		if (up == NULL) {
 			if (avail < 0)
 				return (int)avail;
-			st->upstream_eof = 1;
+			st->w.upstream_eof = 1;
 			break;
 		}
 		if (st->skip_left) {
@@ -202,25 +170,14 @@ static int zstd_fill(struct archive_read_filter *self, struct zstd_private *st, 
 	return ARCHIVE_OK;
 }
 
-/* deferred failure of a window: kept with the slot, reported when the slot's turn comes */
-static int slot_fail(struct zstd_slot *sl, int rc, const char *fmt, unsigned long long v)
-{
-	sl->rc = rc;
-	snprintf(sl->err, sizeof(sl->err), fmt, v);
-	sl->n = 0;
-	sl->end_kind = LA_END_EOF;
-	return ARCHIVE_OK;
-}
-
 /* Gather, index and QUEUE one window into slot sl (H2D, decode, D2H, marker): nothing is waited for.  Returns
- * ARCHIVE_OK with sl->launched set (sl->n frames, possibly 0; a refusal is kept in sl->rc) or an upstream error. */
+ * ARCHIVE_OK with sl->launched set (sl->n frames, possibly 0; a refusal is kept in sl->verdict) or an upstream error. */
 static int zstd_launch(struct archive_read_filter *self, struct zstd_private *st, struct zstd_slot *sl)
 {
 	la_zstd_index_result ir;
-	size_t want = st->batch_bytes;
+	size_t want = st->w.batch_bytes;
 	sl->launched = 1;
-	sl->rc = ARCHIVE_OK;
-	sl->err[0] = 0;
+	la_verdict_set(&sl->verdict, ARCHIVE_OK, NULL);
 	sl->n = sl->next = 0;
 	sl->end_kind = LA_END_EOF;
 	for (;;) {
@@ -236,8 +193,8 @@ static int zstd_launch(struct archive_read_filter *self, struct zstd_private *st
 				return ARCHIVE_FATAL;
 			}
 		}
-		la_zstd_index_build(st->stage, st->stage_len, st->upstream_eof, st->out_budget, sl->frames, sl->frames_cap, &ir);
-		if (ir.n_frames == 0 && ir.end_kind == LA_END_NEED_MORE && !ir.window_full && !st->upstream_eof && ir.consumed > 0) {
+		la_zstd_index_build(st->stage, st->stage_len, st->w.upstream_eof, st->w.out_budget, sl->frames, sl->frames_cap, &ir);
+		if (ir.n_frames == 0 && ir.end_kind == LA_END_NEED_MORE && !ir.window_full && !st->w.upstream_eof && ir.consumed > 0) {
 			/* nothing but skippable frames in front of an incomplete frame: they are done with -- drop them and gather
 			 * on in the same window (the reference skips such frames in constant memory, zstd.c:196-260; growing the
 			 * window for them ended in "frame too large" once they passed LA_GPU_MAX_BATCH_MIB) */
@@ -245,68 +202,68 @@ static int zstd_launch(struct archive_read_filter *self, struct zstd_private *st
 			st->stage_len -= (size_t)ir.consumed;
 			continue;
 		}
-		if (ir.n_frames == 0 && ir.end_kind == LA_END_NEED_MORE && !ir.window_full && !st->upstream_eof) {
-			if (st->stage_len >= st->max_batch_bytes)
+		if (ir.n_frames == 0 && ir.end_kind == LA_END_NEED_MORE && !ir.window_full && !st->w.upstream_eof) {
+			if (st->stage_len >= st->w.max_batch_bytes) {
 				/* ONE frame whose compressed bytes alone pass LA_GPU_MAX_BATCH_MIB: the whole frame would have to sit in
 				 * host memory and HBM; refused by name (the reference streams it) */
-				return slot_fail(sl, ARCHIVE_FATAL,
+				la_verdict_set(&sl->verdict, ARCHIVE_FATAL,
 				    "zstd frame too large for the GPU data plane (more than %llu compressed bytes; LA_GPU_MAX_BATCH_MIB)",
-				    (unsigned long long)st->max_batch_bytes);
+				    (unsigned long long)st->w.max_batch_bytes);
+				return ARCHIVE_OK;
+			}
 			want = st->stage_len * 2 > want ? st->stage_len * 2 : want * 2;	/* one frame larger than the window: gather on */
-			if (want > st->max_batch_bytes)
-				want = st->max_batch_bytes;
+			if (want > st->w.max_batch_bytes)
+				want = st->w.max_batch_bytes;
 			continue;
 		}
 		break;
 	}
-	sl->n = ir.n_frames;
-	sl->end_kind = ir.end_kind;
-	if (st->batch_bytes < st->target_bytes)
-		st->batch_bytes = st->batch_bytes * 2 < st->target_bytes ? st->batch_bytes * 2 : st->target_bytes;
-	if (st->out_budget && ir.dst_bytes > st->out_budget && ir.dst_bytes > ((uint64_t)4 << 30))
+	la_window_ramp(&st->w);
+	if (st->w.out_budget && ir.dst_bytes > st->w.out_budget && ir.dst_bytes > ((uint64_t)4 << 30)) {
 		/* ONE frame whose blocks may decode to more than the window's budget (the walker stops adding frames at the
 		 * budget, so this is a single frame: e.g. terabytes of one byte as RLE blocks).  The reference streams such a
 		 * frame 128 KiB at a time; this data plane decodes whole frames into HBM and refuses it by name. */
-		return slot_fail(sl, ARCHIVE_FATAL,
+		la_verdict_set(&sl->verdict, ARCHIVE_FATAL,
 		    "zstd frame too large for the GPU data plane (its blocks may decode to %llu bytes; LA_GPU_OUT_BUDGET_MIB)",
 		    (unsigned long long)ir.dst_bytes);
+		return ARCHIVE_OK;
+	}
+	sl->n = ir.n_frames;
+	sl->end_kind = ir.end_kind;
 	if (sl->n) {
+		la_gpu_ctx *gpu = st->w.gpu;
 		const size_t tab = sizeof(la_zstd_frame) * sl->n, rtab = sizeof(la_zstd_result) * sl->n;
-		if (grow_dev(st, &st->d_src, &st->d_src_cap, (size_t)ir.consumed + 64) != LA_OK) return gpu_fail(self, st, "la_gpu_malloc");
-		if (grow_dev(st, &st->d_dst, &st->d_dst_cap, (size_t)ir.dst_bytes + 64) != LA_OK) return gpu_fail(self, st, "la_gpu_malloc");
-		if (tab + rtab > st->d_tab_cap) {
-			if (st->d_frames) la_gpu_free(st->gpu, st->d_frames);
-			st->d_frames = NULL;
-			st->d_tab_cap = 0;
-			if (la_gpu_malloc(st->gpu, &st->d_frames, 2 * (tab + rtab)) != LA_OK) return gpu_fail(self, st, "la_gpu_malloc");
-			st->d_tab_cap = 2 * (tab + rtab);
-		}
-		st->d_results = (uint8_t *)st->d_frames + ((tab + 15u) & ~(size_t)15u);
-		if ((size_t)ir.dst_bytes > sl->out_cap) {
-			if (sl->out) la_gpu_free_host(st->gpu, sl->out);
-			sl->out = NULL;
-			sl->out_cap = 0;
-			void *hp = NULL;
+		const size_t o_res = (tab + 15u) & ~(size_t)15u;	/* the results behind the frame table */
+		if (la_buf_dev(gpu, &st->d_src, (size_t)ir.consumed + 64) < 0 ||
+		    la_buf_dev(gpu, &st->d_dst, (size_t)ir.dst_bytes + 64) < 0 ||
+		    la_buf_dev(gpu, &st->d_tabs, o_res + rtab) < 0)
+			return gpu_fail(self, st, "la_gpu_malloc");
+		if (sl->out.cap < (size_t)ir.dst_bytes) {
+			/* The slab grows to a quarter above the window's slots, not to the next power of two: pinning costs about
+			 * half a millisecond per MiB, and power-of-two slabs (512 MiB for windows of 316 MiB of slots) made a 1 GiB
+			 * stream through la_cat 6-11 % slower (tools/measure_zstd.py's shape). */
 			const size_t nc = ((size_t)ir.dst_bytes + ((size_t)ir.dst_bytes >> 2) + 0xFFFFFu) & ~(size_t)0xFFFFFu;
-			if (la_gpu_malloc_host(st->gpu, &hp, nc) != LA_OK) return gpu_fail(self, st, "la_gpu_malloc_host");
-			sl->out = hp;
-			sl->out_cap = nc;
+			void *hp = NULL;
+			la_buf_release(gpu, &sl->out);
+			if (la_gpu_malloc_host(gpu, &hp, nc) != LA_OK) return gpu_fail(self, st, "la_gpu_malloc_host");
+			sl->out = (la_buf){ hp, nc, LA_BUF_PINNED };
 		}
-		if (la_gpu_memcpy_h2d(st->gpu, st->d_src, st->stage, ir.consumed) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
-		if (la_gpu_memcpy_h2d(st->gpu, st->d_frames, sl->frames, tab) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
+		la_zstd_result *d_results = (la_zstd_result *)(st->d_tabs.p + o_res);
+		if (la_gpu_memcpy_h2d(gpu, st->d_src.p, st->stage, ir.consumed) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
+		if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, sl->frames, tab) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
 		la_zstd_batch bt;
 		memset(&bt, 0, sizeof(bt));
-		bt.d_src = st->d_src; bt.src_bytes = ir.consumed;
-		bt.d_frames = st->d_frames; bt.n_frames = sl->n;
-		bt.d_dst = st->d_dst; bt.dst_cap = ir.dst_bytes;
-		bt.d_results = st->d_results;
-		{ const char *lk = getenv("LA_ZSTD_LANE_KERNEL"); bt.options = (lk && atoi(lk) > 0) ? LA_ZSTD_OPT_LANE_KERNEL : 0u; }
-		if (la_gpu_zstd_decode(st->gpu, &bt) != LA_OK) return gpu_fail(self, st, "la_gpu_zstd_decode");
-		if (la_gpu_memcpy_d2h(st->gpu, sl->results, st->d_results, rtab) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_d2h");
-		if (ir.dst_bytes && la_gpu_memcpy_d2h(st->gpu, sl->out, st->d_dst, ir.dst_bytes) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+		bt.d_src = st->d_src.p; bt.src_bytes = ir.consumed;
+		bt.d_frames = (la_zstd_frame *)st->d_tabs.p; bt.n_frames = sl->n;
+		bt.d_dst = st->d_dst.p; bt.dst_cap = ir.dst_bytes;
+		bt.d_results = d_results;
+		bt.options = st->options;
+		if (la_gpu_zstd_decode(gpu, &bt) != LA_OK) return gpu_fail(self, st, "la_gpu_zstd_decode");
+		if (la_gpu_memcpy_d2h(gpu, sl->results, d_results, rtab) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+		if (ir.dst_bytes && la_gpu_memcpy_d2h(gpu, sl->out.p, st->d_dst.p, ir.dst_bytes) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_d2h");
 		/* the stage (pageable memory) and the host frame table have been read by the copies above when they return:
 		 * the marker covers the rest */
-		if (la_gpu_mark(st->gpu) != LA_OK) return gpu_fail(self, st, "la_gpu_mark");
+		if (la_gpu_mark(gpu) != LA_OK) return gpu_fail(self, st, "la_gpu_mark");
 	}
 	/* keep what the window did not cover */
 	memmove(st->stage, st->stage + ir.consumed, st->stage_len - (size_t)ir.consumed);
@@ -317,11 +274,11 @@ static int zstd_launch(struct archive_read_filter *self, struct zstd_private *st
 /* does anything follow the window in slot sl?  (an end kind that ends the stream, or no input left) */
 static int slot_is_last(const struct zstd_private *st, const struct zstd_slot *sl)
 {
-	if (sl->rc != ARCHIVE_OK)
+	if (sl->verdict.rc != ARCHIVE_OK)
 		return 1;
 	if (sl->end_kind == LA_END_TRUNCATED || sl->end_kind == LA_END_ZSTD_BAD_MAGIC || sl->end_kind == LA_END_ZSTD_BAD_BLOCK)
 		return 1;
-	return sl->end_kind == LA_END_EOF && st->upstream_eof && st->stage_len == 0;
+	return sl->end_kind == LA_END_EOF && st->w.upstream_eof && st->stage_len == 0;
 }
 
 static ssize_t zstd_filter_read(struct archive_read_filter *self, const void **p)
@@ -337,7 +294,7 @@ static ssize_t zstd_filter_read(struct archive_read_filter *self, const void **p
 			int r = zstd_launch(self, st, sl);
 			if (r != ARCHIVE_OK)
 				return r;
-			if (sl->n && la_gpu_wait_mark(st->gpu) != LA_OK)
+			if (sl->n && la_gpu_wait_mark(st->w.gpu) != LA_OK)
 				return gpu_fail(self, st, "la_gpu_wait_mark");
 			if (!slot_is_last(st, sl)) {
 				r = zstd_launch(self, st, &st->slot[st->cur ^ 1]);
@@ -361,15 +318,14 @@ static ssize_t zstd_filter_read(struct archive_read_filter *self, const void **p
 			while (sl->next < sl->n && sl->results[sl->next].status == LA_ST_OK && sl->results[sl->next].out_len != 0 &&
 			    sl->frames[sl->next].dst_off == sl->frames[i].dst_off + len && len < ((uint64_t)1 << 30))
 				len += sl->results[sl->next++].out_len;
-			*p = sl->out + sl->frames[i].dst_off;
+			*p = sl->out.p + sl->frames[i].dst_off;
 			st->total_out += (int64_t)len;
 			return (ssize_t)len;
 		}
 		/* the window is handed out: what did preparing it end with, and what came behind its last frame? */
-		if (sl->rc != ARCHIVE_OK) {
-			archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "%s", sl->err);
+		if (sl->verdict.rc != ARCHIVE_OK) {
 			st->finished = 1;
-			return sl->rc;
+			return la_verdict_report(self, &sl->verdict);
 		}
 		{
 			const char *m = NULL;
@@ -389,7 +345,7 @@ static ssize_t zstd_filter_read(struct archive_read_filter *self, const void **p
 		if (!nx->launched) {
 			/* nothing was put in flight behind this window: it was the last one (zstd.c:208-211: end of input on a
 			 * frame boundary), or the walker wants more input than one window gave it */
-			if (sl->end_kind == LA_END_EOF && st->upstream_eof && st->stage_len == 0) {
+			if (sl->end_kind == LA_END_EOF && st->w.upstream_eof && st->stage_len == 0) {
 				st->finished = 1;
 				return 0;
 			}
@@ -398,7 +354,7 @@ static ssize_t zstd_filter_read(struct archive_read_filter *self, const void **p
 				return r;
 		}
 		/* the next window's turn: wait for its slab, then put the one after it in flight into the slot just emptied */
-		if (nx->n && la_gpu_wait_mark(st->gpu) != LA_OK)
+		if (nx->n && la_gpu_wait_mark(st->w.gpu) != LA_OK)
 			return gpu_fail(self, st, "la_gpu_wait_mark");
 		st->cur ^= 1;
 		sl->launched = 0;
@@ -415,15 +371,14 @@ static int zstd_filter_close(struct archive_read_filter *self)
 	struct zstd_private *st = (struct zstd_private *)self->data;
 	if (st == NULL)
 		return ARCHIVE_OK;
-	if (st->gpu) {
-		if (st->d_src) la_gpu_free(st->gpu, st->d_src);
-		if (st->d_dst) la_gpu_free(st->gpu, st->d_dst);
-		if (st->d_frames) la_gpu_free(st->gpu, st->d_frames);
-		(void)la_gpu_sync(st->gpu);	/* a window may still be in flight */
-		for (int i = 0; i < 2; i++)
-			if (st->slot[i].out) la_gpu_free_host(st->gpu, st->slot[i].out);
-		la_gpu_close(st->gpu);
-	}
+	la_gpu_ctx *gpu = st->w.gpu;
+	(void)la_gpu_sync(gpu);	/* a window may still be in flight */
+	la_buf_release(gpu, &st->d_src);
+	la_buf_release(gpu, &st->d_dst);
+	la_buf_release(gpu, &st->d_tabs);
+	for (int i = 0; i < 2; i++)
+		la_buf_release(gpu, &st->slot[i].out);
+	la_gpu_close(gpu);
 	free(st->stage);
 	for (int i = 0; i < 2; i++) {
 		free(st->slot[i].frames);

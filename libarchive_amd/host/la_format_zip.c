@@ -285,8 +285,7 @@ static int zip_read_header(struct archive_read *a, struct archive_entry *entry)
 static int zip_run_batch(struct archive_read *a, struct zip_private *z, uint32_t first)
 {
 	if (!z->gpu) {
-		const char *dev = getenv("LA_GPU_DEVICE");
-		if (la_gpu_open(dev ? atoi(dev) : 0, &z->gpu) != LA_OK)
+		if (la_gpu_open(la_env_device(), &z->gpu) != LA_OK)
 			return zip_fail(a, ARCHIVE_FATAL, "ZIP reader: no usable MI355X device (this build has no CPU inflate)");
 		if (la_gpu_malloc(z->gpu, &z->d_img, z->img_len + 64) != LA_OK ||
 		    la_gpu_memcpy_h2d(z->gpu, z->d_img, z->img, z->img_len) != LA_OK)

@@ -109,17 +109,6 @@ static int push(la_gz_index *x)
 #if defined(__x86_64__)
 #include <immintrin.h>
 
-/* Largest compressed span of ONE member the tables can express (32-bit fields).  LA_GZ_TEST_SPAN_LIMIT lowers it
- * so that the refusal path (LA_END_GZ_TOO_LARGE, "gzip member too large ...") can be reached by a test without a
- * 4 GiB input; it cannot raise it. */
-uint64_t la_gz_span_limit(void)
-{
-	const char *v = getenv("LA_GZ_TEST_SPAN_LIMIT");
-	uint64_t lim = 0xFFFFFFFFull;
-	if (v != NULL && strtoull(v, NULL, 10) > 0 && strtoull(v, NULL, 10) < lim)
-		lim = strtoull(v, NULL, 10);
-	return lim;
-}
 __attribute__((target("avx2")))
 static uint64_t find_magic_avx2(const uint8_t *p, uint64_t len, uint64_t i)
 {
@@ -184,24 +173,12 @@ static uint64_t next_candidate(const uint8_t *img, uint64_t len, uint64_t from, 
 
 #define LA_GZ_MAX_SLOT 0x80000000u
 
-int la_gz_index_build2(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
-    uint32_t first_cap, la_gz_index *x)
-{
-	return la_gz_index_build3(img, len, at_eof, first_skip, first_cap, 0, x);
-}
-
-int la_gz_index_build3(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
-    uint32_t first_cap, uint32_t flags, la_gz_index *x)
-{
-	return la_gz_index_build4(img, len, at_eof, first_skip, first_cap, flags, 0, x);
-}
-
 /* out_budget != 0 bounds the window by DECODED bytes too (sum of the members' output slots): a window of
  * highly compressible members would otherwise claim up to 1032 x its size in slab.  The walker stops in front
  * of the member that would pass the budget (at least one member is always taken) and reports
  * LA_END_NEED_MORE: the rest of the window is the next window's. */
-int la_gz_index_build4(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
-    uint32_t first_cap, uint32_t flags, uint64_t out_budget, la_gz_index *x)
+int la_gz_index_build_ex(const uint8_t *img, uint64_t len, int at_eof, uint32_t first_skip,
+    uint32_t first_cap, uint32_t flags, uint64_t out_budget, uint64_t span_limit, la_gz_index *x)
 {
 	const int strict = (flags & LA_GZ_INDEX_STRICT) != 0;
 	uint64_t pos = 0, out = 0;
@@ -261,7 +238,7 @@ int la_gz_index_build4(const uint8_t *img, uint64_t len, int at_eof, uint32_t fi
 			}
 		}
 		uint64_t span = next - body;
-		if (span > la_gz_span_limit()) {
+		if (span > span_limit) {
 			x->end_kind = LA_END_GZ_TOO_LARGE;	/* > 4 GiB member: beyond the table's u32 fields */
 			break;
 		}
@@ -293,5 +270,5 @@ int la_gz_index_build4(const uint8_t *img, uint64_t len, int at_eof, uint32_t fi
 
 int la_gz_index_build(const uint8_t *img, uint64_t len, int at_eof, la_gz_index *x)
 {
-	return la_gz_index_build2(img, len, at_eof, 0, 0, x);
+	return la_gz_index_build_ex(img, len, at_eof, 0, 0, 0, 0, LA_GZ_SPAN_LIMIT, x);
 }

@@ -241,10 +241,8 @@ static int dev_ready(void)
 	if (dev_state == 0) {
 		const uint32_t nj = LA_HASH_GPU_STAGE / LA_HASH_GPU_RANGE;
 		/* the same device as the filters and the ZIP reader (its caller for stored entries) use */
-		const char *dv = getenv("LA_GPU_DEVICE");
-		const int device = dv != NULL ? atoi(dv) : 0;
 		dev_state = -1;
-		if (la_gpu_open(device, &dev_ctx) == LA_OK &&
+		if (la_gpu_open(la_env_device(), &dev_ctx) == LA_OK &&
 		    la_gpu_malloc(dev_ctx, &dev_buf, LA_HASH_GPU_STAGE) == LA_OK &&
 		    la_gpu_malloc(dev_ctx, &dev_jobs, nj * sizeof(la_hash_job)) == LA_OK &&
 		    la_gpu_malloc(dev_ctx, &dev_out, nj * sizeof(uint32_t)) == LA_OK &&

@@ -80,12 +80,7 @@ void la_lz4_index_free(la_lz4_index *x)
 
 int la_lz4_index_build(const uint8_t *img, uint64_t len, int at_eof, la_lz4_index *x)
 {
-	return la_lz4_index_build2(img, len, at_eof, NULL, x);
-}
-
-int la_lz4_index_build2(const uint8_t *img, uint64_t len, int at_eof, la_lz4_resume *rs, la_lz4_index *x)
-{
-	return la_lz4_index_build3(img, len, at_eof, rs, 0, x);
+	return la_lz4_index_build_ex(img, len, at_eof, NULL, 0, x);
 }
 
 /* out_budget != 0 bounds the window by DECODED bytes too (sum of the blocks' dst_cap): highly
@@ -93,7 +88,7 @@ int la_lz4_index_build2(const uint8_t *img, uint64_t len, int at_eof, la_lz4_res
  * slab (the reference streams with one block buffer, lz4.c:240-263).  The walker stops in front of
  * the block that would pass the budget -- inside a frame only with a resume record -- and reports
  * LA_END_NEED_MORE; at least one block is always taken. */
-int la_lz4_index_build3(const uint8_t *img, uint64_t len, int at_eof, la_lz4_resume *rs, uint64_t out_budget,
+int la_lz4_index_build_ex(const uint8_t *img, uint64_t len, int at_eof, la_lz4_resume *rs, uint64_t out_budget,
     la_lz4_index *x)
 {
 	uint64_t pos = 0;

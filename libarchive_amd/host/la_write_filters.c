@@ -390,8 +390,8 @@ static int lz4w_write(struct archive_write_filter *f, const void *buff, size_t l
 static int lz4w_open(struct archive_write_filter *f)
 {
 	struct lz4w_private *d = f->data;
-	const char *dev = getenv("LA_GPU_DEVICE"), *wm = getenv("LA_GPU_WRITE_WINDOW_MIB");
-	if (la_gpu_open(dev ? atoi(dev) : 0, &d->gpu) != LA_OK) {
+	const char *wm = getenv("LA_GPU_WRITE_WINDOW_MIB");
+	if (la_gpu_open(la_env_device(), &d->gpu) != LA_OK) {
 		archive_set_error(f->archive, ARCHIVE_ERRNO_MISC,
 		    "Can't initialize %s GPU data plane (no usable gfx950 device); no CPU fallback is built", d->kind ? "gzip" : "lz4");
 		return ARCHIVE_FATAL;
