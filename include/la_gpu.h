@@ -347,6 +347,36 @@ uint64_t la_gpu_gzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t chunk
 uint64_t la_gpu_gzip_compress_bound(uint64_t src_bytes, uint32_t chunk_bytes);
 int      la_gpu_gzip_compress(la_gpu_ctx *ctx, const la_gzc_batch *batch);
 
+/* =====================================================================
+ * zstd compression -- the data plane of the zstd WRITE filter (host/la_write_zstd.c): replaces, for a whole stream
+ * per call, what libarchive/archive_write_add_filter_zstd.c gets from libzstd's ZSTD_compressStream2.  d_src[0,
+ * src_bytes) is cut into blocks of block_size bytes (at most 128 KiB, Block_Maximum_Size), blocks_per_frame of them
+ * form one frame (Single_Segment_Flag set, Frame_Content_Size present).  Blocks are independent (no match reaches an
+ * earlier block, no repeat offsets, every block states its own tables).  Empty input is one frame with one empty raw
+ * block.  d_out receives the concatenated frames, *d_out_bytes their total size (if it exceeds out_cap nothing past
+ * out_cap was written: call again with a larger buffer; la_gpu_zstd_compress_bound() always fits).  The bytes are not
+ * libzstd's (a zstd stream is not unique); every conforming decoder returns the input.
+ * ===================================================================== */
+#define LA_ZSTDC_CHECKSUM     1u	/* Content_Checksum_Flag + XXH64 (low 32 bits) of every frame's input */
+#define LA_ZSTDC_RAW_LITERALS 2u	/* no Huffman literals (the filter's negative / zero levels) */
+
+typedef struct la_zstdc_batch {
+	const uint8_t *d_src;
+	uint64_t       src_bytes;
+	uint32_t       block_size;		/* 1 .. 131072 */
+	uint32_t       blocks_per_frame;	/* >= 1; block_size * blocks_per_frame < 2^31 */
+	uint32_t       flags;			/* LA_ZSTDC_* */
+	uint32_t       reserved;
+	uint8_t       *d_out;
+	uint64_t       out_cap;
+	uint64_t      *d_out_bytes;		/* one u64 on the device */
+} la_zstdc_batch;
+
+uint64_t la_gpu_zstd_compress_workspace_bytes(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame);
+/* upper bound of the stream la_gpu_zstd_compress writes for this shape: the input, 3 bytes per block, 13 per frame */
+uint64_t la_gpu_zstd_compress_bound(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame);
+int      la_gpu_zstd_compress(la_gpu_ctx *ctx, const la_zstdc_batch *batch);
+
 #ifdef __cplusplus
 }
 #endif

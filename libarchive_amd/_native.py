@@ -68,6 +68,17 @@ class _Lz4cBatchC(C.Structure):
 LA_LZ4C_BLOCK_SUM, LA_LZ4C_CONTENT_SUM = 1, 2
 
 
+class _ZstdcBatchC(C.Structure):
+    _fields_ = [
+        ("d_src", C.c_void_p), ("src_bytes", C.c_uint64),
+        ("block_size", C.c_uint32), ("blocks_per_frame", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+        ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p),
+    ]
+
+
+LA_ZSTDC_CHECKSUM, LA_ZSTDC_RAW_LITERALS = 1, 2
+
+
 class _GzcBatchC(C.Structure):
     _fields_ = [
         ("d_src", C.c_void_p), ("src_bytes", C.c_uint64),
@@ -146,6 +157,11 @@ def gpu_lib():
         lib.la_gpu_lz4_compress_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_lz4_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         lib.la_gpu_gzip_decode.argtypes = [C.c_void_p, C.POINTER(_GzBatchC)]
+        lib.la_gpu_zstd_compress.argtypes = [C.c_void_p, C.POINTER(_ZstdcBatchC)]
+        lib.la_gpu_zstd_compress_bound.restype = C.c_uint64
+        lib.la_gpu_zstd_compress_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+        lib.la_gpu_zstd_compress_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_zstd_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         _gpu = lib
     return _gpu
 
@@ -307,6 +323,9 @@ class GpuContext:
 
     def lz4_compress(self, batch: _Lz4cBatchC):
         self._check(gpu_lib().la_gpu_lz4_compress(self._h, C.byref(batch)), "la_gpu_lz4_compress")
+
+    def zstd_compress(self, batch: _ZstdcBatchC):
+        self._check(gpu_lib().la_gpu_zstd_compress(self._h, C.byref(batch)), "la_gpu_zstd_compress")
 
     def gzip_compress(self, batch: _GzcBatchC):
         self._check(gpu_lib().la_gpu_gzip_compress(self._h, C.byref(batch)), "la_gpu_gzip_compress")

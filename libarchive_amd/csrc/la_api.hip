@@ -637,4 +637,28 @@ int la_gpu_gzip_compress(la_gpu_ctx *c, const la_gzc_batch *bt)
 	return LA_OK;
 }
 
+/* ------------------------------------------------------------------ zstd compression */
+
+int la_gpu_zstd_compress(la_gpu_ctx *c, const la_zstdc_batch *bt)
+{
+	if (!c || !bt || !bt->d_out_bytes || (bt->src_bytes && (!bt->d_src || !bt->d_out)))
+		return LA_ERR_ARG;
+	if (bt->block_size == 0 || bt->block_size > 131072u || bt->blocks_per_frame == 0 ||
+	    (uint64_t)bt->block_size * bt->blocks_per_frame > 0x7FFFFFFFull ||
+	    (bt->src_bytes + bt->block_size - 1) / bt->block_size > 0x7FFFFFFEull)
+		return LA_ERR_ARG;
+	const uint64_t need = la_gpu_zstd_compress_workspace_bytes(bt->src_bytes, bt->block_size, bt->blocks_per_frame);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	int h = prof_open(c, "zstd_compress", c->stream);
+	la_launch_zstd_compress(c->stream, bt->d_src, bt->src_bytes, bt->block_size, bt->blocks_per_frame, bt->flags,
+	    bt->d_out, bt->out_cap, bt->d_out_bytes, (uint8_t *)c->ws);
+	prof_close(c, h, c->stream);
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 } /* extern "C" */

@@ -502,6 +502,8 @@ void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_by
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
 
 /* la_deflate_comp.hip */
+void la_launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
+    uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
 void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t chunk, uint32_t mtime,
     uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
 

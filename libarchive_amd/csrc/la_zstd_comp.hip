@@ -1,0 +1,740 @@
+/*
+ * la_zstd_comp.hip -- Zstandard COMPRESSION + frame assembly on the device (gfx950): the data plane of the zstd write
+ * filter (host/la_write_zstd.c).
+ *
+ * Replaces, for a whole stream per call, what libarchive/archive_write_add_filter_zstd.c gets from libzstd's
+ * ZSTD_compressStream2 with ZSTD_c_checksumFlag set.  The bytes are not libzstd's (a zstd stream is not unique);
+ * parity for this direction is the round trip -- libzstd, the oracle and this repository's device decoder must
+ * return the input -- plus the format rules RFC 8878 sets on every frame and block.  Written from the RFC alone.
+ *
+ * Shape.  The input is cut into blocks of at most 128 KiB (Block_Maximum_Size); blocks_per_frame of them form one
+ * frame with Single_Segment_Flag set and the Frame_Content_Size present, so the read walker reserves exact output
+ * slots.  Blocks are compressed INDEPENDENTLY: no match reaches into an earlier block, the repeat-offset codes are
+ * never used (every sequence writes Offset_Value = offset + 3), every block states its own tables.  So all blocks of
+ * all frames run in parallel:
+ *   zstd_compress_blocks_kernel   ONE WAVE per block.  A block whose bytes are all equal is an RLE_Block.  Otherwise
+ *       the LZ77 matcher of lz4_compress_blocks_kernel: 64 positions per step, a 4096-entry table of 32-bit positions
+ *       in LDS (16 KiB), 4-byte minimum match at any offset inside the block, matches verified and extended, taken
+ *       in position order with ballot; literals and sequences (ll, ml, offset) go to the workspace.
+ *       Literals section: RLE when all literals are one byte; Raw under LA_ZSTDC_RAW_LITERALS, for fewer than 32
+ *       literals or a largest byte above 128; otherwise Huffman: an LDS histogram, Shannon lengths clamped to 11 bits
+ *       and made complete (Kraft sum exactly 1) by greedy lengthening / shortening with wave-wide arg-max rounds,
+ *       direct 4-bit weights, one stream up to 1023 literals and four with the jump table above.  Streams are encoded
+ *       in parallel: every literal's bit position is a wave prefix sum of code lengths (reverse symbol order, a
+ *       Huffman stream is read backwards), lanes OR their bits into an LDS stage and whole dwords leave
+ *       (deflate_fixed_kernel's scheme).  Sections whose coded form would not be smaller are written raw.
+ *       Sequences section: Predefined_Mode for LL, OF and ML; the interleaved FSE stream is written last sequence
+ *       first, uniformly by the wave (64 sequences' codes and extra bits computed lane-parallel, then taken one by
+ *       one with v_readlane), with encoder tables (symbol x next state -> state) spread from the decoder's own
+ *       fse_build in LDS.  A block whose compressed form is not smaller than its input is a Raw_Block.
+ *   zstdc_frame_sums_kernel       XXH64 of every frame's input, four lanes per frame.
+ *   zstdc_sizes_kernel / scan     stream bytes of every block (header + payload, frame header and checksum).
+ *   zstd_pack_frames_kernel       one workgroup per block: frame header, block header, payload, checksum.
+ * LDS per wave: 16 KiB table (the FSE tables reuse it after matching) + 1.8 KiB histogram / code / stage:
+ * 8 waves per CU by LDS.
+ */
+#include "la_dev.h"
+#include "la_zstd_common.h"
+
+#define ZC_HASH_BITS 12
+#define ZC_MINMATCH  4u
+#define ZC_BLOCK_MAX 131072u
+#define ZC_RAW_LIT_MIN 32u	/* fewer literals than this are never worth a Huffman table */
+
+__host__ __device__ static inline uint64_t zc_tmp_stride(uint32_t bs) { return ((uint64_t)bs + 64u + 15u) & ~15ull; }
+__host__ __device__ static inline uint64_t zc_lit_stride(uint32_t bs) { return ((uint64_t)bs + 15u) & ~15ull; }
+__host__ __device__ static inline uint64_t zc_seq_stride(uint32_t bs) { return ((uint64_t)bs / ZC_MINMATCH + 1u) * 8u; }
+
+struct zc_fse_lds {
+	fse_tab ll, ml, of;		/* decoder tables of the predefined distributions (fse_build: the decoder's spread) */
+	uint8_t ell[36 * 64];		/* encoder: [symbol][next state] -> state whose range holds it */
+	uint8_t eml[53 * 64];
+	uint8_t eof[29 * 32];
+};
+struct zc_lds {
+	union {
+		uint32_t tab[1u << ZC_HASH_BITS];
+		zc_fse_lds f;
+	} u;
+	uint32_t hist[256];
+	uint16_t code[256];
+	uint8_t len[256];
+	uint32_t wcnt[16];
+	uint32_t stage[32];
+};
+static_assert(sizeof(zc_fse_lds) <= sizeof(uint32_t) * (1u << ZC_HASH_BITS), "FSE tables must fit in the match table");
+
+__device__ __forceinline__ uint64_t zc_ld64(const uint8_t *p)
+{
+	uint64_t v;
+	__builtin_memcpy(&v, p, 8);
+	return v;
+}
+
+__device__ __forceinline__ void zc_copy(uint8_t *d, const uint8_t *s, uint32_t n, uint32_t lane)
+{
+	for (uint32_t i = lane; i < n; i += 64)
+		d[i] = s[i];
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1)
+		v += (uint32_t)__shfl_xor((int)v, d, 64);
+	return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t o = (uint32_t)__shfl_xor((int)v, d, 64);
+		v = o > v ? o : v;
+	}
+	return v;
+}
+
+/* literal-length / match-length codes (RFC 8878 3.1.1.3.2.1.1) */
+__device__ __forceinline__ uint32_t ll_code(uint32_t ll)
+{
+	if (ll < 16u) return ll;
+	if (ll >= 64u) return (uint32_t)highbit(ll) + 19u;
+	uint32_t c = 16;
+	while (c < 24u && SEQ_TABS.ll_base[c + 1] <= ll) c++;
+	return c;
+}
+__device__ __forceinline__ uint32_t ml_code(uint32_t ml)
+{
+	if (ml < 35u) return ml - 3u;
+	if (ml >= 131u) return (uint32_t)highbit(ml - 3u) + 36u;
+	uint32_t c = 32;
+	while (c < 42u && SEQ_TABS.ml_base[c + 1] <= ml) c++;
+	return c;
+}
+
+/* literals section header for Raw (type 0) / RLE (type 1): 1, 2 or 3 bytes */
+__device__ __forceinline__ uint32_t lit_hdr_rr(uint8_t *o, uint32_t type, uint32_t regen, bool write)
+{
+	if (regen < 32u) {
+		if (write) o[0] = (uint8_t)(type | (regen << 3));
+		return 1;
+	}
+	if (regen < 4096u) {
+		const uint32_t v = type | (1u << 2) | (regen << 4);
+		if (write) { o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); }
+		return 2;
+	}
+	const uint32_t v = type | (3u << 2) | (regen << 4);
+	if (write) { o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16); }
+	return 3;
+}
+
+/* one Huffman stream of literals [a, b): written last literal first, then the end-mark bit; returns its bytes */
+__device__ static uint32_t huf_stream_enc(zc_lds &L, const uint8_t *lits, uint32_t a, uint32_t b, uint8_t *out, uint32_t lane)
+{
+	uint64_t bp = 0;
+	for (uint32_t i = lane; i < 32; i += 64)
+		L.stage[i] = 0;
+	__builtin_amdgcn_wave_barrier();
+	uint32_t e = b;
+	while (e > a) {
+		const uint32_t cnt = e - a < 64u ? e - a : 64u;
+		uint32_t nb = 0, bits = 0;
+		if (lane < cnt) {
+			const uint32_t s = lits[e - 1u - lane];
+			nb = L.len[s];
+			bits = L.code[s];
+		}
+		uint32_t inc = nb;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint32_t t = __shfl_up(inc, d, 64);
+			if ((int)lane >= d) inc += t;
+		}
+		const uint32_t total = __shfl(inc, 63, 64);
+		const uint32_t at = (uint32_t)(bp & 31u) + inc - nb;
+		if (nb) {
+			const uint64_t w = (uint64_t)bits << (at & 31u);
+			atomicOr(&L.stage[at >> 5], (uint32_t)w);
+			if ((uint32_t)(w >> 32))
+				atomicOr(&L.stage[(at >> 5) + 1], (uint32_t)(w >> 32));
+		}
+		__builtin_amdgcn_wave_barrier();
+		/* whole dwords leave (64 x 11 + 31 bits: at most 22 of them); the partial one stays in front */
+		const uint32_t nd = ((uint32_t)(bp & 31u) + total) >> 5;
+		const uint64_t g0 = (bp >> 5) * 4u;
+		uint32_t mine = 0;
+		const uint32_t carry = L.stage[nd];
+		if (lane < nd)
+			mine = L.stage[lane];
+		__builtin_amdgcn_wave_barrier();
+		if (lane < nd) {
+			uint8_t *d = out + g0 + 4u * lane;
+			d[0] = (uint8_t)mine; d[1] = (uint8_t)(mine >> 8); d[2] = (uint8_t)(mine >> 16); d[3] = (uint8_t)(mine >> 24);
+		}
+		if (lane <= nd)
+			L.stage[lane] = 0;
+		__builtin_amdgcn_wave_barrier();
+		if (lane == 0)
+			L.stage[0] = carry;
+		__builtin_amdgcn_wave_barrier();
+		bp += total;
+		e -= cnt;
+	}
+	/* end mark, then the last bytes */
+	const uint32_t last = L.stage[0] | (1u << (bp & 31u));
+	bp += 1;
+	const uint32_t bytes = (uint32_t)((bp + 7u) >> 3);
+	const uint32_t g0 = (uint32_t)(bp - 1u) >> 5;
+	if (lane < bytes - 4u * g0)
+		out[4u * g0 + lane] = (uint8_t)(last >> (8u * lane));
+	__builtin_amdgcn_wave_barrier();
+	return bytes;
+}
+
+/* serial LSB-first bit writer (wave-uniform state; lane 0 stores) */
+struct zc_bw {
+	uint8_t *out;
+	uint32_t op, cap;
+	uint64_t acc;
+	uint32_t n;
+	bool over;
+};
+__device__ __forceinline__ void bw_put(zc_bw &w, uint32_t v, uint32_t nb, uint32_t lane)
+{
+	w.acc |= (uint64_t)v << w.n;
+	w.n += nb;
+	if (w.n >= 32u) {
+		if (w.op + 4u > w.cap) {
+			w.over = true;
+		} else if (lane == 0) {
+			const uint32_t x = (uint32_t)w.acc;
+			w.out[w.op] = (uint8_t)x; w.out[w.op + 1] = (uint8_t)(x >> 8); w.out[w.op + 2] = (uint8_t)(x >> 16); w.out[w.op + 3] = (uint8_t)(x >> 24);
+		}
+		w.op += 4u;
+		w.acc >>= 32;
+		w.n -= 32u;
+	}
+}
+
+__global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
+    uint32_t block_size, uint32_t n_blocks, uint32_t flags, uint8_t *__restrict__ tmp, uint8_t *__restrict__ lits_ws,
+    uint64_t *__restrict__ seqs_ws, uint32_t *__restrict__ btype, uint32_t *__restrict__ csize)
+{
+	__shared__ zc_lds L;
+	const uint32_t bi = blockIdx.x, lane = threadIdx.x;
+	if (bi >= n_blocks)
+		return;
+	const uint64_t so = (uint64_t)bi * block_size;
+	const uint32_t n = src_bytes > so ? (uint32_t)(src_bytes - so < block_size ? src_bytes - so : block_size) : 0u;
+	const uint8_t *in = src + so;
+	uint8_t *out = tmp + (uint64_t)bi * zc_tmp_stride(block_size);
+	uint8_t *lits = lits_ws + (uint64_t)bi * zc_lit_stride(block_size);
+	uint64_t *seqs = (uint64_t *)(void *)((uint8_t *)seqs_ws + (uint64_t)bi * zc_seq_stride(block_size));
+	const uint32_t cap = (uint32_t)zc_tmp_stride(block_size);
+
+	/* ---- RLE_Block: every byte equal ---- */
+	if (n == 0) {
+		if (lane == 0) { btype[bi] = 0; csize[bi] = 0; }
+		return;
+	}
+	{
+		const uint8_t b0 = in[0];
+		bool same = true;
+		for (uint32_t base = 0; base < n && same; base += 64 * 16) {
+			bool diff = false;
+			for (uint32_t k = 0; k < 16; k++) {
+				const uint32_t i = base + k * 64 + lane;
+				diff |= i < n && in[i] != b0;
+			}
+			same = __ballot(diff) == 0;
+		}
+		if (same && n > 1) {
+			if (lane == 0) { btype[bi] = 1; csize[bi] = 1; }
+			return;
+		}
+	}
+
+	for (uint32_t i = lane; i < (1u << ZC_HASH_BITS); i += 64)
+		L.u.tab[i] = 0;
+	for (uint32_t i = lane; i < 256; i += 64)
+		L.hist[i] = 0;
+	__syncthreads();
+
+	/* ---- matching: sequences and literals ---- */
+	uint32_t anchor = 0, nseq = 0, nlit = 0;	/* wave-uniform */
+	if (n >= ZC_MINMATCH) {
+		const uint32_t plast = n - ZC_MINMATCH;	/* last position a match may start at */
+		uint32_t base = 0;
+		while (base <= plast) {
+			const uint32_t p = base + lane;
+			const bool valid = p <= plast;
+			uint32_t v = 0, cand = 0, mlen = 0;
+			bool ok = false;
+			const uint32_t h = valid ? ((ld_u32(in + p) * 2654435761u) >> (32 - ZC_HASH_BITS)) : 0u;
+			if (valid) {
+				v = ld_u32(in + p);
+				cand = L.u.tab[h];	/* every lane reads before any lane of this window writes */
+			}
+			__builtin_amdgcn_wave_barrier();
+			if (valid) {
+				L.u.tab[h] = p;
+				/* (position 0 doubles as "empty": a candidate is only taken if its bytes match) */
+				ok = cand < p && ld_u32(in + cand) == v;
+				if (ok) {
+					mlen = 4;
+					while (p + mlen + 8u <= n && zc_ld64(in + p + mlen) == zc_ld64(in + cand + mlen))
+						mlen += 8;
+					while (p + mlen < n && in[p + mlen] == in[cand + mlen])
+						mlen++;
+				}
+			}
+			uint64_t mask = __ballot(ok);
+			while (mask != 0) {
+				const uint32_t f = (uint32_t)__builtin_ctzll(mask);
+				mask &= mask - 1;
+				const uint32_t pf = base + f;
+				if (pf < anchor)
+					continue;	/* an earlier match of this window already covers it */
+				const uint32_t mf = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)f);
+				const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)cand, (int)f);
+				const uint32_t lit = pf - anchor;
+				zc_copy(lits + nlit, in + anchor, lit, lane);
+				if (lane == 0)
+					seqs[nseq] = (uint64_t)lit | ((uint64_t)mf << 20) | ((uint64_t)(pf - cf) << 40);
+				nlit += lit;
+				nseq++;
+				anchor = pf + mf;
+			}
+			base = (base + 64 > anchor) ? base + 64 : anchor;
+		}
+	}
+	zc_copy(lits + nlit, in + anchor, n - anchor, lane);
+	nlit += n - anchor;
+	__syncthreads();	/* literals and sequences are in the workspace */
+
+	/* ---- literals section ---- */
+	for (uint32_t i = lane; i < nlit; i += 64)
+		atomicAdd(&L.hist[lits[i]], 1u);
+	__syncthreads();
+	uint32_t maxsym = 0, nsym = 0;
+	for (uint32_t s = lane; s < 256; s += 64)
+		if (L.hist[s]) { maxsym = s; nsym++; }
+	maxsym = wave_max(maxsym);
+	nsym = wave_sum(nsym);
+	uint32_t op = 0;	/* bytes of the block written so far */
+	bool lit_done = false;
+	if (nlit > 0 && nsym == 1) {	/* RLE_Literals_Block */
+		op = lit_hdr_rr(out, 1, nlit, lane == 0);
+		if (lane == 0) out[op] = lits[0];
+		op += 1;
+		lit_done = true;
+	} else if (!(flags & LA_ZSTDC_RAW_LITERALS) && nlit >= ZC_RAW_LIT_MIN && maxsym <= 128u) {
+		/* code lengths: Shannon lengths ceil(log2(nlit / f)) clamped to [1, 11], then made complete.
+		 * K = sum of 2^(11 - len) over the used symbols; complete means K == 2048. */
+		uint32_t Ls[4];
+		uint32_t K = 0;
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const uint32_t f = L.hist[lane + 64 * k];
+			uint32_t l = 0;
+			if (f) {
+				while (((uint64_t)f << l) < nlit) l++;
+				l = l < 1u ? 1u : (l > 11u ? 11u : l);
+				K += 1u << (11u - l);
+			}
+			Ls[k] = l;
+		}
+		K = wave_sum(K);
+		/* too long a code after clamping: lengthen the rarest symbol that can still grow */
+		for (uint32_t it = 0; it < 4096u && K > 2048u; it++) {
+			uint32_t key = 0;
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				const uint32_t s = lane + 64 * k, f = L.hist[s];
+				if (f && Ls[k] < 11u) {
+					const uint32_t c = ((0x3FFFFu - f) << 8) | s;
+					key = c > key ? c : key;
+				}
+			}
+			key = wave_max(key);
+			if (key == 0)
+				break;
+			const uint32_t s = key & 255u;
+			if ((s & 63u) == lane) {
+				K -= 1u << (10u - Ls[s >> 6]);
+				Ls[s >> 6]++;
+			}
+			K = (uint32_t)__shfl((int)K, (int)(s & 63u), 64);
+		}
+		/* room left: shorten the most frequent symbol whose code can shrink without overflowing */
+		for (uint32_t it = 0; it < 4096u && K < 2048u; it++) {
+			const uint32_t room = 2048u - K;
+			uint32_t key = 0;
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				const uint32_t s = lane + 64 * k, f = L.hist[s];
+				if (f && Ls[k] > 1u && (1u << (11u - Ls[k])) <= room) {
+					const uint32_t c = (f << 8) | s | 0x80000000u;
+					key = c > key ? c : key;
+				}
+			}
+			key = wave_max(key);
+			if (key == 0)
+				break;
+			const uint32_t s = key & 255u;
+			if ((s & 63u) == lane) {
+				K += 1u << (11u - Ls[s >> 6]);
+				Ls[s >> 6]--;
+			}
+			K = (uint32_t)__shfl((int)K, (int)(s & 63u), 64);
+		}
+		uint32_t lmax = 0;
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			L.len[lane + 64 * k] = (uint8_t)Ls[k];
+			lmax = Ls[k] > lmax ? Ls[k] : lmax;
+		}
+		lmax = wave_max(lmax);
+		__syncthreads();
+		if (K == 2048u) {
+			/* canonical codes exactly as the decoder lays them out: by weight ascending, then by symbol */
+			if (lane == 0) {
+				for (uint32_t w = 0; w < 16; w++) L.wcnt[w] = 0;
+				for (uint32_t s = 0; s <= maxsym; s++)
+					if (L.len[s]) L.wcnt[lmax + 1u - L.len[s]]++;
+				uint32_t pos = 0;
+				for (uint32_t w = 1; w <= lmax; w++) {
+					const uint32_t c = L.wcnt[w];
+					L.wcnt[w] = pos;
+					pos += c << (w - 1u);
+				}
+				for (uint32_t s = 0; s <= maxsym; s++)
+					if (L.len[s]) {
+						const uint32_t w = lmax + 1u - L.len[s];
+						L.code[s] = (uint16_t)(L.wcnt[w] >> (w - 1u));
+						L.wcnt[w] += 1u << (w - 1u);
+					}
+			}
+			__syncthreads();
+			/* exact sizes: bits of every stream */
+			const uint32_t four = nlit > 1023u;
+			const uint32_t q = four ? (nlit + 3u) / 4u : nlit;
+			uint32_t sb[4] = { 0, 0, 0, 0 };
+			for (uint32_t i = lane; i < nlit; i += 64) {
+				const uint32_t l = L.len[lits[i]], j = i / q;
+				sb[0] += j == 0 ? l : 0u; sb[1] += j == 1 ? l : 0u; sb[2] += j == 2 ? l : 0u; sb[3] += j == 3 ? l : 0u;
+			}
+			uint32_t sbytes[4], body = 0;
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				sbytes[j] = wave_sum(sb[j]) / 8u + 1u;	/* bits + end mark, rounded up */
+				if (j == 0 || four) body += sbytes[j];
+			}
+			const uint32_t nw = maxsym;	/* weights written: symbols 0 .. maxsym - 1 (the last one is implied) */
+			const uint32_t tree = 1u + (nw + 1u) / 2u;
+			const uint32_t comp = tree + (four ? 6u : 0u) + body;
+			const uint32_t hl = !four ? 3u : (nlit < 16384u && comp < 16384u) ? 4u : 5u;
+			const uint32_t raw_size = lit_hdr_rr(out, 0, nlit, false) + nlit;
+			if (hl + comp < raw_size && (four || comp < 1024u)) {
+				if (lane == 0) {
+					const uint32_t sf = !four ? 0u : hl == 4u ? 2u : 3u;
+					const uint64_t v = 2u | (sf << 2) | ((uint64_t)nlit << 4) | ((uint64_t)comp << (hl == 3u ? 14 : hl == 4u ? 18 : 22));
+					for (uint32_t k = 0; k < hl; k++) out[k] = (uint8_t)(v >> (8u * k));
+					out[hl] = (uint8_t)(127u + nw);
+				}
+				/* direct 4-bit weights, two per byte, the first in the high nibble */
+				for (uint32_t k = lane; k < (nw + 1u) / 2u; k += 64) {
+					const uint32_t s0 = 2u * k, s1 = 2u * k + 1u;
+					const uint32_t w0 = L.len[s0] ? lmax + 1u - L.len[s0] : 0u;
+					const uint32_t w1 = (s1 < nw && L.len[s1]) ? lmax + 1u - L.len[s1] : 0u;
+					out[hl + 1u + k] = (uint8_t)((w0 << 4) | w1);
+				}
+				op = hl + tree;
+				if (four) {
+					if (lane == 0) {
+						out[op] = (uint8_t)sbytes[0]; out[op + 1] = (uint8_t)(sbytes[0] >> 8);
+						out[op + 2] = (uint8_t)sbytes[1]; out[op + 3] = (uint8_t)(sbytes[1] >> 8);
+						out[op + 4] = (uint8_t)sbytes[2]; out[op + 5] = (uint8_t)(sbytes[2] >> 8);
+					}
+					op += 6;
+					for (uint32_t j = 0; j < 4; j++) {
+						const uint32_t a = j * q, b = (j + 1u) * q < nlit ? (j + 1u) * q : nlit;
+						op += huf_stream_enc(L, lits, a, b, out + op, lane);
+					}
+				} else {
+					op += huf_stream_enc(L, lits, 0, nlit, out + op, lane);
+				}
+				lit_done = true;
+			}
+		}
+	}
+	if (!lit_done) {	/* Raw_Literals_Block */
+		op = lit_hdr_rr(out, 0, nlit, lane == 0);
+		zc_copy(out + op, lits, nlit, lane);
+		op += nlit;
+	}
+	__syncthreads();	/* the FSE tables below reuse the match table */
+
+	/* ---- sequences section ---- */
+	if (op + 4u > cap || op >= n) {
+		if (lane == 0) { btype[bi] = 0; csize[bi] = n; }
+		return;
+	}
+	if (nseq < 128u) {
+		if (lane == 0) out[op] = (uint8_t)nseq;
+		op += 1;
+	} else if (nseq < 0x7F00u) {
+		if (lane == 0) { out[op] = (uint8_t)((nseq >> 8) + 128u); out[op + 1] = (uint8_t)nseq; }
+		op += 2;
+	} else {
+		if (lane == 0) { out[op] = 255; out[op + 1] = (uint8_t)(nseq - 0x7F00u); out[op + 2] = (uint8_t)((nseq - 0x7F00u) >> 8); }
+		op += 3;
+	}
+	bool over = false;
+	if (nseq > 0) {
+		if (lane == 0) {
+			out[op] = 0;	/* Symbol_Compression_Modes: Predefined_Mode for LL, OF and ML */
+			fse_build(&L.u.f.ll, LL_DEF, 36, 6);
+			fse_build(&L.u.f.ml, ML_DEF, 53, 6);
+			fse_build(&L.u.f.of, OF_DEF, 29, 5);
+		}
+		op += 1;
+		__syncthreads();
+		/* encoder tables: for every state u, the next states its range covers lead back to u */
+		{
+			const fse_ent e = L.u.f.ll.e[lane];
+			for (uint32_t t = 0; t < (1u << e.nbits); t++) L.u.f.ell[e.sym * 64u + e.base + t] = (uint8_t)lane;
+			const fse_ent m = L.u.f.ml.e[lane];
+			for (uint32_t t = 0; t < (1u << m.nbits); t++) L.u.f.eml[m.sym * 64u + m.base + t] = (uint8_t)lane;
+			if (lane < 32) {
+				const fse_ent o = L.u.f.of.e[lane];
+				for (uint32_t t = 0; t < (1u << o.nbits); t++) L.u.f.eof[o.sym * 32u + o.base + t] = (uint8_t)lane;
+			}
+		}
+		__syncthreads();
+		zc_bw w;
+		w.out = out; w.op = op; w.cap = cap; w.acc = 0; w.n = 0; w.over = false;
+		uint32_t sl = 0, sm = 0, sof = 0;
+		/* last sequence first, 64 at a time: lane j prepares sequence hi - 1 - j */
+		for (uint32_t hi = nseq; hi > 0;) {
+			const uint32_t cnt = hi < 64u ? hi : 64u;
+			uint32_t codes = 0, lmx = 0, lmbits = 0, ov = 0;
+			if (lane < cnt) {
+				const uint64_t s = seqs[hi - 1u - lane];
+				const uint32_t ll = (uint32_t)(s & 0xFFFFFu), ml = (uint32_t)((s >> 20) & 0xFFFFFu), off = (uint32_t)(s >> 40);
+				const uint32_t lc = ll_code(ll), mc = ml_code(ml);
+				ov = off + 3u;
+				const uint32_t oc = (uint32_t)highbit(ov);
+				codes = lc | (mc << 8) | (oc << 16);
+				lmx = (ll - SEQ_TABS.ll_base[lc]) | ((ml - SEQ_TABS.ml_base[mc]) << 16);
+				lmbits = SEQ_TABS.ll_bits[lc] | ((uint32_t)SEQ_TABS.ml_bits[mc] << 8);
+				ov -= 1u << oc;
+			}
+			for (uint32_t j = 0; j < cnt; j++) {
+				const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)codes, (int)j);
+				const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lmx, (int)j);
+				const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)lmbits, (int)j);
+				const uint32_t ox = (uint32_t)__builtin_amdgcn_readlane((int)ov, (int)j);
+				const uint32_t lc = c & 255u, mc = (c >> 8) & 255u, oc = c >> 16;
+				if (hi == nseq && j == 0) {
+					/* the block's last sequence: any state of its symbols */
+					sl = L.u.f.ell[lc * 64u]; sm = L.u.f.eml[mc * 64u]; sof = L.u.f.eof[oc * 32u];
+				} else {
+					/* state of this sequence whose range holds the next one's state; the bits select it */
+					const uint32_t uo = L.u.f.eof[oc * 32u + sof], um = L.u.f.eml[mc * 64u + sm], ul = L.u.f.ell[lc * 64u + sl];
+					const fse_ent eo = L.u.f.of.e[uo], em = L.u.f.ml.e[um], el = L.u.f.ll.e[ul];
+					bw_put(w, sof - eo.base, eo.nbits, lane);
+					bw_put(w, sm - em.base, em.nbits, lane);
+					bw_put(w, sl - el.base, el.nbits, lane);
+					sl = ul; sm = um; sof = uo;
+				}
+				/* extra bits: the decoder reads offset, match length, literal length */
+				bw_put(w, x & 0xFFFFu, b & 255u, lane);
+				bw_put(w, x >> 16, b >> 8, lane);
+				bw_put(w, ox, oc, lane);
+			}
+			hi -= cnt;
+		}
+		/* initial states: the decoder reads LL, OF, ML */
+		bw_put(w, sm, 6, lane);
+		bw_put(w, sof, 5, lane);
+		bw_put(w, sl, 6, lane);
+		bw_put(w, 1, 1, lane);	/* end mark */
+		const uint32_t tail = (w.n + 7u) >> 3;
+		if (w.op + tail > cap) {
+			w.over = true;
+		} else if (lane == 0) {
+			for (uint32_t k = 0; k < tail; k++)
+				out[w.op + k] = (uint8_t)(w.acc >> (8u * k));
+		}
+		op = w.op + tail;
+		over = w.over;
+	}
+	if (lane == 0) {
+		const bool comp = !over && op < n;
+		btype[bi] = comp ? 2u : 0u;
+		csize[bi] = comp ? op : n;
+	}
+}
+
+/* XXH64 by FOUR adjacent lanes (lane j of the quad owns accumulator j and reads the j-th word of every 32-byte
+ * stripe); the result is valid in all four lanes */
+__device__ static uint64_t xxh64_quad(const uint8_t *p, uint64_t len, uint32_t j)
+{
+	const uint8_t *end = p + len;
+	uint64_t h;
+	if (len >= 32) {
+		uint64_t v = j == 0 ? P64_1 + P64_2 : (j == 1 ? P64_2 : (j == 2 ? 0ull : 0ull - P64_1));
+		const uint64_t stripes = len / 32;
+		const uint8_t *q = p + 8u * j;
+#pragma unroll 8
+		for (uint64_t s = 0; s < stripes; s++)
+			v = xxh64_round(v, rd64(q + 32u * s));
+		const uint32_t q0 = threadIdx.x & ~3u;
+		uint64_t a[4];
+		for (uint32_t k = 0; k < 4; k++) {
+			const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)(q0 + k), 64);
+			const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)(q0 + k), 64);
+			a[k] = (uint64_t)lo | ((uint64_t)hi << 32);
+		}
+		h = rotl64(a[0], 1) + rotl64(a[1], 7) + rotl64(a[2], 12) + rotl64(a[3], 18);
+		h = xxh64_merge(h, a[0]); h = xxh64_merge(h, a[1]); h = xxh64_merge(h, a[2]); h = xxh64_merge(h, a[3]);
+		p += stripes * 32u;
+	} else {
+		h = P64_5;
+	}
+	h += len;
+	while (p + 8 <= end) { h ^= xxh64_round(0, rd64(p)); h = rotl64(h, 27) * P64_1 + P64_4; p += 8; }
+	if (p + 4 <= end) { h ^= (uint64_t)rd32(p) * P64_1; h = rotl64(h, 23) * P64_2 + P64_3; p += 4; }
+	while (p < end) { h ^= (uint64_t)(*p++) * P64_5; h = rotl64(h, 11) * P64_1; }
+	h ^= h >> 33; h *= P64_2; h ^= h >> 29; h *= P64_3; h ^= h >> 32;
+	return h;
+}
+
+__global__ __launch_bounds__(64) void zstdc_frame_sums_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
+    uint64_t frame_bytes, uint32_t n_frames, uint32_t *__restrict__ frame_sum)
+{
+	const uint32_t q = (blockIdx.x * 64 + threadIdx.x) >> 2, j = threadIdx.x & 3u;
+	const bool have = q < n_frames;
+	const uint64_t fo = have ? (uint64_t)q * frame_bytes : 0;
+	const uint64_t fl = have && src_bytes > fo ? (src_bytes - fo < frame_bytes ? src_bytes - fo : frame_bytes) : 0;
+	const uint64_t h = xxh64_quad(src + fo, fl, j);
+	if (have && j == 0)
+		frame_sum[q] = (uint32_t)h;
+}
+
+__host__ __device__ static inline uint32_t zc_fcs_len(uint64_t fcs) { return fcs < 256u ? 1u : fcs < 65536u + 256u ? 2u : 4u; }
+
+/* bytes of the stream each block contributes: block header + payload, plus the frame header in front of the
+ * frame's first block and the checksum behind its last */
+__global__ __launch_bounds__(256) void zstdc_sizes_kernel(const uint32_t *__restrict__ csize, uint64_t src_bytes,
+    uint32_t block_size, uint32_t n_blocks, uint32_t bpf, uint32_t flags, uint32_t *__restrict__ contrib)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_blocks)
+		return;
+	uint32_t c = 3u + csize[i];
+	if (i % bpf == 0) {
+		const uint64_t fo = (uint64_t)i * block_size, fb = (uint64_t)bpf * block_size;
+		const uint64_t fcs = src_bytes - fo < fb ? src_bytes - fo : fb;
+		c += 5u + zc_fcs_len(fcs);
+	}
+	if ((i % bpf == bpf - 1 || i + 1 == n_blocks) && (flags & LA_ZSTDC_CHECKSUM))
+		c += 4u;
+	contrib[i] = c;
+}
+
+__global__ __launch_bounds__(256) void zstd_pack_frames_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
+    uint32_t block_size, uint32_t n_blocks, uint32_t bpf, uint32_t flags, const uint8_t *__restrict__ tmp,
+    const uint32_t *__restrict__ btype, const uint32_t *__restrict__ csize, const uint64_t *__restrict__ off,
+    const uint32_t *__restrict__ frame_sum, uint8_t *__restrict__ out, uint64_t out_cap, uint64_t *__restrict__ out_bytes)
+{
+	const uint32_t bi = blockIdx.x, tid = threadIdx.x;
+	if (bi >= n_blocks)
+		return;
+	const uint64_t so = (uint64_t)bi * block_size;
+	const uint32_t n = src_bytes > so ? (uint32_t)(src_bytes - so < block_size ? src_bytes - so : block_size) : 0u;
+	const uint32_t type = btype[bi], pay = csize[bi];
+	const bool last = bi % bpf == bpf - 1 || bi + 1 == n_blocks;
+	uint64_t o = off[bi];
+	if (bi + 1 == n_blocks && tid == 0)
+		*out_bytes = off[n_blocks];
+	if (off[bi + 1] > out_cap)
+		return;		/* the caller sees out_bytes > out_cap */
+	if (bi % bpf == 0) {
+		const uint64_t fb = (uint64_t)bpf * block_size;
+		const uint64_t fcs = src_bytes - so < fb ? src_bytes - so : fb;
+		const uint32_t fl = zc_fcs_len(fcs);
+		if (tid == 0) {
+			/* magic; FHD: FCS_Field_Size flag, Single_Segment_Flag, Content_Checksum_Flag, no dictionary */
+			out[o] = 0x28; out[o + 1] = 0xB5; out[o + 2] = 0x2F; out[o + 3] = 0xFD;
+			out[o + 4] = (uint8_t)((fl == 1u ? 0u : fl == 2u ? 0x40u : 0x80u) | 0x20u | ((flags & LA_ZSTDC_CHECKSUM) ? 4u : 0u));
+			const uint64_t v = fl == 2u ? fcs - 256u : fcs;
+			for (uint32_t k = 0; k < fl; k++)
+				out[o + 5 + k] = (uint8_t)(v >> (8u * k));
+		}
+		o += 5u + fl;
+	}
+	if (tid == 0) {
+		const uint32_t bh = (last ? 1u : 0u) | (type << 1) | ((type == 2u ? pay : n) << 3);
+		out[o] = (uint8_t)bh; out[o + 1] = (uint8_t)(bh >> 8); out[o + 2] = (uint8_t)(bh >> 16);
+	}
+	o += 3;
+	const uint8_t *payload = type == 2u ? tmp + (uint64_t)bi * zc_tmp_stride(block_size) : src + so;
+	for (uint32_t i = tid; i < pay; i += 256)
+		out[o + i] = payload[i];
+	o += pay;
+	if (last && (flags & LA_ZSTDC_CHECKSUM) && tid == 0) {
+		const uint32_t c = frame_sum[bi / bpf];
+		out[o] = (uint8_t)c; out[o + 1] = (uint8_t)(c >> 8); out[o + 2] = (uint8_t)(c >> 16); out[o + 3] = (uint8_t)(c >> 24);
+	}
+}
+
+static uint64_t zc_blocks(uint64_t src_bytes, uint32_t bs) { return src_bytes ? (src_bytes + bs - 1) / bs : 1u; }
+
+extern "C" uint64_t la_gpu_zstd_compress_workspace_bytes(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame)
+{
+	if (block_size == 0 || block_size > ZC_BLOCK_MAX || blocks_per_frame == 0)
+		return 0;
+	const uint64_t nb = zc_blocks(src_bytes, block_size), nf = (nb + blocks_per_frame - 1) / blocks_per_frame;
+	return nb * (zc_tmp_stride(block_size) + zc_lit_stride(block_size) + zc_seq_stride(block_size)) + nb * 4 * 3 +
+	    (nb + 1) * 8 + nf * 4 + la_scan_scratch_bytes((uint32_t)nb) + 4096;
+}
+
+extern "C" uint64_t la_gpu_zstd_compress_bound(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame)
+{
+	if (block_size == 0 || block_size > ZC_BLOCK_MAX || blocks_per_frame == 0)
+		return 0;
+	const uint64_t nb = zc_blocks(src_bytes, block_size), nf = (nb + blocks_per_frame - 1) / blocks_per_frame;
+	return src_bytes + nb * 3u + nf * 13u + 64u;	/* a block is at most its input (raw); frame header 9, checksum 4 */
+}
+
+void la_launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
+    uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws)
+{
+	const uint32_t nb = (uint32_t)zc_blocks(src_bytes, block_size);
+	const uint32_t nf = (nb + bpf - 1) / bpf;
+	uint64_t o = 0;
+	uint8_t *tmp = ws + o; o += (uint64_t)nb * zc_tmp_stride(block_size);
+	uint8_t *lits = ws + o; o += (uint64_t)nb * zc_lit_stride(block_size);
+	o = (o + 7) & ~7ull;
+	uint64_t *seqs = (uint64_t *)(ws + o); o += (uint64_t)nb * zc_seq_stride(block_size);
+	uint32_t *btype = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
+	uint32_t *csize = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
+	uint32_t *contrib = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
+	o = (o + 7) & ~7ull;
+	uint64_t *off = (uint64_t *)(ws + o); o += ((uint64_t)nb + 1) * 8;
+	uint32_t *fsum = (uint32_t *)(ws + o); o += (uint64_t)nf * 4;
+	o = (o + 255) & ~255ull;
+	void *scan = ws + o;
+	hipLaunchKernelGGL(zstd_compress_blocks_kernel, dim3(nb), dim3(64), 0, s, d_src, src_bytes, block_size, nb, flags,
+	    tmp, lits, seqs, btype, csize);
+	if (flags & LA_ZSTDC_CHECKSUM)
+		hipLaunchKernelGGL(zstdc_frame_sums_kernel, dim3((nf + 15) / 16), dim3(64), 0, s, d_src, src_bytes,
+		    (uint64_t)bpf * block_size, nf, fsum);
+	hipLaunchKernelGGL(zstdc_sizes_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, csize, src_bytes, block_size, nb, bpf, flags, contrib);
+	la_launch_scan_u32(s, contrib, nb, off, scan);
+	hipLaunchKernelGGL(zstd_pack_frames_kernel, dim3(nb), dim3(256), 0, s, d_src, src_bytes, block_size, nb, bpf, flags,
+	    tmp, btype, csize, off, fsum, d_out, out_cap, d_out_bytes);
+}

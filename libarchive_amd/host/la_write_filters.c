@@ -37,26 +37,9 @@
 #include <unistd.h>
 
 #include "la_read_private.h"
+#include "la_write_private.h"
 #include "../../include/la_gpu.h"
 #include "../../include/la_host.h"
-
-struct archive_write_filter {	/* archive_write_private.h:46-63 */
-	int64_t bytes_written;
-	struct archive *archive;
-	struct archive_write_filter *next_filter;
-	int (*options)(struct archive_write_filter *, const char *key, const char *value);
-	int (*open)(struct archive_write_filter *);
-	int (*write)(struct archive_write_filter *, const void *, size_t);
-	int (*flush)(struct archive_write_filter *);
-	int (*close)(struct archive_write_filter *);
-	int (*free)(struct archive_write_filter *);
-	void *data;
-	const char *name;
-	int code;
-	int bytes_per_block;
-	int bytes_in_last_block;
-	int state;
-};
 
 struct archive_write {
 	struct archive archive;		/* first: the error helpers of la_read_core.c work on it */

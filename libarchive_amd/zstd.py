@@ -61,3 +61,23 @@ class ZstdDevicePlan:
     def results(self):
         self.ctx.sync()
         return self.d_results.cpu().numpy().view(ZSTD_RESULT_DTYPE)[:self.n]
+
+
+def compress_to_frames(ctx, d_plain, block_size=131072, blocks_per_frame=1, flags=N.LA_ZSTDC_CHECKSUM):
+    """Device zstd compression (la_gpu_zstd_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8 CUDA
+    tensor holding the concatenated frames (harness for the tests and for stream synthesis)."""
+    import torch
+    n = int(d_plain.numel())
+    cap = int(N.gpu_lib().la_gpu_zstd_compress_bound(n, block_size, blocks_per_frame))
+    d_out = torch.empty(max(cap, 16), dtype=torch.uint8, device=d_plain.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_plain.device)
+    b = N._ZstdcBatchC()
+    b.d_src = d_plain.data_ptr() if n else None
+    b.src_bytes = n
+    b.block_size, b.blocks_per_frame, b.flags = block_size, blocks_per_frame, flags
+    b.d_out, b.out_cap, b.d_out_bytes = d_out.data_ptr(), cap, d_len.data_ptr()
+    ctx.zstd_compress(b)
+    ctx.sync()
+    total = int(d_len.cpu()[0])
+    assert total <= cap, (total, cap)
+    return d_out[:total]
