@@ -575,14 +575,22 @@ int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 	return LA_OK;
 }
 
-/* ------------------------------------------------------------------ lz4 compression */
+/* ------------------------------------------------------------------ compression */
 
-uint64_t la_gpu_lz4_compress_bound(uint64_t src_bytes, uint32_t block_size, uint32_t bpf)
+/* the body every compress entry shares once its arguments are checked: workspace, profile range, launch */
+extern "C++" template <typename Launch>
+static int compress_run(la_gpu_ctx *c, uint64_t need, const char *name, Launch launch)
 {
-	if (block_size == 0 || bpf == 0)
-		return 0;
-	const uint64_t nb = (src_bytes + block_size - 1) / block_size, nf = (nb + bpf - 1) / bpf;
-	return src_bytes + nb * (block_size / 255u + 16u + 8u) + nf * 15u + 64u;
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	int h = prof_open(c, name, c->stream);
+	launch((uint8_t *)c->ws);
+	prof_close(c, h, c->stream);
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
 }
 
 int la_gpu_lz4_compress(la_gpu_ctx *c, const la_lz4c_batch *bt)
@@ -593,28 +601,11 @@ int la_gpu_lz4_compress(la_gpu_ctx *c, const la_lz4c_batch *bt)
 	    (uint64_t)bt->block_size * bt->blocks_per_frame > 0x7FFFFFFFull ||
 	    (bt->src_bytes + bt->block_size - 1) / bt->block_size > 0xFFFFFFFEull)
 		return LA_ERR_ARG;
-	const uint64_t need = la_gpu_lz4_compress_workspace_bytes(bt->src_bytes, bt->block_size, bt->blocks_per_frame);
-	if (need > c->ws_bytes) {
-		int rc = la_gpu_reserve(c, need);
-		if (rc != LA_OK) return rc;
-	}
-	prof_begin(c);
-	int h = prof_open(c, "lz4_compress", c->stream);
-	la_launch_lz4_compress(c->stream, bt->d_src, bt->src_bytes, bt->block_size, bt->blocks_per_frame, bt->flags,
-	    bt->d_out, bt->out_cap, bt->d_out_bytes, (uint8_t *)c->ws);
-	prof_close(c, h, c->stream);
-	HIPCHK(c, hipGetLastError());
-	return LA_OK;
-}
-
-/* ------------------------------------------------------------------ gzip compression */
-
-uint64_t la_gpu_gzip_compress_bound(uint64_t src_bytes, uint32_t chunk)
-{
-	if (chunk == 0)
-		return 0;
-	const uint64_t nc = (src_bytes + chunk - 1) / chunk;
-	return src_bytes + nc * (18u + 8u + 5u) + 64u;	/* a chunk that does not shrink is stored: 5 bytes of block header */
+	return compress_run(c, la_gpu_lz4_compress_workspace_bytes(bt->src_bytes, bt->block_size, bt->blocks_per_frame),
+	    "lz4_compress", [&](uint8_t *ws) {
+		la_launch_lz4_compress(c->stream, bt->d_src, bt->src_bytes, bt->block_size, bt->blocks_per_frame, bt->flags,
+		    bt->d_out, bt->out_cap, bt->d_out_bytes, ws);
+	});
 }
 
 int la_gpu_gzip_compress(la_gpu_ctx *c, const la_gzc_batch *bt)
@@ -623,21 +614,11 @@ int la_gpu_gzip_compress(la_gpu_ctx *c, const la_gzc_batch *bt)
 		return LA_ERR_ARG;
 	if (bt->chunk_bytes == 0 || bt->chunk_bytes > 49152u || (bt->src_bytes + bt->chunk_bytes - 1) / bt->chunk_bytes > 0xFFFFFFFEull)
 		return LA_ERR_ARG;
-	const uint64_t need = la_gpu_gzip_compress_workspace_bytes(bt->src_bytes, bt->chunk_bytes);
-	if (need > c->ws_bytes) {
-		int rc = la_gpu_reserve(c, need);
-		if (rc != LA_OK) return rc;
-	}
-	prof_begin(c);
-	int h = prof_open(c, "gzip_compress", c->stream);
-	la_launch_gzip_compress(c->stream, bt->d_src, bt->src_bytes, bt->chunk_bytes, bt->mtime, bt->d_out, bt->out_cap,
-	    bt->d_out_bytes, (uint8_t *)c->ws);
-	prof_close(c, h, c->stream);
-	HIPCHK(c, hipGetLastError());
-	return LA_OK;
+	return compress_run(c, la_gpu_gzip_compress_workspace_bytes(bt->src_bytes, bt->chunk_bytes), "gzip_compress", [&](uint8_t *ws) {
+		la_launch_gzip_compress(c->stream, bt->d_src, bt->src_bytes, bt->chunk_bytes, bt->mtime, bt->d_out, bt->out_cap,
+		    bt->d_out_bytes, ws);
+	});
 }
-
-/* ------------------------------------------------------------------ zstd compression */
 
 int la_gpu_zstd_compress(la_gpu_ctx *c, const la_zstdc_batch *bt)
 {
@@ -647,18 +628,11 @@ int la_gpu_zstd_compress(la_gpu_ctx *c, const la_zstdc_batch *bt)
 	    (uint64_t)bt->block_size * bt->blocks_per_frame > 0x7FFFFFFFull ||
 	    (bt->src_bytes + bt->block_size - 1) / bt->block_size > 0x7FFFFFFEull)
 		return LA_ERR_ARG;
-	const uint64_t need = la_gpu_zstd_compress_workspace_bytes(bt->src_bytes, bt->block_size, bt->blocks_per_frame);
-	if (need > c->ws_bytes) {
-		int rc = la_gpu_reserve(c, need);
-		if (rc != LA_OK) return rc;
-	}
-	prof_begin(c);
-	int h = prof_open(c, "zstd_compress", c->stream);
-	la_launch_zstd_compress(c->stream, bt->d_src, bt->src_bytes, bt->block_size, bt->blocks_per_frame, bt->flags,
-	    bt->d_out, bt->out_cap, bt->d_out_bytes, (uint8_t *)c->ws);
-	prof_close(c, h, c->stream);
-	HIPCHK(c, hipGetLastError());
-	return LA_OK;
+	return compress_run(c, la_gpu_zstd_compress_workspace_bytes(bt->src_bytes, bt->block_size, bt->blocks_per_frame),
+	    "zstd_compress", [&](uint8_t *ws) {
+		la_launch_zstd_compress(c->stream, bt->d_src, bt->src_bytes, bt->block_size, bt->blocks_per_frame, bt->flags,
+		    bt->d_out, bt->out_cap, bt->d_out_bytes, ws);
+	});
 }
 
 } /* extern "C" */

@@ -19,11 +19,11 @@
  *       order and marks what they cover; then every lane knows its token -- literal, match start or
  *       nothing -- as at most 31 bits of a FIXED-Huffman block (RFC 1951 3.2.6), a wave prefix sum of
  *       the bit counts gives every token its place, lanes OR their bits into a small LDS stage and whole
- *       dwords go out coalesced.  A chunk that would not shrink is written as a stored block instead.
+ *       dwords go out coalesced (wave_bits_append, la_comp_common.h).  A chunk that would not shrink is written as a stored block instead.
  *   gz_jobs_kernel + crc32_many  CRC32 of every chunk (la_hash.hip).
  *   gz_pack_members_kernel  header, body (fixed-Huffman or stored), trailer at their scanned offsets.
  */
-#include "la_dev.h"
+#include "la_comp_common.h"
 
 #define DFL_CHUNK_MAX 49152u
 #define DFL_HASH_BITS 12
@@ -140,41 +140,8 @@ __global__ __launch_bounds__(64) void deflate_fixed_kernel(const uint8_t *__rest
 			else
 				bits = fixed_lit(in[p], &nb);
 		}
-		/* its place: exclusive prefix sum of the bit counts over the wave */
-		uint32_t inc = nb;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t t = __shfl_up(inc, d, 64);
-			if ((int)lane >= d) inc += t;
-		}
-		const uint32_t total = __shfl(inc, 63, 64);
-		const uint32_t at = (uint32_t)(bp & 31u) + inc - nb;	/* bit offset inside the stage */
-		if (nb) {
-			const uint64_t w = (uint64_t)bits << (at & 31u);
-			atomicOr(&stage[at >> 5], (uint32_t)w);
-			if ((uint32_t)(w >> 32))
-				atomicOr(&stage[(at >> 5) + 1], (uint32_t)(w >> 32));
-		}
-		__builtin_amdgcn_wave_barrier();
-		/* whole dwords leave; the partial last one stays as the next window's first */
-		const uint32_t tb = (uint32_t)(bp & 31u) + total, nd = tb >> 5;
-		const uint32_t g0 = (uint32_t)(bp >> 5);
-		uint32_t mine = 0, carry = stage[nd];
-		if (lane < nd)
-			mine = stage[lane];
-		__builtin_amdgcn_wave_barrier();
-		if (lane < nd)
-			out[g0 + lane] = mine;
-		if (lane <= nd && lane < 72)
-			stage[lane] = 0;
-		if (nd >= 64 && lane == 0) {	/* (at most 64 * 31 + 31 bits: dword 64 can only be the partial one) */
-			stage[64] = 0;
-		}
-		__builtin_amdgcn_wave_barrier();
-		if (lane == 0)
-			stage[0] = carry;
-		__builtin_amdgcn_wave_barrier();
-		bp += total;
+		/* its place in the stream; whole dwords go out aligned */
+		bp += wave_bits_append(bp, bits, nb, stage, lane, [&](uint32_t i, uint32_t w) { out[i] = w; });
 	}
 	/* end-of-block (seven zero bits), then the partial dword */
 	bp += 7;
@@ -225,14 +192,13 @@ __global__ __launch_bounds__(256) void gz_pack_members_kernel(const uint8_t *__r
 	if (tid == 0) {
 		uint8_t *h = out + o;
 		h[0] = 0x1f; h[1] = 0x8b; h[2] = 8; h[3] = 4;	/* FEXTRA */
-		h[4] = (uint8_t)mtime; h[5] = (uint8_t)(mtime >> 8); h[6] = (uint8_t)(mtime >> 16); h[7] = (uint8_t)(mtime >> 24);
+		st_le32(h + 4, mtime);
 		h[8] = 0; h[9] = 3;				/* XFL 0, OS = Unix (archive_write_add_filter_gzip.c:230-231) */
 		h[10] = 6; h[11] = 0; h[12] = 'B'; h[13] = 'C'; h[14] = 2; h[15] = 0;
 		h[16] = (uint8_t)(total - 1u); h[17] = (uint8_t)((total - 1u) >> 8);
 		uint8_t *t = out + o + DFL_HDR + body;
-		const uint32_t c = crc[ci];
-		t[0] = (uint8_t)c; t[1] = (uint8_t)(c >> 8); t[2] = (uint8_t)(c >> 16); t[3] = (uint8_t)(c >> 24);
-		t[4] = (uint8_t)n; t[5] = (uint8_t)(n >> 8); t[6] = (uint8_t)(n >> 16); t[7] = (uint8_t)(n >> 24);
+		st_le32(t, crc[ci]);
+		st_le32(t + 4, n);
 	}
 	uint8_t *b = out + o + DFL_HDR;
 	if (stored) {
@@ -249,38 +215,62 @@ __global__ __launch_bounds__(256) void gz_pack_members_kernel(const uint8_t *__r
 	}
 }
 
+struct gzc_ws {
+	uint8_t *tmp;
+	uint32_t *body_len, *contrib, *crc;
+	la_hash_job *jobs;
+	uint64_t *off;
+	void *scan;
+};
+
+/* the launcher's workspace on `base` (null: sizes only); returns its bytes before the scan scratch */
+static uint64_t gzc_carve(gzc_ws *w, uint8_t *base, uint64_t nc, uint32_t stride)
+{
+	la_carve c = { base, 0 };
+	w->tmp = c.take<uint8_t>(nc * stride);
+	w->body_len = c.take<uint32_t>(nc);
+	w->contrib = c.take<uint32_t>(nc);
+	w->crc = c.take<uint32_t>(nc);
+	w->jobs = c.take<la_hash_job>(nc, 16);
+	w->off = c.take<uint64_t>(nc + 1);
+	w->scan = c.take<uint8_t>(0, 256);
+	return c.off;
+}
+
+static uint32_t gzc_stride(uint32_t chunk) { return (dfl_body_bound(chunk) + 15u) & ~15u; }
+
 extern "C" uint64_t la_gpu_gzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t chunk)
 {
 	if (chunk == 0)
 		return 0;
 	const uint64_t nc = (src_bytes + chunk - 1) / chunk;
-	const uint64_t stride = (dfl_body_bound(chunk) + 15u) & ~15ull;
-	return nc * stride + nc * (4 + 4 + 4 + sizeof(la_hash_job)) + (nc + 1) * 8 + la_scan_scratch_bytes((uint32_t)nc) + 4096;
+	gzc_ws w;
+	return gzc_carve(&w, nullptr, nc, gzc_stride(chunk)) + la_scan_scratch_bytes((uint32_t)nc);
+}
+
+extern "C" uint64_t la_gpu_gzip_compress_bound(uint64_t src_bytes, uint32_t chunk)
+{
+	if (chunk == 0)
+		return 0;
+	const uint64_t nc = (src_bytes + chunk - 1) / chunk;
+	return src_bytes + nc * (18u + 8u + 5u) + 64u;	/* a chunk that does not shrink is stored: 5 bytes of block header */
 }
 
 void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t chunk, uint32_t mtime,
     uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws)
 {
 	const uint32_t nc = (uint32_t)((src_bytes + chunk - 1) / chunk);
-	const uint32_t stride = (dfl_body_bound(chunk) + 15u) & ~15u;
-	uint64_t o = 0;
-	uint8_t *tmp = ws + o; o += (uint64_t)nc * stride;
-	uint32_t *body_len = (uint32_t *)(ws + o); o += (uint64_t)nc * 4;
-	uint32_t *contrib = (uint32_t *)(ws + o); o += (uint64_t)nc * 4;
-	uint32_t *crc = (uint32_t *)(ws + o); o += (uint64_t)nc * 4;
-	o = (o + 15) & ~15ull;
-	la_hash_job *jobs = (la_hash_job *)(ws + o); o += (uint64_t)nc * sizeof(la_hash_job);
-	uint64_t *off = (uint64_t *)(ws + o); o += ((uint64_t)nc + 1) * 8;
-	o = (o + 255) & ~255ull;
-	void *scan = ws + o;
+	const uint32_t stride = gzc_stride(chunk);
+	gzc_ws w;
+	gzc_carve(&w, ws, nc, stride);
 	if (nc == 0) {
 		(void)hipMemsetAsync(d_out_bytes, 0, 8, s);
 		return;
 	}
-	hipLaunchKernelGGL(deflate_fixed_kernel, dim3(nc), dim3(64), 0, s, d_src, src_bytes, chunk, nc, tmp, stride, body_len);
-	hipLaunchKernelGGL(gz_jobs_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, body_len, jobs, contrib);
-	la_launch_crc32_many(s, d_src, jobs, nc, crc);
-	la_launch_scan_u32(s, contrib, nc, off, scan);
-	hipLaunchKernelGGL(gz_pack_members_kernel, dim3(nc), dim3(256), 0, s, d_src, src_bytes, chunk, nc, mtime, tmp, stride,
-	    body_len, crc, off, d_out, out_cap, d_out_bytes);
+	hipLaunchKernelGGL(deflate_fixed_kernel, dim3(nc), dim3(64), 0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len);
+	hipLaunchKernelGGL(gz_jobs_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.jobs, w.contrib);
+	la_launch_crc32_many(s, d_src, w.jobs, nc, w.crc);
+	la_launch_scan_u32(s, w.contrib, nc, w.off, w.scan);
+	hipLaunchKernelGGL(gz_pack_members_kernel, dim3(nc), dim3(256), 0, s, d_src, src_bytes, chunk, nc, mtime, w.tmp, stride,
+	    w.body_len, w.crc, w.off, d_out, out_cap, d_out_bytes);
 }

@@ -484,8 +484,9 @@ void la_launch_lz4_expand_fast_big(hipStream_t s, const uint8_t *d_src, uint64_t
     const uint32_t *d_nseq, const la_lz4_seq *d_table, const uint64_t *d_table_off,
     uint32_t *d_big /* n + 1 words */, uint32_t long_thr);
 
-/* la_lz4_inorder.hip: the default expand step since round 3 (in-order matcher wave + literal wave + flush wave per
- * 64 KiB LDS window); the same contract, blocks of any sequence count (no _big launch) */
+/* la_lz4_inorder.hip: the in-order expand step, run on request as the cross-check of the polling kernel (in-order
+ * matcher wave + literal wave + flush wave per 64 KiB LDS window); the same contract, blocks of any sequence count
+ * (no _big launch) */
 bool la_lz4_expand_inorder_takes(uint64_t src_bytes);	/* false: image too short for it, use the polling kernel */
 void la_launch_lz4_expand_inorder(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
@@ -501,9 +502,11 @@ void la_launch_zstd_frames(hipStream_t s, const uint8_t *d_src, uint64_t src_byt
 void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
 
-/* la_deflate_comp.hip */
+/* la_zstd_comp.hip */
 void la_launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
+
+/* la_deflate_comp.hip */
 void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t chunk, uint32_t mtime,
     uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
 

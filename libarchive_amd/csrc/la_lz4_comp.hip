@@ -13,11 +13,8 @@
  * (last five bytes literal, last match at least 12 bytes before the end, offsets inside the block).
  *
  *   lz4_compress_blocks_kernel   ONE WAVE per block of at most 64 KiB.  A 4096-entry hash table of
- *       16-bit positions in LDS; the wave looks at 64 consecutive positions at a time: every lane
- *       hashes the four bytes at its position, takes the table's candidate (from an earlier window),
- *       replaces it, verifies the candidate and extends the match eight bytes at a time.  The wave
- *       then takes the matches in position order (ballot + first set bit), skipping the ones an
- *       earlier match has covered, and writes each sequence cooperatively: token and length bytes by
+ *       16-bit positions in LDS, matched by lz77_match (la_comp_common.h: 64 positions per step, matches
+ *       taken in position order); the wave writes each sequence cooperatively: token and length bytes by
  *       the first lanes, the literal run 64 bytes per step.  Input is read from global memory
  *       (it stays in L1 / L2 for the lifetime of a block), so LDS holds only the table and many
  *       waves fit a CU.
@@ -25,30 +22,16 @@
  *   lz4_pack_frames_kernel       one workgroup per block: size word, payload (compressed, or the
  *       input itself when it did not shrink), block checksum; the frame's first / last block also
  *       writes the 7-byte header / EndMark + content checksum.
+ *   frame_sums_kernel            XXH32 of every frame's input (la_comp_common.h), four lanes per frame.
  * The two kinds of XXH32 (per block over the written payload, per frame over the input) run on
  * xxh32_lane / xxh32_quad of la_dev.h.
  */
-#include "la_dev.h"
+#include "la_comp_common.h"
 
-#define LZ4C_HASH_BITS 12
 #define LZ4C_MFLIMIT   12u
 #define LZ4C_LASTLIT   5u
 
 __host__ __device__ static inline uint32_t lz4c_bound(uint32_t n) { return n + n / 255u + 16u; }
-
-__device__ __forceinline__ uint64_t ld_u64(const uint8_t *p)
-{
-	uint64_t v;
-	__builtin_memcpy(&v, p, 8);
-	return v;
-}
-
-/* wave-cooperative byte copy, n uniform */
-__device__ __forceinline__ void wave_copy(uint8_t *d, const uint8_t *s, uint32_t n, uint32_t lane)
-{
-	for (uint32_t i = lane; i < n; i += 64)
-		d[i] = s[i];
-}
 
 /* length field beyond the token nibble: v - 15 as 255, 255, ..., rest (lanes write in parallel); returns bytes written */
 __device__ __forceinline__ uint32_t wave_put_len(uint8_t *d, uint32_t v, uint32_t lane)
@@ -63,7 +46,7 @@ __global__ __launch_bounds__(64) void lz4_compress_blocks_kernel(const uint8_t *
     uint32_t block_size, uint32_t n_blocks, uint8_t *__restrict__ tmp, uint32_t tmp_stride,
     uint32_t *__restrict__ csize)
 {
-	__shared__ uint16_t tab[1u << LZ4C_HASH_BITS];
+	__shared__ uint16_t tab[1u << LZ77_HASH_BITS];
 	const uint32_t bi = blockIdx.x, lane = threadIdx.x;
 	if (bi >= n_blocks)
 		return;
@@ -71,68 +54,32 @@ __global__ __launch_bounds__(64) void lz4_compress_blocks_kernel(const uint8_t *
 	const uint32_t n = (uint32_t)(src_bytes - so < block_size ? src_bytes - so : block_size);
 	const uint8_t *in = src + so;
 	uint8_t *out = tmp + (uint64_t)bi * tmp_stride;
-	for (uint32_t i = lane; i < (1u << LZ4C_HASH_BITS); i += 64)
+	for (uint32_t i = lane; i < (1u << LZ77_HASH_BITS); i += 64)
 		tab[i] = 0;
 	__syncthreads();
 
 	uint32_t anchor = 0, op = 0;	/* wave-uniform */
 	if (n > LZ4C_MFLIMIT) {
-		const uint32_t mflimit = n - LZ4C_MFLIMIT;	/* last position a match may START at */
-		const uint32_t matchlimit = n - LZ4C_LASTLIT;	/* matches END at or before this */
-		uint32_t base = 0;
-		while (base <= mflimit) {
-			const uint32_t p = base + lane;
-			const bool valid = p <= mflimit;
-			uint32_t v = 0, cand = 0, mlen = 0;
-			bool ok = false;
-			if (valid) {
-				v = ld_u32(in + p);
-				const uint32_t h = (v * 2654435761u) >> (32 - LZ4C_HASH_BITS);
-				cand = tab[h];		/* every lane reads before any lane of this window writes */
+		/* matches start at or before n - 12 and end at or before n - 5 */
+		anchor = lz77_match(tab, in, n - LZ4C_MFLIMIT, n - LZ4C_LASTLIT, lane,
+		    [&](uint32_t pf, uint32_t mf, uint32_t cf, uint32_t anchor) {
+			const uint32_t lit = pf - anchor, off = pf - cf, ml = mf - 4u;
+			/* one sequence: token, literal length, literals, offset, match length */
+			if (lane == 0)
+				out[op] = (uint8_t)(((lit < 15u ? lit : 15u) << 4) | (ml < 15u ? ml : 15u));
+			op += 1;
+			if (lit >= 15u)
+				op += wave_put_len(out + op, lit, lane);
+			wave_copy(out + op, in + anchor, lit, lane);
+			op += lit;
+			if (lane == 0) {
+				out[op] = (uint8_t)off;
+				out[op + 1] = (uint8_t)(off >> 8);
 			}
-			__builtin_amdgcn_wave_barrier();
-			if (valid) {
-				const uint32_t h = (v * 2654435761u) >> (32 - LZ4C_HASH_BITS);
-				tab[h] = (uint16_t)p;
-				/* (position 0 doubles as "empty": a candidate is only taken if its bytes match) */
-				ok = cand < p && ld_u32(in + cand) == v;
-				if (ok) {
-					mlen = 4;
-					while (p + mlen + 8 <= matchlimit && ld_u64(in + p + mlen) == ld_u64(in + cand + mlen))
-						mlen += 8;
-					while (p + mlen < matchlimit && in[p + mlen] == in[cand + mlen])
-						mlen++;
-				}
-			}
-			uint64_t mask = __ballot(ok);
-			while (mask != 0) {
-				const uint32_t f = (uint32_t)__builtin_ctzll(mask);
-				mask &= mask - 1;
-				const uint32_t pf = base + f;
-				if (pf < anchor)
-					continue;	/* an earlier match of this window already covers it */
-				const uint32_t mf = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)f);
-				const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)cand, (int)f);
-				const uint32_t lit = pf - anchor, off = pf - cf, ml = mf - 4u;
-				/* one sequence: token, literal length, literals, offset, match length */
-				if (lane == 0)
-					out[op] = (uint8_t)(((lit < 15u ? lit : 15u) << 4) | (ml < 15u ? ml : 15u));
-				op += 1;
-				if (lit >= 15u)
-					op += wave_put_len(out + op, lit, lane);
-				wave_copy(out + op, in + anchor, lit, lane);
-				op += lit;
-				if (lane == 0) {
-					out[op] = (uint8_t)off;
-					out[op + 1] = (uint8_t)(off >> 8);
-				}
-				op += 2;
-				if (ml >= 15u)
-					op += wave_put_len(out + op, ml, lane);
-				anchor = pf + mf;
-			}
-			base = (base + 64 > anchor) ? base + 64 : anchor;
-		}
+			op += 2;
+			if (ml >= 15u)
+				op += wave_put_len(out + op, ml, lane);
+		});
 	}
 	/* last sequence: literals only (at least the block's last five bytes) */
 	{
@@ -166,11 +113,6 @@ __global__ __launch_bounds__(256) void lz4c_sizes_kernel(const uint32_t *__restr
 	if (i % bpf == bpf - 1 || i + 1 == n_blocks)
 		c += 4u + ((flags & LA_LZ4C_CONTENT_SUM) ? 4u : 0u);
 	contrib[i] = c;
-}
-
-__device__ __forceinline__ void st_le32(uint8_t *p, uint32_t v)
-{
-	p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
 }
 
 __global__ __launch_bounds__(256) void lz4_pack_frames_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
@@ -229,26 +171,47 @@ __global__ __launch_bounds__(256) void lz4_pack_frames_kernel(const uint8_t *__r
 	}
 }
 
-/* content checksum of every frame: XXH32 over its input bytes, four lanes per frame */
-__global__ __launch_bounds__(64) void lz4c_frame_sums_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
-    uint32_t block_size, uint32_t bpf, uint32_t n_frames, uint32_t *__restrict__ frame_sum)
+struct lz4c_xxh32 {
+	__device__ uint32_t operator()(const uint8_t *p, uint64_t len, uint32_t j) const { return xxh32_quad(p, (uint32_t)len, 0, (int)j); }
+};
+
+struct lz4c_ws {
+	uint8_t *tmp;
+	uint32_t *csize, *contrib, *fsum;
+	uint64_t *off;
+	void *scan;
+};
+
+/* the launcher's workspace on `base` (null: sizes only); returns its bytes before the scan scratch */
+static uint64_t lz4c_carve(lz4c_ws *w, uint8_t *base, uint64_t nb, uint64_t nf, uint32_t stride)
 {
-	const uint32_t q = (blockIdx.x * 64 + threadIdx.x) >> 2, j = threadIdx.x & 3;
-	const bool have = q < n_frames;
-	const uint64_t fo = (uint64_t)(have ? q : 0) * bpf * block_size;
-	const uint64_t fl = have ? (src_bytes - fo < (uint64_t)bpf * block_size ? src_bytes - fo : (uint64_t)bpf * block_size) : 0;
-	const uint32_t h = xxh32_quad(src + fo, (uint32_t)fl, 0, (int)j);
-	if (have && j == 0)
-		frame_sum[q] = h;
+	la_carve c = { base, 0 };
+	w->tmp = c.take<uint8_t>(nb * stride);
+	w->csize = c.take<uint32_t>(nb);
+	w->contrib = c.take<uint32_t>(nb);
+	w->off = c.take<uint64_t>(nb + 1);
+	w->fsum = c.take<uint32_t>(nf);
+	w->scan = c.take<uint8_t>(0, 256);
+	return c.off;
 }
+
+static uint32_t lz4c_stride(uint32_t block_size) { return (lz4c_bound(block_size) + 15u) & ~15u; }
 
 extern "C" uint64_t la_gpu_lz4_compress_workspace_bytes(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame)
 {
 	if (block_size == 0 || blocks_per_frame == 0)
 		return 0;
 	const uint64_t nb = (src_bytes + block_size - 1) / block_size, nf = (nb + blocks_per_frame - 1) / blocks_per_frame;
-	const uint64_t stride = (lz4c_bound(block_size) + 15u) & ~15ull;
-	return nb * stride + nb * 4 * 2 + (nb + 1) * 8 + nf * 4 + la_scan_scratch_bytes((uint32_t)nb) + 4096;
+	lz4c_ws w;
+	return lz4c_carve(&w, nullptr, nb, nf, lz4c_stride(block_size)) + la_scan_scratch_bytes((uint32_t)nb);
+}
+
+extern "C" uint64_t la_gpu_lz4_compress_bound(uint64_t src_bytes, uint32_t block_size, uint32_t bpf)
+{
+	if (block_size == 0 || bpf == 0)
+		return 0;
+	const uint64_t nb = (src_bytes + block_size - 1) / block_size, nf = (nb + bpf - 1) / bpf;
+	return src_bytes + nb * (block_size / 255u + 16u + 8u) + nf * 15u + 64u;
 }
 
 void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
@@ -256,25 +219,19 @@ void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_by
 {
 	const uint32_t nb = (uint32_t)((src_bytes + block_size - 1) / block_size);
 	const uint32_t nf = (nb + bpf - 1) / bpf;
-	const uint32_t stride = (lz4c_bound(block_size) + 15u) & ~15u;
-	uint64_t o = 0;
-	uint8_t *tmp = ws + o; o += (uint64_t)nb * stride;
-	uint32_t *csize = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
-	uint32_t *contrib = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
-	o = (o + 7) & ~7ull;
-	uint64_t *off = (uint64_t *)(ws + o); o += ((uint64_t)nb + 1) * 8;
-	uint32_t *fsum = (uint32_t *)(ws + o); o += (uint64_t)nf * 4;
-	o = (o + 255) & ~255ull;
-	void *scan = ws + o;
+	const uint32_t stride = lz4c_stride(block_size);
+	lz4c_ws w;
+	lz4c_carve(&w, ws, nb, nf, stride);
 	if (nb == 0) {
 		(void)hipMemsetAsync(d_out_bytes, 0, 8, s);
 		return;
 	}
-	hipLaunchKernelGGL(lz4_compress_blocks_kernel, dim3(nb), dim3(64), 0, s, d_src, src_bytes, block_size, nb, tmp, stride, csize);
+	hipLaunchKernelGGL(lz4_compress_blocks_kernel, dim3(nb), dim3(64), 0, s, d_src, src_bytes, block_size, nb, w.tmp, stride, w.csize);
 	if (flags & LA_LZ4C_CONTENT_SUM)
-		hipLaunchKernelGGL(lz4c_frame_sums_kernel, dim3((nf + 15) / 16), dim3(64), 0, s, d_src, src_bytes, block_size, bpf, nf, fsum);
-	hipLaunchKernelGGL(lz4c_sizes_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, csize, src_bytes, block_size, nb, bpf, flags, contrib);
-	la_launch_scan_u32(s, contrib, nb, off, scan);
+		hipLaunchKernelGGL(frame_sums_kernel<lz4c_xxh32>, dim3((nf + 15) / 16), dim3(64), 0, s, d_src, src_bytes,
+		    (uint64_t)bpf * block_size, nf, w.fsum);
+	hipLaunchKernelGGL(lz4c_sizes_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, w.csize, src_bytes, block_size, nb, bpf, flags, w.contrib);
+	la_launch_scan_u32(s, w.contrib, nb, w.off, w.scan);
 	hipLaunchKernelGGL(lz4_pack_frames_kernel, dim3(nb), dim3(256), 0, s, d_src, src_bytes, block_size, nb, bpf, flags,
-	    tmp, stride, csize, off, fsum, d_out, out_cap, d_out_bytes);
+	    w.tmp, stride, w.csize, w.off, w.fsum, d_out, out_cap, d_out_bytes);
 }

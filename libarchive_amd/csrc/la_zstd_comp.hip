@@ -13,8 +13,8 @@
  * never used (every sequence writes Offset_Value = offset + 3), every block states its own tables.  So all blocks of
  * all frames run in parallel:
  *   zstd_compress_blocks_kernel   ONE WAVE per block.  A block whose bytes are all equal is an RLE_Block.  Otherwise
- *       the LZ77 matcher of lz4_compress_blocks_kernel: 64 positions per step, a 4096-entry table of 32-bit positions
- *       in LDS (16 KiB), 4-byte minimum match at any offset inside the block, matches verified and extended, taken
+ *       the LZ77 matcher of lz4_compress_blocks_kernel (lz77_match, la_comp_common.h): 64 positions per step, a
+ *       4096-entry table of 32-bit positions in LDS (16 KiB), 4-byte minimum match at any offset inside the block, matches verified and extended, taken
  *       in position order with ballot; literals and sequences (ll, ml, offset) go to the workspace.
  *       Literals section: RLE when all literals are one byte; Raw under LA_ZSTDC_RAW_LITERALS, for fewer than 32
  *       literals or a largest byte above 128; otherwise Huffman: an LDS histogram, Shannon lengths clamped to 11 bits
@@ -22,21 +22,20 @@
  *       direct 4-bit weights, one stream up to 1023 literals and four with the jump table above.  Streams are encoded
  *       in parallel: every literal's bit position is a wave prefix sum of code lengths (reverse symbol order, a
  *       Huffman stream is read backwards), lanes OR their bits into an LDS stage and whole dwords leave
- *       (deflate_fixed_kernel's scheme).  Sections whose coded form would not be smaller are written raw.
+ *       (wave_bits_append, shared with deflate_fixed_kernel).  Sections whose coded form would not be smaller are written raw.
  *       Sequences section: Predefined_Mode for LL, OF and ML; the interleaved FSE stream is written last sequence
  *       first, uniformly by the wave (64 sequences' codes and extra bits computed lane-parallel, then taken one by
  *       one with v_readlane), with encoder tables (symbol x next state -> state) spread from the decoder's own
  *       fse_build in LDS.  A block whose compressed form is not smaller than its input is a Raw_Block.
- *   zstdc_frame_sums_kernel       XXH64 of every frame's input, four lanes per frame.
+ *   frame_sums_kernel             XXH64 of every frame's input (la_comp_common.h), four lanes per frame.
  *   zstdc_sizes_kernel / scan     stream bytes of every block (header + payload, frame header and checksum).
  *   zstd_pack_frames_kernel       one workgroup per block: frame header, block header, payload, checksum.
  * LDS per wave: 16 KiB table (the FSE tables reuse it after matching) + 1.8 KiB histogram / code / stage:
  * 8 waves per CU by LDS.
  */
-#include "la_dev.h"
+#include "la_comp_common.h"
 #include "la_zstd_common.h"
 
-#define ZC_HASH_BITS 12
 #define ZC_MINMATCH  4u
 #define ZC_BLOCK_MAX 131072u
 #define ZC_RAW_LIT_MIN 32u	/* fewer literals than this are never worth a Huffman table */
@@ -53,7 +52,7 @@ struct zc_fse_lds {
 };
 struct zc_lds {
 	union {
-		uint32_t tab[1u << ZC_HASH_BITS];
+		uint32_t tab[1u << LZ77_HASH_BITS];
 		zc_fse_lds f;
 	} u;
 	uint32_t hist[256];
@@ -62,20 +61,7 @@ struct zc_lds {
 	uint32_t wcnt[16];
 	uint32_t stage[32];
 };
-static_assert(sizeof(zc_fse_lds) <= sizeof(uint32_t) * (1u << ZC_HASH_BITS), "FSE tables must fit in the match table");
-
-__device__ __forceinline__ uint64_t zc_ld64(const uint8_t *p)
-{
-	uint64_t v;
-	__builtin_memcpy(&v, p, 8);
-	return v;
-}
-
-__device__ __forceinline__ void zc_copy(uint8_t *d, const uint8_t *s, uint32_t n, uint32_t lane)
-{
-	for (uint32_t i = lane; i < n; i += 64)
-		d[i] = s[i];
-}
+static_assert(sizeof(zc_fse_lds) <= sizeof(uint32_t) * (1u << LZ77_HASH_BITS), "FSE tables must fit in the match table");
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
@@ -145,40 +131,8 @@ __device__ static uint32_t huf_stream_enc(zc_lds &L, const uint8_t *lits, uint32
 			nb = L.len[s];
 			bits = L.code[s];
 		}
-		uint32_t inc = nb;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t t = __shfl_up(inc, d, 64);
-			if ((int)lane >= d) inc += t;
-		}
-		const uint32_t total = __shfl(inc, 63, 64);
-		const uint32_t at = (uint32_t)(bp & 31u) + inc - nb;
-		if (nb) {
-			const uint64_t w = (uint64_t)bits << (at & 31u);
-			atomicOr(&L.stage[at >> 5], (uint32_t)w);
-			if ((uint32_t)(w >> 32))
-				atomicOr(&L.stage[(at >> 5) + 1], (uint32_t)(w >> 32));
-		}
-		__builtin_amdgcn_wave_barrier();
-		/* whole dwords leave (64 x 11 + 31 bits: at most 22 of them); the partial one stays in front */
-		const uint32_t nd = ((uint32_t)(bp & 31u) + total) >> 5;
-		const uint64_t g0 = (bp >> 5) * 4u;
-		uint32_t mine = 0;
-		const uint32_t carry = L.stage[nd];
-		if (lane < nd)
-			mine = L.stage[lane];
-		__builtin_amdgcn_wave_barrier();
-		if (lane < nd) {
-			uint8_t *d = out + g0 + 4u * lane;
-			d[0] = (uint8_t)mine; d[1] = (uint8_t)(mine >> 8); d[2] = (uint8_t)(mine >> 16); d[3] = (uint8_t)(mine >> 24);
-		}
-		if (lane <= nd)
-			L.stage[lane] = 0;
-		__builtin_amdgcn_wave_barrier();
-		if (lane == 0)
-			L.stage[0] = carry;
-		__builtin_amdgcn_wave_barrier();
-		bp += total;
+		/* whole dwords leave (64 x 11 + 31 bits: at most 22 of them), four bytes each: the destination is not aligned */
+		bp += wave_bits_append(bp, bits, nb, L.stage, lane, [&](uint32_t i, uint32_t w) { st_le32(out + 4u * i, w); });
 		e -= cnt;
 	}
 	/* end mark, then the last bytes */
@@ -208,8 +162,7 @@ __device__ __forceinline__ void bw_put(zc_bw &w, uint32_t v, uint32_t nb, uint32
 		if (w.op + 4u > w.cap) {
 			w.over = true;
 		} else if (lane == 0) {
-			const uint32_t x = (uint32_t)w.acc;
-			w.out[w.op] = (uint8_t)x; w.out[w.op + 1] = (uint8_t)(x >> 8); w.out[w.op + 2] = (uint8_t)(x >> 16); w.out[w.op + 3] = (uint8_t)(x >> 24);
+			st_le32(w.out + w.op, (uint32_t)w.acc);
 		}
 		w.op += 4u;
 		w.acc >>= 32;
@@ -255,7 +208,7 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 		}
 	}
 
-	for (uint32_t i = lane; i < (1u << ZC_HASH_BITS); i += 64)
+	for (uint32_t i = lane; i < (1u << LZ77_HASH_BITS); i += 64)
 		L.u.tab[i] = 0;
 	for (uint32_t i = lane; i < 256; i += 64)
 		L.hist[i] = 0;
@@ -264,52 +217,17 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 	/* ---- matching: sequences and literals ---- */
 	uint32_t anchor = 0, nseq = 0, nlit = 0;	/* wave-uniform */
 	if (n >= ZC_MINMATCH) {
-		const uint32_t plast = n - ZC_MINMATCH;	/* last position a match may start at */
-		uint32_t base = 0;
-		while (base <= plast) {
-			const uint32_t p = base + lane;
-			const bool valid = p <= plast;
-			uint32_t v = 0, cand = 0, mlen = 0;
-			bool ok = false;
-			const uint32_t h = valid ? ((ld_u32(in + p) * 2654435761u) >> (32 - ZC_HASH_BITS)) : 0u;
-			if (valid) {
-				v = ld_u32(in + p);
-				cand = L.u.tab[h];	/* every lane reads before any lane of this window writes */
-			}
-			__builtin_amdgcn_wave_barrier();
-			if (valid) {
-				L.u.tab[h] = p;
-				/* (position 0 doubles as "empty": a candidate is only taken if its bytes match) */
-				ok = cand < p && ld_u32(in + cand) == v;
-				if (ok) {
-					mlen = 4;
-					while (p + mlen + 8u <= n && zc_ld64(in + p + mlen) == zc_ld64(in + cand + mlen))
-						mlen += 8;
-					while (p + mlen < n && in[p + mlen] == in[cand + mlen])
-						mlen++;
-				}
-			}
-			uint64_t mask = __ballot(ok);
-			while (mask != 0) {
-				const uint32_t f = (uint32_t)__builtin_ctzll(mask);
-				mask &= mask - 1;
-				const uint32_t pf = base + f;
-				if (pf < anchor)
-					continue;	/* an earlier match of this window already covers it */
-				const uint32_t mf = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)f);
-				const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)cand, (int)f);
-				const uint32_t lit = pf - anchor;
-				zc_copy(lits + nlit, in + anchor, lit, lane);
-				if (lane == 0)
-					seqs[nseq] = (uint64_t)lit | ((uint64_t)mf << 20) | ((uint64_t)(pf - cf) << 40);
-				nlit += lit;
-				nseq++;
-				anchor = pf + mf;
-			}
-			base = (base + 64 > anchor) ? base + 64 : anchor;
-		}
+		/* matches start at or before n - 4 and may run to the block's end */
+		anchor = lz77_match(L.u.tab, in, n - ZC_MINMATCH, n, lane, [&](uint32_t pf, uint32_t mf, uint32_t cf, uint32_t anchor) {
+			const uint32_t lit = pf - anchor;
+			wave_copy(lits + nlit, in + anchor, lit, lane);
+			if (lane == 0)
+				seqs[nseq] = (uint64_t)lit | ((uint64_t)mf << 20) | ((uint64_t)(pf - cf) << 40);
+			nlit += lit;
+			nseq++;
+		});
 	}
-	zc_copy(lits + nlit, in + anchor, n - anchor, lane);
+	wave_copy(lits + nlit, in + anchor, n - anchor, lane);
 	nlit += n - anchor;
 	__syncthreads();	/* literals and sequences are in the workspace */
 
@@ -471,7 +389,7 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 	}
 	if (!lit_done) {	/* Raw_Literals_Block */
 		op = lit_hdr_rr(out, 0, nlit, lane == 0);
-		zc_copy(out + op, lits, nlit, lane);
+		wave_copy(out + op, lits, nlit, lane);
 		op += nlit;
 	}
 	__syncthreads();	/* the FSE tables below reuse the match table */
@@ -612,17 +530,9 @@ __device__ static uint64_t xxh64_quad(const uint8_t *p, uint64_t len, uint32_t j
 	return h;
 }
 
-__global__ __launch_bounds__(64) void zstdc_frame_sums_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
-    uint64_t frame_bytes, uint32_t n_frames, uint32_t *__restrict__ frame_sum)
-{
-	const uint32_t q = (blockIdx.x * 64 + threadIdx.x) >> 2, j = threadIdx.x & 3u;
-	const bool have = q < n_frames;
-	const uint64_t fo = have ? (uint64_t)q * frame_bytes : 0;
-	const uint64_t fl = have && src_bytes > fo ? (src_bytes - fo < frame_bytes ? src_bytes - fo : frame_bytes) : 0;
-	const uint64_t h = xxh64_quad(src + fo, fl, j);
-	if (have && j == 0)
-		frame_sum[q] = (uint32_t)h;
-}
+struct zc_xxh64 {
+	__device__ uint32_t operator()(const uint8_t *p, uint64_t len, uint32_t j) const { return (uint32_t)xxh64_quad(p, len, j); }
+};
 
 __host__ __device__ static inline uint32_t zc_fcs_len(uint64_t fcs) { return fcs < 256u ? 1u : fcs < 65536u + 256u ? 2u : 4u; }
 
@@ -668,7 +578,7 @@ __global__ __launch_bounds__(256) void zstd_pack_frames_kernel(const uint8_t *__
 		const uint32_t fl = zc_fcs_len(fcs);
 		if (tid == 0) {
 			/* magic; FHD: FCS_Field_Size flag, Single_Segment_Flag, Content_Checksum_Flag, no dictionary */
-			out[o] = 0x28; out[o + 1] = 0xB5; out[o + 2] = 0x2F; out[o + 3] = 0xFD;
+			st_le32(out + o, 0xFD2FB528u);
 			out[o + 4] = (uint8_t)((fl == 1u ? 0u : fl == 2u ? 0x40u : 0x80u) | 0x20u | ((flags & LA_ZSTDC_CHECKSUM) ? 4u : 0u));
 			const uint64_t v = fl == 2u ? fcs - 256u : fcs;
 			for (uint32_t k = 0; k < fl; k++)
@@ -685,21 +595,42 @@ __global__ __launch_bounds__(256) void zstd_pack_frames_kernel(const uint8_t *__
 	for (uint32_t i = tid; i < pay; i += 256)
 		out[o + i] = payload[i];
 	o += pay;
-	if (last && (flags & LA_ZSTDC_CHECKSUM) && tid == 0) {
-		const uint32_t c = frame_sum[bi / bpf];
-		out[o] = (uint8_t)c; out[o + 1] = (uint8_t)(c >> 8); out[o + 2] = (uint8_t)(c >> 16); out[o + 3] = (uint8_t)(c >> 24);
-	}
+	if (last && (flags & LA_ZSTDC_CHECKSUM) && tid == 0)
+		st_le32(out + o, frame_sum[bi / bpf]);
 }
 
 static uint64_t zc_blocks(uint64_t src_bytes, uint32_t bs) { return src_bytes ? (src_bytes + bs - 1) / bs : 1u; }
+
+struct zc_ws {
+	uint8_t *tmp, *lits;
+	uint64_t *seqs, *off;
+	uint32_t *btype, *csize, *contrib, *fsum;
+	void *scan;
+};
+
+/* the launcher's workspace on `base` (null: sizes only); returns its bytes before the scan scratch */
+static uint64_t zc_carve(zc_ws *w, uint8_t *base, uint64_t nb, uint64_t nf, uint32_t bs)
+{
+	la_carve c = { base, 0 };
+	w->tmp = c.take<uint8_t>(nb * zc_tmp_stride(bs));
+	w->lits = c.take<uint8_t>(nb * zc_lit_stride(bs));
+	w->seqs = c.take<uint64_t>(nb * zc_seq_stride(bs) / 8u);
+	w->btype = c.take<uint32_t>(nb);
+	w->csize = c.take<uint32_t>(nb);
+	w->contrib = c.take<uint32_t>(nb);
+	w->off = c.take<uint64_t>(nb + 1);
+	w->fsum = c.take<uint32_t>(nf);
+	w->scan = c.take<uint8_t>(0, 256);
+	return c.off;
+}
 
 extern "C" uint64_t la_gpu_zstd_compress_workspace_bytes(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame)
 {
 	if (block_size == 0 || block_size > ZC_BLOCK_MAX || blocks_per_frame == 0)
 		return 0;
 	const uint64_t nb = zc_blocks(src_bytes, block_size), nf = (nb + blocks_per_frame - 1) / blocks_per_frame;
-	return nb * (zc_tmp_stride(block_size) + zc_lit_stride(block_size) + zc_seq_stride(block_size)) + nb * 4 * 3 +
-	    (nb + 1) * 8 + nf * 4 + la_scan_scratch_bytes((uint32_t)nb) + 4096;
+	zc_ws w;
+	return zc_carve(&w, nullptr, nb, nf, block_size) + la_scan_scratch_bytes((uint32_t)nb);
 }
 
 extern "C" uint64_t la_gpu_zstd_compress_bound(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame)
@@ -715,26 +646,15 @@ void la_launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 {
 	const uint32_t nb = (uint32_t)zc_blocks(src_bytes, block_size);
 	const uint32_t nf = (nb + bpf - 1) / bpf;
-	uint64_t o = 0;
-	uint8_t *tmp = ws + o; o += (uint64_t)nb * zc_tmp_stride(block_size);
-	uint8_t *lits = ws + o; o += (uint64_t)nb * zc_lit_stride(block_size);
-	o = (o + 7) & ~7ull;
-	uint64_t *seqs = (uint64_t *)(ws + o); o += (uint64_t)nb * zc_seq_stride(block_size);
-	uint32_t *btype = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
-	uint32_t *csize = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
-	uint32_t *contrib = (uint32_t *)(ws + o); o += (uint64_t)nb * 4;
-	o = (o + 7) & ~7ull;
-	uint64_t *off = (uint64_t *)(ws + o); o += ((uint64_t)nb + 1) * 8;
-	uint32_t *fsum = (uint32_t *)(ws + o); o += (uint64_t)nf * 4;
-	o = (o + 255) & ~255ull;
-	void *scan = ws + o;
+	zc_ws w;
+	zc_carve(&w, ws, nb, nf, block_size);
 	hipLaunchKernelGGL(zstd_compress_blocks_kernel, dim3(nb), dim3(64), 0, s, d_src, src_bytes, block_size, nb, flags,
-	    tmp, lits, seqs, btype, csize);
+	    w.tmp, w.lits, w.seqs, w.btype, w.csize);
 	if (flags & LA_ZSTDC_CHECKSUM)
-		hipLaunchKernelGGL(zstdc_frame_sums_kernel, dim3((nf + 15) / 16), dim3(64), 0, s, d_src, src_bytes,
-		    (uint64_t)bpf * block_size, nf, fsum);
-	hipLaunchKernelGGL(zstdc_sizes_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, csize, src_bytes, block_size, nb, bpf, flags, contrib);
-	la_launch_scan_u32(s, contrib, nb, off, scan);
+		hipLaunchKernelGGL(frame_sums_kernel<zc_xxh64>, dim3((nf + 15) / 16), dim3(64), 0, s, d_src, src_bytes,
+		    (uint64_t)bpf * block_size, nf, w.fsum);
+	hipLaunchKernelGGL(zstdc_sizes_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, w.csize, src_bytes, block_size, nb, bpf, flags, w.contrib);
+	la_launch_scan_u32(s, w.contrib, nb, w.off, w.scan);
 	hipLaunchKernelGGL(zstd_pack_frames_kernel, dim3(nb), dim3(256), 0, s, d_src, src_bytes, block_size, nb, bpf, flags,
-	    tmp, btype, csize, off, fsum, d_out, out_cap, d_out_bytes);
+	    w.tmp, w.btype, w.csize, w.off, w.fsum, d_out, out_cap, d_out_bytes);
 }

@@ -26,7 +26,9 @@
  *
  * The write core below is the minimum the filters need outside libarchive: archive_write_new,
  * _add_filter_lz4, _set_format_raw (one entry, data passed through: archive_write_set_format_raw.c),
- * _set_filter_option, _open_memory / _open_fd, _header, _data, _close, _free.
+ * _set_filter_option, _open_memory / _open_fd, _header, _data, _close, _free.  Next to it, the write window
+ * (la_write_private.h) that the lz4, gzip and zstd filters share: each filter adds its output bound and its one
+ * compress call.
  */
 #include <errno.h>
 #include <stdint.h>
@@ -243,28 +245,116 @@ int archive_write_free(struct archive *_a)
 	return rc;
 }
 
+/* ------------------------------------------------------------------ the write window */
+
+int la_write_window_fail(struct archive_write_filter *f, const char *what)
+{
+	const struct la_write_window *w = f->data;
+	archive_set_error(f->archive, ARCHIVE_ERRNO_MISC, "%s GPU data plane: %s failed: %s", w->name, what,
+	    w->gpu ? la_gpu_last_error(w->gpu) : "no device");
+	return ARCHIVE_FATAL;
+}
+
+int la_write_window_flush(struct archive_write_filter *f, int force_empty)
+{
+	struct la_write_window *w = f->data;
+	if (w->len == 0 && !force_empty)
+		return ARCHIVE_OK;
+	/* buffers for a full window, at first use */
+	if (w->d_in == NULL && w->len && la_gpu_malloc(w->gpu, &w->d_in, w->cap) != LA_OK)
+		return la_write_window_fail(f, "device allocation");
+	if (w->out == NULL) {
+		const uint64_t cap = w->bound(f, w->cap);
+		void *hp = NULL;
+		if ((w->d_out == NULL && la_gpu_malloc(w->gpu, &w->d_out, cap) != LA_OK) || la_gpu_malloc_host(w->gpu, &hp, cap) != LA_OK)
+			return la_write_window_fail(f, "output allocation");
+		w->out = hp; w->out_cap = cap;
+	}
+	if (w->d_len == NULL && la_gpu_malloc(w->gpu, &w->d_len, 64) != LA_OK)
+		return la_write_window_fail(f, "device allocation");
+	uint64_t total = 0;
+	if ((w->len && la_gpu_memcpy_h2d(w->gpu, w->d_in, w->win, w->len) != LA_OK) ||
+	    w->compress(f, w) != LA_OK ||
+	    la_gpu_memcpy_d2h(w->gpu, &total, w->d_len, sizeof(total)) != LA_OK ||
+	    la_gpu_sync(w->gpu) != LA_OK)
+		return la_write_window_fail(f, "compress");
+	if (total > w->out_cap)
+		return la_write_window_fail(f, "compress (output bound)");
+	if (la_gpu_memcpy_d2h(w->gpu, w->out, w->d_out, total) != LA_OK || la_gpu_sync(w->gpu) != LA_OK)
+		return la_write_window_fail(f, "device to host copy");
+	w->len = 0;
+	w->wrote_anything = 1;
+	return __archive_write_filter(f->next_filter, w->out, (size_t)total);
+}
+
+static int window_write(struct archive_write_filter *f, const void *buff, size_t length)
+{
+	struct la_write_window *w = f->data;
+	const uint8_t *p = buff;
+	while (length) {
+		size_t n = w->cap - w->len;
+		if (n > length) n = length;
+		memcpy(w->win + w->len, p, n);
+		w->len += n; p += n; length -= n;
+		if (w->len == w->cap) {
+			int r = la_write_window_flush(f, 0);
+			if (r != ARCHIVE_OK)
+				return r;
+		}
+	}
+	return ARCHIVE_OK;
+}
+
+int la_write_window_open(struct archive_write_filter *f, size_t unit)
+{
+	struct la_write_window *w = f->data;
+	const char *wm = getenv("LA_GPU_WRITE_WINDOW_MIB");
+	if (la_gpu_open(la_env_device(), &w->gpu) != LA_OK) {
+		archive_set_error(f->archive, ARCHIVE_ERRNO_MISC,
+		    "Can't initialize %s GPU data plane (no usable gfx950 device); no CPU fallback is built", w->name);
+		return ARCHIVE_FATAL;
+	}
+	w->cap = ((size_t)(wm && atoi(wm) > 0 ? atoi(wm) : 64) << 20) / unit * unit;
+	if (w->cap == 0)
+		w->cap = unit;
+	void *hp = NULL;
+	if (la_gpu_malloc_host(w->gpu, &hp, w->cap) != LA_OK)
+		return la_write_window_fail(f, "pinned window allocation");
+	w->win = hp;
+	f->write = window_write;
+	return ARCHIVE_OK;
+}
+
+int la_write_window_free(struct archive_write_filter *f)
+{
+	struct la_write_window *w = f->data;
+	if (w) {
+		if (w->gpu) {
+			la_gpu_sync(w->gpu);
+			if (w->win) la_gpu_free_host(w->gpu, w->win);
+			if (w->out) la_gpu_free_host(w->gpu, w->out);
+			if (w->d_in) la_gpu_free(w->gpu, w->d_in);
+			if (w->d_out) la_gpu_free(w->gpu, w->d_out);
+			if (w->d_len) la_gpu_free(w->gpu, w->d_len);
+			la_gpu_close(w->gpu);
+		}
+		free(w);
+	}
+	f->data = NULL;
+	return ARCHIVE_OK;
+}
+
 /* ------------------------------------------------------------------ the lz4 write filter */
 
 #define LZ4W_BLOCK 65536u
 #define LZ4W_BPF   16u
 #define GZW_CHUNK  49152u
 
-struct lz4w_private {	/* archive_write_add_filter_lz4.c:49-68; the gzip filter shares the window machinery */
-	int kind;		/* 0 = lz4, 1 = gzip */
-	int timestamp;		/* gzip: > 0 writes time(NULL) into the member headers (archive_write_add_filter_gzip.c:213-220) */
-	uint32_t mtime;
+struct lz4w_private {	/* archive_write_add_filter_lz4.c:49-68 */
+	struct la_write_window w;	/* first */
 	int compression_level;
 	unsigned block_independence:1, block_checksum:1, stream_checksum:1;
 	unsigned block_maximum_size:3;
-	la_gpu_ctx *gpu;
-	uint8_t *win;		/* pinned input window */
-	size_t win_cap, win_len;
-	uint8_t *out;		/* pinned output of one window */
-	size_t out_cap;
-	void *d_in, *d_out, *d_len;
-	size_t d_in_cap, d_out_cap;
-	int wrote_anything;
-	int64_t total_in;
 };
 
 static int lz4w_options(struct archive_write_filter *f, const char *key, const char *value)
@@ -294,115 +384,29 @@ static int lz4w_options(struct archive_write_filter *f, const char *key, const c
 	return ARCHIVE_WARN;
 }
 
-static int lz4w_gpu_fail(struct archive_write_filter *f, struct lz4w_private *d, const char *what)
-{
-	archive_set_error(f->archive, ARCHIVE_ERRNO_MISC, "%s GPU data plane: %s failed: %s", d->kind ? "gzip" : "lz4", what,
-	    d->gpu ? la_gpu_last_error(d->gpu) : "no device");
-	return ARCHIVE_FATAL;
-}
+static uint64_t lz4w_bound(struct archive_write_filter *f, uint64_t n) { (void)f; return la_gpu_lz4_compress_bound(n, LZ4W_BLOCK, LZ4W_BPF); }
 
-/* compress the window and hand the frames to the next filter */
-static int lz4w_flush_window(struct archive_write_filter *f, struct lz4w_private *d)
+static int lz4w_compress(struct archive_write_filter *f, const struct la_write_window *w)
 {
-	if (d->win_len == 0)
-		return ARCHIVE_OK;
-	const uint32_t flags = (d->block_checksum ? LA_LZ4C_BLOCK_SUM : 0) | (d->stream_checksum ? LA_LZ4C_CONTENT_SUM : 0);
-	const uint64_t bound = d->kind ? la_gpu_gzip_compress_bound(d->win_len, GZW_CHUNK) : la_gpu_lz4_compress_bound(d->win_len, LZ4W_BLOCK, LZ4W_BPF);
-	if (d->d_in_cap < d->win_len) {
-		if (d->d_in) la_gpu_free(d->gpu, d->d_in);
-		d->d_in = NULL; d->d_in_cap = 0;
-		if (la_gpu_malloc(d->gpu, &d->d_in, d->win_cap) != LA_OK)
-			return lz4w_gpu_fail(f, d, "device allocation");
-		d->d_in_cap = d->win_cap;
-	}
-	if (d->d_out_cap < bound) {
-		if (d->d_out) la_gpu_free(d->gpu, d->d_out);
-		if (d->out) la_gpu_free_host(d->gpu, d->out);
-		d->d_out = NULL; d->out = NULL; d->d_out_cap = d->out_cap = 0;
-		const uint64_t cap = d->kind ? la_gpu_gzip_compress_bound(d->win_cap, GZW_CHUNK) : la_gpu_lz4_compress_bound(d->win_cap, LZ4W_BLOCK, LZ4W_BPF);
-		void *hp = NULL;
-		if (la_gpu_malloc(d->gpu, &d->d_out, cap) != LA_OK || la_gpu_malloc_host(d->gpu, &hp, cap) != LA_OK)
-			return lz4w_gpu_fail(f, d, "output allocation");
-		d->out = hp; d->d_out_cap = d->out_cap = cap;
-	}
-	if (d->d_len == NULL && la_gpu_malloc(d->gpu, &d->d_len, 64) != LA_OK)
-		return lz4w_gpu_fail(f, d, "device allocation");
+	const struct lz4w_private *d = f->data;
 	la_lz4c_batch bt;
 	memset(&bt, 0, sizeof(bt));
-	bt.d_src = d->d_in; bt.src_bytes = d->win_len;
-	bt.block_size = LZ4W_BLOCK; bt.blocks_per_frame = LZ4W_BPF; bt.flags = flags;
-	bt.d_out = d->d_out; bt.out_cap = d->d_out_cap; bt.d_out_bytes = d->d_len;
-	la_gzc_batch gt;
-	memset(&gt, 0, sizeof(gt));
-	gt.d_src = d->d_in; gt.src_bytes = d->win_len; gt.chunk_bytes = GZW_CHUNK; gt.mtime = d->mtime;
-	gt.d_out = d->d_out; gt.out_cap = d->d_out_cap; gt.d_out_bytes = d->d_len;
-	uint64_t total = 0;
-	if (la_gpu_memcpy_h2d(d->gpu, d->d_in, d->win, d->win_len) != LA_OK ||
-	    (d->kind ? la_gpu_gzip_compress(d->gpu, &gt) : la_gpu_lz4_compress(d->gpu, &bt)) != LA_OK ||
-	    la_gpu_memcpy_d2h(d->gpu, &total, d->d_len, sizeof(total)) != LA_OK ||
-	    la_gpu_sync(d->gpu) != LA_OK)
-		return lz4w_gpu_fail(f, d, "compress");
-	if (total > d->out_cap)
-		return lz4w_gpu_fail(f, d, "compress (output bound)");
-	if (la_gpu_memcpy_d2h(d->gpu, d->out, d->d_out, total) != LA_OK || la_gpu_sync(d->gpu) != LA_OK)
-		return lz4w_gpu_fail(f, d, "device to host copy");
-	d->win_len = 0;
-	d->wrote_anything = 1;
-	return __archive_write_filter(f->next_filter, d->out, (size_t)total);
+	bt.d_src = w->d_in; bt.src_bytes = w->len;
+	bt.block_size = LZ4W_BLOCK; bt.blocks_per_frame = LZ4W_BPF;
+	bt.flags = (d->block_checksum ? LA_LZ4C_BLOCK_SUM : 0) | (d->stream_checksum ? LA_LZ4C_CONTENT_SUM : 0);
+	bt.d_out = w->d_out; bt.out_cap = w->out_cap; bt.d_out_bytes = w->d_len;
+	return la_gpu_lz4_compress(w->gpu, &bt);
 }
 
-static int lz4w_write(struct archive_write_filter *f, const void *buff, size_t length)
-{
-	struct lz4w_private *d = f->data;
-	const uint8_t *p = buff;
-	d->total_in += (int64_t)length;
-	while (length) {
-		size_t n = d->win_cap - d->win_len;
-		if (n > length) n = length;
-		memcpy(d->win + d->win_len, p, n);
-		d->win_len += n; p += n; length -= n;
-		if (d->win_len == d->win_cap) {
-			int r = lz4w_flush_window(f, d);
-			if (r != ARCHIVE_OK)
-				return r;
-		}
-	}
-	return ARCHIVE_OK;
-}
-
-static int lz4w_open(struct archive_write_filter *f)
-{
-	struct lz4w_private *d = f->data;
-	const char *wm = getenv("LA_GPU_WRITE_WINDOW_MIB");
-	if (la_gpu_open(la_env_device(), &d->gpu) != LA_OK) {
-		archive_set_error(f->archive, ARCHIVE_ERRNO_MISC,
-		    "Can't initialize %s GPU data plane (no usable gfx950 device); no CPU fallback is built", d->kind ? "gzip" : "lz4");
-		return ARCHIVE_FATAL;
-	}
-	d->win_cap = (size_t)(wm && atoi(wm) > 0 ? atoi(wm) : 64) << 20;	/* (a multiple of the 1 MiB frame) */
-	void *hp = NULL;
-	if (la_gpu_malloc_host(d->gpu, &hp, d->win_cap) != LA_OK)
-		return lz4w_gpu_fail(f, d, "pinned window allocation");
-	d->win = hp;
-	if (d->kind && d->timestamp >= 0)
-		d->mtime = (uint32_t)time(NULL);
-	f->write = lz4w_write;
-	return ARCHIVE_OK;
-}
+static int lz4w_open(struct archive_write_filter *f) { return la_write_window_open(f, 1); }	/* (64 MiB: whole 1 MiB frames) */
 
 static int lz4w_close(struct archive_write_filter *f)
 {
 	struct lz4w_private *d = f->data;
-	if (d->gpu == NULL)
+	if (d->w.gpu == NULL)
 		return ARCHIVE_OK;
-	int r = lz4w_flush_window(f, d);
-	if (r == ARCHIVE_OK && !d->wrote_anything && d->kind) {
-		/* nothing was written: one member with an empty deflate stream, as zlib's Z_FINISH on no input gives
-		 * the reference (header, 03 00, crc 0, isize 0) */
-		const uint8_t m[20] = { 0x1f, 0x8b, 8, 0, (uint8_t)d->mtime, (uint8_t)(d->mtime >> 8), (uint8_t)(d->mtime >> 16),
-		    (uint8_t)(d->mtime >> 24), 0, 3, 0x03, 0x00, 0, 0, 0, 0, 0, 0, 0, 0 };
-		r = __archive_write_filter(f->next_filter, m, sizeof(m));
-	} else if (r == ARCHIVE_OK && !d->wrote_anything) {
+	int r = la_write_window_flush(f, 0);
+	if (r == ARCHIVE_OK && !d->w.wrote_anything) {
 		/* nothing was written: one empty frame (header, EndMark, checksum of nothing), as the
 		 * reference's close does (archive_write_add_filter_lz4.c:300-330) */
 		uint8_t h[15];
@@ -421,25 +425,6 @@ static int lz4w_close(struct archive_write_filter *f)
 	return r;
 }
 
-static int lz4w_free(struct archive_write_filter *f)
-{
-	struct lz4w_private *d = f->data;
-	if (d) {
-		if (d->gpu) {
-			la_gpu_sync(d->gpu);
-			if (d->win) la_gpu_free_host(d->gpu, d->win);
-			if (d->out) la_gpu_free_host(d->gpu, d->out);
-			if (d->d_in) la_gpu_free(d->gpu, d->d_in);
-			if (d->d_out) la_gpu_free(d->gpu, d->d_out);
-			if (d->d_len) la_gpu_free(d->gpu, d->d_len);
-			la_gpu_close(d->gpu);
-		}
-		free(d);
-	}
-	f->data = NULL;
-	return ARCHIVE_OK;
-}
-
 int archive_write_add_filter_lz4(struct archive *_a)
 {
 	struct archive_write_filter *f = __archive_write_allocate_filter(_a);
@@ -449,6 +434,9 @@ int archive_write_add_filter_lz4(struct archive *_a)
 		archive_set_error(_a, ENOMEM, "Out of memory");
 		return ARCHIVE_FATAL;
 	}
+	d->w.name = "lz4";
+	d->w.bound = lz4w_bound;
+	d->w.compress = lz4w_compress;
 	d->compression_level = 1;
 	d->block_independence = 1;
 	d->block_checksum = 0;
@@ -458,7 +446,7 @@ int archive_write_add_filter_lz4(struct archive *_a)
 	f->options = lz4w_options;
 	f->open = lz4w_open;
 	f->close = lz4w_close;
-	f->free = lz4w_free;
+	f->free = la_write_window_free;
 	f->code = ARCHIVE_FILTER_LZ4;
 	f->name = "lz4";
 	return ARCHIVE_OK;
@@ -466,9 +454,16 @@ int archive_write_add_filter_lz4(struct archive *_a)
 
 /* ------------------------------------------------------------------ the gzip write filter */
 
+struct gzw_private {	/* archive_write_add_filter_gzip.c:58-60 */
+	struct la_write_window w;	/* first */
+	int compression_level;
+	int timestamp;		/* > 0 writes time(NULL) into the member headers (archive_write_add_filter_gzip.c:213-220) */
+	uint32_t mtime;
+};
+
 static int gzw_options(struct archive_write_filter *f, const char *key, const char *value)
 {
-	struct lz4w_private *d = f->data;
+	struct gzw_private *d = f->data;
 	if (strcmp(key, "compression-level") == 0) {	/* archive_write_add_filter_gzip.c:147-153 */
 		if (value == NULL || !(value[0] >= '0' && value[0] <= '9') || value[1] != '\0')
 			return ARCHIVE_WARN;
@@ -482,22 +477,61 @@ static int gzw_options(struct archive_write_filter *f, const char *key, const ch
 	return ARCHIVE_WARN;
 }
 
+static uint64_t gzw_bound(struct archive_write_filter *f, uint64_t n) { (void)f; return la_gpu_gzip_compress_bound(n, GZW_CHUNK); }
+
+static int gzw_compress(struct archive_write_filter *f, const struct la_write_window *w)
+{
+	const struct gzw_private *d = f->data;
+	la_gzc_batch bt;
+	memset(&bt, 0, sizeof(bt));
+	bt.d_src = w->d_in; bt.src_bytes = w->len; bt.chunk_bytes = GZW_CHUNK; bt.mtime = d->mtime;
+	bt.d_out = w->d_out; bt.out_cap = w->out_cap; bt.d_out_bytes = w->d_len;
+	return la_gpu_gzip_compress(w->gpu, &bt);
+}
+
+static int gzw_open(struct archive_write_filter *f)
+{
+	struct gzw_private *d = f->data;
+	int r = la_write_window_open(f, 1);	/* (not whole 48 KiB chunks: rounding would move member boundaries) */
+	if (r == ARCHIVE_OK && d->timestamp >= 0)
+		d->mtime = (uint32_t)time(NULL);
+	return r;
+}
+
+static int gzw_close(struct archive_write_filter *f)
+{
+	struct gzw_private *d = f->data;
+	if (d->w.gpu == NULL)
+		return ARCHIVE_OK;
+	int r = la_write_window_flush(f, 0);
+	if (r == ARCHIVE_OK && !d->w.wrote_anything) {
+		/* nothing was written: one member with an empty deflate stream, as zlib's Z_FINISH on no input gives
+		 * the reference (header, 03 00, crc 0, isize 0) */
+		const uint8_t m[20] = { 0x1f, 0x8b, 8, 0, (uint8_t)d->mtime, (uint8_t)(d->mtime >> 8), (uint8_t)(d->mtime >> 16),
+		    (uint8_t)(d->mtime >> 24), 0, 3, 0x03, 0x00, 0, 0, 0, 0, 0, 0, 0, 0 };
+		r = __archive_write_filter(f->next_filter, m, sizeof(m));
+	}
+	return r;
+}
+
 int archive_write_add_filter_gzip(struct archive *_a)
 {
 	struct archive_write_filter *f = __archive_write_allocate_filter(_a);
-	struct lz4w_private *d = calloc(1, sizeof(*d));
+	struct gzw_private *d = calloc(1, sizeof(*d));
 	if (f == NULL || d == NULL) {
 		free(d);
 		archive_set_error(_a, ENOMEM, "Out of memory");
 		return ARCHIVE_FATAL;
 	}
-	d->kind = 1;
+	d->w.name = "gzip";
+	d->w.bound = gzw_bound;
+	d->w.compress = gzw_compress;
 	d->compression_level = 6;	/* Z_DEFAULT_COMPRESSION in the reference; informational here */
 	f->data = d;
 	f->options = gzw_options;
-	f->open = lz4w_open;
-	f->close = lz4w_close;
-	f->free = lz4w_free;
+	f->open = gzw_open;
+	f->close = gzw_close;
+	f->free = la_write_window_free;
 	f->code = ARCHIVE_FILTER_GZIP;
 	f->name = "gzip";
 	return ARCHIVE_OK;

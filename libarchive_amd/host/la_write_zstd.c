@@ -13,8 +13,9 @@
  * archive_write_set_filter_option turns into ARCHIVE_FAILED "Undefined option".
  *
  * What differs from the reference by design:
- *   - write() only gathers input into a pinned window; a full window (LA_GPU_WRITE_WINDOW_MIB, default 64, rounded
- *     down to whole frames) goes to la_gpu_zstd_compress() in ONE call and the frames come back in one copy;
+ *   - write() only gathers input into the write window of la_write_private.h; a full window (LA_GPU_WRITE_WINDOW_MIB,
+ *     default 64, rounded down to whole frames) goes to la_gpu_zstd_compress() in ONE call and the frames come back
+ *     in one copy;
  *   - the stream is a sequence of small frames, by default ONE 128 KiB block each, not the reference's single frame:
  *     the device read side decodes one frame per wave, so a many-frame stream is the shape it reads fast (and the
  *     shape its default bid policy takes), and every zstd reader reads concatenated frames.  "max-frame-in" n below
@@ -38,18 +39,11 @@
 #define ZSTDW_FRAME_MAX  (128u << 20)
 
 struct zstdw_private {
+	struct la_write_window w;	/* first */
 	int compression_level;
 	int threads, long_distance, frame_per_file;	/* accepted, no effect here */
 	uint64_t min_frame_in, min_frame_out, max_frame_in, max_frame_out;
 	uint32_t block_size, blocks_per_frame;
-	la_gpu_ctx *gpu;
-	uint8_t *win;		/* pinned input window */
-	size_t win_cap, win_len;
-	uint8_t *out;		/* pinned output of one window */
-	size_t out_cap;
-	void *d_in, *d_out, *d_len;
-	size_t d_in_cap, d_out_cap;
-	int wrote_anything;
 };
 
 /* a decimal integer, nothing else (archive_write_add_filter_zstd.c string_to_number) */
@@ -142,80 +136,27 @@ static int zstdw_options(struct archive_write_filter *f, const char *key, const 
 	return ARCHIVE_WARN;
 }
 
-static int zstdw_gpu_fail(struct archive_write_filter *f, struct zstdw_private *d, const char *what)
+static uint64_t zstdw_bound(struct archive_write_filter *f, uint64_t n)
 {
-	archive_set_error(f->archive, ARCHIVE_ERRNO_MISC, "zstd GPU data plane: %s failed: %s", what,
-	    d->gpu ? la_gpu_last_error(d->gpu) : "no device");
-	return ARCHIVE_FATAL;
+	const struct zstdw_private *d = f->data;
+	return la_gpu_zstd_compress_bound(n, d->block_size, d->blocks_per_frame);
 }
 
-/* compress the window (an empty one too when `empty_frame`: the stream's one empty frame) and pass the frames on */
-static int zstdw_flush_window(struct archive_write_filter *f, struct zstdw_private *d, int empty_frame)
+static int zstdw_compress(struct archive_write_filter *f, const struct la_write_window *w)
 {
-	if (d->win_len == 0 && !empty_frame)
-		return ARCHIVE_OK;
-	const uint32_t flags = LA_ZSTDC_CHECKSUM | (d->compression_level <= 0 ? LA_ZSTDC_RAW_LITERALS : 0);
-	if (d->d_in == NULL && d->win_len) {
-		if (la_gpu_malloc(d->gpu, &d->d_in, d->win_cap) != LA_OK)
-			return zstdw_gpu_fail(f, d, "device allocation");
-		d->d_in_cap = d->win_cap;
-	}
-	if (d->d_out == NULL) {
-		const uint64_t cap = la_gpu_zstd_compress_bound(d->win_cap, d->block_size, d->blocks_per_frame);
-		void *hp = NULL;
-		if (la_gpu_malloc(d->gpu, &d->d_out, cap) != LA_OK || la_gpu_malloc_host(d->gpu, &hp, cap) != LA_OK)
-			return zstdw_gpu_fail(f, d, "output allocation");
-		d->out = hp; d->d_out_cap = d->out_cap = cap;
-	}
-	if (d->d_len == NULL && la_gpu_malloc(d->gpu, &d->d_len, 64) != LA_OK)
-		return zstdw_gpu_fail(f, d, "device allocation");
+	const struct zstdw_private *d = f->data;
 	la_zstdc_batch bt;
 	memset(&bt, 0, sizeof(bt));
-	bt.d_src = d->d_in; bt.src_bytes = d->win_len;
-	bt.block_size = d->block_size; bt.blocks_per_frame = d->blocks_per_frame; bt.flags = flags;
-	bt.d_out = d->d_out; bt.out_cap = d->d_out_cap; bt.d_out_bytes = d->d_len;
-	uint64_t total = 0;
-	if ((d->win_len && la_gpu_memcpy_h2d(d->gpu, d->d_in, d->win, d->win_len) != LA_OK) ||
-	    la_gpu_zstd_compress(d->gpu, &bt) != LA_OK ||
-	    la_gpu_memcpy_d2h(d->gpu, &total, d->d_len, sizeof(total)) != LA_OK ||
-	    la_gpu_sync(d->gpu) != LA_OK)
-		return zstdw_gpu_fail(f, d, "compress");
-	if (total > d->out_cap)
-		return zstdw_gpu_fail(f, d, "compress (output bound)");
-	if (la_gpu_memcpy_d2h(d->gpu, d->out, d->d_out, total) != LA_OK || la_gpu_sync(d->gpu) != LA_OK)
-		return zstdw_gpu_fail(f, d, "device to host copy");
-	d->win_len = 0;
-	d->wrote_anything = 1;
-	return __archive_write_filter(f->next_filter, d->out, (size_t)total);
-}
-
-static int zstdw_write(struct archive_write_filter *f, const void *buff, size_t length)
-{
-	struct zstdw_private *d = f->data;
-	const uint8_t *p = buff;
-	while (length) {
-		size_t n = d->win_cap - d->win_len;
-		if (n > length) n = length;
-		memcpy(d->win + d->win_len, p, n);
-		d->win_len += n; p += n; length -= n;
-		if (d->win_len == d->win_cap) {
-			int r = zstdw_flush_window(f, d, 0);
-			if (r != ARCHIVE_OK)
-				return r;
-		}
-	}
-	return ARCHIVE_OK;
+	bt.d_src = w->d_in; bt.src_bytes = w->len;
+	bt.block_size = d->block_size; bt.blocks_per_frame = d->blocks_per_frame;
+	bt.flags = LA_ZSTDC_CHECKSUM | (d->compression_level <= 0 ? LA_ZSTDC_RAW_LITERALS : 0);
+	bt.d_out = w->d_out; bt.out_cap = w->out_cap; bt.d_out_bytes = w->d_len;
+	return la_gpu_zstd_compress(w->gpu, &bt);
 }
 
 static int zstdw_open(struct archive_write_filter *f)
 {
 	struct zstdw_private *d = f->data;
-	const char *wm = getenv("LA_GPU_WRITE_WINDOW_MIB");
-	if (la_gpu_open(la_env_device(), &d->gpu) != LA_OK) {
-		archive_set_error(f->archive, ARCHIVE_ERRNO_MISC,
-		    "Can't initialize zstd GPU data plane (no usable gfx950 device); no CPU fallback is built");
-		return ARCHIVE_FATAL;
-	}
 	/* frame shape: one 128 KiB block by default; max-frame-in below a block is one smaller block */
 	uint64_t fin = d->max_frame_in < ZSTDW_FRAME_MAX ? d->max_frame_in : ZSTDW_FRAME_MAX;
 	if (fin < ZSTDW_BLOCK) {
@@ -225,45 +166,16 @@ static int zstdw_open(struct archive_write_filter *f)
 		d->block_size = ZSTDW_BLOCK;
 		d->blocks_per_frame = d->max_frame_in == UINT64_MAX ? 1u : (uint32_t)(fin / ZSTDW_BLOCK);
 	}
-	const size_t frame = (size_t)d->block_size * d->blocks_per_frame;
-	const size_t want = (size_t)(wm && atoi(wm) > 0 ? atoi(wm) : 64) << 20;
-	d->win_cap = want / frame * frame;
-	if (d->win_cap == 0)
-		d->win_cap = frame;
-	void *hp = NULL;
-	if (la_gpu_malloc_host(d->gpu, &hp, d->win_cap) != LA_OK)
-		return zstdw_gpu_fail(f, d, "pinned window allocation");
-	d->win = hp;
-	f->write = zstdw_write;
-	return ARCHIVE_OK;
+	return la_write_window_open(f, (size_t)d->block_size * d->blocks_per_frame);	/* whole frames */
 }
 
 static int zstdw_close(struct archive_write_filter *f)
 {
 	struct zstdw_private *d = f->data;
-	if (d->gpu == NULL)
+	if (d->w.gpu == NULL)
 		return ARCHIVE_OK;
 	/* nothing written at all: one empty frame (FCS 0, one empty last raw block, the checksum of nothing) */
-	return zstdw_flush_window(f, d, !d->wrote_anything);
-}
-
-static int zstdw_free(struct archive_write_filter *f)
-{
-	struct zstdw_private *d = f->data;
-	if (d) {
-		if (d->gpu) {
-			la_gpu_sync(d->gpu);
-			if (d->win) la_gpu_free_host(d->gpu, d->win);
-			if (d->out) la_gpu_free_host(d->gpu, d->out);
-			if (d->d_in) la_gpu_free(d->gpu, d->d_in);
-			if (d->d_out) la_gpu_free(d->gpu, d->d_out);
-			if (d->d_len) la_gpu_free(d->gpu, d->d_len);
-			la_gpu_close(d->gpu);
-		}
-		free(d);
-	}
-	f->data = NULL;
-	return ARCHIVE_OK;
+	return la_write_window_flush(f, !d->w.wrote_anything);
 }
 
 int archive_write_add_filter_zstd(struct archive *_a)
@@ -275,6 +187,9 @@ int archive_write_add_filter_zstd(struct archive *_a)
 		archive_set_error(_a, ENOMEM, "Out of memory");
 		return ARCHIVE_FATAL;
 	}
+	d->w.name = "zstd";
+	d->w.bound = zstdw_bound;
+	d->w.compress = zstdw_compress;
 	d->compression_level = 3;	/* CLEVEL_DEFAULT in the reference */
 	d->max_frame_in = UINT64_MAX;
 	d->max_frame_out = UINT64_MAX;
@@ -282,7 +197,7 @@ int archive_write_add_filter_zstd(struct archive *_a)
 	f->options = zstdw_options;
 	f->open = zstdw_open;
 	f->close = zstdw_close;
-	f->free = zstdw_free;
+	f->free = la_write_window_free;
 	f->code = ARCHIVE_FILTER_ZSTD;
 	f->name = "zstd";
 	return ARCHIVE_OK;

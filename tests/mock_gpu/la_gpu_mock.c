@@ -273,6 +273,52 @@ int la_gpu_gzip_compress(la_gpu_ctx *c, const la_gzc_batch *bt)
 	return LA_OK;
 }
 
+/* zstd compression stand-in: every block a Raw_Block, in single-segment frames with their content size and the
+ * XXH64 checksum; empty input is one empty frame */
+uint64_t la_gpu_zstd_compress_workspace_bytes(uint64_t s, uint32_t b, uint32_t f) { (void)s; (void)b; (void)f; return 0; }
+uint64_t la_gpu_zstd_compress_bound(uint64_t src_bytes, uint32_t block_size, uint32_t bpf)
+{
+	if (block_size == 0 || block_size > 131072u || bpf == 0) return 0;
+	const uint64_t nb = src_bytes ? (src_bytes + block_size - 1) / block_size : 1, nf = (nb + bpf - 1) / bpf;
+	return src_bytes + nb * 3u + nf * 13u + 64u;
+}
+int la_gpu_zstd_compress(la_gpu_ctx *c, const la_zstdc_batch *bt)
+{
+	(void)c;
+	if (!bt || bt->block_size == 0 || bt->block_size > 131072u || bt->blocks_per_frame == 0)
+		return LA_ERR_ARG;
+	const uint64_t fb = (uint64_t)bt->block_size * bt->blocks_per_frame;
+	uint64_t o = 0, so = 0;
+	do {
+		const uint64_t fcs = bt->src_bytes - so < fb ? bt->src_bytes - so : fb;
+		const uint32_t fl = fcs < 256u ? 1u : fcs < 65536u + 256u ? 2u : 4u;
+		const uint64_t nb = fcs ? (fcs + bt->block_size - 1) / bt->block_size : 1;
+		if (o + 5u + fl + nb * 3u + fcs + 4u > bt->out_cap) return LA_ERR_ARG;
+		uint8_t *p = bt->d_out + o;
+		mock_le32(p, 0xFD2FB528u);
+		p[4] = (uint8_t)((fl == 1u ? 0u : fl == 2u ? 0x40u : 0x80u) | 0x20u | ((bt->flags & LA_ZSTDC_CHECKSUM) ? 4u : 0u));
+		const uint64_t v = fl == 2u ? fcs - 256u : fcs;
+		for (uint32_t k = 0; k < fl; k++)
+			p[5 + k] = (uint8_t)(v >> (8u * k));
+		o += 5u + fl;
+		uint64_t b = 0;
+		do {
+			const uint32_t n = (uint32_t)(fcs - b < bt->block_size ? fcs - b : bt->block_size);
+			const uint32_t bh = (b + n == fcs ? 1u : 0u) | (n << 3);	/* Last_Block, Raw_Block, Block_Size */
+			bt->d_out[o] = (uint8_t)bh; bt->d_out[o + 1] = (uint8_t)(bh >> 8); bt->d_out[o + 2] = (uint8_t)(bh >> 16);
+			if (n) memcpy(bt->d_out + o + 3, bt->d_src + so + b, n);
+			o += 3u + n; b += n;
+		} while (b < fcs);
+		if (bt->flags & LA_ZSTDC_CHECKSUM) {
+			mock_le32(bt->d_out + o, (uint32_t)orc_xxh64(bt->d_src + so, (size_t)fcs, 0));
+			o += 4;
+		}
+		so += fcs;
+	} while (so < bt->src_bytes);
+	*bt->d_out_bytes = o;
+	return LA_OK;
+}
+
 /* zstd: one oracle stream decode per frame (test stand-in, CPU only) */
 uint64_t la_gpu_zstd_workspace_bytes(uint32_t n) { (void)n; return 0; }
 int la_gpu_zstd_decode(la_gpu_ctx *c, const la_zstd_batch *bt)

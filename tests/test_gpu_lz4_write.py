@@ -22,7 +22,8 @@ def _lib():
 
 def _lib_setup(lib):
     lib.archive_write_new.restype = C.c_void_p
-    for f in ("archive_write_add_filter_lz4", "archive_write_add_filter_gzip", "archive_write_set_format_raw", "archive_write_close", "archive_write_free"):
+    for f in ("archive_write_add_filter_lz4", "archive_write_add_filter_gzip", "archive_write_add_filter_zstd", "archive_write_set_format_raw",
+              "archive_write_close", "archive_write_free"):
         getattr(lib, f).argtypes = [C.c_void_p]
     lib.archive_write_set_filter_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]
     lib.archive_write_open_memory.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]

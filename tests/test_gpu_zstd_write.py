@@ -2,14 +2,12 @@
 archive_write_new -> add_filter_zstd -> set_format_raw -> open_memory -> header -> data (in pieces) -> close.  What it
 writes must read back as the input through the image's libzstd (the library the reference's filter calls), the
 oracle's stream decoder and this repository's own read path (la_api.cat), and must have the frame shape it promises."""
-import ctypes as C
 import random
 
 import pytest
 
 import la_api
 import zstd_support as Z
-import libarchive_amd as la
 from test_gpu_lz4_write import ARCHIVE_FAILED, ARCHIVE_FATAL, ARCHIVE_OK, write_lz4
 from test_gpu_zstd_compress import walk
 
@@ -17,7 +15,6 @@ pytestmark = pytest.mark.gpu
 
 
 def write_zstd(data, options=(), piece=None, cap=None):
-    la.host_lib().archive_write_add_filter_zstd.argtypes = [C.c_void_p]
     return write_lz4(data, options, piece, cap, codec="zstd")
 
 

@@ -89,11 +89,12 @@ from test_gpu_zip import (  # noqa: E402,F401
 
 
 def test_write_filter_host_logic_on_the_mock(gpu_ctx, monkeypatch):
-    """The lz4 write filter's host side (windows, options, frame hand-off, empty stream, client errors) against the
-    mock device (which stores every block): what it writes reads back through the read path."""
+    """The write filters' host side (windows, options, frame hand-off, empty stream, client errors) against the
+    mock device (which stores every block): what they write reads back through the read path."""
     import ctypes as C
     import random
     import test_gpu_lz4_write as W
+    import test_gpu_zstd_write as ZW
     mock = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
     monkeypatch.setattr(W, "_lib", lambda: W._lib_setup(mock))
     monkeypatch.setenv("LA_GPU_WRITE_WINDOW_MIB", "1")
@@ -103,6 +104,11 @@ def test_write_filter_host_logic_on_the_mock(gpu_ctx, monkeypatch):
         for opts in ((), (("block-checksum", "1"),), (("stream-checksum", None), ("block-size", "5"))):
             rc, img = W.write_lz4(data, opts, rnd.choice([None, 4097]))
             assert rc == 0 and la_api.cat(img).data == data
+    for size in (0, 1, 131072, 3 * (1 << 20) + 999):
+        data = rnd.randbytes(size)
+        for opts in ((), (("max-frame-in", "64k"),), (("max-frame-in", "1M"),)):
+            rc, img = ZW.write_zstd(data, opts, rnd.choice([None, 4097, 70001]))
+            assert rc == 0 and la_api.cat(img).data == data, (size, opts)
     W.test_write_filter_options_and_errors(None)
     W.test_gzip_write_filter_round_trips(None, monkeypatch)
 

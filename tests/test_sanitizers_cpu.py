@@ -112,6 +112,16 @@ for size in (0, 1, 65535, 65536, 1 << 20, (1 << 20) + 1, 3 * (1 << 20) + 12345):
         n += 1
     rc, err = W.write_lz4(data, (), None, cap=max(1, size // 2))
     n += 1
+# zstd write filter on the same window: frame sizes, pieces, the empty stream
+import test_gpu_zstd_write as ZW
+for size in (0, 1, 131072, (1 << 20) + 1, 3 * (1 << 20) + 12345):
+    data = bytes(rnd.getrandbits(8) for _ in range(min(size, 4096))) * (size // 4096 + 1)
+    data = data[:size]
+    for opts in ((), (("max-frame-in", "64k"),), (("max-frame-in", "1M"),)):
+        rc, img = ZW.write_zstd(data, opts, rnd.choice([None, 1000, 70000]))
+        assert rc == 0
+        assert la_api.cat(img).data == data, (size, opts)
+        n += 1
 # zstd filter and frame walker: mutated / truncated multi-frame streams (frame headers, block headers, skippable frames)
 import zstd_support as Z
 zz = Z.libzstd()
@@ -180,7 +190,7 @@ def test_filters_read_core_and_tar_walker_under_asan_ubsan(tmp_path):
     mock = os.path.join(ROOT, "tests", "mock_gpu")
     orc = os.path.join(ROOT, "oracle")
     srcs = [os.path.join(host, f) for f in ("la_lz4_index.c", "la_gzip_index.c", "la_read_core.c", "la_format_tar.c",
-                                            "la_format_zip.c", "la_hash_dropin.c", "la_write_filters.c", "la_filter_lz4.c", "la_filter_gzip.c", "la_filter_zstd.c", "la_bid_policy.c", "la_zstd_index.c")]
+                                            "la_format_zip.c", "la_hash_dropin.c", "la_write_filters.c", "la_write_zstd.c", "la_filter_lz4.c", "la_filter_gzip.c", "la_filter_zstd.c", "la_bid_policy.c", "la_zstd_index.c")]
     srcs += [os.path.join(mock, "la_gpu_mock.c")] + [os.path.join(orc, f) for f in ("orc_hash.c", "orc_lz4.c", "orc_inflate.c", "orc_zstd.c")]
     subprocess.check_call(["gcc", "-O1", "-g", "-fPIC", "-std=gnu11", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
                            "-I" + os.path.join(ROOT, "include"), "-shared", "-o", os.path.join(mock, "libla_host_mock_asan.so")] + srcs)
