@@ -71,6 +71,13 @@
  * the early payload loads moved behind the table loads / made branch-free (the compiler
  * waits for them right behind the loads because a byte-wise tail path defines the same
  * registers; removing that wait changed nothing measurable).
+ *
+ * Round 4, the poll iteration of phase M: each slot's copy class is fixed once (six classes, one flat test
+ * each against the ready lanes), the spin bound counts per wave in a scalar register, and the body keeps only
+ * the flag look, the copies, the done bit and one exit ballot.  Per wave VALU -16 %, SALU -8 %, wave cycles
+ * -3 %; expand 5.34 -> 5.18 ms per C2 launch, 25.7 -> 24.7 ms for gzip C3.  The per-slot register picks were
+ * already outside the loop (hoisted by the compiler), so the iteration did not halve: a level's time is the
+ * LDS round trips in series, not issue.  s_sleep 0 instead of 1: no change beyond noise.
  */
 #include "la_dev.h"
 
@@ -491,6 +498,7 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	for (uint32_t r = 0; r < MAXSTEPS; r++) {
 		if (r * FAST_THREADS >= ns)
 			break;
+		/* ---- per-slot setup, once per slot: everything the poll iteration needs ---- */
 		const uint32_t k = fast_seq_index(r, wave, lane);
 		const bool active = k < ns;
 		/* registers of step r (the array is indexed by a loop counter: pick by selects) */
@@ -510,121 +518,131 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 #else
 		const uint32_t qstop = q + (qp >> 16);	/* exclusive; q == qstop: nothing to wait for */
 #endif
-		uint32_t spins = 0;
-		bool fin = mlen == 0;
-		if (active && fin)
+		uint8_t *const mp = W + mdst;
+		const uint8_t *const fp = W + s0;
+		/* The copy class of the lane's match, fixed for the slot.  The iteration tests each class
+		 * against the ready lanes once: a class without ready lanes is one skipped branch.
+		 *   c_long   no overlap, 16 bytes and more: 16-byte pieces, the last one placed so that it
+		 *            ENDS with the match (overlapping stores instead of a ragged tail)
+		 *   c_mid    no overlap, 8..15 bytes: two 8-byte pieces, the second one end-aligned
+		 *   c_short  no overlap, 4..7 bytes: one 8-byte load (it may read up to 7 bytes past the
+		 *            source: window bytes or slack), two overlapping 4-byte stores
+		 *   c_tiny   no overlap, 1..3 bytes (only the deflate front end makes these): one 8-byte
+		 *            load, the bytes stored piece by piece
+		 *   c_per8   overlapping, period >= 8: forward 8-byte steps only read bytes stored at
+		 *            least one step earlier
+		 *   c_per1   overlapping, period < 8: byte by byte
+		 * An unaligned LDS access costs one cycle per ACTIVE LANE whatever its width
+		 * (tools/ubench_lds.hip): every lane moves its match with as few, as wide accesses as it
+		 * takes, and the loads of a class are all issued before anything is stored.  Nothing is
+		 * read outside the source from 8 bytes up. */
+		const bool disjoint = off >= mlen;
+		/* c_long: 32 bytes per trip from i = 0 to tl, then 16..47 bytes left: one piece from tl, a
+		 * second one behind it from 33 left, an end-aligned one from 17 left */
+		const uint32_t tl = mlen >= 16 ? (mlen - 16) & ~31u : 0u;
+		const bool l33 = mlen - tl > 32, l17 = mlen - tl > 16;
+		uint8_t *const mpt = mp + tl;
+		const uint8_t *const fpt = fp + tl;
+		const bool c_long = disjoint && mlen >= 16;
+		const bool c_mid = disjoint && mlen >= 8 && mlen < 16;
+		const bool c_short = disjoint && mlen >= 4 && mlen < 8;
+		const bool c_tiny = disjoint && mlen != 0 && mlen < 4;
+		const bool c_per8 = !disjoint && off >= 8;
+		const bool c_per1 = !disjoint && off < 8;
+		bool todo = mlen != 0;	/* the lane's match is not in the window yet */
+		if (active && !todo)
 			atomicOr(&donebits[k >> 5], 1u << (k & 31));
+		uint32_t spins = 0;	/* wave-uniform: iterations of this slot that left some lane waiting */
 
+		/* ---- the poll iteration: one flag look for the waiting lanes, the copies of the ready
+		 * lanes class by class, their done bits, one ballot ---- */
 		for (;;) {
 #if defined(LA_DIAG) && !defined(LA_DIAG_L) && !defined(LA_DIAG_M)
 			if (lane == 0 && la_diag_stamps) atomicAdd(&la_diag_stamps[(size_t)blockIdx.x * 8 + 6], 1ull);
 			const unsigned long long t_it0 = __builtin_readcyclecounter();
 #endif
-			if (!fin) {
-				/* advance q over finished sequences: ONE look at the flag word of q per
-				 * iteration (a second look in the same iteration would only be another LDS
-				 * round trip for the whole wave; a wait that spans two words takes two
-				 * iterations) */
-				if (q < qstop) {
-					/* bit 0 of `word` is the flag of q; the zeros shifted in from the
-					 * top end the run at the word boundary */
-					const uint32_t word = __hip_atomic_load(&donebits[q >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> (q & 31);
-					const uint32_t inv = ~word;
-					q += inv ? (uint32_t)__builtin_ctz(inv) : 32u;
-				}
-				/* every wait is bounded: a dependency that never completes (impossible
-				 * for a table the parse kernel produced) fails the block instead of
-				 * hanging the GPU */
-				if (q < qstop && ++spins > (1u << 20)) {
-					status_out[bi] = LA_ST_LZ4_DECODE;
-					q = qstop;
-				}
-				if (q >= qstop) {
-					asm volatile("" ::: "memory");
-					uint8_t *mp = W + mdst;
-					const uint8_t *fp = W + s0;
+			/* advance q over finished sequences: ONE look at the flag word of q per iteration (a
+			 * second look in the same iteration would only be another LDS round trip for the whole
+			 * wave; a wait that spans two words takes two iterations).  Bit 0 of `word` is the flag
+			 * of q; the zeros shifted in from the top end the run at the word boundary.  (Only lanes
+			 * that still have their match to copy have q < qstop.) */
+			if (q < qstop) {
+				const uint32_t word = __hip_atomic_load(&donebits[q >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> (q & 31);
+				const uint32_t inv = ~word;
+				q += inv ? (uint32_t)__builtin_ctz(inv) : 32u;
+			}
+			if (todo && q >= qstop) {
+				asm volatile("" ::: "memory");
 #ifndef FAST_EXP_NOCOPY	/* (what-if, wrong output: the flag protocol alone) */
-					if (off >= mlen) {
-						/* Source and destination do not overlap.  ONE LDS round trip per 64
-						 * bytes: every load is issued before anything is stored, and the
-						 * ragged end is one more 8-byte (or 4-byte) copy placed so that it
-						 * ENDS with the match -- overlapping stores instead of a cascade of
-						 * 4/2/1-byte ones.  Loads may run past the source into later window
-						 * bytes or the slack behind the window; stores never pass the match. */
-						/* An unaligned LDS access costs one cycle per ACTIVE LANE whatever its width
-						 * (tools/ubench_lds.hip), and this phase runs at the speed of the LDS pipe: so
-						 * every lane moves its match with as few, as wide accesses as it takes --
-						 * 16-byte pieces from 16 bytes up (the last one placed so that it ENDS with the
-						 * match: overlapping stores instead of a ragged tail), two 8-byte ones below that,
-						 * one 8-byte load and two 4-byte stores below 8.  All loads of a step are issued
-						 * before anything is stored.  Nothing is read outside the source from 8 bytes up. */
-						if (mlen >= 16) {
-							for (uint32_t i = 0;; i += 32) {	/* one trip up to 47 bytes */
-								const uint32_t left = mlen - i;
-								const uint4 v0 = lds_ld16(fp + i);
-								uint4 v1 = make_uint4(0, 0, 0, 0), vt = make_uint4(0, 0, 0, 0);	/* (not from v0: nothing makes one DS read wait for another) */
-								if (left >= 32)
-									v1 = lds_ld16(fp + i + 16);
-								const bool last = left < 48;	/* 16..47 bytes left: this trip ends the match */
-								if (last && (left & 15))
-									vt = lds_ld16(fp + mlen - 16);
-								lds_st16(mp + i, v0);
-								if (left >= 32)
-									lds_st16(mp + i + 16, v1);
-								if (last) {
-									if (left & 15)
-										lds_st16(mp + mlen - 16, vt);
-									break;
-								}
-							}
-						} else if (mlen >= 8) {
-							const uint64_t a0 = lds_ld8(fp), at = lds_ld8(fp + mlen - 8);
-							lds_st8(mp, a0);
-							if (mlen != 8)
-								lds_st8(mp + mlen - 8, at);
-						} else {
-							const uint64_t a0 = lds_ld8(fp);	/* (may read up to 7 bytes past the source: window bytes or slack) */
-							if (mlen < 4) {
-								/* 1..3 bytes: only the deflate front end makes these (LZ4 matches are
-								 * at least four bytes long) */
-								lds_st_tail(mp, a0, mlen);
-							} else {
-								/* 4 <= mlen <= 7: two overlapping 4-byte stores */
-								lds_st4(mp, (uint32_t)a0);
-								if (mlen != 4)
-									lds_st4(mp + mlen - 4, (uint32_t)(a0 >> (8 * (mlen - 4))));
-							}
+				if (c_long) {
+					if (tl != 0) {	/* 48 bytes and more */
+						for (uint32_t i = 0; i < tl; i += 32) {
+							const uint4 v0 = lds_ld16(fp + i), v1 = lds_ld16(fp + i + 16);
+							lds_st16(mp + i, v0);
+							lds_st16(mp + i + 16, v1);
 						}
-					} else if (off >= 8) {
-						/* overlapping, period >= 8: a forward 8-byte copy only reads bytes
-						 * that this thread stored at least one iteration earlier */
-						uint32_t i = 0;
-						for (; i + 8 <= mlen; i += 8) {
-							uint64_t a = lds_ld8(mp + i - off);
-							lds_st8(mp + i, a);
-							asm volatile("" ::: "memory");	/* keep load/store order: the ranges overlap */
-						}
-						for (; i < mlen; i++)
-							{ uint8_t bq = mp[(int)i - (int)off]; asm volatile("" ::: "memory"); mp[i] = bq; asm volatile("" ::: "memory"); }
-					} else {
-						/* overlapping match: replicate with period `off`; every byte
-						 * read is one this thread (or an earlier sequence) already wrote */
-						for (uint32_t i = 0; i < mlen; i++)
-							{ uint8_t bq = mp[(int)i - (int)off]; asm volatile("" ::: "memory"); mp[i] = bq; asm volatile("" ::: "memory"); }
 					}
-#else
-					(void)mp; (void)fp;
-#endif
-					asm volatile("" ::: "memory");
-					atomicOr(&donebits[k >> 5], 1u << (k & 31));
-					fin = true;
+					uint4 vb, vt;	/* (loaded and stored under the same tests) */
+					const uint4 va = lds_ld16(fpt);
+					if (l33)
+						vb = lds_ld16(fpt + 16);
+					if (l17)
+						vt = lds_ld16(fp + mlen - 16);
+					lds_st16(mpt, va);
+					if (l33)
+						lds_st16(mpt + 16, vb);
+					if (l17)
+						lds_st16(mp + mlen - 16, vt);
 				}
+				if (c_mid) {
+					const uint64_t a0 = lds_ld8(fp), at = lds_ld8(fp + mlen - 8);
+					lds_st8(mp, a0);
+					lds_st8(mp + mlen - 8, at);
+				}
+				if (c_short) {
+					const uint64_t a0 = lds_ld8(fp);
+					lds_st4(mp, (uint32_t)a0);
+					lds_st4(mp + mlen - 4, (uint32_t)(a0 >> (8 * (mlen - 4))));
+				}
+				if (c_tiny)
+					lds_st_tail(mp, lds_ld8(fp), mlen);
+				if (c_per8) {
+					uint32_t i = 0;
+					for (; i + 8 <= mlen; i += 8) {
+						uint64_t a = lds_ld8(mp + i - off);
+						lds_st8(mp + i, a);
+						asm volatile("" ::: "memory");	/* keep load/store order: the ranges overlap */
+					}
+					for (; i < mlen; i++)
+						{ uint8_t bq = mp[(int)i - (int)off]; asm volatile("" ::: "memory"); mp[i] = bq; asm volatile("" ::: "memory"); }
+				}
+				if (c_per1) {
+					/* replicate with period `off`: every byte read is one this lane (or an earlier
+					 * sequence) already wrote */
+					for (uint32_t i = 0; i < mlen; i++)
+						{ uint8_t bq = mp[(int)i - (int)off]; asm volatile("" ::: "memory"); mp[i] = bq; asm volatile("" ::: "memory"); }
+				}
+#else
+				(void)mp; (void)fp; (void)mpt; (void)fpt; (void)l33; (void)l17; (void)c_long; (void)c_mid; (void)c_short; (void)c_tiny; (void)c_per8; (void)c_per1;
+#endif
+				asm volatile("" ::: "memory");
+				atomicOr(&donebits[k >> 5], 1u << (k & 31));
+				todo = false;
 			}
 #if defined(LA_DIAG) && !defined(LA_DIAG_L) && !defined(LA_DIAG_M)
 			if (lane == 0 && la_diag_stamps) atomicAdd(&la_diag_stamps[(size_t)blockIdx.x * 8 + 7], __builtin_readcyclecounter() - t_it0);
 #endif
-			if (__ballot(!fin) == 0)
+			if (__ballot(todo) == 0)
 				break;
+			/* every wait is bounded: a dependency that never completes (impossible for a table
+			 * the parse kernel produced) fails the block instead of hanging the GPU; the lanes
+			 * still waiting then copy in the next iteration */
+			if (++spins > (1u << 20)) {
+				if (todo) {
+					status_out[bi] = LA_ST_LZ4_DECODE;
+					q = qstop;
+				}
+			}
 			__builtin_amdgcn_s_sleep(POLL_SLEEP);	/* back off: polling waves share the LDS with copying ones */
 		}
 	}
