@@ -329,10 +329,19 @@ int      la_gpu_lz4_compress(la_gpu_ctx *ctx, const la_lz4c_batch *batch);
  * gzip compression -- the data plane of the gzip WRITE filter: replaces, for a whole stream per
  * call, deflate() through zlib, the hand-built header, the CRC32 of the input and the trailer of
  * libarchive/archive_write_add_filter_gzip.c:201-237, :263-266, :293-345.  d_src[0, src_bytes) is cut into chunks of
- * chunk_bytes (at most 49152); every chunk becomes one gzip member (fixed-Huffman deflate, or a stored block when
- * it would not shrink) whose header carries the BGZF-compatible "BC" size subfield.  d_out receives the concatenated
- * members, *d_out_bytes their size (beyond out_cap nothing is written; la_gpu_gzip_compress_bound() always fits).
+ * chunk_bytes (at most 49152); every chunk becomes one gzip member of one deflate block, whose header carries the
+ * BGZF-compatible "BC" size subfield.  `options` selects the block: LA_GZC_FIXED a fixed-Huffman block, or a stored
+ * one when that would not shrink; LA_GZC_DYNAMIC the smallest of a dynamic-Huffman, the fixed-Huffman and the stored
+ * block of the same tokens, chosen per chunk from their exact sizes, so never larger than LA_GZC_FIXED gives;
+ * LA_GZC_STORED stored blocks only (zlib level 0).  Any other value is LA_ERR_ARG; a zeroed struct means
+ * LA_GZC_FIXED.  d_out receives the concatenated members, *d_out_bytes their size (beyond out_cap nothing is written;
+ * la_gpu_gzip_compress_bound() always fits, in every mode).  The two fields joined the end of the struct under ABI
+ * version 3.
  * ===================================================================== */
+#define LA_GZC_FIXED    0u   /* as before: fixed-Huffman block, stored when that would not shrink */
+#define LA_GZC_DYNAMIC  1u   /* smallest of dynamic-Huffman, fixed-Huffman and stored, per chunk */
+#define LA_GZC_STORED   2u   /* stored blocks only (zlib level 0) */
+
 typedef struct la_gzc_batch {
 	const uint8_t *d_src;
 	uint64_t       src_bytes;
@@ -341,6 +350,8 @@ typedef struct la_gzc_batch {
 	uint8_t       *d_out;
 	uint64_t       out_cap;
 	uint64_t      *d_out_bytes;	/* one u64 on the device */
+	uint32_t       options;		/* LA_GZC_FIXED, LA_GZC_DYNAMIC or LA_GZC_STORED */
+	uint32_t       reserved;
 } la_gzc_batch;
 
 uint64_t la_gpu_gzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t chunk_bytes);

@@ -84,7 +84,11 @@ class _GzcBatchC(C.Structure):
         ("d_src", C.c_void_p), ("src_bytes", C.c_uint64),
         ("chunk_bytes", C.c_uint32), ("mtime", C.c_uint32),
         ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p),
+        ("options", C.c_uint32), ("reserved", C.c_uint32),
     ]
+
+
+LA_GZC_FIXED, LA_GZC_DYNAMIC, LA_GZC_STORED = 0, 1, 2
 
 
 class _GzBatchC(C.Structure):

@@ -1,6 +1,6 @@
 /*
  * la_comp_common.h -- device code the three compressors share (la_lz4_comp.hip, la_deflate_comp.hip,
- * la_zstd_comp.hip): small load / copy / store helpers, the LZ77 window matcher of the lz4 and zstd block kernels,
+ * la_zstd_comp.hip): small load / copy / store helpers, wave reductions, the LZ77 window matcher of the lz4 and zstd block kernels,
  * the wave bit-stream appender of the deflate and Huffman encoders, the per-frame checksum kernel and the workspace
  * carver of the launchers.
  */
@@ -28,6 +28,23 @@ __device__ __forceinline__ void wave_copy(uint8_t *d, const uint8_t *s, uint32_t
 __device__ __forceinline__ void st_le32(uint8_t *p, uint32_t v)
 {
 	p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1)
+		v += (uint32_t)__shfl_xor((int)v, d, 64);
+	return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t o = (uint32_t)__shfl_xor((int)v, d, 64);
+		v = o > v ? o : v;
+	}
+	return v;
 }
 
 /* LZ77 matching of one block by one wave.  The wave looks at 64 consecutive positions at a time: every lane hashes

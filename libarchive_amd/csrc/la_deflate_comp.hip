@@ -20,6 +20,9 @@
  *       nothing -- as at most 31 bits of a FIXED-Huffman block (RFC 1951 3.2.6), a wave prefix sum of
  *       the bit counts gives every token its place, lanes OR their bits into a small LDS stage and whole
  *       dwords go out coalesced (wave_bits_append, la_comp_common.h).  A chunk that would not shrink is written as a stored block instead.
+ *   deflate_dynamic_kernel  (LA_GZC_DYNAMIC) the same matcher, but a token is kept and its symbols counted; the wave
+ *       then builds length-limited complete codes for the chunk (RFC 1951 3.2.7), knows the exact size of the dynamic,
+ *       the fixed and the stored block, and writes the smallest in a second pass over the tokens.
  *   gz_jobs_kernel + crc32_many  CRC32 of every chunk (la_hash.hip).
  *   gz_pack_members_kernel  header, body (fixed-Huffman or stored), trailer at their scanned offsets.
  */
@@ -42,26 +45,39 @@ __device__ __forceinline__ uint32_t fixed_lit(uint32_t sym, uint32_t *nb)
 	*nb = 8; return rev_bits(0xC0u + (sym - 280u), 8);
 }
 
+/* length symbol (257..285) of a match length 3..258, with its extra bits (RFC 1951 3.2.5) */
+__device__ __forceinline__ uint32_t dfl_len_code(uint32_t len, uint32_t *eb, uint32_t *ex)
+{
+	const uint32_t l = len - 3u;
+	*eb = 0; *ex = 0;
+	if (l < 8u)
+		return 257u + l;
+	if (l == 255u)
+		return 285u;
+	const uint32_t n = 31u - (uint32_t)__builtin_clz(l);
+	*eb = n - 2u;
+	*ex = (l - (1u << n)) & ((1u << (n - 2u)) - 1u);
+	return 257u + 4u * (n - 1u) + ((l - (1u << n)) >> (n - 2u));
+}
+
+/* distance symbol (0..29) of a distance 1..32768, with its extra bits */
+__device__ __forceinline__ uint32_t dfl_dist_code(uint32_t dist, uint32_t *eb, uint32_t *ex)
+{
+	const uint32_t d = dist - 1u;
+	*eb = 0; *ex = 0;
+	if (d < 4u)
+		return d;
+	const uint32_t n = 31u - (uint32_t)__builtin_clz(d);
+	*eb = n - 1u;
+	*ex = d & ((1u << (n - 1u)) - 1u);
+	return 2u * n + ((d >> (n - 1u)) & 1u);
+}
+
 /* a match of `len` (3..258) at `dist` (1..32768) as bits; returns the bit count (at most 31) */
 __device__ __forceinline__ uint32_t fixed_match(uint32_t len, uint32_t dist, uint32_t *bits)
 {
-	uint32_t l = len - 3u, lcode, leb, lex;
-	if (l < 8u) { lcode = 257u + l; leb = 0; lex = 0; }
-	else if (l == 255u) { lcode = 285u; leb = 0; lex = 0; }
-	else {
-		const uint32_t n = 31u - (uint32_t)__builtin_clz(l);
-		leb = n - 2u;
-		lcode = 257u + 4u * (n - 1u) + ((l - (1u << n)) >> leb);
-		lex = (l - (1u << n)) & ((1u << leb) - 1u);
-	}
-	uint32_t d = dist - 1u, dcode, deb, dex;
-	if (d < 4u) { dcode = d; deb = 0; dex = 0; }
-	else {
-		const uint32_t n = 31u - (uint32_t)__builtin_clz(d);
-		deb = n - 1u;
-		dcode = 2u * n + ((d >> (n - 1u)) & 1u);
-		dex = d & ((1u << deb) - 1u);
-	}
+	uint32_t leb, lex, deb, dex;
+	const uint32_t lcode = dfl_len_code(len, &leb, &lex), dcode = dfl_dist_code(dist, &deb, &dex);
 	uint32_t nb, v = fixed_lit(lcode, &nb);
 	v |= lex << nb; nb += leb;
 	v |= rev_bits(dcode, 5) << nb; nb += 5u;
@@ -158,6 +174,421 @@ __global__ __launch_bounds__(64) void deflate_fixed_kernel(const uint8_t *__rest
 		body_len[ci] = (uint32_t)((bp + 7) >> 3);
 }
 
+/* ------------------------------------------------------------------ dynamic Huffman (RFC 1951 3.2.7) */
+
+#define DFL_NLL   286u		/* literal / length symbols */
+#define DFL_ND    30u		/* distance symbols */
+#define DFL_DOFF  288u		/* the distance symbols' place in the 320-entry histogram and code tables */
+#define DFL_WAVES 3328u		/* waves of deflate_dynamic_kernel: 13 per CU by LDS on 256 CUs; each owns a token buffer */
+#define DFL_TOK_MATCH 0x80000000u	/* token: a literal byte, or this | (len - 3) << 16 | (dist - 1) */
+
+/* wave_bits_append for tokens of up to 48 bits: a length symbol with its extra bits and a distance symbol with its
+ * extra bits are 15 + 5 + 15 + 13 bits.  The stage holds two dwords more than 64 such tokens can fill. */
+template <uint32_t N, typename Store>
+__device__ __forceinline__ uint32_t wave_bits_append64(uint64_t bp, uint64_t bits, uint32_t nb, uint32_t (&stage)[N],
+    uint32_t lane, Store store)
+{
+	static_assert(N >= (31u + 64u * 48u) / 32u + 3u, "stage too small for 64 tokens of 48 bits");
+	uint32_t inc = nb;
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t t = __shfl_up(inc, d, 64);
+		if ((int)lane >= d) inc += t;
+	}
+	const uint32_t total = __shfl(inc, 63, 64);
+	const uint32_t at = (uint32_t)(bp & 31u) + inc - nb;
+	if (nb) {
+		const uint32_t sh = at & 31u;
+		const uint64_t rest = (bits >> 1) >> (31u - sh);	/* what the first dword does not take */
+		atomicOr(&stage[at >> 5], (uint32_t)(bits << sh));
+		if ((uint32_t)rest)
+			atomicOr(&stage[(at >> 5) + 1], (uint32_t)rest);
+		if ((uint32_t)(rest >> 32))
+			atomicOr(&stage[(at >> 5) + 2], (uint32_t)(rest >> 32));
+	}
+	__builtin_amdgcn_wave_barrier();
+	const uint32_t nd = ((uint32_t)(bp & 31u) + total) >> 5;	/* at most 96 */
+	const uint32_t g0 = (uint32_t)(bp >> 5);
+	const uint32_t carry = stage[nd];
+	const uint32_t m0 = lane < nd ? stage[lane] : 0, m1 = lane + 64u < nd ? stage[lane + 64u] : 0;
+	__builtin_amdgcn_wave_barrier();
+	if (lane < nd)
+		store(g0 + lane, m0);
+	if (lane + 64u < nd)
+		store(g0 + lane + 64u, m1);
+	if (lane <= nd)
+		stage[lane] = 0;
+	if (lane + 64u <= nd)
+		stage[lane + 64u] = 0;
+	__builtin_amdgcn_wave_barrier();
+	if (lane == 0)
+		stage[0] = carry;
+	__builtin_amdgcn_wave_barrier();
+	return total;
+}
+
+/* A code must have two symbols to be complete: with fewer in use, give symbol 0 (or 1, when 0 is the one in use) a
+ * count of one, as zlib's build_tree does.  F = this lane's count, lane = its symbol. */
+__device__ __forceinline__ uint32_t dfl_force_two(uint32_t F, uint32_t lane)
+{
+	const uint64_t used = __ballot(F != 0);
+	const uint32_t nused = (uint32_t)__builtin_popcountll(used);
+	if (nused >= 2u)
+		return F;
+	const uint32_t extra = (used & 1u) ? 1u : 0u;
+	return (lane == extra || (nused == 0 && lane == 1u)) ? 1u : F;
+}
+
+/* Code lengths of a complete prefix code (Kraft sum exactly 1) of at most `maxbits` bits for the symbols with a
+ * count; lane `lane` holds the symbols lane + 64 k.  At least two symbols have a count.  Shannon lengths
+ * ceil(log2(N / f)) clamped to maxbits; where the clamp over-subscribes the code, the rarest symbols that can still
+ * grow are lengthened; the room left is then given to the symbol whose count is largest for the code space it holds
+ * (f * 2^len: the one the rounding-up cost most), one wave arg-max round per step.  Every step has a candidate (the
+ * longest code always fits the room), so the rounds end in a complete code; the return value says that they did. */
+template <int SLOTS>
+__device__ __forceinline__ bool dfl_code_lengths(const uint32_t (&F)[SLOTS], uint32_t (&Ls)[SLOTS], uint32_t maxbits,
+    uint32_t lane)
+{
+	uint32_t N = 0;
+#pragma unroll
+	for (int k = 0; k < SLOTS; k++)
+		N += F[k];
+	N = wave_sum(N);
+	const uint32_t full = 1u << maxbits;
+	uint32_t K = 0;
+#pragma unroll
+	for (int k = 0; k < SLOTS; k++) {
+		uint32_t l = 0;
+		if (F[k]) {
+			while ((F[k] << l) < N) l++;
+			l = l < 1u ? 1u : (l > maxbits ? maxbits : l);
+			K += full >> l;
+		}
+		Ls[k] = l;
+	}
+	K = wave_sum(K);
+	for (uint32_t it = 0; it < 8192u && K != full; it++) {
+		const bool grow = K > full;
+		const uint32_t room = full - K;
+		uint32_t key = 0;
+#pragma unroll
+		for (int k = 0; k < SLOTS; k++) {
+			const uint32_t s = lane + 64u * k;
+			uint32_t c = 0;
+			if (grow) {
+				if (F[k] && Ls[k] < maxbits)
+					c = 0x80000000u | ((0xFFFFu - F[k]) << 9) | s;
+			} else if (F[k] && Ls[k] > 1u && (full >> Ls[k]) <= room) {
+				const uint32_t w = F[k] << Ls[k];
+				c = 0x80000000u | ((w < 0x3FFFFFu ? w : 0x3FFFFFu) << 9) | s;
+			}
+			key = c > key ? c : key;
+		}
+		key = wave_max(key);
+		if (key == 0)
+			break;
+		const uint32_t s = key & 511u;
+#pragma unroll
+		for (int k = 0; k < SLOTS; k++)
+			if (s == lane + 64u * k) {
+				if (grow) { Ls[k]++; K -= full >> Ls[k]; }
+				else { K += full >> Ls[k]; Ls[k]--; }
+			}
+		K = (uint32_t)__shfl((int)K, (int)(s & 63u), 64);
+	}
+	return K == full;
+}
+
+/* canonical codes (RFC 1951 3.2.2) for the lengths of dfl_code_lengths, bit-reversed for LSB-first packing, into
+ * tab[symbol] = code | length << 16 (0 for a symbol without a code) */
+template <int SLOTS>
+__device__ __forceinline__ void dfl_assign_codes(const uint32_t (&Ls)[SLOTS], uint32_t maxbits, uint32_t *tab,
+    uint32_t lane)
+{
+	const uint64_t below = ((uint64_t)1 << lane) - 1u;
+	uint32_t next = 0;
+#pragma unroll
+	for (int k = 0; k < SLOTS; k++)
+		if (Ls[k] == 0)
+			tab[lane + 64u * k] = 0;
+	for (uint32_t L = 1; L <= maxbits; L++) {
+		next <<= 1;
+#pragma unroll
+		for (int k = 0; k < SLOTS; k++) {
+			const bool m = Ls[k] == L;
+			const uint64_t b = __ballot(m);
+			if (m)
+				tab[lane + 64u * k] = rev_bits(next + (uint32_t)__builtin_popcountll(b & below), L) | (L << 16);
+			next += (uint32_t)__builtin_popcountll(b);
+		}
+	}
+}
+
+__device__ __forceinline__ uint32_t fixed_lit_len(uint32_t sym) { return sym < 144u ? 8u : (sym < 256u ? 9u : (sym < 280u ? 7u : 8u)); }
+
+/* One wave per chunk, chunks ci = blockIdx.x + k * gridDim.x.  Pass 1 is deflate_fixed_kernel's matcher; instead of
+ * coding a token it counts its symbols in LDS histograms and keeps the token in this wave's token buffer.  Then the
+ * wave builds the two codes and the block header's code-length code, and knows the exact size of the dynamic, the
+ * fixed and the stored block; it writes the smallest (nothing for a stored block: body_len >= n + 5 tells the pack
+ * kernel) in a second pass over the tokens, with codes from an LDS table. */
+__global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
+    uint32_t chunk, uint32_t n_chunks, uint8_t *__restrict__ tmp, uint32_t tmp_stride, uint32_t *__restrict__ body_len,
+    uint32_t *__restrict__ tokbuf)
+{
+	__shared__ uint16_t tab[1u << DFL_HASH_BITS];
+	__shared__ uint32_t stage[104];
+	__shared__ uint32_t hist[320];		/* [0, 286) literal / length, [288, 318) distance */
+	__shared__ uint32_t code[DFL_DOFF + 64];	/* same places: code | length << 16 */
+	__shared__ uint32_t clh[64], clc[64];	/* code-length alphabet: counts, codes */
+	__shared__ uint32_t hdr[4];		/* ncls, extra bits of the 16 / 17 / 18 symbols */
+	uint16_t *cls = tab;	/* the header's code-length symbols, symbol | extra bits << 8: the match table is free by then */
+	const uint32_t lane = threadIdx.x;
+	const uint64_t below = ((uint64_t)1 << lane) - 1u;
+	uint32_t *toks = tokbuf + (uint64_t)blockIdx.x * chunk;
+	for (uint32_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
+		const uint64_t so = (uint64_t)ci * chunk;
+		const uint32_t n = (uint32_t)(src_bytes - so < chunk ? src_bytes - so : chunk);
+		const uint8_t *in = src + so;
+		uint32_t *out = (uint32_t *)(void *)(tmp + (uint64_t)ci * tmp_stride);
+		__syncthreads();	/* the previous chunk's tables are done with */
+		for (uint32_t i = lane; i < (1u << DFL_HASH_BITS); i += 64)
+			tab[i] = 0;
+		for (uint32_t i = lane; i < 104; i += 64)
+			stage[i] = 0;
+		for (uint32_t i = lane; i < 320; i += 64)
+			hist[i] = 0;
+		clh[lane] = 0;
+		__syncthreads();
+
+		/* ---- pass 1: tokens and histograms ---- */
+		uint32_t anchor = 0, ntok = 0, xbits = 0, nmatch = 0;	/* xbits, nmatch: this lane's share */
+		for (uint32_t base = 0; base < n; base += 64) {
+			const uint32_t p = base + lane;
+			const bool have = p < n;
+			uint32_t cand = 0, mlen = 0, v3 = 0;
+			const bool can = have && p + 3u <= n;
+			if (can) {
+				v3 = (uint32_t)in[p] | ((uint32_t)in[p + 1] << 8) | ((uint32_t)in[p + 2] << 16);
+				cand = tab[(v3 * 2654435761u) >> (32 - DFL_HASH_BITS)];
+			}
+			__builtin_amdgcn_wave_barrier();
+			bool ok = false;
+			if (can) {
+				tab[(v3 * 2654435761u) >> (32 - DFL_HASH_BITS)] = (uint16_t)p;
+				if (cand < p && p - cand <= 32768u) {
+					const uint32_t c3 = (uint32_t)in[cand] | ((uint32_t)in[cand + 1] << 8) | ((uint32_t)in[cand + 2] << 16);
+					if (c3 == v3) {
+						const uint32_t lim = n - p < 258u ? n - p : 258u;
+						mlen = 3;
+						while (mlen < lim && in[p + mlen] == in[cand + mlen])
+							mlen++;
+						ok = true;
+					}
+				}
+			}
+			bool covered = have && p < anchor, taken = false;
+			uint64_t mask = __ballot(ok);
+			while (mask != 0) {
+				const uint32_t f = (uint32_t)__builtin_ctzll(mask);
+				mask &= mask - 1;
+				const uint32_t pf = base + f;
+				if (pf < anchor)
+					continue;
+				const uint32_t mf = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)f);
+				if (lane == f)
+					taken = true;
+				covered = covered || (p > pf && p < pf + mf);
+				anchor = pf + mf;
+			}
+			const bool tok = have && !covered;
+			uint32_t t = 0;
+			if (tok) {
+				if (taken) {
+					uint32_t leb, lex, deb, dex;
+					atomicAdd(&hist[dfl_len_code(mlen, &leb, &lex)], 1u);
+					atomicAdd(&hist[DFL_DOFF + dfl_dist_code(p - cand, &deb, &dex)], 1u);
+					xbits += leb + deb;
+					nmatch++;
+					t = DFL_TOK_MATCH | ((mlen - 3u) << 16) | (p - cand - 1u);
+				} else {
+					t = in[p];
+					atomicAdd(&hist[t], 1u);
+				}
+			}
+			const uint64_t tb = __ballot(tok);
+			if (tok)
+				toks[ntok + (uint32_t)__builtin_popcountll(tb & below)] = t;
+			ntok += (uint32_t)__builtin_popcountll(tb);
+		}
+		xbits = wave_sum(xbits);
+		nmatch = wave_sum(nmatch);
+		__syncthreads();	/* histograms complete; the tokens are visible to the whole wave */
+		if (lane == 0)
+			hist[256] = 1;	/* end-of-block */
+		__syncthreads();
+
+		/* ---- the two codes; the cost of the symbols under them and under the fixed code ---- */
+		uint32_t F[5], Ls[5], Fd[1], Ld[1];
+		uint32_t dyn_bits = 0, fix_bits = 0, top = 0;
+#pragma unroll
+		for (int k = 0; k < 5; k++) {
+			const uint32_t s = lane + 64u * k;
+			F[k] = s < DFL_NLL ? hist[s] : 0;
+		}
+		bool complete = dfl_code_lengths<5>(F, Ls, 15u, lane);
+#pragma unroll
+		for (int k = 0; k < 5; k++) {
+			const uint32_t s = lane + 64u * k;
+			dyn_bits += F[k] * Ls[k];
+			fix_bits += F[k] * fixed_lit_len(s);
+			if (Ls[k])
+				top = s;
+		}
+		const uint32_t fd = lane < DFL_ND ? hist[DFL_DOFF + lane] : 0;
+		Fd[0] = dfl_force_two(fd, lane);
+		complete = dfl_code_lengths<1>(Fd, Ld, 15u, lane) && complete;
+		dyn_bits += fd * Ld[0];
+		dyn_bits = wave_sum(dyn_bits) + xbits;
+		fix_bits = wave_sum(fix_bits) + 5u * nmatch + xbits + 3u;
+		const uint32_t nlit = wave_max(top) + 1u;			/* 257 .. 286 */
+		const uint32_t ndist = wave_max(Ld[0] ? lane : 0u) + 1u;	/* 2 .. 30 */
+
+		/* ---- the header: both length arrays as one run-length coded sequence (one lane: 316 steps at most) ---- */
+#pragma unroll
+		for (int k = 0; k < 5; k++)
+			code[lane + 64u * k] = Ls[k];	/* lengths for now; the codes replace them below */
+		__builtin_amdgcn_wave_barrier();
+		if (lane < DFL_ND)
+			code[DFL_DOFF + lane] = Ld[0];
+		__syncthreads();
+		if (lane == 0) {
+			const uint32_t total = nlit + ndist;
+			uint32_t nc = 0, i = 0;
+			while (i < total) {
+				const uint32_t v = code[i < nlit ? i : DFL_DOFF + i - nlit];
+				uint32_t run = 1;
+				while (i + run < total && code[i + run < nlit ? i + run : DFL_DOFF + i + run - nlit] == v)
+					run++;
+				i += run;
+				if (v != 0) {
+					cls[nc++] = (uint16_t)v; clh[v]++;
+					run--;
+				}
+				while (run >= 3u) {
+					uint32_t r, sym, base;
+					if (v != 0) { sym = 16; base = 3; r = run < 6u ? run : 6u; }
+					else if (run < 11u) { sym = 17; base = 3; r = run; }
+					else { sym = 18; base = 11; r = run < 138u ? run : 138u; }
+					cls[nc++] = (uint16_t)(sym | ((r - base) << 8)); clh[sym]++;
+					run -= r;
+				}
+				for (; run > 0; run--) {
+					cls[nc++] = (uint16_t)v; clh[v]++;
+				}
+			}
+			hdr[0] = nc;
+			hdr[1] = 2u * clh[16] + 3u * clh[17] + 7u * clh[18];
+		}
+		__syncthreads();
+		const uint32_t ncls = hdr[0];
+		/* the code-length code, at most 7 bits; lane j < 19 also looks after place j of the RFC's order */
+		uint32_t Fc[1], Lc[1];
+		Fc[0] = dfl_force_two(lane < 19u ? clh[lane] : 0u, lane);
+		complete = dfl_code_lengths<1>(Fc, Lc, 7u, lane) && complete;
+		dfl_assign_codes<1>(Lc, 7u, clc, lane);
+		uint32_t hbits = wave_sum((lane < 19u ? clh[lane] : 0u) * Lc[0]) + hdr[1];
+		__syncthreads();
+		/* place j of the RFC's order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15 */
+		const uint32_t osym = lane < 3u ? 16u + lane : (uint32_t)((0xF1E2D3C4B5A69780ull >> (4u * ((lane - 3u) & 15u))) & 15u);
+		const uint32_t olen = lane < 19u ? (clc[osym] >> 16) : 0u;
+		uint32_t hclen = 64u - (uint32_t)__builtin_clzll(__ballot(olen != 0) | 1u);
+		hclen = hclen < 4u ? 4u : hclen;
+		dyn_bits += 3u + 14u + 3u * hclen + hbits;
+
+		/* ---- the smallest of the three; a stored block is n + 5 bytes and is not written here ---- */
+		const uint32_t dyn_bytes = (dyn_bits + 7u) >> 3, fix_bytes = (fix_bits + 7u) >> 3;
+		const bool dyn = complete && dyn_bytes < fix_bytes;
+		const uint32_t bytes = dyn ? dyn_bytes : fix_bytes;
+		if (bytes >= n + 5u) {
+			if (lane == 0)
+				body_len[ci] = n + 5u;
+			continue;
+		}
+		const auto put = [&](uint32_t i, uint32_t w) { if (i < tmp_stride / 4u) out[i] = w; };	/* (bytes < n + 5 fits) */
+		uint64_t bp = 0;
+		if (dyn) {
+			dfl_assign_codes<5>(Ls, 15u, code, lane);
+			__builtin_amdgcn_wave_barrier();
+			dfl_assign_codes<1>(Ld, 15u, code + DFL_DOFF, lane);
+			__syncthreads();
+			/* BFINAL = 1, BTYPE = 10, HLIT, HDIST, HCLEN from lane 0; the code-length code's lengths from lanes 1 .. HCLEN */
+			const uint32_t prev = (uint32_t)__shfl_up((int)olen, 1, 64);
+			uint64_t hb = prev;
+			uint32_t hn = lane <= hclen ? 3u : 0u;
+			if (lane == 0) {
+				hb = 5u | ((nlit - 257u) << 3) | ((ndist - 1u) << 8) | ((hclen - 4u) << 13);
+				hn = 17u;
+			}
+			bp += wave_bits_append64(bp, hb, hn, stage, lane, put);
+			for (uint32_t b0 = 0; b0 < ncls; b0 += 64) {
+				uint64_t v = 0;
+				uint32_t nb = 0;
+				if (b0 + lane < ncls) {
+					const uint32_t c = cls[b0 + lane], sym = c & 255u, cc = clc[sym];
+					nb = cc >> 16;
+					v = (cc & 0xFFFFu) | ((c >> 8) << nb);
+					nb += sym == 16u ? 2u : (sym == 17u ? 3u : (sym == 18u ? 7u : 0u));
+				}
+				bp += wave_bits_append64(bp, v, nb, stage, lane, put);
+			}
+		} else {
+#pragma unroll
+			for (int k = 0; k < 5; k++) {
+				uint32_t nb;
+				const uint32_t s = lane + 64u * k, c = fixed_lit(s, &nb);
+				code[s] = s < DFL_NLL ? (c | (nb << 16)) : 0u;
+			}
+			__builtin_amdgcn_wave_barrier();
+			if (lane < DFL_ND)
+				code[DFL_DOFF + lane] = rev_bits(lane, 5) | (5u << 16);
+			__syncthreads();
+			bp += wave_bits_append64(bp, 3u, lane == 0 ? 3u : 0u, stage, lane, put);	/* BFINAL = 1, BTYPE = 01 */
+		}
+
+		/* ---- pass 2: the tokens, 64 at a time, then end-of-block from the lane after the last one ---- */
+		for (uint32_t b0 = 0; b0 <= ntok; b0 += 64) {
+			uint64_t v = 0;
+			uint32_t nb = 0;
+			if (b0 + lane < ntok) {
+				const uint32_t t = toks[b0 + lane];
+				if (t & DFL_TOK_MATCH) {
+					uint32_t leb, lex, deb, dex;
+					const uint32_t cl = code[dfl_len_code(((t >> 16) & 255u) + 3u, &leb, &lex)];
+					const uint32_t cd = code[DFL_DOFF + dfl_dist_code((t & 0x7FFFu) + 1u, &deb, &dex)];
+					nb = cl >> 16;
+					v = (cl & 0xFFFFu) | (lex << nb);
+					nb += leb;
+					v |= (uint64_t)((cd & 0xFFFFu) | (dex << (cd >> 16))) << nb;
+					nb += (cd >> 16) + deb;
+				} else {
+					const uint32_t cl = code[t];
+					v = cl & 0xFFFFu;
+					nb = cl >> 16;
+				}
+			} else if (b0 + lane == ntok) {
+				v = code[256] & 0xFFFFu;
+				nb = code[256] >> 16;
+			}
+			bp += wave_bits_append64(bp, v, nb, stage, lane, put);
+		}
+		if (lane == 0) {
+			if (bp & 31u)
+				out[bp >> 5] = stage[0];
+			body_len[ci] = (uint32_t)((bp + 7) >> 3);	/* == bytes */
+		}
+	}
+}
+
 __global__ __launch_bounds__(256) void gz_jobs_kernel(uint64_t src_bytes, uint32_t chunk, uint32_t n_chunks,
     const uint32_t *__restrict__ body_len, la_hash_job *__restrict__ jobs, uint32_t *__restrict__ contrib)
 {
@@ -221,10 +652,11 @@ struct gzc_ws {
 	la_hash_job *jobs;
 	uint64_t *off;
 	void *scan;
+	uint32_t *toks;	/* deflate_dynamic_kernel: `chunk` tokens per wave */
 };
 
 /* the launcher's workspace on `base` (null: sizes only); returns its bytes before the scan scratch */
-static uint64_t gzc_carve(gzc_ws *w, uint8_t *base, uint64_t nc, uint32_t stride)
+static uint64_t gzc_carve(gzc_ws *w, uint8_t *base, uint64_t nc, uint32_t stride, uint32_t chunk, uint32_t options)
 {
 	la_carve c = { base, 0 };
 	w->tmp = c.take<uint8_t>(nc * stride);
@@ -233,19 +665,26 @@ static uint64_t gzc_carve(gzc_ws *w, uint8_t *base, uint64_t nc, uint32_t stride
 	w->crc = c.take<uint32_t>(nc);
 	w->jobs = c.take<la_hash_job>(nc, 16);
 	w->off = c.take<uint64_t>(nc + 1);
+	w->toks = c.take<uint32_t>(options == LA_GZC_DYNAMIC ? (nc < DFL_WAVES ? nc : DFL_WAVES) * chunk : 0, 16);
 	w->scan = c.take<uint8_t>(0, 256);
 	return c.off;
 }
 
 static uint32_t gzc_stride(uint32_t chunk) { return (dfl_body_bound(chunk) + 15u) & ~15u; }
 
-extern "C" uint64_t la_gpu_gzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t chunk)
+/* the workspace one mode needs; the public function answers for the largest, LA_GZC_DYNAMIC */
+uint64_t la_gzip_compress_ws_bytes(uint64_t src_bytes, uint32_t chunk, uint32_t options)
 {
 	if (chunk == 0)
 		return 0;
 	const uint64_t nc = (src_bytes + chunk - 1) / chunk;
 	gzc_ws w;
-	return gzc_carve(&w, nullptr, nc, gzc_stride(chunk)) + la_scan_scratch_bytes((uint32_t)nc);
+	return gzc_carve(&w, nullptr, nc, gzc_stride(chunk), chunk, options) + la_scan_scratch_bytes((uint32_t)nc);
+}
+
+extern "C" uint64_t la_gpu_gzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t chunk)
+{
+	return la_gzip_compress_ws_bytes(src_bytes, chunk, LA_GZC_DYNAMIC);
 }
 
 extern "C" uint64_t la_gpu_gzip_compress_bound(uint64_t src_bytes, uint32_t chunk)
@@ -257,17 +696,23 @@ extern "C" uint64_t la_gpu_gzip_compress_bound(uint64_t src_bytes, uint32_t chun
 }
 
 void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t chunk, uint32_t mtime,
-    uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws)
+    uint32_t options, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws)
 {
 	const uint32_t nc = (uint32_t)((src_bytes + chunk - 1) / chunk);
 	const uint32_t stride = gzc_stride(chunk);
 	gzc_ws w;
-	gzc_carve(&w, ws, nc, stride);
+	gzc_carve(&w, ws, nc, stride, chunk, options);
 	if (nc == 0) {
 		(void)hipMemsetAsync(d_out_bytes, 0, 8, s);
 		return;
 	}
-	hipLaunchKernelGGL(deflate_fixed_kernel, dim3(nc), dim3(64), 0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len);
+	if (options == LA_GZC_STORED)	/* a body length no chunk can have: every member comes out stored */
+		(void)hipMemsetAsync(w.body_len, 0xFF, (uint64_t)nc * 4u, s);
+	else if (options == LA_GZC_DYNAMIC)
+		hipLaunchKernelGGL(deflate_dynamic_kernel, dim3(nc < DFL_WAVES ? nc : DFL_WAVES), dim3(64), 0, s, d_src, src_bytes, chunk, nc,
+		    w.tmp, stride, w.body_len, w.toks);
+	else
+		hipLaunchKernelGGL(deflate_fixed_kernel, dim3(nc), dim3(64), 0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len);
 	hipLaunchKernelGGL(gz_jobs_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.jobs, w.contrib);
 	la_launch_crc32_many(s, d_src, w.jobs, nc, w.crc);
 	la_launch_scan_u32(s, w.contrib, nc, w.off, w.scan);

@@ -63,23 +63,6 @@ struct zc_lds {
 };
 static_assert(sizeof(zc_fse_lds) <= sizeof(uint32_t) * (1u << LZ77_HASH_BITS), "FSE tables must fit in the match table");
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1)
-		v += (uint32_t)__shfl_xor((int)v, d, 64);
-	return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = (uint32_t)__shfl_xor((int)v, d, 64);
-		v = o > v ? o : v;
-	}
-	return v;
-}
-
 /* literal-length / match-length codes (RFC 8878 3.1.1.3.2.1.1) */
 __device__ __forceinline__ uint32_t ll_code(uint32_t ll)
 {

@@ -37,9 +37,10 @@ class GzDevicePlan:
         return self.d_results.cpu().numpy().view(N.GZ_RESULT_DTYPE)[:self.n]
 
 
-def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0):
+def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0, options=0):
     """Device gzip compression (la_gpu_gzip_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8 CUDA
-    tensor holding the concatenated gzip members (harness for the tests)."""
+    tensor holding the concatenated gzip members (harness for the tests).  options: 0 fixed Huffman, 1 the smallest of
+    dynamic Huffman, fixed Huffman and stored per chunk, 2 stored blocks only (LA_GZC_*)."""
     import torch
     from . import _native as N
     n = int(d_plain.numel())
@@ -49,7 +50,7 @@ def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0):
     b = N._GzcBatchC()
     b.d_src = d_plain.data_ptr() if n else None
     b.src_bytes = n
-    b.chunk_bytes, b.mtime = chunk_bytes, mtime
+    b.chunk_bytes, b.mtime, b.options = chunk_bytes, mtime, options
     b.d_out, b.out_cap, b.d_out_bytes = d_out.data_ptr(), cap, d_len.data_ptr()
     ctx.gzip_compress(b)
     ctx.sync()

@@ -21,8 +21,10 @@
  * options "compression-level" and "timestamp" :142-167) works the same way on la_gpu_gzip_compress(): the stream
  * is a sequence of members of at most 48 KiB of input each, every one with the BGZF-compatible size subfield, so
  * that the read side indexes them without searching (every gzip reader reads concatenated members:
- * archive_read_support_filter_gzip.c:340-365).  "compression-level" 0..9 is accepted and means the one level the
- * device has (fixed Huffman codes; chunks that do not shrink are stored).
+ * archive_read_support_filter_gzip.c:340-365).  "compression-level" 0..9 selects what the device has: 0 stored
+ * blocks (what zlib's level 0 writes), 1 fixed Huffman codes (the fast level), 2..9 and the default 6 the smallest
+ * of a dynamic-Huffman, a fixed-Huffman and a stored block per chunk (LA_GZC_* in la_gpu.h).  The matcher is the
+ * same at every level.
  *
  * The write core below is the minimum the filters need outside libarchive: archive_write_new,
  * _add_filter_lz4, _set_format_raw (one entry, data passed through: archive_write_set_format_raw.c),
@@ -467,7 +469,7 @@ static int gzw_options(struct archive_write_filter *f, const char *key, const ch
 	if (strcmp(key, "compression-level") == 0) {	/* archive_write_add_filter_gzip.c:147-153 */
 		if (value == NULL || !(value[0] >= '0' && value[0] <= '9') || value[1] != '\0')
 			return ARCHIVE_WARN;
-		d->compression_level = value[0] - '0';	/* (the device has one level) */
+		d->compression_level = value[0] - '0';	/* gzw_compress turns it into a LA_GZC_* mode */
 		return ARCHIVE_OK;
 	}
 	if (strcmp(key, "timestamp") == 0) {		/* :154-157 */
@@ -486,6 +488,7 @@ static int gzw_compress(struct archive_write_filter *f, const struct la_write_wi
 	memset(&bt, 0, sizeof(bt));
 	bt.d_src = w->d_in; bt.src_bytes = w->len; bt.chunk_bytes = GZW_CHUNK; bt.mtime = d->mtime;
 	bt.d_out = w->d_out; bt.out_cap = w->out_cap; bt.d_out_bytes = w->d_len;
+	bt.options = d->compression_level == 0 ? LA_GZC_STORED : (d->compression_level == 1 ? LA_GZC_FIXED : LA_GZC_DYNAMIC);
 	return la_gpu_gzip_compress(w->gpu, &bt);
 }
 
@@ -526,7 +529,7 @@ int archive_write_add_filter_gzip(struct archive *_a)
 	d->w.name = "gzip";
 	d->w.bound = gzw_bound;
 	d->w.compress = gzw_compress;
-	d->compression_level = 6;	/* Z_DEFAULT_COMPRESSION in the reference; informational here */
+	d->compression_level = 6;	/* Z_DEFAULT_COMPRESSION in the reference: dynamic Huffman here */
 	f->data = d;
 	f->options = gzw_options;
 	f->open = gzw_open;

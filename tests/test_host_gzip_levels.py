@@ -1,0 +1,82 @@
+"""CPU-only: the gzip write filter's compression levels and the C ABI field that carries them.  la_gzc_batch ends in
+`options` / `reserved` (LA_GZC_*): the struct a C compiler lays out from include/la_gpu.h must be the one ctypes
+builds in libarchive_amd/_native.py.  The filter's option table is archive_write_add_filter_gzip.c:142-167; against the
+CPU mock (whose members are stored blocks and which ignores the field) every level still round-trips."""
+import ctypes as C
+import gzip
+import io
+import os
+import random
+import subprocess
+
+import pytest
+
+import la_api
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+MOCK_DIR = os.path.join(HERE, "mock_gpu")
+ARCHIVE_OK, ARCHIVE_WARN, ARCHIVE_FAILED = 0, -20, -25
+
+
+def test_batch_struct_layout_matches_ctypes(tmp_path):
+    from libarchive_amd import _native as N
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "la_gpu.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %u %u %u\\n", sizeof(la_gzc_batch), offsetof(la_gzc_batch, options),\n'
+                   '    offsetof(la_gzc_batch, reserved), LA_GZC_FIXED, LA_GZC_DYNAMIC, LA_GZC_STORED); return 0; }\n')
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-std=gnu11", "-Wall", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    size, off_opt, off_res, fixed, dynamic, stored = map(int, subprocess.check_output([str(exe)]).split())
+    assert (size, off_opt, off_res) == (C.sizeof(N._GzcBatchC), N._GzcBatchC.options.offset, N._GzcBatchC.reserved.offset)
+    assert (size, off_opt, off_res) == (56, 48, 52)        # x86-64
+    assert (fixed, dynamic, stored) == (N.LA_GZC_FIXED, N.LA_GZC_DYNAMIC, N.LA_GZC_STORED) == (0, 1, 2)
+    assert N._GzcBatchC().options == 0                      # a zeroed struct asks for the fixed-Huffman mode
+
+
+@pytest.fixture(scope="module")
+def mock_writer():
+    import test_gpu_lz4_write as W
+    subprocess.check_call(["make", "-s", "-C", MOCK_DIR])
+    mock = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
+    la_api.use_library(mock)
+    saved = W._lib
+    W._lib = lambda: W._lib_setup(mock)
+    yield W
+    W._lib = saved
+    la_api.use_library(None)
+
+
+def test_option_table(mock_writer):
+    W = mock_writer
+    lib = W._lib()
+
+    def set_option(key, value):
+        a = lib.archive_write_new()
+        assert lib.archive_write_add_filter_gzip(a) == ARCHIVE_OK
+        # the filter's own verdict: name the module, so that ARCHIVE_WARN comes back as FAILED "Undefined option"
+        rc = lib.archive_write_set_filter_option(a, b"gzip", key.encode(), None if value is None else value.encode())
+        lib.archive_write_free(a)
+        return rc
+
+    for level in "0123456789":
+        assert set_option("compression-level", level) == ARCHIVE_OK
+    for bad in ("10", "x", "", "-1", None):
+        assert set_option("compression-level", bad) == ARCHIVE_FAILED, bad
+    assert set_option("timestamp", "1") == ARCHIVE_OK
+    assert set_option("timestamp", None) == ARCHIVE_OK      # "!timestamp"
+    assert set_option("no-such-option", "1") == ARCHIVE_FAILED
+
+
+def test_levels_round_trip_on_an_abi_that_ignores_the_field(mock_writer, monkeypatch):
+    W = mock_writer
+    monkeypatch.setenv("LA_GPU_WRITE_WINDOW_MIB", "1")
+    rnd = random.Random(41)
+    words = [rnd.randbytes(rnd.randint(2, 10)) for _ in range(100)]
+    text = b"".join(rnd.choice(words) for _ in range(300000))[:(1 << 20) + 4321]
+    for data, piece in ((b"", None), (b"q", None), (text, 65537), (rnd.randbytes(70000), 7)):
+        for level in ("0", "1", "9"):
+            rc, img = W.write_lz4(data, (("compression-level", level), ("timestamp", None)), piece, codec="gzip")
+            assert rc == ARCHIVE_OK and img[:3] == b"\x1f\x8b\x08"
+            assert gzip.GzipFile(fileobj=io.BytesIO(img)).read() == data
+            assert la_api.cat(img).data == data
