@@ -362,7 +362,11 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 	HIPCHK(c, hipStreamWaitEvent(sp, c->slice_ev[LA_MAX_SLICES], 0));
 
 	/* second stream: token-chain parse (+ sequence tables) of the whole batch.  One lane per
-	 * block: it needs the whole table in one launch to fill the chip. */
+	 * block: it needs the whole table in one launch to fill the chip.  Parsing slice by slice
+	 * beside the expand launches was measured and is slower (profiles/r06_parse_pipeline.md):
+	 * the parse's small workgroups take every LDS gap a finished expand workgroup leaves, the
+	 * expand kernel stands still until they are through, and four partial rounds of the parse
+	 * cost 7.2 ms where one launch costs 4.4. */
 	if (n)
 		HIPCHK(c, hipMemsetAsync(bt->d_block_status, 0, (size_t)n * sizeof(uint32_t), sp));
 	if (fast) {

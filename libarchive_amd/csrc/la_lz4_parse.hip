@@ -43,23 +43,24 @@
 #define LZ4_MFLIMIT 12
 #define LZ4_LASTLIT 5
 
-#ifndef PS_CH
-#define PS_CH 128u		/* bytes of every block staged per round (multiple of 16).  Measured on the
-				 * 16 GiB workload: 32 -> 9.9 ms, 64 -> 6.0, 128 -> 5.2, 256 -> 8.4 (a larger
-				 * ring lets lanes drift further apart before they wait for each other, but
-				 * LDS per wave sets how many waves a CU holds) */
-#endif
+/* The kernel's two LDS sizes are template parameters (spelt like the macros derived from them):
+ *   PS_CH     bytes of every block staged per round (multiple of 16).  Measured on the 16 GiB
+ *             workload, whole table in one launch on an empty chip: 32 -> 9.9 ms, 64 -> 6.0,
+ *             128 -> 5.2, 256 -> 8.4 (a larger ring lets lanes drift further apart before they
+ *             wait for each other, but LDS per wave sets how many waves a CU holds)
+ *   PS_STAGE  staged table entries per lane (a power of two; they leave in groups of
+ *             min(PS_STAGE, 8))
+ * la_launch_lz4_parse_staged() picks the pair by the rounds of waves a launch needs (below). */
 #ifndef PS_THREADS
 #define PS_THREADS 64u		/* waves of a workgroup share nothing: the size only sets the LDS granule */
 #endif
-#ifndef PS_STAGE
-#define PS_STAGE   16u		/* staged table entries per lane (two groups of eight) */
-#endif
 #define PS_WAVES   (PS_THREADS / 64u)
+#define PS_GROUP   (PS_STAGE < 8u ? PS_STAGE : 8u)	/* table entries per store burst */
 #define PS_RINGW   (2u * PS_CH / 4u)	/* ring = two chunks, in dwords (power of two) */
 #define PS_PIECES  (PS_CH / 16u)	/* 16-byte pieces per chunk = load instructions per round */
 #define PS_BPI     (64u / PS_PIECES)	/* blocks covered by one load instruction */
 
+template <uint32_t PS_CH>
 struct ps_loader {
 	uint64_t ptr[PS_PIECES];	/* image offset of this lane's piece 0-chunk for instruction i */
 	uint32_t need[PS_PIECES];	/* payload bytes to stage for that block */
@@ -67,7 +68,8 @@ struct ps_loader {
 };
 
 /* issue the loads of chunk c (PS_PIECES x 16 bytes per lane) */
-__device__ __forceinline__ void ps_load_chunk(const uint8_t *__restrict__ src, const ps_loader &L,
+template <uint32_t PS_CH>
+__device__ __forceinline__ void ps_load_chunk(const uint8_t *__restrict__ src, const ps_loader<PS_CH> &L,
     uint32_t c, uint32_t piece, uint4 (&fl)[PS_PIECES])
 {
 #pragma unroll
@@ -90,7 +92,7 @@ __device__ __forceinline__ void ps_load_chunk(const uint8_t *__restrict__ src, c
 	}
 }
 
-template <bool EMIT, bool SUMS>
+template <uint32_t PS_CH, uint32_t PS_STAGE, bool EMIT, bool SUMS>
 __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint8_t *__restrict__ src,
     uint64_t src_bytes, const la_lz4_block *__restrict__ blocks, uint32_t n,
     uint32_t *__restrict__ out_len, uint32_t *__restrict__ nseq_out, uint32_t *__restrict__ status,
@@ -98,8 +100,8 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
     const uint64_t *__restrict__ table_off, uint64_t table_cap)
 {
 	__shared__ uint32_t ring[PS_WAVES][PS_RINGW + 4u][64];	/* last rows = copies of rows 0..3: up to five consecutive dwords never wrap */
-	/* table entries wait here (transposed: conflict free) and leave in groups of eight = one
-	 * aligned 64-byte burst per lane (see la_lz4.hip), at the START of a round: the stores
+	/* table entries wait here (transposed: conflict free) and leave in groups of PS_GROUP (eight = one
+	 * aligned 64-byte burst per lane, see la_lz4.hip), at the START of a round: the stores
 	 * then have a whole round of LDS-only work to complete in before the wave next waits on
 	 * its memory counter (gfx950 counts loads and stores in one in-order counter, so a store
 	 * issued just before the wait for the next chunk would put its full latency on the path) */
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 	const uint32_t stage_len = (do_parse || do_sum) ? b.src_len + sk : 0u;	/* staged bytes, from the chunk grid */
 
 	/* ---- loader set-up: which block and piece this lane fetches in instruction i ---- */
-	ps_loader L;
+	ps_loader<PS_CH> L;
 	const uint32_t piece = lane % PS_PIECES;
 #pragma unroll
 	for (uint32_t k = 0; k < PS_PIECES; k++) {
@@ -168,11 +170,11 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 
 	uint4 fl[PS_PIECES];
 	if (nrounds) {
-		ps_load_chunk(src, L, 0, piece, fl);
+		ps_load_chunk<PS_CH>(src, L, 0, piece, fl);
 		PS_STORE_CHUNK(0u);
-		ps_load_chunk(src, L, 1, piece, fl);
+		ps_load_chunk<PS_CH>(src, L, 1, piece, fl);
 		PS_STORE_CHUNK(1u);
-		ps_load_chunk(src, L, 2, piece, fl);
+		ps_load_chunk<PS_CH>(src, L, 2, piece, fl);
 	}
 
 	/* ---- per-lane parse state ---- */
@@ -199,19 +201,19 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 		    ((uint64_t)(uint16_t)(lit_len_) << 16) | ((uint64_t)(uint16_t)(dst_) << 32) |  \
 		    ((uint64_t)(uint16_t)(off_) << 48);                                            \
 	} while (0)
-	uint32_t nfl = 0;	/* entries already written to the table (multiple of 8) */
-	/* write every complete group of eight staged entries */
+	uint32_t nfl = 0;	/* entries already written to the table (multiple of PS_GROUP) */
+	/* write every complete group of staged entries */
 	auto flush_groups = [&]() {
-		while (__ballot(emit && nseq - nfl >= 8u) != 0) {
-			if (emit && nseq - nfl >= 8u) {
-				const uint32_t g = nfl & (PS_STAGE - 1u);	/* 0 or 8 */
+		while (__ballot(emit && nseq - nfl >= PS_GROUP) != 0) {
+			if (emit && nseq - nfl >= PS_GROUP) {
+				const uint32_t g = nfl & (PS_STAGE - 1u);	/* a multiple of PS_GROUP */
 				uint4 *o4 = (uint4 *)(tab + nfl);
 #pragma unroll
-				for (int j = 0; j < 4; j++) {
+				for (uint32_t j = 0; j < PS_GROUP / 2u; j++) {
 					const uint64_t a_ = stage[g + 2 * j][threadIdx.x], b_ = stage[g + 2 * j + 1][threadIdx.x];
 					o4[j] = make_uint4((uint32_t)a_, (uint32_t)(a_ >> 32), (uint32_t)b_, (uint32_t)(b_ >> 32));
 				}
-				nfl += 8u;
+				nfl += PS_GROUP;
 			}
 		}
 	};
@@ -394,7 +396,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 
 		/* ---- chunk r is spent: chunk r+2 takes its slot, chunk r+3 goes in flight ---- */
 		PS_STORE_CHUNK(r + 2u);
-		ps_load_chunk(src, L, r + 3u, piece, fl);
+		ps_load_chunk<PS_CH>(src, L, r + 3u, piece, fl);
 	}
 	if (SUMS && do_sum && !hfin && b.src_len == 0) {	/* (an empty payload on a grid point stages nothing) */
 		if (xxh_avalanche(XXH_P5) != b.block_sum)
@@ -417,7 +419,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 	if (EMIT)
 		flush_groups();
 	if (emit && ok)
-		for (uint32_t j = nfl; j < nseq; j++)	/* the last, incomplete group of eight */
+		for (uint32_t j = nfl; j < nseq; j++)	/* the last, incomplete group */
 			tab[j] = stage[j & (PS_STAGE - 1u)][threadIdx.x];
 #undef EMIT_SEQ
 #undef PS_STORE_CHUNK
@@ -428,23 +430,49 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 		status[i] = LA_ST_LZ4_DECODE;
 }
 
+template <uint32_t PS_CH, uint32_t PS_STAGE>
+static void ps_launch(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
+    const la_lz4_block *d_blocks, uint32_t n, uint32_t *d_out_len, uint32_t *d_nseq,
+    uint32_t *d_status, uint32_t *d_sum_status, la_lz4_seq *d_table, const uint64_t *d_table_off,
+    uint64_t table_cap)
+{
+	static_assert(PS_STAGE >= 2u && (PS_STAGE & (PS_STAGE - 1u)) == 0, "table entries leave in pairs at least");
+	const dim3 grid((n + PS_THREADS - 1) / PS_THREADS), wg(PS_THREADS);
+	if (d_table && d_sum_status)
+		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, true, true>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
+		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+	else if (d_table)
+		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, true, false>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
+		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+	else if (d_sum_status)
+		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, false, true>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
+		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+	else
+		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, false, false>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
+		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+}
+
+/* Waves the chip holds of the two shapes the launcher knows: LDS per wave (ring + stage) sets how many fit on
+ * a CU's 160 KiB, gfx950 has 256 CUs.  A lane walks its whole block, so a launch runs in rounds of that many
+ * waves and a round lasts as long as the serial walk of a block whatever the number of waves in it. */
+#define PS_CHIP_CUS       256u
+#define PS_WAVES_WIDE     (PS_CHIP_CUS * 6u)	/* <128, 16>: 25 600 B per wave */
+#define PS_WAVES_NARROW   (PS_CHIP_CUS * 8u)	/* <128, 4>:  19 456 B per wave */
+
 void la_launch_lz4_parse_staged(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_lz4_block *d_blocks, uint32_t n, uint32_t *d_out_len, uint32_t *d_nseq,
     uint32_t *d_status, uint32_t *d_sum_status, la_lz4_seq *d_table, const uint64_t *d_table_off,
     uint64_t table_cap)
 {
 	if (n == 0) return;
-	const dim3 grid((n + PS_THREADS - 1) / PS_THREADS), wg(PS_THREADS);
-	if (d_table && d_sum_status)
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<true, true>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
-	else if (d_table)
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<true, false>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
-	else if (d_sum_status)
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<false, true>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+	/* The sixteen-entry stage (two bursts of 64 bytes per lane) is the faster wave; the four-entry one puts
+	 * eight waves on a CU instead of six.  It is taken where that saves a round: the 16 GiB workload's 4 096
+	 * waves are three rounds of 1 536 (the last one two thirds full) or two full rounds of 2 048, 5.2 -> 4.5 ms. */
+	const uint32_t waves = (n + 63u) / 64u;
+	const uint32_t rounds_wide = (waves + PS_WAVES_WIDE - 1u) / PS_WAVES_WIDE;
+	const uint32_t rounds_narrow = (waves + PS_WAVES_NARROW - 1u) / PS_WAVES_NARROW;
+	if (rounds_narrow < rounds_wide)
+		ps_launch<128u, 4u>(s, d_src, src_bytes, d_blocks, n, d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
 	else
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<false, false>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+		ps_launch<128u, 16u>(s, d_src, src_bytes, d_blocks, n, d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
 }
