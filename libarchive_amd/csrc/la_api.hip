@@ -54,6 +54,14 @@ static void prof_close(la_gpu_ctx *c, int h, hipStream_t s)
 		(void)hipEventRecord(c->prof_b[h], s);
 }
 
+template <typename Launch>
+static void prof_range(la_gpu_ctx *c, const char *name, hipStream_t s, Launch launch)	/* one named range around what launch() queues on s */
+{
+	const int h = prof_open(c, name, s);
+	launch();
+	prof_close(c, h, s);
+}
+
 #define HIPCHK(ctx, call)                                                              \
 	do {                                                                           \
 		hipError_t e_ = (call);                                                \
@@ -305,26 +313,27 @@ struct lz4_ws {
 	uint64_t total;
 };
 
-static void lz4_ws_layout(lz4_ws *w, uint8_t *base, uint32_t n, uint64_t src_bytes, bool with_table)
+/* (every field starts on a 256-byte boundary; the total is rounded up likewise, plus 4 KiB of slack) */
+static void lz4_ws_carve(lz4_ws *w, uint8_t *base, uint32_t n, uint64_t src_bytes, bool with_table)
 {
-	uint64_t o = 0;
-	w->nseq = (uint32_t *)(base + o); o += align_up((uint64_t)n * 4, 256);
-	w->caps = (uint32_t *)(base + o); o += align_up((uint64_t)n * 4, 256);
-	w->sum_status = (uint32_t *)(base + o); o += align_up((uint64_t)n * 4, 256);
-	w->big = (uint32_t *)(base + o); o += align_up((uint64_t)(n + 1) * 4, 256);
-	w->table_off = (uint64_t *)(base + o); o += align_up(((uint64_t)n + 1) * 8, 256);
-	w->scan = base + o; o += align_up(la_scan_scratch_bytes(n), 256);
+	la_carve cv = { base, 0 };
+	w->nseq = cv.take<uint32_t>(n, 256);
+	w->caps = cv.take<uint32_t>(n, 256);
+	w->sum_status = cv.take<uint32_t>(n, 256);
+	w->big = cv.take<uint32_t>(n + 1, 256);
+	w->table_off = cv.take<uint64_t>((uint64_t)n + 1, 256);
+	w->scan = cv.take<uint8_t>(la_scan_scratch_bytes(n), 256);
 	/* a non-final sequence takes >= 3 payload bytes; slots are rounded up to 8 entries:
 	 * sum((src_len/3 + 1 + 7) & ~7) <= src_bytes/3 + 8n */
 	w->table_cap = with_table ? src_bytes / 3 + 8ull * n : 0;
-	w->table = (la_lz4_seq *)(base + o); o += align_up(w->table_cap * sizeof(la_lz4_seq), 256);
-	w->total = o + 4096;
+	w->table = cv.take<la_lz4_seq>(w->table_cap, 256);
+	w->total = align_up(cv.off, 256) + 4096;
 }
 
 uint64_t la_gpu_lz4_workspace_bytes(uint32_t n_blocks, uint64_t src_bytes)
 {
 	lz4_ws w;
-	lz4_ws_layout(&w, NULL, n_blocks, src_bytes, true);
+	lz4_ws_carve(&w, NULL, n_blocks, src_bytes, true);
 	return w.total;
 }
 
@@ -332,29 +341,30 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 {
 	if (!c || !bt)
 		return LA_ERR_ARG;
-	if (bt->n_blocks && (!bt->d_src || !bt->d_blocks || !bt->d_dst || !bt->d_out_len ||
-	    !bt->d_dst_off || !bt->d_block_status))
+	/* (d_dst_off even for an empty batch: the scan writes its one total there) */
+	if (!bt->d_dst_off || (bt->n_blocks && (!bt->d_src || !bt->d_blocks || !bt->d_dst || !bt->d_out_len ||
+	    !bt->d_block_status)))
 		return LA_ERR_ARG;
 	if (bt->n_frames && (!bt->d_frames || !bt->d_frame_status))
-		return LA_ERR_ARG;
-	if (!bt->d_dst_off)
 		return LA_ERR_ARG;
 	const bool fast = !(bt->options & LA_LZ4_OPT_GENERAL_ONLY);
 	const bool verify = !(bt->options & LA_LZ4_OPT_NO_VERIFY);
 	/* the in-order expand kernel runs on request (cross-check); not for images of less than 16 bytes */
 	const bool poll = (bt->options & LA_LZ4_OPT_EXPAND_INORDER) == 0 || !la_lz4_expand_inorder_takes(bt->src_bytes);
 	lz4_ws w;
-	lz4_ws_layout(&w, NULL, bt->n_blocks, bt->src_bytes, fast);
+	lz4_ws_carve(&w, NULL, bt->n_blocks, bt->src_bytes, fast);
 	if (w.total > c->ws_bytes) {
 		int rc = la_gpu_reserve(c, w.total);
 		if (rc != LA_OK) return rc;
 	}
-	lz4_ws_layout(&w, (uint8_t *)c->ws, bt->n_blocks, bt->src_bytes, fast);
+	lz4_ws_carve(&w, (uint8_t *)c->ws, bt->n_blocks, bt->src_bytes, fast);
 	hipStream_t sx = c->stream;		/* main stream (the caller's): checksums, expand, summary */
 	hipStream_t sp = c->aux_stream;		/* second stream: parse beside the block checksums, frame
 						 * checksums beside the expand kernel */
 	const uint32_t n = bt->n_blocks;
-	int h;
+	const la_expand_job xj = {	/* every expand launch below is this job, or a slice of it */ bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_dst, bt->dst_cap, bt->d_dst_off,
+	    bt->d_out_len, bt->d_block_status, w.nseq, fast ? w.table : NULL, w.table_off,
+	    LA_LZ4_LONG_SEQ_BYTES };	/* blocks of few long sequences go to the general kernel (la_dev.h) */
 
 	prof_begin(c);
 	/* the second stream starts after whatever the caller queued on its stream */
@@ -379,68 +389,50 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 	if (verify && n)
 		HIPCHK(c, hipMemsetAsync(w.sum_status, 0, (size_t)n * sizeof(uint32_t), sp));
 	if (bt->options & LA_LZ4_OPT_PARSE_V1) {
-		if (verify && n) {
-			h = prof_open(c, "lz4_block_sums", sp);
-			la_launch_lz4_block_sums(sp, bt->d_src, bt->d_blocks, n, w.sum_status);
-			prof_close(c, h, sp);
-		}
-		h = prof_open(c, "lz4_parse", sp);
-		la_launch_lz4_parse(sp, bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_out_len, w.nseq,
-		    bt->d_block_status, fast ? w.table : NULL, w.table_off, w.table_cap);
-		prof_close(c, h, sp);
+		if (verify && n)
+			prof_range(c, "lz4_block_sums", sp, [&] { la_launch_lz4_block_sums(sp, bt->d_src, bt->d_blocks, n, w.sum_status); });
+		prof_range(c, "lz4_parse", sp, [&] {
+			la_launch_lz4_parse(sp, bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_out_len, w.nseq,
+			    bt->d_block_status, fast ? w.table : NULL, w.table_off, w.table_cap);
+		});
 	} else {
-		h = prof_open(c, "lz4_parse", sp);
-		la_launch_lz4_parse_staged(sp, bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_out_len, w.nseq,
-		    bt->d_block_status, verify ? w.sum_status : NULL, fast ? w.table : NULL, w.table_off, w.table_cap);
-		prof_close(c, h, sp);
+		prof_range(c, "lz4_parse", sp, [&] {
+			la_launch_lz4_parse_staged(sp, bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_out_len, w.nseq,
+			    bt->d_block_status, verify ? w.sum_status : NULL, fast ? w.table : NULL, w.table_off, w.table_cap);
+		});
 	}
 	HIPCHK(c, hipEventRecord(c->slice_ev[0], sp));
 
 	HIPCHK(c, hipStreamWaitEvent(sx, c->slice_ev[0], 0));
-	h = prof_open(c, "scan", sx);
-	la_launch_scan_u32(sx, bt->d_out_len, n, bt->d_dst_off, w.scan);
-	prof_close(c, h, sx);
+	prof_range(c, "scan", sx, [&] { la_launch_scan_u32(sx, bt->d_out_len, n, bt->d_dst_off, w.scan); });
 
 	/* blocks the LDS-window kernel does not take (any size, stored, chains of dependent
 	 * blocks) first, over the whole table; then the LDS-window kernel in slices, each
 	 * slice's frames hashed on the second stream while the next slice expands */
-	h = prof_open(c, fast ? "lz4_expand_general" : "lz4_expand", sx);
-	la_launch_lz4_expand_general(sx, bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_dst,
-	    bt->dst_cap, bt->d_dst_off, bt->d_out_len, bt->d_block_status, w.nseq,
-	    fast ? 0xFFFFFFFEu : 0u,	/* the LDS-window kernel takes every eligible block that got a table ... */
-	    bt->hist_len, LA_LZ4_LONG_SEQ_BYTES);	/* ... except blocks of few long sequences (la_dev.h) */
-	prof_close(c, h, sx);
-	if (fast && poll) {
+	prof_range(c, fast ? "lz4_expand_general" : "lz4_expand", sx, [&] { la_launch_lz4_expand_general(sx, xj, bt->hist_len); });
+	if (fast && poll)
 		/* eligible blocks with more sequences than one LDS segment: classified on the device, shared out over a
 		 * small grid (a no-op launch when there are none).  (The in-order kernel takes blocks of any sequence count.) */
-		h = prof_open(c, "lz4_expand_big", sx);
-		la_launch_lz4_expand_fast_big(sx, bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_dst, bt->dst_cap,
-		    bt->d_dst_off, bt->d_out_len, bt->d_block_status, w.nseq, w.table, w.table_off, w.big, LA_LZ4_LONG_SEQ_BYTES);
-		prof_close(c, h, sx);
-	}
+		prof_range(c, "lz4_expand_big", sx, [&] { la_launch_lz4_expand_fast_big(sx, xj, w.big); });
 	const uint32_t nsl = (fast && n >= 4u * 8192u) ? 4u : 1u;
 	if (bt->n_frames && !verify)
 		HIPCHK(c, hipMemsetAsync(bt->d_frame_status, 0, (size_t)bt->n_frames * sizeof(uint32_t), sx));
 	for (uint32_t i = 0; i < nsl; i++) {
 		const uint32_t first = (uint32_t)((uint64_t)n * i / nsl), last = (uint32_t)((uint64_t)n * (i + 1) / nsl);
-		if (fast) {
-			h = prof_open(c, "lz4_expand", sx);
-			(poll ? la_launch_lz4_expand_fast : la_launch_lz4_expand_inorder)(sx, bt->d_src, bt->src_bytes, bt->d_blocks + first, last - first, bt->d_dst,
-			    bt->dst_cap, bt->d_dst_off + first, bt->d_out_len + first, bt->d_block_status + first,
-			    w.nseq + first, w.table, w.table_off + first, LA_LZ4_LONG_SEQ_BYTES);
-			prof_close(c, h, sx);
-		}
+		const la_expand_job sj = xj.slice(first, last - first);
+		if (fast)
+			prof_range(c, "lz4_expand", sx, [&] { (poll ? la_launch_lz4_expand_fast : la_launch_lz4_expand_inorder)(sx, sj); });
 		if (bt->n_frames && verify) {
 			HIPCHK(c, hipEventRecord(c->slice_ev[1 + i], sx));
 			HIPCHK(c, hipStreamWaitEvent(sp, c->slice_ev[1 + i], 0));
-			h = prof_open(c, "lz4_frame_sums", sp);
-			/* frames that END in this slice: all their blocks are in the slab now */
-			la_launch_lz4_frame_sums(sp, bt->d_src, bt->d_dst, bt->d_frames, bt->n_frames,
-			    bt->d_dst_off, bt->dst_cap, bt->d_frame_status, i ? first + 1 : 0u, last,
-			    bt->d_carry_in, bt->d_carry_out,
-			    /* nothing overlaps the last slice's hashes (nor a small batch's): the low-latency form */
-			    i + 1 == nsl);
-			prof_close(c, h, sp);
+			prof_range(c, "lz4_frame_sums", sp, [&] {
+				/* frames that END in this slice: all their blocks are in the slab now */
+				la_launch_lz4_frame_sums(sp, bt->d_src, bt->d_dst, bt->d_frames, bt->n_frames,
+				    bt->d_dst_off, bt->dst_cap, bt->d_frame_status, i ? first + 1 : 0u, last,
+				    bt->d_carry_in, bt->d_carry_out,
+				    /* nothing overlaps the last slice's hashes (nor a small batch's): the low-latency form */
+				    i + 1 == nsl);
+			});
 		}
 	}
 	/* join the second stream */
@@ -448,12 +440,10 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 	HIPCHK(c, hipStreamWaitEvent(sx, c->slice_ev[LA_MAX_SLICES - 1], 0));
 	if (verify)
 		la_launch_lz4_merge_status(sx, w.sum_status, n, bt->d_block_status);
-	if (bt->d_summary) {
-		h = prof_open(c, "summary", sx);
-		la_launch_lz4_summary(sx, bt->d_out_len, bt->d_block_status, n,
-		    bt->d_frame_status, bt->n_frames, bt->d_dst_off, bt->d_summary);
-		prof_close(c, h, sx);
-	}
+	if (bt->d_summary)
+		prof_range(c, "summary", sx, [&] {
+			la_launch_lz4_summary(sx, bt->d_out_len, bt->d_block_status, n, bt->d_frame_status, bt->n_frames, bt->d_dst_off, bt->d_summary);
+		});
 	HIPCHK(c, hipGetLastError());
 	return LA_OK;
 }
@@ -475,12 +465,32 @@ int la_gpu_zstd_decode(la_gpu_ctx *c, const la_zstd_batch *bt)
 		if (rc != LA_OK) return rc;
 	}
 	prof_begin(c);
-	int h = prof_open(c, "zstd_frames", c->stream);
-	la_launch_zstd_frames(c->stream, bt->d_src, bt->src_bytes, bt->d_frames, bt->n_frames, bt->d_dst, bt->dst_cap,
-	    bt->d_results, (uint8_t *)c->ws, bt->options);
-	prof_close(c, h, c->stream);
+	prof_range(c, "zstd_frames", c->stream, [&] {
+		la_launch_zstd_frames(c->stream, bt->d_src, bt->src_bytes, bt->d_frames, bt->n_frames, bt->d_dst, bt->dst_cap,
+		    bt->d_results, (uint8_t *)c->ws, bt->options);
+	});
 	HIPCHK(c, hipGetLastError());
 	return LA_OK;
+}
+
+/* workspace of a gzip batch on the lane kernels: their scratch, then (two phases) E and the SEG launch's list; returns its size */
+static uint64_t gz_ws_carve(uint8_t *base, uint32_t n, bool two_phase, la_inflate_emit *E, uint32_t **big)
+{
+	la_carve cv = { base, 0 };
+	cv.take<uint8_t>(la_inflate_lanes_scratch_bytes(n), 256);
+	if (two_phase) {
+		E->lit = cv.take<uint8_t>((uint64_t)n * 65536u, 256);
+		E->table = cv.take<la_lz4_seq>((uint64_t)n * LA_INFLATE_MAXSEQ, 256);
+		E->blocks = cv.take<la_lz4_block>(n, 256);
+		E->out_len = cv.take<uint32_t>(n, 256);
+		E->nseq = cv.take<uint32_t>(n, 256);
+		E->xstatus = cv.take<uint32_t>(n, 256);
+		E->todo = cv.take<uint32_t>(n, 256);
+		E->dst_off = cv.take<uint64_t>(n + 1, 256);
+		E->table_off = cv.take<uint64_t>(n + 1, 256);
+		*big = cv.take<uint32_t>(n + 1, 256);
+	}
+	return align_up(cv.off, 256);
 }
 
 int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
@@ -501,78 +511,48 @@ int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 	la_inflate_emit E = {};
 	uint32_t *gz_big = NULL;
 	if (lanes) {
-		uint64_t need = align_up(la_inflate_lanes_scratch_bytes(n), 256);
-		const uint64_t o_scratch = 0;
-		uint64_t o = need;
-		uint64_t o_lit = 0, o_tab = 0, o_blk = 0, o_olen = 0, o_nseq = 0, o_xst = 0, o_todo = 0, o_doff = 0, o_toff = 0, o_big = 0;
-		if (two_phase) {
-			o_lit = o;  o += align_up((uint64_t)n * 65536u, 256);
-			o_tab = o;  o += align_up((uint64_t)n * LA_INFLATE_MAXSEQ * sizeof(la_lz4_seq), 256);
-			o_blk = o;  o += align_up((uint64_t)n * sizeof(la_lz4_block), 256);
-			o_olen = o; o += align_up((uint64_t)n * 4, 256);
-			o_nseq = o; o += align_up((uint64_t)n * 4, 256);
-			o_xst = o;  o += align_up((uint64_t)n * 4, 256);
-			o_todo = o; o += align_up((uint64_t)n * 4, 256);
-			o_doff = o; o += align_up((uint64_t)(n + 1) * 8, 256);
-			o_toff = o; o += align_up((uint64_t)(n + 1) * 8, 256);
-			o_big = o;  o += align_up((uint64_t)(n + 1) * 4, 256);
-		}
-		if (o > c->ws_bytes) {
-			int rc = la_gpu_reserve(c, o);
+		const uint64_t need = gz_ws_carve(NULL, n, two_phase, &E, &gz_big);
+		if (need > c->ws_bytes) {
+			int rc = la_gpu_reserve(c, need);
 			if (rc != LA_OK) return rc;
 		}
 		wsb = (uint8_t *)c->ws;
-		(void)o_scratch;
-		if (two_phase) {
-			E.lit = wsb + o_lit;
-			E.table = (la_lz4_seq *)(wsb + o_tab);
-			E.blocks = (la_lz4_block *)(wsb + o_blk);
-			E.out_len = (uint32_t *)(wsb + o_olen);
-			E.nseq = (uint32_t *)(wsb + o_nseq);
-			E.xstatus = (uint32_t *)(wsb + o_xst);
-			E.todo = (uint32_t *)(wsb + o_todo);
-			E.dst_off = (uint64_t *)(wsb + o_doff);
-			E.table_off = (uint64_t *)(wsb + o_toff);
-			gz_big = (uint32_t *)(wsb + o_big);
-		}
+		gz_ws_carve(wsb, n, two_phase, &E, &gz_big);
 	}
 	prof_begin(c);
-	int h;
 	if (two_phase) {
-		h = prof_open(c, "inflate_symbols", s);
-		la_launch_inflate_symbols(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->dst_cap, bt->d_results, wsb, E);
-		prof_close(c, h, s);
-		h = prof_open(c, "inflate_expand", s);
-		if (!(bt->options & LA_GZ_OPT_EXPAND_INORDER)) {
-			la_launch_lz4_expand_fast(s, E.lit, (uint64_t)n * 65536u, E.blocks, n, bt->d_dst, bt->dst_cap,
-			    E.dst_off, E.out_len, E.xstatus, E.nseq, E.table, E.table_off, 0u);
-			/* members with more matches than one LDS segment of the polling kernel holds */
-			la_launch_lz4_expand_fast_big(s, E.lit, (uint64_t)n * 65536u, E.blocks, n, bt->d_dst, bt->dst_cap,
-			    E.dst_off, E.out_len, E.xstatus, E.nseq, E.table, E.table_off, gz_big, 0u);
-		} else {
-			la_launch_lz4_expand_inorder(s, E.lit, (uint64_t)n * 65536u, E.blocks, n, bt->d_dst, bt->dst_cap,
-			    E.dst_off, E.out_len, E.xstatus, E.nseq, E.table, E.table_off, 0u);
-		}
-		prof_close(c, h, s);
+		prof_range(c, "inflate_symbols", s, [&] {
+			la_launch_inflate_symbols(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->dst_cap, bt->d_results, wsb, E);
+		});
+		const la_expand_job xj = la_inflate_expand_job(E, n, bt->d_dst, bt->dst_cap);
+		prof_range(c, "inflate_expand", s, [&] {
+			if (!(bt->options & LA_GZ_OPT_EXPAND_INORDER)) {
+				la_launch_lz4_expand_fast(s, xj);
+				/* members with more matches than one LDS segment of the polling kernel holds */
+				la_launch_lz4_expand_fast_big(s, xj, gz_big);
+			} else {
+				la_launch_lz4_expand_inorder(s, xj);
+			}
+		});
 		/* members the LDS-window kernel cannot take: decoded in place */
-		h = prof_open(c, "inflate", s);
-		la_launch_inflate_lanes(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst,
-		    bt->dst_cap, bt->d_results, wsb, E.todo);
-		prof_close(c, h, s);
-	} else {
-		h = prof_open(c, "inflate", s);
-		if (lanes)
+		prof_range(c, "inflate", s, [&] {
 			la_launch_inflate_lanes(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst,
-			    bt->dst_cap, bt->d_results, wsb, NULL);
-		else
-			la_launch_inflate(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst, bt->dst_cap,
-			    bt->d_results);
-		prof_close(c, h, s);
+			    bt->dst_cap, bt->d_results, wsb, E.todo);
+		});
+	} else {
+		prof_range(c, "inflate", s, [&] {
+			if (lanes)
+				la_launch_inflate_lanes(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst,
+				    bt->dst_cap, bt->d_results, wsb, NULL);
+			else
+				la_launch_inflate(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst, bt->dst_cap,
+				    bt->d_results);
+		});
 	}
-	h = prof_open(c, "gz_crc32", s);
-	la_launch_gz_verify(s, bt->d_src, bt->src_bytes, bt->d_members, bt->n_members, bt->d_dst,
-	    bt->d_results, (bt->options & LA_GZ_OPT_RAW) ? 2 : !(bt->options & LA_GZ_OPT_NO_VERIFY));
-	prof_close(c, h, s);
+	prof_range(c, "gz_crc32", s, [&] {
+		la_launch_gz_verify(s, bt->d_src, bt->src_bytes, bt->d_members, bt->n_members, bt->d_dst,
+		    bt->d_results, (bt->options & LA_GZ_OPT_RAW) ? 2 : !(bt->options & LA_GZ_OPT_NO_VERIFY));
+	});
 	if (bt->d_summary)
 		la_launch_gz_summary(s, bt->d_results, bt->n_members, bt->d_summary);
 	HIPCHK(c, hipGetLastError());
@@ -590,9 +570,7 @@ static int compress_run(la_gpu_ctx *c, uint64_t need, const char *name, Launch l
 		if (rc != LA_OK) return rc;
 	}
 	prof_begin(c);
-	int h = prof_open(c, name, c->stream);
-	launch((uint8_t *)c->ws);
-	prof_close(c, h, c->stream);
+	prof_range(c, name, c->stream, [&] { launch((uint8_t *)c->ws); });
 	HIPCHK(c, hipGetLastError());
 	return LA_OK;
 }

@@ -1,8 +1,8 @@
 /*
  * la_comp_common.h -- device code the three compressors share (la_lz4_comp.hip, la_deflate_comp.hip,
  * la_zstd_comp.hip): small load / copy / store helpers, wave reductions, the LZ77 window matcher of the lz4 and zstd block kernels,
- * the wave bit-stream appender of the deflate and Huffman encoders, the per-frame checksum kernel and the workspace
- * carver of the launchers.
+ * the wave bit-stream appender of the deflate and Huffman encoders and the per-frame checksum kernel.  (The launchers'
+ * workspace carver, la_carve, comes with la_dev.h.)
  */
 #ifndef LA_COMP_COMMON_H
 #define LA_COMP_COMMON_H
@@ -159,19 +159,5 @@ __global__ __launch_bounds__(64) void frame_sums_kernel(const uint8_t *__restric
 	if (have && j == 0)
 		frame_sum[q] = h;
 }
-
-/* Bump carver over a launcher's workspace.  The launcher carves the workspace it is given; its
- * *_compress_workspace_bytes function runs the same carve on a null base and reads the size off `off`. */
-struct la_carve {
-	uint8_t *base;
-	uint64_t off;
-	template <typename T> T *take(uint64_t count, uint64_t align = alignof(T))
-	{
-		off = (off + align - 1) & ~(align - 1);
-		T *p = base ? (T *)(void *)(base + off) : nullptr;
-		off += count * sizeof(T);
-		return p;
-	}
-};
 
 #endif /* LA_COMP_COMMON_H */

@@ -415,6 +415,20 @@ __device__ __forceinline__ void io_copy_fast(const uint64_t R, const io_cls &K, 
 }
 #undef IO_DS
 
+/* Bump carver over a launcher's workspace.  The launcher carves the workspace it is given; its
+ * *_workspace_bytes function runs the same carve on a null base and reads the size off `off`. */
+struct la_carve {
+	uint8_t *base;
+	uint64_t off;
+	template <typename T> T *take(uint64_t count, uint64_t align = alignof(T))
+	{
+		off = (off + align - 1) & ~(align - 1);
+		T *p = base ? (T *)(void *)(base + off) : nullptr;
+		off += count * sizeof(T);
+		return p;
+	}
+};
+
 /* ---- launch interface (definitions live next to their kernels) ---- */
 
 /* la_hash.hip */
@@ -442,7 +456,8 @@ struct la_lz4_seq {	/* one LZ4 sequence, 8 bytes, written by the parse kernel */
 #define LA_LZ4_FAST_MAXSEQ 4096u	/* sequences per block the LDS-window kernel holds (per segment) */
 #define LA_INFLATE_MAXSEQ 12288u	/* table entries per deflate member in the two-phase path (three segments) */
 
-/* blocks the LDS-window kernel may take: compressed, independent, window <= 64 KiB */
+/* blocks that get a table slot (the LDS-window kernels can only take these): compressed, independent,
+ * window <= 64 KiB.  Who EXPANDS a block is la_lz4_route's decision, below. */
 __host__ __device__ __forceinline__ bool la_lz4_fast_eligible(const la_lz4_block &b)
 {
 	return !(b.flags & (LA_LZ4B_STORED | LA_LZ4B_DEPENDENT)) && b.dst_cap <= 65536u && b.src_len <= 65536u;
@@ -452,12 +467,57 @@ __host__ __device__ __forceinline__ bool la_lz4_fast_eligible(const la_lz4_block
  * sequence or more) go to the wave-wide general kernel even when the LDS-window kernels could take them: one lane per
  * match copies a 64 KiB run at the speed of one lane (10 GB/s on blocks of zeros), the general kernel's wave-wide
  * copies reach 250 GB/s on them (tools/measure_long_matches.py).  thr = 0 switches the routing off (the deflate
- * front end has no general kernel behind it).  The same predicate is used on both sides. */
+ * front end has no general kernel behind it).  Asked by la_lz4_route only. */
 #define LA_LZ4_LONG_SEQ_BYTES 512u
 __host__ __device__ __forceinline__ bool la_lz4_long_sequences(uint32_t nseq, uint32_t out_len, uint32_t thr)
 {
 	return thr != 0 && nseq != 0xFFFFFFFFu && (uint64_t)nseq * thr <= out_len;
 }
+
+/* Which expand kernel writes a block's bytes: THE place where that is decided.  Every expand kernel and the classify
+ * kernel ask with the block's words and act on one answer: the general kernel takes GENERAL, the polling kernel WINDOW
+ * or, in its segmented launch, WINDOW_SEG; the in-order kernel, run instead of both, takes both.  Nobody takes NONE.
+ * have_tables: the batch was parsed into sequence tables; nseq = 0xFFFFFFFF: no room for this block's table.
+ * The in-order kernel alone used to refuse out_len > 64 KiB, nseq == 0 and src_off > src_bytes, blocks the general
+ * kernel stood aside for.  Dropped, because a block with a window answer cannot be in such a state: both parse kernels
+ * fail a sequence that passes dst_cap (<= 64 KiB if eligible), count every sequence they put in a table, and read zeros
+ * beyond the image, which fail (offset 0) or decode to nothing; the deflate front end sends members above 64 KiB
+ * elsewhere, closes its table with the last literals, and sets src_off inside its own literal buffer. */
+enum la_expand_route { LA_XR_NONE, LA_XR_GENERAL, LA_XR_WINDOW, LA_XR_WINDOW_SEG };
+__host__ __device__ __forceinline__ la_expand_route la_lz4_route(const la_lz4_block &b, uint32_t status, uint32_t out_len,
+    uint32_t nseq, uint64_t dst_off, uint64_t dst_cap, bool have_tables, uint32_t long_thr)
+{
+	if (status != LA_ST_OK || out_len == 0 || dst_off + out_len > dst_cap)	/* never write past the slab, whatever the tables say */
+		return LA_XR_NONE;
+	if (!have_tables || !la_lz4_fast_eligible(b) || la_lz4_long_sequences(nseq, out_len, long_thr) || nseq == 0xFFFFFFFFu)
+		return LA_XR_GENERAL;
+	return nseq <= LA_LZ4_FAST_MAXSEQ ? LA_XR_WINDOW : LA_XR_WINDOW_SEG;
+}
+
+/* One expand step over a table of blocks: what every expand launch is given.  Host side only: the launchers unpack
+ * it into their kernels' (restrict-qualified) arguments. */
+struct la_expand_job {
+	const uint8_t *src;		/* compressed image (deflate front end: its literal buffers) */
+	uint64_t src_bytes;
+	const la_lz4_block *blocks;	/* [n] */
+	uint32_t n;
+	uint8_t *dst;			/* decoded slab */
+	uint64_t dst_cap;
+	const uint64_t *dst_off;	/* per block, as out_len, status, nseq and table_off */
+	const uint32_t *out_len;
+	uint32_t *status;
+	const uint32_t *nseq;
+	const la_lz4_seq *table;	/* NULL: no sequence tables, the general kernel takes every block */
+	const uint64_t *table_off;
+	uint32_t long_thr;		/* la_lz4_long_sequences */
+
+	/* blocks first .. first + count - 1: the per-block arrays move; image, slab and table (absolute offsets) stay */
+	la_expand_job slice(uint32_t first, uint32_t count) const
+	{
+		return la_expand_job{ src, src_bytes, blocks + first, count, dst, dst_cap, dst_off + first, out_len + first,
+		    status + first, nseq + first, table, table_off + first, long_thr };
+	}
+};
 
 void la_launch_lz4_table_caps(hipStream_t s, const la_lz4_block *d_blocks, uint32_t n, uint32_t *d_caps);
 void la_launch_lz4_parse(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
@@ -470,28 +530,15 @@ void la_launch_lz4_parse_staged(hipStream_t s, const uint8_t *d_src, uint64_t sr
     const la_lz4_block *d_blocks, uint32_t n, uint32_t *d_out_len, uint32_t *d_nseq,
     uint32_t *d_status, uint32_t *d_sum_status, la_lz4_seq *d_table, const uint64_t *d_table_off,
     uint64_t table_cap);
-void la_launch_lz4_expand_general(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
-    const uint64_t *d_dst_off, const uint32_t *d_out_len, const uint32_t *d_status,
-    const uint32_t *d_nseq, uint32_t fast_max_seq /* 0: take every block */, uint32_t hist_len, uint32_t long_thr);
-void la_launch_lz4_expand_fast(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
-    const uint64_t *d_dst_off, const uint32_t *d_out_len, uint32_t *d_status,
-    const uint32_t *d_nseq, const la_lz4_seq *d_table, const uint64_t *d_table_off, uint32_t long_thr);
-void la_launch_lz4_expand_fast_big(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
-    const uint64_t *d_dst_off, const uint32_t *d_out_len, uint32_t *d_status,
-    const uint32_t *d_nseq, const la_lz4_seq *d_table, const uint64_t *d_table_off,
-    uint32_t *d_big /* n + 1 words */, uint32_t long_thr);
+void la_launch_lz4_expand_general(hipStream_t s, const la_expand_job &j, uint32_t hist_len);
+void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j);
+void la_launch_lz4_expand_fast_big(hipStream_t s, const la_expand_job &j, uint32_t *d_big /* n + 1 words */);
 
 /* la_lz4_inorder.hip: the in-order expand step, run on request as the cross-check of the polling kernel (in-order
  * matcher wave + literal wave + flush wave per 64 KiB LDS window); the same contract, blocks of any sequence count
  * (no _big launch) */
 bool la_lz4_expand_inorder_takes(uint64_t src_bytes);	/* false: image too short for it, use the polling kernel */
-void la_launch_lz4_expand_inorder(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
-    const uint64_t *d_dst_off, const uint32_t *d_out_len, uint32_t *d_status,
-    const uint32_t *d_nseq, const la_lz4_seq *d_table, const uint64_t *d_table_off, uint32_t long_thr);
+void la_launch_lz4_expand_inorder(hipStream_t s, const la_expand_job &j);
 
 /* la_zstd.hip */
 uint64_t la_zstd_workspace_bytes(uint32_t n_frames);
@@ -528,6 +575,12 @@ struct la_inflate_emit {
 	uint64_t *dst_off;	/* [n+1] */
 	uint64_t *table_off;	/* [n+1] */
 };
+/* the expand step behind the entropy-only launch (no long-sequence routing: no general kernel runs behind it) */
+static inline la_expand_job la_inflate_expand_job(const la_inflate_emit &E, uint32_t n, uint8_t *d_dst, uint64_t dst_cap)
+{
+	return la_expand_job{ E.lit, (uint64_t)n * 65536u, E.blocks, n, d_dst, dst_cap, E.dst_off, E.out_len, E.xstatus,
+	    E.nseq, E.table, E.table_off, 0u };
+}
 void la_launch_inflate_lanes(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results,
     void *d_scratch, const uint32_t *d_only /* NULL: every member */);

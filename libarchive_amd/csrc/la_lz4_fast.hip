@@ -164,10 +164,10 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	const uint32_t olen = out_len[bi];
 	const uint32_t ns_all = nseq[bi];
 	const uint64_t doff = dst_off[bi];
-	/* same predicate as the general kernel's skip test (0xFFFFFFFF: the block has no table) */
-	if (status[bi] != LA_ST_OK || olen == 0 || !la_lz4_fast_eligible(b) || ns_all == 0xFFFFFFFFu ||
-	    doff + olen > dst_cap || la_lz4_long_sequences(ns_all, olen, long_thr))
-		return;		/* (few long sequences: the general kernel takes the block, la_dev.h) */
+	/* this launch's share of the table: blocks of one LDS segment, or (SEG) of more */
+	static_assert(MAXSEQ == LA_LZ4_FAST_MAXSEQ, "la_lz4_route splits the window kernels' blocks at LA_LZ4_FAST_MAXSEQ");
+	if (la_lz4_route(b, status[bi], olen, ns_all, doff, dst_cap, true, long_thr) != (SEG ? LA_XR_WINDOW_SEG : LA_XR_WINDOW))
+		return;
 
 	STAMP(0);
 	const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -652,12 +652,8 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	/* the usual block is one segment: that copy of the body is compiled with kb = 0 folded in
 	 * (and without the register pressure of a loop around it) */
 	if (!SEG) {
-		if (ns_all > MAXSEQ)
-			return;		/* the SEG launch takes it */
 		segment(0u);
 	} else {
-		if (ns_all <= MAXSEQ)
-			return;
 		for (uint32_t kb = 0; kb < ns_all; kb += MAXSEQ)
 			segment(kb);
 	}
@@ -689,7 +685,8 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	}
 }
 
-/* blocks the SEG launch must take: eligible, with a table, more than MAXSEQ sequences */
+/* blocks the SEG launch must take.  (This kernel is not given the slab: it lists a block without that bound, and the
+ * SEG launch asks again with it before it touches the block.) */
 __global__ __launch_bounds__(256) void lz4_classify_kernel(const la_lz4_block *__restrict__ blocks, uint32_t n,
     const uint32_t *__restrict__ status, const uint32_t *__restrict__ nseq, uint32_t *__restrict__ big_list,
     uint32_t *__restrict__ big_count, const uint32_t *__restrict__ out_len, uint32_t long_thr)
@@ -697,9 +694,7 @@ __global__ __launch_bounds__(256) void lz4_classify_kernel(const la_lz4_block *_
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n)
 		return;
-	const uint32_t ns = nseq[i];
-	if (ns != 0xFFFFFFFFu && ns > LA_LZ4_FAST_MAXSEQ && status[i] == LA_ST_OK && la_lz4_fast_eligible(blocks[i]) &&
-	    !la_lz4_long_sequences(ns, out_len[i], long_thr))
+	if (la_lz4_route(blocks[i], status[i], out_len[i], nseq[i], 0, ~0ull, true, long_thr) == LA_XR_WINDOW_SEG)
 		big_list[atomicAdd(big_count, 1u)] = i;
 }
 
@@ -711,30 +706,24 @@ extern "C" int la_diag_set_stamps(void *d_buf)
 }
 #endif
 
-void la_launch_lz4_expand_fast(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
-    const uint64_t *d_dst_off, const uint32_t *d_out_len, uint32_t *d_status,
-    const uint32_t *d_nseq, const la_lz4_seq *d_table, const uint64_t *d_table_off, uint32_t long_thr)
+void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j)
 {
-	if (n == 0) return;
-	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false>), dim3(n), dim3(FAST_THREADS), 0, s,
-	    d_src, src_bytes, d_blocks, n, d_dst, dst_cap, d_dst_off, d_out_len, d_status, d_nseq,
-	    d_table, d_table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, long_thr);
+	if (j.n == 0) return;
+	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false>), dim3(j.n), dim3(FAST_THREADS), 0, s,
+	    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
+	    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr);
 }
 
 /* blocks with more than LA_LZ4_FAST_MAXSEQ sequences, over the WHOLE table: classify + a small
  * grid that shares them out.  d_big: n + 1 words of workspace (count first). */
-void la_launch_lz4_expand_fast_big(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
-    const uint64_t *d_dst_off, const uint32_t *d_out_len, uint32_t *d_status,
-    const uint32_t *d_nseq, const la_lz4_seq *d_table, const uint64_t *d_table_off, uint32_t *d_big, uint32_t long_thr)
+void la_launch_lz4_expand_fast_big(hipStream_t s, const la_expand_job &j, uint32_t *d_big)
 {
-	if (n == 0) return;
+	if (j.n == 0) return;
 	(void)hipMemsetAsync(d_big, 0, sizeof(uint32_t), s);
-	hipLaunchKernelGGL(lz4_classify_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_blocks, n, d_status, d_nseq,
-	    d_big + 1, d_big, d_out_len, long_thr);
-	const uint32_t grid = n < 1024u ? n : 1024u;
+	hipLaunchKernelGGL(lz4_classify_kernel, dim3((j.n + 255) / 256), dim3(256), 0, s, j.blocks, j.n, j.status, j.nseq,
+	    d_big + 1, d_big, j.out_len, j.long_thr);
+	const uint32_t grid = j.n < 1024u ? j.n : 1024u;
 	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, true>), dim3(grid), dim3(FAST_THREADS), 0, s,
-	    d_src, src_bytes, d_blocks, n, d_dst, dst_cap, d_dst_off, d_out_len, d_status, d_nseq,
-	    d_table, d_table_off, (const uint32_t *)(d_big + 1), (const uint32_t *)d_big, long_thr);
+	    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
+	    j.table, j.table_off, (const uint32_t *)(d_big + 1), (const uint32_t *)d_big, j.long_thr);
 }

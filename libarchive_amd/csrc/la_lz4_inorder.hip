@@ -156,9 +156,9 @@ __device__ __forceinline__ io_blk io_load_blk(uint32_t bi, uint32_t n, const uin
 	const la_lz4_block b = blocks[bi];
 	const uint32_t olen = out_len[bi], ns = nseq[bi];
 	const uint64_t doff = dst_off[bi];
-	/* same predicate as the general kernel's skip test (0xFFFFFFFF: the block has no table) */
-	if (status[bi] != LA_ST_OK || olen == 0 || olen > 65536u || !la_lz4_fast_eligible(b) || ns == 0xFFFFFFFFu || ns == 0 ||
-	    doff + olen > dst_cap || b.src_off > src_bytes || la_lz4_long_sequences(ns, olen, long_thr))
+	/* blocks of any sequence count: this kernel runs in place of both launches of the polling kernel */
+	const la_expand_route xr = la_lz4_route(b, status[bi], olen, ns, doff, dst_cap, true, long_thr);
+	if (xr != LA_XR_WINDOW && xr != LA_XR_WINDOW_SEG)
 		return r;
 	r.take = true;
 	r.ns = ns;
@@ -706,14 +706,11 @@ extern "C" int la_diag_set_io_stamps(void *d_buf)
  * that go to the previous-generation kernel (the caller's choice, la_api.hip) */
 bool la_lz4_expand_inorder_takes(uint64_t src_bytes) { return src_bytes >= 16; }
 
-void la_launch_lz4_expand_inorder(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_lz4_block *d_blocks, uint32_t n, uint8_t *d_dst, uint64_t dst_cap,
-    const uint64_t *d_dst_off, const uint32_t *d_out_len, uint32_t *d_status,
-    const uint32_t *d_nseq, const la_lz4_seq *d_table, const uint64_t *d_table_off, uint32_t long_thr)
+void la_launch_lz4_expand_inorder(hipStream_t s, const la_expand_job &j)
 {
-	if (n == 0) return;
-	const uint32_t grid = (n + IO_BPW - 1) / IO_BPW;
+	if (j.n == 0) return;
+	const uint32_t grid = (j.n + IO_BPW - 1) / IO_BPW;
 	hipLaunchKernelGGL(lz4_expand_inorder_kernel, dim3(grid), dim3(IO_THREADS), 0, s,
-	    d_src, src_bytes, d_blocks, n, d_dst, dst_cap, d_dst_off, d_out_len, d_status, d_nseq,
-	    d_table, d_table_off, long_thr);
+	    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
+	    j.table, j.table_off, j.long_thr);
 }

@@ -40,6 +40,28 @@ def test_abi_struct_sizes():
     assert la.gpu_lib().la_gpu_abi_version() == 3
 
 
+# la_gpu_lz4_workspace_bytes(n_blocks, src_bytes) is public: bench.py and the filters reserve by it.  The figures were
+# read from a build made before the decode workspace was laid out by la_carve; they are recorded, not recomputed.
+LZ4_WORKSPACE_BYTES = {
+    # n_blocks: sizes for src_bytes = 0, 1, 65 536, 7 527 480 016
+    0: (4864, 4864, 179712, 20073285120),
+    1: (5888, 5888, 180480, 20073285888),
+    63: (9984, 9984, 184832, 20073289984),
+    64: (10496, 10496, 185344, 20073290752),
+    4096: (365312, 365312, 540160, 20073645568),
+    262144: (23074560, 23074560, 23249408, 20096354816),
+}
+
+
+def test_lz4_workspace_bytes_are_the_recorded_ones():
+    if not os.path.exists(N.GPU_LIB_PATH):
+        pytest.skip("libla_gpu.so has not been built")
+    lib = la.gpu_lib()                                         # loads without a device; only la_gpu_open needs one
+    got = {n: tuple(lib.la_gpu_lz4_workspace_bytes(n, sb) for sb in (0, 1, 65536, 7527480016))
+           for n in LZ4_WORKSPACE_BYTES}
+    assert got == LZ4_WORKSPACE_BYTES
+
+
 @pytest.mark.parametrize("read_size", [1, 2, 7, 200, 65536, None])
 def test_raw_passthrough_with_small_reader_blocks(read_size):
     rnd = random.Random(read_size or 0)
