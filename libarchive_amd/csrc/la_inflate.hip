@@ -14,7 +14,8 @@
  *   - literals are gathered in a 64-entry lane buffer and stored 64 at a time;
  *   - match copies are wave-wide (64 bytes per step) with the same
  *     store->load visibility rule as the general LZ4 kernel.
- * Accept/reject rules follow zlib 1.2.11 (see oracle/orc_inflate.c).
+ * Accept/reject rules follow zlib 1.2.11 (oracle/orc_inflate.c); the block-header rules are stated in
+ * la_deflate_dev.h, shared with la_inflate_lanes.hip, and read here through `wave_reader`.
  * Byte/integer work; no MFMA.
  *
  * Speed (one 64 KiB member, ms): 21.8 at first -- the bit reader and the window lived in SCRATCH memory
@@ -38,6 +39,7 @@
  * member and, with only two waves per CU, 77.6 instead of 12.5 ms for 4 096 members.
  */
 #include "la_dev.h"
+#include "la_deflate_dev.h"
 
 /* Diagnostic build only (make diag, -DLA_DIAG): per-member cycle totals of the symbol loop's parts go to a
  * buffer of their own (8 x u64 per member); no output value depends on them. */
@@ -111,8 +113,6 @@ __device__ __forceinline__ uint32_t br_take(bitreader &B, int n)
 	B.bits -= n;
 	return v;
 }
-
-__device__ __constant__ uint8_t c_clc_order[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
 
 __device__ __forceinline__ uint32_t bitrev(uint32_t v, int n) { return __builtin_bitreverse32(v) >> (32 - n); }
 
@@ -233,10 +233,8 @@ __device__ __forceinline__ void out_flush(out_state &O, int lane)
 }
 
 /* returns LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED or LA_ST_GZ_OUT_FULL */
-__device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, const inf_tables *T, bool fixed,
-    const uint16_t *fx_ll_fast, int lane DIAG_ARG)
+__device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, const inf_tables *T, int lane DIAG_ARG)
 {
-	(void)fixed; (void)fx_ll_fast;
 	for (;;) {
 		DIAG_T0();
 		int sym = huff_decode(B, T->ll_fast, LL_FAST_BITS, T->ll_count, T->ll_symbol, T->ll_maxlen, lane);
@@ -256,18 +254,15 @@ __device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, co
 		if (sym == 256)
 			return LA_ST_OK;
 		sym -= 257;
-		if (sym >= 29) return LA_ST_GZ_DATA;
-		/* base value and extra bits by arithmetic (RFC 1951 3.2.5), as in la_inflate_lanes.hip: a
-		 * constant-table load is a scalar memory round trip in the middle of the serial chain */
-		int xb = sym < 8 ? 0 : sym == 28 ? 0 : (sym - 4) >> 2;
-		if (!br_need(B, xb, lane)) return LA_ST_GZ_TRUNCATED;
-		uint32_t length = (sym < 8 ? 3u + (uint32_t)sym : sym == 28 ? 258u : ((4u + ((uint32_t)sym & 3u)) << xb) + 3u) + br_take(B, xb);
+		uint32_t bs, xb;
+		if (!dfl_len_sym((uint32_t)sym, bs, xb)) return LA_ST_GZ_DATA;
+		if (!br_need(B, (int)xb, lane)) return LA_ST_GZ_TRUNCATED;
+		uint32_t length = bs + br_take(B, (int)xb);
 		int ds = huff_decode(B, T->d_fast, D_FAST_BITS, T->d_count, T->d_symbol, T->d_maxlen, lane);
 		if (ds == -1) return LA_ST_GZ_TRUNCATED;
-		if (ds < 0 || ds >= 30) return LA_ST_GZ_DATA;
-		xb = ds < 4 ? 0 : (ds >> 1) - 1;
-		if (!br_need(B, xb, lane)) return LA_ST_GZ_TRUNCATED;
-		uint32_t dist = (ds < 4 ? (uint32_t)ds + 1u : ((2u + ((uint32_t)ds & 1u)) << xb) + 1u) + br_take(B, xb);
+		if (ds < 0 || !dfl_dist_sym((uint32_t)ds, bs, xb)) return LA_ST_GZ_DATA;
+		if (!br_need(B, (int)xb, lane)) return LA_ST_GZ_TRUNCATED;
+		uint32_t dist = bs + br_take(B, (int)xb);
 		DIAG_ACC(2); DIAG_CNT(7);
 		out_flush(O, lane);
 		if (dist > O.op) return LA_ST_GZ_DATA;
@@ -289,6 +284,44 @@ __device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, co
 		DIAG_ACC(3);
 	}
 }
+
+/* the block-header walks of la_deflate_dev.h over this kernel's bit reader and LDS tables.  All lanes hold the
+ * same values; lens[] is written by lane 0, or by up to three lane-strided stores for a repeat (<= 138).  The
+ * code-length code borrows the distance table's slots (19 symbols, codes of <= 7 bits). */
+struct wave_reader {
+	bitreader &B;
+	inf_tables *T;
+	int lane;
+	int cl_max;
+	__device__ __forceinline__ bool take(uint32_t n, uint32_t &v)
+	{
+		/* (n == 32: br_refill tops up to MORE than 32 bits whenever four bytes are left, and fewer are
+		 * left for good when it does not) */
+		if (!br_need(B, (int)n, lane))
+			return false;
+		v = br_take(B, (int)n);
+		return true;
+	}
+	__device__ __forceinline__ void to_byte() { br_take(B, B.bits & 7); }
+	__device__ __forceinline__ void store(uint32_t idx, uint32_t val, uint32_t rep)
+	{
+		if ((uint32_t)lane < rep) T->lens[idx + lane] = (uint8_t)val;
+		if (rep > 64 && (uint32_t)lane + 64 < rep) T->lens[idx + lane + 64] = (uint8_t)val;
+		if (rep > 128 && (uint32_t)lane + 128 < rep) T->lens[idx + lane + 128] = (uint8_t)val;
+	}
+	__device__ __forceinline__ uint32_t len_at(uint32_t idx) { return T->lens[idx]; }
+	__device__ __forceinline__ int clc_build(uint32_t &maxlen)
+	{
+		const int e = huff_build(T->lens, 19, T->d_count, T->d_symbol, T->d_fast, D_FAST_BITS, &T->d_maxlen, lane);
+		cl_max = __builtin_amdgcn_readfirstlane((int)T->d_maxlen);
+		maxlen = (uint32_t)cl_max;
+		return e;
+	}
+	__device__ __forceinline__ int clc_sym()
+	{
+		return huff_decode(B, T->d_fast, D_FAST_BITS, T->d_count, T->d_symbol, cl_max, lane);
+	}
+};
 
 __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const uint8_t *__restrict__ src,
     uint64_t src_bytes, const la_gz_member *__restrict__ members, uint32_t n, uint8_t *dst,
@@ -322,21 +355,15 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 	if (m.dst_off + m.dst_cap > dst_cap)
 		O.cap = m.dst_off < dst_cap ? (uint32_t)(dst_cap - m.dst_off) : 0;
 
+	wave_reader R = { B, T, lane, 0 };
 	for (;;) {
 		if (!br_need(B, 3, lane)) { status = LA_ST_GZ_TRUNCATED; break; }
 		int last = (int)br_take(B, 1);
 		int type = (int)br_take(B, 2);
 		if (type == 0) {
-			br_take(B, B.bits & 7);
-			/* LEN / NLEN */
-			if (!br_need(B, 32, lane)) {
-				/* br_refill only tops up to > 32 bits; try once more for exactly 32 */
-				br_refill(B, lane);
-				if (B.bits < 32) { status = LA_ST_GZ_TRUNCATED; break; }
-			}
-			uint32_t v = br_take(B, 32);
-			uint32_t len = v & 0xffff, nlen = v >> 16;
-			if (len != (nlen ^ 0xffff)) { status = LA_ST_GZ_DATA; break; }
+			uint32_t len;
+			status = dfl_stored_header(R, len);
+			if (status != LA_ST_OK) break;
 			out_flush(O, lane);
 			/* whole bytes still in the bit buffer go back to the byte stream */
 			B.ip -= B.bits >> 3;
@@ -349,90 +376,24 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 			O.op += take;
 			B.ip += take;
 			if (take < len) { status = LA_ST_GZ_TRUNCATED; break; }
-		} else if (type == 1) {
-			/* fixed code: lengths 8/9/7/8 for 288 symbols, 5 bits for 32 distance symbols */
-			for (int i = lane; i < 320; i += LA_WAVE)
-				T->lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5;
-			huff_build(T->lens, 288, T->ll_count, T->ll_symbol, T->ll_fast, LL_FAST_BITS, &T->ll_maxlen, lane);
-			huff_build(T->lens + 288, 32, T->d_count, T->d_symbol, T->d_fast, D_FAST_BITS, &T->d_maxlen, lane);
-			status = inflate_codes(B, O, T, true, nullptr, lane DIAG_PASS);
-			if (status != LA_ST_OK) break;
-		} else if (type == 2) {
-			if (!br_need(B, 14, lane)) { status = LA_ST_GZ_TRUNCATED; break; }
-			int nlen = (int)br_take(B, 5) + 257;
-			int ndist = (int)br_take(B, 5) + 1;
-			int ncode = (int)br_take(B, 4) + 4;
-			if (nlen > 286 || ndist > 30) { status = LA_ST_GZ_DATA; break; }
-			for (int i = lane; i < 320; i += LA_WAVE)
-				T->lens[i] = 0;
-			bool trunc = false;
-			for (int i = 0; i < ncode; i++) {
-				if (!br_need(B, 3, lane)) { trunc = true; break; }
-				uint32_t v = br_take(B, 3);
-				if (lane == 0) T->lens[c_clc_order[i]] = (uint8_t)v;
-			}
-			if (trunc) { status = LA_ST_GZ_TRUNCATED; break; }
-			/* the code-length code reuses the distance table slots (19 symbols, 7-bit codes) */
-			int e = huff_build(T->lens, 19, T->d_count, T->d_symbol, T->d_fast, D_FAST_BITS, &T->d_maxlen, lane);
-			int cl_max = T->d_maxlen;
-			cl_max = __builtin_amdgcn_readfirstlane(cl_max);
-			if (e != 0 && cl_max != 0) { status = LA_ST_GZ_DATA; break; }
-			/* code lengths are decoded into a scratch copy first (lens[] holds the CL code) */
-			int idx = 0;
-			uint32_t prev = 0;
-			uint8_t *L = T->lens;		/* overwritten in place AFTER the CL table is built */
-			if (cl_max == 0) {
-				/* zlib 1.2.11: an all-zero code-length code yields one-bit "length 0" symbols */
-				if (!br_need(B, 1, lane)) { status = LA_ST_GZ_TRUNCATED; break; }
-				for (; idx < nlen + ndist; idx++) {
-					if (!br_need(B, 1, lane)) break;
-					br_take(B, 1);
-				}
-				if (idx < nlen + ndist) { status = LA_ST_GZ_TRUNCATED; break; }
-				for (int i = lane; i < 320; i += LA_WAVE) L[i] = 0;
+		} else if (type == 1 || type == 2) {
+			int nlen = 288, ndist = 32;
+			if (type == 1) {
+				for (int i = lane; i < 320; i += LA_WAVE)
+					T->lens[i] = (uint8_t)dfl_fixed_len(i);
 			} else {
-				for (int i = lane; i < 320; i += LA_WAVE) L[i] = 0;
-				while (idx < nlen + ndist) {
-					int sym = huff_decode(B, T->d_fast, D_FAST_BITS, T->d_count, T->d_symbol, cl_max, lane);
-					if (sym == -1) { status = LA_ST_GZ_TRUNCATED; break; }
-					if (sym < 0) { status = LA_ST_GZ_DATA; break; }
-					if (sym < 16) {
-						if (lane == 0) L[idx] = (uint8_t)sym;
-						prev = (uint32_t)sym;
-						idx++;
-						continue;
-					}
-					int rep;
-					uint32_t val = 0;
-					if (sym == 16) {
-						if (!br_need(B, 2, lane)) { status = LA_ST_GZ_TRUNCATED; break; }
-						if (idx == 0) { status = LA_ST_GZ_DATA; break; }
-						val = prev;
-						rep = 3 + (int)br_take(B, 2);
-					} else if (sym == 17) {
-						if (!br_need(B, 3, lane)) { status = LA_ST_GZ_TRUNCATED; break; }
-						rep = 3 + (int)br_take(B, 3);
-					} else {
-						if (!br_need(B, 7, lane)) { status = LA_ST_GZ_TRUNCATED; break; }
-						rep = 11 + (int)br_take(B, 7);
-					}
-					if (idx + rep > nlen + ndist) { status = LA_ST_GZ_DATA; break; }
-					if (lane < rep) L[idx + lane] = (uint8_t)val;
-					if (rep > 64 && lane + 64 < rep) L[idx + lane + 64] = (uint8_t)val;
-					if (rep > 128 && lane + 128 < rep) L[idx + lane + 128] = (uint8_t)val;
-					prev = val;
-					idx += rep;
-				}
+				status = dfl_dynamic_header(R, nlen, ndist);
 				if (status != LA_ST_OK) break;
 			}
-			if (L[256] == 0) { status = LA_ST_GZ_DATA; break; }
-			e = huff_build(L, nlen, T->ll_count, T->ll_symbol, T->ll_fast, LL_FAST_BITS, &T->ll_maxlen, lane);
+			int e = huff_build(T->lens, nlen, T->ll_count, T->ll_symbol, T->ll_fast, LL_FAST_BITS, &T->ll_maxlen, lane);
 			int llm = __builtin_amdgcn_readfirstlane((int)T->ll_maxlen);
-			if (e < 0 || (e > 0 && llm != 1)) { status = LA_ST_GZ_DATA; break; }
-			e = huff_build(L + nlen, ndist, T->d_count, T->d_symbol, T->d_fast, D_FAST_BITS, &T->d_maxlen, lane);
+			status = dfl_code_verdict(e, (uint32_t)llm, DFL_CODE_LITLEN);
+			if (status != LA_ST_OK) break;
+			e = huff_build(T->lens + nlen, ndist, T->d_count, T->d_symbol, T->d_fast, D_FAST_BITS, &T->d_maxlen, lane);
 			int dm = __builtin_amdgcn_readfirstlane((int)T->d_maxlen);
-			if (e < 0 || (e > 0 && dm > 1)) { status = LA_ST_GZ_DATA; break; }
-			status = inflate_codes(B, O, T, false, nullptr, lane DIAG_PASS);
+			status = dfl_code_verdict(e, (uint32_t)dm, DFL_CODE_DIST);
+			if (status != LA_ST_OK) break;
+			status = inflate_codes(B, O, T, lane DIAG_PASS);
 			if (status != LA_ST_OK) break;
 		} else {
 			status = LA_ST_GZ_DATA;

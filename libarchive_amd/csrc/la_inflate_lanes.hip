@@ -2,13 +2,14 @@
  * la_inflate_lanes.hip -- raw DEFLATE decode, ONE LANE PER MEMBER (gfx950).
  *
  * Same job and same accept/reject rules as la_inflate.hip (zlib inflate(),
- * gzip.c:431-511 / :479; rules in oracle/orc_inflate.c), different shape: a
+ * gzip.c:431-511 / :479; rules in oracle/orc_inflate.c, the block-header ones stated
+ * once for both kernels in la_deflate_dev.h and read here through `lane_reader`), different shape: a
  * deflate stream is one serial bit chain, so for batches of MANY independent
  * members (BGZF-style multi-member streams, SURVEY config 3: 262 144 members)
  * the parallel axis is "members", exactly as the LZ4 parse kernel walks one token
  * chain per lane.  Each lane owns
  *   - a 64-bit bit buffer refilled with unaligned 8-byte loads of its member,
- *   - its Huffman code in REGISTERS and LDS (round 3, IL_CANON): the literal/length code is resolved by a
+ *   - its Huffman code in REGISTERS and LDS (round 3): the literal/length code is resolved by a
  *     canonical walk -- the next 15 bits, left-justified, against one limit per code length (the limits grow
  *     with the length), branch-free, four operations per length; limit, index bias and the "symbols from 256
  *     up start here" mark of every length live in registers.  LDS holds only what needs an index:
@@ -36,26 +37,16 @@
  *         instruction only every ~8 cycles.
  *   46.7  so a second wave per SIMD pays once the tables fit twice: on the C3 members nearly every literal code
  *         is longer than the 7-bit table anyway (random literals: 8-9 bits), the table bought nothing there, and
- *         the canonical walk costs the same whatever the code length.  (IL_CANON=0 keeps the table version.)
+ *         the canonical walk costs the same whatever the code length.  (The table version can still be read in
+ *         commit 37404fd.)
  */
 #include "la_dev.h"
+#include "la_deflate_dev.h"
 
 #ifndef IL_THREADS
 #define IL_THREADS 256
 #endif
-#ifndef IL_CANON
-#define IL_CANON 1	/* 1: no literal/length fast table; every literal/length code resolves by the canonical walk over
-			 * per-length limits kept in registers, 320 B of LDS per lane, TWO workgroups per CU */
-#endif
-#ifndef LL_BITS
-#define LL_BITS 7
-#endif
-#ifndef DT_BITS
-#define DT_BITS (IL_CANON ? 5 : 6)
-#endif
-#ifndef IL_SL_GLOBAL
-#define IL_SL_GLOBAL 0	/* 1: the literal/length symbol list for long codes lives in global scratch, not LDS */
-#endif
+#define DT_BITS 5	/* index width of the distance / code-length fast table */
 #ifndef IL_LIT_ROUNDS
 #define IL_LIT_ROUNDS 2
 #endif
@@ -73,25 +64,18 @@ __device__ unsigned long long *la_diag_il;
 #define IL_CNT(slot, v) do { } while (0)
 #define IL_NOW() 0ull
 #endif
-#define IL_SCRATCH_PER_LANE 1024u	/* bytes of global scratch per member: lens[320] + sorted symbols u16[320] + pad */
+#define IL_SCRATCH_PER_LANE 1024u	/* stride of a member's global scratch slot; the slot holds lens[320], the rest is pad */
 
 /* ---- per-lane LDS tables, transposed: element e of lane t at [e][t] ---- */
-/* 608 bytes per lane = 152 KiB per 256-lane workgroup (one workgroup per CU):
- *   ll  fast table of the literal/length code, LL_BITS wide, entry = symbol << 4 | length
+/* 320 bytes per lane = 80 KiB per 256-lane workgroup (two workgroups per CU):
  *   sl  the literal/length symbols in canonical code order (low byte; symbols above 255 come
- *       last within their length, the lane keeps that boundary per length in registers), so
- *       a code longer than the fast table still resolves without a trip to global memory --
- *       every lane of the wave waits for such a trip whenever one lane needs it, and with
- *       64 lanes one nearly always does
+ *       last within their length, the lane keeps that boundary per length in registers): the
+ *       canonical walk ends in an index into this list, and a list in global memory would be a
+ *       trip that every lane of the wave waits for whenever one lane needs it
  *   dt  fast table of the distance code (and, while a block header is read, of the
  *       code-length code), DT_BITS wide, entry = symbol << 3 | length */
 struct il_lds {
-#if !IL_CANON
-	uint16_t ll[1 << LL_BITS][IL_THREADS];
-#endif
-#if !IL_SL_GLOBAL
 	uint8_t sl[288][IL_THREADS];
-#endif
 	uint8_t dt[1 << DT_BITS][IL_THREADS];
 };
 
@@ -197,23 +181,31 @@ __device__ __forceinline__ int32_t lb_avail(const lane_bits &B)
 __device__ __forceinline__ uint32_t lb_peek(const lane_bits &B, uint32_t n) { return (uint32_t)B.hold & ((1u << n) - 1u); }
 __device__ __forceinline__ void lb_drop(lane_bits &B, uint32_t n) { B.hold >>= n; B.bits -= n; }
 
-/* per-lane canonical code description kept in registers for the slow path */
+/* Per-lane canonical code description, in registers.  One struct for both kinds of code; each kind sets and
+ * reads only its own group of members below, so the other group costs no register.  Measured alternatives
+ * (profiles/r08_deflate_rules.md): one struct per kind with every member kept compiles to the same register
+ * counts, one struct per kind with `count` / `nlow` as locals of the literal/length build to 8 more VGPRs; the
+ * one struct is kept: a split buys no register and adds a type. */
 struct lane_code {
+	/* both kinds */
 	packed16 count;		/* codes per length 1..15 */
-	uint32_t maxlen;
-	uint32_t first_p, index_p;	/* canonical-walk state after the lengths the fast table covers */
-	packed16 nlow;		/* literal/length code only: symbols below 256 per length */
-#if IL_CANON
-	/* literal/length code, canonical walk: per length k, lim[k] = (left-justified 15-bit end of the codes of
-	 * length k) | (index of the length's first symbol - its first code) << 16, hib[k] = index from which the
-	 * length's symbols are 256 and up; bit k of `has`: the code has words of length k */
+	uint32_t maxlen;	/* longest code length, 0: empty code */
+
+	/* distance / code-length code only.  Codes of up to DT_BITS bits resolve in the LDS table (il_lds::dt);
+	 * longer ones by a walk over `count` that starts from first_p / index_p, the canonical walk's first code
+	 * and symbol index after the lengths the table covers.  y0..y7 hold the (at most 32) symbols in canonical
+	 * order, one byte each, IN REGISTERS (named scalars: an array would be indexed through scratch memory): a
+	 * long distance code then costs a few selects instead of a trip to global scratch that the whole wave
+	 * waits for. */
+	uint32_t first_p, index_p;
+	uint32_t y0, y1, y2, y3, y4, y5, y6, y7;
+
+	/* literal/length code only, resolved by a canonical walk.  nlow: symbols below 256 per length (build only).
+	 * Per length k: lim[k] = (left-justified 15-bit end of the codes of length k) | (index of the length's
+	 * first symbol - its first code) << 16; hib[k] = index from which the length's symbols are 256 and up;
+	 * bit k of `has`: the code has words of length k.  The symbols themselves are in LDS (il_lds::sl). */
+	packed16 nlow;
 	uint32_t lim[16], hib[16], has;
-#endif
-	uint32_t y0, y1, y2, y3, y4, y5, y6, y7;	/* distance / code-length code only: the (at most 32) symbols in
-				 * canonical order, one byte each, IN REGISTERS (named scalars: an array
-				 * would be indexed through scratch memory): a long distance code then
-				 * costs a few selects instead of a trip to global scratch that the whole
-				 * wave waits for */
 };
 __device__ __forceinline__ void lc_sym_set(lane_code &C, uint32_t pos, uint32_t sy)
 {
@@ -236,18 +228,68 @@ __device__ __forceinline__ uint32_t lc_sym_get(const lane_code &C, uint32_t pos)
 }
 
 /*
- * Build one table from lens[0..n) (global scratch, this lane's): counts, sorted symbol
- * list (global scratch, for codes longer than the fast table) and the LDS fast table.
+ * Build the literal/length code from lens[0..n) (global scratch, this lane's): the per-length
+ * limits in registers and the symbol list in LDS.
  * Returns 0 complete, >0 incomplete, <0 over-subscribed.
  */
-template <int FAST_BITS, bool LL>
-__device__ __forceinline__ int il_build(const uint8_t *lens, int n, lane_code &C, uint16_t *sorted,
-    il_lds &T, int tid)
+__device__ __forceinline__ int il_build_ll(const uint8_t *lens, int n, lane_code &C, il_lds &T, int tid)
 {
 	p16_zero(C.count);
 	p16_zero(C.nlow);
-	if (!LL)
-		C.y0 = C.y1 = C.y2 = C.y3 = C.y4 = C.y5 = C.y6 = C.y7 = 0;
+	for (int i = 0; i < n; i++)
+		p16_add(C.count, lens[i], 1);
+	int left = 1, maxlen = 0;
+	packed16 next_off;
+	p16_zero(next_off);
+	uint32_t off = 0;
+	for (int l = 1; l < 16; l++) {
+		const uint32_t c = p16_get(C.count, l);
+		if (c) maxlen = l;
+		left = left * 2 - (int)c;
+		if (left < 0) left = -100000;
+		p16_add(next_off, l, off);
+		off += c;
+	}
+	C.maxlen = (uint32_t)maxlen;
+	{
+		uint32_t cd = 0, ix = 0;
+		C.has = 0;
+		C.lim[0] = C.hib[0] = 0;
+#pragma unroll
+		for (int l = 1; l < 16; l++) {
+			const uint32_t c = p16_get(C.count, l);
+			cd = (cd + (l > 1 ? p16_get(C.count, l - 1) : 0u)) << 1;	/* first code of length l */
+			C.lim[l] = (((cd + c) << (15 - l)) & 0xFFFFu) | ((ix - cd) << 16);
+			C.hib[l] = ix;	/* (+ the literals of this length, below) */
+			C.has |= (c ? 1u : 0u) << l;
+			ix += c;
+		}
+	}
+	if (left < 0)
+		return -1;
+	for (int sy = 0; sy < n; sy++) {
+		const uint32_t l = lens[sy];
+		if (l == 0) continue;
+		const uint32_t pos = p16_get(next_off, l);
+		p16_add(next_off, l, 1);
+		T.sl[pos][tid] = (uint8_t)sy;
+		if (sy < 256)
+			p16_add(C.nlow, l, 1);
+	}
+#pragma unroll
+	for (int l = 1; l < 16; l++)
+		C.hib[l] += p16_get(C.nlow, l);
+	return left;
+}
+
+/*
+ * Build the distance or code-length code from lens[0..n): counts, the symbols in registers and
+ * the LDS fast table.  Returns 0 complete, >0 incomplete, <0 over-subscribed.
+ */
+__device__ __forceinline__ int il_build_dt(const uint8_t *lens, int n, lane_code &C, il_lds &T, int tid)
+{
+	p16_zero(C.count);
+	C.y0 = C.y1 = C.y2 = C.y3 = C.y4 = C.y5 = C.y6 = C.y7 = 0;
 	for (int i = 0; i < n; i++)
 		p16_add(C.count, lens[i], 1);
 	int left = 1, maxlen = 0;
@@ -267,7 +309,7 @@ __device__ __forceinline__ int il_build(const uint8_t *lens, int n, lane_code &C
 	C.maxlen = (uint32_t)maxlen;
 	{
 		uint32_t fi = 0, ix = 0;
-		for (int l = 1; l <= FAST_BITS; l++) {
+		for (int l = 1; l <= DT_BITS; l++) {
 			const uint32_t c = p16_get(C.count, l);
 			ix += c;
 			fi = (fi + c) << 1;
@@ -275,28 +317,8 @@ __device__ __forceinline__ int il_build(const uint8_t *lens, int n, lane_code &C
 		C.first_p = fi;
 		C.index_p = ix;
 	}
-#if IL_CANON
-	if (LL) {
-		uint32_t cd = 0, ix = 0;
-		C.has = 0;
-		C.lim[0] = C.hib[0] = 0;
-#pragma unroll
-		for (int l = 1; l < 16; l++) {
-			const uint32_t c = p16_get(C.count, l);
-			cd = (cd + (l > 1 ? p16_get(C.count, l - 1) : 0u)) << 1;	/* first code of length l */
-			C.lim[l] = (((cd + c) << (15 - l)) & 0xFFFFu) | ((ix - cd) << 16);
-			C.hib[l] = ix;	/* (+ the literals of this length, below) */
-			C.has |= (c ? 1u : 0u) << l;
-			ix += c;
-		}
-	} else
-#endif
-	for (int i = 0; i < (1 << FAST_BITS); i++) {
-#if !IL_CANON
-		if (LL) T.ll[i][tid] = 0; else
-#endif
+	for (int i = 0; i < (1 << DT_BITS); i++)
 		T.dt[i][tid] = 0;
-	}
 	if (left < 0)
 		return -1;
 	for (int sy = 0; sy < n; sy++) {
@@ -304,94 +326,70 @@ __device__ __forceinline__ int il_build(const uint8_t *lens, int n, lane_code &C
 		if (l == 0) continue;
 		const uint32_t pos = p16_get(next_off, l);
 		p16_add(next_off, l, 1);
-		if (LL && !IL_SL_GLOBAL) {
-#if !IL_SL_GLOBAL
-			T.sl[pos][tid] = (uint8_t)sy;
-#endif
-			if (sy < 256)
-				p16_add(C.nlow, l, 1);
-		} else if (LL) {
-			sorted[pos] = (uint16_t)sy;
-		} else {
-			lc_sym_set(C, pos & 31u, (uint32_t)sy);
-		}
+		lc_sym_set(C, pos & 31u, (uint32_t)sy);
 		const uint32_t cw = p16_get(next_code, l);
 		p16_add(next_code, l, 1);
-		if (l <= (uint32_t)FAST_BITS && !(IL_CANON && LL)) {
+		if (l <= (uint32_t)DT_BITS) {
 			const uint32_t r = __builtin_bitreverse32(cw) >> (32 - l);
-			for (uint32_t idx = r; idx < (1u << FAST_BITS); idx += (1u << l)) {
-#if !IL_CANON
-				if (LL) T.ll[idx][tid] = (uint16_t)((sy << 4) | l);
-				else
-#endif
+			for (uint32_t idx = r; idx < (1u << DT_BITS); idx += (1u << l))
 				T.dt[idx][tid] = (uint8_t)((sy << 3) | l);
-			}
 		}
 	}
-#if IL_CANON
-	if (LL) {
-#pragma unroll
-		for (int l = 1; l < 16; l++)
-			C.hib[l] += p16_get(C.nlow, l);
-	}
-#endif
 	return left;
 }
 
-/* decode one symbol; *used = bits consumed.  >= 0 symbol, -2 unassigned code.
+/* decode one literal/length symbol; *used = bits consumed.  >= 0 symbol, -2 unassigned code.
  * The caller checks availability of the consumed bits afterwards. */
-template <int FAST_BITS, bool LL>
-__device__ __forceinline__ int il_decode(lane_bits &B, const lane_code &C, const uint16_t *sorted,
-    const il_lds &T, int tid, uint32_t *used, uint32_t whas = 0)
+__device__ __forceinline__ int il_decode_ll(lane_bits &B, const lane_code &C, const il_lds &T, int tid,
+    uint32_t *used, uint32_t whas)
 {
-#if IL_CANON
-	if (LL) {
-		/* the code's 15-bit left-justified value against the per-length limits (they grow with the
-		 * length): the first limit above it is the code's length.  Lengths nobody in the wave has words
-		 * of cost a test and a jump; a length somebody has costs seven operations for everybody. */
-		const uint32_t rev = __builtin_bitreverse32(lb_peek(B, 15)) >> 17;	/* first bit read = bit 14 */
-		IL_CNT(4, 1);
-		/* Branch-free, longest length first: every length whose limit lies above the code overwrites the
-		 * choice, so the SHORTEST such length stands at the end (the limits grow with the length; lengths
-		 * the code has no words of repeat their neighbour's limit and change nothing).  Four operations per
-		 * length; the rare lengths (1-3 and 13-15 bits) sit behind one wave-uniform test each (`whas`:
-		 * the lengths some lane of the wave has words of, set up once per block). */
-		uint32_t hit_len = 0, bias = 0, hb = 0;
+	/* the code's 15-bit left-justified value against the per-length limits (they grow with the
+	 * length): the first limit above it is the code's length.  Lengths nobody in the wave has words
+	 * of cost a test and a jump; a length somebody has costs seven operations for everybody. */
+	const uint32_t rev = __builtin_bitreverse32(lb_peek(B, 15)) >> 17;	/* first bit read = bit 14 */
+	IL_CNT(4, 1);
+	/* Branch-free, longest length first: every length whose limit lies above the code overwrites the
+	 * choice, so the SHORTEST such length stands at the end (the limits grow with the length; lengths
+	 * the code has no words of repeat their neighbour's limit and change nothing).  Four operations per
+	 * length; the rare lengths (1-3 and 13-15 bits) sit behind one wave-uniform test each (`whas`:
+	 * the lengths some lane of the wave has words of, set up once per block). */
+	uint32_t hit_len = 0, bias = 0, hb = 0;
 #define IL_TRY(k)                                                                     \
-		do {                                                                  \
-			const uint32_t a_ = C.lim[k];                                 \
-			const bool under_ = rev < (a_ & 0xFFFFu);                     \
-			hit_len = under_ ? (uint32_t)(k) : hit_len;                   \
-			bias = under_ ? (uint32_t)((int32_t)a_ >> 16) : bias;         \
-			hb = under_ ? C.hib[k] : hb;                                  \
-		} while (0)
-		if (whas & 0xE000u) { IL_TRY(15); IL_TRY(14); IL_TRY(13); }
-		IL_TRY(12); IL_TRY(11); IL_TRY(10); IL_TRY(9); IL_TRY(8); IL_TRY(7); IL_TRY(6); IL_TRY(5); IL_TRY(4);
-		if (whas & 0x000Eu) { IL_TRY(3); IL_TRY(2); IL_TRY(1); }
+	do {                                                                  \
+		const uint32_t a_ = C.lim[k];                                 \
+		const bool under_ = rev < (a_ & 0xFFFFu);                     \
+		hit_len = under_ ? (uint32_t)(k) : hit_len;                   \
+		bias = under_ ? (uint32_t)((int32_t)a_ >> 16) : bias;         \
+		hb = under_ ? C.hib[k] : hb;                                  \
+	} while (0)
+	if (whas & 0xE000u) { IL_TRY(15); IL_TRY(14); IL_TRY(13); }
+	IL_TRY(12); IL_TRY(11); IL_TRY(10); IL_TRY(9); IL_TRY(8); IL_TRY(7); IL_TRY(6); IL_TRY(5); IL_TRY(4);
+	if (whas & 0x000Eu) { IL_TRY(3); IL_TRY(2); IL_TRY(1); }
 #undef IL_TRY
-		IL_CNT(5, 9);
-		const uint32_t hit_idx = (rev >> (15u - hit_len)) + bias;	/* (hit_len 0: unused) */
-		const uint32_t hit_hi = hit_idx >= hb ? 256u : 0u;
-		if (hit_len) {
-			lb_drop(B, hit_len);
-			*used = hit_len;
-			return (int)((uint32_t)T.sl[hit_idx][tid] | hit_hi);
-		}
-		const uint32_t ml = C.maxlen ? C.maxlen : 1;
-		lb_drop(B, ml);
-		*used = ml;
-		return -2;
+	IL_CNT(5, 9);
+	const uint32_t hit_idx = (rev >> (15u - hit_len)) + bias;	/* (hit_len 0: unused) */
+	const uint32_t hit_hi = hit_idx >= hb ? 256u : 0u;
+	if (hit_len) {
+		lb_drop(B, hit_len);
+		*used = hit_len;
+		return (int)((uint32_t)T.sl[hit_idx][tid] | hit_hi);
 	}
-	const uint32_t e = (uint32_t)T.dt[lb_peek(B, FAST_BITS)][tid];
+	const uint32_t ml = C.maxlen ? C.maxlen : 1;
+	lb_drop(B, ml);
+	*used = ml;
+	return -2;
+}
+
+/* decode one distance or code-length symbol; results as il_decode_ll */
+__device__ __forceinline__ int il_decode_dt(lane_bits &B, const lane_code &C, const il_lds &T, int tid,
+    uint32_t *used)
+{
+	const uint32_t e = (uint32_t)T.dt[lb_peek(B, DT_BITS)][tid];
 	const uint32_t l = e & 7u;
-#else
-	const uint32_t e = LL ? (uint32_t)T.ll[lb_peek(B, FAST_BITS)][tid] : (uint32_t)T.dt[lb_peek(B, FAST_BITS)][tid];
-	const uint32_t l = LL ? (e & 15u) : (e & 7u);
-#endif
 	if (l) {
 		lb_drop(B, l);
 		*used = l;
-		return (int)(LL ? (e >> 4) : (e >> 3));
+		return (int)(e >> 3);
 	}
 	/* Long or unassigned code.  The canonical walk for the lengths the fast table covers
 	 * cannot hit (the table would have had the code) and its state after them does not
@@ -399,20 +397,18 @@ __device__ __forceinline__ int il_decode(lane_bits &B, const lane_code &C, const
 	 * tried in straight-line code on the next 15 bits (every lane of the wave pays for this
 	 * path whenever one lane takes it, so it has no loop and no dynamic counter picks). */
 	const uint32_t rev = __builtin_bitreverse32(lb_peek(B, 15)) >> 17;	/* first bit read = bit 14 */
-	IL_CNT(LL ? 4 : 8, 1);
+	IL_CNT(8, 1);
 	int first = (int)C.first_p, index = (int)C.index_p;
-	int hit_len = 0, hit_idx = 0, hit_hi = 0;
+	int hit_len = 0, hit_idx = 0;
 #pragma unroll
-	for (int k = FAST_BITS + 1; k <= 15; k++) {
+	for (int k = DT_BITS + 1; k <= 15; k++) {
 		if (__ballot(hit_len == 0 && (uint32_t)k <= C.maxlen) == 0)
 			break;	/* (wave-uniform) every lane here has its code, or no longer ones exist */
-		IL_CNT(LL ? 5 : 9, 1);
+		IL_CNT(9, 1);
 		const int cn = (int)((C.count.w[k >> 2] >> (16 * (k & 3))) & 0xFFFFu);
 		const int codev = (int)(rev >> (15 - k));
 		const bool hit = hit_len == 0 && (uint32_t)k <= C.maxlen && codev - cn < first;
 		hit_idx = hit ? index + (codev - first) : hit_idx;
-		if (LL)	/* symbols above 255 are the last ones of their length */
-			hit_hi = hit ? ((codev - first) >= (int)((C.nlow.w[k >> 2] >> (16 * (k & 3))) & 0xFFFFu) ? 256 : 0) : hit_hi;
 		hit_len = hit ? k : hit_len;
 		index += cn;
 		first = (first + cn) << 1;
@@ -420,41 +416,57 @@ __device__ __forceinline__ int il_decode(lane_bits &B, const lane_code &C, const
 	if (hit_len) {
 		lb_drop(B, (uint32_t)hit_len);
 		*used = (uint32_t)hit_len;
-#if !IL_SL_GLOBAL
-		if (LL)
-			return (int)T.sl[hit_idx][tid] | hit_hi;
-#endif
-		if (!LL)
-			return (int)lc_sym_get(C, (uint32_t)hit_idx & 31u);
-		return sorted[hit_idx];
+		return (int)lc_sym_get(C, (uint32_t)hit_idx & 31u);
 	}
-	{
-		const uint32_t ml = C.maxlen ? C.maxlen : 1;
-		lb_drop(B, ml);
-		*used = ml;
-	}
+	const uint32_t ml = C.maxlen ? C.maxlen : 1;
+	lb_drop(B, ml);
+	*used = ml;
 	return -2;
 }
-
-/* length / distance symbol -> base value and extra bits, by arithmetic (RFC 1951 3.2.5):
- * no table in memory, a divergent table read costs more than these few operations */
-__device__ __forceinline__ void il_len_sym(uint32_t sy, uint32_t &base, uint32_t &extra)
-{
-	extra = sy < 8 ? 0u : sy == 28 ? 0u : (sy - 4) >> 2;
-	base = sy < 8 ? 3u + sy : sy == 28 ? 258u : ((4u + (sy & 3u)) << extra) + 3u;
-}
-__device__ __forceinline__ void il_dist_sym(uint32_t ds, uint32_t &base, uint32_t &extra)
-{
-	extra = ds < 4 ? 0u : (ds >> 1) - 1u;
-	base = ds < 4 ? ds + 1u : ((2u + (ds & 1u)) << extra) + 1u;
-}
-
-__device__ __constant__ uint8_t il_clc_order[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
 
 /* the symbol just taken needed bits the member does not have */
 /* (bits can only run out once the byte cursor has passed the end of the member: one compare
  * in the common case) */
-#define IL_CHECK_TRUNC()  do { if (B.ip > B.iend && lb_avail(B) < 0) { status = LA_ST_GZ_TRUNCATED; goto done; } } while (0)
+__device__ __forceinline__ bool lb_ended(const lane_bits &B) { return B.ip > B.iend && lb_avail(B) < 0; }
+#define IL_CHECK_TRUNC()  do { if (lb_ended(B)) { status = LA_ST_GZ_TRUNCATED; goto done; } } while (0)
+
+/* the block-header walks of la_deflate_dev.h over this lane's bit buffer, its lens[] in global scratch and the
+ * distance-code builder / decoder (the code-length code borrows the distance table: 19 symbols, <= 7 bits).
+ * Bits are taken first and checked afterwards, as everywhere in this kernel. */
+struct lane_reader {
+	lane_bits &B;
+	uint8_t *lens;
+	il_lds &T;
+	int tid;
+	lane_code CC;
+	__device__ __forceinline__ bool take(uint32_t n, uint32_t &v)
+	{
+		if (B.bits < n) lb_refill(B);
+		v = n == 32 ? (uint32_t)B.hold : lb_peek(B, n);
+		lb_drop(B, n);
+		return !lb_ended(B);
+	}
+	__device__ __forceinline__ void to_byte() { lb_drop(B, B.bits & 7); }
+	__device__ __forceinline__ void store(uint32_t idx, uint32_t val, uint32_t rep)
+	{
+		for (uint32_t t = 0; t < rep; t++)
+			lens[idx + t] = (uint8_t)val;
+	}
+	__device__ __forceinline__ uint32_t len_at(uint32_t idx) { return lens[idx]; }
+	__device__ __forceinline__ int clc_build(uint32_t &maxlen)
+	{
+		const int e = il_build_dt(lens, 19, CC, T, tid);
+		maxlen = CC.maxlen;
+		return e;
+	}
+	__device__ __forceinline__ int clc_sym()
+	{
+		lb_refill(B);
+		uint32_t used;
+		const int sym = il_decode_dt(B, CC, T, tid, &used);
+		return lb_ended(B) ? -1 : sym;
+	}
+};
 
 /*
  * EMIT = false: the member is decoded in place (literals and match copies go straight to the
@@ -549,8 +561,6 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 		ns++;                                                                             \
 	} while (0)
 	uint8_t *lens = scratch + (uint64_t)mi * IL_SCRATCH_PER_LANE;		/* [320] */
-	uint16_t *sorted_ll = (uint16_t *)(lens + 320);				/* [288] */
-	uint16_t *sorted_d = sorted_ll + 288;					/* [32] */
 	uint32_t status = LA_ST_OK;
 	lane_bits B;
 	B.s = src + m.src_off;
@@ -571,6 +581,8 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 	CL.maxlen = CD.maxlen = 0;
 	p16_zero(CL.count); p16_zero(CD.count);
 
+	lane_reader R = { B, lens, T, tid, {} };
+
 	[[maybe_unused]] const unsigned long long il_t_start = IL_NOW();
 	for (;;) {
 		[[maybe_unused]] const unsigned long long il_t_hdr = IL_NOW();
@@ -581,14 +593,10 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 		lb_drop(B, 3);
 		IL_CHECK_TRUNC();
 		if (type == 0) {
-			/* stored: to the byte boundary, LEN / NLEN, raw bytes */
-			lb_drop(B, B.bits & 7);
-			lb_refill(B);
-			const uint32_t v = (uint32_t)B.hold;
-			lb_drop(B, 32);
-			IL_CHECK_TRUNC();
-			const uint32_t len = v & 0xFFFFu, nlen = v >> 16;
-			if (len != (nlen ^ 0xFFFFu)) { status = LA_ST_GZ_DATA; goto done; }
+			/* stored: LEN / NLEN, raw bytes */
+			uint32_t len;
+			status = dfl_stored_header(R, len);
+			if (status != LA_ST_OK) goto done;
 			/* whole bytes still in the bit buffer go back to the byte stream */
 			B.ip -= B.bits >> 3;
 			const uint32_t avail = B.ip < B.iend ? B.iend - B.ip : 0;
@@ -611,87 +619,25 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 			int nlen = 288, ndist = 32;
 			if (type == 1) {
 				for (int i = 0; i < 320; i++)
-					lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5;
+					lens[i] = (uint8_t)dfl_fixed_len(i);
 			} else {
-				lb_refill(B);
-				nlen = (int)lb_peek(B, 5) + 257; lb_drop(B, 5);
-				ndist = (int)lb_peek(B, 5) + 1; lb_drop(B, 5);
-				const int ncode = (int)lb_peek(B, 4) + 4; lb_drop(B, 4);
-				IL_CHECK_TRUNC();
-				if (nlen > 286 || ndist > 30) { status = LA_ST_GZ_DATA; goto done; }
-				for (int i = 0; i < 19; i++)
-					lens[i] = 0;
-				for (int i = 0; i < ncode; i++) {
-					if (B.bits < 3) lb_refill(B);
-					lens[il_clc_order[i]] = (uint8_t)lb_peek(B, 3);
-					lb_drop(B, 3);
-					IL_CHECK_TRUNC();
-				}
-				/* code-length code: 19 symbols, <= 7 bits; its fast table borrows the distance table */
-				lane_code CC;
-				const int e = il_build<DT_BITS, false>(lens, 19, CC, sorted_d, T, tid);
-				if (e != 0 && CC.maxlen != 0) { status = LA_ST_GZ_DATA; goto done; }
-				int idx = 0;
-				uint32_t prev = 0;
-				if (CC.maxlen == 0) {
-					/* zlib 1.2.11: an all-zero code-length code yields one-bit "length 0" symbols */
-					lb_refill(B);
-					if (lb_avail(B) < 1) { status = LA_ST_GZ_TRUNCATED; goto done; }
-					for (; idx < nlen + ndist; idx++) {
-						if (B.bits < 1) lb_refill(B);
-						lb_drop(B, 1);
-						IL_CHECK_TRUNC();
-						lens[idx] = 0;
-					}
-				} else {
-					while (idx < nlen + ndist) {
-						lb_refill(B);
-						uint32_t used;
-						const int sym = il_decode<DT_BITS, false>(B, CC, sorted_d, T, tid, &used);
-						IL_CHECK_TRUNC();
-						if (sym < 0) { status = LA_ST_GZ_DATA; goto done; }
-						if (sym < 16) {
-							lens[idx++] = (uint8_t)sym;
-							prev = (uint32_t)sym;
-							continue;
-						}
-						int rep;
-						uint32_t val = 0;
-						if (sym == 16) {
-							rep = 3 + (int)lb_peek(B, 2); lb_drop(B, 2);
-							IL_CHECK_TRUNC();
-							if (idx == 0) { status = LA_ST_GZ_DATA; goto done; }
-							val = prev;
-						} else if (sym == 17) {
-							rep = 3 + (int)lb_peek(B, 3); lb_drop(B, 3);
-							IL_CHECK_TRUNC();
-						} else {
-							rep = 11 + (int)lb_peek(B, 7); lb_drop(B, 7);
-							IL_CHECK_TRUNC();
-						}
-						if (idx + rep > nlen + ndist) { status = LA_ST_GZ_DATA; goto done; }
-						for (int t = 0; t < rep; t++)
-							lens[idx + t] = (uint8_t)val;
-						prev = val;
-						idx += rep;
-					}
-				}
-				if (lens[256] == 0) { status = LA_ST_GZ_DATA; goto done; }
+				status = dfl_dynamic_header(R, nlen, ndist);
+				if (status != LA_ST_OK) goto done;
 			}
 			{
-				int e = il_build<LL_BITS, true>(lens, nlen, CL, sorted_ll, T, tid);
-				if (e < 0 || (e > 0 && CL.maxlen != 1)) { status = LA_ST_GZ_DATA; goto done; }
-				e = il_build<DT_BITS, false>(lens + nlen, ndist, CD, sorted_d, T, tid);
-				if (e < 0 || (e > 0 && CD.maxlen > 1)) { status = LA_ST_GZ_DATA; goto done; }
+				int e = il_build_ll(lens, nlen, CL, T, tid);
+				status = dfl_code_verdict(e, CL.maxlen, DFL_CODE_LITLEN);
+				if (status != LA_ST_OK) goto done;
+				e = il_build_dt(lens + nlen, ndist, CD, T, tid);
+				status = dfl_code_verdict(e, CD.maxlen, DFL_CODE_DIST);
+				if (status != LA_ST_OK) goto done;
 			}
 			uint32_t whas = 0;
-#if IL_CANON
 			/* the lanes that run the symbol loop together keep their codes for all of it: which code
 			 * lengths exist among them is one wave-uniform word for the whole loop */
 #pragma unroll
 			for (int k = 1; k <= 15; k++)
 				whas |= __ballot((CL.has >> k) & 1u) ? 1u << k : 0u;
-#endif
 			IL_CNT(2, IL_NOW() - il_t_hdr);
 			IL_CNT(3, 1);
 			/* ---- symbols ---- */
@@ -718,7 +664,7 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 					if (EMIT) IL_FLUSH();
 #pragma unroll	/* (no loop around the burst: a loop head makes the compiler wait for the prefetch there) */
 					for (int burst = 0; burst < IL_LIT_BURST; burst++) {
-						sym = il_decode<LL_BITS, true>(B, CL, sorted_ll, T, tid, &used, whas);
+						sym = il_decode_ll(B, CL, T, tid, &used, whas);
 						IL_CHECK_TRUNC();
 						if (sym < 0) { status = LA_ST_GZ_DATA; goto done; }
 						if (sym >= 256)
@@ -742,16 +688,14 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 				lb_refill(B);	/* (unconditional: a branch around it makes the refill wait for its own prefetch, see lb_refill) */
 				IL_CNT(7, 1);
 				sym -= 257;
-				if (sym >= 29) { status = LA_ST_GZ_DATA; goto done; }
 				uint32_t xb, bs;
-				il_len_sym((uint32_t)sym, bs, xb);
+				if (!dfl_len_sym((uint32_t)sym, bs, xb)) { status = LA_ST_GZ_DATA; goto done; }
 				const uint32_t length = bs + lb_peek(B, xb);
 				lb_drop(B, xb);
 				IL_CHECK_TRUNC();
-				const int ds = il_decode<DT_BITS, false>(B, CD, sorted_d, T, tid, &used);
+				const int ds = il_decode_dt(B, CD, T, tid, &used);
 				IL_CHECK_TRUNC();
-				if (ds < 0 || ds >= 30) { status = LA_ST_GZ_DATA; goto done; }
-				il_dist_sym((uint32_t)ds, bs, xb);
+				if (ds < 0 || !dfl_dist_sym((uint32_t)ds, bs, xb)) { status = LA_ST_GZ_DATA; goto done; }
 				const uint32_t dist = bs + lb_peek(B, xb);
 				lb_drop(B, xb);
 				IL_CHECK_TRUNC();
