@@ -97,7 +97,7 @@ enum {
 	LA_ST_ZSTD_BAD_CHECKSUM   = 13,	/* "Restored data doesn't match checksum" */
 	LA_ST_ZSTD_OUT_FULL       = 14,	/* the frame produces more than dst_cap bytes: host retries with a larger slot */
 	LA_ST_ZSTD_UNSUPPORTED    = 15,	/* reserved header bit: "Unsupported frame parameter" */
-	LA_ST_ZSTD_WINDOW         = 16,	/* window above 2^27 (ZSTD_decompressStream's default limit): "Frame requires too much memory for decoding" */
+	LA_ST_ZSTD_WINDOW         = 16,	/* window above 2^27 + 1 (ZSTD_decompressStream's default limit): "Frame requires too much memory for decoding" */
 	LA_ST_ZSTD_DICTIONARY     = 17	/* the frame names a dictionary: "Dictionary mismatch" */
 };
 

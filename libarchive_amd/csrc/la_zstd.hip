@@ -466,7 +466,7 @@ template <bool W> __device__ __forceinline__ static int64_t zstd_block(zframe *f
 	size_t nseq = p[0];
 	if (nseq == 0) { p += 1; left -= 1; }
 	else if (nseq < 128) { p += 1; left -= 1; }
-	else if (nseq < 255) { if (left < 2) return -1; nseq = ((nseq - 128) << 8) + p[1]; p += 2; left -= 2; }
+	else if (nseq < 255) { if (left < 2) return -1; nseq = ((nseq - 128) << 8) + p[1]; p += 2; left -= 2; if (nseq == 0) return -1; }	/* (no sequences is the ONE byte 0: libzstd goes on to read tables here) */
 	else { if (left < 3) return -1; nseq = p[1] + ((size_t)p[2] << 8) + 0x7F00; p += 3; left -= 3; }
 	size_t out = dst_pos, lit_pos = 0;
 	if (nseq) {
@@ -636,7 +636,10 @@ template <bool W> __device__ __forceinline__ static int64_t zstd_frame(const uin
 	p += (size_t)fcs_len;
 	if (single) window = fcs;
 	if (did != 0) return -7;			/* no dictionary is ever loaded by the filter: "Dictionary mismatch" */
-	if (window > (1ull << 27)) return -6;	/* ZSTD_decompressStream's default window limit (2^27) */
+	if (window > (1ull << 27) + 1) return -6;	/* ZSTD_decompressStream's default window limit ((1 << 27) + 1) */
+	/* Block_Maximum_Size = min(Window_Size, 128 KiB) (RFC 8878 3.1.1.2); a single-segment frame's window is its content
+	 * size.  It bounds a block's Block_Size and what the block produces: ZSTD_decompressStream refuses both */
+	const uint32_t bmax = window < ZBLOCK_MAX ? (uint32_t)window : ZBLOCK_MAX;
 	zframe &f = *fp;
 	f.have_huf = f.have_ll = f.have_of = f.have_ml = 0;
 	f.rep[0] = 1; f.rep[1] = 4; f.rep[2] = 8;
@@ -649,7 +652,8 @@ template <bool W> __device__ __forceinline__ static int64_t zstd_frame(const uin
 		const int last = bh & 1, type = (bh >> 1) & 3;
 		const uint32_t bsize = bh >> 3;
 		if (type == 3) return -1;
-		if (bsize > ZBLOCK_MAX) return -1;
+		if ((type == 1 && bsize == 0 ? 1u : bsize) > bmax) return -1;	/* (an RLE block's one byte counts: libzstd compares it) */
+		if (type == 2 && bsize < 3) return -1;	/* (libzstd: literals header, its one byte of content, sequence count) */
 		if (type == 1) {
 			if (p + 1 > len) return -3;
 			if (out + bsize > dst_cap) return -2;
@@ -662,6 +666,7 @@ template <bool W> __device__ __forceinline__ static int64_t zstd_frame(const uin
 			} else {
 				const int64_t r = zstd_block<W>(&f, src + p, bsize, dst + dst_pos, out - dst_pos, dst_cap - dst_pos);
 				if (r < 0) return r;
+				if ((uint64_t)r > bmax) return -1;
 				out += (size_t)r;
 			}
 			p += bsize;

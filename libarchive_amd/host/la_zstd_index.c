@@ -3,7 +3,7 @@
  * entropy decoding.  It cuts the image into whole frames for la_gpu_zstd_decode (include/la_gpu.h), drops skippable
  * frames (the reference's bidder accepts them, archive_read_support_filter_zstd.c:117-130, and libzstd skips them)
  * and gives every frame an output slot: Frame_Content_Size when the header carries one, otherwise the sum over its
- * blocks of Block_Size (raw, RLE) or 128 KiB (compressed: Block_Maximum_Size).
+ * blocks of Block_Size (raw, RLE) or Block_Maximum_Size = min(Window_Size, 128 KiB) (compressed).
  */
 #include "la_host.h"
 #include <string.h>
@@ -58,6 +58,14 @@ static int zstd_frame_extent(const uint8_t *p, uint64_t len, uint64_t *flen, uin
 	if (fcs_len == 2)
 		fcs += 256;
 	q += (uint64_t)fcs_len;
+	/* Block_Maximum_Size = min(Window_Size, 128 KiB) (RFC 8878 3.1.1.2); a single-segment frame's window is its
+	 * content size */
+	uint64_t window = fcs;
+	if (!single) {
+		const uint64_t base = 1ull << (10 + (p[5] >> 3));
+		window = base + (base >> 3) * (uint64_t)(p[5] & 7);
+	}
+	const uint32_t bmax = window < 128u * 1024u ? (uint32_t)window : 128u * 1024u;
 	uint64_t sum = 0;
 	for (;;) {
 		if (q + 3 > len)
@@ -66,7 +74,7 @@ static int zstd_frame_extent(const uint8_t *p, uint64_t len, uint64_t *flen, uin
 		q += 3;
 		const int last = bh & 1, type = (bh >> 1) & 3;
 		const uint32_t bsize = bh >> 3;
-		if (type == 3 || bsize > 128u * 1024u) {	/* the device names the error; nothing behind it can be found */
+		if (type == 3 || (type == 1 && bsize == 0 ? 1u : bsize) > bmax) {	/* the device names the error; nothing behind it can be found */
 			*bad_block = 1;
 			*flen = q;
 			*bound = (fcs_len && fcs < sum) ? fcs : sum;	/* (never the bare claim: it may be forged) */
@@ -76,7 +84,7 @@ static int zstd_frame_extent(const uint8_t *p, uint64_t len, uint64_t *flen, uin
 		if (q + body > len)
 			return 0;
 		q += body;
-		sum += type == 2 ? 128u * 1024u : bsize;
+		sum += type == 2 ? bmax : bsize;
 		if (last)
 			break;
 	}

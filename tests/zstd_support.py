@@ -83,3 +83,55 @@ def gen(rnd, n, kind):
 
 def skippable(payload, nibble=0):
     return (0x184D2A50 + nibble).to_bytes(4, "little") + len(payload).to_bytes(4, "little") + payload
+
+
+class _InBuffer(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("size", ctypes.c_size_t), ("pos", ctypes.c_size_t)]
+
+
+class _OutBuffer(ctypes.Structure):
+    _fields_ = [("dst", ctypes.c_void_p), ("size", ctypes.c_size_t), ("pos", ctypes.c_size_t)]
+
+
+def zstd_stream_decompress(z, img, in_chunk=None):
+    """The call the reference's filter makes (archive_read_support_filter_zstd.c:196-239): ZSTD_decompressStream with
+    one ZSTD_DStreamOutSize() output buffer per call, over every frame of img.  Returns (bytes, verdict): verdict is
+    "ok", "Truncated zstd input" (the input ended inside a frame) or libzstd's ZSTD_getErrorName() text; the bytes
+    are what came out in front of the verdict.  in_chunk = how many input bytes one call may see (None: all of
+    them).  libzstd decodes a frame whose content size fits the output buffer through its one-shot path when the
+    whole frame is in the input; small pieces keep it on the streaming path, which is the stricter of the two."""
+    z.ZSTD_createDStream.restype = ctypes.c_void_p
+    z.ZSTD_initDStream.argtypes = [ctypes.c_void_p]
+    z.ZSTD_initDStream.restype = ctypes.c_size_t
+    z.ZSTD_freeDStream.argtypes = [ctypes.c_void_p]
+    z.ZSTD_DStreamOutSize.restype = ctypes.c_size_t
+    z.ZSTD_decompressStream.restype = ctypes.c_size_t
+    z.ZSTD_decompressStream.argtypes = [ctypes.c_void_p, ctypes.POINTER(_OutBuffer), ctypes.POINTER(_InBuffer)]
+    z.ZSTD_getErrorName.restype = ctypes.c_char_p
+    z.ZSTD_getErrorName.argtypes = [ctypes.c_size_t]
+    zds = z.ZSTD_createDStream()
+    z.ZSTD_initDStream(zds)
+    out_size = z.ZSTD_DStreamOutSize()
+    obuf = ctypes.create_string_buffer(out_size)
+    src = ctypes.create_string_buffer(bytes(img), max(len(img), 1))
+    base = ctypes.addressof(src)
+    out, in_frame, full, p, n = bytearray(), False, False, 0, len(img)
+    try:
+        while True:
+            if p == n and not in_frame:
+                return bytes(out), "ok"
+            if p == n and not full:               # (a full output buffer may have left bytes inside libzstd: drain them)
+                return bytes(out), "Truncated zstd input"
+            if not in_frame:
+                z.ZSTD_initDStream(zds)
+            k = n - p if in_chunk is None else min(in_chunk, n - p)
+            ib = _InBuffer(base + p, k, 0)
+            ob = _OutBuffer(ctypes.addressof(obuf), out_size, 0)
+            hint = z.ZSTD_decompressStream(zds, ctypes.byref(ob), ctypes.byref(ib))
+            if z.ZSTD_isError(hint):
+                return bytes(out), z.ZSTD_getErrorName(hint).decode()
+            out += obuf.raw[:ob.pos]
+            p += ib.pos
+            in_frame, full = hint != 0, ob.pos == out_size
+    finally:
+        z.ZSTD_freeDStream(zds)
