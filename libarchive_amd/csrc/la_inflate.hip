@@ -376,6 +376,11 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 			O.op += take;
 			B.ip += take;
 			if (take < len) { status = LA_ST_GZ_TRUNCATED; break; }
+			/* the cursor stepped BACK over the whole bytes of the bit buffer: when the window had just slid it
+			 * can now lie up to 4 bytes in front of it, and win_u32 only looks forward (a distance of -4..-1
+			 * wraps to one it takes for a hit) */
+			if (B.ip < B.W.base)
+				win_reset(B.W, B.ip, lane);
 		} else if (type == 1 || type == 2) {
 			int nlen = 288, ndist = 32;
 			if (type == 1) {

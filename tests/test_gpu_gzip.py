@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from deflate_build import _Bits, _canon, _LEN_BASE, _LEN_XB, _DIST_BASE, _DIST_XB, _dynamic_block
 
 pytestmark = pytest.mark.gpu
 
@@ -219,83 +220,6 @@ def test_many_members_batch(gpu_ctx):
 
 
 # ---------------------------------------------------------------- hand-built dynamic blocks
-
-class _Bits:
-    """LSB-first bit writer (RFC 1951 3.1.1); Huffman codes go in MSB-first."""
-    def __init__(self):
-        self.acc, self.n, self.out = 0, 0, bytearray()
-
-    def put(self, v, nbits):
-        self.acc |= (v & ((1 << nbits) - 1)) << self.n
-        self.n += nbits
-        while self.n >= 8:
-            self.out.append(self.acc & 255)
-            self.acc >>= 8
-            self.n -= 8
-
-    def code(self, c, nbits):
-        self.put(int(format(c, "0%db" % nbits)[::-1], 2), nbits)
-
-    def done(self):
-        if self.n:
-            self.out.append(self.acc & 255)
-        return bytes(self.out)
-
-
-def _canon(lens):
-    """symbol -> (code, length), canonical assignment of RFC 1951 3.2.2"""
-    bl = [0] * 16
-    for l in lens:
-        bl[l] += 1 if l else 0
-    nxt, c = [0] * 16, 0
-    for b in range(1, 16):
-        c = (c + bl[b - 1]) << 1
-        nxt[b] = c
-    out = {}
-    for sy, l in enumerate(lens):
-        if l:
-            out[sy] = (nxt[l], l)
-            nxt[l] += 1
-    return out
-
-
-_LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-_LEN_XB = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
-_DIST_BASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577]
-_DIST_XB = [0, 0, 0, 0] + [i // 2 for i in range(2, 28)]
-
-
-def _dynamic_block(ll_lens, d_lens, ops, final=True):
-    """One dynamic-Huffman block with the GIVEN code lengths (286 / 30 entries).  The lengths are sent one by one
-    (no repeat codes) through a flat code-length code: sixteen 4-bit words for the lengths 0..15.
-    ops: ints (literal bytes) or (length symbol index, extra value, distance symbol, extra value)."""
-    w = _Bits()
-    w.put(1 if final else 0, 1)
-    w.put(2, 2)
-    nlen, ndist = 286, 30
-    w.put(nlen - 257, 5)
-    w.put(ndist - 1, 5)
-    w.put(19 - 4, 4)
-    order = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
-    cl_lens = [4 if s < 16 else 0 for s in range(19)]		# sixteen 4-bit codes: a complete code
-    for s in order:
-        w.put(cl_lens[s], 3)
-    clc = _canon(cl_lens)
-    for l in list(ll_lens) + list(d_lens):
-        w.code(*clc[l])
-    ll, dd = _canon(ll_lens), _canon(d_lens)
-    for op in ops:
-        if isinstance(op, int):
-            w.code(*ll[op])
-        else:
-            ls, lx, ds, dx = op
-            w.code(*ll[257 + ls])
-            w.put(lx, _LEN_XB[ls])
-            w.code(*dd[ds])
-            w.put(dx, _DIST_XB[ds])
-    w.code(*ll[256])
-    return w
-
 
 def test_hand_built_codes_of_every_length(gpu_ctx):
     """The canonical walk of the entropy decoder (per-length limits in registers, no fast table) against codes
