@@ -337,10 +337,26 @@ int      la_gpu_lz4_compress(la_gpu_ctx *ctx, const la_lz4c_batch *batch);
  * LA_GZC_FIXED.  d_out receives the concatenated members, *d_out_bytes their size (beyond out_cap nothing is written;
  * la_gpu_gzip_compress_bound() always fits, in every mode).  The two fields joined the end of the struct under ABI
  * version 3.
+ *
+ * `framing` selects the shape of the output.  LA_GZC_FRAME_MEMBERS (a zeroed field) is the above.  With
+ * LA_GZC_FRAME_STREAM d_out receives a byte-aligned piece of ONE raw-deflate stream of any length: no gzip header, no
+ * trailer, no "BC" field, no CRC32 (la_gpu_crc32_many's jobs take a running seed), and `mtime` is ignored.  The chunks
+ * are cut and compressed in parallel as before, `options` keeps its meaning, and each chunk contributes either
+ *   - a Huffman block with BFINAL = 0, its end-of-block symbol, then zlib's sync-flush shape: the three zero bits that
+ *     open an empty non-final stored block, zero bits up to the next byte boundary and the bytes 00 00 FF FF; or
+ *   - a stored block 00 LEN NLEN data (byte-aligned as it is), whenever the Huffman form with that tail would take
+ *     n + 5 bytes or more: a chunk of n bytes never takes more than n + 5, and la_gpu_gzip_compress_bound() still fits.
+ * No block of the piece has BFINAL set: the caller continues the stream with the next piece or ends it, for example
+ * with the empty fixed block 03 00.  Input of length 0 gives 0 bytes.  No match crosses a chunk boundary, so a
+ * chunk's bytes do not depend on its neighbours, and every chunk starts on a byte after a sync marker.  Any other
+ * value of `framing` is LA_ERR_ARG and nothing is written.
  * ===================================================================== */
 #define LA_GZC_FIXED    0u   /* as before: fixed-Huffman block, stored when that would not shrink */
 #define LA_GZC_DYNAMIC  1u   /* smallest of dynamic-Huffman, fixed-Huffman and stored, per chunk */
 #define LA_GZC_STORED   2u   /* stored blocks only (zlib level 0) */
+
+#define LA_GZC_FRAME_MEMBERS 0u   /* one gzip member per chunk */
+#define LA_GZC_FRAME_STREAM  1u   /* a continuable piece of one raw-deflate stream */
 
 typedef struct la_gzc_batch {
 	const uint8_t *d_src;
@@ -351,7 +367,10 @@ typedef struct la_gzc_batch {
 	uint64_t       out_cap;
 	uint64_t      *d_out_bytes;	/* one u64 on the device */
 	uint32_t       options;		/* LA_GZC_FIXED, LA_GZC_DYNAMIC or LA_GZC_STORED */
-	uint32_t       reserved;
+	union {
+		uint32_t framing;	/* LA_GZC_FRAME_MEMBERS or LA_GZC_FRAME_STREAM */
+		uint32_t reserved;	/* the field's name before it had a meaning: same place, kept for sources that zero it */
+	};
 } la_gzc_batch;
 
 uint64_t la_gpu_gzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t chunk_bytes);

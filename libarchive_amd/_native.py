@@ -79,16 +79,22 @@ class _ZstdcBatchC(C.Structure):
 LA_ZSTDC_CHECKSUM, LA_ZSTDC_RAW_LITERALS = 1, 2
 
 
+class _GzcFramingC(C.Union):     # the header's anonymous union: `reserved` is the field's earlier name
+    _fields_ = [("framing", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _GzcBatchC(C.Structure):
+    _anonymous_ = ("_framing",)
     _fields_ = [
         ("d_src", C.c_void_p), ("src_bytes", C.c_uint64),
         ("chunk_bytes", C.c_uint32), ("mtime", C.c_uint32),
         ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p),
-        ("options", C.c_uint32), ("reserved", C.c_uint32),
+        ("options", C.c_uint32), ("_framing", _GzcFramingC),
     ]
 
 
 LA_GZC_FIXED, LA_GZC_DYNAMIC, LA_GZC_STORED = 0, 1, 2
+LA_GZC_FRAME_MEMBERS, LA_GZC_FRAME_STREAM = 0, 1
 
 
 class _GzBatchC(C.Structure):

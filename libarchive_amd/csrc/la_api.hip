@@ -596,11 +596,11 @@ int la_gpu_gzip_compress(la_gpu_ctx *c, const la_gzc_batch *bt)
 		return LA_ERR_ARG;
 	if (bt->chunk_bytes == 0 || bt->chunk_bytes > 49152u || (bt->src_bytes + bt->chunk_bytes - 1) / bt->chunk_bytes > 0xFFFFFFFEull)
 		return LA_ERR_ARG;
-	if (bt->options > LA_GZC_STORED)
+	if (bt->options > LA_GZC_STORED || bt->framing > LA_GZC_FRAME_STREAM)
 		return LA_ERR_ARG;
 	return compress_run(c, la_gzip_compress_ws_bytes(bt->src_bytes, bt->chunk_bytes, bt->options), "gzip_compress", [&](uint8_t *ws) {
-		la_launch_gzip_compress(c->stream, bt->d_src, bt->src_bytes, bt->chunk_bytes, bt->mtime, bt->options, bt->d_out,
-		    bt->out_cap, bt->d_out_bytes, ws);
+		la_launch_gzip_compress(c->stream, bt->d_src, bt->src_bytes, bt->chunk_bytes, bt->mtime, bt->options, bt->framing,
+		    bt->d_out, bt->out_cap, bt->d_out_bytes, ws);
 	});
 }
 

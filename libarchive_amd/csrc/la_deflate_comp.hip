@@ -24,7 +24,14 @@
  *       then builds length-limited complete codes for the chunk (RFC 1951 3.2.7), knows the exact size of the dynamic,
  *       the fixed and the stored block, and writes the smallest in a second pass over the tokens.
  *   gz_jobs_kernel + crc32_many  CRC32 of every chunk (la_hash.hip).
- *   gz_pack_members_kernel  header, body (fixed-Huffman or stored), trailer at their scanned offsets.
+ *   gz_pack_kernel          header, body (Huffman or stored), trailer at their scanned offsets.
+ *
+ * Second shape (LA_GZC_FRAME_STREAM).  The same chunks, the same kernels, but the output is a byte-aligned piece of ONE
+ * raw-deflate stream that the caller continues or ends: no gzip header, no trailer, no CRC32, no block with BFINAL
+ * set.  A Huffman chunk is a non-final block followed by zlib's sync-flush shape -- the three header bits of an empty
+ * non-final stored block, zero bits up to the byte boundary, 00 00 FF FF -- so that the next chunk starts on a byte; a
+ * stored chunk is 00 LEN NLEN data.  Matches still end with their chunk, so a chunk's bytes do not depend on its
+ * neighbours.  The kernels take the shape as a template parameter: the members build of each is the code it was.
  */
 #include "la_comp_common.h"
 
@@ -32,7 +39,25 @@
 #define DFL_HASH_BITS 12
 #define DFL_HDR       18u	/* 10 fixed + XLEN(2) + "BC" 2 0 BSIZE(2) */
 
+/* Room of one chunk's Huffman body in the workspace.  The longest is the fixed block of n 9-bit literals: 3 header
+ * bits, 9 n, 7 of end-of-block, so at most ((9 n + 7) >> 3) + 2 bytes.  The stream shape's tail (DFL_TAIL_MAX) and the
+ * three bytes a last whole-dword store may add make that + 10 at most: inside the 16 bytes of slack. */
 __host__ __device__ static inline uint32_t dfl_body_bound(uint32_t n) { return ((n * 9u + 7u) >> 3) + 16u; }
+
+/* Stream shape: what follows a Huffman block's end-of-block symbol -- 3 bits, 0..7 bits of padding, 4 bytes.  It
+ * adds at most 5 bytes to the block's whole bytes: ((bits + 3 + 7) >> 3) + 4 <= ((bits + 7) >> 3) + 1 + 4. */
+#define DFL_TAIL_MAX 5u
+__device__ __forceinline__ uint32_t dfl_block_bytes(uint32_t bits, bool stream)
+{
+	return stream ? ((bits + 3u + 7u) >> 3) + 4u : (bits + 7u) >> 3;
+}
+/* The tail as three tokens for the bit stage, bp = the bits before it: lane 0 the empty stored block's header with
+ * the padding, lane 1 its LEN 0000, lane 2 its NLEN FFFF. */
+__device__ __forceinline__ uint32_t dfl_tail_token(uint64_t bp, uint32_t lane, uint32_t *bits)
+{
+	*bits = lane == 2u ? 0xFFFFu : 0u;
+	return lane == 0 ? 3u + ((0u - ((uint32_t)bp + 3u)) & 7u) : (lane < 3u ? 16u : 0u);
+}
 
 __device__ __forceinline__ uint32_t rev_bits(uint32_t v, uint32_t n) { return __builtin_bitreverse32(v) >> (32u - n); }
 
@@ -86,6 +111,7 @@ __device__ __forceinline__ uint32_t fixed_match(uint32_t len, uint32_t dist, uin
 	return nb;
 }
 
+template <bool STREAM>
 __global__ __launch_bounds__(64) void deflate_fixed_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
     uint32_t chunk, uint32_t n_chunks, uint8_t *__restrict__ tmp, uint32_t tmp_stride, uint32_t *__restrict__ body_len)
 {
@@ -104,7 +130,7 @@ __global__ __launch_bounds__(64) void deflate_fixed_kernel(const uint8_t *__rest
 		stage[i] = 0;
 	__syncthreads();
 	if (lane == 0)
-		stage[0] = 3u;	/* block header: BFINAL = 1, BTYPE = 01 (fixed Huffman), LSB first */
+		stage[0] = STREAM ? 2u : 3u;	/* block header: BFINAL = 1 (0 in a stream), BTYPE = 01 (fixed Huffman), LSB first */
 	uint64_t bp = 3;	/* bits written so far (wave-uniform) */
 	uint32_t anchor = 0;	/* first position not covered by a match taken so far */
 	__builtin_amdgcn_wave_barrier();
@@ -160,8 +186,15 @@ __global__ __launch_bounds__(64) void deflate_fixed_kernel(const uint8_t *__rest
 		bp += wave_bits_append(bp, bits, nb, stage, lane, [&](uint32_t i, uint32_t w) { out[i] = w; });
 	}
 	/* end-of-block (seven zero bits), then the partial dword */
-	bp += 7;
-	{
+	if constexpr (STREAM) {
+		/* lane 0's token of the tail takes the seven bits along */
+		uint32_t bits;
+		const uint32_t nb = dfl_tail_token(bp + 7, lane, &bits) + (lane == 0 ? 7u : 0u);
+		bp += wave_bits_append(bp, bits, nb, stage, lane, [&](uint32_t i, uint32_t w) { out[i] = w; });
+		if (lane == 0 && (bp & 31u))
+			out[bp >> 5] = stage[0];
+	} else {
+		bp += 7;
 		const uint32_t g0 = (uint32_t)((bp - 7) >> 5);
 		const uint32_t tb = (uint32_t)((bp - 7) & 31u) + 7u;
 		if (lane == 0) {
@@ -171,7 +204,7 @@ __global__ __launch_bounds__(64) void deflate_fixed_kernel(const uint8_t *__rest
 		}
 	}
 	if (lane == 0)
-		body_len[ci] = (uint32_t)((bp + 7) >> 3);
+		body_len[ci] = (uint32_t)((bp + 7) >> 3);	/* (a stream's tail ends on a byte) */
 }
 
 /* ------------------------------------------------------------------ dynamic Huffman (RFC 1951 3.2.7) */
@@ -330,7 +363,9 @@ __device__ __forceinline__ uint32_t fixed_lit_len(uint32_t sym) { return sym < 1
  * coding a token it counts its symbols in LDS histograms and keeps the token in this wave's token buffer.  Then the
  * wave builds the two codes and the block header's code-length code, and knows the exact size of the dynamic, the
  * fixed and the stored block; it writes the smallest (nothing for a stored block: body_len >= n + 5 tells the pack
- * kernel) in a second pass over the tokens, with codes from an LDS table. */
+ * kernel) in a second pass over the tokens, with codes from an LDS table.  In a stream the sizes it compares include
+ * the tail, which then follows the end-of-block symbol through the bit stage. */
+template <bool STREAM>
 __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
     uint32_t chunk, uint32_t n_chunks, uint8_t *__restrict__ tmp, uint32_t tmp_stride, uint32_t *__restrict__ body_len,
     uint32_t *__restrict__ tokbuf)
@@ -506,7 +541,7 @@ __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__re
 		dyn_bits += 3u + 14u + 3u * hclen + hbits;
 
 		/* ---- the smallest of the three; a stored block is n + 5 bytes and is not written here ---- */
-		const uint32_t dyn_bytes = (dyn_bits + 7u) >> 3, fix_bytes = (fix_bits + 7u) >> 3;
+		const uint32_t dyn_bytes = dfl_block_bytes(dyn_bits, STREAM), fix_bytes = dfl_block_bytes(fix_bits, STREAM);
 		const bool dyn = complete && dyn_bytes < fix_bytes;
 		const uint32_t bytes = dyn ? dyn_bytes : fix_bytes;
 		if (bytes >= n + 5u) {
@@ -521,12 +556,12 @@ __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__re
 			__builtin_amdgcn_wave_barrier();
 			dfl_assign_codes<1>(Ld, 15u, code + DFL_DOFF, lane);
 			__syncthreads();
-			/* BFINAL = 1, BTYPE = 10, HLIT, HDIST, HCLEN from lane 0; the code-length code's lengths from lanes 1 .. HCLEN */
+			/* BFINAL = 1 (0 in a stream), BTYPE = 10, HLIT, HDIST, HCLEN from lane 0; the code-length code's lengths from lanes 1 .. HCLEN */
 			const uint32_t prev = (uint32_t)__shfl_up((int)olen, 1, 64);
 			uint64_t hb = prev;
 			uint32_t hn = lane <= hclen ? 3u : 0u;
 			if (lane == 0) {
-				hb = 5u | ((nlit - 257u) << 3) | ((ndist - 1u) << 8) | ((hclen - 4u) << 13);
+				hb = (STREAM ? 4u : 5u) | ((nlit - 257u) << 3) | ((ndist - 1u) << 8) | ((hclen - 4u) << 13);
 				hn = 17u;
 			}
 			bp += wave_bits_append64(bp, hb, hn, stage, lane, put);
@@ -552,7 +587,7 @@ __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__re
 			if (lane < DFL_ND)
 				code[DFL_DOFF + lane] = rev_bits(lane, 5) | (5u << 16);
 			__syncthreads();
-			bp += wave_bits_append64(bp, 3u, lane == 0 ? 3u : 0u, stage, lane, put);	/* BFINAL = 1, BTYPE = 01 */
+			bp += wave_bits_append64(bp, STREAM ? 2u : 3u, lane == 0 ? 3u : 0u, stage, lane, put);	/* BFINAL = 1 (0 in a stream), BTYPE = 01 */
 		}
 
 		/* ---- pass 2: the tokens, 64 at a time, then end-of-block from the lane after the last one ---- */
@@ -581,6 +616,11 @@ __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__re
 			}
 			bp += wave_bits_append64(bp, v, nb, stage, lane, put);
 		}
+		if constexpr (STREAM) {
+			uint32_t bits;
+			const uint32_t nb = dfl_tail_token(bp, lane, &bits);
+			bp += wave_bits_append64(bp, bits, nb, stage, lane, put);
+		}
 		if (lane == 0) {
 			if (bp & 31u)
 				out[bp >> 5] = stage[0];
@@ -602,7 +642,21 @@ __global__ __launch_bounds__(256) void gz_jobs_kernel(uint64_t src_bytes, uint32
 	contrib[i] = DFL_HDR + body + 8u;
 }
 
-__global__ __launch_bounds__(256) void gz_pack_members_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
+/* a stream's contributions: the chunk's Huffman block with its tail, or the stored block when that is no larger */
+__global__ __launch_bounds__(256) void dfl_stream_contrib_kernel(uint64_t src_bytes, uint32_t chunk, uint32_t n_chunks,
+    const uint32_t *__restrict__ body_len, uint32_t *__restrict__ contrib)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_chunks)
+		return;
+	const uint64_t so = (uint64_t)i * chunk;
+	const uint32_t n = (uint32_t)(src_bytes - so < chunk ? src_bytes - so : chunk);
+	contrib[i] = body_len[i] < n + 5u ? body_len[i] : n + 5u;
+}
+
+/* STREAM: the bodies alone, back to back (no header, no trailer; `mtime` and `crc` are not read) */
+template <bool STREAM>
+__global__ __launch_bounds__(256) void gz_pack_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
     uint32_t chunk, uint32_t n_chunks, uint32_t mtime, const uint8_t *__restrict__ tmp, uint32_t tmp_stride,
     const uint32_t *__restrict__ body_len, const uint32_t *__restrict__ crc, const uint64_t *__restrict__ off,
     uint8_t *__restrict__ out, uint64_t out_cap, uint64_t *__restrict__ out_bytes)
@@ -619,8 +673,9 @@ __global__ __launch_bounds__(256) void gz_pack_members_kernel(const uint8_t *__r
 		*out_bytes = off[n_chunks];
 	if (off[ci + 1] > out_cap)
 		return;
+	constexpr uint32_t HDR = STREAM ? 0u : DFL_HDR;
 	const uint32_t total = DFL_HDR + body + 8u;
-	if (tid == 0) {
+	if (!STREAM && tid == 0) {
 		uint8_t *h = out + o;
 		h[0] = 0x1f; h[1] = 0x8b; h[2] = 8; h[3] = 4;	/* FEXTRA */
 		st_le32(h + 4, mtime);
@@ -631,10 +686,10 @@ __global__ __launch_bounds__(256) void gz_pack_members_kernel(const uint8_t *__r
 		st_le32(t, crc[ci]);
 		st_le32(t + 4, n);
 	}
-	uint8_t *b = out + o + DFL_HDR;
+	uint8_t *b = out + o + HDR;
 	if (stored) {
 		if (tid == 0) {
-			b[0] = 1;	/* BFINAL = 1, BTYPE = 00 */
+			b[0] = STREAM ? 0 : 1;	/* BFINAL = 1 (0 in a stream), BTYPE = 00 */
 			b[1] = (uint8_t)n; b[2] = (uint8_t)(n >> 8); b[3] = (uint8_t)~n; b[4] = (uint8_t)(~n >> 8);
 		}
 		for (uint32_t i = tid; i < n; i += 256)
@@ -696,8 +751,9 @@ extern "C" uint64_t la_gpu_gzip_compress_bound(uint64_t src_bytes, uint32_t chun
 }
 
 void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t chunk, uint32_t mtime,
-    uint32_t options, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws)
+    uint32_t options, uint32_t framing, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws)
 {
+	const bool stream = framing == LA_GZC_FRAME_STREAM;
 	const uint32_t nc = (uint32_t)((src_bytes + chunk - 1) / chunk);
 	const uint32_t stride = gzc_stride(chunk);
 	gzc_ws w;
@@ -706,16 +762,21 @@ void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 		(void)hipMemsetAsync(d_out_bytes, 0, 8, s);
 		return;
 	}
-	if (options == LA_GZC_STORED)	/* a body length no chunk can have: every member comes out stored */
+	if (options == LA_GZC_STORED)	/* a body length no chunk can have: every chunk comes out stored */
 		(void)hipMemsetAsync(w.body_len, 0xFF, (uint64_t)nc * 4u, s);
 	else if (options == LA_GZC_DYNAMIC)
-		hipLaunchKernelGGL(deflate_dynamic_kernel, dim3(nc < DFL_WAVES ? nc : DFL_WAVES), dim3(64), 0, s, d_src, src_bytes, chunk, nc,
-		    w.tmp, stride, w.body_len, w.toks);
+		hipLaunchKernelGGL(stream ? deflate_dynamic_kernel<true> : deflate_dynamic_kernel<false>, dim3(nc < DFL_WAVES ? nc : DFL_WAVES),
+		    dim3(64), 0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len, w.toks);
 	else
-		hipLaunchKernelGGL(deflate_fixed_kernel, dim3(nc), dim3(64), 0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len);
-	hipLaunchKernelGGL(gz_jobs_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.jobs, w.contrib);
-	la_launch_crc32_many(s, d_src, w.jobs, nc, w.crc);
+		hipLaunchKernelGGL(stream ? deflate_fixed_kernel<true> : deflate_fixed_kernel<false>, dim3(nc), dim3(64), 0, s, d_src,
+		    src_bytes, chunk, nc, w.tmp, stride, w.body_len);
+	if (stream) {	/* no member, so no CRC32: the caller hashes what it frames (la_gpu_crc32_many) */
+		hipLaunchKernelGGL(dfl_stream_contrib_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.contrib);
+	} else {
+		hipLaunchKernelGGL(gz_jobs_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.jobs, w.contrib);
+		la_launch_crc32_many(s, d_src, w.jobs, nc, w.crc);
+	}
 	la_launch_scan_u32(s, w.contrib, nc, w.off, w.scan);
-	hipLaunchKernelGGL(gz_pack_members_kernel, dim3(nc), dim3(256), 0, s, d_src, src_bytes, chunk, nc, mtime, w.tmp, stride,
-	    w.body_len, w.crc, w.off, d_out, out_cap, d_out_bytes);
+	hipLaunchKernelGGL(stream ? gz_pack_kernel<true> : gz_pack_kernel<false>, dim3(nc), dim3(256), 0, s, d_src, src_bytes, chunk, nc,
+	    mtime, w.tmp, stride, w.body_len, w.crc, w.off, d_out, out_cap, d_out_bytes);
 }

@@ -555,7 +555,7 @@ void la_launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 
 /* la_deflate_comp.hip */
 void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t chunk, uint32_t mtime,
-    uint32_t options, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
+    uint32_t options, uint32_t framing, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);	/* LA_GZC_*, LA_GZC_FRAME_* */
 uint64_t la_gzip_compress_ws_bytes(uint64_t src_bytes, uint32_t chunk, uint32_t options);	/* LA_GZC_* */
 
 /* la_inflate.hip */

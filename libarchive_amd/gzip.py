@@ -37,12 +37,12 @@ class GzDevicePlan:
         return self.d_results.cpu().numpy().view(N.GZ_RESULT_DTYPE)[:self.n]
 
 
-def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0, options=0):
+def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0, options=0, framing=0):
     """Device gzip compression (la_gpu_gzip_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8 CUDA
     tensor holding the concatenated gzip members (harness for the tests).  options: 0 fixed Huffman, 1 the smallest of
-    dynamic Huffman, fixed Huffman and stored per chunk, 2 stored blocks only (LA_GZC_*)."""
+    dynamic Huffman, fixed Huffman and stored per chunk, 2 stored blocks only (LA_GZC_*).  framing: LA_GZC_FRAME_*
+    (compress_to_stream asks for the other one)."""
     import torch
-    from . import _native as N
     n = int(d_plain.numel())
     cap = int(N.gpu_lib().la_gpu_gzip_compress_bound(n, chunk_bytes))
     d_out = torch.empty(max(cap, 16), dtype=torch.uint8, device=d_plain.device)
@@ -50,10 +50,16 @@ def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0, options=0):
     b = N._GzcBatchC()
     b.d_src = d_plain.data_ptr() if n else None
     b.src_bytes = n
-    b.chunk_bytes, b.mtime, b.options = chunk_bytes, mtime, options
+    b.chunk_bytes, b.mtime, b.options, b.framing = chunk_bytes, mtime, options, framing
     b.d_out, b.out_cap, b.d_out_bytes = d_out.data_ptr(), cap, d_len.data_ptr()
     ctx.gzip_compress(b)
     ctx.sync()
     total = int(d_len.cpu()[0])
     assert total <= cap, (total, cap)
     return d_out[:total]
+
+
+def compress_to_stream(ctx, d_plain, chunk_bytes=49152, options=0):
+    """The same call with LA_GZC_FRAME_STREAM: returns a uint8 CUDA tensor holding a byte-aligned piece of one
+    raw-deflate stream, no block of it final (followed by 03 00 it inflates to d_plain)."""
+    return compress_to_members(ctx, d_plain, chunk_bytes, 0, options, N.LA_GZC_FRAME_STREAM)

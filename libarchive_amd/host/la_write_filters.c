@@ -25,6 +25,13 @@
  * blocks (what zlib's level 0 writes), 1 fixed Huffman codes (the fast level), 2..9 and the default 6 the smallest
  * of a dynamic-Huffman, a fixed-Huffman and a stored block per chunk (LA_GZC_* in la_gpu.h).  The matcher is the
  * same at every level.
+ *   "single-member" (boolean, off by default; not an option of the reference, whose only shape this is) writes what
+ * archive_write_add_filter_gzip.c:190-345 writes: ONE member for the whole stream.  open sends the reference's
+ * 10-byte header (:201-238); every window goes through la_gpu_gzip_compress() with LA_GZC_FRAME_STREAM, which returns
+ * a byte-aligned piece of one raw-deflate stream, its chunks still compressed in parallel, while
+ * la_gpu_crc32_many() continues the running CRC32 over the window; close ends the stream with the empty fixed block
+ * 03 00 and writes the trailer.  For this repository's read filter such a member is one serial unit, which is why
+ * many members stay the default.
  *
  * The write core below is the minimum the filters need outside libarchive: archive_write_new,
  * _add_filter_lz4, _set_format_raw (one entry, data passed through: archive_write_set_format_raw.c),
@@ -461,6 +468,9 @@ struct gzw_private {	/* archive_write_add_filter_gzip.c:58-60 */
 	int compression_level;
 	int timestamp;		/* > 0 writes time(NULL) into the member headers (archive_write_add_filter_gzip.c:213-220) */
 	uint32_t mtime;
+	int single_member;	/* one member for the whole stream, as the reference writes */
+	uint32_t crc;		/* single member: CRC32 and length of the input so far */
+	uint64_t total_in;
 };
 
 static int gzw_options(struct archive_write_filter *f, const char *key, const char *value)
@@ -476,6 +486,10 @@ static int gzw_options(struct archive_write_filter *f, const char *key, const ch
 		d->timestamp = (value == NULL) ? -1 : 1;
 		return ARCHIVE_OK;
 	}
+	if (strcmp(key, "single-member") == 0) {
+		d->single_member = value != NULL;
+		return ARCHIVE_OK;
+	}
 	return ARCHIVE_WARN;
 }
 
@@ -489,7 +503,31 @@ static int gzw_compress(struct archive_write_filter *f, const struct la_write_wi
 	bt.d_src = w->d_in; bt.src_bytes = w->len; bt.chunk_bytes = GZW_CHUNK; bt.mtime = d->mtime;
 	bt.d_out = w->d_out; bt.out_cap = w->out_cap; bt.d_out_bytes = w->d_len;
 	bt.options = d->compression_level == 0 ? LA_GZC_STORED : (d->compression_level == 1 ? LA_GZC_FIXED : LA_GZC_DYNAMIC);
+	bt.framing = d->single_member ? LA_GZC_FRAME_STREAM : LA_GZC_FRAME_MEMBERS;
 	return la_gpu_gzip_compress(w->gpu, &bt);
+}
+
+/* single member: the window's piece of the deflate stream, and the member's CRC32 continued over the window by one
+ * seeded job per call (a job's length is 32 bits: a window of 4 GiB or more takes several).  The job and its result
+ * live behind the byte count in d_len (64 bytes): job at 16, result at 32. */
+static int gzw_compress_stream(struct archive_write_filter *f, const struct la_write_window *w)
+{
+	struct gzw_private *d = f->data;
+	int rc = gzw_compress(f, w);
+	uint8_t *t = w->d_len;
+	for (uint64_t at = 0; rc == LA_OK && at < w->len; ) {
+		const uint64_t left = w->len - at;
+		const la_hash_job job = { at, (uint32_t)(left < 0x80000000u ? left : 0x80000000u), d->crc };
+		if ((rc = la_gpu_memcpy_h2d(w->gpu, t + 16, &job, sizeof(job))) != LA_OK ||
+		    (rc = la_gpu_crc32_many(w->gpu, w->d_in, (const la_hash_job *)(t + 16), 1, (uint32_t *)(t + 32))) != LA_OK ||
+		    (rc = la_gpu_memcpy_d2h(w->gpu, &d->crc, t + 32, sizeof(d->crc))) != LA_OK ||
+		    (rc = la_gpu_sync(w->gpu)) != LA_OK)	/* `job` leaves scope; the next one is seeded with d->crc */
+			break;
+		at += job.len;
+	}
+	if (rc == LA_OK)
+		d->total_in += w->len;
+	return rc;
 }
 
 static int gzw_open(struct archive_write_filter *f)
@@ -498,6 +536,16 @@ static int gzw_open(struct archive_write_filter *f)
 	int r = la_write_window_open(f, 1);	/* (not whole 48 KiB chunks: rounding would move member boundaries) */
 	if (r == ARCHIVE_OK && d->timestamp >= 0)
 		d->mtime = (uint32_t)time(NULL);
+	if (r == ARCHIVE_OK && d->single_member) {
+		/* the reference's header (archive_write_add_filter_gzip.c:201-238): no flags, XFL 2 at level 9 and 4 at
+		 * level 1, OS 3 (Unix) */
+		const uint8_t xfl = d->compression_level == 9 ? 2 : (d->compression_level == 1 ? 4 : 0);
+		const uint8_t h[10] = { 0x1f, 0x8b, 8, 0, (uint8_t)d->mtime, (uint8_t)(d->mtime >> 8), (uint8_t)(d->mtime >> 16),
+		    (uint8_t)(d->mtime >> 24), xfl, 3 };
+		d->w.compress = gzw_compress_stream;
+		d->crc = 0; d->total_in = 0;
+		r = __archive_write_filter(f->next_filter, h, sizeof(h));
+	}
 	return r;
 }
 
@@ -507,6 +555,14 @@ static int gzw_close(struct archive_write_filter *f)
 	if (d->w.gpu == NULL)
 		return ARCHIVE_OK;
 	int r = la_write_window_flush(f, 0);
+	if (d->single_member) {
+		/* the stream's end and the member's trailer (archive_write_add_filter_gzip.c:309-331): an empty final
+		 * fixed block, CRC32 and ISIZE of all the input */
+		const uint32_t n = (uint32_t)d->total_in;
+		const uint8_t t[10] = { 0x03, 0x00, (uint8_t)d->crc, (uint8_t)(d->crc >> 8), (uint8_t)(d->crc >> 16), (uint8_t)(d->crc >> 24),
+		    (uint8_t)n, (uint8_t)(n >> 8), (uint8_t)(n >> 16), (uint8_t)(n >> 24) };
+		return r == ARCHIVE_OK ? __archive_write_filter(f->next_filter, t, sizeof(t)) : r;
+	}
 	if (r == ARCHIVE_OK && !d->w.wrote_anything) {
 		/* nothing was written: one member with an empty deflate stream, as zlib's Z_FINISH on no input gives
 		 * the reference (header, 03 00, crc 0, isize 0) */

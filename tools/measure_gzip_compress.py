@@ -2,8 +2,10 @@
 """Measurement: la_gpu_gzip_compress (device gzip compression, the write filter's data plane), resident in HBM, in its
 three block modes (LA_GZC_FIXED, LA_GZC_DYNAMIC, LA_GZC_STORED).  Input GB/s and ratio on C2-like data (the plain bytes
 of streams.synth_lz4_stream) and on ASCII word text; zlib levels 1 and 6 on a 16 MiB host sample next to them; the
-device read side's decode speed on the stream the dynamic mode wrote.
+device read side's decode speed on the stream the dynamic mode wrote.  Every mode is measured in both framings
+(LA_GZC_FRAME_MEMBERS, LA_GZC_FRAME_STREAM): a line each, with the output size.
 usage: python tools/measure_gzip_compress.py [GiB of C2-like input, default 4] [--once] [--modes 0,1,2] [--reps N]
+           [--framings 0,1]
   --once: one compression of each input in each mode and nothing else (for a rocprofv3 --kernel-trace --stats run)
   --reps: timed repetitions of the whole measurement per mode (each prints its own line; default 1)"""
 import os
@@ -32,9 +34,11 @@ def opt(name, default):
 once = "--once" in argv
 modes = [int(m) for m in opt("--modes", "0,1,2").split(",")]
 reps = int(opt("--reps", "1"))
-pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--modes", "--reps"))]
+framings = [int(f) for f in opt("--framings", "0,1").split(",")]
+pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--modes", "--reps", "--framings"))]
 gib = int(pos[0]) if pos else 4
 NAMES = {0: "fixed", 1: "dynamic", 2: "stored"}
+FRAMES = {0: "members", 1: "stream"}
 ctx = la.GpuContext(0)
 ctx.set_stream(torch.cuda.current_stream().cuda_stream)
 
@@ -62,19 +66,22 @@ for name, plain in inputs:
     n = int(d_plain.numel())
     if once:
         for m in modes:
-            LG.compress_to_members(ctx, d_plain, options=m)
+            for fr in framings:
+                LG.compress_to_members(ctx, d_plain, options=m, framing=fr)
         ctx.sync()
         continue
     sample = plain[:16 << 20].tobytes()
     z1, z6 = len(sample) / len(zlib.compress(sample, 1)), len(sample) / len(zlib.compress(sample, 6))
     for m in modes:
-        img = LG.compress_to_members(ctx, d_plain, options=m)
-        size = int(img.numel())
-        del img
-        for _ in range(reps):
-            dt = timed(lambda: LG.compress_to_members(ctx, d_plain, options=m))
-            print("%-8s %5.2f GiB in: gzip_compress %-7s %7.1f ms = %5.1f GB/s; ratio %.3f (zlib -1 %.3f, -6 %.3f on 16 MiB)"
-                  % (name, n / 2**30, NAMES[m], dt * 1e3, n / dt / 1e9, n / size, z1, z6), flush=True)
+        for fr in framings:
+            img = LG.compress_to_members(ctx, d_plain, options=m, framing=fr)
+            size = int(img.numel())
+            del img
+            for _ in range(reps):
+                dt = timed(lambda: LG.compress_to_members(ctx, d_plain, options=m, framing=fr))
+                print("%-8s %5.2f GiB in: gzip_compress %-7s %-7s %7.1f ms = %5.1f GB/s; %d bytes out, ratio %.3f "
+                      "(zlib -1 %.3f, -6 %.3f on 16 MiB)" % (name, n / 2**30, NAMES[m], FRAMES[fr], dt * 1e3, n / dt / 1e9,
+                                                            size, n / size, z1, z6), flush=True)
     if 1 in modes:
         # the device read side on what the dynamic mode wrote, through the filter (a 256 MiB piece)
         piece = d_plain[:256 << 20]
