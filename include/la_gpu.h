@@ -98,7 +98,12 @@ enum {
 	LA_ST_ZSTD_OUT_FULL       = 14,	/* the frame produces more than dst_cap bytes: host retries with a larger slot */
 	LA_ST_ZSTD_UNSUPPORTED    = 15,	/* reserved header bit: "Unsupported frame parameter" */
 	LA_ST_ZSTD_WINDOW         = 16,	/* window above 2^27 + 1 (ZSTD_decompressStream's default limit): "Frame requires too much memory for decoding" */
-	LA_ST_ZSTD_DICTIONARY     = 17	/* the frame names a dictionary: "Dictionary mismatch" */
+	LA_ST_ZSTD_DICTIONARY     = 17,	/* the frame names a dictionary: "Dictionary mismatch" */
+	/* LA_GZ_OPT_PIECES only: how a PIECE of one raw-deflate stream ends when its stream does not end in it */
+	LA_ST_GZ_PIECE_END        = 18,	/* a non-final block ended on a byte boundary and on the last byte of the span:
+					 * the next piece starts right behind it (consumed == src_len) */
+	LA_ST_GZ_NEEDS_HISTORY    = 19	/* a match reaches in front of the piece's first output byte: the blocks behind this
+					 * flush point depend on earlier output (Z_SYNC_FLUSH), the piece cannot be decoded alone */
 };
 
 /* =====================================================================
@@ -255,6 +260,16 @@ typedef struct la_gz_batch {
 #define LA_GZ_OPT_RAW        16u	/* members are bare raw-deflate streams (ZIP entries, archive_read_support_format_zip.c:2536-2700):
 					 * no gzip trailer follows the body, nothing is compared; status, out_len, consumed and
 					 * the CRC32 of the produced bytes are reported */
+
+#define LA_GZ_OPT_PIECES     64u	/* every la_gz_member is a span that CLAIMS to start on a byte-aligned block boundary of one
+					 * raw-deflate stream (behind a flush marker 00 00 FF FF, a stored block, or the member header).
+					 * Verified as LA_GZ_OPT_RAW (no trailer is read, crc32 is that of the bytes produced).  A piece
+					 * ends with LA_ST_OK (a final block ended; consumed points behind it, rounded up to the byte),
+					 * LA_ST_GZ_PIECE_END (see there; tested before the next block header is asked for, so a
+					 * non-final block that ends mid-byte at the end of the span is LA_ST_GZ_TRUNCATED),
+					 * LA_ST_GZ_NEEDS_HISTORY (out_len = the whole symbols in front of the match), or as any member
+					 * does.  Nothing in the claim is trusted: the caller confirms a chain of pieces in stream order
+					 * (la_gz_pieces_build, la_host.h). */
 
 int la_gpu_gzip_decode(la_gpu_ctx *ctx, const la_gz_batch *batch);
 

@@ -119,6 +119,42 @@ int    la_gz_index_build_ex(const uint8_t *img, uint64_t len, int at_eof, uint32
            uint32_t first_cap, uint32_t flags, uint64_t out_budget, uint64_t span_limit, la_gz_index *idx);
 void   la_gz_index_free(la_gz_index *idx);
 
+/* ---- pieces of ONE gzip member (flush points; la_gzip_index.c) ----
+ * Any byte-aligned block boundary of a deflate stream is a place to start a decoder, provided the blocks behind it
+ * reach no further back than the boundary.  zlib's Z_FULL_FLUSH, pigz -i and this project's gzip:single-member write
+ * filter leave such boundaries behind the four bytes 00 00 FF FF (an empty stored block's LEN / NLEN).  The walker
+ * cuts img[from .. len) -- `from` on a true block boundary: behind the member header, or behind a confirmed piece --
+ * at every such four bytes: piece k is [end of piece k-1, marker + 4), a la_gz_member for la_gpu_gzip_decode with
+ * LA_GZ_OPT_PIECES.  NOTHING is trusted: 00 00 FF FF also occurs inside stored data and Huffman bits.  The caller
+ * walks the results in stream order and confirms piece k only when it answers LA_ST_GZ_PIECE_END with consumed ==
+ * src_len; piece 0 starts on a true boundary and a confirmed piece ends on one, so a confirmed chain is correct by
+ * induction.  A piece that answers LA_ST_GZ_TRUNCATED with bytes behind it ended in a false marker: the caller comes
+ * back with `from` = that piece's start and first_skip one higher, which merges it with the next one.
+ *   The span behind the last marker runs to the end of the window; it is queued only with at_eof (last_open = 1: it
+ *   holds the final block, or the stream was cut) -- otherwise its bytes are the next window's and `consumed` stops
+ *   in front of them.
+ *   first_skip  markers to pass over for the first piece (refuted by a decode)
+ *   min_cap     no slot below this (a piece answered LA_ST_GZ_OUT_FULL: doubled from that piece on, like hint_cap)
+ *   out_budget  stop in front of the piece that would take the sum of slots past it (0 = no bound; one is always taken)
+ *   span_limit  as la_gz_index_build_ex
+ * end_kind: LA_END_EOF (at_eof and everything is queued), LA_END_NEED_MORE (bytes behind `consumed` wait for the
+ * next window), LA_END_GZ_TOO_LARGE. */
+typedef struct la_gz_pieces {
+	la_gz_member *pieces;
+	uint32_t      n, cap;
+	int           end_kind;
+	int           last_open;	/* the last piece queued is the span behind the last marker */
+	uint64_t      consumed;		/* img offset behind the last piece queued (`from` when none is) */
+	uint64_t      max_out;		/* sum of the slots (each rounded up to 16 bytes) */
+} la_gz_pieces;
+int      la_gz_pieces_build(const uint8_t *img, uint64_t len, uint64_t from, int at_eof, uint32_t first_skip,
+             uint32_t min_cap, uint64_t out_budget, uint64_t span_limit, la_gz_pieces *x);
+void     la_gz_pieces_free(la_gz_pieces *x);
+/* offset of the first 00 00 FF FF at or behind `from`, or len */
+uint64_t la_gz_next_marker(const uint8_t *img, uint64_t len, uint64_t from);
+/* LA_GZIP_FLUSH_POINTS=1: the gzip read filter and its bid policy look for flush points */
+int      la_gz_flush_points_enabled(void);
+
 /* ---- zstd (host/la_zstd_index.c) ---- */
 typedef struct la_zstd_index_result {
 	uint32_t n_frames;	/* entries written to frames[] (skippable frames are passed over) */
@@ -213,6 +249,8 @@ extern const struct la_archive_xxhash la_archive_xxhash;
 #endif
 unsigned long la_crc32(unsigned long crc, const void *buf, size_t len);
 unsigned long la_crc32_host(unsigned long crc, const void *buf, size_t len);
+/* crc32(A || B) from crc32(A), crc32(B) and len(B): the GF(2) combine (the drop-in's ranges, the gzip filter's pieces) */
+uint32_t la_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
 /* The reference's error string for a device status word / an end kind */
 const char *la_status_message(uint32_t la_st);

@@ -34,6 +34,10 @@ LA_LZ4B_STORED, LA_LZ4B_CHECKSUM, LA_LZ4B_DEPENDENT, LA_LZ4B_FIRST = 1, 2, 4, 8
 LA_LZ4F_CONTENT_SUM, LA_LZ4F_HEADER_SUM, LA_LZ4F_CONT, LA_LZ4F_OPEN, LA_LZ4F_HASHED = 1, 2, 4, 8, 16
 LA_LZ4_OPT_GENERAL_ONLY, LA_LZ4_OPT_NO_VERIFY, LA_LZ4_OPT_PARSE_V1, LA_LZ4_OPT_EXPAND_INORDER = 1, 2, 4, 8
 LA_GPU_ABI_VERSION = 3
+LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED, LA_ST_GZ_OUT_FULL, LA_ST_GZ_NO_TRAILER = 0, 5, 6, 9, 10
+LA_ST_GZ_PIECE_END, LA_ST_GZ_NEEDS_HISTORY = 18, 19     # LA_GZ_OPT_PIECES only
+(LA_GZ_OPT_NO_VERIFY, LA_GZ_OPT_WAVE_KERNEL, LA_GZ_OPT_LANE_KERNEL, LA_GZ_OPT_TWO_PHASE, LA_GZ_OPT_RAW,
+ LA_GZ_OPT_EXPAND_INORDER, LA_GZ_OPT_PIECES) = 1, 2, 4, 8, 16, 32, 64
 
 (LA_END_EOF, LA_END_TRUNCATED, LA_END_MALFORMED, LA_END_MALFORMED_SKIP, LA_END_EMPTY_FRAME,
  LA_END_NEED_MORE, LA_END_GZ_NO_TRAILER, LA_END_GZ_TOO_LARGE) = range(8)
@@ -272,6 +276,42 @@ def gz_index(image, at_eof: bool = True) -> GzIndex:
         return GzIndex(mem, hdr, c.end_kind, c.consumed, c.max_out, c.speculative)
     finally:
         lib.la_gz_index_free(C.byref(c))
+
+
+class _GzPiecesC(C.Structure):
+    _fields_ = [("pieces", C.c_void_p), ("n", C.c_uint32), ("cap", C.c_uint32), ("end_kind", C.c_int),
+                ("last_open", C.c_int), ("consumed", C.c_uint64), ("max_out", C.c_uint64)]
+
+
+class GzPieces:
+    """Piece table of one member body (host walker, la_gz_pieces_build): `members` has the layout of GzIndex.members."""
+
+    def __init__(self, members, end_kind, last_open, consumed, max_out):
+        self.members, self.end_kind, self.last_open = members, end_kind, bool(last_open)
+        self.consumed, self.max_out = consumed, max_out
+
+
+def gz_pieces(image, start=0, at_eof=True, first_skip=0, min_cap=0, out_budget=0, span_limit=0xFFFFFFFF) -> GzPieces:
+    """Cut image[start:] -- `start` on a byte-aligned deflate block boundary -- at its flush markers."""
+    if isinstance(image, (bytes, bytearray, memoryview)):
+        image = np.frombuffer(bytes(image), dtype=np.uint8)
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    lib = host_lib()
+    lib.la_gz_pieces_build.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32,
+                                       C.c_uint64, C.c_uint64, C.POINTER(_GzPiecesC)]
+    lib.la_gz_pieces_free.argtypes = [C.POINTER(_GzPiecesC)]
+    lib.la_gz_pieces_free.restype = None
+    c = _GzPiecesC()
+    if lib.la_gz_pieces_build(image.ctypes.data, image.size, start, 1 if at_eof else 0, first_skip, min_cap,
+                              out_budget, span_limit, C.byref(c)) != 0:
+        raise MemoryError("la_gz_pieces_build")
+    try:
+        mem = np.empty(c.n, dtype=GZ_MEMBER_DTYPE)
+        if c.n:
+            C.memmove(mem.ctypes.data, c.pieces, mem.nbytes)
+        return GzPieces(mem, c.end_kind, c.last_open, c.consumed, c.max_out)
+    finally:
+        lib.la_gz_pieces_free(C.byref(c))
 
 
 class GpuContext:

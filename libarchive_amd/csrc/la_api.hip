@@ -507,6 +507,7 @@ int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 	 * LDS-window expand kernel of the lz4 path; LA_GZ_OPT_LANE_KERNEL forces the in-place lane kernel */
 	const bool two_phase = lanes && !(bt->options & LA_GZ_OPT_LANE_KERNEL);
 	const uint32_t n = bt->n_members;
+	const bool pieces = (bt->options & LA_GZ_OPT_PIECES) != 0;	/* (every launch below: the template instance that knows pieces) */
 	uint8_t *wsb = NULL;
 	la_inflate_emit E = {};
 	uint32_t *gz_big = NULL;
@@ -522,7 +523,7 @@ int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 	prof_begin(c);
 	if (two_phase) {
 		prof_range(c, "inflate_symbols", s, [&] {
-			la_launch_inflate_symbols(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->dst_cap, bt->d_results, wsb, E);
+			la_launch_inflate_symbols(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->dst_cap, bt->d_results, wsb, E, pieces);
 		});
 		const la_expand_job xj = la_inflate_expand_job(E, n, bt->d_dst, bt->dst_cap);
 		prof_range(c, "inflate_expand", s, [&] {
@@ -537,21 +538,21 @@ int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 		/* members the LDS-window kernel cannot take: decoded in place */
 		prof_range(c, "inflate", s, [&] {
 			la_launch_inflate_lanes(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst,
-			    bt->dst_cap, bt->d_results, wsb, E.todo);
+			    bt->dst_cap, bt->d_results, wsb, E.todo, pieces);
 		});
 	} else {
 		prof_range(c, "inflate", s, [&] {
 			if (lanes)
 				la_launch_inflate_lanes(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst,
-				    bt->dst_cap, bt->d_results, wsb, NULL);
+				    bt->dst_cap, bt->d_results, wsb, NULL, pieces);
 			else
 				la_launch_inflate(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst, bt->dst_cap,
-				    bt->d_results);
+				    bt->d_results, pieces);
 		});
 	}
 	prof_range(c, "gz_crc32", s, [&] {
 		la_launch_gz_verify(s, bt->d_src, bt->src_bytes, bt->d_members, bt->n_members, bt->d_dst,
-		    bt->d_results, (bt->options & LA_GZ_OPT_RAW) ? 2 : !(bt->options & LA_GZ_OPT_NO_VERIFY));
+		    bt->d_results, (bt->options & (LA_GZ_OPT_RAW | LA_GZ_OPT_PIECES)) ? 2 : !(bt->options & LA_GZ_OPT_NO_VERIFY));
 	});
 	if (bt->d_summary)
 		la_launch_gz_summary(s, bt->d_results, bt->n_members, bt->d_summary);

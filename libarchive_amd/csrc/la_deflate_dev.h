@@ -1,6 +1,7 @@
 /*
  * la_deflate_dev.h -- what RFC 1951 and zlib 1.2.11 say about a deflate block header, stated ONCE for the
- * two inflate kernels (la_inflate.hip: one wave per member; la_inflate_lanes.hip: one lane per member).
+ * two inflate kernels (la_inflate.hip: one wave per member; la_inflate_lanes.hip: one lane per member), and with
+ * them the two rules a PIECE of a stream adds.
  * The written statement of the rules is oracle/orc_inflate.c; this is its device form.  Include after la_dev.h.
  *
  * Here: the code-length order, the fixed code's lengths, the length / distance symbol arithmetic, the verdict on
@@ -31,6 +32,15 @@
  *               nothing before it), LA_ST_GZ_DATA (repeat past HLIT + HDIST)
  *            6. LA_ST_GZ_DATA       no end-of-block code (lens[256] == 0)
  *            (then the kernel builds the literal/length code, then the distance code: dfl_code_verdict each)
+ *
+ * Pieces (LA_GZ_OPT_PIECES, a template parameter of the kernels: the other builds do not hold a byte of it).  A
+ * span that claims to start on a byte-aligned block boundary is decoded like a member, with two rules more:
+ *   end      behind a block WITHOUT BFINAL, and BEFORE the next three header bits are asked for: when not one bit
+ *            of the span is unread -- none pending in the current byte, the byte cursor on src_len -- the piece
+ *            is over, LA_ST_GZ_PIECE_END (dfl_piece_end).  A block that ends mid-byte on the span's last byte
+ *            leaves padding bits unread: no piece end, the header read runs out of input as it always did.
+ *   history  a distance that reaches in front of the piece's first output byte is LA_ST_GZ_NEEDS_HISTORY, not
+ *            LA_ST_GZ_DATA (dfl_far_back): the bytes it points at exist, in the piece before.
  */
 #ifndef LA_DEFLATE_DEV_H
 #define LA_DEFLATE_DEV_H
@@ -74,6 +84,18 @@ __device__ __forceinline__ uint32_t dfl_code_verdict(int left, uint32_t maxlen, 
 	const bool ok = kind == DFL_CODE_LITLEN ? maxlen == 1 : kind == DFL_CODE_DIST ? maxlen <= 1 : maxlen == 0;
 	return ok ? LA_ST_OK : LA_ST_GZ_DATA;
 }
+
+/* The end-of-piece rule, behind a block without BFINAL.  unread_bits: the bits of the span [src_off, src_off +
+ * src_len) that the kernel's bit reader has not handed out -- those in its buffer that came from inside the span
+ * plus eight per byte the cursor has not fetched. */
+template <bool PIECES>
+__device__ __forceinline__ bool dfl_piece_end(int64_t unread_bits)
+{
+	return PIECES && unread_bits == 0;
+}
+/* the verdict on a match distance above the bytes produced so far */
+template <bool PIECES>
+__device__ __forceinline__ uint32_t dfl_far_back() { return PIECES ? LA_ST_GZ_NEEDS_HISTORY : LA_ST_GZ_DATA; }
 
 /* stored block, behind the three header bits: to the byte boundary, LEN against ~NLEN */
 template <class R>

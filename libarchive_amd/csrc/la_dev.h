@@ -560,7 +560,7 @@ uint64_t la_gzip_compress_ws_bytes(uint64_t src_bytes, uint32_t chunk, uint32_t 
 
 /* la_inflate.hip */
 void la_launch_inflate(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results);
+    const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, bool pieces);
 uint64_t la_inflate_lanes_scratch_bytes(uint32_t n);
 /* outputs of the entropy-only launch (la_launch_inflate_symbols): everything
  * lz4_expand_fast_kernel needs to build the members in its LDS window */
@@ -583,10 +583,10 @@ static inline la_expand_job la_inflate_expand_job(const la_inflate_emit &E, uint
 }
 void la_launch_inflate_lanes(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results,
-    void *d_scratch, const uint32_t *d_only /* NULL: every member */);
+    void *d_scratch, const uint32_t *d_only /* NULL: every member */, bool pieces);
 void la_launch_inflate_symbols(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, uint64_t dst_cap, la_gz_result *d_results,
-    void *d_scratch, la_inflate_emit E);
+    void *d_scratch, la_inflate_emit E, bool pieces);
 void la_launch_gz_verify(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, const uint8_t *d_dst, la_gz_result *d_results, int verify);
 void la_launch_gz_summary(hipStream_t s, const la_gz_result *d_results, uint32_t n, la_batch_summary *d_summary);

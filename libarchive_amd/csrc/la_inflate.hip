@@ -232,7 +232,8 @@ __device__ __forceinline__ void out_flush(out_state &O, int lane)
 	}
 }
 
-/* returns LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED or LA_ST_GZ_OUT_FULL */
+/* returns LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED or LA_ST_GZ_OUT_FULL (PIECES: or LA_ST_GZ_NEEDS_HISTORY) */
+template <bool PIECES>
 __device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, const inf_tables *T, int lane DIAG_ARG)
 {
 	for (;;) {
@@ -265,7 +266,7 @@ __device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, co
 		uint32_t dist = bs + br_take(B, (int)xb);
 		DIAG_ACC(2); DIAG_CNT(7);
 		out_flush(O, lane);
-		if (dist > O.op) return LA_ST_GZ_DATA;
+		if (dist > O.op) return dfl_far_back<PIECES>();
 		if (O.op + length > O.cap) return LA_ST_GZ_OUT_FULL;
 		/* wave-wide copy; the modulo form only reads bytes below op */
 		uint32_t span = length < dist ? length : dist;
@@ -323,6 +324,8 @@ struct wave_reader {
 	}
 };
 
+/* PIECES: the members are pieces of one raw-deflate stream (LA_GZ_OPT_PIECES; the rules are in la_deflate_dev.h) */
+template <bool PIECES>
 __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const uint8_t *__restrict__ src,
     uint64_t src_bytes, const la_gz_member *__restrict__ members, uint32_t n, uint8_t *dst,
     uint64_t dst_cap, la_gz_result *__restrict__ results)
@@ -398,7 +401,7 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 			int dm = __builtin_amdgcn_readfirstlane((int)T->d_maxlen);
 			status = dfl_code_verdict(e, (uint32_t)dm, DFL_CODE_DIST);
 			if (status != LA_ST_OK) break;
-			status = inflate_codes(B, O, T, lane DIAG_PASS);
+			status = inflate_codes<PIECES>(B, O, T, lane DIAG_PASS);
 			if (status != LA_ST_OK) break;
 		} else {
 			status = LA_ST_GZ_DATA;
@@ -406,6 +409,12 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 		}
 		if (last)
 			break;
+		/* (the bit buffer only ever holds bytes from inside the span, and behind a stored block it is empty
+		 * with the cursor stepped back: both counts are exact here) */
+		if (dfl_piece_end<PIECES>((int64_t)B.bits + 8 * (int64_t)(B.iend - B.ip))) {
+			status = LA_ST_GZ_PIECE_END;
+			break;
+		}
 	}
 	/* what zlib would have emitted before noticing: whole symbols, stored data bytewise */
 	if (status != LA_ST_GZ_OUT_FULL)
@@ -429,10 +438,11 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 }
 
 void la_launch_inflate(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
-    const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results)
+    const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, bool pieces)
 {
 	if (n == 0) return;
-	hipLaunchKernelGGL(inflate_kernel, dim3((n + INF_WAVES_PER_WG - 1) / INF_WAVES_PER_WG),
+	const auto kernel = pieces ? inflate_kernel<true> : inflate_kernel<false>;
+	hipLaunchKernelGGL(kernel, dim3((n + INF_WAVES_PER_WG - 1) / INF_WAVES_PER_WG),
 	    dim3(64 * INF_WAVES_PER_WG), 0, s, d_src, src_bytes, d_members, n, d_dst, dst_cap, d_results);
 }
 

@@ -479,8 +479,10 @@ struct lane_reader {
  * loads, matches with LDS copies) instead of this lane chasing its own output through global
  * memory one match at a time.  Members the LDS-window kernel cannot take (slot above 64 KiB,
  * more than LA_INFLATE_MAXSEQ matches) are flagged in E.todo for an EMIT = false launch.
+ *
+ * PIECES: the members are pieces of one raw-deflate stream (LA_GZ_OPT_PIECES; the rules are in la_deflate_dev.h).
  */
-template <bool EMIT>
+template <bool EMIT, bool PIECES>
 __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t *__restrict__ src,
     uint64_t src_bytes, const la_gz_member *__restrict__ members, uint32_t n, uint8_t *dst,
     uint64_t dst_cap, la_gz_result *__restrict__ results, uint8_t *scratch, const uint32_t *__restrict__ only,
@@ -699,7 +701,7 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 				const uint32_t dist = bs + lb_peek(B, xb);
 				lb_drop(B, xb);
 				IL_CHECK_TRUNC();
-				if (dist > op) { status = LA_ST_GZ_DATA; goto done; }
+				if (dist > op) { status = dfl_far_back<PIECES>(); goto done; }
 				if (op + length > cap) { status = LA_ST_GZ_OUT_FULL; goto done; }
 				if (EMIT) {
 					IL_PUT_SEQ(dist);
@@ -738,6 +740,12 @@ __global__ __launch_bounds__(IL_THREADS) void inflate_lanes_kernel(const uint8_t
 		}
 		if (last)
 			break;
+		/* (bits that came along from past the span were never counted: what is left of the span is the buffer's
+		 * bits less those, or the buffer's plus the bytes not yet fed to it) */
+		if (dfl_piece_end<PIECES>((int64_t)B.bits + 8 * ((int64_t)B.iend - (int64_t)B.ip))) {
+			status = LA_ST_GZ_PIECE_END;
+			break;
+		}
 	}
 done:
 	if ((tid & 63) == 0) { IL_CNT(0, IL_NOW() - il_t_start); IL_CNT(1, 1); }
@@ -826,20 +834,22 @@ uint64_t la_inflate_lanes_scratch_bytes(uint32_t n)
 
 void la_launch_inflate_lanes(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results,
-    void *d_scratch, const uint32_t *d_only)
+    void *d_scratch, const uint32_t *d_only, bool pieces)
 {
 	if (n == 0) return;
 	la_inflate_emit none = {};
-	hipLaunchKernelGGL(inflate_lanes_kernel<false>, dim3((n + IL_THREADS - 1) / IL_THREADS), dim3(IL_THREADS), 0, s,
+	const auto kernel = pieces ? inflate_lanes_kernel<false, true> : inflate_lanes_kernel<false, false>;
+	hipLaunchKernelGGL(kernel, dim3((n + IL_THREADS - 1) / IL_THREADS), dim3(IL_THREADS), 0, s,
 	    d_src, src_bytes, d_members, n, d_dst, dst_cap, d_results, (uint8_t *)d_scratch, d_only, none);
 }
 
 void la_launch_inflate_symbols(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, uint64_t dst_cap, la_gz_result *d_results,
-    void *d_scratch, la_inflate_emit E)
+    void *d_scratch, la_inflate_emit E, bool pieces)
 {
 	if (n == 0) return;
-	hipLaunchKernelGGL(inflate_lanes_kernel<true>, dim3((n + IL_THREADS - 1) / IL_THREADS), dim3(IL_THREADS), 0, s,
+	const auto kernel = pieces ? inflate_lanes_kernel<true, true> : inflate_lanes_kernel<true, false>;
+	hipLaunchKernelGGL(kernel, dim3((n + IL_THREADS - 1) / IL_THREADS), dim3(IL_THREADS), 0, s,
 	    d_src, src_bytes, d_members, n, (uint8_t *)nullptr, dst_cap, d_results, (uint8_t *)d_scratch,
 	    (const uint32_t *)nullptr, E);
 }

@@ -37,6 +37,20 @@ class GzDevicePlan:
         return self.d_results.cpu().numpy().view(N.GZ_RESULT_DTYPE)[:self.n]
 
 
+def piece_index(image, start=0, at_eof=True, **kw):
+    """Piece table of ONE member's body (image[start:] starts on a byte-aligned deflate block boundary, e.g. behind the
+    gzip header): one la_gz_member per span between flush markers, for GzDevicePlan + decode_pieces."""
+    return N.gz_pieces(image, start, at_eof, **kw)
+
+
+def decode_pieces(ctx, d_src, pieces, options=0):
+    """la_gpu_gzip_decode with LA_GZ_OPT_PIECES over a piece table; returns (plan, results).  A piece is confirmed
+    when it answers LA_ST_GZ_PIECE_END with consumed == src_len (or LA_ST_OK: its stream ends in it)."""
+    plan = GzDevicePlan(ctx, d_src, pieces)
+    plan.run(options | N.LA_GZ_OPT_PIECES)
+    return plan, plan.results()
+
+
 def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0, options=0, framing=0):
     """Device gzip compression (la_gpu_gzip_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8 CUDA
     tensor holding the concatenated gzip members (harness for the tests).  options: 0 fixed Huffman, 1 the smallest of

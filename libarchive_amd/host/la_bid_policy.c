@@ -58,13 +58,41 @@ const unsigned char *la_bid_peek(struct archive_read_filter *filter, size_t want
 	return p;
 }
 
+int la_gz_flush_points_enabled(void)
+{
+	const char *v = getenv("LA_GZIP_FLUSH_POINTS");
+	return v != NULL && v[0] == '1';
+}
+
+/* LA_GZIP_FLUSH_POINTS=1: ONE member whose body is a chain of flush points (00 00 FF FF, la_gz_pieces_build) decodes a
+ * piece per lane.  Evidence inside the look-ahead: at least LA_BID_GZ_MARKERS markers behind the header, none further
+ * than LA_BID_GZ_GAP from the one before (the first: from the header) -- the pieces of zlib's Z_FULL_FLUSH writers,
+ * pigz -i and gzip:single-member are that close; four stray 00 00 FF FF in 256 KiB of a plain deflate stream, each
+ * within 128 KiB of the last, are not impossible, and such a stream then costs what LA_GPU_BID=all costs. */
+#define LA_BID_GZ_MARKERS 4u
+#define LA_BID_GZ_GAP     ((size_t)128 << 10)
+static int gzip_flush_points(const unsigned char *p, size_t n, size_t hdr_len)
+{
+	size_t prev = hdr_len;
+	for (unsigned k = 0; k < LA_BID_GZ_MARKERS; k++) {
+		const size_t mk = (size_t)la_gz_next_marker(p, n, prev);
+		if (mk >= n || mk - prev > LA_BID_GZ_GAP)
+			return 0;
+		prev = mk + 4;
+	}
+	return 1;
+}
+
 /* gzip: p[0..n) starts with a member whose header (hdr_len bytes, parsed by the caller) carries no BGZF size.
  * 1 = take it.  A second member header inside the look-ahead counts as evidence of a many-member stream; the
- * candidate test is the strict one of the boundary search (XFL / OS bytes that real writers emit). */
+ * candidate test is the strict one of the boundary search (XFL / OS bytes that real writers emit).  With
+ * LA_GZIP_FLUSH_POINTS=1 a chain of flush points counts too. */
 int la_bid_gzip_parallel(const unsigned char *p, size_t n, size_t hdr_len, size_t lookahead)
 {
 	if (n < lookahead)
 		return 1;	/* the whole stream is smaller than the look-ahead */
+	if (la_gz_flush_points_enabled() && gzip_flush_points(p, n, hdr_len))
+		return 1;
 	for (size_t i = hdr_len + 1; i + 10 <= n; i++) {
 		const unsigned char *q = memchr(p + i, 0x1f, n - 10 - i + 1);
 		if (q == NULL)

@@ -21,7 +21,7 @@
  *     first 64 KiB were produced (gzip.c:160-163, :196-201, :280-296).
  * There is no CPU decode path: without a usable GPU, init() fails the open.
  *
- * Environment: LA_GPU_DEVICE, LA_GPU_BATCH_MIB (as for lz4), LA_GZIP_STRICT.
+ * Environment: LA_GPU_DEVICE, LA_GPU_BATCH_MIB (as for lz4), LA_GZIP_STRICT, LA_GZIP_FLUSH_POINTS.
  */
 #include "la_read_private.h"
 #include "../../include/la_gpu.h"
@@ -77,6 +77,17 @@ struct gzip_private {
 	size_t o_res;
 	la_verdict verdict;	/* what the next read() reports once the bytes in front of it are out */
 	int eof;
+	/* Piece mode (LA_GZIP_FLUSH_POINTS=1): ONE member decoded from its flush points, a piece per lane or wave
+	 * (la_gz_pieces_build, LA_GZ_OPT_PIECES).  The member may span any number of windows; what is carried from one
+	 * to the next is {in the member, CRC32 so far, bytes so far}. */
+	int fp_on;
+	struct { int in_member; uint32_t crc; uint64_t bytes; } pm;
+	int pm_declined;	/* the member at the head of the window is decoded the ordinary way (its pieces depend on each other) */
+	uint32_t pm_skip, pm_cap;	/* as hint_skip / hint_cap, for the first piece of the next window */
+	size_t pm_from;		/* where the pieces of the window in flight start: behind the header in a member's first window, else 0 */
+	la_gz_pieces pcs;
+	int inflight_pieces;	/* the window in flight is st->pcs, not st->idx */
+	int pm_retry;		/* the last walk asked for the same bytes again on other terms (merged pieces, larger slots, the ordinary way) */
 };
 
 static int gzip_bidder_bid(struct archive_read_filter_bidder *, struct archive_read_filter *);
@@ -177,6 +188,7 @@ static int gzip_bidder_init(struct archive_read_filter *self)
 		if (v != NULL && strtoull(v, NULL, 10) > 0 && strtoull(v, NULL, 10) < st->span_limit)
 			st->span_limit = strtoull(v, NULL, 10);
 	}
+	st->fp_on = la_gz_flush_points_enabled();
 	st->trace = getenv("LA_GPU_TRACE") != NULL && atoi(getenv("LA_GPU_TRACE")) != 0;
 	st->no_ahead = getenv("LA_GZ_NO_COPY_AHEAD") != NULL && atoi(getenv("LA_GZ_NO_COPY_AHEAD")) != 0;
 	if (la_window_open(self, &st->w, "gzip") != ARCHIVE_OK) {
@@ -199,6 +211,67 @@ static int gzip_read_header(struct archive_read_filter *self, struct archive_ent
 }
 
 #define ALIGN256(x) (((x) + 255) & ~(size_t)255)
+
+/*
+ * The end of a window's stream-order walk, for members and pieces alike: bring the bytes of units [0, take) behind
+ * the carry and decide how much of [carry | new bytes] may go out now.  total: stream offset behind the units taken
+ * whole; last_out: bytes of a failing last unit that still count as produced; cutoff: deliver only up to here
+ * (UINT64_MAX: no error follows).
+ */
+static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, const la_gz_member *mem,
+    const la_gz_result *res, uint32_t take, int contiguous, uint32_t last_out, uint64_t total, uint64_t cutoff,
+    double b0, double b1)
+{
+	la_gpu_ctx *gpu = st->w.gpu;
+	uint64_t new_bytes = (total - st->total_out) + last_out;
+	const int ahead = st->ahead_ok && take && contiguous && last_out == 0 && st->carry_len == st->ahead_rem &&
+	    new_bytes <= st->ahead_len;
+	st->ahead_ok = 0;
+	if (ahead) {
+		/* they came over while the caller was busy (the sync above covered the copy): carry in front, change slabs */
+		if (st->carry_len)
+			memcpy(st->slab2.p, st->slab.p, st->carry_len);
+		const la_buf tb = st->slab; st->slab = st->slab2; st->slab2 = tb;
+	} else if (la_buf_pinned(gpu, &st->slab, st->carry_len + (size_t)new_bytes + 16, st->carry_len) < 0)
+		return la_window_fail(self, &st->w, "pinned slab allocation");
+	uint8_t *dstp = st->slab.p + st->carry_len;
+	const double b2 = st->trace ? gz_now() : 0;
+	if (take && !ahead) {
+		if (contiguous && last_out == 0) {
+			if (la_gpu_memcpy_d2h(gpu, dstp, st->d_dst.p, (size_t)new_bytes) != LA_OK)
+				return la_window_fail(self, &st->w, "device to host copy");
+		} else {
+			size_t w = 0;
+			for (uint32_t i = 0; i < take; i++) {
+				size_t len = res[i].out_len;
+				if (len && la_gpu_memcpy_d2h(gpu, dstp + w, st->d_dst.p + mem[i].dst_off, len) != LA_OK)
+					return la_window_fail(self, &st->w, "device to host copy");
+				w += len;
+			}
+		}
+		if (la_gpu_sync(gpu) != LA_OK)
+			return la_window_fail(self, &st->w, "device to host copy");
+	}
+	if (st->trace)
+		fprintf(stderr, "la_gzip:   h2d+decode %.1f ms, walk+grow %.1f ms, d2h %.1f ms (%llu bytes, contiguous %d, copied ahead %d)\n",
+		    b1 - b0, b2 - b1, gz_now() - b2, (unsigned long long)new_bytes, contiguous, ahead);
+	st->total_out = total + last_out;
+	st->carry_len += (size_t)new_bytes;
+
+	/* how much of [carry | new bytes] may go out now */
+	uint64_t slab_start = st->total_out - st->carry_len;	/* stream offset of slab[0] */
+	uint64_t lim;
+	if (cutoff != UINT64_MAX)
+		lim = cutoff;					/* an error follows: the reference's count */
+	else if (st->eof)
+		lim = st->total_out;				/* clean end: everything */
+	else
+		lim = (st->total_out / OUT_BLOCK) * OUT_BLOCK;	/* keep the partial last block back */
+	if (lim < slab_start)
+		lim = slab_start;
+	st->last_ret = (size_t)(lim - slab_start);
+	return 0;
+}
 
 /*
  * One batch: decode every indexed member, then walk the results in stream
@@ -392,55 +465,252 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 		}
 	}
 
-	/* ---- bring the bytes of members [0, take) behind the carry ---- */
-	uint64_t new_bytes = (total - st->total_out) + last_out;
-	const int ahead = st->ahead_ok && take && contiguous && last_out == 0 && st->carry_len == st->ahead_rem &&
-	    new_bytes <= st->ahead_len;
-	st->ahead_ok = 0;
-	if (ahead) {
-		/* they came over while the caller was busy (the sync above covered the copy): carry in front, change slabs */
-		if (st->carry_len)
-			memcpy(st->slab2.p, st->slab.p, st->carry_len);
-		const la_buf tb = st->slab; st->slab = st->slab2; st->slab2 = tb;
-	} else if (la_buf_pinned(gpu, &st->slab, st->carry_len + (size_t)new_bytes + 16, st->carry_len) < 0)
-		return la_window_fail(self, &st->w, "pinned slab allocation");
-	uint8_t *dstp = st->slab.p + st->carry_len;
-	const double b2 = st->trace ? gz_now() : 0;
-	if (take && !ahead) {
-		if (contiguous && last_out == 0) {
-			if (la_gpu_memcpy_d2h(gpu, dstp, st->d_dst.p, (size_t)new_bytes) != LA_OK)
-				return la_window_fail(self, &st->w, "device to host copy");
-		} else {
-			size_t w = 0;
-			for (uint32_t i = 0; i < take; i++) {
-				size_t len = res[i].out_len;
-				if (len && la_gpu_memcpy_d2h(gpu, dstp + w, st->d_dst.p + x->members[i].dst_off, len) != LA_OK)
-					return la_window_fail(self, &st->w, "device to host copy");
-				w += len;
-			}
-		}
-		if (la_gpu_sync(gpu) != LA_OK)
-			return la_window_fail(self, &st->w, "device to host copy");
-	}
-	if (st->trace)
-		fprintf(stderr, "la_gzip:   h2d+decode %.1f ms, walk+grow %.1f ms, d2h %.1f ms (%llu bytes, contiguous %d, copied ahead %d)\n",
-		    b1 - b0, b2 - b1, gz_now() - b2, (unsigned long long)new_bytes, contiguous, ahead);
-	st->total_out = total + last_out;
-	st->carry_len += (size_t)new_bytes;
+	return gz_slab(self, st, x->members, res, take, contiguous, last_out, total, cutoff, b0, b1);
+}
 
-	/* how much of [carry | new bytes] may go out now */
-	uint64_t slab_start = st->total_out - st->carry_len;	/* stream offset of slab[0] */
-	uint64_t lim;
-	if (cutoff != UINT64_MAX)
-		lim = cutoff;					/* an error follows: the reference's count */
-	else if (st->eof)
-		lim = st->total_out;				/* clean end: everything */
-	else
-		lim = (st->total_out / OUT_BLOCK) * OUT_BLOCK;	/* keep the partial last block back */
-	if (lim < slab_start)
-		lim = slab_start;
-	st->last_ret = (size_t)(lim - slab_start);
-	return 0;
+/*
+ * One window of piece mode, the counterpart of gzip_run_batch: phase 0 queues la_gpu_gzip_decode with
+ * LA_GZ_OPT_PIECES over st->pcs, phase 1 walks the results in stream order.  Piece k is confirmed only by
+ * LA_ST_GZ_PIECE_END with consumed == src_len (la_host.h: the chain is then correct by induction); what the first
+ * unconfirmed piece answers decides how the walk ends, and whatever the pieces behind it decoded is discarded.
+ */
+static int gzip_run_pieces(struct archive_read_filter *self, struct gzip_private *st, size_t *used, int phase)
+{
+	const la_gz_pieces *x = &st->pcs;
+	const uint32_t n = x->n;
+	size_t o = 0;
+	const size_t o_mem = o; o += ALIGN256((size_t)n * sizeof(la_gz_member));
+	const size_t o_res = o; o += ALIGN256((size_t)n * sizeof(la_gz_result));
+	la_gpu_ctx *gpu = st->w.gpu;
+	const double b0 = st->trace ? gz_now() : 0;
+	if (phase == 0) {
+		if (la_buf_dev(gpu, &st->d_dst, (size_t)x->max_out + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o) < 0)
+			return la_window_fail(self, &st->w, "device allocation");
+		uint8_t *T = st->d_tabs.p;
+		if (la_gpu_memcpy_h2d(gpu, T + o_mem, x->pieces, (size_t)n * sizeof(la_gz_member)) != LA_OK)
+			return la_window_fail(self, &st->w, "host to device copy");
+		la_gz_batch bt;
+		memset(&bt, 0, sizeof(bt));
+		bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
+		bt.d_members = (const la_gz_member *)(T + o_mem); bt.n_members = n;
+		bt.d_dst = st->d_dst.p; bt.dst_cap = x->max_out;
+		bt.d_results = (la_gz_result *)(T + o_res);
+		bt.options = LA_GZ_OPT_PIECES;
+		if (la_gpu_gzip_decode(gpu, &bt) != LA_OK)
+			return la_window_fail(self, &st->w, "la_gpu_gzip_decode");
+		return 0;
+	}
+	if (la_buf_host(&st->h_res, (size_t)n * sizeof(la_gz_result)) < 0) {
+		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
+		return ARCHIVE_FATAL;
+	}
+	const la_gz_result *res = (const la_gz_result *)st->h_res.p;
+	if (la_gpu_memcpy_d2h(gpu, st->h_res.p, st->d_tabs.p + o_res, (size_t)n * sizeof(la_gz_result)) != LA_OK ||
+	    la_gpu_sync(gpu) != LA_OK)
+		return la_window_fail(self, &st->w, "result copy");
+	const double b1 = st->trace ? gz_now() : 0;
+
+	uint64_t total = st->total_out, cutoff = UINT64_MAX;
+	uint32_t take = 0, last_out = 0;
+	int contiguous = 1, stop = 0;
+	const uint32_t prev_skip = st->pm_skip, prev_cap = st->pm_cap;
+	st->pm_skip = 0;		/* (pm_cap stays for the rest of the member: "from that piece on") */
+	st->pm_retry = 0;
+	*used = (size_t)x->consumed;
+	if (!st->pm.in_member && st->total_out < OUT_BLOCK) {
+		/* header metadata, as in gzip_run_batch (dropped again should the member leave piece mode: it is then
+		 * parsed a second time) */
+		la_gz_header h;
+		la_gz_header_parse(st->stage.p, st->stage_len, &h);
+		st->mtime = h.mtime;
+		if (h.name_off) {
+			free(st->name);
+			st->name = strdup((const char *)st->stage.p + h.name_off);
+		}
+	}
+	for (uint32_t i = 0; i < n && !stop; i++) {
+		const la_gz_result *r = &res[i];
+		const la_gz_member *m = &x->pieces[i];
+		/* where the next window starts when piece i has to be decoded again (piece 0 of a member's first
+		 * window: at the header) */
+		const size_t again = i == 0 ? 0 : (size_t)m->src_off;
+		const int more_behind = m->src_off + m->src_len < st->stage_len || !st->w.upstream_eof;
+		stop = 1;
+		switch (r->status) {
+		case LA_ST_GZ_PIECE_END:
+			if (r->consumed != m->src_len) {	/* (a span the image cut short: not a boundary we can vouch for) */
+				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
+				cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
+				break;
+			}
+			st->pm.crc = la_crc32_combine(st->pm.crc, r->crc32, r->out_len);
+			st->pm.bytes += r->out_len;
+			st->pm.in_member = 1;
+			if (i + 1 < n && (r->out_len != m->dst_cap || (m->dst_cap & 15)))
+				contiguous = 0;
+			take = i + 1;
+			total += r->out_len;
+			stop = 0;
+			break;
+		case LA_ST_OK: {
+			/* the stream's final block ended inside this piece: the member's trailer follows */
+			const uint64_t tr = m->src_off + (uint64_t)r->consumed;
+			if (tr + 8 > st->stage_len && !st->w.upstream_eof) {
+				*used = again;	/* the trailer lies beyond this window */
+				break;
+			}
+			take = i + 1;
+			if (tr + 8 > st->stage_len) {
+				/* short trailer at the end of input: the LA_ST_GZ_NO_TRAILER rules */
+				la_verdict_set(&st->verdict, ARCHIVE_FATAL, NULL);
+				cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
+				    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
+				last_out = r->out_len;
+				break;
+			}
+			const uint8_t *t = st->stage.p + tr;
+			const uint32_t crc = la_crc32_combine(st->pm.crc, r->crc32, r->out_len);
+			const uint32_t isize = (uint32_t)(st->pm.bytes + r->out_len);
+			const uint32_t t_crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+			const uint32_t t_len = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+			if (st->strict && (t_crc != crc || t_len != isize)) {
+				/* as a many-member mismatch: everything in front of the unit that shows it, then the error */
+				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s",
+				    la_status_message(t_crc != crc ? LA_ST_GZ_BAD_CRC : LA_ST_GZ_BAD_ISIZE));
+				cutoff = total;
+				take = i;
+				break;
+			}
+			total += r->out_len;
+			/* the member is over: indexing resumes the ordinary way behind its trailer */
+			memset(&st->pm, 0, sizeof(st->pm));
+			st->pm_cap = 0;
+			*used = (size_t)(tr + 8);
+			break;
+		}
+		case LA_ST_GZ_NEEDS_HISTORY:
+			/* the blocks behind this flush point reach back into the piece before (Z_SYNC_FLUSH) */
+			if (st->pm_from) {
+				/* the member's header is still at the head of the window, so nothing of the member has left
+				 * a walk: piece mode is left, the pieces confirmed above are dropped, and the member is
+				 * indexed again from its header the ordinary way */
+				memset(&st->pm, 0, sizeof(st->pm));
+				st->pm_cap = 0;
+				st->pm_declined = st->pm_retry = 1;
+				total = st->total_out;
+				take = 0;
+				contiguous = 1;
+				*used = 0;
+				break;
+			}
+			/* a member that changes its nature after pieces of it are out: refused by name (deliberate
+			 * divergences) -- the device has no window of the bytes in front to go on from */
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL,
+			    "gzip member stops being independent pieces: blocks behind a flush point depend on earlier output (read it without LA_GZIP_FLUSH_POINTS)");
+			cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
+			break;
+		case LA_ST_GZ_TRUNCATED:
+			if (more_behind) {
+				/* the marker this piece ends in is not a block boundary (00 00 FF FF inside stored data or
+				 * Huffman bits): merge the piece with the next one and decode again from here */
+				*used = again;
+				st->pm_skip = (i == 0 ? prev_skip : 0) + 1;
+				st->pm_retry = 1;
+				break;
+			}
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
+			cutoff = ((total + r->out_len) / OUT_BLOCK) * OUT_BLOCK;
+			last_out = r->out_len;
+			take = i + 1;
+			break;
+		case LA_ST_GZ_OUT_FULL: {
+			*used = again;
+			const uint32_t base = m->dst_cap > prev_cap ? m->dst_cap : prev_cap;
+			if (base >= st->slot_limit) {
+				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
+				cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
+				break;
+			}
+			st->pm_cap = base > st->slot_limit / 2 ? st->slot_limit : base * 2;
+			st->pm_skip = i == 0 ? prev_skip : 0;
+			st->pm_retry = 1;
+			break;
+		}
+		case LA_ST_GZ_DATA:
+		default:
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
+			cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
+			    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
+			last_out = r->out_len;
+			take = i + 1;
+			break;
+		}
+	}
+	if (!stop && st->w.upstream_eof && x->consumed >= st->stage_len) {
+		/* every piece confirmed, no final block, no byte left: the member was cut behind a flush point */
+		la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
+		cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
+	} else if (!stop && x->end_kind == LA_END_GZ_TOO_LARGE) {
+		la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
+		cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
+	}
+	st->ahead_ok = 0;
+	return gz_slab(self, st, x->pieces, res, take, contiguous, last_out, total, cutoff, b0, b1);
+}
+
+/*
+ * gz_prepare's piece-mode branch, behind the gather and the upload.  2: the window is not one for piece mode (go on
+ * the ordinary way); otherwise as gz_prepare.
+ */
+static int gz_prepare_pieces(struct archive_read_filter *self, struct gzip_private *st)
+{
+	size_t from = 0;
+	if (!st->pm.in_member) {
+		/* a member without a BGZF size enters piece mode if the window shows a marker inside its body */
+		la_gz_header h;
+		const size_t hlen = la_gz_header_parse(st->stage.p, st->stage_len, &h);
+		if (hlen == 0 || h.bgzf_size || hlen >= st->stage_len ||
+		    la_gz_next_marker(st->stage.p, st->stage_len, hlen) >= st->stage_len)
+			return 2;
+		from = hlen;
+	}
+	if (la_gz_pieces_build(st->stage.p, st->stage_len, from, st->w.upstream_eof, st->pm_skip, st->pm_cap,
+	    st->w.out_budget, st->span_limit, &st->pcs) != 0) {
+		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
+		return ARCHIVE_FATAL;
+	}
+	st->pm_from = from;
+	if (st->pcs.n == 0) {
+		const int kind = st->pcs.end_kind;
+		la_gz_pieces_free(&st->pcs);
+		if (la_gpu_sync(st->w.gpu) != LA_OK)	/* the upload: the window may move now */
+			return la_window_fail(self, &st->w, "host to device copy");
+		if (kind == LA_END_GZ_TOO_LARGE)
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
+		else if (st->w.upstream_eof)
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");	/* in a member, no byte left */
+		else if (st->w.batch_bytes < st->w.max_batch_bytes)
+			st->w.batch_bytes *= 2;		/* no marker behind the current position: as for a member larger than the window */
+		else if (from) {
+			st->pm_skip = st->pm_cap = 0;
+			st->pm_declined = 1;		/* (the LA_ST_GZ_NEEDS_HISTORY route, before anything of the member is out) */
+		} else
+			la_verdict_set(&st->verdict, ARCHIVE_FATAL,
+			    "gzip member stops being independent pieces: no flush point within LA_GPU_MAX_BATCH_MIB (read it without LA_GZIP_FLUSH_POINTS)");
+		return 0;
+	}
+	size_t used = 0;
+	const int rc = gzip_run_pieces(self, st, &used, 0);
+	if (rc < 0) {
+		la_gz_pieces_free(&st->pcs);
+		return rc;
+	}
+	st->inflight = st->inflight_pieces = 1;
+	st->ahead_ok = 0;
+	la_window_ramp(&st->w);
+	if (st->trace)
+		fprintf(stderr, "la_gzip: window %zu bytes, %u pieces queued from %zu\n", st->stage_len, st->pcs.n, from);
+	return 1;
 }
 
 /*
@@ -462,6 +732,11 @@ static int gz_prepare(struct archive_read_filter *self, struct gzip_private *st)
 	    (la_buf_dev(st->w.gpu, &st->d_src, st->stage_len + 64) < 0 ||
 	     la_gpu_memcpy_h2d(st->w.gpu, st->d_src.p, st->stage.p, st->stage_len) != LA_OK))
 		return la_window_fail(self, &st->w, "host to device copy");
+	if (st->fp_on && !st->pm_declined) {
+		const int pr = gz_prepare_pieces(self, st);
+		if (pr != 2)
+			return pr;
+	}
 	if (la_gz_index_build_ex(st->stage.p, st->stage_len, st->w.upstream_eof, st->hint_skip, st->hint_cap,
 	    st->loose ? 0 : LA_GZ_INDEX_STRICT, st->w.out_budget, st->span_limit, &st->idx) != 0) {
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
@@ -552,9 +827,14 @@ static ssize_t gzip_filter_read(struct archive_read_filter *self, const void **p
 		/* the window in flight: results, stream-order walk, slab */
 		size_t used = 0;
 		const double t2 = st->trace ? gz_now() : 0;
-		int rc = gzip_run_batch(self, st, &st->idx, &used, 1);
-		st->inflight = 0;
+		const int pieces = st->inflight_pieces;
+		int rc = pieces ? gzip_run_pieces(self, st, &used, 1) : gzip_run_batch(self, st, &st->idx, &used, 1);
+		st->inflight = st->inflight_pieces = 0;
 		int made_progress = used > 0;
+		if (pieces)
+			la_gz_pieces_free(&st->pcs);
+		else if (made_progress)
+			st->pm_declined = 0;	/* (the member that left piece mode is behind us, or will be found declined again) */
 		if (st->trace)
 			fprintf(stderr, "la_gzip:   finished in %.1f ms, used %zu of %zu, out %zu\n", gz_now() - t2, used, st->stage_len, st->last_ret);
 		la_gz_index_free(&st->idx);
@@ -563,7 +843,8 @@ static ssize_t gzip_filter_read(struct archive_read_filter *self, const void **p
 		if (used < st->stage_len)
 			memmove(st->stage.p, st->stage.p + used, st->stage_len - used);
 		st->stage_len -= used;
-		if (!made_progress && !st->verdict.rc && !st->eof && st->hint_skip == 0 && st->hint_cap == 0) {
+		if (!made_progress && !st->verdict.rc && !st->eof && st->hint_skip == 0 && st->hint_cap == 0 &&
+		    !(pieces && st->pm_retry)) {
 			/* nothing could be finished in this window: it has to grow */
 			if (st->w.upstream_eof) { st->eof = 1; continue; }
 			st->w.batch_bytes *= 2;
@@ -591,7 +872,9 @@ static int gzip_filter_close(struct archive_read_filter *self)
 		return ARCHIVE_OK;
 	la_gpu_ctx *gpu = st->w.gpu;
 	la_gpu_sync(gpu);
-	if (st->inflight)
+	if (st->inflight && st->inflight_pieces)
+		la_gz_pieces_free(&st->pcs);
+	else if (st->inflight)
 		la_gz_index_free(&st->idx);
 	la_buf_release(gpu, &st->stage);
 	la_buf_release(gpu, &st->slab);

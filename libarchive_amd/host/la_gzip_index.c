@@ -104,15 +104,16 @@ static int push(la_gz_index *x)
 	return 0;
 }
 
-/* first offset >= from with the bytes 1f 8b 08, or len: the one pass over the window that finds plain gzip
- * members (they do not say how long they are).  Two compares per 32 bytes where AVX2 is there, memchr otherwise. */
+/* first offset >= from with the bytes b0 b1 b2, or len: the one pass over the window that finds plain gzip
+ * members (1f 8b 08: they do not say how long they are) and flush markers (la_gz_pieces_build).  Two compares per
+ * 32 bytes where AVX2 is there, memchr otherwise. */
 #if defined(__x86_64__)
 #include <immintrin.h>
 
 __attribute__((target("avx2")))
-static uint64_t find_magic_avx2(const uint8_t *p, uint64_t len, uint64_t i)
+static uint64_t find3_avx2(const uint8_t *p, uint64_t len, uint64_t i, uint8_t b0, uint8_t b1, uint8_t b2)
 {
-	const __m256i a = _mm256_set1_epi8(0x1f), b = _mm256_set1_epi8((char)0x8b);
+	const __m256i a = _mm256_set1_epi8((char)b0), b = _mm256_set1_epi8((char)b1);
 	for (; i + 34 <= len; i += 32) {
 		__m256i x = _mm256_loadu_si256((const __m256i *)(p + i));
 		__m256i y = _mm256_loadu_si256((const __m256i *)(p + i + 1));
@@ -120,36 +121,41 @@ static uint64_t find_magic_avx2(const uint8_t *p, uint64_t len, uint64_t i)
 		while (m) {
 			unsigned k = (unsigned)__builtin_ctz(m);
 			m &= m - 1;
-			if (p[i + k + 2] == 0x08)
+			if (p[i + k + 2] == b2)
 				return i + k;
 		}
 	}
 	for (; i + 3 <= len; i++)
-		if (p[i] == 0x1f && p[i + 1] == 0x8b && p[i + 2] == 0x08)
+		if (p[i] == b0 && p[i + 1] == b1 && p[i + 2] == b2)
 			return i;
 	return len;
 }
 #endif
 
-static uint64_t find_magic(const uint8_t *p, uint64_t len, uint64_t from)
+static uint64_t find3(const uint8_t *p, uint64_t len, uint64_t from, uint8_t b0, uint8_t b1, uint8_t b2)
 {
 #if defined(__x86_64__)
 	static int have_avx2 = -1;
 	if (have_avx2 < 0)
 		have_avx2 = (__builtin_cpu_supports("avx2") && getenv("LA_NO_AVX2") == NULL) ? 1 : 0;
 	if (have_avx2)
-		return find_magic_avx2(p, len, from);
+		return find3_avx2(p, len, from, b0, b1, b2);
 #endif
 	while (from + 3 <= len) {
-		const uint8_t *hit = memchr(p + from, 0x1f, (size_t)(len - from - 2));
+		const uint8_t *hit = memchr(p + from, b0, (size_t)(len - from - 2));
 		if (!hit)
 			return len;
 		uint64_t o = (uint64_t)(hit - p);
-		if (p[o + 1] == 0x8b && p[o + 2] == 0x08)
+		if (p[o + 1] == b1 && p[o + 2] == b2)
 			return o;
 		from = o + 1;
 	}
 	return len;
+}
+
+static uint64_t find_magic(const uint8_t *p, uint64_t len, uint64_t from)
+{
+	return find3(p, len, from, 0x1f, 0x8b, 0x08);
 }
 
 /* next offset >= from where a plausible member header starts, or len */
@@ -271,4 +277,104 @@ int la_gz_index_build_ex(const uint8_t *img, uint64_t len, int at_eof, uint32_t 
 int la_gz_index_build(const uint8_t *img, uint64_t len, int at_eof, la_gz_index *x)
 {
 	return la_gz_index_build_ex(img, len, at_eof, 0, 0, 0, 0, LA_GZ_SPAN_LIMIT, x);
+}
+
+/* ------------------------------------------------------------------ pieces of ONE member (flush points) */
+
+/* offset of the first 00 00 FF FF at or behind `from` (the empty stored block of zlib's Z_SYNC_FLUSH / Z_FULL_FLUSH,
+ * or the LEN / NLEN of any empty stored block), or len.  The pass looks for 00 FF FF -- 00 00 would stop at every
+ * run of zeros -- and then at the byte in front. */
+uint64_t la_gz_next_marker(const uint8_t *img, uint64_t len, uint64_t from)
+{
+	uint64_t at = from + 1;
+	while (at + 3 <= len) {
+		const uint64_t o = find3(img, len, at, 0x00, 0xFF, 0xFF);
+		if (o >= len)
+			return len;
+		if (img[o - 1] == 0x00)
+			return o - 1;
+		at = o + 1;
+	}
+	return len;
+}
+
+void la_gz_pieces_free(la_gz_pieces *x)
+{
+	if (!x) return;
+	free(x->pieces);
+	memset(x, 0, sizeof(*x));
+}
+
+/* The first guess at a piece's output slot, from its compressed length alone (a piece says nothing else):
+ *   max(64 KiB, 8 x length), but never more than deflate can make of that many bytes (1032 x length + 64).
+ * 64 KiB holds every piece of this project's writer (at most 48 KiB of input each) and is the largest slot the
+ * LDS-window expand takes; 8 x covers text at zlib's usual 3-4 x twice over; the 1032 x bound keeps the slots of
+ * tiny pieces (a bare marker: 5 bytes) tiny.  A piece that needs more answers LA_ST_GZ_OUT_FULL and the caller
+ * comes back with min_cap doubled. */
+static uint32_t piece_slot(uint64_t span, uint32_t min_cap)
+{
+	uint64_t s = span * 8 > 65536 ? span * 8 : 65536;
+	if (s < min_cap) s = min_cap;
+	const uint64_t bound = span * 1032 + 64;
+	if (s > bound) s = bound;
+	if (s > LA_GZ_MAX_SLOT) s = LA_GZ_MAX_SLOT;
+	return (uint32_t)s;
+}
+
+int la_gz_pieces_build(const uint8_t *img, uint64_t len, uint64_t from, int at_eof, uint32_t first_skip,
+    uint32_t min_cap, uint64_t out_budget, uint64_t span_limit, la_gz_pieces *x)
+{
+	uint64_t pos = from < len ? from : len, out = 0, search = pos;
+	uint32_t skip = first_skip;
+	memset(x, 0, sizeof(*x));
+	x->end_kind = LA_END_NEED_MORE;
+	x->consumed = pos;
+	for (;;) {
+		if (out_budget && x->n > 0 && out >= out_budget)
+			break;			/* the rest is the next window's */
+		uint64_t end;
+		int open = 0;
+		const uint64_t mk = la_gz_next_marker(img, len, search);
+		if (mk < len && skip) {		/* a marker the decode has refuted for this piece */
+			skip--;
+			search = mk + 1;
+			continue;
+		}
+		if (mk < len)
+			end = mk + 4;
+		else if (at_eof && pos < len) {
+			end = len;		/* the last span: the stream's final block, or a cut */
+			open = 1;
+		} else {
+			if (at_eof)
+				x->end_kind = LA_END_EOF;
+			break;			/* (not at the end of input: these bytes are the next window's) */
+		}
+		if (end - pos > span_limit) {
+			x->end_kind = LA_END_GZ_TOO_LARGE;
+			break;
+		}
+		if (x->n == x->cap) {
+			const uint32_t nc = x->cap ? x->cap * 2 : 256;
+			la_gz_member *m = realloc(x->pieces, (size_t)nc * sizeof(*m));
+			if (!m) return -1;
+			x->pieces = m;
+			x->cap = nc;
+		}
+		la_gz_member *m = &x->pieces[x->n++];
+		m->src_off = pos;
+		m->src_len = (uint32_t)(end - pos);
+		m->dst_cap = piece_slot(end - pos, min_cap);
+		m->dst_off = out;
+		out += ((uint64_t)m->dst_cap + 15) & ~(uint64_t)15;	/* (16-byte aligned slots: the lane kernel's wide copies) */
+		x->last_open = open;
+		pos = search = end;
+		x->consumed = pos;
+		if (open) {
+			x->end_kind = LA_END_EOF;
+			break;
+		}
+	}
+	x->max_out = out;
+	return 0;
 }

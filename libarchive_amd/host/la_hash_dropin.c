@@ -203,7 +203,7 @@ static void gf2_square(uint32_t *sq, const uint32_t *mat)
 {
 	for (int n = 0; n < 32; n++) sq[n] = gf2_times(mat, mat[n]);
 }
-static uint32_t crc_combine(uint32_t crc1, uint32_t crc2, uint64_t len2)
+uint32_t la_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2)
 {
 	uint32_t even[32], odd[32];
 	if (len2 == 0) return crc1;
@@ -291,7 +291,7 @@ static int crc_device(uint32_t *crc, const uint8_t *p, size_t len)
 				break;
 			}
 			for (uint32_t j = 0; j < nj; j++)
-				c = crc_combine(c, host_out[j], host_jobs[j].len);
+				c = la_crc32_combine(c, host_out[j], host_jobs[j].len);
 			p += n; len -= n;
 		}
 		if (rc == 0)
