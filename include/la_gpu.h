@@ -248,7 +248,11 @@ typedef struct la_gz_batch {
 	la_gz_result       *d_results;	/* [n_members] */
 	la_batch_summary   *d_summary;
 	uint32_t            options;
-	uint32_t            reserved;
+	union {
+		uint32_t    hist_len;	/* LA_GZ_OPT_CHAIN: bytes (0 .. 32768) of the same stream's earlier output that the caller
+					 * has placed in d_dst directly in FRONT of d_members[0].dst_off; not read otherwise */
+		uint32_t    reserved;	/* the field's name before it had a meaning: same place, kept for sources that zero it */
+	};
 } la_gz_batch;
 
 #define LA_GZ_OPT_NO_VERIFY   1u	/* do not compare the trailer (reference behaviour) */
@@ -270,6 +274,23 @@ typedef struct la_gz_batch {
 					 * LA_ST_GZ_NEEDS_HISTORY (out_len = the whole symbols in front of the match), or as any member
 					 * does.  Nothing in the claim is trusted: the caller confirms a chain of pieces in stream order
 					 * (la_gz_pieces_build, la_host.h). */
+
+#define LA_GZ_OPT_CHAIN      128u	/* with LA_GZ_OPT_PIECES only (alone, or with LA_GZ_OPT_LANE_KERNEL, LA_GZ_OPT_TWO_PHASE or
+					 * LA_GZ_OPT_EXPAND_INORDER: LA_ERR_ARG, as are hist_len > 32768 and dst_cap + hist_len >= 2^32): the
+					 * members are the pieces of ONE raw-deflate stream in stream order, claimed as for LA_GZ_OPT_PIECES,
+					 * and they are decoded as one stream -- a distance may reach over the piece's first byte into the
+					 * pieces before it and into the hist_len bytes in front of the chain (Z_SYNC_FLUSH, pigz).
+					 *   Output is PACKED: piece i's bytes start at d_members[0].dst_off + the sum of out_len of the
+					 * pieces before it; d_members[i].dst_off is ignored for i > 0, d_members[i].dst_cap stays the
+					 * piece's own bound, and batch.dst_cap counts from d_members[0].dst_off.
+					 *   A distance in front of byte -hist_len of the chain is LA_ST_GZ_DATA (out_len = the whole symbols
+					 * in front of the match); LA_ST_GZ_NEEDS_HISTORY is never reported.  The first piece whose packed end
+					 * would pass batch.dst_cap is LA_ST_GZ_OUT_FULL (out_len 0), the pieces in front of it are intact.
+					 * LA_ST_GZ_PIECE_END, LA_ST_OK, LA_ST_GZ_TRUNCATED and consumed are as in piece mode; crc32 is that
+					 * of the piece's own packed bytes (fold with la_crc32_combine).  Behind the first piece that is
+					 * neither LA_ST_GZ_PIECE_END nor LA_ST_OK results are unspecified.  Nothing outside
+					 * [dst_off[0] - hist_len, dst_off[0] + dst_cap) and the workspace is touched, whatever the claims.
+					 *   Workspace: 4 bytes per byte of batch.dst_cap and about 40 bytes per piece (la_gpu_reserve). */
 
 int la_gpu_gzip_decode(la_gpu_ctx *ctx, const la_gz_batch *batch);
 

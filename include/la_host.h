@@ -152,8 +152,10 @@ int      la_gz_pieces_build(const uint8_t *img, uint64_t len, uint64_t from, int
 void     la_gz_pieces_free(la_gz_pieces *x);
 /* offset of the first 00 00 FF FF at or behind `from`, or len */
 uint64_t la_gz_next_marker(const uint8_t *img, uint64_t len, uint64_t from);
-/* LA_GZIP_FLUSH_POINTS=1: the gzip read filter and its bid policy look for flush points */
+/* LA_GZIP_FLUSH_POINTS=1 or =chain: the gzip read filter and its bid policy look for flush points */
 int      la_gz_flush_points_enabled(void);
+/* LA_GZIP_FLUSH_POINTS=chain: the pieces may depend on each other, the filter decodes them with LA_GZ_OPT_CHAIN */
+int      la_gz_flush_points_chain(void);
 
 /* ---- zstd (host/la_zstd_index.c) ---- */
 typedef struct la_zstd_index_result {

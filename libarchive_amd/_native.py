@@ -38,6 +38,7 @@ LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED, LA_ST_GZ_OUT_FULL, LA_ST_GZ_NO_TRAI
 LA_ST_GZ_PIECE_END, LA_ST_GZ_NEEDS_HISTORY = 18, 19     # LA_GZ_OPT_PIECES only
 (LA_GZ_OPT_NO_VERIFY, LA_GZ_OPT_WAVE_KERNEL, LA_GZ_OPT_LANE_KERNEL, LA_GZ_OPT_TWO_PHASE, LA_GZ_OPT_RAW,
  LA_GZ_OPT_EXPAND_INORDER, LA_GZ_OPT_PIECES) = 1, 2, 4, 8, 16, 32, 64
+LA_GZ_OPT_CHAIN = 128      # with LA_GZ_OPT_PIECES: the pieces depend on each other, output is packed
 
 (LA_END_EOF, LA_END_TRUNCATED, LA_END_MALFORMED, LA_END_MALFORMED_SKIP, LA_END_EMPTY_FRAME,
  LA_END_NEED_MORE, LA_END_GZ_NO_TRAILER, LA_END_GZ_TOO_LARGE) = range(8)
@@ -101,13 +102,18 @@ LA_GZC_FIXED, LA_GZC_DYNAMIC, LA_GZC_STORED = 0, 1, 2
 LA_GZC_FRAME_MEMBERS, LA_GZC_FRAME_STREAM = 0, 1
 
 
+class _GzHistC(C.Union):        # the header's anonymous union: `reserved` is the field's earlier name
+    _fields_ = [("hist_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _GzBatchC(C.Structure):
+    _anonymous_ = ("_hist",)
     _fields_ = [
         ("d_src", C.c_void_p), ("src_bytes", C.c_uint64),
         ("d_members", C.c_void_p), ("n_members", C.c_uint32),
         ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64),
         ("d_results", C.c_void_p), ("d_summary", C.c_void_p),
-        ("options", C.c_uint32), ("reserved", C.c_uint32),
+        ("options", C.c_uint32), ("_hist", _GzHistC),
     ]
 
 

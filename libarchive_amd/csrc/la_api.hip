@@ -493,12 +493,79 @@ static uint64_t gz_ws_carve(uint8_t *base, uint32_t n, bool two_phase, la_inflat
 	return align_up(cv.off, 256);
 }
 
+/* workspace of a chain batch (LA_GZ_OPT_CHAIN).  Everything is sized by what the host knows, n and the batch's
+ * dst_cap: 4 B of source pointer per byte of capacity, then per piece 4 B of measured length, 8 B of packed offset, the
+ * scan's scratch and 24 B of packed member record, and the 256 B control block (no staging copy of the bytes and no
+ * match records: the emit pass writes bytes and pointers where they belong) */
+struct gz_chain_ws {
+	uint32_t *ptr, *len, *ctl;
+	uint64_t *packed_off;
+	void *scan;
+	la_gz_member *packed;
+};
+static uint64_t gz_chain_carve(uint8_t *base, uint32_t n, uint64_t dst_cap, gz_chain_ws *w)
+{
+	la_carve cv = { base, 0 };
+	w->ctl = cv.take<uint32_t>(LA_CHAIN_CTL_WORDS, 256);
+	w->ptr = cv.take<uint32_t>(dst_cap, 256);
+	w->len = cv.take<uint32_t>(n, 256);
+	w->packed_off = cv.take<uint64_t>((uint64_t)n + 1, 256);
+	w->scan = cv.take<uint8_t>(la_scan_scratch_bytes(n), 256);
+	w->packed = cv.take<la_gz_member>(n, 256);
+	return align_up(cv.off, 256);
+}
+
+/* LA_GZ_OPT_CHAIN: measure, scan, emit (la_inflate.hip), pointer jumping and gather (la_inflate_chain.hip), then the
+ * CRC32 launch over the packed ranges and the summary */
+static int gzip_decode_chain(la_gpu_ctx *c, const la_gz_batch *bt)
+{
+	hipStream_t s = c->stream;
+	const uint32_t n = bt->n_members;
+	gz_chain_ws w;
+	const uint64_t need = gz_chain_carve(NULL, n, bt->dst_cap, &w);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	gz_chain_carve((uint8_t *)c->ws, n, bt->dst_cap, &w);
+	const la_inflate_chain C = { w.packed_off, w.ptr, bt->hist_len };
+	prof_begin(c);
+	prof_range(c, "chain_measure", s, [&] {
+		la_launch_inflate_chain(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst, bt->dst_cap, bt->d_results, C, false);
+	});
+	prof_range(c, "chain_scan", s, [&] {
+		la_launch_chain_lengths(s, bt->d_results, n, w.len);
+		la_launch_scan_u32(s, w.len, n, w.packed_off, w.scan);
+	});
+	prof_range(c, "chain_emit", s, [&] {
+		la_launch_inflate_chain(s, bt->d_src, bt->src_bytes, bt->d_members, n, bt->d_dst, bt->dst_cap, bt->d_results, C, true);
+	});
+	prof_range(c, "chain_resolve", s, [&] {
+		la_launch_chain_resolve(s, bt->d_members, bt->d_results, n, bt->d_dst, bt->dst_cap, C, w.packed, w.ctl);
+	});
+	prof_range(c, "gz_crc32", s, [&] {
+		la_launch_gz_verify(s, bt->d_src, bt->src_bytes, w.packed, n, bt->d_dst, bt->d_results, 2);
+	});
+	if (bt->d_summary)
+		la_launch_gz_summary(s, bt->d_results, n, bt->d_summary);
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 {
 	if (!c || !bt)
 		return LA_ERR_ARG;
 	if (bt->n_members && (!bt->d_src || !bt->d_members || !bt->d_dst || !bt->d_results))
 		return LA_ERR_ARG;
+	if (bt->options & LA_GZ_OPT_CHAIN) {
+		/* pieces only, the wave kernel only; coordinates of history + range are 32-bit words */
+		if (!(bt->options & LA_GZ_OPT_PIECES) ||
+		    (bt->options & (LA_GZ_OPT_LANE_KERNEL | LA_GZ_OPT_TWO_PHASE | LA_GZ_OPT_EXPAND_INORDER)) ||
+		    bt->hist_len > 32768u || bt->dst_cap + bt->hist_len > 0xFFFFFFFFull)
+			return LA_ERR_ARG;
+		return gzip_decode_chain(c, bt);
+	}
 	hipStream_t s = c->stream;
 	/* many members: one LANE per member (la_inflate_lanes.hip); few: one wave per member */
 	const bool lanes = (bt->n_members >= LA_GZ_LANES_MIN || (bt->options & (LA_GZ_OPT_LANE_KERNEL | LA_GZ_OPT_TWO_PHASE))) &&

@@ -41,6 +41,13 @@
  *            leaves padding bits unread: no piece end, the header read runs out of input as it always did.
  *   history  a distance that reaches in front of the piece's first output byte is LA_ST_GZ_NEEDS_HISTORY, not
  *            LA_ST_GZ_DATA (dfl_far_back): the bytes it points at exist, in the piece before.
+ *
+ * A chain (LA_GZ_OPT_CHAIN on top of the pieces, a second template parameter of the wave kernel only).  The pieces are
+ * decoded as ONE stream: a distance may reach over the piece's first byte into the packed bytes of the pieces before
+ * it and then into the hist_len bytes the caller put in front of the chain.  The kernel copies no match (it writes
+ * one source pointer per byte, la_inflate_chain.hip follows them), so the only rule left is zlib's own:
+ *   too far  a distance above (bytes of this piece so far) + (packed bytes in front of the piece) + hist_len is
+ *            LA_ST_GZ_DATA (dfl_chain_too_far), "invalid distance too far back"; LA_ST_GZ_NEEDS_HISTORY does not occur.
  */
 #ifndef LA_DEFLATE_DEV_H
 #define LA_DEFLATE_DEV_H
@@ -96,6 +103,12 @@ __device__ __forceinline__ bool dfl_piece_end(int64_t unread_bits)
 /* the verdict on a match distance above the bytes produced so far */
 template <bool PIECES>
 __device__ __forceinline__ uint32_t dfl_far_back() { return PIECES ? LA_ST_GZ_NEEDS_HISTORY : LA_ST_GZ_DATA; }
+
+/* chain mode: in_front = packed bytes of the earlier pieces + hist_len (below 2^32 with op: la_api.hip checks the batch) */
+__device__ __forceinline__ bool dfl_chain_too_far(uint32_t dist, uint32_t op, uint32_t in_front)
+{
+	return (uint64_t)dist > (uint64_t)op + in_front;
+}
 
 /* stored block, behind the three header bits: to the byte boundary, LEN against ~NLEN */
 template <class R>

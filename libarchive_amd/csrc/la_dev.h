@@ -561,6 +561,21 @@ uint64_t la_gzip_compress_ws_bytes(uint64_t src_bytes, uint32_t chunk, uint32_t 
 /* la_inflate.hip */
 void la_launch_inflate(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, bool pieces);
+/* LA_GZ_OPT_CHAIN: what the emit instance of the wave kernel is given beside the batch (la_inflate.hip) */
+struct la_inflate_chain {
+	const uint64_t *packed_off;	/* [n + 1] exclusive scan of the measured out_len */
+	uint32_t *ptr;			/* one source pointer per packed output byte */
+	uint32_t hist_len;
+};
+void la_launch_inflate_chain(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_gz_member *d_members,
+    uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, const la_inflate_chain &C, bool emit);
+/* la_inflate_chain.hip: between the two instances (measured lengths as the scan's input), and behind them (packed
+ * member table for the CRC32 launch, the pointer-jumping passes, the gather) */
+#define LA_CHAIN_JUMP_PASSES 32u
+#define LA_CHAIN_CTL_WORDS 64u	/* [0, 32) one "changed" flag per jump pass, [32] bytes of the packed range */
+void la_launch_chain_lengths(hipStream_t s, const la_gz_result *d_results, uint32_t n, uint32_t *d_len);
+void la_launch_chain_resolve(hipStream_t s, const la_gz_member *d_members, const la_gz_result *d_results, uint32_t n,
+    uint8_t *d_dst, uint64_t dst_cap, const la_inflate_chain &C, la_gz_member *d_packed, uint32_t *d_ctl);
 uint64_t la_inflate_lanes_scratch_bytes(uint32_t n);
 /* outputs of the entropy-only launch (la_launch_inflate_symbols): everything
  * lz4_expand_fast_kernel needs to build the members in its LDS window */

@@ -232,9 +232,48 @@ __device__ __forceinline__ void out_flush(out_state &O, int lane)
 	}
 }
 
-/* returns LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED or LA_ST_GZ_OUT_FULL (PIECES: or LA_ST_GZ_NEEDS_HISTORY) */
-template <bool PIECES>
-__device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, const inf_tables *T, int lane DIAG_ARG)
+/*
+ * Chain mode (LA_GZ_OPT_CHAIN, the rule is in la_deflate_dev.h): a second template parameter, so the other instances
+ * do not hold a byte of it.  The pieces are decoded TWICE by instances of this kernel, a scan between them:
+ *   LA_CHAIN_MEASURE  the entropy decode alone: nothing is stored but the piece's result (out_len bounded by the
+ *                     piece's dst_cap, consumed, status); no distance is judged, the piece's place is not known yet;
+ *   LA_CHAIN_EMIT     with the packed place of the piece (exclusive scan of the measured out_len): literals and stored
+ *                     bytes go straight to their packed place, and for EVERY byte one source pointer goes to the
+ *                     pointer table -- itself for a literal, the byte the match names for a match byte.  No match is
+ *                     copied and nothing is read back from the output: la_inflate_chain.hip follows the pointers.
+ * Coordinates: byte k of the chain (history included) is hist_len + its packed position; X.in_front is that of the
+ * piece's first byte.  A wave writes only inside [packed offset, + measured out_len) of the output and of the pointer
+ * table: the emit pass takes the measured length as its capacity, so a decode that came out longer the second time
+ * (it cannot: same bytes, same code) would end in LA_ST_GZ_OUT_FULL, never in a store outside.
+ */
+enum { LA_CHAIN_OFF = 0, LA_CHAIN_MEASURE = 1, LA_CHAIN_EMIT = 2 };
+
+struct chain_out {
+	uint32_t *ptr;		/* pointer table entry of the piece's first byte */
+	uint32_t in_front;	/* hist_len + packed bytes in front of the piece */
+};
+
+template <int CHAIN>
+__device__ __forceinline__ void flush_lits(out_state &O, const chain_out &X, int lane)
+{
+	if constexpr (CHAIN == LA_CHAIN_OFF)
+		out_flush(O, lane);
+	else if constexpr (CHAIN == LA_CHAIN_EMIT) {
+		if (O.npend) {
+			if ((uint32_t)lane < O.npend) {
+				O.d[O.op + lane] = (uint8_t)O.litbuf;
+				X.ptr[O.op + lane] = X.in_front + O.op + lane;
+			}
+			O.op += O.npend;
+			O.npend = 0;
+		}
+	}
+	/* (LA_CHAIN_MEASURE counts its literals in O.op at once: nothing is ever pending) */
+}
+
+/* returns LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED or LA_ST_GZ_OUT_FULL (PIECES without CHAIN: or LA_ST_GZ_NEEDS_HISTORY) */
+template <bool PIECES, int CHAIN>
+__device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, const chain_out &X, const inf_tables *T, int lane DIAG_ARG)
 {
 	for (;;) {
 		DIAG_T0();
@@ -244,11 +283,15 @@ __device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, co
 		if (sym < 0) return LA_ST_GZ_DATA;
 		if (sym < 256) {
 			if (O.op + O.npend >= O.cap) return LA_ST_GZ_OUT_FULL;
+			if constexpr (CHAIN == LA_CHAIN_MEASURE) {
+				O.op++;
+				continue;
+			}
 			if ((uint32_t)lane == O.npend)
 				O.litbuf = (uint32_t)sym;
 			O.npend++;
 			if (O.npend == LA_WAVE)
-				out_flush(O, lane);
+				flush_lits<CHAIN>(O, X, lane);
 			DIAG_ACC(1);
 			continue;
 		}
@@ -265,9 +308,29 @@ __device__ __forceinline__ uint32_t inflate_codes(bitreader &B, out_state &O, co
 		if (!br_need(B, (int)xb, lane)) return LA_ST_GZ_TRUNCATED;
 		uint32_t dist = bs + br_take(B, (int)xb);
 		DIAG_ACC(2); DIAG_CNT(7);
-		out_flush(O, lane);
-		if (dist > O.op) return dfl_far_back<PIECES>();
+		flush_lits<CHAIN>(O, X, lane);
+		if constexpr (CHAIN == LA_CHAIN_OFF) {
+			if (dist > O.op) return dfl_far_back<PIECES>();
+		} else if constexpr (CHAIN == LA_CHAIN_EMIT) {
+			if (dfl_chain_too_far(dist, O.op, X.in_front)) return LA_ST_GZ_DATA;
+		}
 		if (O.op + length > O.cap) return LA_ST_GZ_OUT_FULL;
+		if constexpr (CHAIN != LA_CHAIN_OFF) {
+			if constexpr (CHAIN == LA_CHAIN_EMIT) {
+				/* the source of byte j: where the wave-wide copy below would read it (the modulo form names a
+				 * byte in front of the match at once, not the byte `dist` back that is itself a copy) */
+				const uint32_t from = X.in_front + O.op - dist;
+				if (dist >= length) {
+					for (uint32_t j = (uint32_t)lane; j < length; j += LA_WAVE)
+						X.ptr[O.op + j] = from + j;
+				} else {
+					for (uint32_t j = (uint32_t)lane; j < length; j += LA_WAVE)
+						X.ptr[O.op + j] = from + j % dist;
+				}
+			}
+			O.op += length;
+			continue;
+		}
 		/* wave-wide copy; the modulo form only reads bytes below op */
 		uint32_t span = length < dist ? length : dist;
 		if (O.op - dist + span > O.visible) {
@@ -324,11 +387,12 @@ struct wave_reader {
 	}
 };
 
-/* PIECES: the members are pieces of one raw-deflate stream (LA_GZ_OPT_PIECES; the rules are in la_deflate_dev.h) */
-template <bool PIECES>
+/* PIECES: the members are pieces of one raw-deflate stream (LA_GZ_OPT_PIECES; the rules are in la_deflate_dev.h);
+ * CHAIN: see above (C is read by the chain instances only) */
+template <bool PIECES, int CHAIN>
 __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const uint8_t *__restrict__ src,
     uint64_t src_bytes, const la_gz_member *__restrict__ members, uint32_t n, uint8_t *dst,
-    uint64_t dst_cap, la_gz_result *__restrict__ results)
+    uint64_t dst_cap, la_gz_result *__restrict__ results, la_inflate_chain C)
 {
 	__shared__ inf_tables tabs[INF_WAVES_PER_WG];
 	const int lane = threadIdx.x & 63;
@@ -352,11 +416,33 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 	B.W.limit = src + src_bytes;
 	win_reset(B.W, B.ip, lane);
 	out_state O;
-	O.d = dst + m.dst_off;
 	O.op = 0; O.visible = 0; O.npend = 0; O.litbuf = 0;
-	O.cap = m.dst_cap;
-	if (m.dst_off + m.dst_cap > dst_cap)
-		O.cap = m.dst_off < dst_cap ? (uint32_t)(dst_cap - m.dst_off) : 0;
+	chain_out X = { nullptr, 0 };
+	if constexpr (CHAIN == LA_CHAIN_OFF) {
+		O.d = dst + m.dst_off;
+		O.cap = m.dst_cap;
+		if (m.dst_off + m.dst_cap > dst_cap)
+			O.cap = m.dst_off < dst_cap ? (uint32_t)(dst_cap - m.dst_off) : 0;
+	} else if constexpr (CHAIN == LA_CHAIN_MEASURE) {
+		O.d = nullptr;
+		O.cap = m.dst_cap;
+	} else {
+		/* the packed place: [first piece's dst_off + scan, + measured length), inside dst_cap bytes from the first
+		 * piece's dst_off or not written at all */
+		const uint32_t measured = results[mi].out_len;
+		const uint64_t at = C.packed_off[mi];
+		if (at + measured > dst_cap) {
+			if (lane == 0) {
+				results[mi].status = LA_ST_GZ_OUT_FULL;
+				results[mi].out_len = 0;
+			}
+			return;
+		}
+		O.d = dst + members[0].dst_off + at;
+		O.cap = measured;
+		X.ptr = C.ptr + at;
+		X.in_front = C.hist_len + (uint32_t)at;
+	}
 
 	wave_reader R = { B, T, lane, 0 };
 	for (;;) {
@@ -367,15 +453,21 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 			uint32_t len;
 			status = dfl_stored_header(R, len);
 			if (status != LA_ST_OK) break;
-			out_flush(O, lane);
+			flush_lits<CHAIN>(O, X, lane);
 			/* whole bytes still in the bit buffer go back to the byte stream */
 			B.ip -= B.bits >> 3;
 			B.bits = 0; B.hold = 0;
 			uint32_t avail = (uint32_t)(B.iend - B.ip);
 			uint32_t take = len < avail ? len : avail;
 			if (O.op + take > O.cap) { status = LA_ST_GZ_OUT_FULL; break; }
-			for (uint32_t j = (uint32_t)lane; j < take; j += LA_WAVE)
-				O.d[O.op + j] = B.ip[j];
+			if constexpr (CHAIN != LA_CHAIN_MEASURE) {
+				for (uint32_t j = (uint32_t)lane; j < take; j += LA_WAVE)
+					O.d[O.op + j] = B.ip[j];
+			}
+			if constexpr (CHAIN == LA_CHAIN_EMIT) {
+				for (uint32_t j = (uint32_t)lane; j < take; j += LA_WAVE)
+					X.ptr[O.op + j] = X.in_front + O.op + j;
+			}
 			O.op += take;
 			B.ip += take;
 			if (take < len) { status = LA_ST_GZ_TRUNCATED; break; }
@@ -401,7 +493,7 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 			int dm = __builtin_amdgcn_readfirstlane((int)T->d_maxlen);
 			status = dfl_code_verdict(e, (uint32_t)dm, DFL_CODE_DIST);
 			if (status != LA_ST_OK) break;
-			status = inflate_codes<PIECES>(B, O, T, lane DIAG_PASS);
+			status = inflate_codes<PIECES, CHAIN>(B, O, X, T, lane DIAG_PASS);
 			if (status != LA_ST_OK) break;
 		} else {
 			status = LA_ST_GZ_DATA;
@@ -417,8 +509,17 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 		}
 	}
 	/* what zlib would have emitted before noticing: whole symbols, stored data bytewise */
-	if (status != LA_ST_GZ_OUT_FULL)
-		out_flush(O, lane);
+	if constexpr (CHAIN == LA_CHAIN_OFF) {
+		if (status != LA_ST_GZ_OUT_FULL)
+			out_flush(O, lane);
+	} else if constexpr (CHAIN == LA_CHAIN_EMIT) {
+		/* (a literal is only taken while op + npend < cap: the pending ones always fit) */
+		flush_lits<CHAIN>(O, X, lane);
+		/* a piece that ends here in front of its measured length (a distance too far back): the rest of its
+		 * range names itself, so that every pointer of the packed range is one the passes may follow */
+		for (uint32_t j = O.op + (uint32_t)lane; j < O.cap; j += LA_WAVE)
+			X.ptr[j] = X.in_front + j;
+	}
 #ifdef LA_DIAG
 	if (lane == 0 && la_inf_diag) {
 		for (int k = 0; k < 8; k++)
@@ -441,8 +542,18 @@ void la_launch_inflate(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_gz_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, bool pieces)
 {
 	if (n == 0) return;
-	const auto kernel = pieces ? inflate_kernel<true> : inflate_kernel<false>;
+	const auto kernel = pieces ? inflate_kernel<true, LA_CHAIN_OFF> : inflate_kernel<false, LA_CHAIN_OFF>;
 	hipLaunchKernelGGL(kernel, dim3((n + INF_WAVES_PER_WG - 1) / INF_WAVES_PER_WG),
-	    dim3(64 * INF_WAVES_PER_WG), 0, s, d_src, src_bytes, d_members, n, d_dst, dst_cap, d_results);
+	    dim3(64 * INF_WAVES_PER_WG), 0, s, d_src, src_bytes, d_members, n, d_dst, dst_cap, d_results, la_inflate_chain{});
+}
+
+/* the two chain instances: emit = false measures (C is not read), emit = true writes bytes and pointers */
+void la_launch_inflate_chain(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_gz_member *d_members,
+    uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, const la_inflate_chain &C, bool emit)
+{
+	if (n == 0) return;
+	const auto kernel = emit ? inflate_kernel<true, LA_CHAIN_EMIT> : inflate_kernel<true, LA_CHAIN_MEASURE>;
+	hipLaunchKernelGGL(kernel, dim3((n + INF_WAVES_PER_WG - 1) / INF_WAVES_PER_WG),
+	    dim3(64 * INF_WAVES_PER_WG), 0, s, d_src, src_bytes, d_members, n, d_dst, dst_cap, d_results, C);
 }
 

@@ -61,7 +61,15 @@ const unsigned char *la_bid_peek(struct archive_read_filter *filter, size_t want
 int la_gz_flush_points_enabled(void)
 {
 	const char *v = getenv("LA_GZIP_FLUSH_POINTS");
-	return v != NULL && v[0] == '1';
+	return v != NULL && (v[0] == '1' || strcmp(v, "chain") == 0);
+}
+
+/* LA_GZIP_FLUSH_POINTS=chain: piece mode as for =1 (the same bid evidence), and the pieces are decoded as one stream
+ * (LA_GZ_OPT_CHAIN): blocks behind a flush point may reach back over it (Z_SYNC_FLUSH, pigz without -i) */
+int la_gz_flush_points_chain(void)
+{
+	const char *v = getenv("LA_GZIP_FLUSH_POINTS");
+	return v != NULL && strcmp(v, "chain") == 0;
 }
 
 /* LA_GZIP_FLUSH_POINTS=1: ONE member whose body is a chain of flush points (00 00 FF FF, la_gz_pieces_build) decodes a

@@ -39,6 +39,7 @@ static double gz_now(void)
 }
 
 #define OUT_BLOCK 65536u	/* gzip.c:314 */
+#define LA_GZ_HIST 32768u	/* the deflate window: as far as a distance reaches */
 
 struct gzip_private {
 	la_window w;
@@ -77,7 +78,7 @@ struct gzip_private {
 	size_t o_res;
 	la_verdict verdict;	/* what the next read() reports once the bytes in front of it are out */
 	int eof;
-	/* Piece mode (LA_GZIP_FLUSH_POINTS=1): ONE member decoded from its flush points, a piece per lane or wave
+	/* Piece mode (LA_GZIP_FLUSH_POINTS=1 or =chain): ONE member decoded from its flush points, a piece per lane or wave
 	 * (la_gz_pieces_build, LA_GZ_OPT_PIECES).  The member may span any number of windows; what is carried from one
 	 * to the next is {in the member, CRC32 so far, bytes so far}. */
 	int fp_on;
@@ -87,6 +88,16 @@ struct gzip_private {
 	size_t pm_from;		/* where the pieces of the window in flight start: behind the header in a member's first window, else 0 */
 	la_gz_pieces pcs;
 	int inflight_pieces;	/* the window in flight is st->pcs, not st->idx */
+	/* LA_GZIP_FLUSH_POINTS=chain: the pieces are decoded as one stream (LA_GZ_OPT_CHAIN), so a member in piece mode carries
+	 * one thing more from window to window: the last min(32768, bytes so far) bytes of its output, which go in front of
+	 * the next window's packed range on the device.  They are kept HERE, on the host, and uploaded with each window, not
+	 * copied from the previous window's output on the device: the bytes pass through the host slab anyway; a window that
+	 * gave fewer than 32 KiB needs bytes of the windows before it, which on the device would be a copy onto itself; the
+	 * output buffer may be reallocated when a window needs a larger one; and after a retry (merged pieces, larger slots)
+	 * only the host knows which of the device's bytes were confirmed.  32 KiB per window of megabytes is not measurable. */
+	int fp_chain;
+	la_buf hist;		/* pinned, LA_GZ_HIST bytes */
+	size_t hist_len;
 	int pm_retry;		/* the last walk asked for the same bytes again on other terms (merged pieces, larger slots, the ordinary way) */
 };
 
@@ -189,6 +200,7 @@ static int gzip_bidder_init(struct archive_read_filter *self)
 			st->span_limit = strtoull(v, NULL, 10);
 	}
 	st->fp_on = la_gz_flush_points_enabled();
+	st->fp_chain = la_gz_flush_points_chain();
 	st->trace = getenv("LA_GPU_TRACE") != NULL && atoi(getenv("LA_GPU_TRACE")) != 0;
 	st->no_ahead = getenv("LA_GZ_NO_COPY_AHEAD") != NULL && atoi(getenv("LA_GZ_NO_COPY_AHEAD")) != 0;
 	if (la_window_open(self, &st->w, "gzip") != ARCHIVE_OK) {
@@ -216,11 +228,12 @@ static int gzip_read_header(struct archive_read_filter *self, struct archive_ent
  * The end of a window's stream-order walk, for members and pieces alike: bring the bytes of units [0, take) behind
  * the carry and decide how much of [carry | new bytes] may go out now.  total: stream offset behind the units taken
  * whole; last_out: bytes of a failing last unit that still count as produced; cutoff: deliver only up to here
- * (UINT64_MAX: no error follows).
+ * (UINT64_MAX: no error follows).  d_out: where unit 0's bytes are on the device; packed: the units' bytes lie back to
+ * back from there whatever their slots say (LA_GZ_OPT_CHAIN), one copy brings them all.
  */
 static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, const la_gz_member *mem,
     const la_gz_result *res, uint32_t take, int contiguous, uint32_t last_out, uint64_t total, uint64_t cutoff,
-    double b0, double b1)
+    double b0, double b1, const uint8_t *d_out, int packed)
 {
 	la_gpu_ctx *gpu = st->w.gpu;
 	uint64_t new_bytes = (total - st->total_out) + last_out;
@@ -237,14 +250,14 @@ static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, co
 	uint8_t *dstp = st->slab.p + st->carry_len;
 	const double b2 = st->trace ? gz_now() : 0;
 	if (take && !ahead) {
-		if (contiguous && last_out == 0) {
-			if (la_gpu_memcpy_d2h(gpu, dstp, st->d_dst.p, (size_t)new_bytes) != LA_OK)
+		if (packed || (contiguous && last_out == 0)) {
+			if (new_bytes && la_gpu_memcpy_d2h(gpu, dstp, d_out, (size_t)new_bytes) != LA_OK)
 				return la_window_fail(self, &st->w, "device to host copy");
 		} else {
 			size_t w = 0;
 			for (uint32_t i = 0; i < take; i++) {
 				size_t len = res[i].out_len;
-				if (len && la_gpu_memcpy_d2h(gpu, dstp + w, st->d_dst.p + mem[i].dst_off, len) != LA_OK)
+				if (len && la_gpu_memcpy_d2h(gpu, dstp + w, d_out + mem[i].dst_off, len) != LA_OK)
 					return la_window_fail(self, &st->w, "device to host copy");
 				w += len;
 			}
@@ -255,6 +268,21 @@ static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, co
 	if (st->trace)
 		fprintf(stderr, "la_gzip:   h2d+decode %.1f ms, walk+grow %.1f ms, d2h %.1f ms (%llu bytes, contiguous %d, copied ahead %d)\n",
 		    b1 - b0, b2 - b1, gz_now() - b2, (unsigned long long)new_bytes, contiguous, ahead);
+	if (packed && st->pm.in_member) {
+		/* the member goes on: the last LA_GZ_HIST bytes of [history | confirmed bytes of this window] are the next
+		 * window's history */
+		const size_t nb = (size_t)(total - st->total_out);
+		if (nb >= LA_GZ_HIST) {
+			memcpy(st->hist.p, dstp + nb - LA_GZ_HIST, LA_GZ_HIST);
+			st->hist_len = LA_GZ_HIST;
+		} else {
+			const size_t keep = st->hist_len < LA_GZ_HIST - nb ? st->hist_len : LA_GZ_HIST - nb;
+			memmove(st->hist.p, st->hist.p + st->hist_len - keep, keep);
+			memcpy(st->hist.p + keep, dstp, nb);
+			st->hist_len = keep + nb;
+		}
+	} else if (packed)
+		st->hist_len = 0;
 	st->total_out = total + last_out;
 	st->carry_len += (size_t)new_bytes;
 
@@ -465,7 +493,7 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 		}
 	}
 
-	return gz_slab(self, st, x->members, res, take, contiguous, last_out, total, cutoff, b0, b1);
+	return gz_slab(self, st, x->members, res, take, contiguous, last_out, total, cutoff, b0, b1, st->d_dst.p, 0);
 }
 
 /*
@@ -483,19 +511,34 @@ static int gzip_run_pieces(struct archive_read_filter *self, struct gzip_private
 	const size_t o_res = o; o += ALIGN256((size_t)n * sizeof(la_gz_result));
 	la_gpu_ctx *gpu = st->w.gpu;
 	const double b0 = st->trace ? gz_now() : 0;
+	/* chain: room for the history in front of the packed range (piece 0's slot starts at offset 0 of its table) */
+	const size_t lead = st->fp_chain ? LA_GZ_HIST : 0;
 	if (phase == 0) {
-		if (la_buf_dev(gpu, &st->d_dst, (size_t)x->max_out + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o) < 0)
+		if (la_buf_dev(gpu, &st->d_dst, lead + (size_t)x->max_out + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o) < 0)
 			return la_window_fail(self, &st->w, "device allocation");
 		uint8_t *T = st->d_tabs.p;
 		if (la_gpu_memcpy_h2d(gpu, T + o_mem, x->pieces, (size_t)n * sizeof(la_gz_member)) != LA_OK)
 			return la_window_fail(self, &st->w, "host to device copy");
+		if (st->fp_chain) {
+			if (la_buf_pinned(gpu, &st->hist, LA_GZ_HIST, st->hist_len) < 0)
+				return la_window_fail(self, &st->w, "pinned history allocation");
+			if (!st->pm.in_member)
+				st->hist_len = 0;
+			if (st->hist_len &&
+			    la_gpu_memcpy_h2d(gpu, st->d_dst.p + lead - st->hist_len, st->hist.p, st->hist_len) != LA_OK)
+				return la_window_fail(self, &st->w, "host to device copy");
+		}
 		la_gz_batch bt;
 		memset(&bt, 0, sizeof(bt));
 		bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
 		bt.d_members = (const la_gz_member *)(T + o_mem); bt.n_members = n;
-		bt.d_dst = st->d_dst.p; bt.dst_cap = x->max_out;
+		bt.d_dst = st->d_dst.p + lead; bt.dst_cap = x->max_out;
 		bt.d_results = (la_gz_result *)(T + o_res);
 		bt.options = LA_GZ_OPT_PIECES;
+		if (st->fp_chain) {
+			bt.options |= LA_GZ_OPT_CHAIN;
+			bt.hist_len = (uint32_t)st->hist_len;
+		}
 		if (la_gpu_gzip_decode(gpu, &bt) != LA_OK)
 			return la_window_fail(self, &st->w, "la_gpu_gzip_decode");
 		return 0;
@@ -655,7 +698,7 @@ static int gzip_run_pieces(struct archive_read_filter *self, struct gzip_private
 		cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
 	}
 	st->ahead_ok = 0;
-	return gz_slab(self, st, x->pieces, res, take, contiguous, last_out, total, cutoff, b0, b1);
+	return gz_slab(self, st, x->pieces, res, take, contiguous, last_out, total, cutoff, b0, b1, st->d_dst.p + lead, st->fp_chain);
 }
 
 /*
@@ -883,6 +926,7 @@ static int gzip_filter_close(struct archive_read_filter *self)
 	la_buf_release(gpu, &st->d_dst);
 	la_buf_release(gpu, &st->d_tabs);
 	la_buf_release(gpu, &st->h_res);
+	la_buf_release(gpu, &st->hist);
 	la_gpu_close(gpu);
 	free(st->name);
 	free(st);
