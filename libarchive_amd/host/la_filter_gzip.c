@@ -41,6 +41,13 @@ static double gz_now(void)
 #define OUT_BLOCK 65536u	/* gzip.c:314 */
 #define LA_GZ_HIST 32768u	/* the deflate window: as far as a distance reaches */
 
+/* What a walk asks of the next window's first unit, because a decode refuted the table: pass over `skip` candidate
+ * boundaries (1f 8b 08 guesses, 00 00 FF FF markers) and give it an output slot of `cap` bytes at least. */
+struct gz_hint { uint32_t skip, cap; };
+
+/* which table the window in flight was queued from */
+enum gz_inflight { GZ_NONE = 0, GZ_MEMBERS, GZ_PIECES };
+
 struct gzip_private {
 	la_window w;
 	la_buf stage;		/* pinned */
@@ -61,7 +68,7 @@ struct gzip_private {
 	size_t last_ret;	/* bytes handed out by the previous read() */
 	la_buf h_res;
 	uint64_t total_out;	/* bytes decoded so far (delivered + carry) */
-	uint32_t hint_skip, hint_cap;
+	struct gz_hint hint;	/* for the first member of the next window, and for that one only */
 	int strict;
 	uint32_t slot_limit;	/* an output slot cannot pass 2 GiB (32-bit positions on the device); LA_GZ_TEST_SLOT_LIMIT lowers it for tests */
 	uint64_t span_limit;	/* a member's compressed span cannot pass 4 GiB - 1 (32-bit table); LA_GZ_TEST_SPAN_LIMIT lowers it */
@@ -72,10 +79,10 @@ struct gzip_private {
 	char *name;
 	/* the window whose device work is queued but not yet looked at (decode-ahead: it was gathered,
 	 * uploaded, indexed and launched BEFORE the previous read() returned, so the device works on it
-	 * while the caller consumes the slab it was given) */
+	 * while the caller consumes the slab it was given): st->idx or st->pcs, as `inflight` says */
 	la_gz_index idx;
-	int inflight;
-	size_t o_res;
+	enum gz_inflight inflight;
+	size_t o_res;		/* where its results are in d_tabs */
 	la_verdict verdict;	/* what the next read() reports once the bytes in front of it are out */
 	int eof;
 	/* Piece mode (LA_GZIP_FLUSH_POINTS=1 or =chain): ONE member decoded from its flush points, a piece per lane or wave
@@ -84,10 +91,9 @@ struct gzip_private {
 	int fp_on;
 	struct { int in_member; uint32_t crc; uint64_t bytes; } pm;
 	int pm_declined;	/* the member at the head of the window is decoded the ordinary way (its pieces depend on each other) */
-	uint32_t pm_skip, pm_cap;	/* as hint_skip / hint_cap, for the first piece of the next window */
+	struct gz_hint pm_hint;	/* skip: for the first piece of the next window; cap: from that piece on, for the rest of the member */
 	size_t pm_from;		/* where the pieces of the window in flight start: behind the header in a member's first window, else 0 */
 	la_gz_pieces pcs;
-	int inflight_pieces;	/* the window in flight is st->pcs, not st->idx */
 	/* LA_GZIP_FLUSH_POINTS=chain: the pieces are decoded as one stream (LA_GZ_OPT_CHAIN), so a member in piece mode carries
 	 * one thing more from window to window: the last min(32768, bytes so far) bytes of its output, which go in front of
 	 * the next window's packed range on the device.  They are kept HERE, on the host, and uploaded with each window, not
@@ -98,7 +104,6 @@ struct gzip_private {
 	int fp_chain;
 	la_buf hist;		/* pinned, LA_GZ_HIST bytes */
 	size_t hist_len;
-	int pm_retry;		/* the last walk asked for the same bytes again on other terms (merged pieces, larger slots, the ordinary way) */
 };
 
 static int gzip_bidder_bid(struct archive_read_filter_bidder *, struct archive_read_filter *);
@@ -224,20 +229,180 @@ static int gzip_read_header(struct archive_read_filter *self, struct archive_ent
 
 #define ALIGN256(x) (((x) + 255) & ~(size_t)255)
 
+/* The units in flight, members of st->idx or pieces of st->pcs: what the launch, the result fetch and the slab need of
+ * either table. */
+struct gz_units {
+	enum gz_inflight kind;
+	const la_gz_member *tab;
+	uint32_t n;
+	uint64_t consumed;	/* bytes of the window the table covers */
+	uint64_t max_out;	/* sum of the slots */
+	int end_kind;		/* LA_END_*: what follows the last unit */
+	size_t lead;		/* room in front of unit 0's output on the device: chain keeps the history there */
+	int packed;		/* the units' bytes lie back to back from unit 0's, whatever their slots say (LA_GZ_OPT_CHAIN) */
+};
+
+static struct gz_units gz_units_of(const struct gzip_private *st, enum gz_inflight kind)
+{
+	const la_gz_pieces *p = &st->pcs;
+	const la_gz_index *x = &st->idx;
+	if (kind == GZ_PIECES)
+		return (struct gz_units){ kind, p->pieces, p->n, p->consumed, p->max_out, p->end_kind,
+		    st->fp_chain ? LA_GZ_HIST : 0, st->fp_chain };
+	return (struct gz_units){ kind, x->members, x->n, x->consumed, x->max_out, x->end_kind, 0, 0 };
+}
+
+/* the window's table is done with (the one that is not in use is empty: freeing it changes nothing) */
+static void gz_free_tables(struct gzip_private *st)
+{
+	la_gz_pieces_free(&st->pcs);
+	la_gz_index_free(&st->idx);
+}
+
+/* One window's stream-order walk: what gzip_walk_members and gzip_walk_pieces work out and gz_slab acts on. */
+struct gz_walk {
+	uint64_t total;		/* stream offset behind the units taken whole */
+	uint64_t cutoff;	/* deliver only up to here (UINT64_MAX: no error follows) */
+	uint32_t take;		/* units whose bytes join the slab */
+	uint32_t last_out;	/* bytes of a failing last unit that still count as produced */
+	int contiguous;		/* every unit taken filled its slot: their bytes are one range on the device */
+	size_t used;		/* compressed bytes of the window that are done with (all the table covers, unless a unit comes again) */
+	int again;		/* the walk asked for the same bytes again on other terms (merged units, larger slots, the ordinary way) */
+	double b0, b1;		/* trace stamps: in front of and behind the wait for the results */
+};
+
+/* ---- the delivery rules of the reference, each stated once ---- */
+
+/* gzip.c:314, :446: on an error the reference has delivered whole 64 KiB blocks only */
+static uint64_t gz_floor(uint64_t off)
+{
+	return (off / OUT_BLOCK) * OUT_BLOCK;
+}
+
+/* an error stands in front of the next unit: whole blocks of what is confirmed, then the message */
+static void gz_refuse(struct gzip_private *st, struct gz_walk *w, const char *msg)
+{
+	la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", msg);
+	w->cutoff = gz_floor(w->total);
+}
+
+static void gz_too_large(struct gzip_private *st, struct gz_walk *w)
+{
+	gz_refuse(st, w, la_end_message(LA_END_GZ_TOO_LARGE, 1));
+}
+
+/* a trailer that does not match under LA_GZIP_STRICT=1 (new behaviour: the reference never looks, gzip.c:423), or an
+ * answer the walk does not know: EVERYTHING in front of the unit that shows it, then the message */
+static void gz_fail_in_front(struct gzip_private *st, struct gz_walk *w, const char *msg)
+{
+	la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", msg);
+	w->cutoff = w->total;
+}
+
+/* inflate() failed after out_len bytes of the last unit taken: the block that holds the last of them is not out yet.
+ * GZ_DATA_ERROR (gzip.c:494-499), or GZ_NO_TRAILER -- the body is complete, the trailer is short: ARCHIVE_FATAL
+ * without a message (gzip.c:419-421). */
+#define GZ_DATA_ERROR "gzip decompression failed"
+#define GZ_NO_TRAILER NULL
+static void gz_failed_after(struct gzip_private *st, struct gz_walk *w, uint32_t take, uint32_t out_len, const char *msg)
+{
+	la_verdict_set(&st->verdict, ARCHIVE_FATAL, msg ? "%s" : NULL, msg);
+	w->cutoff = out_len == 0 ? gz_floor(w->total) : gz_floor(w->total + out_len - 1);
+	w->last_out = out_len;
+	w->take = take;
+}
+
+/* the input ended after out_len bytes (gzip.c:464-469): the reference has flushed the block they complete */
+static void gz_truncated(struct gzip_private *st, struct gz_walk *w, uint32_t take, uint32_t out_len)
+{
+	la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
+	w->cutoff = gz_floor(w->total + out_len);
+	w->last_out = out_len;
+	w->take = take;
+}
+
 /*
- * The end of a window's stream-order walk, for members and pieces alike: bring the bytes of units [0, take) behind
- * the carry and decide how much of [carry | new bytes] may go out now.  total: stream offset behind the units taken
- * whole; last_out: bytes of a failing last unit that still count as produced; cutoff: deliver only up to here
- * (UINT64_MAX: no error follows).  d_out: where unit 0's bytes are on the device; packed: the units' bytes lie back to
- * back from there whatever their slots say (LA_GZ_OPT_CHAIN), one copy brings them all.
+ * LA_ST_GZ_OUT_FULL: unit i comes again with twice the slot, up to st->slot_limit; a slot that cannot grow any further
+ * (32-bit positions on the device) is said by name instead of retrying for ever or delivering a wrapped slot.
+ * `prev`: the hint this window was built with, `h`: the one for the next.  small_to_64k: a slot below 32 KiB goes
+ * straight to 64 KiB -- the member walk's rule (an ISIZE claim may be anything); a piece's slot is never that small
+ * unless it is all its span can produce (piece_slot, la_gzip_index.c), so the piece walk has no such step.
  */
-static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, const la_gz_member *mem,
-    const la_gz_result *res, uint32_t take, int contiguous, uint32_t last_out, uint64_t total, uint64_t cutoff,
-    double b0, double b1, const uint8_t *d_out, int packed)
+static void gz_grow_slot(struct gzip_private *st, struct gz_walk *w, struct gz_hint *h, struct gz_hint prev, uint32_t i,
+    uint32_t dst_cap, int small_to_64k)
+{
+	const uint32_t base = dst_cap > prev.cap ? dst_cap : prev.cap;
+	if (base >= st->slot_limit) { gz_too_large(st, w); return; }
+	h->cap = small_to_64k && base < 32768 ? 65536 : (base > st->slot_limit / 2 ? st->slot_limit : base * 2);
+	h->skip = i == 0 ? prev.skip : 0;
+	w->again = 1;
+}
+
+/* header metadata: what the reference has parsed while the first 64 KiB were produced (gzip.c:160-163, :196-201) */
+static void gz_take_metadata(struct gzip_private *st, const struct gz_walk *w, const la_gz_header *h)
+{
+	if (w->total >= OUT_BLOCK)
+		return;
+	st->mtime = h->mtime;
+	if (h->name_off) {
+		free(st->name);
+		st->name = strdup((const char *)st->stage.p + h->off + h->name_off);
+	}
+}
+
+/*
+ * Queue the device work of one window (its compressed bytes are already on their way: gz_prepare): table layout,
+ * device buffers, table upload, under chain the history in front of the output, and the decode.  Nothing is waited for.
+ */
+static int gz_launch(struct archive_read_filter *self, struct gzip_private *st, const struct gz_units *u)
 {
 	la_gpu_ctx *gpu = st->w.gpu;
-	uint64_t new_bytes = (total - st->total_out) + last_out;
-	const int ahead = st->ahead_ok && take && contiguous && last_out == 0 && st->carry_len == st->ahead_rem &&
+	const int pieces = u->kind == GZ_PIECES;
+	size_t o = 0;
+	const size_t o_mem = o; o += ALIGN256((size_t)u->n * sizeof(la_gz_member));
+	const size_t o_res = o; o += ALIGN256((size_t)u->n * sizeof(la_gz_result));	/* (st->o_res once the window is in flight) */
+	const size_t o_sum = o; o += 256;
+	if (la_buf_dev(gpu, &st->d_dst, u->lead + (size_t)u->max_out + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o) < 0)
+		return la_window_fail(self, &st->w, "device allocation");
+	uint8_t *T = st->d_tabs.p;
+	if (la_gpu_memcpy_h2d(gpu, T + o_mem, u->tab, (size_t)u->n * sizeof(la_gz_member)) != LA_OK)
+		return la_window_fail(self, &st->w, "host to device copy");
+	la_gz_batch bt = {
+		.d_src = st->d_src.p, .src_bytes = pieces ? st->stage_len : (size_t)u->consumed,
+		.d_members = (const la_gz_member *)(T + o_mem), .n_members = u->n,
+		.d_dst = st->d_dst.p + u->lead, .dst_cap = u->max_out, .d_results = (la_gz_result *)(T + o_res),
+		.d_summary = pieces ? NULL : (la_batch_summary *)(T + o_sum), .options = pieces ? LA_GZ_OPT_PIECES : 0,
+	};
+	if (u->packed) {
+		if (la_buf_pinned(gpu, &st->hist, LA_GZ_HIST, st->hist_len) < 0)
+			return la_window_fail(self, &st->w, "pinned history allocation");
+		if (!st->pm.in_member)
+			st->hist_len = 0;
+		if (st->hist_len &&
+		    la_gpu_memcpy_h2d(gpu, st->d_dst.p + u->lead - st->hist_len, st->hist.p, st->hist_len) != LA_OK)
+			return la_window_fail(self, &st->w, "host to device copy");
+		bt.options |= LA_GZ_OPT_CHAIN;
+		bt.hist_len = (uint32_t)st->hist_len;
+	}
+	if (la_gpu_gzip_decode(gpu, &bt) != LA_OK)
+		return la_window_fail(self, &st->w, "la_gpu_gzip_decode");
+	st->o_res = o_res;
+	st->inflight = u->kind;
+	return 0;
+}
+
+/*
+ * The end of a window's stream-order walk, for members and pieces alike: bring the bytes of units [0, w->take) behind
+ * the carry and decide how much of [carry | new bytes] may go out now.
+ */
+static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, const struct gz_units *u,
+    const la_gz_result *res, const struct gz_walk *w)
+{
+	la_gpu_ctx *gpu = st->w.gpu;
+	const uint8_t *d_out = st->d_dst.p + u->lead;	/* where unit 0's bytes are on the device */
+	const uint32_t take = w->take, last_out = w->last_out;
+	uint64_t new_bytes = (w->total - st->total_out) + last_out;
+	const int ahead = st->ahead_ok && take && w->contiguous && last_out == 0 && st->carry_len == st->ahead_rem &&
 	    new_bytes <= st->ahead_len;
 	st->ahead_ok = 0;
 	if (ahead) {
@@ -250,16 +415,16 @@ static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, co
 	uint8_t *dstp = st->slab.p + st->carry_len;
 	const double b2 = st->trace ? gz_now() : 0;
 	if (take && !ahead) {
-		if (packed || (contiguous && last_out == 0)) {
+		if (u->packed || (w->contiguous && last_out == 0)) {	/* one copy brings them all */
 			if (new_bytes && la_gpu_memcpy_d2h(gpu, dstp, d_out, (size_t)new_bytes) != LA_OK)
 				return la_window_fail(self, &st->w, "device to host copy");
 		} else {
-			size_t w = 0;
+			size_t at = 0;
 			for (uint32_t i = 0; i < take; i++) {
 				size_t len = res[i].out_len;
-				if (len && la_gpu_memcpy_d2h(gpu, dstp + w, d_out + mem[i].dst_off, len) != LA_OK)
+				if (len && la_gpu_memcpy_d2h(gpu, dstp + at, d_out + u->tab[i].dst_off, len) != LA_OK)
 					return la_window_fail(self, &st->w, "device to host copy");
-				w += len;
+				at += len;
 			}
 		}
 		if (la_gpu_sync(gpu) != LA_OK)
@@ -267,11 +432,11 @@ static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, co
 	}
 	if (st->trace)
 		fprintf(stderr, "la_gzip:   h2d+decode %.1f ms, walk+grow %.1f ms, d2h %.1f ms (%llu bytes, contiguous %d, copied ahead %d)\n",
-		    b1 - b0, b2 - b1, gz_now() - b2, (unsigned long long)new_bytes, contiguous, ahead);
-	if (packed && st->pm.in_member) {
+		    w->b1 - w->b0, b2 - w->b1, gz_now() - b2, (unsigned long long)new_bytes, w->contiguous, ahead);
+	if (u->packed && st->pm.in_member) {
 		/* the member goes on: the last LA_GZ_HIST bytes of [history | confirmed bytes of this window] are the next
 		 * window's history */
-		const size_t nb = (size_t)(total - st->total_out);
+		const size_t nb = (size_t)(w->total - st->total_out);
 		if (nb >= LA_GZ_HIST) {
 			memcpy(st->hist.p, dstp + nb - LA_GZ_HIST, LA_GZ_HIST);
 			st->hist_len = LA_GZ_HIST;
@@ -281,20 +446,20 @@ static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, co
 			memcpy(st->hist.p + keep, dstp, nb);
 			st->hist_len = keep + nb;
 		}
-	} else if (packed)
+	} else if (u->packed)
 		st->hist_len = 0;
-	st->total_out = total + last_out;
+	st->total_out = w->total + last_out;
 	st->carry_len += (size_t)new_bytes;
 
 	/* how much of [carry | new bytes] may go out now */
 	uint64_t slab_start = st->total_out - st->carry_len;	/* stream offset of slab[0] */
 	uint64_t lim;
-	if (cutoff != UINT64_MAX)
-		lim = cutoff;					/* an error follows: the reference's count */
+	if (w->cutoff != UINT64_MAX)
+		lim = w->cutoff;			/* an error follows: the reference's count */
 	else if (st->eof)
-		lim = st->total_out;				/* clean end: everything */
+		lim = st->total_out;			/* clean end: everything */
 	else
-		lim = (st->total_out / OUT_BLOCK) * OUT_BLOCK;	/* keep the partial last block back */
+		lim = gz_floor(st->total_out);		/* keep the partial last block back */
 	if (lim < slab_start)
 		lim = slab_start;
 	st->last_ret = (size_t)(lim - slab_start);
@@ -302,65 +467,16 @@ static int gz_slab(struct archive_read_filter *self, struct gzip_private *st, co
 }
 
 /*
- * One batch: decode every indexed member, then walk the results in stream
- * order.  On return *used = compressed bytes of the window that are done with,
- * the slab holds carry + newly decoded bytes (st->carry_len updated to the
- * total now waiting), *cutoff = stream offset up to which bytes may be
- * delivered (everything, unless an error follows).
+ * The stream-order walk over the members of st->idx: each one is judged by its own trailer.  On return w->used =
+ * compressed bytes of the window that are done with, w->cutoff = stream offset up to which bytes may be delivered
+ * (everything, unless an error follows).
  */
-static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private *st,
-    const la_gz_index *x, size_t *used, int phase /* 0: queue the device work; 1: results, stream-order walk, slab */)
+static void gzip_walk_members(struct gzip_private *st, const la_gz_result *res, struct gz_walk *w)
 {
-	const uint32_t n = x->n;
-	size_t o = 0;
-	const size_t o_mem = o; o += ALIGN256((size_t)n * sizeof(la_gz_member));
-	const size_t o_res = o; o += ALIGN256((size_t)n * sizeof(la_gz_result));
-	const size_t o_sum = o; o += 256;
-	size_t src_len = (size_t)x->consumed;
-	la_gpu_ctx *gpu = st->w.gpu;
-	if (phase == 0 &&
-	    (la_buf_dev(gpu, &st->d_src, src_len + 64) < 0 ||
-	     la_buf_dev(gpu, &st->d_dst, (size_t)x->max_out + 64) < 0 ||
-	     la_buf_dev(gpu, &st->d_tabs, o) < 0))
-		return la_window_fail(self, &st->w, "device allocation");
-	uint8_t *T = st->d_tabs.p;
-	const double b0 = st->trace ? gz_now() : 0;
-	/* (the compressed bytes are already on their way: gz_prepare) */
-	if (phase == 0 && la_gpu_memcpy_h2d(gpu, T + o_mem, x->members, (size_t)n * sizeof(la_gz_member)) != LA_OK)
-		return la_window_fail(self, &st->w, "host to device copy");
-	la_gz_batch bt;
-	memset(&bt, 0, sizeof(bt));
-	bt.d_src = st->d_src.p; bt.src_bytes = src_len;
-	bt.d_members = (const la_gz_member *)(T + o_mem); bt.n_members = n;
-	bt.d_dst = st->d_dst.p; bt.dst_cap = x->max_out;
-	bt.d_results = (la_gz_result *)(T + o_res);
-	bt.d_summary = (la_batch_summary *)(T + o_sum);
-	if (phase == 0) {
-		if (la_gpu_gzip_decode(gpu, &bt) != LA_OK)
-			return la_window_fail(self, &st->w, "la_gpu_gzip_decode");
-		return 0;
-	}
-	if (la_buf_host(&st->h_res, (size_t)n * sizeof(la_gz_result)) < 0) {
-		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
-		return ARCHIVE_FATAL;
-	}
-	const la_gz_result *res = (const la_gz_result *)st->h_res.p;
-	if (la_gpu_memcpy_d2h(gpu, st->h_res.p, T + o_res, (size_t)n * sizeof(la_gz_result)) != LA_OK ||
-	    la_gpu_sync(gpu) != LA_OK)
-		return la_window_fail(self, &st->w, "result copy");
-	const double b1 = st->trace ? gz_now() : 0;
-
-	/* ---- stream-order walk ---- */
-	uint64_t total = st->total_out;		/* stream offset of the next decoded byte */
-	uint64_t cutoff = UINT64_MAX;		/* deliver only up to here (set when an error follows) */
-	uint32_t take = 0;			/* members whose bytes join the slab */
-	uint32_t last_out = 0;			/* bytes of a failing member that still count as produced */
-	int contiguous = 1;
-	int stop = 0;
-	*used = src_len;
-	const uint32_t prev_skip = st->hint_skip, prev_cap = st->hint_cap;
-	st->hint_skip = st->hint_cap = 0;
-	for (uint32_t i = 0; i < n && !stop; i++) {
+	const la_gz_index *x = &st->idx;
+	const struct gz_hint prev = st->hint;
+	st->hint.skip = st->hint.cap = 0;
+	for (uint32_t i = 0; i < x->n; i++) {
 		const la_gz_result *r = &res[i];
 		const la_gz_member *m = &x->members[i];
 		const la_gz_header *h = &x->headers[i];
@@ -374,63 +490,41 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 		    /* ... or it ended with fewer than 8 bytes left in a span that a BGZF size field or a
 		     * boundary guess cut short while the window holds more bytes: same cure */
 		    (r->status == LA_ST_GZ_NO_TRAILER && m->src_off + m->src_len < st->stage_len)) {
-			*used = (size_t)member_start;
-			st->hint_skip = (i == 0 ? prev_skip : 0) + 1;
-			st->hint_cap = i == 0 ? prev_cap : 0;
-			stop = 1;
-			break;
+			w->used = (size_t)member_start;
+			st->hint.skip = (i == 0 ? prev.skip : 0) + 1;
+			st->hint.cap = i == 0 ? prev.cap : 0;
+			w->again = 1;
+			return;
 		}
 		if (r->status == LA_ST_GZ_OUT_FULL) {
 			/* the ISIZE claim was too small for what the member really holds */
-			*used = (size_t)member_start;
-			uint32_t base = m->dst_cap > prev_cap ? m->dst_cap : prev_cap;
-			if (base >= st->slot_limit) {
-				/* the slot cannot grow any further (32-bit positions on the device): say so
-				 * instead of retrying for ever or delivering a wrapped slot */
-				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
-				cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
-				stop = 1;
-				break;
-			}
-			st->hint_cap = base < 32768 ? 65536 : (base > st->slot_limit / 2 ? st->slot_limit : base * 2);
-			st->hint_skip = i == 0 ? prev_skip : 0;
-			stop = 1;
-			break;
+			w->used = (size_t)member_start;
+			gz_grow_slot(st, w, &st->hint, prev, i, m->dst_cap, 1);
+			return;
 		}
 		if (r->status == LA_ST_GZ_NO_TRAILER && !st->w.upstream_eof) {
 			/* the trailer lies beyond this window */
-			*used = (size_t)member_start;
-			stop = 1;
-			break;
+			w->used = (size_t)member_start;
+			return;
 		}
-		/* header metadata: parsed by the reference while the first 64 KiB were produced */
-		if (total < OUT_BLOCK) {
-			st->mtime = h->mtime;
-			if (h->name_off) {
-				free(st->name);
-				st->name = strdup((const char *)st->stage.p + h->off + h->name_off);
-			}
-		}
+		gz_take_metadata(st, w, h);
 		switch (r->status) {
 		case LA_ST_OK:
 		case LA_ST_GZ_BAD_CRC:
 		case LA_ST_GZ_BAD_ISIZE:
 			if (st->strict && r->status != LA_ST_OK) {
-				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_status_message(r->status));
-				cutoff = total;	/* new behaviour: everything before the bad member, then the error */
-				stop = 1;
+				gz_fail_in_front(st, w, la_status_message(r->status));
 				break;
 			}
 			if (r->out_len != m->dst_cap)
-				contiguous = 0;
-			take = i + 1;
-			total += r->out_len;
+				w->contiguous = 0;
+			w->take = i + 1;
+			w->total += r->out_len;
 			if (h->bgzf_size && (uint64_t)r->consumed + 8 < m->src_len) {
 				/* the member ended before the place its BGZF size field points at: the field is
 				 * only a hint (the reference never reads FEXTRA, gzip.c:185-199) and it was wrong.
 				 * The stream goes on right behind this member's trailer: index again from there. */
-				*used = (size_t)(m->src_off + (uint64_t)r->consumed + 8);
-				stop = 1;
+				w->used = (size_t)(m->src_off + (uint64_t)r->consumed + 8);
 				break;
 			}
 			if (x->speculative && !h->bgzf_size && (uint64_t)r->consumed + 8 < m->src_len) {
@@ -441,174 +535,88 @@ static int gzip_run_batch(struct archive_read_filter *self, struct gzip_private 
 					/* a header the strict boundary search passed over (unusual XFL / OS): the
 					 * stream goes on here; from now on every 1f 8b 08 is a candidate */
 					st->loose = 1;
-					*used = (size_t)p;
-					stop = 1;
+					w->used = (size_t)p;
 					break;
 				}
 				/* bytes after the trailer are not a member header: silent end (gzip.c:351-353) */
 				st->eof = 1;
-				stop = 1;
+				break;
 			}
-			break;
+			continue;	/* the member is fine: on to the next */
 		case LA_ST_GZ_DATA:
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
-			cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
-			    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
-			last_out = r->out_len;
-			take = i + 1;
-			stop = 1;
+			gz_failed_after(st, w, i + 1, r->out_len, GZ_DATA_ERROR);
 			break;
 		case LA_ST_GZ_TRUNCATED:
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
-			cutoff = ((total + r->out_len) / OUT_BLOCK) * OUT_BLOCK;
-			last_out = r->out_len;
-			take = i + 1;
-			stop = 1;
+			gz_truncated(st, w, i + 1, r->out_len);
 			break;
 		case LA_ST_GZ_NO_TRAILER:
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, NULL);	/* ARCHIVE_FATAL without a message (gzip.c:419-421) */
-			cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
-			    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
-			last_out = r->out_len;
-			take = i + 1;
-			stop = 1;
+			gz_failed_after(st, w, i + 1, r->out_len, GZ_NO_TRAILER);
 			break;
 		default:
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
-			cutoff = total;
-			stop = 1;
+			gz_fail_in_front(st, w, GZ_DATA_ERROR);
 			break;
 		}
+		return;		/* the walk ends at member i */
 	}
-	if (!stop) {
-		/* every member of the window is fine: what comes after it? */
-		if (x->end_kind == LA_END_EOF)
-			st->eof = 1;
-		else if (x->end_kind == LA_END_TRUNCATED) {
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
-			cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
-		} else if (x->end_kind == LA_END_GZ_TOO_LARGE) {
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
-			cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
-		}
-	}
-
-	return gz_slab(self, st, x->members, res, take, contiguous, last_out, total, cutoff, b0, b1, st->d_dst.p, 0);
+	/* every member of the window is fine: what comes after it? */
+	if (x->end_kind == LA_END_EOF)
+		st->eof = 1;
+	else if (x->end_kind == LA_END_TRUNCATED)
+		gz_truncated(st, w, w->take, 0);
+	else if (x->end_kind == LA_END_GZ_TOO_LARGE)
+		gz_too_large(st, w);
 }
 
 /*
- * One window of piece mode, the counterpart of gzip_run_batch: phase 0 queues la_gpu_gzip_decode with
- * LA_GZ_OPT_PIECES over st->pcs, phase 1 walks the results in stream order.  Piece k is confirmed only by
- * LA_ST_GZ_PIECE_END with consumed == src_len (la_host.h: the chain is then correct by induction); what the first
- * unconfirmed piece answers decides how the walk ends, and whatever the pieces behind it decoded is discarded.
+ * The stream-order walk over the pieces of st->pcs.  Piece k is confirmed only by LA_ST_GZ_PIECE_END with consumed ==
+ * src_len (la_host.h: the chain is then correct by induction); what the first unconfirmed piece answers decides how the
+ * walk ends, and whatever the pieces behind it decoded is discarded.
  */
-static int gzip_run_pieces(struct archive_read_filter *self, struct gzip_private *st, size_t *used, int phase)
+static void gzip_walk_pieces(struct gzip_private *st, const la_gz_result *res, struct gz_walk *w)
 {
 	const la_gz_pieces *x = &st->pcs;
-	const uint32_t n = x->n;
-	size_t o = 0;
-	const size_t o_mem = o; o += ALIGN256((size_t)n * sizeof(la_gz_member));
-	const size_t o_res = o; o += ALIGN256((size_t)n * sizeof(la_gz_result));
-	la_gpu_ctx *gpu = st->w.gpu;
-	const double b0 = st->trace ? gz_now() : 0;
-	/* chain: room for the history in front of the packed range (piece 0's slot starts at offset 0 of its table) */
-	const size_t lead = st->fp_chain ? LA_GZ_HIST : 0;
-	if (phase == 0) {
-		if (la_buf_dev(gpu, &st->d_dst, lead + (size_t)x->max_out + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o) < 0)
-			return la_window_fail(self, &st->w, "device allocation");
-		uint8_t *T = st->d_tabs.p;
-		if (la_gpu_memcpy_h2d(gpu, T + o_mem, x->pieces, (size_t)n * sizeof(la_gz_member)) != LA_OK)
-			return la_window_fail(self, &st->w, "host to device copy");
-		if (st->fp_chain) {
-			if (la_buf_pinned(gpu, &st->hist, LA_GZ_HIST, st->hist_len) < 0)
-				return la_window_fail(self, &st->w, "pinned history allocation");
-			if (!st->pm.in_member)
-				st->hist_len = 0;
-			if (st->hist_len &&
-			    la_gpu_memcpy_h2d(gpu, st->d_dst.p + lead - st->hist_len, st->hist.p, st->hist_len) != LA_OK)
-				return la_window_fail(self, &st->w, "host to device copy");
-		}
-		la_gz_batch bt;
-		memset(&bt, 0, sizeof(bt));
-		bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
-		bt.d_members = (const la_gz_member *)(T + o_mem); bt.n_members = n;
-		bt.d_dst = st->d_dst.p + lead; bt.dst_cap = x->max_out;
-		bt.d_results = (la_gz_result *)(T + o_res);
-		bt.options = LA_GZ_OPT_PIECES;
-		if (st->fp_chain) {
-			bt.options |= LA_GZ_OPT_CHAIN;
-			bt.hist_len = (uint32_t)st->hist_len;
-		}
-		if (la_gpu_gzip_decode(gpu, &bt) != LA_OK)
-			return la_window_fail(self, &st->w, "la_gpu_gzip_decode");
-		return 0;
-	}
-	if (la_buf_host(&st->h_res, (size_t)n * sizeof(la_gz_result)) < 0) {
-		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
-		return ARCHIVE_FATAL;
-	}
-	const la_gz_result *res = (const la_gz_result *)st->h_res.p;
-	if (la_gpu_memcpy_d2h(gpu, st->h_res.p, st->d_tabs.p + o_res, (size_t)n * sizeof(la_gz_result)) != LA_OK ||
-	    la_gpu_sync(gpu) != LA_OK)
-		return la_window_fail(self, &st->w, "result copy");
-	const double b1 = st->trace ? gz_now() : 0;
-
-	uint64_t total = st->total_out, cutoff = UINT64_MAX;
-	uint32_t take = 0, last_out = 0;
-	int contiguous = 1, stop = 0;
-	const uint32_t prev_skip = st->pm_skip, prev_cap = st->pm_cap;
-	st->pm_skip = 0;		/* (pm_cap stays for the rest of the member: "from that piece on") */
-	st->pm_retry = 0;
-	*used = (size_t)x->consumed;
-	if (!st->pm.in_member && st->total_out < OUT_BLOCK) {
-		/* header metadata, as in gzip_run_batch (dropped again should the member leave piece mode: it is then
-		 * parsed a second time) */
+	const struct gz_hint prev = st->pm_hint;
+	st->pm_hint.skip = 0;		/* (pm_hint.cap stays for the rest of the member: "from that piece on") */
+	/* A retry that the member walk asked for and a window of pieces overtook (the member at the head of that window
+	 * shows a flush point) is still on record in st->hint, and has always counted as "asked again" for this window
+	 * too: kept as it is (open point). */
+	w->again = st->hint.skip != 0 || st->hint.cap != 0;
+	if (!st->pm.in_member) {
+		/* (dropped again should the member leave piece mode: it is then parsed a second time) */
 		la_gz_header h;
 		la_gz_header_parse(st->stage.p, st->stage_len, &h);
-		st->mtime = h.mtime;
-		if (h.name_off) {
-			free(st->name);
-			st->name = strdup((const char *)st->stage.p + h.name_off);
-		}
+		gz_take_metadata(st, w, &h);
 	}
-	for (uint32_t i = 0; i < n && !stop; i++) {
+	for (uint32_t i = 0; i < x->n; i++) {
 		const la_gz_result *r = &res[i];
 		const la_gz_member *m = &x->pieces[i];
 		/* where the next window starts when piece i has to be decoded again (piece 0 of a member's first
 		 * window: at the header) */
-		const size_t again = i == 0 ? 0 : (size_t)m->src_off;
+		const size_t again_at = i == 0 ? 0 : (size_t)m->src_off;
 		const int more_behind = m->src_off + m->src_len < st->stage_len || !st->w.upstream_eof;
-		stop = 1;
 		switch (r->status) {
 		case LA_ST_GZ_PIECE_END:
 			if (r->consumed != m->src_len) {	/* (a span the image cut short: not a boundary we can vouch for) */
-				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
-				cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
+				gz_refuse(st, w, GZ_DATA_ERROR);
 				break;
 			}
 			st->pm.crc = la_crc32_combine(st->pm.crc, r->crc32, r->out_len);
 			st->pm.bytes += r->out_len;
 			st->pm.in_member = 1;
-			if (i + 1 < n && (r->out_len != m->dst_cap || (m->dst_cap & 15)))
-				contiguous = 0;
-			take = i + 1;
-			total += r->out_len;
-			stop = 0;
-			break;
+			if (i + 1 < x->n && (r->out_len != m->dst_cap || (m->dst_cap & 15)))
+				w->contiguous = 0;
+			w->take = i + 1;
+			w->total += r->out_len;
+			continue;	/* confirmed: on to the next */
 		case LA_ST_OK: {
 			/* the stream's final block ended inside this piece: the member's trailer follows */
 			const uint64_t tr = m->src_off + (uint64_t)r->consumed;
 			if (tr + 8 > st->stage_len && !st->w.upstream_eof) {
-				*used = again;	/* the trailer lies beyond this window */
+				w->used = again_at;	/* the trailer lies beyond this window */
 				break;
 			}
-			take = i + 1;
-			if (tr + 8 > st->stage_len) {
-				/* short trailer at the end of input: the LA_ST_GZ_NO_TRAILER rules */
-				la_verdict_set(&st->verdict, ARCHIVE_FATAL, NULL);
-				cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
-				    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
-				last_out = r->out_len;
+			if (tr + 8 > st->stage_len) {	/* short trailer at the end of input */
+				gz_failed_after(st, w, i + 1, r->out_len, GZ_NO_TRAILER);
 				break;
 			}
 			const uint8_t *t = st->stage.p + tr;
@@ -617,18 +625,16 @@ static int gzip_run_pieces(struct archive_read_filter *self, struct gzip_private
 			const uint32_t t_crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
 			const uint32_t t_len = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
 			if (st->strict && (t_crc != crc || t_len != isize)) {
-				/* as a many-member mismatch: everything in front of the unit that shows it, then the error */
-				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s",
-				    la_status_message(t_crc != crc ? LA_ST_GZ_BAD_CRC : LA_ST_GZ_BAD_ISIZE));
-				cutoff = total;
-				take = i;
+				/* as a many-member mismatch: everything in front of the unit that shows it (the pieces confirmed so far) */
+				gz_fail_in_front(st, w, la_status_message(t_crc != crc ? LA_ST_GZ_BAD_CRC : LA_ST_GZ_BAD_ISIZE));
 				break;
 			}
-			total += r->out_len;
+			w->take = i + 1;
+			w->total += r->out_len;
 			/* the member is over: indexing resumes the ordinary way behind its trailer */
 			memset(&st->pm, 0, sizeof(st->pm));
-			st->pm_cap = 0;
-			*used = (size_t)(tr + 8);
+			st->pm_hint.cap = 0;
+			w->used = (size_t)(tr + 8);
 			break;
 		}
 		case LA_ST_GZ_NEEDS_HISTORY:
@@ -638,67 +644,116 @@ static int gzip_run_pieces(struct archive_read_filter *self, struct gzip_private
 				 * a walk: piece mode is left, the pieces confirmed above are dropped, and the member is
 				 * indexed again from its header the ordinary way */
 				memset(&st->pm, 0, sizeof(st->pm));
-				st->pm_cap = 0;
-				st->pm_declined = st->pm_retry = 1;
-				total = st->total_out;
-				take = 0;
-				contiguous = 1;
-				*used = 0;
+				st->pm_hint.cap = 0;
+				st->pm_declined = w->again = 1;
+				w->total = st->total_out;
+				w->take = 0;
+				w->contiguous = 1;
+				w->used = 0;
 				break;
 			}
 			/* a member that changes its nature after pieces of it are out: refused by name (deliberate
 			 * divergences) -- the device has no window of the bytes in front to go on from */
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL,
+			gz_refuse(st, w,
 			    "gzip member stops being independent pieces: blocks behind a flush point depend on earlier output (read it without LA_GZIP_FLUSH_POINTS)");
-			cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
 			break;
 		case LA_ST_GZ_TRUNCATED:
 			if (more_behind) {
 				/* the marker this piece ends in is not a block boundary (00 00 FF FF inside stored data or
 				 * Huffman bits): merge the piece with the next one and decode again from here */
-				*used = again;
-				st->pm_skip = (i == 0 ? prev_skip : 0) + 1;
-				st->pm_retry = 1;
+				w->used = again_at;
+				st->pm_hint.skip = (i == 0 ? prev.skip : 0) + 1;
+				w->again = 1;
 				break;
 			}
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
-			cutoff = ((total + r->out_len) / OUT_BLOCK) * OUT_BLOCK;
-			last_out = r->out_len;
-			take = i + 1;
+			gz_truncated(st, w, i + 1, r->out_len);
 			break;
-		case LA_ST_GZ_OUT_FULL: {
-			*used = again;
-			const uint32_t base = m->dst_cap > prev_cap ? m->dst_cap : prev_cap;
-			if (base >= st->slot_limit) {
-				la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
-				cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
-				break;
-			}
-			st->pm_cap = base > st->slot_limit / 2 ? st->slot_limit : base * 2;
-			st->pm_skip = i == 0 ? prev_skip : 0;
-			st->pm_retry = 1;
+		case LA_ST_GZ_OUT_FULL:
+			w->used = again_at;
+			gz_grow_slot(st, w, &st->pm_hint, prev, i, m->dst_cap, 0);
 			break;
-		}
 		case LA_ST_GZ_DATA:
 		default:
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "gzip decompression failed");
-			cutoff = r->out_len == 0 ? (total / OUT_BLOCK) * OUT_BLOCK
-			    : ((total + r->out_len - 1) / OUT_BLOCK) * OUT_BLOCK;
-			last_out = r->out_len;
-			take = i + 1;
+			gz_failed_after(st, w, i + 1, r->out_len, GZ_DATA_ERROR);
 			break;
 		}
+		return;		/* the walk ends at piece i */
 	}
-	if (!stop && st->w.upstream_eof && x->consumed >= st->stage_len) {
+	if (st->w.upstream_eof && x->consumed >= st->stage_len)
 		/* every piece confirmed, no final block, no byte left: the member was cut behind a flush point */
-		la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
-		cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
-	} else if (!stop && x->end_kind == LA_END_GZ_TOO_LARGE) {
-		la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
-		cutoff = (total / OUT_BLOCK) * OUT_BLOCK;
+		gz_truncated(st, w, w->take, 0);
+	else if (x->end_kind == LA_END_GZ_TOO_LARGE)
+		gz_too_large(st, w);
+}
+
+/*
+ * The window in flight: results, stream-order walk, slab.  On return the slab holds carry + newly decoded bytes
+ * (st->carry_len updated to the total now waiting) and st->last_ret says how many of them go out now.
+ */
+static int gz_finish(struct archive_read_filter *self, struct gzip_private *st, struct gz_walk *w)
+{
+	const struct gz_units u = gz_units_of(st, st->inflight);
+	*w = (struct gz_walk){ .total = st->total_out, .cutoff = UINT64_MAX, .contiguous = 1, .used = (size_t)u.consumed,
+	    .b0 = st->trace ? gz_now() : 0 };
+	if (la_buf_host(&st->h_res, (size_t)u.n * sizeof(la_gz_result)) < 0) {
+		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
+		return ARCHIVE_FATAL;
 	}
-	st->ahead_ok = 0;
-	return gz_slab(self, st, x->pieces, res, take, contiguous, last_out, total, cutoff, b0, b1, st->d_dst.p + lead, st->fp_chain);
+	const la_gz_result *res = (const la_gz_result *)st->h_res.p;
+	if (la_gpu_memcpy_d2h(st->w.gpu, st->h_res.p, st->d_tabs.p + st->o_res, (size_t)u.n * sizeof(la_gz_result)) != LA_OK ||
+	    la_gpu_sync(st->w.gpu) != LA_OK)
+		return la_window_fail(self, &st->w, "result copy");
+	w->b1 = st->trace ? gz_now() : 0;
+	if (u.kind == GZ_PIECES) {
+		gzip_walk_pieces(st, res, w);
+		st->ahead_ok = 0;
+	} else
+		gzip_walk_members(st, res, w);
+	return gz_slab(self, st, &u, res, w);
+}
+
+/*
+ * A window in which the walker found no unit to queue, for either table: free it, let the window move, and say what
+ * the next look at the state will find.
+ */
+static int gz_nothing_queued(struct archive_read_filter *self, struct gzip_private *st, enum gz_inflight kind)
+{
+	const int pieces = kind == GZ_PIECES;
+	const int end_kind = gz_units_of(st, kind).end_kind;
+	gz_free_tables(st);
+	if (la_gpu_sync(st->w.gpu) != LA_OK)	/* the upload: the window may move now */
+		return la_window_fail(self, &st->w, "host to device copy");
+	if (end_kind == LA_END_GZ_TOO_LARGE)
+		la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
+	else if (pieces ? st->w.upstream_eof : end_kind == LA_END_TRUNCATED)
+		la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");	/* (pieces: in a member, no byte left) */
+	else if (!pieces && (end_kind != LA_END_NEED_MORE || st->w.upstream_eof))
+		st->eof = 1;
+	else if (!pieces && !st->loose)
+		/* no trusted boundary in the whole window: before widening it, look
+		 * with every 1f 8b 08 as a candidate (and keep doing so) */
+		st->loose = 1;
+	else if (!pieces || st->w.batch_bytes < st->w.max_batch_bytes)
+		st->w.batch_bytes *= 2;		/* one member larger than the window / no marker behind the current position */
+	else if (st->pm_from) {	/* the member's header is at the head of the window */
+		st->pm_hint.skip = st->pm_hint.cap = 0;
+		st->pm_declined = 1;		/* (the LA_ST_GZ_NEEDS_HISTORY route, before anything of the member is out) */
+	} else
+		la_verdict_set(&st->verdict, ARCHIVE_FATAL,
+		    "gzip member stops being independent pieces: no flush point within LA_GPU_MAX_BATCH_MIB (read it without LA_GZIP_FLUSH_POINTS)");
+	return 0;
+}
+
+/* The table just built goes to the device.  1: in flight; 0: it is empty, the state changed instead; < 0: error. */
+static int gz_queue(struct archive_read_filter *self, struct gzip_private *st, enum gz_inflight kind)
+{
+	const struct gz_units u = gz_units_of(st, kind);
+	if (u.n == 0)
+		return gz_nothing_queued(self, st, kind);
+	const int rc = gz_launch(self, st, &u);
+	if (rc < 0)
+		gz_free_tables(st);
+	return rc < 0 ? rc : 1;
 }
 
 /*
@@ -717,38 +772,15 @@ static int gz_prepare_pieces(struct archive_read_filter *self, struct gzip_priva
 			return 2;
 		from = hlen;
 	}
-	if (la_gz_pieces_build(st->stage.p, st->stage_len, from, st->w.upstream_eof, st->pm_skip, st->pm_cap,
+	if (la_gz_pieces_build(st->stage.p, st->stage_len, from, st->w.upstream_eof, st->pm_hint.skip, st->pm_hint.cap,
 	    st->w.out_budget, st->span_limit, &st->pcs) != 0) {
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
 		return ARCHIVE_FATAL;
 	}
 	st->pm_from = from;
-	if (st->pcs.n == 0) {
-		const int kind = st->pcs.end_kind;
-		la_gz_pieces_free(&st->pcs);
-		if (la_gpu_sync(st->w.gpu) != LA_OK)	/* the upload: the window may move now */
-			return la_window_fail(self, &st->w, "host to device copy");
-		if (kind == LA_END_GZ_TOO_LARGE)
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
-		else if (st->w.upstream_eof)
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");	/* in a member, no byte left */
-		else if (st->w.batch_bytes < st->w.max_batch_bytes)
-			st->w.batch_bytes *= 2;		/* no marker behind the current position: as for a member larger than the window */
-		else if (from) {
-			st->pm_skip = st->pm_cap = 0;
-			st->pm_declined = 1;		/* (the LA_ST_GZ_NEEDS_HISTORY route, before anything of the member is out) */
-		} else
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL,
-			    "gzip member stops being independent pieces: no flush point within LA_GPU_MAX_BATCH_MIB (read it without LA_GZIP_FLUSH_POINTS)");
-		return 0;
-	}
-	size_t used = 0;
-	const int rc = gzip_run_pieces(self, st, &used, 0);
-	if (rc < 0) {
-		la_gz_pieces_free(&st->pcs);
+	const int rc = gz_queue(self, st, GZ_PIECES);
+	if (rc <= 0)
 		return rc;
-	}
-	st->inflight = st->inflight_pieces = 1;
 	st->ahead_ok = 0;
 	la_window_ramp(&st->w);
 	if (st->trace)
@@ -758,7 +790,7 @@ static int gz_prepare_pieces(struct archive_read_filter *self, struct gzip_priva
 
 /*
  * Gather one window, start its upload, find the member boundaries and queue the decode: nothing is
- * waited for.  Returns 1 when a window is in flight (st->idx, st->inflight), 0 when the state changed
+ * waited for.  Returns 1 when a window is in flight (st->inflight), 0 when the state changed
  * instead (end of stream, pending error, wider window, looser boundary search: the caller looks again),
  * ARCHIVE_FATAL on error.
  */
@@ -780,48 +812,20 @@ static int gz_prepare(struct archive_read_filter *self, struct gzip_private *st)
 		if (pr != 2)
 			return pr;
 	}
-	if (la_gz_index_build_ex(st->stage.p, st->stage_len, st->w.upstream_eof, st->hint_skip, st->hint_cap,
+	if (la_gz_index_build_ex(st->stage.p, st->stage_len, st->w.upstream_eof, st->hint.skip, st->hint.cap,
 	    st->loose ? 0 : LA_GZ_INDEX_STRICT, st->w.out_budget, st->span_limit, &st->idx) != 0) {
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
 		return ARCHIVE_FATAL;
 	}
-	if (st->idx.n == 0) {
-		int kind = st->idx.end_kind;
-		la_gz_index_free(&st->idx);
-		if (la_gpu_sync(st->w.gpu) != LA_OK)	/* the upload above: the window may move now */
-			return la_window_fail(self, &st->w, "host to device copy");
-		if (kind == LA_END_NEED_MORE) {
-			if (st->w.upstream_eof) { st->eof = 1; return 0; }
-			if (!st->loose) {
-				/* no trusted boundary in the whole window: before widening it, look
-				 * with every 1f 8b 08 as a candidate (and keep doing so) */
-				st->loose = 1;
-				return 0;
-			}
-			st->w.batch_bytes *= 2;	/* one member larger than the window */
-			return 0;
-		}
-		if (kind == LA_END_TRUNCATED)
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "truncated gzip input");
-		else if (kind == LA_END_GZ_TOO_LARGE)
-			la_verdict_set(&st->verdict, ARCHIVE_FATAL, "%s", la_end_message(LA_END_GZ_TOO_LARGE, 1));
-		else
-			st->eof = 1;
-		return 0;
-	}
-	size_t used = 0;
-	int rc = gzip_run_batch(self, st, &st->idx, &used, 0);
-	if (rc < 0) {
-		la_gz_index_free(&st->idx);
+	const int rc = gz_queue(self, st, GZ_MEMBERS);
+	if (rc <= 0)
 		return rc;
-	}
-	st->inflight = 1;
 	/* decoded bytes of this window towards the OTHER slab, behind the place of what will be left of the carry: only for a
 	 * window whose boundaries and sizes are the index's own (no guessed boundary, no retry hints) and of ordinary size */
 	st->ahead_ok = 0;
 	/* (not before the window ramp has reached its target: a second pinned slab costs about half a millisecond per MiB, and one
 	 * that has to grow three times costs a short stream more than the copies it hides) */
-	if (!st->no_ahead && st->w.batch_bytes >= st->w.target_bytes && !st->idx.speculative && st->hint_skip == 0 && st->hint_cap == 0 && st->idx.max_out != 0 &&
+	if (!st->no_ahead && st->w.batch_bytes >= st->w.target_bytes && !st->idx.speculative && st->hint.skip == 0 && st->hint.cap == 0 && st->idx.max_out != 0 &&
 	    st->idx.max_out <= ((uint64_t)1 << 30) && st->carry_len >= st->last_ret) {
 		const size_t rem = st->carry_len - st->last_ret;
 		if (la_buf_pinned(st->w.gpu, &st->slab2, rem + (size_t)st->idx.max_out + 16, 0) == 0 &&
@@ -860,7 +864,7 @@ static ssize_t gzip_filter_read(struct archive_read_filter *self, const void **p
 			}
 			return 0;
 		}
-		if (!st->inflight) {
+		if (st->inflight == GZ_NONE) {
 			int pr = gz_prepare(self, st);
 			if (pr < 0)
 				return pr;
@@ -868,27 +872,25 @@ static ssize_t gzip_filter_read(struct archive_read_filter *self, const void **p
 				continue;
 		}
 		/* the window in flight: results, stream-order walk, slab */
-		size_t used = 0;
+		struct gz_walk w;
 		const double t2 = st->trace ? gz_now() : 0;
-		const int pieces = st->inflight_pieces;
-		int rc = pieces ? gzip_run_pieces(self, st, &used, 1) : gzip_run_batch(self, st, &st->idx, &used, 1);
-		st->inflight = st->inflight_pieces = 0;
-		int made_progress = used > 0;
-		if (pieces)
-			la_gz_pieces_free(&st->pcs);
-		else if (made_progress)
+		const int members = st->inflight == GZ_MEMBERS;
+		int rc = gz_finish(self, st, &w);
+		const size_t used = w.used;
+		const int made_progress = used > 0;
+		gz_free_tables(st);
+		st->inflight = GZ_NONE;
+		if (members && made_progress)
 			st->pm_declined = 0;	/* (the member that left piece mode is behind us, or will be found declined again) */
 		if (st->trace)
 			fprintf(stderr, "la_gzip:   finished in %.1f ms, used %zu of %zu, out %zu\n", gz_now() - t2, used, st->stage_len, st->last_ret);
-		la_gz_index_free(&st->idx);
 		if (rc < 0)
 			return rc;
 		if (used < st->stage_len)
 			memmove(st->stage.p, st->stage.p + used, st->stage_len - used);
 		st->stage_len -= used;
-		if (!made_progress && !st->verdict.rc && !st->eof && st->hint_skip == 0 && st->hint_cap == 0 &&
-		    !(pieces && st->pm_retry)) {
-			/* nothing could be finished in this window: it has to grow */
+		if (!made_progress && !st->verdict.rc && !st->eof && !w.again) {
+			/* nothing could be finished in this window and nothing asked for the same bytes again: it has to grow */
 			if (st->w.upstream_eof) { st->eof = 1; continue; }
 			st->w.batch_bytes *= 2;
 		}
@@ -915,10 +917,7 @@ static int gzip_filter_close(struct archive_read_filter *self)
 		return ARCHIVE_OK;
 	la_gpu_ctx *gpu = st->w.gpu;
 	la_gpu_sync(gpu);
-	if (st->inflight && st->inflight_pieces)
-		la_gz_pieces_free(&st->pcs);
-	else if (st->inflight)
-		la_gz_index_free(&st->idx);
+	gz_free_tables(st);
 	la_buf_release(gpu, &st->stage);
 	la_buf_release(gpu, &st->slab);
 	la_buf_release(gpu, &st->slab2);

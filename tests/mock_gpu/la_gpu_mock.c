@@ -11,6 +11,7 @@
 #include "../../oracle/la_oracle.h"
 #include <stdlib.h>
 #include <string.h>
+#include <zlib.h>	/* LA_GZ_OPT_PIECES: Z_BLOCK and inflateSetDictionary */
 
 /* test hook: how many blocks were decoded against a carried history */
 static unsigned long mock_hist_blocks;
@@ -139,9 +140,101 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 	return LA_OK;
 }
 
+/*
+ * LA_GZ_OPT_PIECES, alone or with LA_GZ_OPT_CHAIN, as include/la_gpu.h words them: zlib's raw inflate, one fresh stream
+ * per piece, stopped at every block end (Z_BLOCK) to see whether a non-final block ended on a byte boundary and on the
+ * last byte of the span.  Under chain the piece starts from a dictionary, the last 32 KiB of [history | bytes packed so
+ * far], and writes behind the piece before it; a distance zlib calls too far back is then in front of the history
+ * (LA_ST_GZ_DATA), and without the chain in front of the piece (LA_ST_GZ_NEEDS_HISTORY).  Every piece is decoded into a
+ * buffer of its own with one byte more than its slot, so that "does not fit" is seen and never written.
+ */
+static int mock_gz_pieces(const la_gz_batch *bt)
+{
+	const int chain = (bt->options & LA_GZ_OPT_CHAIN) != 0;
+	const uint64_t base = bt->n_members ? bt->d_members[0].dst_off : 0;
+	uint8_t *const front = bt->d_dst + base - (chain ? bt->hist_len : 0);	/* chain: [history | packed bytes] starts here */
+	uint64_t packed = 0;
+	int dead = 0;		/* chain: a piece in front ended the chain; what follows is unspecified */
+	for (uint32_t i = 0; i < bt->n_members; i++) {
+		const la_gz_member *m = &bt->d_members[i];
+		la_gz_result *r = &bt->d_results[i];
+		memset(r, 0, sizeof(*r));
+		r->status = LA_ST_GZ_DATA;
+		if (dead)
+			continue;
+		const uint64_t in_room = m->src_off < bt->src_bytes ? bt->src_bytes - m->src_off : 0;
+		const size_t slen = m->src_len < in_room ? m->src_len : (size_t)in_room;
+		const uint64_t at = chain ? packed : m->dst_off;	/* counted from base under chain, from d_dst otherwise */
+		const uint64_t out_room = at < bt->dst_cap ? bt->dst_cap - at : 0;
+		const size_t cap = m->dst_cap < out_room ? m->dst_cap : (size_t)out_room;
+		uint8_t *dst = chain ? bt->d_dst + base + packed : bt->d_dst + m->dst_off;
+		uint8_t *tmp = malloc(cap + 1);
+		z_stream z;
+		memset(&z, 0, sizeof(z));
+		if (tmp == NULL || inflateInit2(&z, -15) != Z_OK) {
+			free(tmp);
+			return LA_ERR_NOMEM;
+		}
+		if (chain) {
+			const uint64_t have = bt->hist_len + packed;
+			const uInt dl = (uInt)(have < 32768 ? have : 32768);
+			if (dl)
+				inflateSetDictionary(&z, front + have - dl, dl);
+		}
+		z.next_in = (Bytef *)(bt->d_src + m->src_off);
+		z.avail_in = (uInt)slen;
+		z.next_out = tmp;
+		z.avail_out = (uInt)(cap + 1);
+		uint32_t st;
+		for (;;) {
+			const int rc = inflate(&z, Z_BLOCK);
+			if (z.total_out > cap) { st = LA_ST_GZ_OUT_FULL; break; }
+			if (rc == Z_STREAM_END) { st = LA_ST_OK; break; }
+			if (rc == Z_DATA_ERROR) {
+				const int far_back = z.msg != NULL && strcmp(z.msg, "invalid distance too far back") == 0;
+				st = far_back && !chain ? LA_ST_GZ_NEEDS_HISTORY : LA_ST_GZ_DATA;
+				break;
+			}
+			if (rc != Z_OK && rc != Z_BUF_ERROR) { inflateEnd(&z); free(tmp); return LA_ERR_NOMEM; }
+			if ((z.data_type & 128) && !(z.data_type & 64) && z.avail_in == 0) {
+				/* a non-final block ended with the span: on a byte boundary, or in the middle of its last byte */
+				st = (z.data_type & 63) == 0 ? LA_ST_GZ_PIECE_END : LA_ST_GZ_TRUNCATED;
+				break;
+			}
+			if (z.avail_in == 0 && !(z.data_type & 128)) { st = LA_ST_GZ_TRUNCATED; break; }
+			if (rc == Z_BUF_ERROR) { st = LA_ST_GZ_TRUNCATED; break; }	/* (no progress: cannot happen with room on both sides) */
+		}
+		r->status = st;
+		r->consumed = (uint32_t)z.total_in;
+		r->out_len = st == LA_ST_GZ_OUT_FULL ? (chain ? 0 : (uint32_t)cap) : (uint32_t)z.total_out;
+		inflateEnd(&z);
+		if (st != LA_ST_GZ_OUT_FULL || !chain)
+			memcpy(dst, tmp, r->out_len);
+		free(tmp);
+		r->crc32 = orc_crc32(0, dst, r->out_len);
+		packed += r->out_len;
+		if (chain && st != LA_ST_GZ_PIECE_END)
+			dead = 1;
+	}
+	if (bt->d_summary) {
+		summary_init(bt->d_summary);
+		for (uint32_t i = 0; i < bt->n_members; i++)
+			bt->d_summary->total_out += bt->d_results[i].out_len;
+	}
+	return LA_OK;
+}
+
 int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 {
 	(void)c;
+	if (bt->options & LA_GZ_OPT_CHAIN) {
+		if (!(bt->options & LA_GZ_OPT_PIECES) ||
+		    (bt->options & (LA_GZ_OPT_LANE_KERNEL | LA_GZ_OPT_TWO_PHASE | LA_GZ_OPT_EXPAND_INORDER)) ||
+		    bt->hist_len > 32768 || bt->dst_cap + bt->hist_len >= ((uint64_t)1 << 32))
+			return LA_ERR_ARG;
+	}
+	if (bt->options & LA_GZ_OPT_PIECES)
+		return mock_gz_pieces(bt);
 	const int verify = !(bt->options & LA_GZ_OPT_NO_VERIFY);
 	la_batch_summary sm;
 	summary_init(&sm);

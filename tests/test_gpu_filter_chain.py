@@ -160,3 +160,38 @@ def test_second_member_behind_the_trailer(gpu_ctx, plain, sync_member, chain_mod
     second = co.compress(second_plain) + co.flush()
     assert cat(img + second) == (plain + second_plain, 0, "")
     assert cat(img + img) == (plain + plain, 0, "")
+
+
+# ---- slot growth and the slot limit under chain, a member whose flush points stop, and a window of pieces right behind
+# a window of members that asked for a retry: the streams of tests/test_gpu_filter_flush_points.py, written with
+# Z_SYNC_FLUSH where the test is about the pieces ----
+
+import test_gpu_filter_flush_points as F
+
+
+def test_slots_grow_until_the_piece_fits(gpu_ctx, chain_mode):
+    grow, img = F.run_stream(zlib.Z_SYNC_FLUSH)
+    assert zlib.decompress(img, 31) == grow
+    assert cat(img) == (grow, 0, "")
+    assert cat(img, read_size=4099) == (grow, 0, "")
+
+
+def test_slot_limit_refuses_the_piece_that_cannot_fit(gpu_ctx, chain_mode):
+    grow, img = F.run_stream(zlib.Z_SYNC_FLUSH)
+    chain_mode.setenv("LA_GZ_TEST_SLOT_LIMIT", "262144")
+    assert cat(img) == (grow[:(300_000 // 65536) * 65536], la_api.ARCHIVE_FATAL, F.TOO_LARGE)
+
+
+def test_no_flush_point_within_the_widest_window(gpu_ctx, chain_mode):
+    head, img = F.no_flush_point_member(zlib.Z_SYNC_FLUSH)
+    chain_mode.setenv("LA_GPU_MAX_BATCH_MIB", "1")
+    data, rc, msg = cat(img)
+    assert rc == la_api.ARCHIVE_FATAL and "no flush point within LA_GPU_MAX_BATCH_MIB" in msg
+    assert len(data) % 65536 == 0 and head.startswith(data) and len(head) - 65536 < len(data)
+
+
+def test_pieces_right_behind_members_that_asked_for_a_retry(gpu_ctx, plain, sync_member, chain_mode):
+    front_plain, front = F.members_with_a_planted_header(24)
+    want, res = O.gzip_stream_decode(front + sync_member[2], len(front_plain) + len(plain) + 65536)
+    assert (want.tobytes(), res.rc) == (front_plain + plain, 0)
+    assert cat(front + sync_member[2]) == (front_plain + plain, 0, "")

@@ -173,3 +173,106 @@ def test_what_follows_the_trailer(gpu_ctx, plain, full_member, piece_mode):
     assert cat(img + second) == (plain + second_plain, 0, "")
     assert cat(img + b"not a gzip header at all" * 3) == (plain, 0, "")
     assert cat(img + img) == (plain + plain, 0, "")
+
+
+# ---- branches of the piece walk that the streams above do not reach: slot growth, the slot and span limits, a member
+# whose flush points stop, and a window of pieces right behind a window of members that asked for a retry ----
+
+TOO_LARGE = "gzip member too large for the GPU data plane (4 GiB limit)"
+GROW_SPANS = (100_000, 100_000, 100_000, 400_000, 400_000, 400_000, 400_000)
+
+
+def run_stream(flush):
+    """runs of one byte value between flush points: 400 000 of them are a few hundred compressed bytes, so the first
+    slot of such a piece (64 KiB) is too small three times over"""
+    plain = b"".join(bytes([65 + k]) * n for k, n in enumerate(GROW_SPANS))
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    pieces, at = [], 0
+    for n in GROW_SPANS:
+        pieces.append(c.compress(plain[at:at + n]) + c.flush(flush))
+        at += n
+    assert max(len(p) for p in pieces) < 1000
+    return plain, member(b"".join(pieces) + c.flush(), plain)
+
+
+def test_slots_grow_until_the_piece_fits(gpu_ctx, piece_mode):
+    plain, img = run_stream(zlib.Z_FULL_FLUSH)
+    assert zlib.decompress(img, 31) == plain
+    assert cat(img) == (plain, 0, "")
+    assert cat(img, read_size=4099) == (plain, 0, "")
+
+
+def test_slot_limit_refuses_the_piece_that_cannot_fit(gpu_ctx, piece_mode):
+    plain, img = run_stream(zlib.Z_FULL_FLUSH)
+    piece_mode.setenv("LA_GZ_TEST_SLOT_LIMIT", "262144")
+    # the ordinary path's message for the same limit (a member whose ISIZE claims too little)
+    piece_mode.delenv("LA_GZIP_FLUSH_POINTS")
+    fat = bytes(range(256)) * 4096
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    liar = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03" + c.compress(fat) + c.flush() + struct.pack("<II", zlib.crc32(fat), 10)
+    ordinary = cat(liar)
+    assert ordinary[1:] == (la_api.ARCHIVE_FATAL, TOO_LARGE)
+    piece_mode.setenv("LA_GZIP_FLUSH_POINTS", "1")
+    # the three pieces of 100 000 fit into 128 KiB; the fourth needs 400 000: whole 64 KiB blocks of the 300 000 in front
+    k = 300_000 // 65536
+    assert cat(img) == (plain[:k * 65536], la_api.ARCHIVE_FATAL, ordinary[2])
+
+
+def test_span_limit_refuses_the_piece_that_is_too_long(gpu_ctx, piece_mode):
+    rnd = random.Random(21)
+    small, large = rnd.randbytes(200_000), rnd.randbytes(300_000)      # stored: a piece is as long as its step
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    body = b"".join(c.compress(small[i:i + 10_000]) + c.flush(zlib.Z_FULL_FLUSH) for i in range(0, len(small), 10_000))
+    body += b"".join(c.compress(large[i:i + STEP]) + c.flush(zlib.Z_FULL_FLUSH) for i in range(0, len(large), STEP)) + c.flush()
+    whole = small + large
+    assert zlib.decompress(body, -15) == whole
+    piece_mode.setenv("LA_GZ_TEST_SPAN_LIMIT", "20000")
+    data, rc, msg = cat(member(body, whole))
+    assert (rc, msg) == (la_api.ARCHIVE_FATAL, TOO_LARGE)
+    # whole 64 KiB blocks of what stands in front of the first piece of 30 000
+    assert data == whole[:(len(small) // 65536) * 65536]
+    piece_mode.delenv("LA_GZ_TEST_SPAN_LIMIT")
+    assert cat(member(body, whole)) == (whole, 0, "")
+
+
+def no_flush_point_member(flush):
+    """flush points for two windows of 1 MiB and more, then 2.5 MiB without one"""
+    rnd = random.Random(22)
+    head = rnd.randbytes(2_300_000)
+    tail = rnd.randbytes(2_700_000).replace(b"\xff\xff", b"\xff\xfe")      # (no accidental 00 00 FF FF in the stored bytes)
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    body = b"".join(c.compress(head[i:i + STEP]) + c.flush(flush) for i in range(0, len(head), STEP))
+    rest = c.compress(tail) + c.flush()
+    assert len(body) > 2 << 20 and len(rest) > 5 << 19 and MARKER not in rest
+    return head, member(body + rest, head + tail)
+
+
+def test_no_flush_point_within_the_widest_window(gpu_ctx, piece_mode):
+    head, img = no_flush_point_member(zlib.Z_FULL_FLUSH)
+    piece_mode.setenv("LA_GPU_MAX_BATCH_MIB", "1")
+    data, rc, msg = cat(img)
+    assert rc == la_api.ARCHIVE_FATAL and "no flush point within LA_GPU_MAX_BATCH_MIB" in msg
+    assert len(data) % 65536 == 0 and head.startswith(data) and len(head) - 65536 < len(data)
+
+
+def members_with_a_planted_header(seed):
+    """two members of stored data, 600 000 bytes each and free of 00 00 FF FF, so that the first 1 MiB window is walked as
+    members; the second holds what looks like a member header, the boundary guess the decode refutes"""
+    rnd = random.Random(seed)
+    clean = lambda b: b.replace(b"\xff\xff", b"\xff\xfe").replace(b"\x1f\x8b", b"\x1f\x8c").replace(b"\x00", b"\x01")
+    one = clean(rnd.randbytes(600_000))
+    two = clean(rnd.randbytes(250_000)) + b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03" + clean(rnd.randbytes(350_000))
+    img = b""
+    for d in (one, two):
+        co = zlib.compressobj(1, zlib.DEFLATED, 31)     # (random bytes: stored blocks, the last of them not an empty one)
+        img += co.compress(d) + co.flush()
+    assert MARKER not in img
+    return one + two, img
+
+
+def test_pieces_right_behind_members_that_asked_for_a_retry(gpu_ctx, plain, full_member, piece_mode):
+    front_plain, front = members_with_a_planted_header(23)
+    want, res = O.gzip_stream_decode(front + full_member[2], len(front_plain) + len(plain) + 65536)
+    assert (want.tobytes(), res.rc) == (front_plain + plain, 0)
+    assert cat(front + full_member[2]) == (front_plain + plain, 0, "")
+    assert cat(front + full_member[2], read_size=70001) == (front_plain + plain, 0, "")
