@@ -82,10 +82,13 @@ int  archive_write_add_filter_lz4(struct archive *);				/* archive.h:819; archiv
 int  archive_write_add_filter_gzip(struct archive *);				/* archive.h:816; archive_write_add_filter_gzip.c:98 */
 int  archive_write_add_filter_zstd(struct archive *);				/* archive.h:837; archive_write_add_filter_zstd.c:115 (host/la_write_zstd.c) */
 int  archive_write_set_format_raw(struct archive *);				/* one entry, data passed through */
+int  archive_write_set_format_zip(struct archive *);				/* archive.h:867; archive_write_set_format_zip.c:720 (host/la_write_zip.c): deflate + CRC32 of a window of entries per device call */
+int  archive_write_set_format_option(struct archive *, const char *m, const char *o, const char *v);	/* archive.h:927; "zip", "compression", "store" ... */
 int  archive_write_set_filter_option(struct archive *, const char *m, const char *o, const char *v);	/* "lz4", "block-checksum", "1" ... */
 int  archive_write_open_memory(struct archive *, void *buffer, size_t buffSize, size_t *used);
 int  archive_write_open_fd(struct archive *, int fd);
-int  archive_write_header(struct archive *, struct archive_entry *);
+int  archive_write_header(struct archive *, struct archive_entry *);		/* finishes the entry before it (archive_write.c:751) */
+int  archive_write_finish_entry(struct archive *);				/* archive.h:909 */
 ssize_t archive_write_data(struct archive *, const void *, size_t);
 int  archive_write_close(struct archive *);
 int  archive_write_free(struct archive *);
@@ -112,6 +115,14 @@ unsigned    archive_entry_filetype(struct archive_entry *);			/* AE_IFREG 010000
 unsigned    archive_entry_perm(struct archive_entry *);
 void        archive_entry_set_pathname(struct archive_entry *, const char *);
 void        archive_entry_set_mtime(struct archive_entry *, int64_t, long);
+/* entries of the caller's own, for archive_write_header (archive_entry.h:235-239, :355, :393, :397-398) */
+struct archive_entry *archive_entry_new(void);
+struct archive_entry *archive_entry_clear(struct archive_entry *);
+void        archive_entry_free(struct archive_entry *);
+void        archive_entry_set_size(struct archive_entry *, int64_t);
+void        archive_entry_unset_size(struct archive_entry *);
+void        archive_entry_set_filetype(struct archive_entry *, unsigned);	/* AE_IFREG, AE_IFDIR ... */
+void        archive_entry_set_perm(struct archive_entry *, unsigned);
 
 #define ARCHIVE_ERRNO_MISC (-1)			/* archive_platform.h:213 */
 #define ARCHIVE_ERRNO_FILE_FORMAT 84		/* EILSEQ-like, archive_platform.h */

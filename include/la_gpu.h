@@ -414,6 +414,77 @@ uint64_t la_gpu_gzip_compress_bound(uint64_t src_bytes, uint32_t chunk_bytes);
 int      la_gpu_gzip_compress(la_gpu_ctx *ctx, const la_gzc_batch *batch);
 
 /* =====================================================================
+ * ZIP entries -- the data plane of the ZIP writer (host/la_write_zip.c): replaces, for a whole write window of
+ * entries per call, the deflate() loop and the crc32() of libarchive/archive_write_set_format_zip.c (:1271-1301 the
+ * data of a deflated entry, :1245-1266 of a stored one, :1324-1349 the end of its stream).  The window is a table of
+ * SEGMENTS on the device; a segment is an entry's bytes, or the part of an entry that lies in this window.
+ *
+ * Output.  For segment i, in table order and back to back: gap_before[i] bytes that are left untouched (the host
+ * writes the local file header there), the segment's stream bytes at d_results[i].out_off, out_len long, then
+ * gap_after[i] untouched bytes (the data descriptor).  *d_out_bytes is the total.
+ *   The stream bytes of a segment are exactly what la_gpu_gzip_compress gives with LA_GZC_FRAME_STREAM for
+ * d_src[src_off, src_off + src_len) alone with the same chunk_bytes and options -- chunks are cut from the segment's
+ * first byte, none crosses a segment -- followed, if LA_ZIPC_LAST is set, by the empty final fixed block 03 00.  So a
+ * last segment of length 0 is 03 00 and any other of length 0 is nothing, and the segments of one entry, in
+ * consecutive calls or in one, concatenate to one raw-deflate stream.  With LA_ZIPC_STORE (method 0) the stream bytes
+ * are the segment's bytes, copied; LA_ZIPC_LAST adds nothing to them.
+ *   crc32 is the CRC32 of the segment's input continued from crc_seed (0 for an entry's first segment, the previous
+ * segment's crc32 after that), whatever the method.
+ *
+ * Errors.  LA_ERR_ARG, with nothing written to d_out, d_results or d_out_bytes, for chunk_bytes 0 or above 49152, an
+ * unknown value of `options`, a non-zero `reserved`, and for a segment with unknown flag bits, a non-zero `reserved`,
+ * src_len >= 2^31, a range outside d_src, or gaps and worst-case stream bytes (src_len + 5 per chunk + 2) that
+ * together pass 2^32 - 1.  Launches are sized by ceil(src_bytes / chunk_bytes) + n_segs chunks, which segments that do
+ * not overlap never exceed; a table that does is LA_ERR_ARG too, and so are n_segs >= 2^31 and a chunk bound above
+ * 2^31 - 1.  Because the table is device memory, the call waits for the stream once, for this verdict (one 4-byte read
+ * behind the kernels that build the chunk table): everything queued on the context's stream before the call is
+ * therefore complete when it returns, which matters to a caller that overlaps other work on that stream; the
+ * compression itself is then queued as every other call's is.  A write is made only if it ends inside out_cap, so with an
+ * out_cap that is too small nothing lies beyond it and *d_out_bytes says what was needed;
+ * la_gpu_zip_compress_bound() always fits, gap_bytes_total being the sum of all gaps.
+ * These are additions under ABI version 3: no earlier struct or function changed.
+ * ===================================================================== */
+#define LA_ZIPC_LAST  1u	/* the entry ends with this segment */
+#define LA_ZIPC_STORE 2u	/* method 0: the bytes are copied as they are */
+
+typedef struct la_zipc_seg {
+	uint64_t src_off;	/* in d_src */
+	uint32_t src_len;	/* 0 allowed; below 2^31 */
+	uint32_t crc_seed;	/* running CRC32 of the entry's earlier segments, 0 for its first */
+	uint32_t gap_before;	/* bytes left untouched in front of the segment's stream bytes (local header) */
+	uint32_t gap_after;	/* ... and behind them (data descriptor) */
+	uint32_t flags;		/* LA_ZIPC_* */
+	uint32_t reserved;	/* 0 */
+} la_zipc_seg;
+
+typedef struct la_zipc_result {
+	uint64_t out_off;	/* first stream byte inside d_out */
+	uint32_t out_len;	/* stream bytes, 03 00 included */
+	uint32_t crc32;
+} la_zipc_result;
+
+typedef struct la_zipc_batch {
+	const uint8_t     *d_src;
+	uint64_t           src_bytes;
+	const la_zipc_seg *d_segs;
+	uint32_t           n_segs;
+	uint32_t           chunk_bytes;	/* 1 .. 49152 */
+	uint32_t           options;	/* LA_GZC_FIXED, LA_GZC_DYNAMIC or LA_GZC_STORED: the blocks of a deflated segment */
+	uint32_t           reserved;	/* 0 */
+	uint8_t           *d_out;
+	uint64_t           out_cap;
+	la_zipc_result    *d_results;	/* [n_segs] */
+	uint64_t          *d_out_bytes;	/* one u64 on the device */
+} la_zipc_batch;
+
+/* workspace of the largest mode (for la_gpu_reserve; the call reserves what it needs itself) */
+uint64_t la_gpu_zip_compress_workspace_bytes(uint64_t src_bytes, uint32_t n_segs, uint32_t chunk_bytes);
+/* upper bound of *d_out_bytes: the input, 5 bytes per chunk (at most ceil(src_bytes / chunk_bytes) + n_segs of them), 2 per
+ * segment, the gaps */
+uint64_t la_gpu_zip_compress_bound(uint64_t src_bytes, uint32_t n_segs, uint32_t chunk_bytes, uint64_t gap_bytes_total);
+int      la_gpu_zip_compress(la_gpu_ctx *ctx, const la_zipc_batch *batch);
+
+/* =====================================================================
  * zstd compression -- the data plane of the zstd WRITE filter (host/la_write_zstd.c): replaces, for a whole stream
  * per call, what libarchive/archive_write_add_filter_zstd.c gets from libzstd's ZSTD_compressStream2.  d_src[0,
  * src_bytes) is cut into blocks of block_size bytes (at most 128 KiB, Block_Maximum_Size), blocks_per_frame of them

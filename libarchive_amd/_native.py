@@ -99,6 +99,22 @@ class _GzcBatchC(C.Structure):
 
 
 LA_GZC_FIXED, LA_GZC_DYNAMIC, LA_GZC_STORED = 0, 1, 2
+LA_ZIPC_LAST, LA_ZIPC_STORE = 1, 2
+LA_ERR_ARG = -3
+ZIPC_SEG_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u4"), ("crc_seed", "<u4"), ("gap_before", "<u4"),
+                           ("gap_after", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+ZIPC_RESULT_DTYPE = np.dtype([("out_off", "<u8"), ("out_len", "<u4"), ("crc32", "<u4")])
+assert ZIPC_SEG_DTYPE.itemsize == 32 and ZIPC_RESULT_DTYPE.itemsize == 16
+
+
+class _ZipcBatchC(C.Structure):
+    _fields_ = [
+        ("d_src", C.c_void_p), ("src_bytes", C.c_uint64),
+        ("d_segs", C.c_void_p), ("n_segs", C.c_uint32), ("chunk_bytes", C.c_uint32),
+        ("options", C.c_uint32), ("reserved", C.c_uint32),
+        ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_results", C.c_void_p), ("d_out_bytes", C.c_void_p),
+    ]
+
 LA_GZC_FRAME_MEMBERS, LA_GZC_FRAME_STREAM = 0, 1
 
 
@@ -177,6 +193,11 @@ def gpu_lib():
         lib.la_gpu_lz4_compress_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_lz4_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         lib.la_gpu_gzip_decode.argtypes = [C.c_void_p, C.POINTER(_GzBatchC)]
+        lib.la_gpu_zip_compress.argtypes = [C.c_void_p, C.POINTER(_ZipcBatchC)]
+        lib.la_gpu_zip_compress_bound.restype = C.c_uint64
+        lib.la_gpu_zip_compress_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]
+        lib.la_gpu_zip_compress_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_zip_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         lib.la_gpu_zstd_compress.argtypes = [C.c_void_p, C.POINTER(_ZstdcBatchC)]
         lib.la_gpu_zstd_compress_bound.restype = C.c_uint64
         lib.la_gpu_zstd_compress_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
@@ -385,6 +406,13 @@ class GpuContext:
 
     def gzip_compress(self, batch: _GzcBatchC):
         self._check(gpu_lib().la_gpu_gzip_compress(self._h, C.byref(batch)), "la_gpu_gzip_compress")
+
+    def zip_compress(self, batch: _ZipcBatchC) -> int:
+        """la_gpu_zip_compress; returns LA_OK or LA_ERR_ARG (the segment table is checked on the device), raises otherwise"""
+        rc = gpu_lib().la_gpu_zip_compress(self._h, C.byref(batch))
+        if rc != LA_ERR_ARG:
+            self._check(rc, "la_gpu_zip_compress")
+        return rc
 
     def gzip_decode(self, batch: _GzBatchC):
         self._check(gpu_lib().la_gpu_gzip_decode(self._h, C.byref(batch)), "la_gpu_gzip_decode")

@@ -672,6 +672,42 @@ int la_gpu_gzip_compress(la_gpu_ctx *c, const la_gzc_batch *bt)
 	});
 }
 
+int la_gpu_zip_compress(la_gpu_ctx *c, const la_zipc_batch *bt)
+{
+	if (!c || !bt || !bt->d_out_bytes || (bt->n_segs && (!bt->d_segs || !bt->d_results || !bt->d_out)) || (bt->src_bytes && !bt->d_src))
+		return LA_ERR_ARG;
+	if (bt->chunk_bytes == 0 || bt->chunk_bytes > 49152u || bt->options > LA_GZC_STORED || bt->reserved != 0 ||
+	    bt->n_segs >= 0x80000000u ||	/* (a span names its segment in 31 bits; a launch has at most 2^31 - 1 blocks) */
+	    (bt->src_bytes + bt->chunk_bytes - 1) / bt->chunk_bytes + bt->n_segs > 0x7FFFFFFFull)
+		return LA_ERR_ARG;
+	if (bt->n_segs == 0) {
+		HIPCHK(c, hipMemsetAsync(bt->d_out_bytes, 0, 8, c->stream));
+		return LA_OK;
+	}
+	const uint64_t need = la_zip_compress_ws_bytes(bt->src_bytes, bt->n_segs, bt->chunk_bytes, bt->options);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	uint8_t *ws = (uint8_t *)c->ws;
+	prof_begin(c);
+	prof_range(c, "zip_spans", c->stream, [&] {
+		la_launch_zip_spans(c->stream, bt->src_bytes, bt->d_segs, bt->n_segs, bt->chunk_bytes, bt->options, ws);
+	});
+	/* the segment table lives on the device: its verdict is the one thing the call waits for, before d_out is touched */
+	uint32_t verdict = 0;
+	HIPCHK(c, hipMemcpyAsync(&verdict, ws, 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (verdict != 0)
+		return LA_ERR_ARG;
+	prof_range(c, "zip_compress", c->stream, [&] {
+		la_launch_zip_compress(c->stream, bt->d_src, bt->src_bytes, bt->d_segs, bt->n_segs, bt->chunk_bytes, bt->options,
+		    bt->d_out, bt->out_cap, bt->d_results, bt->d_out_bytes, ws);
+	});
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 int la_gpu_zstd_compress(la_gpu_ctx *c, const la_zstdc_batch *bt)
 {
 	if (!c || !bt || !bt->d_out_bytes || (bt->src_bytes && (!bt->d_src || !bt->d_out)))

@@ -32,6 +32,10 @@
  * non-final stored block, zero bits up to the byte boundary, 00 00 FF FF -- so that the next chunk starts on a byte; a
  * stored chunk is 00 LEN NLEN data.  Matches still end with their chunk, so a chunk's bytes do not depend on its
  * neighbours.  The kernels take the shape as a template parameter: the members build of each is the code it was.
+ *
+ * Third shape (la_gpu_zip_compress, at the end of this file).  The stream shape for a whole write window of ZIP
+ * entries in one call: the chunks are cut per entry segment, not on an even grid, so the four kernels take where a
+ * chunk lies as a second template parameter (dfl_even / dfl_spans below); the even instances are the code they were.
  */
 #include "la_comp_common.h"
 
@@ -111,19 +115,67 @@ __device__ __forceinline__ uint32_t fixed_match(uint32_t len, uint32_t dist, uin
 	return nb;
 }
 
-template <bool STREAM>
+/* Where chunk ci of a launch lies.  dfl_even: chunk ci is src[ci * chunk, ...), the members and stream shapes.  dfl_spans:
+ * a table built on the device says it (la_gpu_zip_compress: no chunk crosses a segment), its length is known on the
+ * device only -- n_chunks is then the bound the launch is sized by -- and a chunk has its own room in `tmp`.  The
+ * kernels take the geometry as a template parameter and the table as their last parameter; with dfl_even the table is
+ * not read and each kernel is the code it was. */
+#define DFL_SPAN_COPY 0x80000000u	/* dfl_span.seg: the segment is LA_ZIPC_STORE, the chunk is copied as it is */
+struct dfl_span {
+	uint64_t off;	/* in src */
+	uint32_t len;	/* 1 .. chunk */
+	uint32_t seg;	/* its segment | DFL_SPAN_COPY */
+};
+struct dfl_span_table {
+	const dfl_span *tab;
+	const uint64_t *tmp_off;	/* [count + 1]: chunk ci's room in tmp, a multiple of 16 at a multiple of 16 */
+	const uint64_t *n;		/* how many there are */
+	const uint64_t *delta;		/* [segments]: pack kernel, what to add to a chunk's scanned offset */
+};
+
+struct dfl_even {
+	uint64_t src_bytes;
+	uint32_t chunk, n_chunks;
+	static constexpr bool SPANS = false;
+	__device__ __forceinline__ dfl_even(uint64_t src_bytes_, uint32_t chunk_, uint32_t n_chunks_, const dfl_span_table &)
+	    : src_bytes(src_bytes_), chunk(chunk_), n_chunks(n_chunks_) {}
+	__device__ __forceinline__ uint32_t count() const { return n_chunks; }
+	__device__ __forceinline__ uint32_t span(uint32_t ci, uint64_t *so) const
+	{
+		*so = (uint64_t)ci * chunk;
+		return (uint32_t)(src_bytes - *so < chunk ? src_bytes - *so : chunk);
+	}
+	__device__ __forceinline__ bool deflates(uint32_t) const { return true; }
+	__device__ __forceinline__ uint64_t tmp_at(uint32_t ci, uint32_t stride) const { return (uint64_t)ci * stride; }
+	__device__ __forceinline__ uint32_t tmp_room(uint32_t, uint32_t stride) const { return stride; }
+};
+
+struct dfl_spans : dfl_span_table {
+	uint32_t chunk;
+	static constexpr bool SPANS = true;
+	__device__ __forceinline__ dfl_spans(uint64_t, uint32_t chunk_, uint32_t, const dfl_span_table &t) : dfl_span_table(t), chunk(chunk_) {}
+	__device__ __forceinline__ uint32_t count() const { return (uint32_t)*n; }
+	__device__ __forceinline__ uint32_t span(uint32_t ci, uint64_t *so) const { *so = tab[ci].off; return tab[ci].len; }
+	__device__ __forceinline__ bool deflates(uint32_t ci) const { return !(tab[ci].seg & DFL_SPAN_COPY); }
+	__device__ __forceinline__ uint64_t tmp_at(uint32_t ci, uint32_t) const { return tmp_off[ci]; }
+	__device__ __forceinline__ uint32_t tmp_room(uint32_t ci, uint32_t) const { return (uint32_t)(tmp_off[ci + 1] - tmp_off[ci]); }
+};
+
+template <bool STREAM, typename GEO>
 __global__ __launch_bounds__(64) void deflate_fixed_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
-    uint32_t chunk, uint32_t n_chunks, uint8_t *__restrict__ tmp, uint32_t tmp_stride, uint32_t *__restrict__ body_len)
+    uint32_t chunk, uint32_t n_chunks, uint8_t *__restrict__ tmp, uint32_t tmp_stride, uint32_t *__restrict__ body_len,
+    const dfl_span_table spans)
 {
+	const GEO geo(src_bytes, chunk, n_chunks, spans);
 	__shared__ uint16_t tab[1u << DFL_HASH_BITS];
 	__shared__ uint32_t stage[72];
 	const uint32_t ci = blockIdx.x, lane = threadIdx.x;
-	if (ci >= n_chunks)
+	if (ci >= geo.count() || !geo.deflates(ci))
 		return;
-	const uint64_t so = (uint64_t)ci * chunk;
-	const uint32_t n = (uint32_t)(src_bytes - so < chunk ? src_bytes - so : chunk);
+	uint64_t so;
+	const uint32_t n = geo.span(ci, &so);
 	const uint8_t *in = src + so;
-	uint32_t *out = (uint32_t *)(void *)(tmp + (uint64_t)ci * tmp_stride);	/* dword aligned: the stride is a multiple of 16 */
+	uint32_t *out = (uint32_t *)(void *)(tmp + geo.tmp_at(ci, tmp_stride));	/* dword aligned: the stride is a multiple of 16 */
 	for (uint32_t i = lane; i < (1u << DFL_HASH_BITS); i += 64)
 		tab[i] = 0;
 	for (uint32_t i = lane; i < 72; i += 64)
@@ -365,11 +417,12 @@ __device__ __forceinline__ uint32_t fixed_lit_len(uint32_t sym) { return sym < 1
  * fixed and the stored block; it writes the smallest (nothing for a stored block: body_len >= n + 5 tells the pack
  * kernel) in a second pass over the tokens, with codes from an LDS table.  In a stream the sizes it compares include
  * the tail, which then follows the end-of-block symbol through the bit stage. */
-template <bool STREAM>
+template <bool STREAM, typename GEO>
 __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
-    uint32_t chunk, uint32_t n_chunks, uint8_t *__restrict__ tmp, uint32_t tmp_stride, uint32_t *__restrict__ body_len,
-    uint32_t *__restrict__ tokbuf)
+    uint32_t chunk, uint32_t n_chunks_, uint8_t *__restrict__ tmp, uint32_t tmp_stride, uint32_t *__restrict__ body_len,
+    uint32_t *__restrict__ tokbuf, const dfl_span_table spans)
 {
+	const GEO geo(src_bytes, chunk, n_chunks_, spans);
 	__shared__ uint16_t tab[1u << DFL_HASH_BITS];
 	__shared__ uint32_t stage[104];
 	__shared__ uint32_t hist[320];		/* [0, 286) literal / length, [288, 318) distance */
@@ -379,12 +432,15 @@ __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__re
 	uint16_t *cls = tab;	/* the header's code-length symbols, symbol | extra bits << 8: the match table is free by then */
 	const uint32_t lane = threadIdx.x;
 	const uint64_t below = ((uint64_t)1 << lane) - 1u;
-	uint32_t *toks = tokbuf + (uint64_t)blockIdx.x * chunk;
+	uint32_t *toks = tokbuf + (uint64_t)blockIdx.x * geo.chunk;
+	const uint32_t n_chunks = geo.count();
 	for (uint32_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
-		const uint64_t so = (uint64_t)ci * chunk;
-		const uint32_t n = (uint32_t)(src_bytes - so < chunk ? src_bytes - so : chunk);
+		if (!geo.deflates(ci))
+			continue;
+		uint64_t so;
+		const uint32_t n = geo.span(ci, &so);
 		const uint8_t *in = src + so;
-		uint32_t *out = (uint32_t *)(void *)(tmp + (uint64_t)ci * tmp_stride);
+		uint32_t *out = (uint32_t *)(void *)(tmp + geo.tmp_at(ci, tmp_stride));
 		__syncthreads();	/* the previous chunk's tables are done with */
 		for (uint32_t i = lane; i < (1u << DFL_HASH_BITS); i += 64)
 			tab[i] = 0;
@@ -549,7 +605,7 @@ __global__ __launch_bounds__(64) void deflate_dynamic_kernel(const uint8_t *__re
 				body_len[ci] = n + 5u;
 			continue;
 		}
-		const auto put = [&](uint32_t i, uint32_t w) { if (i < tmp_stride / 4u) out[i] = w; };	/* (bytes < n + 5 fits) */
+		const auto put = [&](uint32_t i, uint32_t w) { if (i < geo.tmp_room(ci, tmp_stride) / 4u) out[i] = w; };	/* (bytes < n + 5 fits) */
 		uint64_t bp = 0;
 		if (dyn) {
 			dfl_assign_codes<5>(Ls, 15u, code, lane);
@@ -643,36 +699,59 @@ __global__ __launch_bounds__(256) void gz_jobs_kernel(uint64_t src_bytes, uint32
 }
 
 /* a stream's contributions: the chunk's Huffman block with its tail, or the stored block when that is no larger */
+template <typename GEO>
 __global__ __launch_bounds__(256) void dfl_stream_contrib_kernel(uint64_t src_bytes, uint32_t chunk, uint32_t n_chunks,
-    const uint32_t *__restrict__ body_len, uint32_t *__restrict__ contrib)
+    const uint32_t *__restrict__ body_len, uint32_t *__restrict__ contrib, const dfl_span_table spans)
 {
+	const GEO geo(src_bytes, chunk, n_chunks, spans);
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n_chunks)
+	if (i >= geo.count())
 		return;
-	const uint64_t so = (uint64_t)i * chunk;
-	const uint32_t n = (uint32_t)(src_bytes - so < chunk ? src_bytes - so : chunk);
+	uint64_t so;
+	const uint32_t n = geo.span(i, &so);
+	if (!geo.deflates(i)) {	/* (a copied chunk: its bytes) */
+		contrib[i] = n;
+		return;
+	}
 	contrib[i] = body_len[i] < n + 5u ? body_len[i] : n + 5u;
 }
 
 /* STREAM: the bodies alone, back to back (no header, no trailer; `mtime` and `crc` are not read) */
-template <bool STREAM>
+template <bool STREAM, typename GEO>
 __global__ __launch_bounds__(256) void gz_pack_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
-    uint32_t chunk, uint32_t n_chunks, uint32_t mtime, const uint8_t *__restrict__ tmp, uint32_t tmp_stride,
+    uint32_t chunk, uint32_t n_chunks_, uint32_t mtime, const uint8_t *__restrict__ tmp, uint32_t tmp_stride,
     const uint32_t *__restrict__ body_len, const uint32_t *__restrict__ crc, const uint64_t *__restrict__ off,
-    uint8_t *__restrict__ out, uint64_t out_cap, uint64_t *__restrict__ out_bytes)
+    uint8_t *__restrict__ out, uint64_t out_cap, uint64_t *__restrict__ out_bytes, const dfl_span_table spans)
 {
+	const GEO geo(src_bytes, chunk, n_chunks_, spans);
 	const uint32_t ci = blockIdx.x, tid = threadIdx.x;
+	const uint32_t n_chunks = geo.count();
 	if (ci >= n_chunks)
 		return;
-	const uint64_t so = (uint64_t)ci * chunk;
-	const uint32_t n = (uint32_t)(src_bytes - so < chunk ? src_bytes - so : chunk);
+	uint64_t so;
+	const uint32_t n = geo.span(ci, &so);
+	if constexpr (GEO::SPANS) {
+		/* the chunk's place is its scanned offset moved to its segment's stream bytes; the segments' sizes and the total
+		 * are zip_finish_kernel's to report */
+		const uint64_t at = off[ci] + geo.delta[geo.tab[ci].seg & ~DFL_SPAN_COPY];
+		if (at + (off[ci + 1] - off[ci]) > out_cap)
+			return;
+		if (!geo.deflates(ci)) {
+			for (uint32_t i = tid; i < n; i += 256)
+				out[at + i] = src[so + i];
+			return;
+		}
+		out += at - off[ci];
+	}
 	const bool stored = body_len[ci] >= n + 5u;
 	const uint32_t body = stored ? n + 5u : body_len[ci];
 	const uint64_t o = off[ci];
-	if (ci + 1 == n_chunks && tid == 0)
-		*out_bytes = off[n_chunks];
-	if (off[ci + 1] > out_cap)
-		return;
+	if constexpr (!GEO::SPANS) {
+		if (ci + 1 == n_chunks && tid == 0)
+			*out_bytes = off[n_chunks];
+		if (off[ci + 1] > out_cap)
+			return;
+	}
 	constexpr uint32_t HDR = STREAM ? 0u : DFL_HDR;
 	const uint32_t total = DFL_HDR + body + 8u;
 	if (!STREAM && tid == 0) {
@@ -695,7 +774,7 @@ __global__ __launch_bounds__(256) void gz_pack_kernel(const uint8_t *__restrict_
 		for (uint32_t i = tid; i < n; i += 256)
 			b[5 + i] = src[so + i];
 	} else {
-		const uint8_t *t = tmp + (uint64_t)ci * tmp_stride;
+		const uint8_t *t = tmp + geo.tmp_at(ci, tmp_stride);
 		for (uint32_t i = tid; i < body; i += 256)
 			b[i] = t[i];
 	}
@@ -762,21 +841,235 @@ void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 		(void)hipMemsetAsync(d_out_bytes, 0, 8, s);
 		return;
 	}
+	const dfl_span_table none = {};
 	if (options == LA_GZC_STORED)	/* a body length no chunk can have: every chunk comes out stored */
 		(void)hipMemsetAsync(w.body_len, 0xFF, (uint64_t)nc * 4u, s);
 	else if (options == LA_GZC_DYNAMIC)
-		hipLaunchKernelGGL(stream ? deflate_dynamic_kernel<true> : deflate_dynamic_kernel<false>, dim3(nc < DFL_WAVES ? nc : DFL_WAVES),
-		    dim3(64), 0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len, w.toks);
+		hipLaunchKernelGGL((stream ? deflate_dynamic_kernel<true, dfl_even> : deflate_dynamic_kernel<false, dfl_even>),
+		    dim3(nc < DFL_WAVES ? nc : DFL_WAVES), dim3(64), 0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len, w.toks, none);
 	else
-		hipLaunchKernelGGL(stream ? deflate_fixed_kernel<true> : deflate_fixed_kernel<false>, dim3(nc), dim3(64), 0, s, d_src,
-		    src_bytes, chunk, nc, w.tmp, stride, w.body_len);
+		hipLaunchKernelGGL((stream ? deflate_fixed_kernel<true, dfl_even> : deflate_fixed_kernel<false, dfl_even>), dim3(nc), dim3(64),
+		    0, s, d_src, src_bytes, chunk, nc, w.tmp, stride, w.body_len, none);
 	if (stream) {	/* no member, so no CRC32: the caller hashes what it frames (la_gpu_crc32_many) */
-		hipLaunchKernelGGL(dfl_stream_contrib_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.contrib);
+		hipLaunchKernelGGL(dfl_stream_contrib_kernel<dfl_even>, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.contrib, none);
 	} else {
 		hipLaunchKernelGGL(gz_jobs_kernel, dim3((nc + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nc, w.body_len, w.jobs, w.contrib);
 		la_launch_crc32_many(s, d_src, w.jobs, nc, w.crc);
 	}
 	la_launch_scan_u32(s, w.contrib, nc, w.off, w.scan);
-	hipLaunchKernelGGL(stream ? gz_pack_kernel<true> : gz_pack_kernel<false>, dim3(nc), dim3(256), 0, s, d_src, src_bytes, chunk, nc,
-	    mtime, w.tmp, stride, w.body_len, w.crc, w.off, d_out, out_cap, d_out_bytes);
+	hipLaunchKernelGGL((stream ? gz_pack_kernel<true, dfl_even> : gz_pack_kernel<false, dfl_even>), dim3(nc), dim3(256), 0, s, d_src, src_bytes,
+	    chunk, nc, mtime, w.tmp, stride, w.body_len, w.crc, w.off, d_out, out_cap, d_out_bytes, none);
+}
+
+/* ------------------------------------------------------------------ ZIP entries (la_gpu_zip_compress)
+ *
+ * One call, a write window of segments: the stream shape above, cut so that no chunk crosses a segment, with room for
+ * what the host writes around every entry.  The chunks of all segments form one span table, built here from the
+ * segment table (a count per segment, a scan, a fill), so the compress kernels run once over all of them however
+ * small the entries are.  The host does not learn how many spans there are: launches are sized by the bound
+ * ceil(src_bytes / chunk) + n_segs and return early above the scanned total.  A segment's stream bytes are a
+ * difference of the chunk scan, so a segment without a chunk needs none; a second scan over the segments' whole
+ * sizes places them.  No workgroup waits for another.
+ */
+#define ZIPC_FLAGS    (LA_ZIPC_LAST | LA_ZIPC_STORE)
+#define ZIPC_ERR_SEG   1u	/* a segment's fields */
+#define ZIPC_ERR_SPANS 2u	/* more chunks, or more room for their bodies, than segments that do not overlap can need */
+
+struct zipc_ws {
+	uint32_t *err;			/* one word, first in the workspace: la_zip_compress_check reads it */
+	uint32_t *cnt;			/* [n_segs] chunks of a segment */
+	uint64_t *span_off;		/* [n_segs + 1] their scan */
+	dfl_span *spans;		/* [nb] */
+	uint32_t *need, *body_len, *contrib;	/* [nb] */
+	uint64_t *tmp_off, *off;	/* [nb + 1] scans of need, contrib */
+	uint32_t *seg_bytes, *crc;	/* [n_segs] */
+	uint64_t *seg_off;		/* [n_segs + 1] */
+	uint64_t *delta;		/* [n_segs] */
+	la_hash_job *jobs;		/* [n_segs] */
+	uint32_t *toks;
+	uint8_t *tmp;
+	void *scan;
+};
+
+static uint64_t zipc_spans_bound(uint64_t src_bytes, uint32_t n_segs, uint32_t chunk) { return (src_bytes + chunk - 1) / chunk + n_segs; }
+/* room for the Huffman bodies: every chunk takes dfl_body_bound() of its length rounded up to 16, at most 9/8 n + 32 */
+static uint64_t zipc_tmp_cap(uint64_t src_bytes, uint64_t nb) { return (((src_bytes * 9u + 7u) >> 3) + 32u * nb + 15u) & ~(uint64_t)15u; }
+
+static uint64_t zipc_carve(zipc_ws *w, uint8_t *base, uint64_t src_bytes, uint32_t n_segs, uint32_t chunk, uint32_t options)
+{
+	const uint64_t nb = zipc_spans_bound(src_bytes, n_segs, chunk);
+	la_carve c = { base, 0 };
+	w->err = c.take<uint32_t>(4);
+	w->cnt = c.take<uint32_t>(n_segs);
+	w->span_off = c.take<uint64_t>((uint64_t)n_segs + 1);
+	w->spans = c.take<dfl_span>(nb, 16);
+	w->need = c.take<uint32_t>(nb);
+	w->body_len = c.take<uint32_t>(nb);
+	w->contrib = c.take<uint32_t>(nb);
+	w->tmp_off = c.take<uint64_t>(nb + 1);
+	w->off = c.take<uint64_t>(nb + 1);
+	w->seg_bytes = c.take<uint32_t>(n_segs);
+	w->crc = c.take<uint32_t>(n_segs);
+	w->seg_off = c.take<uint64_t>((uint64_t)n_segs + 1);
+	w->delta = c.take<uint64_t>(n_segs);
+	w->jobs = c.take<la_hash_job>(n_segs, 16);
+	w->toks = c.take<uint32_t>(options == LA_GZC_DYNAMIC ? (nb < DFL_WAVES ? nb : DFL_WAVES) * chunk : 0, 16);
+	w->tmp = c.take<uint8_t>(options == LA_GZC_STORED ? 0 : zipc_tmp_cap(src_bytes, nb), 16);
+	w->scan = c.take<uint8_t>(0, 256);
+	return c.off;
+}
+
+uint64_t la_zip_compress_ws_bytes(uint64_t src_bytes, uint32_t n_segs, uint32_t chunk, uint32_t options)
+{
+	if (chunk == 0)
+		return 0;
+	const uint64_t nb = zipc_spans_bound(src_bytes, n_segs, chunk);
+	zipc_ws w;
+	return zipc_carve(&w, nullptr, src_bytes, n_segs, chunk, options) + la_scan_scratch_bytes((uint32_t)(nb > n_segs ? nb : n_segs));
+}
+
+extern "C" uint64_t la_gpu_zip_compress_workspace_bytes(uint64_t src_bytes, uint32_t n_segs, uint32_t chunk)
+{
+	return la_zip_compress_ws_bytes(src_bytes, n_segs, chunk, LA_GZC_DYNAMIC);
+}
+
+extern "C" uint64_t la_gpu_zip_compress_bound(uint64_t src_bytes, uint32_t n_segs, uint32_t chunk, uint64_t gap_bytes_total)
+{
+	if (chunk == 0)
+		return 0;
+	/* a chunk that does not shrink is stored: 5 bytes of block header; 03 00 behind a last segment */
+	return src_bytes + zipc_spans_bound(src_bytes, n_segs, chunk) * 5u + (uint64_t)n_segs * 2u + gap_bytes_total + 64u;
+}
+
+/* one thread per segment: its fields checked, its chunks counted, its CRC32 job */
+__global__ __launch_bounds__(256) void zip_count_kernel(const la_zipc_seg *__restrict__ segs, uint32_t n_segs,
+    uint64_t src_bytes, uint32_t chunk, uint32_t *__restrict__ cnt, la_hash_job *__restrict__ jobs, uint32_t *err)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_segs)
+		return;
+	const la_zipc_seg g = segs[i];
+	bool bad = (g.flags & ~ZIPC_FLAGS) != 0 || g.reserved != 0 || g.src_len >= 0x80000000u || g.src_off > src_bytes ||
+	    g.src_len > src_bytes - g.src_off;
+	const uint32_t c = bad ? 0u : (uint32_t)(((uint64_t)g.src_len + chunk - 1) / chunk);
+	/* the segment's whole size is a 32-bit term of the second scan */
+	bad = bad || (uint64_t)g.gap_before + g.gap_after + g.src_len + (uint64_t)c * 5u + 2u > 0xFFFFFFFFull;
+	cnt[i] = bad ? 0u : c;
+	jobs[i].off = bad ? 0 : g.src_off; jobs[i].len = bad ? 0u : g.src_len; jobs[i].seed = g.crc_seed;
+	if (bad)
+		atomicOr(err, ZIPC_ERR_SEG);
+}
+
+/* one thread per span: its segment is the one whose scanned range holds it */
+__global__ __launch_bounds__(256) void zip_fill_kernel(const la_zipc_seg *__restrict__ segs, uint32_t n_segs, uint32_t chunk,
+    const uint64_t *__restrict__ span_off, uint32_t nb, dfl_span *__restrict__ spans, uint32_t *__restrict__ need, uint32_t *err)
+{
+	const uint32_t ci = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint64_t total = span_off[n_segs];
+	if (ci == 0 && total > nb)
+		atomicOr(err, ZIPC_ERR_SPANS);
+	if (ci >= nb || ci >= total)
+		return;
+	uint32_t lo = 0, hi = n_segs;	/* the first segment whose range starts behind ci lies in (lo, hi] */
+	while (hi - lo > 1u) {
+		const uint32_t mid = lo + (hi - lo) / 2u;
+		if (span_off[mid] > ci) hi = mid; else lo = mid;
+	}
+	const la_zipc_seg g = segs[lo];
+	const uint64_t k = (uint64_t)(ci - span_off[lo]) * chunk;
+	dfl_span sp;
+	sp.off = g.src_off + k;
+	sp.len = (uint32_t)(g.src_len - k < chunk ? g.src_len - k : chunk);
+	sp.seg = lo | ((g.flags & LA_ZIPC_STORE) ? DFL_SPAN_COPY : 0u);
+	spans[ci] = sp;
+	need[ci] = (g.flags & LA_ZIPC_STORE) ? 0u : (dfl_body_bound(sp.len) + 15u) & ~15u;
+}
+
+__global__ void zip_room_kernel(const uint64_t *__restrict__ tmp_off, uint32_t nb, uint64_t tmp_cap, uint32_t *err)
+{
+	if (tmp_off[nb] > tmp_cap)
+		atomicOr(err, ZIPC_ERR_SPANS);
+}
+
+/* a segment's whole size: gap, stream bytes (its chunks' share of the chunk scan, and 03 00 where the entry ends), gap */
+__device__ __forceinline__ uint32_t zip_stream_bytes(const la_zipc_seg &g, const uint64_t *span_off, const uint64_t *off, uint32_t i)
+{
+	const uint32_t body = (uint32_t)(off[span_off[i + 1]] - off[span_off[i]]);
+	return body + ((g.flags & ZIPC_FLAGS) == LA_ZIPC_LAST ? 2u : 0u);
+}
+
+__global__ __launch_bounds__(256) void zip_seg_bytes_kernel(const la_zipc_seg *__restrict__ segs, uint32_t n_segs,
+    const uint64_t *__restrict__ span_off, const uint64_t *__restrict__ off, uint32_t *__restrict__ seg_bytes)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_segs)
+		return;
+	const la_zipc_seg g = segs[i];
+	seg_bytes[i] = g.gap_before + zip_stream_bytes(g, span_off, off, i) + g.gap_after;
+}
+
+/* results, the end of an entry's stream, where the pack kernel puts a segment's chunks, the total */
+__global__ __launch_bounds__(256) void zip_finish_kernel(const la_zipc_seg *__restrict__ segs, uint32_t n_segs,
+    const uint64_t *__restrict__ span_off, const uint64_t *__restrict__ off, const uint64_t *__restrict__ seg_off,
+    const uint32_t *__restrict__ crc, uint64_t *__restrict__ delta, la_zipc_result *__restrict__ results,
+    uint8_t *__restrict__ out, uint64_t out_cap, uint64_t *__restrict__ out_bytes)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_segs)
+		return;
+	const la_zipc_seg g = segs[i];
+	const uint32_t len = zip_stream_bytes(g, span_off, off, i);
+	const uint64_t o = seg_off[i] + g.gap_before;
+	delta[i] = o - off[span_off[i]];
+	results[i].out_off = o; results[i].out_len = len; results[i].crc32 = crc[i];
+	if ((g.flags & ZIPC_FLAGS) == LA_ZIPC_LAST && o + len <= out_cap) {	/* the empty final fixed block */
+		out[o + len - 2u] = 0x03;
+		out[o + len - 1u] = 0x00;
+	}
+	if (i == 0)
+		*out_bytes = seg_off[n_segs];
+}
+
+/* first half of the call: the span table and the checks whose answer the host waits for (4 bytes at the start of ws) */
+void la_launch_zip_spans(hipStream_t s, uint64_t src_bytes, const la_zipc_seg *d_segs, uint32_t n_segs, uint32_t chunk,
+    uint32_t options, uint8_t *ws)
+{
+	const uint32_t nb = (uint32_t)zipc_spans_bound(src_bytes, n_segs, chunk);
+	zipc_ws w;
+	zipc_carve(&w, ws, src_bytes, n_segs, chunk, options);
+	(void)hipMemsetAsync(w.err, 0, 16, s);
+	(void)hipMemsetAsync(w.need, 0, (uint64_t)nb * 4u, s);
+	hipLaunchKernelGGL(zip_count_kernel, dim3((n_segs + 255) / 256), dim3(256), 0, s, d_segs, n_segs, src_bytes, chunk, w.cnt, w.jobs, w.err);
+	la_launch_scan_u32(s, w.cnt, n_segs, w.span_off, w.scan);
+	hipLaunchKernelGGL(zip_fill_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, d_segs, n_segs, chunk, w.span_off, nb, w.spans, w.need, w.err);
+	la_launch_scan_u32(s, w.need, nb, w.tmp_off, w.scan);
+	hipLaunchKernelGGL(zip_room_kernel, dim3(1), dim3(1), 0, s, w.tmp_off, nb, options == LA_GZC_STORED ? ~(uint64_t)0 : zipc_tmp_cap(src_bytes, nb), w.err);
+}
+
+/* second half, for a table that passed: compress, place, pack */
+void la_launch_zip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_zipc_seg *d_segs, uint32_t n_segs,
+    uint32_t chunk, uint32_t options, uint8_t *d_out, uint64_t out_cap, la_zipc_result *d_results, uint64_t *d_out_bytes,
+    uint8_t *ws)
+{
+	const uint32_t nb = (uint32_t)zipc_spans_bound(src_bytes, n_segs, chunk);
+	zipc_ws w;
+	zipc_carve(&w, ws, src_bytes, n_segs, chunk, options);
+	const dfl_span_table geo = { w.spans, w.tmp_off, w.span_off + n_segs, w.delta };
+	if (options == LA_GZC_STORED)
+		(void)hipMemsetAsync(w.body_len, 0xFF, (uint64_t)nb * 4u, s);
+	else if (options == LA_GZC_DYNAMIC)
+		hipLaunchKernelGGL((deflate_dynamic_kernel<true, dfl_spans>), dim3(nb < DFL_WAVES ? nb : DFL_WAVES), dim3(64), 0, s, d_src, src_bytes,
+		    chunk, nb, w.tmp, 0u, w.body_len, w.toks, geo);
+	else
+		hipLaunchKernelGGL((deflate_fixed_kernel<true, dfl_spans>), dim3(nb), dim3(64), 0, s, d_src, src_bytes, chunk, nb, w.tmp, 0u, w.body_len, geo);
+	(void)hipMemsetAsync(w.contrib, 0, (uint64_t)nb * 4u, s);	/* (the scan runs over the bound) */
+	hipLaunchKernelGGL(dfl_stream_contrib_kernel<dfl_spans>, dim3((nb + 255) / 256), dim3(256), 0, s, src_bytes, chunk, nb, w.body_len, w.contrib, geo);
+	la_launch_scan_u32(s, w.contrib, nb, w.off, w.scan);
+	hipLaunchKernelGGL(zip_seg_bytes_kernel, dim3((n_segs + 255) / 256), dim3(256), 0, s, d_segs, n_segs, w.span_off, w.off, w.seg_bytes);
+	la_launch_scan_u32(s, w.seg_bytes, n_segs, w.seg_off, w.scan);
+	la_launch_crc32_many(s, d_src, w.jobs, n_segs, w.crc);
+	hipLaunchKernelGGL(zip_finish_kernel, dim3((n_segs + 255) / 256), dim3(256), 0, s, d_segs, n_segs, w.span_off, w.off, w.seg_off,
+	    w.crc, w.delta, d_results, d_out, out_cap, d_out_bytes);
+	hipLaunchKernelGGL((gz_pack_kernel<true, dfl_spans>), dim3(nb), dim3(256), 0, s, d_src, src_bytes, chunk, nb, 0u, w.tmp, 0u,
+	    w.body_len, (const uint32_t *)nullptr, w.off, d_out, out_cap, d_out_bytes, geo);
 }

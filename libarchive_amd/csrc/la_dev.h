@@ -557,6 +557,14 @@ void la_launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 void la_launch_gzip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t chunk, uint32_t mtime,
     uint32_t options, uint32_t framing, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);	/* LA_GZC_*, LA_GZC_FRAME_* */
 uint64_t la_gzip_compress_ws_bytes(uint64_t src_bytes, uint32_t chunk, uint32_t options);	/* LA_GZC_* */
+/* la_gpu_zip_compress in two halves: the span table with its checks, whose verdict is the first word of `ws` (0 = the
+ * table is good), then everything that writes d_out */
+void la_launch_zip_spans(hipStream_t s, uint64_t src_bytes, const la_zipc_seg *d_segs, uint32_t n_segs, uint32_t chunk,
+    uint32_t options, uint8_t *ws);
+void la_launch_zip_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_zipc_seg *d_segs, uint32_t n_segs,
+    uint32_t chunk, uint32_t options, uint8_t *d_out, uint64_t out_cap, la_zipc_result *d_results, uint64_t *d_out_bytes,
+    uint8_t *ws);
+uint64_t la_zip_compress_ws_bytes(uint64_t src_bytes, uint32_t n_segs, uint32_t chunk, uint32_t options);
 
 /* la_inflate.hip */
 void la_launch_inflate(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,

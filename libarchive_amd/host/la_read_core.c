@@ -72,6 +72,19 @@ void archive_entry_set_mtime(struct archive_entry *e, int64_t t, long ns)
 	e->mtime = t;
 	e->mtime_set = 1;
 }
+/* the write side builds its own entries (archive_entry.c archive_entry_new / _clear / _free) */
+struct archive_entry *archive_entry_new(void) { return calloc(1, sizeof(struct archive_entry)); }
+struct archive_entry *archive_entry_clear(struct archive_entry *e)
+{
+	if (e)
+		memset(e, 0, sizeof(*e));
+	return e;
+}
+void archive_entry_free(struct archive_entry *e) { free(e); }
+void archive_entry_set_size(struct archive_entry *e, int64_t s) { e->size = s; e->size_set = 1; }
+void archive_entry_unset_size(struct archive_entry *e) { e->size = 0; e->size_set = 0; }
+void archive_entry_set_filetype(struct archive_entry *e, unsigned type) { e->filetype = type & AE_IFMT; }
+void archive_entry_set_perm(struct archive_entry *e, unsigned perm) { e->mode = perm & 07777u; }
 
 /* ------------------------------------------------------------------ object */
 

@@ -33,11 +33,12 @@
  * 03 00 and writes the trailer.  For this repository's read filter such a member is one serial unit, which is why
  * many members stay the default.
  *
- * The write core below is the minimum the filters need outside libarchive: archive_write_new,
+ * The write core below is the minimum the filters and formats need outside libarchive: archive_write_new,
  * _add_filter_lz4, _set_format_raw (one entry, data passed through: archive_write_set_format_raw.c),
- * _set_filter_option, _open_memory / _open_fd, _header, _data, _close, _free.  Next to it, the write window
- * (la_write_private.h) that the lz4, gzip and zstd filters share: each filter adds its output bound and its one
- * compress call.
+ * _set_filter_option, _set_format_option, _open_memory / _open_fd, _header, _data, _finish_entry, _close, _free.  A
+ * format is the reference's set of hooks on the handle (la_write_private.h); the raw format is one here, the ZIP
+ * format another in la_write_zip.c, which this file does not know.  Next to it, the write window that the lz4, gzip
+ * and zstd filters and the ZIP format share: each adds its output bound and its one compress call.
  */
 #include <errno.h>
 #include <stdint.h>
@@ -51,15 +52,6 @@
 #include "la_write_private.h"
 #include "../../include/la_gpu.h"
 #include "../../include/la_host.h"
-
-struct archive_write {
-	struct archive archive;		/* first: the error helpers of la_read_core.c work on it */
-	struct archive_write_filter *filter_first, *filter_last;
-	/* client */
-	uint8_t *mem; size_t mem_cap, *mem_used;
-	int fd;
-	int opened, format_raw, entries, closed;
-};
 
 /* ------------------------------------------------------------------ minimal write core */
 
@@ -124,12 +116,93 @@ struct archive *archive_write_new(void)
 	return (struct archive *)a;
 }
 
+int __archive_write_output(struct archive_write *a, const void *buf, size_t len)
+{
+	return __archive_write_filter(a->filter_first, buf, len);
+}
+
+/* the raw format (archive_write_set_format_raw.c): one entry, its data passed through; its only state is the
+ * number of headers seen */
+static int raw_write_header(struct archive_write *a, struct archive_entry *entry)
+{
+	int *entries = a->format_data;
+	(void)entry;
+	if ((*entries)++ > 0) {
+		archive_set_error(&a->archive, ERANGE, "Raw format only supports one entry per archive");	/* archive_write_set_format_raw.c:80-84 */
+		return ARCHIVE_FATAL;
+	}
+	return ARCHIVE_OK;
+}
+
+static ssize_t raw_write_data(struct archive_write *a, const void *buff, size_t s)
+{
+	int r = __archive_write_output(a, buff, s);
+	return r == ARCHIVE_OK ? (ssize_t)s : r;
+}
+
+static int raw_free(struct archive_write *a)
+{
+	free(a->format_data);
+	a->format_data = NULL;
+	return ARCHIVE_OK;
+}
+
 int archive_write_set_format_raw(struct archive *_a)
 {
-	((struct archive_write *)_a)->format_raw = 1;
+	struct archive_write *a = (struct archive_write *)_a;
+	if (a->format_free != NULL)	/* another format was registered (archive_write_set_format_raw.c:54-56) */
+		a->format_free(a);
+	a->format_data = calloc(1, sizeof(int));
+	if (a->format_data == NULL) {
+		archive_set_error(_a, ENOMEM, "Can't allocate raw data");
+		return ARCHIVE_FATAL;
+	}
+	a->format_name = "raw";
+	a->format_init = NULL;
+	a->format_options = NULL;
+	a->format_finish_entry = NULL;
+	a->format_write_header = raw_write_header;
+	a->format_write_data = raw_write_data;
+	a->format_close = NULL;
+	a->format_free = raw_free;
 	_a->archive_format = ARCHIVE_FORMAT_RAW;
 	_a->archive_format_name = "raw";
 	return ARCHIVE_OK;
+}
+
+/* archive_write_set_options.c:38-45, :73-88 with _archive_set_option (archive_options.c:38-72): one option for the
+ * format; `m` names it or is NULL */
+int archive_write_set_format_option(struct archive *_a, const char *m, const char *o, const char *v)
+{
+	struct archive_write *a = (struct archive_write *)_a;
+	const char *mp = (m != NULL && m[0] != '\0') ? m : NULL;
+	const char *op = (o != NULL && o[0] != '\0') ? o : NULL;
+	const char *vp = (v != NULL && v[0] != '\0') ? v : NULL;
+	int r;
+	if (op == NULL && vp == NULL)
+		return ARCHIVE_OK;
+	if (op == NULL) {
+		archive_set_error(_a, ARCHIVE_ERRNO_MISC, "Empty option");
+		return ARCHIVE_FAILED;
+	}
+	if (a->format_name == NULL)
+		r = mp == NULL ? ARCHIVE_FAILED : ARCHIVE_WARN - 1;
+	else if (mp != NULL && strcmp(mp, a->format_name) != 0)
+		r = ARCHIVE_WARN - 1;
+	else if (a->format_options == NULL)
+		r = ARCHIVE_WARN;
+	else
+		r = a->format_options(a, op, vp);
+	if (r == ARCHIVE_WARN - 1) {
+		archive_set_error(_a, ARCHIVE_ERRNO_MISC, "Unknown module name: `%s'", mp);
+		return ARCHIVE_FAILED;
+	}
+	if (r == ARCHIVE_WARN) {
+		archive_set_error(_a, ARCHIVE_ERRNO_MISC, "Undefined option: `%s%s%s%s%s%s'", vp ? "" : "!", mp ? mp : "", mp ? ":" : "",
+		    op, vp ? "=" : "", vp ? vp : "");
+		return ARCHIVE_FAILED;
+	}
+	return r;
 }
 
 int archive_write_set_filter_option(struct archive *_a, const char *m, const char *o, const char *v)
@@ -172,7 +245,7 @@ static int write_open_common(struct archive_write *a)
 	}
 	a->opened = 1;
 	a->archive.state = LA_STATE_HEADER;
-	return ARCHIVE_OK;
+	return a->format_init ? a->format_init(a) : ARCHIVE_OK;	/* archive_write.c archive_write_client_open's last step */
 }
 
 int archive_write_open_memory(struct archive *_a, void *buff, size_t size, size_t *used)
@@ -190,31 +263,43 @@ int archive_write_open_fd(struct archive *_a, int fd)
 	return write_open_common(a);
 }
 
-int archive_write_header(struct archive *_a, struct archive_entry *entry)
+int archive_write_finish_entry(struct archive *_a)	/* archive_write.c:798-812 */
 {
 	struct archive_write *a = (struct archive_write *)_a;
-	(void)entry;
-	if (!a->opened || !a->format_raw) {
+	int ret = ARCHIVE_OK;
+	if (_a->state == LA_STATE_DATA && a->format_finish_entry != NULL)
+		ret = a->format_finish_entry(a);
+	if (_a->state == LA_STATE_DATA)
+		_a->state = LA_STATE_HEADER;
+	return ret;
+}
+
+int archive_write_header(struct archive *_a, struct archive_entry *entry)	/* archive_write.c:734-796 */
+{
+	struct archive_write *a = (struct archive_write *)_a;
+	if (!a->opened || a->format_write_header == NULL) {
 		archive_set_error(_a, ARCHIVE_ERRNO_MISC, "No format defined (this slice writes the raw format)");
 		return ARCHIVE_FATAL;
 	}
-	if (a->entries++ > 0) {
-		archive_set_error(_a, ERANGE, "Raw format only supports one entry per archive");	/* archive_write_set_format_raw.c:80-84 */
-		return ARCHIVE_FATAL;
-	}
+	/* "retry" and "fatal" get returned immediately (:751-758) */
+	int ret = archive_write_finish_entry(_a);
+	if (ret < ARCHIVE_OK && ret != ARCHIVE_WARN)
+		return ret;
+	const int r2 = a->format_write_header(a, entry);
+	if (r2 == ARCHIVE_FAILED || r2 == ARCHIVE_FATAL)
+		return r2;
 	_a->state = LA_STATE_DATA;
-	return ARCHIVE_OK;
+	return r2 < ret ? r2 : ret;
 }
 
 ssize_t archive_write_data(struct archive *_a, const void *buff, size_t s)
 {
 	struct archive_write *a = (struct archive_write *)_a;
-	if (!a->opened || a->entries == 0) {
+	if (!a->opened || _a->state != LA_STATE_DATA || a->format_write_data == NULL) {
 		archive_set_error(_a, ARCHIVE_ERRNO_MISC, "archive_write_data before archive_write_header");
 		return ARCHIVE_FATAL;
 	}
-	int r = __archive_write_filter(a->filter_first, buff, s);
-	return r == ARCHIVE_OK ? (ssize_t)s : r;
+	return a->format_write_data(a, buff, s);
 }
 
 int archive_write_close(struct archive *_a)
@@ -223,6 +308,14 @@ int archive_write_close(struct archive *_a)
 	int rc = ARCHIVE_OK;
 	if (a->closed || !a->opened)
 		return ARCHIVE_OK;
+	/* the last entry, then the archive, then the filters (archive_write.c:631-647) */
+	if (_a->state == LA_STATE_DATA && a->format_finish_entry != NULL)
+		rc = a->format_finish_entry(a);
+	if (a->format_close != NULL) {
+		int r = a->format_close(a);
+		if (r < rc)
+			rc = r;
+	}
 	for (struct archive_write_filter *f = a->filter_first; f; f = f->next_filter) {
 		if (f->close) {
 			int r = f->close(f);
@@ -242,6 +335,8 @@ int archive_write_free(struct archive *_a)
 	if (!a)
 		return ARCHIVE_OK;
 	int rc = archive_write_close(_a);
+	if (a->format_free != NULL)
+		a->format_free(a);
 	struct archive_write_filter *f = a->filter_first;
 	while (f) {
 		struct archive_write_filter *n = f->next_filter;
@@ -293,6 +388,11 @@ int la_write_window_flush(struct archive_write_filter *f, int force_empty)
 		return la_write_window_fail(f, "device to host copy");
 	w->len = 0;
 	w->wrote_anything = 1;
+	if (w->patch) {
+		int r = w->patch(f, w, total);
+		if (r != ARCHIVE_OK)
+			return r;
+	}
 	return __archive_write_filter(f->next_filter, w->out, (size_t)total);
 }
 
