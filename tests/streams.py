@@ -184,6 +184,69 @@ def lz4_dependent_frame(chunks):
     return lz4_frame(blocks, flg=0x44)
 
 
+def lz4_parse_block(payload):
+    """An LZ4 block as written (lz4 Block Format): (sequences, extensions).  sequences = [(literal bytes, offset,
+    match length)], the last one with offset 0 and match length 0 (a block ends in literals); extensions[i] =
+    ((n, last), (n, last)): how many length-extension bytes the literal length and the match length of sequence i
+    took and the value of the last of them (None without any).  Raises ValueError on a block that does not parse to
+    its last byte; it does NOT judge offsets or the end-of-block rules -- lz4_execute and the tests do."""
+    b, p, n = bytes(payload), 0, len(payload)
+    seqs, exts = [], []
+
+    def extension(p):
+        k = 0
+        while True:
+            if p + k >= n:
+                raise ValueError("length extension runs past the block")
+            k += 1
+            if b[p + k - 1] != 255:
+                return k, 255 * (k - 1) + b[p + k - 1], b[p + k - 1]
+
+    while True:
+        if p >= n:
+            raise ValueError("no token at %d" % p)
+        tok = b[p]
+        p += 1
+        ll, le = tok >> 4, (0, None)
+        if ll == 15:
+            k, v, last = extension(p)
+            p, ll, le = p + k, 15 + v, (k, last)
+        if p + ll > n:
+            raise ValueError("literals run past the block")
+        lit = b[p:p + ll]
+        p += ll
+        if p == n:
+            if tok & 15:
+                raise ValueError("the last token names a match")
+            seqs.append((lit, 0, 0))
+            exts.append((le, (0, None)))
+            return seqs, exts
+        if p + 2 > n:
+            raise ValueError("truncated offset")
+        off = b[p] | (b[p + 1] << 8)
+        p += 2
+        ml, me = tok & 15, (0, None)
+        if ml == 15:
+            k, v, last = extension(p)
+            p, ml, me = p + k, 15 + v, (k, last)
+        seqs.append((lit, off, ml + 4))
+        exts.append((le, me))
+
+
+def lz4_execute(seqs):
+    """the bytes a sequence list regenerates (offsets must reach produced bytes: AssertionError otherwise)"""
+    out = bytearray()
+    for lit, off, ml in seqs:
+        out += lit
+        if ml:
+            assert 1 <= off <= len(out), "offset %d with %d bytes produced" % (off, len(out))
+            if off >= ml:
+                out += out[len(out) - off:len(out) - off + ml]
+            else:
+                out += (bytes(out[len(out) - off:]) * (ml // off + 1))[:ml]
+    return bytes(out)
+
+
 # ---------------------------------------------------------------- gzip crafted
 
 def gz_member(data, level=6, name=None, comment=None, extra=None, hcrc=False, mtime=0, strategy=zlib.Z_DEFAULT_STRATEGY,

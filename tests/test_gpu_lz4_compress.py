@@ -1,7 +1,8 @@
 """Device LZ4 compression (la_gpu_lz4_compress): the frames it writes must decode to the input
 with everything that reads the format -- the oracle's filter (a port of the reference reader, with every XXH32
-check), the system's liblz4 block by block, and this repository's own device decoder -- and must obey the
-format's end-of-block rules.  The compressed bytes themselves are not liblz4's (an LZ4 stream is not unique)."""
+check), the system's liblz4 block by block, and this repository's own device decoder.  The format's end-of-block
+rules, about which LZ4_decompress_safe is lenient, are checked on the blocks as written in
+test_gpu_lz4_compress_edges.py.  The compressed bytes themselves are not liblz4's (an LZ4 stream is not unique)."""
 import ctypes as C
 import random
 import struct
