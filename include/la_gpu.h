@@ -310,7 +310,11 @@ typedef struct la_zstd_frame {
 
 typedef struct la_zstd_result {
 	uint32_t status;	/* LA_ST_* */
-	uint32_t reserved;
+	union {
+		uint32_t path;		/* who gave the verdict: 0 the wave or lane kernel (always, without LA_ZSTD_OPT_BLOCK_PARALLEL),
+					 * 1 the block path */
+		uint32_t reserved;	/* the field's name before it had a meaning: same place, kept for sources that read it */
+	};
 	uint64_t out_len;	/* bytes produced (0 on error) */
 } la_zstd_result;
 
@@ -327,6 +331,12 @@ typedef struct la_zstd_batch {
 
 #define LA_ZSTD_OPT_NO_VERIFY 1u	/* skip the content checksum */
 #define LA_ZSTD_OPT_LANE_KERNEL 2u	/* first-generation kernel, one LANE per frame (default: one wave per frame); same results, kept as a cross-check */
+/* Decode the BLOCKS of every frame in parallel (a wave per block, matches resolved by pointer jumping; la_zstd_blocks.hip).
+ * The block path only ever reports success (result.path = 1): a frame it cannot finish -- damaged, truncated, too small
+ * a slot, wrong checksum, more blocks / sequences / literals than its workspace rules hold -- is decoded by the wave
+ * kernel (or the lane kernel, with LA_ZSTD_OPT_LANE_KERNEL) behind it in the same call, with path = 0: statuses and
+ * bytes are those of options 0 and 2. */
+#define LA_ZSTD_OPT_BLOCK_PARALLEL 4u
 
 uint64_t la_gpu_zstd_workspace_bytes(uint32_t n_frames);
 int      la_gpu_zstd_decode(la_gpu_ctx *ctx, const la_zstd_batch *batch);

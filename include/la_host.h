@@ -154,6 +154,7 @@ void     la_gz_pieces_free(la_gz_pieces *x);
 uint64_t la_gz_next_marker(const uint8_t *img, uint64_t len, uint64_t from);
 /* LA_GZIP_FLUSH_POINTS=1 or =chain: the gzip read filter and its bid policy look for flush points */
 int      la_gz_flush_points_enabled(void);
+int      la_zstd_blocks_enabled(void);	/* LA_ZSTD_BLOCKS=1: one zstd frame decodes block-parallel (LA_ZSTD_OPT_BLOCK_PARALLEL) */
 /* LA_GZIP_FLUSH_POINTS=chain: the pieces may depend on each other, the filter decodes them with LA_GZ_OPT_CHAIN */
 int      la_gz_flush_points_chain(void);
 

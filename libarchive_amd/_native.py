@@ -82,6 +82,7 @@ class _ZstdcBatchC(C.Structure):
 
 
 LA_ZSTDC_CHECKSUM, LA_ZSTDC_RAW_LITERALS = 1, 2
+LA_ZSTD_OPT_NO_VERIFY, LA_ZSTD_OPT_LANE_KERNEL, LA_ZSTD_OPT_BLOCK_PARALLEL = 1, 2, 4     # la_zstd_batch.options
 
 
 class _GzcFramingC(C.Union):     # the header's anonymous union: `reserved` is the field's earlier name

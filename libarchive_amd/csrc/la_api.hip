@@ -459,15 +459,26 @@ int la_gpu_zstd_decode(la_gpu_ctx *c, const la_zstd_batch *bt)
 		return LA_ERR_ARG;
 	if (bt->n_frames && (!bt->d_src || !bt->d_frames || !bt->d_dst || !bt->d_results))
 		return LA_ERR_ARG;
-	const uint64_t need = la_zstd_workspace_bytes(bt->n_frames);
+	/* LA_ZSTD_OPT_BLOCK_PARALLEL: the block path in front, its workspace behind the frame kernels'; coordinates are
+	 * 32-bit as in the gzip chain, so a longer d_dst goes to the frame kernels whole */
+	const bool blocks = (bt->options & LA_ZSTD_OPT_BLOCK_PARALLEL) && bt->n_frames && bt->dst_cap <= 0xFFFFFFFFull;
+	const uint64_t ws_frames = (la_zstd_workspace_bytes(bt->n_frames) + 255) & ~255ull;
+	const uint64_t need = ws_frames + (blocks ? la_zstd_blocks_workspace_bytes(bt->n_frames, bt->src_bytes, bt->dst_cap) : 0);
 	if (need > c->ws_bytes) {
 		int rc = la_gpu_reserve(c, need);
 		if (rc != LA_OK) return rc;
 	}
 	prof_begin(c);
+	uint8_t *ws_blocks = (uint8_t *)c->ws + ws_frames;
+	if (blocks)
+		prof_range(c, "zstd_blocks", c->stream, [&] {
+			la_launch_zstd_blocks(c->stream, bt->d_src, bt->src_bytes, bt->d_frames, bt->n_frames, bt->d_dst, bt->dst_cap,
+			    bt->d_results, ws_blocks, bt->options);
+		});
+	/* behind it, the frames it handed back (without the option: every frame) */
 	prof_range(c, "zstd_frames", c->stream, [&] {
 		la_launch_zstd_frames(c->stream, bt->d_src, bt->src_bytes, bt->d_frames, bt->n_frames, bt->d_dst, bt->dst_cap,
-		    bt->d_results, (uint8_t *)c->ws, bt->options);
+		    bt->d_results, (uint8_t *)c->ws, bt->options, blocks ? la_zstd_blocks_todo(ws_blocks) : NULL);
 	});
 	HIPCHK(c, hipGetLastError());
 	return LA_OK;

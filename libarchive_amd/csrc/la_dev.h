@@ -543,6 +543,13 @@ void la_launch_lz4_expand_inorder(hipStream_t s, const la_expand_job &j);
 /* la_zstd.hip */
 uint64_t la_zstd_workspace_bytes(uint32_t n_frames);
 void la_launch_zstd_frames(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_zstd_frame *d_frames, uint32_t n,
+    uint8_t *d_dst, uint64_t dst_cap, la_zstd_result *d_results, uint8_t *ws, uint32_t options,
+    const uint32_t *d_only /* [n] nonzero = decode this frame; NULL = every frame */);
+/* la_zstd_blocks.hip: LA_ZSTD_OPT_BLOCK_PARALLEL.  Finishes what frames it can (status, out_len, path = 1) and leaves
+ * todo[i] != 0 for the others; d_todo is the first array of the workspace (la_zstd_blocks_todo). */
+uint64_t la_zstd_blocks_workspace_bytes(uint32_t n_frames, uint64_t src_bytes, uint64_t dst_cap);
+const uint32_t *la_zstd_blocks_todo(const uint8_t *ws);
+void la_launch_zstd_blocks(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_zstd_frame *d_frames, uint32_t n,
     uint8_t *d_dst, uint64_t dst_cap, la_zstd_result *d_results, uint8_t *ws, uint32_t options);
 
 /* la_lz4_comp.hip */
@@ -584,6 +591,8 @@ void la_launch_inflate_chain(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 void la_launch_chain_lengths(hipStream_t s, const la_gz_result *d_results, uint32_t n, uint32_t *d_len);
 void la_launch_chain_resolve(hipStream_t s, const la_gz_member *d_members, const la_gz_result *d_results, uint32_t n,
     uint8_t *d_dst, uint64_t dst_cap, const la_inflate_chain &C, la_gz_member *d_packed, uint32_t *d_ctl);
+/* the same jump passes and gather over a range that starts at d_dst (coordinate 0, no history): total entries of d_ptr */
+void la_launch_chain_resolve_range(hipStream_t s, uint8_t *d_dst, uint32_t *d_ptr, uint32_t total, uint32_t *d_ctl);
 uint64_t la_inflate_lanes_scratch_bytes(uint32_t n);
 /* outputs of the entropy-only launch (la_launch_inflate_symbols): everything
  * lz4_expand_fast_kernel needs to build the members in its LDS window */

@@ -91,9 +91,10 @@ __global__ __launch_bounds__(CHAIN_TPB) void chain_jump_kernel(uint32_t *ptr, ui
 }
 
 __global__ __launch_bounds__(CHAIN_TPB) void chain_gather_kernel(const uint32_t *__restrict__ ptr, uint32_t hist_len,
-    const uint32_t *__restrict__ ctl, const la_gz_member *__restrict__ members, uint8_t *dst)
+    const uint32_t *__restrict__ ctl, const uint64_t *__restrict__ first_off, uint8_t *dst)
 {
-	uint8_t *chain = dst + members[0].dst_off - hist_len;	/* the byte of coordinate 0 */
+	/* the byte of coordinate 0; first_off: where the range starts in dst (the first piece's dst_off on the device), NULL = at dst */
+	uint8_t *chain = dst + (first_off ? *first_off : 0) - hist_len;
 	const uint32_t total = ctl[LA_CHAIN_JUMP_PASSES];
 	const uint32_t stride = gridDim.x * CHAIN_TPB;
 	for (uint64_t k = blockIdx.x * CHAIN_TPB + threadIdx.x; k < total; k += stride) {
@@ -119,5 +120,22 @@ void la_launch_chain_resolve(hipStream_t s, const la_gz_member *d_members, const
 	for (uint32_t pass = 0; pass < LA_CHAIN_JUMP_PASSES; pass++)
 		hipLaunchKernelGGL(chain_jump_kernel, dim3((uint32_t)blocks), dim3(CHAIN_TPB), 0, s, C.ptr, C.hist_len, d_ctl, pass);
 	hipLaunchKernelGGL(chain_gather_kernel, dim3((uint32_t)blocks), dim3(CHAIN_TPB), 0, s, C.ptr, C.hist_len, d_ctl,
-	    d_members, d_dst);
+	    &d_members->dst_off, d_dst);
+}
+
+__global__ void chain_total_kernel(uint32_t *ctl, uint32_t total) { ctl[LA_CHAIN_JUMP_PASSES] = total; }
+
+/* the jump passes and the gather for a caller that has the pointers of d_dst[0, total) in d_ptr (coordinate = index,
+ * no history): the block path of the zstd decoder (la_zstd_blocks.hip) */
+void la_launch_chain_resolve_range(hipStream_t s, uint8_t *d_dst, uint32_t *d_ptr, uint32_t total, uint32_t *d_ctl)
+{
+	if (total == 0) return;
+	(void)hipMemsetAsync(d_ctl, 0, LA_CHAIN_CTL_WORDS * sizeof(uint32_t), s);
+	hipLaunchKernelGGL(chain_total_kernel, dim3(1), dim3(1), 0, s, d_ctl, total);
+	uint64_t blocks = ((uint64_t)total + 4 * CHAIN_TPB - 1) / (4 * CHAIN_TPB);
+	if (blocks > 4096) blocks = 4096;
+	for (uint32_t pass = 0; pass < LA_CHAIN_JUMP_PASSES; pass++)
+		hipLaunchKernelGGL(chain_jump_kernel, dim3((uint32_t)blocks), dim3(CHAIN_TPB), 0, s, d_ptr, 0u, d_ctl, pass);
+	hipLaunchKernelGGL(chain_gather_kernel, dim3((uint32_t)blocks), dim3(CHAIN_TPB), 0, s, d_ptr, 0u, d_ctl,
+	    (const uint64_t *)NULL, d_dst);
 }

@@ -16,6 +16,7 @@
  *   - evidence of many units inside the look-ahead (a BGZF size subfield, a second member header, a frame that
  *     ends inside it): taken;
  *   - otherwise the first unit is larger than the look-ahead: declined (bid 0).
+ * LA_ZSTD_BLOCKS=1 makes one long zstd frame a parallel unit (its blocks), and the zstd bidder takes it.
  * LA_GPU_BID=all switches the policy off (every stream with the right magic is taken: the stand-alone test core
  * has no other bidder); LA_GPU_BID_LOOKAHEAD_KIB sets the look-ahead (default 1024, gzip 256).
  */
@@ -62,6 +63,17 @@ int la_gz_flush_points_enabled(void)
 {
 	const char *v = getenv("LA_GZIP_FLUSH_POINTS");
 	return v != NULL && (v[0] == '1' || strcmp(v, "chain") == 0);
+}
+
+/* LA_ZSTD_BLOCKS=1: the zstd filter decodes the blocks of a frame in parallel (LA_ZSTD_OPT_BLOCK_PARALLEL) on windows
+ * of large frames, so ONE long frame is no serial unit any more and the bidder takes it.  Read from the environment at
+ * every call, as la_gz_flush_points_enabled is: the bidder asks at bid time, the filter once in its init, so a process
+ * that changes the variable between the two gets a filter that took the stream and decodes it on the frame kernels
+ * (or the reverse): slow, never wrong */
+int la_zstd_blocks_enabled(void)
+{
+	const char *v = getenv("LA_ZSTD_BLOCKS");
+	return v != NULL && v[0] == '1';
 }
 
 /* LA_GZIP_FLUSH_POINTS=chain: piece mode as for =1 (the same bid evidence), and the pieces are decoded as one stream
@@ -136,10 +148,11 @@ int la_bid_lz4_parallel(const unsigned char *p, size_t n, size_t lookahead)
 	return 0;
 }
 
-/* zstd: 1 = take it: the first frame (skippable frames in front of it passed over) ends inside the look-ahead */
+/* zstd: 1 = take it: the first frame (skippable frames in front of it passed over) ends inside the look-ahead; with
+ * LA_ZSTD_BLOCKS=1 a longer frame too (it is by construction many blocks of at most 128 KiB) */
 int la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead)
 {
-	if (n < lookahead)
+	if (n < lookahead || la_zstd_blocks_enabled())
 		return 1;
 	la_zstd_frame fr[4];
 	la_zstd_index_result r;

@@ -7,7 +7,8 @@
  * libzstd's error names, zstd.c:226-231).  Where the reference feeds ZSTD_decompressStream whatever
  * __archive_read_filter_ahead returns and hands out one ZSTD_DStreamOutSize() buffer per read, this filter gathers
  * a window of WHOLE frames (la_zstd_index_build: frame and block headers only), decodes them in one
- * la_gpu_zstd_decode call -- one frame per lane -- and hands out one frame per read.  Bytes in front of an error are
+ * la_gpu_zstd_decode call -- one frame per wave; with LA_ZSTD_BLOCKS=1, windows of large frames one BLOCK per wave --
+ * and hands out one frame per read.  Bytes in front of an error are
  * delivered first, as the reference's loop does.  There is no CPU fallback.
  */
 #include "la_read_private.h"
@@ -17,9 +18,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#define ZSTD_BLOCKS_MIN_FRAME ((uint64_t)1 << 20)	/* LA_ZSTD_BLOCKS=1: mean compressed frame size of a window from which it decodes block-parallel */
+
 struct zstd_private {
 	la_window w;			/* (max_batch_bytes: how far the stage may grow for ONE frame larger than a window) */
 	uint32_t options;		/* la_zstd_batch.options: LA_ZSTD_LANE_KERNEL=1 */
+	int blocks_on;			/* LA_ZSTD_BLOCKS=1: windows of large frames decode block-parallel */
 	/* stage: compressed bytes not decoded yet (pageable: its tail is moved right after its copy is queued) */
 	uint8_t *stage; size_t stage_len, stage_cap;
 	uint64_t skip_left;		/* bytes of a skippable frame still to pass over before anything is staged (zstd.c skips
@@ -98,6 +102,7 @@ static int zstd_reader_init(struct archive_read_filter *self)
 	}
 	const char *lk = getenv("LA_ZSTD_LANE_KERNEL");
 	st->options = (lk && atoi(lk) > 0) ? LA_ZSTD_OPT_LANE_KERNEL : 0u;
+	st->blocks_on = la_zstd_blocks_enabled();
 	if (la_window_open(self, &st->w, "zstd") != ARCHIVE_OK) {
 		free(st);
 		return ARCHIVE_FATAL;
@@ -258,6 +263,10 @@ static int zstd_launch(struct archive_read_filter *self, struct zstd_private *st
 		bt.d_dst = st->d_dst.p; bt.dst_cap = ir.dst_bytes;
 		bt.d_results = d_results;
 		bt.options = st->options;
+		/* a window of few large frames has too few frames to fill the device: its blocks are the parallel units (frames
+		 * the block path hands back go to the kernel st->options names); windows of small frames keep the frame kernels */
+		if (st->blocks_on && ir.consumed / sl->n >= ZSTD_BLOCKS_MIN_FRAME)
+			bt.options |= LA_ZSTD_OPT_BLOCK_PARALLEL;
 		if (la_gpu_zstd_decode(gpu, &bt) != LA_OK) return gpu_fail(self, st, "la_gpu_zstd_decode");
 		if (la_gpu_memcpy_d2h(gpu, sl->results, d_results, rtab) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_d2h");
 		if (ir.dst_bytes && la_gpu_memcpy_d2h(gpu, sl->out.p, st->d_dst.p, ir.dst_bytes) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_d2h");

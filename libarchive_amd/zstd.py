@@ -7,7 +7,10 @@ import numpy as np
 from . import _native as N
 
 ZSTD_FRAME_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst_off", "<u8"), ("dst_cap", "<u8")])
-ZSTD_RESULT_DTYPE = np.dtype([("status", "<u4"), ("reserved", "<u4"), ("out_len", "<u8")])
+# `path` and `reserved` name the same word (the header's anonymous union; `reserved` is the field's earlier name)
+ZSTD_RESULT_DTYPE = np.dtype({"names": ["status", "path", "reserved", "out_len"], "formats": ["<u4", "<u4", "<u4", "<u8"],
+                              "offsets": [0, 4, 4, 8], "itemsize": 16})
+LA_ZSTD_OPT_NO_VERIFY, LA_ZSTD_OPT_LANE_KERNEL, LA_ZSTD_OPT_BLOCK_PARALLEL = N.LA_ZSTD_OPT_NO_VERIFY, N.LA_ZSTD_OPT_LANE_KERNEL, N.LA_ZSTD_OPT_BLOCK_PARALLEL
 
 
 class _IndexResultC(C.Structure):
