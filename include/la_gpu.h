@@ -503,9 +503,20 @@ int      la_gpu_zip_compress(la_gpu_ctx *ctx, const la_zipc_batch *batch);
  * block.  d_out receives the concatenated frames, *d_out_bytes their total size (if it exceeds out_cap nothing past
  * out_cap was written: call again with a larger buffer; la_gpu_zstd_compress_bound() always fits).  The bytes are not
  * libzstd's (a zstd stream is not unique); every conforming decoder returns the input.
+ *
+ * Entropy stage.  Without the two flags below a block's literals are Huffman-coded only when their largest byte is at
+ * most 128 (the tree description is the direct 4-bit form, which holds 128 weights) and the sequences use the
+ * predefined tables; the bytes written for such flags never change.  LA_ZSTDC_FULL_ALPHABET Huffman-codes literals of
+ * any alphabet: the weights go out in the direct form or FSE-coded (RFC 8878 4.2.1.1), whichever is allowed and
+ * smaller; literals whose sent weights are all equal have no FSE form and stay raw above 128 weights.
+ * LA_ZSTDC_FIT_TABLES chooses per block and per field (LL, OF, ML) between Predefined_Mode, RLE_Mode (one code in the
+ * whole block) and FSE_Compressed_Mode with counts normalised from the block's own histogram (accuracy log 5 .. 9, 8
+ * for offsets), by estimated cost; Repeat_Mode is never written.  LA_ZSTDC_RAW_LITERALS wins over FULL_ALPHABET.
  * ===================================================================== */
-#define LA_ZSTDC_CHECKSUM     1u	/* Content_Checksum_Flag + XXH64 (low 32 bits) of every frame's input */
-#define LA_ZSTDC_RAW_LITERALS 2u	/* no Huffman literals (the filter's negative / zero levels) */
+#define LA_ZSTDC_CHECKSUM      1u	/* Content_Checksum_Flag + XXH64 (low 32 bits) of every frame's input */
+#define LA_ZSTDC_RAW_LITERALS  2u	/* no Huffman literals (the filter's negative / zero levels) */
+#define LA_ZSTDC_FULL_ALPHABET 4u	/* Huffman literals for any alphabet (FSE-coded weights where needed or smaller) */
+#define LA_ZSTDC_FIT_TABLES    8u	/* sequence tables per block: predefined, RLE or fitted to the block's histogram */
 
 typedef struct la_zstdc_batch {
 	const uint8_t *d_src;

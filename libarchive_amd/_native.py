@@ -82,6 +82,7 @@ class _ZstdcBatchC(C.Structure):
 
 
 LA_ZSTDC_CHECKSUM, LA_ZSTDC_RAW_LITERALS = 1, 2
+LA_ZSTDC_FULL_ALPHABET, LA_ZSTDC_FIT_TABLES = 4, 8
 LA_ZSTD_OPT_NO_VERIFY, LA_ZSTD_OPT_LANE_KERNEL, LA_ZSTD_OPT_BLOCK_PARALLEL = 1, 2, 4     # la_zstd_batch.options
 
 

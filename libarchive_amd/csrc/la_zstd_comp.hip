@@ -17,21 +17,30 @@
  *       4096-entry table of 32-bit positions in LDS (16 KiB), 4-byte minimum match at any offset inside the block, matches verified and extended, taken
  *       in position order with ballot; literals and sequences (ll, ml, offset) go to the workspace.
  *       Literals section: RLE when all literals are one byte; Raw under LA_ZSTDC_RAW_LITERALS, for fewer than 32
- *       literals or a largest byte above 128; otherwise Huffman: an LDS histogram, Shannon lengths clamped to 11 bits
+ *       literals or, without LA_ZSTDC_FULL_ALPHABET, a largest byte above 128; otherwise Huffman: an LDS histogram, Shannon lengths clamped to 11 bits
  *       and made complete (Kraft sum exactly 1) by greedy lengthening / shortening with wave-wide arg-max rounds,
  *       direct 4-bit weights, one stream up to 1023 literals and four with the jump table above.  Streams are encoded
  *       in parallel: every literal's bit position is a wave prefix sum of code lengths (reverse symbol order, a
  *       Huffman stream is read backwards), lanes OR their bits into an LDS stage and whole dwords leave
  *       (wave_bits_append, shared with deflate_fixed_kernel).  Sections whose coded form would not be smaller are written raw.
+ *       LA_ZSTDC_FULL_ALPHABET: any largest byte; the weights also go through zc_weights_fse (their histogram
+ *       normalised a lane per weight, two interleaved FSE states, written backwards by the serial bit writer) and the
+ *       smaller allowed description is written; weights that are all equal have no FSE form (raw above 128 of them).
  *       Sequences section: Predefined_Mode for LL, OF and ML; the interleaved FSE stream is written last sequence
  *       first, uniformly by the wave (64 sequences' codes and extra bits computed lane-parallel, then taken one by
  *       one with v_readlane), with encoder tables (symbol x next state -> state) spread from the decoder's own
- *       fse_build in LDS.  A block whose compressed form is not smaller than its input is a Raw_Block.
+ *       fse_build in LDS.  LA_ZSTDC_FIT_TABLES (zc_sequences_fit): LDS histograms of the three codes, per field
+ *       RLE_Mode for a single code, FSE_Compressed_Mode when counts normalised from the histogram (accuracy log from
+ *       the sequence count, 5 .. 9, 8 for offsets) are estimated cheaper than the predefined table by more than a
+ *       byte, Predefined_Mode otherwise, never Repeat_Mode; the same chain then runs on compact encoder tables (the
+ *       states of every symbol in next-state order, zc_fse_step) with every field's own accuracy log.  Flags without
+ *       the two run the kernel's <false> instance, which holds none of this: the code and the bytes they had.
+ *       A block whose compressed form is not smaller than its input is a Raw_Block.
  *   frame_sums_kernel             XXH64 of every frame's input (la_comp_common.h), four lanes per frame.
  *   zstdc_sizes_kernel / scan     stream bytes of every block (header + payload, frame header and checksum).
  *   zstd_pack_frames_kernel       one workgroup per block: frame header, block header, payload, checksum.
- * LDS per wave: 16 KiB table (the FSE tables reuse it after matching) + 1.8 KiB histogram / code / stage:
- * 8 waves per CU by LDS.
+ * LDS per wave: 16 KiB table (the FSE tables of either form and the weight tables reuse it after matching: 11 KiB
+ * at most) + 1.9 KiB histogram / code / stage: 8 waves per CU by LDS.
  */
 #include "la_comp_common.h"
 #include "la_zstd_common.h"
@@ -50,10 +59,31 @@ struct zc_fse_lds {
 	uint8_t eml[53 * 64];
 	uint8_t eof[29 * 32];
 };
+/* LA_ZSTDC_FIT_TABLES: per-block tables.  Field 0 = LL, 1 = OF, 2 = ML (the order of the descriptions in the block).
+ * The encoder is compact: st lists the states of every symbol in ascending order (symbol s from start(s) on),
+ * sinfo[s] = count | start << 16; a symbol of normalised count c owns the next-state values c .. 2c - 1 in that
+ * order (the decoder's spread, fse_build), so the state that leads to next state t is found by arithmetic. */
+struct zc_fit_lds {
+	fse_tab t[3];			/* decoder form, built by the decoder's own fse_build */
+	uint16_t st[3][512];
+	uint32_t sinfo[3][64];
+	uint32_t hist[3][64];
+	int16_t norm[3][64];
+};
+/* LA_ZSTDC_FULL_ALPHABET: the FSE form of the Huffman tree description (weights 0..11, accuracy log 5 or 6) */
+struct zc_wfse_lds {
+	fse_tab t;
+	uint16_t st[64];
+	uint32_t sinfo[16];
+	int16_t norm[16];
+	uint8_t tree[136];		/* normalised counts + weight stream: usable below 128 bytes */
+};
 struct zc_lds {
 	union {
 		uint32_t tab[1u << LZ77_HASH_BITS];
 		zc_fse_lds f;
+		zc_fit_lds fit;
+		zc_wfse_lds wf;
 	} u;
 	uint32_t hist[256];
 	uint16_t code[256];
@@ -62,6 +92,9 @@ struct zc_lds {
 	uint32_t stage[32];
 };
 static_assert(sizeof(zc_fse_lds) <= sizeof(uint32_t) * (1u << LZ77_HASH_BITS), "FSE tables must fit in the match table");
+static_assert(sizeof(zc_fit_lds) <= sizeof(uint32_t) * (1u << LZ77_HASH_BITS), "fitted tables must fit in the match table");
+static_assert(sizeof(zc_wfse_lds) <= sizeof(uint32_t) * (1u << LZ77_HASH_BITS), "weight tables must fit in the match table");
+static_assert(sizeof(zc_lds) <= 20u * 1024u, "8 waves per CU by LDS");
 
 /* literal-length / match-length codes (RFC 8878 3.1.1.3.2.1.1) */
 __device__ __forceinline__ uint32_t ll_code(uint32_t ll)
@@ -153,6 +186,327 @@ __device__ __forceinline__ void bw_put(zc_bw &w, uint32_t v, uint32_t nb, uint32
 	}
 }
 
+/* the bytes still in the accumulator leave (the stream is byte-aligned afterwards); returns the stream's end */
+__device__ __forceinline__ uint32_t bw_close(zc_bw &w, uint32_t lane)
+{
+	const uint32_t tail = (w.n + 7u) >> 3;
+	if (w.op + tail > w.cap) {
+		w.over = true;
+	} else if (lane == 0) {
+		for (uint32_t k = 0; k < tail; k++)
+			w.out[w.op + k] = (uint8_t)(w.acc >> (8u * k));
+	}
+	w.op += tail;
+	w.acc = 0;
+	w.n = 0;
+	return w.op;
+}
+
+__device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t lane)
+{
+	uint32_t inc = v;
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t t = __shfl_up(inc, d, 64);
+		if ((int)lane >= d) inc += t;
+	}
+	return inc - v;
+}
+
+/* ---- FSE tables fitted to a histogram (LA_ZSTDC_FULL_ALPHABET: the Huffman weights; LA_ZSTDC_FIT_TABLES: the
+ * sequence codes), a lane per symbol ---- */
+
+/* normalised counts: floor(h * 2^al / total), 1 for a present symbol that would get less, and the difference to 2^al
+ * on the most frequent symbol (the lowest of equals).  False when that symbol would be left below 1.  At most
+ * 2^15 * 2^9: 32-bit arithmetic. */
+__device__ __forceinline__ bool zc_normalize(uint32_t h, uint32_t total, uint32_t al, uint32_t lane, uint32_t &norm)
+{
+	uint32_t c = 0;
+	if (h) {
+		c = (h << al) / total;
+		c = c ? c : 1u;
+	}
+	const uint32_t sum = wave_sum(c);
+	const uint32_t big = 63u - (wave_max(h ? (h << 6) | (63u - lane) : 0u) & 63u);
+	const int32_t fixed = (int32_t)c + (int32_t)(1u << al) - (int32_t)sum;
+	if (lane == big)
+		c = fixed < 1 ? 0u : (uint32_t)fixed;
+	norm = c;
+	return __ballot(lane == big && fixed < 1) == 0;
+}
+
+/* cost of one symbol of normalised count c in a table of 2^al states, in 1/256 bit */
+__device__ __forceinline__ uint32_t zc_bits256(uint32_t al, uint32_t c)
+{
+	return (uint32_t)(((float)al - __log2f((float)c)) * 256.0f + 0.5f);
+}
+
+/* normalised counts in the layout fse_read_ncount reads (RFC 8878 4.1.1): accuracy log, then count + 1 per symbol in
+ * as many bits as what remains allows, a zero count followed by 2-bit repeat flags; the symbols behind the one that
+ * completes the sum are not written.  Wave-uniform; every count is 0 or positive ("less than one" is not used). */
+__device__ static void zc_put_ncount(zc_bw &w, const int16_t *norm, uint32_t n_sym, uint32_t al, uint32_t lane)
+{
+	bw_put(w, al - 5u, 4, lane);
+	uint32_t remaining = (1u << al) + 1u, threshold = 1u << al, nbits = al + 1u, s = 0;
+	while (remaining > 1u && s < n_sym) {
+		const uint32_t c = (uint32_t)norm[s], mx = 2u * threshold - 1u - remaining, v = c + 1u;
+		if (v < mx)
+			bw_put(w, v, nbits - 1u, lane);
+		else if (v < threshold)
+			bw_put(w, v, nbits, lane);
+		else
+			bw_put(w, v + mx, nbits, lane);
+		remaining -= c;
+		s++;
+		if (c == 0) {
+			uint32_t z = 0;
+			while (s + z < n_sym && norm[s + z] == 0) z++;
+			s += z;
+			for (; z >= 3u; z -= 3u)
+				bw_put(w, 3, 2, lane);
+			bw_put(w, z, 2, lane);
+		}
+		while (remaining < threshold) { nbits--; threshold >>= 1; }
+	}
+}
+
+/* compact encoder table from the decoder's: state u, whose range starts at base and is 2^nbits wide, owns the
+ * next-state value (base + size) >> nbits of its symbol; the symbol's states go into st in that order */
+__device__ __forceinline__ void zc_enc_table(const fse_tab *t, uint32_t al, const uint32_t *sinfo, uint16_t *st, uint32_t lane)
+{
+	const uint32_t size = 1u << al;
+	for (uint32_t u = lane; u < size; u += 64) {
+		const fse_ent e = t->e[u];
+		const uint32_t w = sinfo[e.sym];
+		st[(w >> 16) + ((e.base + size) >> e.nbits) - (w & 0xFFFFu)] = (uint16_t)u;
+	}
+}
+
+/* one encoder step: the state of symbol `sym` whose range holds the next state t, and the bits that select t in it.
+ * A symbol of count c has next-state values c .. 2c - 1; t + size shifted by the symbol's larger bit count lands on
+ * one of them or, below c, belongs to a state with one bit less.  (A one-state table, al = 0, gives no bits.) */
+__device__ __forceinline__ uint32_t zc_fse_step(const uint16_t *st, const uint32_t *sinfo, uint32_t al, uint32_t sym,
+    uint32_t t, uint32_t &bits, uint32_t &nb)
+{
+	const uint32_t w = sinfo[sym], c = w & 0xFFFFu, v = t + (1u << al);
+	uint32_t n = al - (31u - (uint32_t)__clz((int)c));
+	uint32_t nx = v >> n;
+	if (nx < c) {
+		n--;
+		nx = v >> n;
+	}
+	nb = n;
+	bits = v & ((1u << n) - 1u);
+	return st[(w >> 16) + nx - c];
+}
+/* a state of `sym` to end on: the one with the most update bits */
+__device__ __forceinline__ uint32_t zc_fse_first(const uint16_t *st, const uint32_t *sinfo, uint32_t sym)
+{
+	return st[sinfo[sym] >> 16];
+}
+
+/* The FSE form of the Huffman tree description (RFC 8878 4.2.1.1) for the weights of symbols 0 .. nw - 1 (nw >= 2),
+ * into L.u.wf.tree: normalised counts of the weights, then the weights through two interleaved states (the first
+ * decodes the even positions), written backwards with an end mark.  The stream carries no count: the decoder stops
+ * when a state update runs out of bits, so the state it ends on must need a bit -- each chain ends on its symbol's
+ * state with the most bits, which is none only when all weights are equal.  Returns the bytes (below 128), or 0 when
+ * this form cannot be used. */
+__device__ static uint32_t zc_weights_fse(zc_lds &L, uint32_t nw, uint32_t lmax, uint32_t lane)
+{
+	zc_wfse_lds &F = L.u.wf;
+	if (lane < 16)
+		L.wcnt[lane] = 0;
+	__syncthreads();
+	for (uint32_t s = lane; s < nw; s += 64)
+		atomicAdd(&L.wcnt[L.len[s] ? lmax + 1u - L.len[s] : 0u], 1u);
+	__syncthreads();
+	const uint32_t h = lane < 16 ? L.wcnt[lane] : 0u;
+	const uint64_t present = __ballot(h != 0);
+	if (__popcll(present) < 2)
+		return 0;
+	const uint32_t n_sym = 64u - (uint32_t)__clzll((long long)present);
+	const uint32_t al = nw > 64u ? 6u : 5u;
+	uint32_t c;
+	if (!zc_normalize(h, nw, al, lane, c))
+		return 0;
+	const uint32_t start = wave_excl_sum(c, lane);
+	if (lane < 16) {
+		F.norm[lane] = (int16_t)c;
+		F.sinfo[lane] = c | (start << 16);
+	}
+	__syncthreads();
+	if (lane == 0)
+		fse_build(&F.t, F.norm, (int)n_sym, (int)al);
+	__syncthreads();
+	zc_enc_table(&F.t, al, F.sinfo, F.st, lane);
+	__syncthreads();
+	zc_bw w;
+	w.out = F.tree; w.op = 0; w.cap = 132; w.acc = 0; w.n = 0; w.over = false;
+	zc_put_ncount(w, F.norm, n_sym, al, lane);
+	bw_close(w, lane);
+	auto weight = [&](uint32_t s) { const uint32_t l = L.len[s]; return l ? lmax + 1u - l : 0u; };
+	/* s0 / s1: the state of the even / odd chain at the position reached so far, from the end */
+	uint32_t s0 = zc_fse_first(F.st, F.sinfo, weight(nw - 1u)), s1 = zc_fse_first(F.st, F.sinfo, weight(nw - 2u));
+	if (!(nw & 1u)) {	/* the last weight stands at an odd position */
+		const uint32_t t = s0; s0 = s1; s1 = t;
+	}
+	for (uint32_t i = nw - 2u; i-- > 0;) {
+		uint32_t bits, nb;
+		const uint32_t u = zc_fse_step(F.st, F.sinfo, al, weight(i), (i & 1u) ? s1 : s0, bits, nb);
+		bw_put(w, bits, nb, lane);
+		if (i & 1u) s1 = u; else s0 = u;
+	}
+	bw_put(w, s1, al, lane);	/* the decoder reads the even chain's state first: it is written last */
+	bw_put(w, s0, al, lane);
+	bw_put(w, 1, 1, lane);		/* end mark */
+	const uint32_t end = bw_close(w, lane);
+	__syncthreads();
+	return (w.over || end >= 128u) ? 0u : end;
+}
+
+/* The sequences section behind Number_of_Sequences under LA_ZSTDC_FIT_TABLES (RFC 8878 3.1.1.3.2.1): the block's
+ * histograms of LL, OF and ML codes, a mode per field -- RLE_Mode when one code is all there is, FSE_Compressed_Mode
+ * when a table normalised from the histogram is estimated cheaper (description + sum of count * log2(size / norm))
+ * than the predefined one by more than a byte, Predefined_Mode otherwise -- then the interleaved stream with every
+ * field's own table and accuracy log.  Returns the section's end; over: it did not fit cap. */
+__device__ static uint32_t zc_sequences_fit(zc_lds &L, const uint64_t *seqs, uint32_t nseq, uint8_t *out, uint32_t op,
+    uint32_t cap, uint32_t lane, bool &over)
+{
+	zc_fit_lds &F = L.u.fit;
+	for (uint32_t f = 0; f < 3; f++)
+		F.hist[f][lane] = 0;
+	__syncthreads();
+	for (uint32_t i = lane; i < nseq; i += 64) {
+		const uint64_t s = seqs[i];
+		atomicAdd(&F.hist[0][ll_code((uint32_t)(s & 0xFFFFFu))], 1u);
+		atomicAdd(&F.hist[1][(uint32_t)highbit((uint32_t)(s >> 40) + 3u)], 1u);
+		atomicAdd(&F.hist[2][ml_code((uint32_t)((s >> 20) & 0xFFFFFu))], 1u);
+	}
+	__syncthreads();
+	zc_bw w;
+	w.out = out; w.op = op + 1u; w.cap = cap; w.acc = 0; w.n = 0; w.over = false;
+	uint32_t modes = 0, als = 0;	/* als: the three accuracy logs, a byte each */
+	bool stuck = false;
+	for (uint32_t f = 0; f < 3; f++) {
+		const int16_t *def = f == 0 ? LL_DEF : f == 1 ? OF_DEF : ML_DEF;
+		const uint32_t def_n = f == 0 ? 36u : f == 1 ? 29u : 53u, def_al = f == 1 ? 5u : 6u, max_al = f == 1 ? 8u : 9u;
+		const uint32_t h = F.hist[f][lane];
+		const uint64_t present = __ballot(h != 0);
+		const uint32_t np = (uint32_t)__popcll(present), n_sym = 64u - (uint32_t)__clzll((long long)present);
+		const int32_t d = lane < def_n ? def[lane] : 0;
+		const uint32_t dc = d < 0 ? 1u : (uint32_t)d;
+		const bool def_ok = __ballot(h != 0 && dc == 0) == 0;	/* the predefined table knows every code used */
+		const uint32_t cost_def = wave_sum(h && dc ? h * zc_bits256(def_al, dc) : 0u);
+		uint32_t mode = 0, al = def_al, c = dc;
+		int32_t nv = d;		/* the counts fse_build gets */
+		if (np == 1u) {
+			if (!def_ok || 8u * 256u < cost_def) {
+				mode = 1; al = 0; c = h ? 1u : 0u;
+				if (w.op + 1u > cap) w.over = true;
+				else if (lane == 0) out[w.op] = (uint8_t)(n_sym - 1u);
+				w.op += 1u;
+			}
+		} else {
+			/* accuracy log: two bits below the sequence count's, enough states for every code present */
+			uint32_t a = (uint32_t)highbit(nseq - 1u);
+			a = a > 2u ? a - 2u : 0u;
+			const uint32_t need = (uint32_t)highbit(np - 1u) + 1u;
+			a = a < need ? need : a;
+			a = a < 5u ? 5u : (a > max_al ? max_al : a);
+			uint32_t nc;
+			const bool fits = zc_normalize(h, nseq, a, lane, nc);
+			if (fits) {
+				F.norm[f][lane] = (int16_t)nc;
+				__syncthreads();
+				zc_bw t = w;	/* written where it would stand; kept only if this mode is chosen */
+				zc_put_ncount(t, F.norm[f], n_sym, a, lane);
+				bw_close(t, lane);
+				const uint32_t cost_fit = wave_sum(h ? h * zc_bits256(a, nc) : 0u) + (t.op - w.op) * 8u * 256u;
+				if (!def_ok || cost_fit + 8u * 256u < cost_def) {
+					mode = 2; al = a; c = nc; nv = (int32_t)nc;
+					w = t;
+				}
+			}
+			stuck |= !def_ok && mode == 0;
+		}
+		__syncthreads();
+		F.norm[f][lane] = (int16_t)nv;
+		F.sinfo[f][lane] = c | (wave_excl_sum(c, lane) << 16);
+		modes |= mode << (6u - 2u * f);
+		als |= al << (8u * f);
+	}
+	if (lane == 0)
+		out[op] = (uint8_t)modes;	/* Symbol_Compression_Modes; Repeat_Mode never: blocks are independent */
+	__syncthreads();
+	if (lane < 3u) {
+		if (((modes >> (6u - 2u * lane)) & 3u) == 1u)
+			F.st[lane][0] = 0;
+		else
+			fse_build(&F.t[lane], F.norm[lane], 64, (int)((als >> (8u * lane)) & 255u));
+	}
+	__syncthreads();
+	const uint32_t al_l = als & 255u, al_o = (als >> 8) & 255u, al_m = (als >> 16) & 255u;
+	if ((modes >> 6) != 1u) zc_enc_table(&F.t[0], al_l, F.sinfo[0], F.st[0], lane);
+	if (((modes >> 4) & 3u) != 1u) zc_enc_table(&F.t[1], al_o, F.sinfo[1], F.st[1], lane);
+	if (((modes >> 2) & 3u) != 1u) zc_enc_table(&F.t[2], al_m, F.sinfo[2], F.st[2], lane);
+	__syncthreads();
+	uint32_t sl = 0, sm = 0, sof = 0;
+	/* last sequence first, 64 at a time: lane j prepares sequence hi - 1 - j */
+	for (uint32_t hi = nseq; hi > 0;) {
+		const uint32_t cnt = hi < 64u ? hi : 64u;
+		uint32_t codes = 0, lmx = 0, lmbits = 0, ov = 0;
+		if (lane < cnt) {
+			const uint64_t s = seqs[hi - 1u - lane];
+			const uint32_t ll = (uint32_t)(s & 0xFFFFFu), ml = (uint32_t)((s >> 20) & 0xFFFFFu), off = (uint32_t)(s >> 40);
+			const uint32_t lc = ll_code(ll), mc = ml_code(ml);
+			ov = off + 3u;
+			const uint32_t oc = (uint32_t)highbit(ov);
+			codes = lc | (mc << 8) | (oc << 16);
+			lmx = (ll - SEQ_TABS.ll_base[lc]) | ((ml - SEQ_TABS.ml_base[mc]) << 16);
+			lmbits = SEQ_TABS.ll_bits[lc] | ((uint32_t)SEQ_TABS.ml_bits[mc] << 8);
+			ov -= 1u << oc;
+		}
+		for (uint32_t j = 0; j < cnt; j++) {
+			const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)codes, (int)j);
+			const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lmx, (int)j);
+			const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)lmbits, (int)j);
+			const uint32_t ox = (uint32_t)__builtin_amdgcn_readlane((int)ov, (int)j);
+			const uint32_t lc = c & 255u, mc = (c >> 8) & 255u, oc = c >> 16;
+			if (hi == nseq && j == 0) {
+				/* the block's last sequence: any state of its symbols */
+				sl = zc_fse_first(F.st[0], F.sinfo[0], lc);
+				sof = zc_fse_first(F.st[1], F.sinfo[1], oc);
+				sm = zc_fse_first(F.st[2], F.sinfo[2], mc);
+			} else {
+				/* state of this sequence whose range holds the next one's state; the bits select it */
+				uint32_t bo, no, bm, nm, bl, nl;
+				sof = zc_fse_step(F.st[1], F.sinfo[1], al_o, oc, sof, bo, no);
+				sm = zc_fse_step(F.st[2], F.sinfo[2], al_m, mc, sm, bm, nm);
+				sl = zc_fse_step(F.st[0], F.sinfo[0], al_l, lc, sl, bl, nl);
+				bw_put(w, bo, no, lane);
+				bw_put(w, bm, nm, lane);
+				bw_put(w, bl, nl, lane);
+			}
+			/* extra bits: the decoder reads offset, match length, literal length */
+			bw_put(w, x & 0xFFFFu, b & 255u, lane);
+			bw_put(w, x >> 16, b >> 8, lane);
+			bw_put(w, ox, oc, lane);
+		}
+		hi -= cnt;
+	}
+	/* initial states, each as wide as its table's accuracy log: the decoder reads LL, OF, ML */
+	bw_put(w, sm, al_m, lane);
+	bw_put(w, sof, al_o, lane);
+	bw_put(w, sl, al_l, lane);
+	bw_put(w, 1, 1, lane);	/* end mark */
+	const uint32_t end = bw_close(w, lane);
+	over = w.over || stuck;
+	return end;
+}
+
+/* ENTROPY: the instance for flags with LA_ZSTDC_FULL_ALPHABET or LA_ZSTDC_FIT_TABLES.  The other instance holds none
+ * of their code, so the flags from before them run the kernel they always ran. */
+template <bool ENTROPY>
 __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
     uint32_t block_size, uint32_t n_blocks, uint32_t flags, uint8_t *__restrict__ tmp, uint8_t *__restrict__ lits_ws,
     uint64_t *__restrict__ seqs_ws, uint32_t *__restrict__ btype, uint32_t *__restrict__ csize)
@@ -230,7 +584,7 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 		if (lane == 0) out[op] = lits[0];
 		op += 1;
 		lit_done = true;
-	} else if (!(flags & LA_ZSTDC_RAW_LITERALS) && nlit >= ZC_RAW_LIT_MIN && maxsym <= 128u) {
+	} else if (!(flags & LA_ZSTDC_RAW_LITERALS) && nlit >= ZC_RAW_LIT_MIN && (maxsym <= 128u || (ENTROPY && (flags & LA_ZSTDC_FULL_ALPHABET)))) {
 		/* code lengths: Shannon lengths ceil(log2(nlit / f)) clamped to [1, 11], then made complete.
 		 * K = sum of 2^(11 - len) over the used symbols; complete means K == 2048. */
 		uint32_t Ls[4];
@@ -333,19 +687,32 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 				if (j == 0 || four) body += sbytes[j];
 			}
 			const uint32_t nw = maxsym;	/* weights written: symbols 0 .. maxsym - 1 (the last one is implied) */
-			const uint32_t tree = 1u + (nw + 1u) / 2u;
+			/* tree description: the direct form holds at most 128 weights; under LA_ZSTDC_FULL_ALPHABET the FSE form
+			 * is taken when it is the only one or the smaller one.  tree = 0: no form, the literals stay raw. */
+			uint32_t tree = nw <= 128u ? 1u + (nw + 1u) / 2u : 0u, fse_bytes = 0;
+			if (ENTROPY && (flags & LA_ZSTDC_FULL_ALPHABET) && nw >= 2u) {
+				const uint32_t fb = zc_weights_fse(L, nw, lmax, lane);
+				if (fb && (tree == 0 || 1u + fb < tree)) {
+					tree = 1u + fb;
+					fse_bytes = fb;
+				}
+			}
 			const uint32_t comp = tree + (four ? 6u : 0u) + body;
 			const uint32_t hl = !four ? 3u : (nlit < 16384u && comp < 16384u) ? 4u : 5u;
 			const uint32_t raw_size = lit_hdr_rr(out, 0, nlit, false) + nlit;
-			if (hl + comp < raw_size && (four || comp < 1024u)) {
+			if (tree && hl + comp < raw_size && (four || comp < 1024u)) {
 				if (lane == 0) {
 					const uint32_t sf = !four ? 0u : hl == 4u ? 2u : 3u;
 					const uint64_t v = 2u | (sf << 2) | ((uint64_t)nlit << 4) | ((uint64_t)comp << (hl == 3u ? 14 : hl == 4u ? 18 : 22));
 					for (uint32_t k = 0; k < hl; k++) out[k] = (uint8_t)(v >> (8u * k));
-					out[hl] = (uint8_t)(127u + nw);
+					out[hl] = (uint8_t)(fse_bytes ? fse_bytes : 127u + nw);
+				}
+				if (fse_bytes) {
+					for (uint32_t k = lane; k < fse_bytes; k += 64)
+						out[hl + 1u + k] = L.u.wf.tree[k];
 				}
 				/* direct 4-bit weights, two per byte, the first in the high nibble */
-				for (uint32_t k = lane; k < (nw + 1u) / 2u; k += 64) {
+				for (uint32_t k = lane; k < (fse_bytes ? 0u : (nw + 1u) / 2u); k += 64) {
 					const uint32_t s0 = 2u * k, s1 = 2u * k + 1u;
 					const uint32_t w0 = L.len[s0] ? lmax + 1u - L.len[s0] : 0u;
 					const uint32_t w1 = (s1 < nw && L.len[s1]) ? lmax + 1u - L.len[s1] : 0u;
@@ -393,7 +760,9 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 		op += 3;
 	}
 	bool over = false;
-	if (nseq > 0) {
+	if (ENTROPY && nseq > 0 && (flags & LA_ZSTDC_FIT_TABLES)) {
+		op = zc_sequences_fit(L, seqs, nseq, out, op, cap, lane, over);
+	} else if (nseq > 0) {
 		if (lane == 0) {
 			out[op] = 0;	/* Symbol_Compression_Modes: Predefined_Mode for LL, OF and ML */
 			fse_build(&L.u.f.ll, LL_DEF, 36, 6);
@@ -631,8 +1000,12 @@ void la_launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 	const uint32_t nf = (nb + bpf - 1) / bpf;
 	zc_ws w;
 	zc_carve(&w, ws, nb, nf, block_size);
-	hipLaunchKernelGGL(zstd_compress_blocks_kernel, dim3(nb), dim3(64), 0, s, d_src, src_bytes, block_size, nb, flags,
-	    w.tmp, w.lits, w.seqs, w.btype, w.csize);
+	if (flags & (LA_ZSTDC_FULL_ALPHABET | LA_ZSTDC_FIT_TABLES))
+		hipLaunchKernelGGL(zstd_compress_blocks_kernel<true>, dim3(nb), dim3(64), 0, s, d_src, src_bytes, block_size, nb, flags,
+		    w.tmp, w.lits, w.seqs, w.btype, w.csize);
+	else
+		hipLaunchKernelGGL(zstd_compress_blocks_kernel<false>, dim3(nb), dim3(64), 0, s, d_src, src_bytes, block_size, nb, flags,
+		    w.tmp, w.lits, w.seqs, w.btype, w.csize);
 	if (flags & LA_ZSTDC_CHECKSUM)
 		hipLaunchKernelGGL(frame_sums_kernel<zc_xxh64>, dim3((nf + 15) / 16), dim3(64), 0, s, d_src, src_bytes,
 		    (uint64_t)bpf * block_size, nf, w.fsum);

@@ -5,7 +5,9 @@
  * Registration and options follow libarchive/archive_write_add_filter_zstd.c (name "zstd", code ARCHIVE_FILTER_ZSTD,
  * default level 3, a content checksum on every frame as its ZSTD_c_checksumFlag = 1), with the option ranges that
  * filter uses when it is built without libzstd's own bounds: "compression-level" -99..22 (0 and below write raw
- * literals, 1 and above mean the device's one Huffman level), "threads" >= 0 (accepted, ignored), "frame-per-file"
+ * literals; 1 and 2 are the fast levels: Huffman literals for alphabets up to byte 128, predefined sequence tables; 3
+ * and above, the default among them, add LA_ZSTDC_FULL_ALPHABET | LA_ZSTDC_FIT_TABLES: Huffman literals for any
+ * alphabet and sequence tables chosen per block, the densest stream the device writes), "threads" >= 0 (accepted, ignored), "frame-per-file"
  * (a no-op: the raw format holds one entry), "min-frame-in" / "min-frame-out" / "min-frame-size" (sizes with k / M /
  * G and an optional B, accepted, ignored), "max-frame-in" / "max-frame-size" >= 1024 (frames hold at most this much
  * input), "max-frame-out" >= 1024 (accepted: frames are bounded by their input only), "long" 10..31 (accepted, no
@@ -149,7 +151,8 @@ static int zstdw_compress(struct archive_write_filter *f, const struct la_write_
 	memset(&bt, 0, sizeof(bt));
 	bt.d_src = w->d_in; bt.src_bytes = w->len;
 	bt.block_size = d->block_size; bt.blocks_per_frame = d->blocks_per_frame;
-	bt.flags = LA_ZSTDC_CHECKSUM | (d->compression_level <= 0 ? LA_ZSTDC_RAW_LITERALS : 0);
+	bt.flags = LA_ZSTDC_CHECKSUM | (d->compression_level <= 0 ? LA_ZSTDC_RAW_LITERALS :
+	    d->compression_level >= 3 ? LA_ZSTDC_FULL_ALPHABET | LA_ZSTDC_FIT_TABLES : 0);
 	bt.d_out = w->d_out; bt.out_cap = w->out_cap; bt.d_out_bytes = w->d_len;
 	return la_gpu_zstd_compress(w->gpu, &bt);
 }

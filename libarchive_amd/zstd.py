@@ -11,6 +11,9 @@ ZSTD_FRAME_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst_off",
 ZSTD_RESULT_DTYPE = np.dtype({"names": ["status", "path", "reserved", "out_len"], "formats": ["<u4", "<u4", "<u4", "<u8"],
                               "offsets": [0, 4, 4, 8], "itemsize": 16})
 LA_ZSTD_OPT_NO_VERIFY, LA_ZSTD_OPT_LANE_KERNEL, LA_ZSTD_OPT_BLOCK_PARALLEL = N.LA_ZSTD_OPT_NO_VERIFY, N.LA_ZSTD_OPT_LANE_KERNEL, N.LA_ZSTD_OPT_BLOCK_PARALLEL
+# la_zstdc_batch.flags (compress_to_frames)
+LA_ZSTDC_CHECKSUM, LA_ZSTDC_RAW_LITERALS = N.LA_ZSTDC_CHECKSUM, N.LA_ZSTDC_RAW_LITERALS
+LA_ZSTDC_FULL_ALPHABET, LA_ZSTDC_FIT_TABLES = N.LA_ZSTDC_FULL_ALPHABET, N.LA_ZSTDC_FIT_TABLES
 
 
 class _IndexResultC(C.Structure):
