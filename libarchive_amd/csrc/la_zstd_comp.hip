@@ -19,22 +19,24 @@
  *       Literals section: RLE when all literals are one byte; Raw under LA_ZSTDC_RAW_LITERALS, for fewer than 32
  *       literals or, without LA_ZSTDC_FULL_ALPHABET, a largest byte above 128; otherwise Huffman: an LDS histogram, Shannon lengths clamped to 11 bits
  *       and made complete (Kraft sum exactly 1) by greedy lengthening / shortening with wave-wide arg-max rounds,
- *       direct 4-bit weights, one stream up to 1023 literals and four with the jump table above.  Streams are encoded
+ *       direct 4-bit weights (zc_weight), one stream up to 1023 literals and four with the jump table above.  Streams are encoded
  *       in parallel: every literal's bit position is a wave prefix sum of code lengths (reverse symbol order, a
  *       Huffman stream is read backwards), lanes OR their bits into an LDS stage and whole dwords leave
  *       (wave_bits_append, shared with deflate_fixed_kernel).  Sections whose coded form would not be smaller are written raw.
  *       LA_ZSTDC_FULL_ALPHABET: any largest byte; the weights also go through zc_weights_fse (their histogram
- *       normalised a lane per weight, two interleaved FSE states, written backwards by the serial bit writer) and the
+ *       normalised a lane per weight, two interleaved FSE states, written backwards by the serial bit writer zc_bw) and the
  *       smaller allowed description is written; weights that are all equal have no FSE form (raw above 128 of them).
- *       Sequences section: Predefined_Mode for LL, OF and ML; the interleaved FSE stream is written last sequence
- *       first, uniformly by the wave (64 sequences' codes and extra bits computed lane-parallel, then taken one by
- *       one with v_readlane), with encoder tables (symbol x next state -> state) spread from the decoder's own
- *       fse_build in LDS.  LA_ZSTDC_FIT_TABLES (zc_sequences_fit): LDS histograms of the three codes, per field
+ *       Sequences section (zc_sequences_predefined): Predefined_Mode for LL, OF and ML, with encoder tables (symbol x
+ *       next state -> state, zc_enc_predefined) spread from the decoder's own fse_build in LDS; the interleaved FSE
+ *       stream is written last sequence first, uniformly by the wave (zc_seq_chain, the one chain of both table
+ *       forms: 64 sequences' codes and extra bits computed lane-parallel, then taken one by one with v_readlane).
+ *       LA_ZSTDC_FIT_TABLES (zc_sequences_fit): LDS histograms of the three codes, per field
  *       RLE_Mode for a single code, FSE_Compressed_Mode when counts normalised from the histogram (accuracy log from
  *       the sequence count, 5 .. 9, 8 for offsets) are estimated cheaper than the predefined table by more than a
  *       byte, Predefined_Mode otherwise, never Repeat_Mode; the same chain then runs on compact encoder tables (the
- *       states of every symbol in next-state order, zc_fse_step) with every field's own accuracy log.  Flags without
- *       the two run the kernel's <false> instance, which holds none of this: the code and the bytes they had.
+ *       states of every symbol in next-state order, zc_fse_step, zc_enc_fitted) with every field's own accuracy log.
+ *       Flags without the two run the kernel's <false> instance, which holds none of this: the code and the bytes
+ *       they had.
  *       A block whose compressed form is not smaller than its input is a Raw_Block.
  *   frame_sums_kernel             XXH64 of every frame's input (la_comp_common.h), four lanes per frame.
  *   zstdc_sizes_kernel / scan     stream bytes of every block (header + payload, frame header and checksum).
@@ -114,6 +116,9 @@ __device__ __forceinline__ uint32_t ml_code(uint32_t ml)
 	return c;
 }
 
+/* Huffman weight of a symbol whose code is len bits long in a tree whose longest code is lmax (RFC 8878 4.2.1) */
+__device__ __forceinline__ uint32_t zc_weight(uint32_t len, uint32_t lmax) { return len ? lmax + 1u - len : 0u; }
+
 /* literals section header for Raw (type 0) / RLE (type 1): 1, 2 or 3 bytes */
 __device__ __forceinline__ uint32_t lit_hdr_rr(uint8_t *o, uint32_t type, uint32_t regen, bool write)
 {
@@ -170,6 +175,13 @@ struct zc_bw {
 	uint32_t n;
 	bool over;
 };
+/* an empty writer that continues out at byte op and stores nothing at or past cap */
+__device__ __forceinline__ zc_bw bw_open(uint8_t *out, uint32_t op, uint32_t cap)
+{
+	zc_bw w;
+	w.out = out; w.op = op; w.cap = cap; w.acc = 0; w.n = 0; w.over = false;
+	return w;
+}
 __device__ __forceinline__ void bw_put(zc_bw &w, uint32_t v, uint32_t nb, uint32_t lane)
 {
 	w.acc |= (uint64_t)v << w.n;
@@ -202,6 +214,7 @@ __device__ __forceinline__ uint32_t bw_close(zc_bw &w, uint32_t lane)
 	return w.op;
 }
 
+/* the one prefix sum written out in this file (wave_bits_append, la_comp_common.h, carries its own) */
 __device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t lane)
 {
 	uint32_t inc = v;
@@ -318,7 +331,7 @@ __device__ static uint32_t zc_weights_fse(zc_lds &L, uint32_t nw, uint32_t lmax,
 		L.wcnt[lane] = 0;
 	__syncthreads();
 	for (uint32_t s = lane; s < nw; s += 64)
-		atomicAdd(&L.wcnt[L.len[s] ? lmax + 1u - L.len[s] : 0u], 1u);
+		atomicAdd(&L.wcnt[zc_weight(L.len[s], lmax)], 1u);
 	__syncthreads();
 	const uint32_t h = lane < 16 ? L.wcnt[lane] : 0u;
 	const uint64_t present = __ballot(h != 0);
@@ -340,11 +353,10 @@ __device__ static uint32_t zc_weights_fse(zc_lds &L, uint32_t nw, uint32_t lmax,
 	__syncthreads();
 	zc_enc_table(&F.t, al, F.sinfo, F.st, lane);
 	__syncthreads();
-	zc_bw w;
-	w.out = F.tree; w.op = 0; w.cap = 132; w.acc = 0; w.n = 0; w.over = false;
+	zc_bw w = bw_open(F.tree, 0, 132);
 	zc_put_ncount(w, F.norm, n_sym, al, lane);
 	bw_close(w, lane);
-	auto weight = [&](uint32_t s) { const uint32_t l = L.len[s]; return l ? lmax + 1u - l : 0u; };
+	auto weight = [&](uint32_t s) { return zc_weight(L.len[s], lmax); };
 	/* s0 / s1: the state of the even / odd chain at the position reached so far, from the end */
 	uint32_t s0 = zc_fse_first(F.st, F.sinfo, weight(nw - 1u)), s1 = zc_fse_first(F.st, F.sinfo, weight(nw - 2u));
 	if (!(nw & 1u)) {	/* the last weight stands at an odd position */
@@ -362,6 +374,117 @@ __device__ static uint32_t zc_weights_fse(zc_lds &L, uint32_t nw, uint32_t lmax,
 	const uint32_t end = bw_close(w, lane);
 	__syncthreads();
 	return (w.over || end >= 128u) ? 0u : end;
+}
+
+/* ---- the sequence chain over either form of encoder table.  An Enc answers, for field 0 = LL, 1 = OF, 2 = ML (a
+ * literal constant at every call): al(field), the accuracy log; first(field, sym), a state of sym for the block's last
+ * sequence; step(field, sym, t, bits, nb), the state of sym whose range holds next state t and the bits selecting t ---- */
+/* the predefined tables: [symbol][next state] bytes beside the decoder's entries */
+struct zc_enc_predefined {
+	const zc_fse_lds *f;
+	__device__ __forceinline__ const uint8_t *enc(uint32_t field) const { return field == 0 ? f->ell : field == 1 ? f->eof : f->eml; }
+	__device__ __forceinline__ const fse_tab &dec(uint32_t field) const { return field == 0 ? f->ll : field == 1 ? f->of : f->ml; }
+	__device__ __forceinline__ uint32_t al(uint32_t field) const { return field == 1 ? 5u : 6u; }
+	__device__ __forceinline__ uint32_t first(uint32_t field, uint32_t sym) const { return enc(field)[sym << al(field)]; }
+	__device__ __forceinline__ uint32_t step(uint32_t field, uint32_t sym, uint32_t t, uint32_t &bits, uint32_t &nb) const
+	{
+		const uint32_t u = enc(field)[(sym << al(field)) + t];
+		const fse_ent e = dec(field).e[u];
+		bits = t - e.base; nb = e.nbits;
+		return u;
+	}
+};
+/* tables fitted to the block: the compact encoder, every field with its own accuracy log (als: a byte each) */
+struct zc_enc_fitted {
+	const zc_fit_lds *f;
+	uint32_t als;
+	__device__ __forceinline__ uint32_t al(uint32_t field) const { return (als >> (8u * field)) & 255u; }
+	__device__ __forceinline__ uint32_t first(uint32_t field, uint32_t sym) const { return zc_fse_first(f->st[field], f->sinfo[field], sym); }
+	__device__ __forceinline__ uint32_t step(uint32_t field, uint32_t sym, uint32_t t, uint32_t &bits, uint32_t &nb) const
+	{ return zc_fse_step(f->st[field], f->sinfo[field], al(field), sym, t, bits, nb); }
+};
+
+/* The interleaved FSE stream of a block's sequences: last sequence first, 64 at a time (lane j prepares sequence
+ * hi - 1 - j), then the initial states and the end mark.  The caller closes the writer. */
+template <typename Enc>
+__device__ __forceinline__ void zc_seq_chain(zc_bw &w, const Enc enc, const uint64_t *seqs, uint32_t nseq, uint32_t lane)
+{
+	uint32_t sl = 0, sm = 0, sof = 0;
+	for (uint32_t hi = nseq; hi > 0;) {
+		const uint32_t cnt = hi < 64u ? hi : 64u;
+		uint32_t codes = 0, lmx = 0, lmbits = 0, ov = 0;
+		if (lane < cnt) {
+			const uint64_t s = seqs[hi - 1u - lane];
+			const uint32_t ll = (uint32_t)(s & 0xFFFFFu), ml = (uint32_t)((s >> 20) & 0xFFFFFu), off = (uint32_t)(s >> 40);
+			const uint32_t lc = ll_code(ll), mc = ml_code(ml);
+			ov = off + 3u;
+			const uint32_t oc = (uint32_t)highbit(ov);
+			codes = lc | (mc << 8) | (oc << 16);
+			lmx = (ll - SEQ_TABS.ll_base[lc]) | ((ml - SEQ_TABS.ml_base[mc]) << 16);
+			lmbits = SEQ_TABS.ll_bits[lc] | ((uint32_t)SEQ_TABS.ml_bits[mc] << 8);
+			ov -= 1u << oc;
+		}
+		for (uint32_t j = 0; j < cnt; j++) {
+			const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)codes, (int)j);
+			const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lmx, (int)j);
+			const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)lmbits, (int)j);
+			const uint32_t ox = (uint32_t)__builtin_amdgcn_readlane((int)ov, (int)j);
+			const uint32_t lc = c & 255u, mc = (c >> 8) & 255u, oc = c >> 16;
+			if (hi == nseq && j == 0) {
+				/* the block's last sequence: any state of its symbols */
+				sl = enc.first(0, lc);
+				sof = enc.first(1, oc);
+				sm = enc.first(2, mc);
+			} else {
+				/* state of this sequence whose range holds the next one's state; the bits select it */
+				uint32_t bo, no, bm, nm, bl, nl;
+				sof = enc.step(1, oc, sof, bo, no);
+				sm = enc.step(2, mc, sm, bm, nm);
+				sl = enc.step(0, lc, sl, bl, nl);
+				bw_put(w, bo, no, lane);
+				bw_put(w, bm, nm, lane);
+				bw_put(w, bl, nl, lane);
+			}
+			/* extra bits: the decoder reads offset, match length, literal length */
+			bw_put(w, x & 0xFFFFu, b & 255u, lane);
+			bw_put(w, x >> 16, b >> 8, lane);
+			bw_put(w, ox, oc, lane);
+		}
+		hi -= cnt;
+	}
+	/* initial states, each as wide as its table's accuracy log: the decoder reads LL, OF, ML */
+	bw_put(w, sm, enc.al(2), lane);
+	bw_put(w, sof, enc.al(1), lane);
+	bw_put(w, sl, enc.al(0), lane);
+	bw_put(w, 1, 1, lane);	/* end mark */
+}
+
+/* The sequences section with Predefined_Mode for LL, OF and ML: the decoder's tables, the encoder bytes spread from
+ * them (for every state u, the next states its range covers lead back to u), the chain.  Returns as zc_sequences_fit. */
+__device__ __forceinline__ uint32_t zc_sequences_predefined(zc_fse_lds &F, const uint64_t *seqs, uint32_t nseq, uint8_t *out,
+    uint32_t op, uint32_t cap, uint32_t lane, bool &over)
+{
+	if (lane == 0) {
+		out[op] = 0;	/* Symbol_Compression_Modes */
+		fse_build(&F.ll, LL_DEF, 36, 6);
+		fse_build(&F.ml, ML_DEF, 53, 6);
+		fse_build(&F.of, OF_DEF, 29, 5);
+	}
+	__syncthreads();
+	const fse_ent e = F.ll.e[lane];
+	for (uint32_t t = 0; t < (1u << e.nbits); t++) F.ell[e.sym * 64u + e.base + t] = (uint8_t)lane;
+	const fse_ent m = F.ml.e[lane];
+	for (uint32_t t = 0; t < (1u << m.nbits); t++) F.eml[m.sym * 64u + m.base + t] = (uint8_t)lane;
+	if (lane < 32) {
+		const fse_ent o = F.of.e[lane];
+		for (uint32_t t = 0; t < (1u << o.nbits); t++) F.eof[o.sym * 32u + o.base + t] = (uint8_t)lane;
+	}
+	__syncthreads();
+	zc_bw w = bw_open(out, op + 1u, cap);
+	zc_seq_chain(w, zc_enc_predefined{ &F }, seqs, nseq, lane);
+	const uint32_t end = bw_close(w, lane);
+	over = w.over;
+	return end;
 }
 
 /* The sequences section behind Number_of_Sequences under LA_ZSTDC_FIT_TABLES (RFC 8878 3.1.1.3.2.1): the block's
@@ -383,8 +506,7 @@ __device__ static uint32_t zc_sequences_fit(zc_lds &L, const uint64_t *seqs, uin
 		atomicAdd(&F.hist[2][ml_code((uint32_t)((s >> 20) & 0xFFFFFu))], 1u);
 	}
 	__syncthreads();
-	zc_bw w;
-	w.out = out; w.op = op + 1u; w.cap = cap; w.acc = 0; w.n = 0; w.over = false;
+	zc_bw w = bw_open(out, op + 1u, cap);
 	uint32_t modes = 0, als = 0;	/* als: the three accuracy logs, a byte each */
 	bool stuck = false;
 	for (uint32_t f = 0; f < 3; f++) {
@@ -445,67 +567,21 @@ __device__ static uint32_t zc_sequences_fit(zc_lds &L, const uint64_t *seqs, uin
 			fse_build(&F.t[lane], F.norm[lane], 64, (int)((als >> (8u * lane)) & 255u));
 	}
 	__syncthreads();
-	const uint32_t al_l = als & 255u, al_o = (als >> 8) & 255u, al_m = (als >> 16) & 255u;
-	if ((modes >> 6) != 1u) zc_enc_table(&F.t[0], al_l, F.sinfo[0], F.st[0], lane);
-	if (((modes >> 4) & 3u) != 1u) zc_enc_table(&F.t[1], al_o, F.sinfo[1], F.st[1], lane);
-	if (((modes >> 2) & 3u) != 1u) zc_enc_table(&F.t[2], al_m, F.sinfo[2], F.st[2], lane);
+	const zc_enc_fitted enc = { &F, als };
+	for (uint32_t f = 0; f < 3; f++)
+		if (((modes >> (6u - 2u * f)) & 3u) != 1u)
+			zc_enc_table(&F.t[f], enc.al(f), F.sinfo[f], F.st[f], lane);
 	__syncthreads();
-	uint32_t sl = 0, sm = 0, sof = 0;
-	/* last sequence first, 64 at a time: lane j prepares sequence hi - 1 - j */
-	for (uint32_t hi = nseq; hi > 0;) {
-		const uint32_t cnt = hi < 64u ? hi : 64u;
-		uint32_t codes = 0, lmx = 0, lmbits = 0, ov = 0;
-		if (lane < cnt) {
-			const uint64_t s = seqs[hi - 1u - lane];
-			const uint32_t ll = (uint32_t)(s & 0xFFFFFu), ml = (uint32_t)((s >> 20) & 0xFFFFFu), off = (uint32_t)(s >> 40);
-			const uint32_t lc = ll_code(ll), mc = ml_code(ml);
-			ov = off + 3u;
-			const uint32_t oc = (uint32_t)highbit(ov);
-			codes = lc | (mc << 8) | (oc << 16);
-			lmx = (ll - SEQ_TABS.ll_base[lc]) | ((ml - SEQ_TABS.ml_base[mc]) << 16);
-			lmbits = SEQ_TABS.ll_bits[lc] | ((uint32_t)SEQ_TABS.ml_bits[mc] << 8);
-			ov -= 1u << oc;
-		}
-		for (uint32_t j = 0; j < cnt; j++) {
-			const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)codes, (int)j);
-			const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lmx, (int)j);
-			const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)lmbits, (int)j);
-			const uint32_t ox = (uint32_t)__builtin_amdgcn_readlane((int)ov, (int)j);
-			const uint32_t lc = c & 255u, mc = (c >> 8) & 255u, oc = c >> 16;
-			if (hi == nseq && j == 0) {
-				/* the block's last sequence: any state of its symbols */
-				sl = zc_fse_first(F.st[0], F.sinfo[0], lc);
-				sof = zc_fse_first(F.st[1], F.sinfo[1], oc);
-				sm = zc_fse_first(F.st[2], F.sinfo[2], mc);
-			} else {
-				/* state of this sequence whose range holds the next one's state; the bits select it */
-				uint32_t bo, no, bm, nm, bl, nl;
-				sof = zc_fse_step(F.st[1], F.sinfo[1], al_o, oc, sof, bo, no);
-				sm = zc_fse_step(F.st[2], F.sinfo[2], al_m, mc, sm, bm, nm);
-				sl = zc_fse_step(F.st[0], F.sinfo[0], al_l, lc, sl, bl, nl);
-				bw_put(w, bo, no, lane);
-				bw_put(w, bm, nm, lane);
-				bw_put(w, bl, nl, lane);
-			}
-			/* extra bits: the decoder reads offset, match length, literal length */
-			bw_put(w, x & 0xFFFFu, b & 255u, lane);
-			bw_put(w, x >> 16, b >> 8, lane);
-			bw_put(w, ox, oc, lane);
-		}
-		hi -= cnt;
-	}
-	/* initial states, each as wide as its table's accuracy log: the decoder reads LL, OF, ML */
-	bw_put(w, sm, al_m, lane);
-	bw_put(w, sof, al_o, lane);
-	bw_put(w, sl, al_l, lane);
-	bw_put(w, 1, 1, lane);	/* end mark */
+	zc_seq_chain(w, enc, seqs, nseq, lane);
 	const uint32_t end = bw_close(w, lane);
 	over = w.over || stuck;
 	return end;
 }
 
 /* ENTROPY: the instance for flags with LA_ZSTDC_FULL_ALPHABET or LA_ZSTDC_FIT_TABLES.  The other instance holds none
- * of their code, so the flags from before them run the kernel they always ran. */
+ * of their code, so the flags from before them run the kernel they always ran.  The body up to the sequences section
+ * is one piece on purpose: with the matcher or the literals section as functions, inlined or called, and even with only
+ * the small steps around them moved out, it measured 0.4 .. 2 % slower (profiles/r16_zstd_comp_refactor.txt). */
 template <bool ENTROPY>
 __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t *__restrict__ src, uint64_t src_bytes,
     uint32_t block_size, uint32_t n_blocks, uint32_t flags, uint8_t *__restrict__ tmp, uint8_t *__restrict__ lits_ws,
@@ -653,7 +729,7 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 		lmax = wave_max(lmax);
 		__syncthreads();
 		if (K == 2048u) {
-			/* canonical codes exactly as the decoder lays them out: by weight ascending, then by symbol */
+			/* canonical codes exactly as the decoder lays them out: by weight ascending, then by symbol (a used symbol's weight) */
 			if (lane == 0) {
 				for (uint32_t w = 0; w < 16; w++) L.wcnt[w] = 0;
 				for (uint32_t s = 0; s <= maxsym; s++)
@@ -714,8 +790,7 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 				/* direct 4-bit weights, two per byte, the first in the high nibble */
 				for (uint32_t k = lane; k < (fse_bytes ? 0u : (nw + 1u) / 2u); k += 64) {
 					const uint32_t s0 = 2u * k, s1 = 2u * k + 1u;
-					const uint32_t w0 = L.len[s0] ? lmax + 1u - L.len[s0] : 0u;
-					const uint32_t w1 = (s1 < nw && L.len[s1]) ? lmax + 1u - L.len[s1] : 0u;
+					const uint32_t w0 = zc_weight(L.len[s0], lmax), w1 = s1 < nw ? zc_weight(L.len[s1], lmax) : 0u;
 					out[hl + 1u + k] = (uint8_t)((w0 << 4) | w1);
 				}
 				op = hl + tree;
@@ -763,83 +838,7 @@ __global__ __launch_bounds__(64) void zstd_compress_blocks_kernel(const uint8_t 
 	if (ENTROPY && nseq > 0 && (flags & LA_ZSTDC_FIT_TABLES)) {
 		op = zc_sequences_fit(L, seqs, nseq, out, op, cap, lane, over);
 	} else if (nseq > 0) {
-		if (lane == 0) {
-			out[op] = 0;	/* Symbol_Compression_Modes: Predefined_Mode for LL, OF and ML */
-			fse_build(&L.u.f.ll, LL_DEF, 36, 6);
-			fse_build(&L.u.f.ml, ML_DEF, 53, 6);
-			fse_build(&L.u.f.of, OF_DEF, 29, 5);
-		}
-		op += 1;
-		__syncthreads();
-		/* encoder tables: for every state u, the next states its range covers lead back to u */
-		{
-			const fse_ent e = L.u.f.ll.e[lane];
-			for (uint32_t t = 0; t < (1u << e.nbits); t++) L.u.f.ell[e.sym * 64u + e.base + t] = (uint8_t)lane;
-			const fse_ent m = L.u.f.ml.e[lane];
-			for (uint32_t t = 0; t < (1u << m.nbits); t++) L.u.f.eml[m.sym * 64u + m.base + t] = (uint8_t)lane;
-			if (lane < 32) {
-				const fse_ent o = L.u.f.of.e[lane];
-				for (uint32_t t = 0; t < (1u << o.nbits); t++) L.u.f.eof[o.sym * 32u + o.base + t] = (uint8_t)lane;
-			}
-		}
-		__syncthreads();
-		zc_bw w;
-		w.out = out; w.op = op; w.cap = cap; w.acc = 0; w.n = 0; w.over = false;
-		uint32_t sl = 0, sm = 0, sof = 0;
-		/* last sequence first, 64 at a time: lane j prepares sequence hi - 1 - j */
-		for (uint32_t hi = nseq; hi > 0;) {
-			const uint32_t cnt = hi < 64u ? hi : 64u;
-			uint32_t codes = 0, lmx = 0, lmbits = 0, ov = 0;
-			if (lane < cnt) {
-				const uint64_t s = seqs[hi - 1u - lane];
-				const uint32_t ll = (uint32_t)(s & 0xFFFFFu), ml = (uint32_t)((s >> 20) & 0xFFFFFu), off = (uint32_t)(s >> 40);
-				const uint32_t lc = ll_code(ll), mc = ml_code(ml);
-				ov = off + 3u;
-				const uint32_t oc = (uint32_t)highbit(ov);
-				codes = lc | (mc << 8) | (oc << 16);
-				lmx = (ll - SEQ_TABS.ll_base[lc]) | ((ml - SEQ_TABS.ml_base[mc]) << 16);
-				lmbits = SEQ_TABS.ll_bits[lc] | ((uint32_t)SEQ_TABS.ml_bits[mc] << 8);
-				ov -= 1u << oc;
-			}
-			for (uint32_t j = 0; j < cnt; j++) {
-				const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)codes, (int)j);
-				const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lmx, (int)j);
-				const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)lmbits, (int)j);
-				const uint32_t ox = (uint32_t)__builtin_amdgcn_readlane((int)ov, (int)j);
-				const uint32_t lc = c & 255u, mc = (c >> 8) & 255u, oc = c >> 16;
-				if (hi == nseq && j == 0) {
-					/* the block's last sequence: any state of its symbols */
-					sl = L.u.f.ell[lc * 64u]; sm = L.u.f.eml[mc * 64u]; sof = L.u.f.eof[oc * 32u];
-				} else {
-					/* state of this sequence whose range holds the next one's state; the bits select it */
-					const uint32_t uo = L.u.f.eof[oc * 32u + sof], um = L.u.f.eml[mc * 64u + sm], ul = L.u.f.ell[lc * 64u + sl];
-					const fse_ent eo = L.u.f.of.e[uo], em = L.u.f.ml.e[um], el = L.u.f.ll.e[ul];
-					bw_put(w, sof - eo.base, eo.nbits, lane);
-					bw_put(w, sm - em.base, em.nbits, lane);
-					bw_put(w, sl - el.base, el.nbits, lane);
-					sl = ul; sm = um; sof = uo;
-				}
-				/* extra bits: the decoder reads offset, match length, literal length */
-				bw_put(w, x & 0xFFFFu, b & 255u, lane);
-				bw_put(w, x >> 16, b >> 8, lane);
-				bw_put(w, ox, oc, lane);
-			}
-			hi -= cnt;
-		}
-		/* initial states: the decoder reads LL, OF, ML */
-		bw_put(w, sm, 6, lane);
-		bw_put(w, sof, 5, lane);
-		bw_put(w, sl, 6, lane);
-		bw_put(w, 1, 1, lane);	/* end mark */
-		const uint32_t tail = (w.n + 7u) >> 3;
-		if (w.op + tail > cap) {
-			w.over = true;
-		} else if (lane == 0) {
-			for (uint32_t k = 0; k < tail; k++)
-				out[w.op + k] = (uint8_t)(w.acc >> (8u * k));
-		}
-		op = w.op + tail;
-		over = w.over;
+		op = zc_sequences_predefined(L.u.f, seqs, nseq, out, op, cap, lane, over);
 	}
 	if (lane == 0) {
 		const bool comp = !over && op < n;

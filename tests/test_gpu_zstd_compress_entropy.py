@@ -202,3 +202,36 @@ def test_flagless_images_are_the_parents(gpu_ctx):
         name, bs, bpf, flags = key.split("/")
         img = T.compress(gpu_ctx, DATA[name], int(bs), int(bpf), int(flags))
         assert hashlib.sha256(img).hexdigest() == digest, key
+
+
+# ---------------------------------------------------------------- 5. nor did the entropy flags' images
+GOLDEN_ENTROPY = os.path.join(os.path.dirname(GOLDEN), "zstd_compress_entropy_parent.json")
+
+
+def pinned_entropy_images(gpu_ctx):
+    """(key, image) of everything tests/golden/zstd_compress_entropy_parent.json pins -- written by
+    tools/record_zstd_entropy_digests.py from the library as it was before the two copies of the sequence chain became
+    one --: every image of this module, from its cache, and the block of test_sequences_that_cost_more_than_they_save,
+    seeded as there, which drives the sequence bit writer past its room, through either instance of the kernel"""
+    for name, _ in INPUTS:
+        for shape in SHAPES:
+            for flags in FLAGS:
+                yield "%s/%d/%d/%d" % (name, shape[0], shape[1], flags), image(gpu_ctx, name, shape, flags, parsed=False)[0]
+    import random
+    import zstd_edge_inputs as E
+    rnd = random.Random(0xC057)
+    T._text(rnd, 131072)
+    costly = E.costly_block(rnd)
+    for flags in (CHECKSUM, FULL | FIT | CHECKSUM):
+        yield "costly_block/131072/1/%d" % flags, T.compress(gpu_ctx, costly, 131072, 1, flags)
+
+
+def test_entropy_images_are_the_parents(gpu_ctx):
+    with open(GOLDEN_ENTROPY) as f:
+        golden = json.load(f)
+    assert len(golden) == 28 * 3 * 4 + 2
+    seen = 0
+    for key, img in pinned_entropy_images(gpu_ctx):
+        assert hashlib.sha256(img).hexdigest() == golden[key], key
+        seen += 1
+    assert seen == len(golden)
