@@ -31,6 +31,7 @@ extern "C" {
 /* archive.h:307-321 */
 #define ARCHIVE_FILTER_NONE 0
 #define ARCHIVE_FILTER_GZIP 1
+#define ARCHIVE_FILTER_BZIP2 2
 #define ARCHIVE_FILTER_LZ4  13
 #define ARCHIVE_FILTER_ZSTD 14
 
@@ -51,6 +52,7 @@ typedef int     archive_close_callback(struct archive *, void *client_data);
 
 struct archive *archive_read_new(void);						/* archive.h:398 */
 int  archive_read_support_filter_all(struct archive *);				/* archive.h:457 */
+int  archive_read_support_filter_bzip2(struct archive *);			/* archive.h:461 */
 int  archive_read_support_filter_gzip(struct archive *);			/* archive.h:466 */
 int  archive_read_support_compression_gzip(struct archive *);			/* deprecated alias, gzip.c:85-92 */
 int  archive_read_support_filter_lz4(struct archive *);				/* archive.h:469 */

@@ -102,8 +102,17 @@ enum {
 	/* LA_GZ_OPT_PIECES only: how a PIECE of one raw-deflate stream ends when its stream does not end in it */
 	LA_ST_GZ_PIECE_END        = 18,	/* a non-final block ended on a byte boundary and on the last byte of the span:
 					 * the next piece starts right behind it (consumed == src_len) */
-	LA_ST_GZ_NEEDS_HISTORY    = 19	/* a match reaches in front of the piece's first output byte: the blocks behind this
+	LA_ST_GZ_NEEDS_HISTORY    = 19,	/* a match reaches in front of the piece's first output byte: the blocks behind this
 					 * flush point depend on earlier output (Z_SYNC_FLUSH), the piece cannot be decoded alone */
+	/* bzip2.c:326-329 -> "bzip decompression failed", :282-286 -> "truncated bzip2 input" */
+	LA_ST_BZ2_DATA            = 20,	/* what libbz2 answers BZ_DATA_ERROR for inside a block: a table, selector or symbol
+					 * that cannot be, more symbols than the level allows, origPtr outside the block */
+	LA_ST_BZ2_TRUNCATED       = 21,	/* the candidate's decode runs off the end of d_src */
+	LA_ST_BZ2_BAD_CRC         = 22,	/* a block's bytes do not give its header's CRC (the bytes are delivered, as libbz2 emits
+					 * them before it compares), or a stream's combined CRC is not the stored one */
+	LA_ST_BZ2_REFUTED         = 23,	/* the chain of confirmed blocks does not pass through this candidate: 48 bits of
+					 * compressed data that look like a magic, or an entry behind the point where the walk ended */
+	LA_ST_BZ2_RANDOMISED      = 24	/* the block's randomised bit is set (bzip2 0.9.0 and older): not decoded, a data error */
 };
 
 /* =====================================================================
@@ -534,6 +543,104 @@ uint64_t la_gpu_zstd_compress_workspace_bytes(uint64_t src_bytes, uint32_t block
 /* upper bound of the stream la_gpu_zstd_compress writes for this shape: the input, 3 bytes per block, 13 per frame */
 uint64_t la_gpu_zstd_compress_bound(uint64_t src_bytes, uint32_t block_size, uint32_t blocks_per_frame);
 int      la_gpu_zstd_compress(la_gpu_ctx *ctx, const la_zstdc_batch *batch);
+
+/* =====================================================================
+ * bzip2 -- replaces, for a window of a stream per call, the BZ2_bzDecompress loop of bzip2_filter_read
+ * (libarchive/archive_read_support_filter_bzip2.c:214-332; libbz2 is the reference's external dependency for this
+ * codec).  A bzip2 stream is "BZh" + level digit, then blocks of at most 100 000 x level bytes, each behind the 48-bit
+ * magic 0x314159265359 at ANY bit position, then the end magic 0x177245385090 + the 32-bit combined CRC, padded to a
+ * byte.  Blocks are independent, so the block is the parallel unit: one workgroup per block.
+ *
+ * la_gpu_bzip2_scan finds every bit position of d_src[0, src_bytes) where one of the two magics starts (all 48 bits
+ * inside the source) and writes them in ascending order to d_cands[0, min(count, cand_cap)); *d_count is the number
+ * found.  A match is a CANDIDATE: 48 bits of compressed data can look like a magic.
+ *
+ * la_gpu_bzip2_decode runs twice over one candidate table, workspace kept between the calls (no other call on the
+ * context in between; n, slot_level and options the same).
+ *   LA_BZ2_MEASURE decodes every block candidate from its own bit position up to its end-of-block symbol (entropy
+ * decode, inverse BWT by a parallel chase, length of the run-length expansion), then confirms candidates in stream
+ * order from state_in: candidate k + 1 is confirmed only if it starts where the confirmed candidate in front of it
+ * ends; behind an end-of-stream candidate the walk takes the stored CRC, goes to the next byte and asks for "BZh[1-9]"
+ * and a candidate 32 bits on (the bid rule, bzip2.c:112-148).  Results: status, level, out_len, end_bit, dst_off (the
+ * exclusive scan of out_len over confirmed blocks) per entry; an entry the walk does not pass through is
+ * LA_ST_BZ2_REFUTED with out_len 0.  d_state_out says where and why the walk ended.
+ *   LA_BZ2_EMIT expands the confirmed blocks among entries [0, n_emit) whose packed end lies inside dst_cap into
+ * d_dst, fills in crc, compares block CRCs with their headers and combined CRCs with the end-of-stream entries
+ * (LA_ST_BZ2_BAD_CRC in the entry's status), and writes d_state_out again: the stream state behind the last entry it
+ * took, first_bad = the first failing entry in stream order.  A block that ends on four equal bytes without their count
+ * is emitted as libbz2 emits it (with the count it makes up from the byte behind the block's last) and then fails with
+ * LA_ST_BZ2_DATA; it is the first_bad entry as a wrong CRC is, its bytes count in total_out.
+ * Blocks with the randomised bit are LA_ST_BZ2_RANDOMISED.  Additions under ABI version 3.
+ * ===================================================================== */
+#define LA_BZ2_KIND_BLOCK 0u
+#define LA_BZ2_KIND_END   1u
+typedef struct la_bz2_cand {
+	uint64_t bit_off;	/* first bit of the magic, counted from the most significant bit of d_src[0] */
+	uint32_t kind;		/* LA_BZ2_KIND_* */
+	uint32_t reserved;
+} la_bz2_cand;
+
+typedef struct la_bz2_result {
+	uint32_t status;	/* LA_ST_* */
+	uint32_t level;		/* level digit (1 .. 9) of the stream the entry belongs to; 0 if refuted */
+	uint64_t out_len;	/* decoded bytes of a confirmed block; 0 for everything else */
+	uint64_t end_bit;	/* block: the bit behind its end-of-block symbol; end of stream: the byte boundary behind the CRC */
+	uint64_t dst_off;	/* where a confirmed block's bytes go in d_dst */
+	uint32_t crc;		/* EMIT: bzip2 CRC of the block's bytes; end of stream: the combined CRC of its blocks */
+	uint32_t stored_crc;	/* the CRC the header (or the end of stream) carries */
+} la_bz2_result;
+
+/* how the walk ended (la_bz2_state.stop) */
+#define LA_BZ2_STOP_TABLE   0u	/* every entry of the table was passed or refuted and the stream goes on at stop_bit: no
+				 * candidate there (the host decides: more input, a damaged magic, the end of the input) */
+#define LA_BZ2_STOP_ENTRY   1u	/* entry stop_entry is the next unit and cannot be taken: see its status (a block that
+				 * is damaged, truncated or randomised; an end of stream whose CRC lies outside d_src) */
+#define LA_BZ2_STOP_BID     2u	/* behind an end of stream, 14 bytes are there and are no "BZh[1-9]" + magic */
+#define LA_BZ2_STOP_SHORT   3u	/* behind an end of stream (or at the start), fewer than 14 bytes are left */
+#define LA_BZ2_STOP_LEVEL   4u	/* a stream begins at stop_bit whose level is above slot_level: decode on from there */
+
+typedef struct la_bz2_state {
+	uint32_t open;		/* 1: inside a stream (a block or end magic is next); 0: a stream header is next */
+	uint32_t level;		/* open: the stream's level digit 1 .. 9 */
+	uint32_t crc;		/* open: the combined CRC of the stream's blocks so far */
+	uint32_t stop;		/* out: LA_BZ2_STOP_* */
+	uint64_t start_bit;	/* in: where the next unit starts in d_src.  out (stop_bit): where the walk ended */
+	uint64_t total_out;	/* out: decoded bytes of the confirmed (MEASURE) / emitted (EMIT) blocks */
+	uint32_t n_taken;	/* out: entries [0, n_taken) were passed: confirmed or refuted */
+	uint32_t stop_entry;	/* out: LA_BZ2_STOP_ENTRY */
+	uint32_t first_bad;	/* out, EMIT: first entry that failed behind its bytes (LA_ST_BZ2_BAD_CRC, or LA_ST_BZ2_DATA for the
+				 * missing count), 0xFFFFFFFF if none */
+	uint32_t reserved;
+} la_bz2_state;
+
+#define LA_BZ2_MEASURE 0u
+#define LA_BZ2_EMIT    1u
+#define LA_BZ2_OPT_SERIAL_CHASE 1u	/* inverse BWT by the plain serial chase (the fallback of the parallel one, and its cross-check) */
+
+typedef struct la_bz2_batch {
+	const uint8_t     *d_src;
+	uint64_t           src_bytes;
+	const la_bz2_cand *d_cands;	/* device-resident, ascending bit_off */
+	uint32_t           n;		/* at most la_gpu_bzip2_max_blocks(slot_level) */
+	uint32_t           phase;	/* LA_BZ2_MEASURE, LA_BZ2_EMIT */
+	uint8_t           *d_dst;	/* EMIT */
+	uint64_t           dst_cap;
+	la_bz2_result     *d_results;	/* [n] */
+	const la_bz2_state *state_in;	/* HOST memory, read during the call */
+	la_bz2_state      *d_state_out;	/* one record on the device */
+	uint32_t           options;	/* LA_BZ2_OPT_* */
+	uint32_t           slot_level;	/* 1 .. 9: every block gets a workspace slot for 100 000 x slot_level bytes */
+	uint32_t           n_emit;	/* EMIT: entries [0, n_emit) */
+	uint32_t           reserved;
+} la_bz2_batch;
+
+/* how many candidates one decode call slots at this level (the table may be longer: pass its front) */
+uint32_t la_gpu_bzip2_max_blocks(uint32_t slot_level);
+uint64_t la_gpu_bzip2_workspace_bytes(uint32_t n, uint32_t slot_level);
+/* ws: counts of the compaction, src_bytes / 16 words and the scan's scratch */
+int      la_gpu_bzip2_scan(la_gpu_ctx *ctx, const uint8_t *d_src, uint64_t src_bytes, la_bz2_cand *d_cands, uint32_t cand_cap,
+    uint32_t *d_count);
+int      la_gpu_bzip2_decode(la_gpu_ctx *ctx, const la_bz2_batch *batch);
 
 #ifdef __cplusplus
 }

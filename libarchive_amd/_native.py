@@ -86,6 +86,33 @@ LA_ZSTDC_FULL_ALPHABET, LA_ZSTDC_FIT_TABLES = 4, 8
 LA_ZSTD_OPT_NO_VERIFY, LA_ZSTD_OPT_LANE_KERNEL, LA_ZSTD_OPT_BLOCK_PARALLEL = 1, 2, 4     # la_zstd_batch.options
 
 
+# bzip2 (la_bz2_cand, la_bz2_result, la_bz2_state, la_bz2_batch)
+BZ2_CAND_DTYPE = np.dtype([("bit_off", "<u8"), ("kind", "<u4"), ("reserved", "<u4")])
+BZ2_RESULT_DTYPE = np.dtype([("status", "<u4"), ("level", "<u4"), ("out_len", "<u8"), ("end_bit", "<u8"), ("dst_off", "<u8"),
+                             ("crc", "<u4"), ("stored_crc", "<u4")])
+BZ2_STATE_DTYPE = np.dtype([("open", "<u4"), ("level", "<u4"), ("crc", "<u4"), ("stop", "<u4"), ("start_bit", "<u8"),
+                            ("total_out", "<u8"), ("n_taken", "<u4"), ("stop_entry", "<u4"), ("first_bad", "<u4"),
+                            ("reserved", "<u4")])
+LA_BZ2_KIND_BLOCK, LA_BZ2_KIND_END = 0, 1
+LA_BZ2_MEASURE, LA_BZ2_EMIT = 0, 1
+LA_BZ2_OPT_SERIAL_CHASE = 1
+LA_BZ2_STOP_TABLE, LA_BZ2_STOP_ENTRY, LA_BZ2_STOP_BID, LA_BZ2_STOP_SHORT, LA_BZ2_STOP_LEVEL = 0, 1, 2, 3, 4
+LA_ST_BZ2_DATA, LA_ST_BZ2_TRUNCATED, LA_ST_BZ2_BAD_CRC, LA_ST_BZ2_REFUTED, LA_ST_BZ2_RANDOMISED = 20, 21, 22, 23, 24
+
+
+class _Bz2StateC(C.Structure):
+    _fields_ = [("open", C.c_uint32), ("level", C.c_uint32), ("crc", C.c_uint32), ("stop", C.c_uint32),
+                ("start_bit", C.c_uint64), ("total_out", C.c_uint64), ("n_taken", C.c_uint32), ("stop_entry", C.c_uint32),
+                ("first_bad", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _Bz2BatchC(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("d_cands", C.c_void_p), ("n", C.c_uint32),
+                ("phase", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p),
+                ("state_in", C.POINTER(_Bz2StateC)), ("d_state_out", C.c_void_p), ("options", C.c_uint32),
+                ("slot_level", C.c_uint32), ("n_emit", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _GzcFramingC(C.Union):     # the header's anonymous union: `reserved` is the field's earlier name
     _fields_ = [("framing", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -201,6 +228,12 @@ def gpu_lib():
         lib.la_gpu_zip_compress_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_zip_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         lib.la_gpu_zstd_compress.argtypes = [C.c_void_p, C.POINTER(_ZstdcBatchC)]
+        lib.la_gpu_bzip2_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.la_gpu_bzip2_decode.argtypes = [C.c_void_p, C.POINTER(_Bz2BatchC)]
+        lib.la_gpu_bzip2_max_blocks.restype = C.c_uint32
+        lib.la_gpu_bzip2_max_blocks.argtypes = [C.c_uint32]
+        lib.la_gpu_bzip2_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_bzip2_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]
         lib.la_gpu_zstd_compress_bound.restype = C.c_uint64
         lib.la_gpu_zstd_compress_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         lib.la_gpu_zstd_compress_workspace_bytes.restype = C.c_uint64
@@ -415,6 +448,12 @@ class GpuContext:
         if rc != LA_ERR_ARG:
             self._check(rc, "la_gpu_zip_compress")
         return rc
+
+    def bzip2_scan(self, d_src_ptr, src_bytes, d_cands_ptr, cand_cap, d_count_ptr):
+        self._check(gpu_lib().la_gpu_bzip2_scan(self._h, d_src_ptr, src_bytes, d_cands_ptr, cand_cap, d_count_ptr), "la_gpu_bzip2_scan")
+
+    def bzip2_decode(self, batch: _Bz2BatchC):
+        self._check(gpu_lib().la_gpu_bzip2_decode(self._h, C.byref(batch)), "la_gpu_bzip2_decode")
 
     def gzip_decode(self, batch: _GzBatchC):
         self._check(gpu_lib().la_gpu_gzip_decode(self._h, C.byref(batch)), "la_gpu_gzip_decode")

@@ -484,6 +484,63 @@ int la_gpu_zstd_decode(la_gpu_ctx *c, const la_zstd_batch *bt)
 	return LA_OK;
 }
 
+uint32_t la_gpu_bzip2_max_blocks(uint32_t slot_level)
+{
+	return slot_level >= 1 && slot_level <= 9 ? la_bzip2_max_blocks(slot_level) : 0;
+}
+
+uint64_t la_gpu_bzip2_workspace_bytes(uint32_t n, uint32_t slot_level)
+{
+	return slot_level >= 1 && slot_level <= 9 ? la_bzip2_workspace_bytes(n, slot_level) : 0;
+}
+
+int la_gpu_bzip2_scan(la_gpu_ctx *c, const uint8_t *d_src, uint64_t src_bytes, la_bz2_cand *d_cands, uint32_t cand_cap, uint32_t *d_count)
+{
+	if (!c || !d_count || (src_bytes && !d_src) || (cand_cap && !d_cands) || src_bytes >= ((uint64_t)1 << 35))
+		return LA_ERR_ARG;
+	const uint64_t need = la_bzip2_scan_ws_bytes(src_bytes);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	prof_range(c, "bz2_scan", c->stream, [&] {
+		la_launch_bzip2_scan(c->stream, d_src, src_bytes, d_cands, cand_cap, d_count, (uint8_t *)c->ws);
+	});
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
+int la_gpu_bzip2_decode(la_gpu_ctx *c, const la_bz2_batch *bt)
+{
+	if (!c || !bt || !bt->state_in || !bt->d_state_out || bt->slot_level < 1 || bt->slot_level > 9 || bt->reserved)
+		return LA_ERR_ARG;
+	if (bt->phase != LA_BZ2_MEASURE && bt->phase != LA_BZ2_EMIT)
+		return LA_ERR_ARG;
+	if (bt->n > la_bzip2_max_blocks(bt->slot_level) || (bt->n && (!bt->d_cands || !bt->d_results)) || (bt->src_bytes && !bt->d_src))
+		return LA_ERR_ARG;
+	if (bt->phase == LA_BZ2_EMIT && bt->dst_cap && !bt->d_dst)
+		return LA_ERR_ARG;
+	const uint64_t need = la_bzip2_workspace_bytes(bt->n, bt->slot_level);
+	if (need > c->ws_bytes) {
+		if (bt->phase == LA_BZ2_EMIT)
+			return LA_ERR_ARG;	/* the workspace of the MEASURE call is gone */
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	uint8_t *ws = (uint8_t *)c->ws;
+	if (bt->phase == LA_BZ2_MEASURE) {
+		prof_range(c, "bz2_measure", c->stream, [&] { la_launch_bzip2_measure(c->stream, bt, ws); });
+		prof_range(c, "bz2_walk", c->stream, [&] { la_launch_bzip2_walk(c->stream, bt, ws); });
+	} else {
+		prof_range(c, "bz2_emit", c->stream, [&] { la_launch_bzip2_emit(c->stream, bt, ws); });
+		prof_range(c, "bz2_verify", c->stream, [&] { la_launch_bzip2_verify(c->stream, bt, ws); });
+	}
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 /* workspace of a gzip batch on the lane kernels: their scratch, then (two phases) E and the SEG launch's list; returns its size */
 static uint64_t gz_ws_carve(uint8_t *base, uint32_t n, bool two_phase, la_inflate_emit *E, uint32_t **big)
 {

@@ -552,6 +552,18 @@ const uint32_t *la_zstd_blocks_todo(const uint8_t *ws);
 void la_launch_zstd_blocks(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_zstd_frame *d_frames, uint32_t n,
     uint8_t *d_dst, uint64_t dst_cap, la_zstd_result *d_results, uint8_t *ws, uint32_t options);
 
+/* la_bzip2.hip */
+uint64_t la_bzip2_workspace_bytes(uint32_t n, uint32_t level);
+uint32_t la_bzip2_max_blocks(uint32_t level);
+uint64_t la_bzip2_scan_ws_bytes(uint64_t src_bytes);
+void la_launch_bzip2_scan(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, la_bz2_cand *d_cands, uint32_t cap,
+    uint32_t *d_count, uint8_t *ws);
+/* la_gpu_bzip2_decode: MEASURE = measure + walk, EMIT = emit + verify; all four carve the same workspace from (n, slot_level) */
+void la_launch_bzip2_measure(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
+void la_launch_bzip2_walk(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
+void la_launch_bzip2_emit(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
+void la_launch_bzip2_verify(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
+
 /* la_lz4_comp.hip */
 void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
