@@ -642,6 +642,52 @@ int      la_gpu_bzip2_scan(la_gpu_ctx *ctx, const uint8_t *d_src, uint64_t src_b
     uint32_t *d_count);
 int      la_gpu_bzip2_decode(la_gpu_ctx *ctx, const la_bz2_batch *batch);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * bzip2 compression -- replaces the BZ2_bzCompress loop of libarchive/archive_write_add_filter_bzip2.c (libbz2 is the
+ * reference's external dependency for this codec).  d_src[0, src_bytes) is cut every
+ * la_gpu_bzip2_compress_block_bytes(level) = 4 * ((100000 * level - 19) / 5) input bytes; every cut is one block (block
+ * magic, block CRC, origPtr, symbol map, 2..6 tables, selectors, symbols), sorted and coded on the device.  The blocks are
+ * concatenated at bit granularity behind the pending bits of *d_state; whole bytes go to d_out, the remaining 0..7 bits
+ * and the running combined CRC go back to *d_state, which lives on the device and is read and written there only.
+ * LA_BZ2C_FIRST resets *d_state and writes "BZh" + level digit in front; LA_BZ2C_LAST writes the end magic, the
+ * combined CRC and zero padding to a byte behind the blocks, so FIRST | LAST with src_bytes == 0 is the 14-byte empty
+ * stream and a call without LAST writes a piece the next call continues.  *d_out_bytes is the size needed; nothing is
+ * written past out_cap; la_gpu_bzip2_compress_bound() always fits.  The bytes are not libbz2's: the cut is fixed (libbz2
+ * fills a block to its limit) and the tables are fitted differently; every conforming reader returns the input.
+ * A call whose piece does not fit (*d_out_bytes > out_cap) leaves *d_state as it found it, so the same call can be made
+ * again with more room; a call whose piece fits moves *d_state on.
+ * src_bytes is at most LA_BZ2C_MAX_SRC_BYTES (1 GiB: positions inside the run-length coded window are 32-bit).  The
+ * workspace is about 46 bytes per input byte (two key and two order buffers of the sort, ranks, the three byte stages,
+ * symbols, the staged bit buffers): 2.9 GiB for a 64 MiB window, about 46 GiB at the limit;
+ * la_gpu_bzip2_compress_workspace_bytes() gives the exact figure, 0 above the limit.
+ * la_gpu_bzip2_compress_sort_rounds() (measurement) synchronises and returns how many sort rounds the context's last
+ * compress call ran before every rank was distinct; 0 without one.
+ * Additions under ABI version 3. */
+#define LA_BZ2C_MAX_SRC_BYTES ((uint64_t)1 << 30)
+#define LA_BZ2C_FIRST 1u	/* reset *d_state, write "BZh" + level digit in front */
+#define LA_BZ2C_LAST  2u	/* behind the blocks: end magic 0x177245385090, combined CRC, zero-pad to a byte */
+typedef struct la_bz2c_state {	/* device-resident, read and rewritten by every call */
+	uint32_t crc;		/* combined CRC of the stream's blocks so far */
+	uint32_t nbits;		/* 0..7 bits of the stream not yet part of a whole byte */
+	uint32_t bits;		/* those bits, most significant first, in the low byte's top */
+	uint32_t reserved;
+} la_bz2c_state;
+typedef struct la_bz2c_batch {
+	const uint8_t *d_src;
+	uint64_t       src_bytes;
+	uint32_t       level;	/* 1..9 */
+	uint32_t       flags;	/* LA_BZ2C_* */
+	la_bz2c_state *d_state;
+	uint8_t       *d_out;
+	uint64_t       out_cap;
+	uint64_t      *d_out_bytes;
+} la_bz2c_batch;
+uint32_t la_gpu_bzip2_compress_block_bytes(uint32_t level);	/* 0 for a level outside 1..9 */
+uint64_t la_gpu_bzip2_compress_workspace_bytes(uint64_t src_bytes, uint32_t level);
+uint64_t la_gpu_bzip2_compress_bound(uint64_t src_bytes, uint32_t level);
+int      la_gpu_bzip2_compress(la_gpu_ctx *ctx, const la_bz2c_batch *batch);
+uint32_t la_gpu_bzip2_compress_sort_rounds(la_gpu_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,18 @@ LA_ZSTDC_FULL_ALPHABET, LA_ZSTDC_FIT_TABLES = 4, 8
 LA_ZSTD_OPT_NO_VERIFY, LA_ZSTD_OPT_LANE_KERNEL, LA_ZSTD_OPT_BLOCK_PARALLEL = 1, 2, 4     # la_zstd_batch.options
 
 
+class _Bz2cBatchC(C.Structure):     # la_bz2c_batch
+    _fields_ = [
+        ("d_src", C.c_void_p), ("src_bytes", C.c_uint64),
+        ("level", C.c_uint32), ("flags", C.c_uint32),
+        ("d_state", C.c_void_p),
+        ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p),
+    ]
+
+
+LA_BZ2C_FIRST, LA_BZ2C_LAST = 1, 2
+BZ2C_STATE_DTYPE = np.dtype([("crc", "<u4"), ("nbits", "<u4"), ("bits", "<u4"), ("reserved", "<u4")])
+
 # bzip2 (la_bz2_cand, la_bz2_result, la_bz2_state, la_bz2_batch)
 BZ2_CAND_DTYPE = np.dtype([("bit_off", "<u8"), ("kind", "<u4"), ("reserved", "<u4")])
 BZ2_RESULT_DTYPE = np.dtype([("status", "<u4"), ("level", "<u4"), ("out_len", "<u8"), ("end_bit", "<u8"), ("dst_off", "<u8"),
@@ -234,6 +246,15 @@ def gpu_lib():
         lib.la_gpu_bzip2_max_blocks.argtypes = [C.c_uint32]
         lib.la_gpu_bzip2_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_bzip2_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.la_gpu_bzip2_compress.argtypes = [C.c_void_p, C.POINTER(_Bz2cBatchC)]
+        lib.la_gpu_bzip2_compress_block_bytes.restype = C.c_uint32
+        lib.la_gpu_bzip2_compress_block_bytes.argtypes = [C.c_uint32]
+        lib.la_gpu_bzip2_compress_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_bzip2_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        lib.la_gpu_bzip2_compress_sort_rounds.restype = C.c_uint32
+        lib.la_gpu_bzip2_compress_sort_rounds.argtypes = [C.c_void_p]
+        lib.la_gpu_bzip2_compress_bound.restype = C.c_uint64
+        lib.la_gpu_bzip2_compress_bound.argtypes = [C.c_uint64, C.c_uint32]
         lib.la_gpu_zstd_compress_bound.restype = C.c_uint64
         lib.la_gpu_zstd_compress_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         lib.la_gpu_zstd_compress_workspace_bytes.restype = C.c_uint64
@@ -438,6 +459,9 @@ class GpuContext:
 
     def zstd_compress(self, batch: _ZstdcBatchC):
         self._check(gpu_lib().la_gpu_zstd_compress(self._h, C.byref(batch)), "la_gpu_zstd_compress")
+
+    def bzip2_compress(self, batch: _Bz2cBatchC):
+        self._check(gpu_lib().la_gpu_bzip2_compress(self._h, C.byref(batch)), "la_gpu_bzip2_compress")
 
     def gzip_compress(self, batch: _GzcBatchC):
         self._check(gpu_lib().la_gpu_gzip_compress(self._h, C.byref(batch)), "la_gpu_gzip_compress")

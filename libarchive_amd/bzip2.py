@@ -1,5 +1,6 @@
-"""Device-resident bzip2 decode through the C ABI (harness for tests / tools).  Plumbing only: torch allocates the HBM
-buffers; the candidate table comes from la_gpu_bzip2_scan, all work is la_gpu_bzip2_decode() in its two phases."""
+"""Device-resident bzip2 decode and compression through the C ABI (harness for tests / tools).  Plumbing only: torch
+allocates the HBM buffers; the candidate table comes from la_gpu_bzip2_scan, all work is la_gpu_bzip2_decode() in its two
+phases and la_gpu_bzip2_compress()."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +11,44 @@ BZ2_CAND_DTYPE, BZ2_RESULT_DTYPE, BZ2_STATE_DTYPE = N.BZ2_CAND_DTYPE, N.BZ2_RESU
 LA_BZ2_OPT_SERIAL_CHASE = N.LA_BZ2_OPT_SERIAL_CHASE
 LA_ST_BZ2_DATA, LA_ST_BZ2_TRUNCATED, LA_ST_BZ2_BAD_CRC = N.LA_ST_BZ2_DATA, N.LA_ST_BZ2_TRUNCATED, N.LA_ST_BZ2_BAD_CRC
 LA_ST_BZ2_REFUTED, LA_ST_BZ2_RANDOMISED = N.LA_ST_BZ2_REFUTED, N.LA_ST_BZ2_RANDOMISED
+LA_BZ2C_FIRST, LA_BZ2C_LAST, BZ2C_STATE_DTYPE = N.LA_BZ2C_FIRST, N.LA_BZ2C_LAST, N.BZ2C_STATE_DTYPE
+
+
+def compress_block_bytes(level):
+    return int(N.gpu_lib().la_gpu_bzip2_compress_block_bytes(level))
+
+
+def compress_bound(n, level):
+    return int(N.gpu_lib().la_gpu_bzip2_compress_bound(n, level))
+
+
+def compress_to_stream(ctx, d_plain, level=9, flags=N.LA_BZ2C_FIRST | N.LA_BZ2C_LAST, state=None, out_cap=None, d_out=None):
+    """Device bzip2 compression (la_gpu_bzip2_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8 CUDA tensor
+    holding the stream, or the piece of it this call wrote.  `state` is the 16-byte device tensor (la_bz2c_state) a
+    stream written in several calls carries from one to the next; without one the call uses its own.  With `out_cap`
+    (and optionally `d_out`) the call gets that much room only and the needed size is returned beside the tensor."""
+    import torch
+    n = int(d_plain.numel())
+    dev = d_plain.device
+    cap = compress_bound(n, level) if out_cap is None else int(out_cap)
+    if d_out is None:
+        d_out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+    d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    if state is None:
+        state = torch.zeros(16, dtype=torch.uint8, device=dev)
+    b = N._Bz2cBatchC()
+    b.d_src = d_plain.data_ptr() if n else None
+    b.src_bytes = n
+    b.level, b.flags = level, flags
+    b.d_state = state.data_ptr()
+    b.d_out, b.out_cap, b.d_out_bytes = d_out.data_ptr(), cap, d_len.data_ptr()
+    ctx.bzip2_compress(b)
+    ctx.sync()
+    total = int(d_len.cpu()[0])
+    if out_cap is not None:
+        return d_out, total
+    assert total <= cap, (total, cap)
+    return d_out[:total]
 
 
 def max_blocks(slot_level):

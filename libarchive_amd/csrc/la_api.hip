@@ -791,4 +791,42 @@ int la_gpu_zstd_compress(la_gpu_ctx *c, const la_zstdc_batch *bt)
 	});
 }
 
+#define LA_BZ2C_SRC_MAX LA_BZ2C_MAX_SRC_BYTES	/* positions of the RLE1 bytes (5/4 of the input) are 32-bit */
+uint32_t la_gpu_bzip2_compress_block_bytes(uint32_t level)
+{
+	return level >= 1u && level <= 9u ? la_bzip2_compress_block_bytes(level) : 0u;
+}
+uint64_t la_gpu_bzip2_compress_workspace_bytes(uint64_t src_bytes, uint32_t level)
+{
+	return level >= 1u && level <= 9u && src_bytes <= LA_BZ2C_SRC_MAX ? la_bzip2_compress_ws_bytes(src_bytes, level) : 0u;
+}
+uint64_t la_gpu_bzip2_compress_bound(uint64_t src_bytes, uint32_t level)
+{
+	return level >= 1u && level <= 9u ? la_bzip2_compress_bound(src_bytes, level) : 0u;
+}
+struct bz2c_prof { la_gpu_ctx *c; int h; };
+static void bz2c_mark(void *cx, const char *name)	/* one profile range per stage of the call */
+{
+	bz2c_prof *p = (bz2c_prof *)cx;
+	if (p->h >= 0)
+		prof_close(p->c, p->h, p->c->stream);
+	p->h = name ? prof_open(p->c, name, p->c->stream) : -1;
+}
+int la_gpu_bzip2_compress(la_gpu_ctx *c, const la_bz2c_batch *bt)
+{
+	if (!c || !bt || !bt->d_out_bytes || !bt->d_state || (bt->src_bytes && !bt->d_src) || (bt->out_cap && !bt->d_out))
+		return LA_ERR_ARG;
+	if (bt->level < 1u || bt->level > 9u || (bt->flags & ~(LA_BZ2C_FIRST | LA_BZ2C_LAST)) || bt->src_bytes > LA_BZ2C_SRC_MAX)
+		return LA_ERR_ARG;
+	return compress_run(c, la_bzip2_compress_ws_bytes(bt->src_bytes, bt->level), "bzip2_compress", [&](uint8_t *ws) {
+		bz2c_prof pr = { c, -1 };
+		const la_stage_hook hook = { bz2c_mark, &pr };
+		la_launch_bzip2_compress(c->stream, bt, ws, &hook);
+	});
+}
+uint32_t la_gpu_bzip2_compress_sort_rounds(la_gpu_ctx *c)
+{
+	return c && c->ws ? la_bzip2_compress_rounds(c->stream, (const uint8_t *)c->ws) : 0u;
+}
+
 } /* extern "C" */

@@ -564,6 +564,15 @@ void la_launch_bzip2_walk(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
 void la_launch_bzip2_emit(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
 void la_launch_bzip2_verify(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
 
+/* la_bzip2_comp.hip */
+uint32_t la_bzip2_compress_block_bytes(uint32_t level);
+uint64_t la_bzip2_compress_ws_bytes(uint64_t src_bytes, uint32_t level);
+uint64_t la_bzip2_compress_bound(uint64_t src_bytes, uint32_t level);
+uint32_t la_bzip2_compress_rounds(hipStream_t s, const uint8_t *ws);
+/* mark(cx, name) ends the stage before and begins `name` (NULL: none): the API layer's profile ranges */
+struct la_stage_hook { void (*mark)(void *cx, const char *name); void *cx; };
+void la_launch_bzip2_compress(hipStream_t s, const la_bz2c_batch *bt, uint8_t *ws, const la_stage_hook *hook);
+
 /* la_lz4_comp.hip */
 void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);
