@@ -32,6 +32,7 @@ extern "C" {
 #define ARCHIVE_FILTER_NONE 0
 #define ARCHIVE_FILTER_GZIP 1
 #define ARCHIVE_FILTER_BZIP2 2
+#define ARCHIVE_FILTER_XZ   6
 #define ARCHIVE_FILTER_LZ4  13
 #define ARCHIVE_FILTER_ZSTD 14
 
@@ -57,6 +58,7 @@ int  archive_read_support_filter_gzip(struct archive *);			/* archive.h:466 */
 int  archive_read_support_compression_gzip(struct archive *);			/* deprecated alias, gzip.c:85-92 */
 int  archive_read_support_filter_lz4(struct archive *);				/* archive.h:469 */
 int  archive_read_support_filter_zstd(struct archive *);			/* archive.h:482 */
+int  archive_read_support_filter_xz(struct archive *);				/* archive.h:481 (host/la_filter_xz.c) */
 int  archive_read_support_filter_none(struct archive *);
 int  archive_read_support_format_raw(struct archive *);
 int  archive_read_support_format_empty(struct archive *);

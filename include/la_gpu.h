@@ -112,7 +112,19 @@ enum {
 					 * them before it compares), or a stream's combined CRC is not the stored one */
 	LA_ST_BZ2_REFUTED         = 23,	/* the chain of confirmed blocks does not pass through this candidate: 48 bits of
 					 * compressed data that look like a magic, or an entry behind the point where the walk ended */
-	LA_ST_BZ2_RANDOMISED      = 24	/* the block's randomised bit is set (bzip2 0.9.0 and older): not decoded, a data error */
+	LA_ST_BZ2_RANDOMISED      = 24,	/* the block's randomised bit is set (bzip2 0.9.0 and older): not decoded, a data error */
+	/* xz.c:443-451 -> "Lzma library error: Corrupted input data", "Lzma library error:  No progress is possible" */
+	LA_ST_XZ_DATA             = 25,	/* refused at a chunk boundary: control 3 .. 0x7F, a first chunk without a dictionary reset,
+					 * an LZMA chunk without the properties it owes, a bad properties byte, a range decoder that
+					 * does not end on the chunk's two sizes (liblzma reports these in the call that emitted the
+					 * last valid byte) */
+	LA_ST_XZ_LZMA             = 26,	/* refused inside an LZMA chunk: a distance beyond the data, a range decoder that asks for
+					 * bytes behind the chunk's compressed size (liblzma reports these in a call of their own) */
+	LA_ST_XZ_TRUNCATED        = 27,	/* the block, its padding or its check field runs off the end of d_src */
+	LA_ST_XZ_SIZE             = 28,	/* the data disagrees with a size of the block header */
+	LA_ST_XZ_BAD_CHECK        = 29,	/* the check field is not the CRC32 / CRC64 / SHA-256 of the block's bytes */
+	LA_ST_XZ_PADDING          = 30,	/* a non-zero byte in the block padding */
+	LA_ST_XZ_OUT_FULL         = 31	/* a block of unknown size produces more than dst_cap bytes: the host retries with more */
 };
 
 /* =====================================================================
@@ -641,6 +653,55 @@ uint64_t la_gpu_bzip2_workspace_bytes(uint32_t n, uint32_t slot_level);
 int      la_gpu_bzip2_scan(la_gpu_ctx *ctx, const uint8_t *d_src, uint64_t src_bytes, la_bz2_cand *d_cands, uint32_t cand_cap,
     uint32_t *d_count);
 int      la_gpu_bzip2_decode(la_gpu_ctx *ctx, const la_bz2_batch *batch);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * xz -- replaces, for a table of blocks per call, what lzma_code does inside a block for xz_filter_read
+ * (libarchive/archive_read_support_filter_xz.c:651-735; liblzma is the reference's external dependency for this codec):
+ * the LZMA2 chunk layer, the LZMA decoder, the block padding and the block check.  The container (stream header, block
+ * headers, index, footer, stream padding) is walked on the host (host/la_filter_xz.c).  Every xz block starts with a
+ * dictionary reset, so blocks are independent: one workgroup per block, the probability model in LDS, the dictionary is
+ * the block's own output in d_dst.  csrc/la_xz_dev.h states the decode rules and the verdicts.
+ * A block whose header carries no compressed size is bounded by src_bytes (and LA_ST_XZ_TRUNCATED says it ran into
+ * that bound); one without an uncompressed size is bounded by dst_cap (LA_ST_XZ_OUT_FULL).  On every failure out_len
+ * (= valid) bytes in front of it are in d_dst.  Checks: None, CRC32, CRC64 and SHA-256 are verified, other IDs are
+ * passed over, as liblzma's stream decoder does without LZMA_TELL_UNSUPPORTED_CHECK.  A block's dst_cap is at most
+ * LA_XZ_DST_CAP_MAX (the CRC32 of a block is one la_hash_job, whose 32-bit length is rounded up to whole 64-byte
+ * rows); an entry above it, or one that points outside d_src or d_dst, is LA_ST_XZ_SIZE and is not decoded.
+ * Additions under ABI version 3. */
+#define LA_XZ_UNKNOWN (~(uint64_t)0)
+#define LA_XZ_DST_CAP_MAX ((uint64_t)0xFFFFFFC0u)
+typedef struct la_xz_block {
+	uint64_t src_off;	/* first byte of the block's LZMA2 data inside d_src (behind the block header) */
+	uint64_t comp_size;	/* of the block header, or LA_XZ_UNKNOWN: bounded by the end of the source */
+	uint64_t uncomp_size;	/* of the block header, or LA_XZ_UNKNOWN: bounded by dst_cap */
+	uint64_t dst_off;	/* where the block's bytes go inside d_dst */
+	uint64_t dst_cap;	/* the block's output budget (the uncompressed size when that is known) */
+	uint64_t check_off;	/* offset of the check field inside d_src, or LA_XZ_UNKNOWN: behind the end marker and the padding */
+	uint32_t dict_size;	/* of the LZMA2 filter's properties */
+	uint32_t check_id;	/* of the stream header: 0 none, 1 CRC32, 4 CRC64, 10 SHA-256 */
+} la_xz_block;
+
+typedef struct la_xz_result {
+	uint32_t status;	/* LA_ST_OK or LA_ST_XZ_* */
+	uint32_t reserved;
+	uint64_t out_len;	/* bytes produced */
+	uint64_t consumed;	/* source bytes of the LZMA2 data, up to and including the 0x00 end marker */
+	uint64_t valid;		/* a failed block: the bytes in front of the failure that are valid (they are in d_dst) */
+} la_xz_result;
+
+typedef struct la_xz_batch {
+	const uint8_t     *d_src;
+	uint64_t           src_bytes;
+	const la_xz_block *d_blocks;	/* device-resident */
+	uint32_t           n;
+	uint32_t           reserved;
+	uint8_t           *d_dst;
+	uint64_t           dst_cap;	/* every block's [dst_off, dst_off + dst_cap) lies inside it */
+	la_xz_result      *d_results;	/* [n] */
+} la_xz_batch;
+
+uint64_t la_gpu_xz_workspace_bytes(uint32_t n);
+int      la_gpu_xz_decode(la_gpu_ctx *ctx, const la_xz_batch *batch);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * bzip2 compression -- replaces the BZ2_bzCompress loop of libarchive/archive_write_add_filter_bzip2.c (libbz2 is the

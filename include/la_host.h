@@ -181,6 +181,7 @@ const unsigned char *la_bid_peek(struct archive_read_filter *filter, size_t want
 int    la_bid_gzip_parallel(const unsigned char *p, size_t n, size_t hdr_len, size_t lookahead);
 int    la_bid_lz4_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead);
+int    la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead);
 
 /* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the lz4, gzip and zstd read filters ---- */
 /* LA_GPU_DEVICE: the device ordinal every filter, the ZIP reader and the hash drop-in open (default 0) */

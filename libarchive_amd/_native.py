@@ -112,6 +112,20 @@ LA_BZ2_STOP_TABLE, LA_BZ2_STOP_ENTRY, LA_BZ2_STOP_BID, LA_BZ2_STOP_SHORT, LA_BZ2
 LA_ST_BZ2_DATA, LA_ST_BZ2_TRUNCATED, LA_ST_BZ2_BAD_CRC, LA_ST_BZ2_REFUTED, LA_ST_BZ2_RANDOMISED = 20, 21, 22, 23, 24
 
 
+# xz (la_xz_block, la_xz_result, la_xz_batch)
+XZ_BLOCK_DTYPE = np.dtype([("src_off", "<u8"), ("comp_size", "<u8"), ("uncomp_size", "<u8"), ("dst_off", "<u8"), ("dst_cap", "<u8"),
+                           ("check_off", "<u8"), ("dict_size", "<u4"), ("check_id", "<u4")])
+XZ_RESULT_DTYPE = np.dtype([("status", "<u4"), ("reserved", "<u4"), ("out_len", "<u8"), ("consumed", "<u8"), ("valid", "<u8")])
+LA_XZ_UNKNOWN = 0xFFFFFFFFFFFFFFFF
+(LA_ST_XZ_DATA, LA_ST_XZ_LZMA, LA_ST_XZ_TRUNCATED, LA_ST_XZ_SIZE, LA_ST_XZ_BAD_CHECK, LA_ST_XZ_PADDING,
+ LA_ST_XZ_OUT_FULL) = 25, 26, 27, 28, 29, 30, 31
+
+
+class _XzBatchC(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("d_blocks", C.c_void_p), ("n", C.c_uint32),
+                ("reserved", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
+
+
 class _Bz2StateC(C.Structure):
     _fields_ = [("open", C.c_uint32), ("level", C.c_uint32), ("crc", C.c_uint32), ("stop", C.c_uint32),
                 ("start_bit", C.c_uint64), ("total_out", C.c_uint64), ("n_taken", C.c_uint32), ("stop_entry", C.c_uint32),
@@ -247,6 +261,9 @@ def gpu_lib():
         lib.la_gpu_bzip2_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_bzip2_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]
         lib.la_gpu_bzip2_compress.argtypes = [C.c_void_p, C.POINTER(_Bz2cBatchC)]
+        lib.la_gpu_xz_decode.argtypes = [C.c_void_p, C.POINTER(_XzBatchC)]
+        lib.la_gpu_xz_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_xz_workspace_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_bzip2_compress_block_bytes.restype = C.c_uint32
         lib.la_gpu_bzip2_compress_block_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_bzip2_compress_workspace_bytes.restype = C.c_uint64
@@ -478,6 +495,9 @@ class GpuContext:
 
     def bzip2_decode(self, batch: _Bz2BatchC):
         self._check(gpu_lib().la_gpu_bzip2_decode(self._h, C.byref(batch)), "la_gpu_bzip2_decode")
+
+    def xz_decode(self, batch: _XzBatchC):
+        self._check(gpu_lib().la_gpu_xz_decode(self._h, C.byref(batch)), "la_gpu_xz_decode")
 
     def gzip_decode(self, batch: _GzBatchC):
         self._check(gpu_lib().la_gpu_gzip_decode(self._h, C.byref(batch)), "la_gpu_gzip_decode")

@@ -541,6 +541,30 @@ int la_gpu_bzip2_decode(la_gpu_ctx *c, const la_bz2_batch *bt)
 	return LA_OK;
 }
 
+uint64_t la_gpu_xz_workspace_bytes(uint32_t n)
+{
+	return la_xz_workspace_bytes(n);
+}
+
+int la_gpu_xz_decode(la_gpu_ctx *c, const la_xz_batch *bt)
+{
+	if (!c || !bt || bt->reserved)
+		return LA_ERR_ARG;
+	if (bt->n && (!bt->d_blocks || !bt->d_results || !bt->d_dst || (bt->src_bytes && !bt->d_src)))
+		return LA_ERR_ARG;
+	const uint64_t need = la_xz_workspace_bytes(bt->n);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	uint8_t *ws = (uint8_t *)c->ws;
+	prof_range(c, "xz_decode", c->stream, [&] { la_launch_xz_decode(c->stream, bt, ws); });
+	prof_range(c, "xz_verify", c->stream, [&] { la_launch_xz_verify(c->stream, bt, ws); });
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 /* workspace of a gzip batch on the lane kernels: their scratch, then (two phases) E and the SEG launch's list; returns its size */
 static uint64_t gz_ws_carve(uint8_t *base, uint32_t n, bool two_phase, la_inflate_emit *E, uint32_t **big)
 {

@@ -564,6 +564,11 @@ void la_launch_bzip2_walk(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
 void la_launch_bzip2_emit(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
 void la_launch_bzip2_verify(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
 
+/* la_xz.hip: ws = the CRC32 jobs of the n blocks, then their CRC32s */
+uint64_t la_xz_workspace_bytes(uint32_t n);
+void la_launch_xz_decode(hipStream_t s, const la_xz_batch *bt, uint8_t *ws);
+void la_launch_xz_verify(hipStream_t s, const la_xz_batch *bt, uint8_t *ws);
+
 /* la_bzip2_comp.hip */
 uint32_t la_bzip2_compress_block_bytes(uint32_t level);
 uint64_t la_bzip2_compress_ws_bytes(uint64_t src_bytes, uint32_t level);

@@ -16,6 +16,8 @@
  *   - evidence of many units inside the look-ahead (a BGZF size subfield, a second member header, a frame that
  *     ends inside it): taken;
  *   - otherwise the first unit is larger than the look-ahead: declined (bid 0).
+ * An .xz stream (la_filter_xz.c) is taken when its first block header carries a compressed size (xz -T, pixz: the
+ * host hops from header to header); a block without one is a serial chain of unknown extent.
  * LA_ZSTD_BLOCKS=1 makes one long zstd frame a parallel unit (its blocks), and the zstd bidder takes it.
  * LA_GPU_BID=all switches the policy off (every stream with the right magic is taken: the stand-alone test core
  * has no other bidder); LA_GPU_BID_LOOKAHEAD_KIB sets the look-ahead (default 1024, gzip 256).
@@ -160,6 +162,16 @@ int la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead)
 	if (la_zstd_index_build(p, n, 0, ~0ull, fr, 4, &r) != 0)
 		return 1;	/* let the filter report what is wrong with it */
 	return r.n_frames >= 1;
+}
+
+/* xz: 1 = take it: the first block header carries a compressed size (a threaded writer: every block does, and the host
+ * hops from header to header), the stream has no block at all, or the look-ahead already holds the whole stream.  A
+ * block without a compressed size is one serial chain whose end only its decoder finds. */
+int la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead)
+{
+	if (n < lookahead || n < 14)
+		return 1;
+	return p[12] == 0 || (p[13] & 0x40) != 0;
 }
 
 /*

@@ -1,0 +1,683 @@
+/*
+ * la_filter_xz.c -- the xz read filter on the MI355X data plane.
+ *
+ * Mirrors libarchive/archive_read_support_filter_xz.c: the same bidder (xz.c:201-221: 6 magic bytes, 48 bits), filter
+ * code and name (ARCHIVE_FILTER_XZ, "xz", xz.c:393-394), vtable shape (read / close, xz.c:462-466) and the strings of
+ * set_error (xz.c:420-458).  Where the reference feeds lzma_code (a stream decoder opened with LZMA_CONCATENATED,
+ * xz.c:512-515) whatever __archive_read_filter_ahead returns (xz.c:651-735), this filter gathers a window of the stream
+ * and walks the container on the host: stream header, block headers, index, footer, stream padding, in liblzma's order
+ * of checks (stream_decoder.c, block_header_decoder.c, index_hash.c, stream_flags_decoder.c of liblzma 5.2).  Blocks
+ * whose header carries both sizes are hopped over without decoding; all of them in a window go to the device in ONE
+ * la_gpu_xz_decode call, output offsets from a prefix sum.  A block without a compressed size is a serial unit of
+ * unknown extent: it is decoded alone, its end is learnt from the result, then the walk goes on.  What the window did
+ * not finish opens the next window at that unit's first byte.  No CPU fallback.
+ *
+ * The index is checked as liblzma checks it, by a running comparison (count, sums of padded sizes, uncompressed sizes
+ * and record lengths, and a hash chain over the pairs), not against a stored list.
+ *
+ * Departures from liblzma.  (1) Only a single LZMA2 filter is decoded: a block that lists delta or a BCJ filter (IDs
+ * 0x03 .. 0x0B) ends the read with "xz GPU data plane: unsupported filter <name> in a block's filter chain"; liblzma
+ * decodes such chains.  (2) A block has to fit a window: more than LA_GPU_MAX_BATCH_MIB (2048) compressed MiB, or more
+ * than min(LA_GPU_OUT_BUDGET_MIB, 4095) decoded MiB (default 4095), is refused by name.  (3) Verdicts inside a block
+ * are the device's (csrc/la_xz_dev.h), where liblzma's reading is pinned: dictionary sizes rounded up to 4096 and to a
+ * multiple of 16, a non-zero first byte of a chunk's range-coder data refused.
+ *
+ * Bytes in front of an error.  The reference hands out its 64 KiB block when lzma_code has filled it (avail_out == 0,
+ * xz.c:669) and, at the end of the stream, the partial block; on an error it returns ARCHIVE_FATAL and the partial block
+ * is lost (xz.c:702-705).  lzma_code goes on reading input when the output block is full -- behind a block's last byte
+ * it takes the end marker, padding, check, the next header, the index -- but it does not decode another LZMA symbol.
+ * With T the bytes liblzma has emitted when it reports:
+ *   - an error of the container or at a chunk boundary (every status but LA_ST_XZ_LZMA) arrives in the call that
+ *     emitted byte T, so that byte's block is not handed out: 64 KiB * floor((T - 1) / 64 KiB) bytes are delivered;
+ *   - an error inside an LZMA chunk (LA_ST_XZ_LZMA), and LZMA_BUF_ERROR for input that ends inside a stream (the
+ *     reference calls lzma_code twice more without input: "No progress is possible", not "truncated input"), arrive
+ *     in a call of their own: 64 KiB * floor(T / 64 KiB) bytes are delivered;
+ *   - a clean end (LZMA_STREAM_END at the end of input, the stream padding a multiple of four) delivers all T.
+ * So at any time everything up to the last 64 KiB boundary strictly below T is safe to hand out; the filter holds the
+ * rest (at most 64 KiB) back until it knows more, as la_filter_bzip2.c does.  (tests/xz_support.py restates the
+ * reference's loop over the real liblzma; the rule above is what that emulator gives.  For T a multiple of 64 KiB the
+ * first case assumes that upstream hands the reference the damaged bytes together with byte T's block, as a memory
+ * reader does.)
+ */
+#include "la_read_private.h"
+#include "la_host.h"
+#include "../csrc/la_xz_dev.h"	/* la_xz_check_size: the rules header is plain C too */
+#include <errno.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#define XZ_OUT_BLOCK  ((uint64_t)65536)	/* xz.c:474 */
+#define XZ_TAB_CAP    4096u		/* blocks one launch takes; a window with more is taken in parts */
+#define XZ_VLI_MAX    (~(uint64_t)0 >> 1)
+
+/* liblzma's return codes, as far as set_error (xz.c:420-458) words them */
+enum { XZ_E_FORMAT, XZ_E_OPTIONS, XZ_E_DATA, XZ_E_BUF };
+static const char *const xz_msg[] = {
+	"Lzma library error: format not recognized", "Lzma library error: Invalid options",
+	"Lzma library error: Corrupted input data", "Lzma library error:  No progress is possible",
+};
+
+enum { SEQ_HEADER, SEQ_BLOCK, SEQ_INDEX, SEQ_FOOTER, SEQ_PADDING };
+
+/* one side of the index comparison (index_hash.c: lzma_index_hash_info) */
+typedef struct xz_sums {
+	uint64_t count, blocks_size, uncomp, list_size, hash;
+} xz_sums;
+
+struct xz_private {
+	la_window w;
+	la_buf stage; size_t stage_len;	/* pinned: the stream from the first byte of the next unit on */
+	la_buf d_src, d_dst, d_tabs;	/* d_tabs: block table, results */
+	la_buf out; size_t out_len, out_pos;	/* pinned: the decoded bytes of the current window */
+	la_xz_block *tab;		/* host copies of the tables (XZ_TAB_CAP entries) */
+	la_xz_result *res;
+	uint8_t *tail; size_t tail_len;	/* held-back bytes of earlier windows (at most 64 KiB) */
+	uint64_t total, delivered, limit;	/* T, bytes handed out, bytes that may be handed out */
+	la_verdict verdict; int ended;
+	int finished;
+	/* where the container stands at stage[0] */
+	int seq, first_stream;
+	uint32_t check_id;		/* of the stream header: the footer's has to be the same */
+	unsigned pad_mod;		/* stream padding bytes so far, mod 4 */
+	xz_sums blocks, records;
+	uint64_t solo_cap;		/* output budget of the next size-less block (grows on LA_ST_XZ_OUT_FULL) */
+};
+
+static int xz_reader_bid(struct archive_read_filter_bidder *, struct archive_read_filter *);
+static int xz_reader_init(struct archive_read_filter *);
+static ssize_t xz_filter_read(struct archive_read_filter *, const void **);
+static int xz_filter_close(struct archive_read_filter *);
+
+static const struct archive_read_filter_bidder_vtable xz_bidder_vtable = {
+	.bid = xz_reader_bid,
+	.init = xz_reader_init,
+};
+static const struct archive_read_filter_vtable xz_reader_vtable = {
+	.read = xz_filter_read,
+	.close = xz_filter_close,
+};
+
+int archive_read_support_filter_xz(struct archive *_a)
+{
+	struct archive_read *a = (struct archive_read *)_a;
+	if (__archive_read_register_bidder(a, NULL, "xz", &xz_bidder_vtable) != ARCHIVE_OK)
+		return ARCHIVE_FATAL;
+	return ARCHIVE_OK;
+}
+
+/* xz.c:201-221 */
+static int xz_reader_bid(struct archive_read_filter_bidder *self, struct archive_read_filter *filter)
+{
+	ssize_t avail;
+	(void)self;
+	const unsigned char *p = __archive_read_filter_ahead(filter, 6, &avail);
+	if (p == NULL)
+		return 0;
+	if (memcmp(p, "\xFD\x37\x7A\x58\x5A\x00", 6) != 0)
+		return 0;
+	/* Default policy (la_bid_policy.c): a block without a compressed size is one serial chain of unknown extent; a
+	 * stream that opens with one and does not end inside the look-ahead is left to liblzma on a host core. */
+	if (!la_bid_take_all()) {
+		const size_t la = la_bid_lookahead(1024);
+		size_t got = 0;
+		const unsigned char *w = la_bid_peek(filter, la, &got);
+		if (w != NULL && !la_bid_xz_parallel(w, got, la))
+			return 0;
+	}
+	return 48;
+}
+
+static int xz_reader_init(struct archive_read_filter *self)
+{
+	self->code = ARCHIVE_FILTER_XZ;
+	self->name = "xz";
+	struct xz_private *st = calloc(1, sizeof(*st));
+	uint8_t *tail = malloc((size_t)XZ_OUT_BLOCK);
+	la_xz_block *tab = malloc(sizeof(la_xz_block) * XZ_TAB_CAP);
+	la_xz_result *res = malloc(sizeof(la_xz_result) * XZ_TAB_CAP);
+	if (st == NULL || tail == NULL || tab == NULL || res == NULL || la_window_open(self, &st->w, "xz") != ARCHIVE_OK) {
+		if (st == NULL || tail == NULL || tab == NULL || res == NULL)
+			archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for xz decompression");	/* xz.c:482-483 */
+		free(st); free(tail); free(tab); free(res);
+		return ARCHIVE_FATAL;
+	}
+	st->tail = tail; st->tab = tab; st->res = res;
+	st->seq = SEQ_HEADER;
+	st->first_stream = 1;
+	if (st->w.out_budget == 0 || st->w.out_budget > ((uint64_t)4095 << 20))
+		st->w.out_budget = (uint64_t)4095 << 20;	/* a block's dst_cap is at most LA_XZ_DST_CAP_MAX */
+	self->data = st;
+	self->vtable = &xz_reader_vtable;
+	return ARCHIVE_OK;
+}
+
+static int gpu_fail(struct archive_read_filter *self, struct xz_private *st, const char *what)
+{
+	st->finished = 1;
+	return la_window_fail(self, &st->w, what);
+}
+
+/* the stream ends here: rc and message are reported once `limit` bytes are out */
+static void xz_end(struct xz_private *st, int rc, const char *msg, uint64_t limit)
+{
+	if (msg)
+		la_verdict_set(&st->verdict, rc, "%s", msg);
+	else
+		la_verdict_set(&st->verdict, rc, NULL);
+	st->ended = 1;
+	st->limit = limit;
+}
+/* an error reported in the call that emitted byte T */
+static void xz_end_early(struct xz_private *st, int e)
+{
+	xz_end(st, ARCHIVE_FATAL, xz_msg[e], st->total ? (st->total - 1) / XZ_OUT_BLOCK * XZ_OUT_BLOCK : 0);
+}
+/* an error reported in a call of its own */
+static void xz_end_late(struct xz_private *st, int e)
+{
+	xz_end(st, ARCHIVE_FATAL, xz_msg[e], st->total / XZ_OUT_BLOCK * XZ_OUT_BLOCK);
+}
+
+/* vli.c, single-call mode: 0 and *pos advanced, or -1 (LZMA_DATA_ERROR: no byte left, a zero byte that is not the first,
+ * a tenth byte).  -2: the bytes end inside the number (multi-call mode asks for more there; single-call mode is -1 too). */
+static int xz_vli(const uint8_t *p, size_t n, size_t *pos, uint64_t *v)
+{
+	uint64_t r = 0;
+	for (unsigned k = 0; k < 9; k++) {
+		if (*pos >= n)
+			return -2;
+		const uint8_t b = p[(*pos)++];
+		r |= (uint64_t)(b & 0x7F) << (7 * k);
+		if (!(b & 0x80)) {
+			if (b == 0 && k > 0)
+				return -1;
+			*v = r;
+			return 0;
+		}
+	}
+	return -1;
+}
+static unsigned xz_vli_size(uint64_t v)
+{
+	unsigned k = 1;
+	while (v >>= 7)
+		k++;
+	return k;
+}
+static uint64_t ceil4(uint64_t v) { return (v + 3) & ~(uint64_t)3; }
+
+static void sums_append(xz_sums *s, uint64_t unpadded, uint64_t uncomp)
+{
+	s->count++;
+	s->blocks_size += ceil4(unpadded);
+	s->uncomp += uncomp;
+	s->list_size += xz_vli_size(unpadded) + xz_vli_size(uncomp);
+	const uint64_t v[2] = { unpadded, uncomp };
+	for (unsigned i = 0; i < 16; i++)	/* FNV-1a over the pair, chained */
+		s->hash = (s->hash ^ ((v[i >> 3] >> (8 * (i & 7))) & 0xFF)) * 1099511628211ull;
+}
+
+static const char *xz_filter_name(uint64_t id)
+{
+	static const char *const names[] = { "delta", "x86 BCJ", "PowerPC BCJ", "IA-64 BCJ", "ARM BCJ", "ARM-Thumb BCJ", "SPARC BCJ",
+		"ARM64 BCJ", "RISC-V BCJ" };	/* (0x0A and 0x0B: xz 5.4 and 5.6; a liblzma from before them answers LZMA_OPTIONS_ERROR) */
+	return id >= 3 && id <= 0x0B ? names[id - 3] : NULL;
+}
+
+typedef struct xz_block_header {
+	uint64_t comp, uncomp;	/* LA_XZ_UNKNOWN when absent */
+	uint32_t dict_size;
+	const char *unsupported;	/* a filter this data plane does not run */
+} xz_block_header;
+
+/* block_header_decoder.c over the whole header h[0, size): -1 or an XZ_E_* */
+static int xz_block_header_parse(const uint8_t *h, size_t size, uint32_t check_id, xz_block_header *bh)
+{
+	const size_t n = size - 4;
+	if ((uint32_t)la_crc32(0, h, n) != archive_le32dec(h + n))
+		return XZ_E_DATA;
+	if (h[1] & 0x3C)
+		return XZ_E_OPTIONS;
+	size_t pos = 2;
+	bh->comp = bh->uncomp = LA_XZ_UNKNOWN;
+	bh->unsupported = NULL;
+	bh->dict_size = 0;
+	if (h[1] & 0x40) {
+		if (xz_vli(h, n, &pos, &bh->comp) != 0)
+			return XZ_E_DATA;
+		/* lzma_block_unpadded_size: no compressed size of 0, no unpadded size above LZMA_VLI_MAX & ~3 */
+		if (bh->comp == 0 || bh->comp > (XZ_VLI_MAX & ~(uint64_t)3) - size - la_xz_check_size(check_id))
+			return XZ_E_DATA;
+	}
+	if ((h[1] & 0x80) && xz_vli(h, n, &pos, &bh->uncomp) != 0)
+		return XZ_E_DATA;
+	const unsigned nf = (h[1] & 3u) + 1u;
+	int lzma2_last = 0, others = 0;
+	for (unsigned f = 0; f < nf; f++) {
+		uint64_t id, psize;
+		if (xz_vli(h, n, &pos, &id) != 0 || id >= ((uint64_t)1 << 62))
+			return XZ_E_DATA;
+		if (xz_vli(h, n, &pos, &psize) != 0 || n - pos < psize)
+			return XZ_E_DATA;
+		if (id == 0x21) {
+			if (psize != 1 || (h[pos] & 0xC0) || h[pos] > 40)
+				return XZ_E_OPTIONS;
+			bh->dict_size = h[pos] == 40 ? 0xFFFFFFFFu : (2u | (h[pos] & 1u)) << (h[pos] / 2 + 11);
+			lzma2_last = f == nf - 1;
+			others += f != nf - 1;
+		} else if (xz_filter_name(id)) {
+			if (bh->unsupported == NULL)
+				bh->unsupported = xz_filter_name(id);
+		} else {
+			return XZ_E_OPTIONS;	/* lzma_properties_decode: no such filter */
+		}
+		pos += (size_t)psize;
+	}
+	while (pos < n)
+		if (h[pos++] != 0)
+			return XZ_E_OPTIONS;
+	if (bh->unsupported)
+		return -1;
+	if (!lzma2_last || others)
+		return XZ_E_OPTIONS;	/* lzma_raw_decoder_init: the chain has to end in LZMA2 and hold it once */
+	return -1;
+}
+
+/* index_hash.c over what is there of the index, p[0] the indicator.  Returns the index's size when it is complete and
+ * sound (the records side is then committed), 0 when the bytes end first, -1 for LZMA_DATA_ERROR. */
+static int64_t xz_index_parse(struct xz_private *st, const uint8_t *p, size_t n)
+{
+	xz_sums rec;
+	memset(&rec, 0, sizeof(rec));
+	size_t pos = 1;
+	uint64_t count;
+	int r = xz_vli(p, n, &pos, &count);
+	if (r != 0)
+		return r == -2 ? 0 : -1;
+	if (count != st->blocks.count)
+		return -1;
+	for (uint64_t i = 0; i < count; i++) {
+		uint64_t unpadded, uncomp;
+		if ((r = xz_vli(p, n, &pos, &unpadded)) != 0)
+			return r == -2 ? 0 : -1;
+		if (unpadded < 5 || unpadded > (XZ_VLI_MAX & ~(uint64_t)3))
+			return -1;
+		if ((r = xz_vli(p, n, &pos, &uncomp)) != 0)
+			return r == -2 ? 0 : -1;
+		sums_append(&rec, unpadded, uncomp);
+		if (st->blocks.blocks_size < rec.blocks_size || st->blocks.uncomp < rec.uncomp || st->blocks.list_size < rec.list_size)
+			return -1;
+	}
+	while (pos & 3) {
+		if (pos >= n)
+			return 0;
+		if (p[pos++] != 0)
+			return -1;
+	}
+	if (pos >= n)
+		return 0;	/* (index_hash.c compares when the first byte behind the padding is there) */
+	if (st->blocks.blocks_size != rec.blocks_size || st->blocks.uncomp != rec.uncomp || st->blocks.list_size != rec.list_size ||
+	    st->blocks.hash != rec.hash)
+		return -1;
+	const uint32_t crc = (uint32_t)la_crc32(0, p, pos);
+	for (unsigned k = 0; k < 4; k++) {
+		if (pos >= n)
+			return 0;
+		if (p[pos++] != ((crc >> (8 * k)) & 0xFF))
+			return -1;
+	}
+	st->records = rec;
+	return (int64_t)pos;
+}
+
+/* Decode tab[0, n) in one call and append the bytes to the window's output; the results are in st->res. */
+static int xz_launch(struct archive_read_filter *self, struct xz_private *st, uint32_t n, uint64_t dst_bytes)
+{
+	la_gpu_ctx *gpu = st->w.gpu;
+	const size_t o_res = sizeof(la_xz_block) * XZ_TAB_CAP;
+	if (la_buf_dev(gpu, &st->d_tabs, o_res + sizeof(la_xz_result) * XZ_TAB_CAP) < 0 || la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0)
+		return gpu_fail(self, st, "la_gpu_malloc");
+	la_xz_batch bt;
+	memset(&bt, 0, sizeof(bt));
+	bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
+	bt.d_blocks = (const la_xz_block *)st->d_tabs.p; bt.n = n;
+	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes;
+	bt.d_results = (la_xz_result *)(st->d_tabs.p + o_res);
+	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, st->tab, sizeof(la_xz_block) * n) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
+	if (la_gpu_xz_decode(gpu, &bt) != LA_OK) return gpu_fail(self, st, "la_gpu_xz_decode");
+	if (la_gpu_memcpy_d2h(gpu, st->res, bt.d_results, sizeof(la_xz_result) * n) != LA_OK || la_gpu_sync(gpu) != LA_OK)
+		return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+	return ARCHIVE_OK;
+}
+
+/* The verdict on a failed block: T counts its valid bytes. */
+static void xz_block_failed(struct xz_private *st, uint32_t status)
+{
+	if (status == LA_ST_XZ_LZMA)
+		xz_end_late(st, XZ_E_DATA);
+	else
+		xz_end_early(st, XZ_E_DATA);
+}
+
+/* Walk the results of tab[0, n) in stream order; the bytes of the blocks in front of the first failure, and the valid
+ * bytes of that one, come back from the device. */
+static int xz_take_results(struct archive_read_filter *self, struct xz_private *st, uint32_t n)
+{
+	la_gpu_ctx *gpu = st->w.gpu;
+	uint64_t bytes = 0;
+	uint32_t bad = n;
+	for (uint32_t i = 0; i < n && bad == n; i++) {
+		if (st->res[i].status != LA_ST_OK)
+			bad = i;
+		bytes = st->tab[i].dst_off + st->res[i].out_len;	/* (the table is packed: no gaps in front of a failure) */
+	}
+	if (bytes) {
+		if (la_buf_pinned(gpu, &st->out, st->out_len + (size_t)bytes + 64, st->out_len) < 0)
+			return gpu_fail(self, st, "la_gpu_malloc_host");
+		if (la_gpu_memcpy_d2h(gpu, st->out.p + st->out_len, st->d_dst.p, bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
+			return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+	}
+	st->out_len += (size_t)bytes;
+	st->total += bytes;
+	if (bad < n)
+		xz_block_failed(st, st->res[bad].status);
+	return ARCHIVE_OK;
+}
+
+/* One window: gather, upload, walk; updates T and limit, and says how the stream ends if this window shows it.
+ * ARCHIVE_OK, or a fatal code with the error set. */
+static int xz_window(struct archive_read_filter *self, struct xz_private *st)
+{
+	la_gpu_ctx *gpu = st->w.gpu;
+	int r = la_window_gather(self, &st->w, &st->stage, &st->stage_len);
+	if (r != ARCHIVE_OK)
+		return r;
+	st->out_len = st->out_pos = 0;
+	const uint8_t *src = st->stage.p;
+	const size_t len = st->stage_len;
+	const int eof = st->w.upstream_eof;
+	if (len) {
+		if (la_buf_dev(gpu, &st->d_src, len + 64) < 0) return gpu_fail(self, st, "la_gpu_malloc");
+		if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
+	}
+	size_t pos = 0;		/* the first byte of the unit the walk stands at */
+	int more = 0;		/* that unit needs bytes the window does not hold */
+	uint32_t n = 0;		/* sized blocks collected for one launch */
+	uint64_t dst_bytes = 0;
+	while (!st->ended && !more) {
+		/* the block header at pos, when the walk stands at one and all of it is here: parsed once per turn */
+		xz_block_header bh;
+		size_t hsize = 0;
+		int hdr = -2;	/* -2: no whole block header at pos; -1: a sound one; otherwise its XZ_E_* */
+		const uint32_t cs = la_xz_check_size(st->check_id);
+		memset(&bh, 0, sizeof(bh));
+		if (st->seq == SEQ_BLOCK && len - pos >= 1 && src[pos] != 0 && len - pos >= (hsize = ((size_t)src[pos] + 1) * 4))
+			hdr = xz_block_header_parse(src + pos, hsize, st->check_id, &bh);
+		const int sound = hdr == -1 && !bh.unsupported;
+		const int too_large = sound && ((bh.comp != LA_XZ_UNKNOWN && bh.comp > st->w.max_batch_bytes) ||
+		    (bh.uncomp != LA_XZ_UNKNOWN && bh.uncomp > st->w.out_budget));
+		/* both sizes in the header and the whole block in the window: hopped over, decoded with its neighbours */
+		const int whole = sound && !too_large && bh.comp != LA_XZ_UNKNOWN && bh.uncomp != LA_XZ_UNKNOWN &&
+		    len - pos - hsize >= ceil4(bh.comp) + cs;
+		if (whole && n < XZ_TAB_CAP && !(n && dst_bytes + bh.uncomp > st->w.out_budget)) {
+			la_xz_block *b = &st->tab[n++];
+			b->src_off = pos + hsize; b->comp_size = bh.comp; b->uncomp_size = bh.uncomp;
+			b->dst_off = dst_bytes; b->dst_cap = bh.uncomp;
+			b->check_off = pos + hsize + ceil4(bh.comp);
+			b->dict_size = bh.dict_size; b->check_id = st->check_id;
+			dst_bytes += bh.uncomp;
+			sums_append(&st->blocks, hsize + bh.comp + cs, bh.uncomp);
+			pos += hsize + (size_t)ceil4(bh.comp) + cs;
+			continue;
+		}
+		if (n) {	/* anything else ends the run of sized blocks: their bytes count in front of what follows */
+			if ((r = xz_launch(self, st, n, dst_bytes)) != ARCHIVE_OK || (r = xz_take_results(self, st, n)) != ARCHIVE_OK)
+				return r;
+			n = 0;
+			dst_bytes = 0;
+			continue;	/* (the unit at pos is looked at again, now with nothing collected) */
+		}
+		switch (st->seq) {
+		case SEQ_HEADER: {
+			if (len - pos < 12) {
+				if (eof) xz_end_late(st, XZ_E_BUF); else more = 1;
+				break;
+			}
+			const uint8_t *h = src + pos;
+			if (memcmp(h, "\xFD\x37\x7A\x58\x5A\x00", 6) != 0)	/* stream_decoder.c: FORMAT_ERROR behind the first stream is DATA_ERROR */
+				xz_end_early(st, st->first_stream ? XZ_E_FORMAT : XZ_E_DATA);
+			else if ((uint32_t)la_crc32(0, h + 6, 2) != archive_le32dec(h + 8))
+				xz_end_early(st, XZ_E_DATA);
+			else if (h[6] != 0 || (h[7] & 0xF0))
+				xz_end_early(st, XZ_E_OPTIONS);
+			else {
+				st->check_id = h[7] & 0x0F;
+				memset(&st->blocks, 0, sizeof(st->blocks));
+				memset(&st->records, 0, sizeof(st->records));
+				st->seq = SEQ_BLOCK;
+				pos += 12;
+			}
+			break;
+		}
+		case SEQ_BLOCK: {
+			if (len - pos >= 1 && src[pos] == 0) {
+				st->seq = SEQ_INDEX;
+				break;
+			}
+			if (hdr == -2) {	/* not one byte, or not the whole header */
+				if (eof) xz_end_late(st, XZ_E_BUF); else more = 1;
+				break;
+			}
+			if (hdr >= 0) {
+				xz_end_early(st, hdr);
+				break;
+			}
+			if (bh.unsupported) {
+				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+				    "xz GPU data plane: unsupported filter %s in a block's filter chain (only LZMA2 is decoded)", bh.unsupported);
+				st->finished = 1;
+				return ARCHIVE_FATAL;
+			}
+			if (too_large) {
+				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+				    "xz block too large for the GPU data plane (more than %llu compressed or %llu decoded bytes; LA_GPU_MAX_BATCH_MIB, LA_GPU_OUT_BUDGET_MIB)",
+				    (unsigned long long)st->w.max_batch_bytes, (unsigned long long)st->w.out_budget);
+				st->finished = 1;
+				return ARCHIVE_FATAL;
+			}
+			/* a size is missing, or the block is not all here: alone, bounded by the window's end and by a budget that grows
+			 * when it proves too small */
+			const uint64_t have = len - pos - hsize;
+			if (!eof && bh.comp != LA_XZ_UNKNOWN && have < ceil4(bh.comp) + cs) {
+				more = 1;	/* the header says how much is missing */
+				break;
+			}
+			uint64_t cap = bh.uncomp;
+			if (cap == LA_XZ_UNKNOWN) {
+				if (st->solo_cap == 0)
+					st->solo_cap = have * 8 > ((uint64_t)1 << 20) ? have * 8 : (uint64_t)1 << 20;
+				if (st->solo_cap > st->w.out_budget)
+					st->solo_cap = st->w.out_budget;
+				cap = st->solo_cap;
+			}
+			la_xz_block *b = &st->tab[0];
+			b->src_off = pos + hsize; b->comp_size = bh.comp; b->uncomp_size = bh.uncomp;
+			b->dst_off = 0; b->dst_cap = cap; b->check_off = LA_XZ_UNKNOWN;
+			b->dict_size = bh.dict_size; b->check_id = st->check_id;
+			if ((r = xz_launch(self, st, 1, cap)) != ARCHIVE_OK)
+				return r;
+			const la_xz_result q = st->res[0];
+			if (q.status == LA_ST_XZ_OUT_FULL) {
+				if (cap >= st->w.out_budget) {
+					archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+					    "xz block too large for the GPU data plane (more than %llu decoded bytes; LA_GPU_OUT_BUDGET_MIB)",
+					    (unsigned long long)st->w.out_budget);
+					st->finished = 1;
+					return ARCHIVE_FATAL;
+				}
+				st->solo_cap = cap * 2;
+				break;	/* again, with twice the room */
+			}
+			if (q.status == LA_ST_XZ_TRUNCATED && !eof) {
+				more = 1;
+				break;
+			}
+			st->solo_cap = 0;
+			if ((r = xz_take_results(self, st, 1)) != ARCHIVE_OK)
+				return r;
+			if (q.status == LA_ST_XZ_TRUNCATED) {
+				st->ended = 0;	/* (not a data error: the input ends inside the block) */
+				xz_end_late(st, XZ_E_BUF);
+			} else if (q.status == LA_ST_OK) {
+				sums_append(&st->blocks, hsize + q.consumed + cs, q.out_len);
+				pos += hsize + (size_t)ceil4(q.consumed) + cs;
+			}
+			break;
+		}
+		case SEQ_INDEX: {
+			const int64_t k = xz_index_parse(st, src + pos, len - pos);
+			if (k < 0)
+				xz_end_early(st, XZ_E_DATA);
+			else if (k == 0) {
+				if (eof) xz_end_late(st, XZ_E_BUF); else more = 1;
+			} else {
+				pos += (size_t)k;
+				st->seq = SEQ_FOOTER;
+			}
+			break;
+		}
+		case SEQ_FOOTER: {
+			if (len - pos < 12) {
+				if (eof) xz_end_late(st, XZ_E_BUF); else more = 1;
+				break;
+			}
+			const uint8_t *f = src + pos;
+			const uint64_t index_size = ceil4(1 + xz_vli_size(st->records.count) + st->records.list_size) + 4;
+			if (f[10] != 'Y' || f[11] != 'Z')	/* (FORMAT_ERROR, which the stream decoder turns into DATA_ERROR) */
+				xz_end_early(st, XZ_E_DATA);
+			else if ((uint32_t)la_crc32(0, f + 4, 6) != archive_le32dec(f))
+				xz_end_early(st, XZ_E_DATA);
+			else if (f[8] != 0 || (f[9] & 0xF0))
+				xz_end_early(st, XZ_E_OPTIONS);
+			else if (((uint64_t)archive_le32dec(f + 4) + 1) * 4 != index_size || (f[9] & 0x0F) != st->check_id)
+				xz_end_early(st, XZ_E_DATA);
+			else {
+				pos += 12;
+				st->seq = SEQ_PADDING;
+				st->pad_mod = 0;
+				st->first_stream = 0;
+			}
+			break;
+		}
+		default: {	/* SEQ_PADDING */
+			while (pos < len && src[pos] == 0) {
+				pos++;
+				st->pad_mod = (st->pad_mod + 1) & 3;
+			}
+			if (pos < len) {
+				if (st->pad_mod)
+					xz_end_early(st, XZ_E_DATA);
+				else
+					st->seq = SEQ_HEADER;
+			} else if (eof) {
+				if (st->pad_mod)
+					xz_end_early(st, XZ_E_DATA);
+				else
+					xz_end(st, ARCHIVE_OK, NULL, st->total);
+			} else {
+				more = 1;
+			}
+			break;
+		}
+		}
+	}
+	la_window_ramp(&st->w);
+	if (st->ended)
+		return ARCHIVE_OK;
+	st->limit = st->total ? (st->total - 1) / XZ_OUT_BLOCK * XZ_OUT_BLOCK : 0;
+	if (pos == 0 && len >= st->w.batch_bytes) {
+		/* one unit larger than the window: widen it, as the other filters do */
+		if (len >= st->w.max_batch_bytes) {
+			archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+			    "xz block too large for the GPU data plane (more than %llu compressed bytes; LA_GPU_MAX_BATCH_MIB)",
+			    (unsigned long long)st->w.max_batch_bytes);
+			st->finished = 1;
+			return ARCHIVE_FATAL;
+		}
+		st->w.batch_bytes = len * 2 < st->w.max_batch_bytes ? len * 2 : st->w.max_batch_bytes;
+	}
+	memmove(st->stage.p, st->stage.p + pos, len - pos);
+	st->stage_len = len - pos;
+	return ARCHIVE_OK;
+}
+
+static ssize_t xz_filter_read(struct archive_read_filter *self, const void **p)
+{
+	struct xz_private *st = (struct xz_private *)self->data;
+	*p = NULL;
+	if (st->finished)
+		return 0;
+	for (;;) {
+		if (st->tail_len && st->delivered + st->tail_len <= st->limit) {
+			const size_t k = st->tail_len;
+			*p = st->tail;
+			st->tail_len = 0;
+			st->delivered += k;
+			return (ssize_t)k;
+		}
+		if (st->tail_len == 0 && st->out_pos < st->out_len && st->delivered < st->limit) {
+			size_t k = st->out_len - st->out_pos;
+			if (k > st->limit - st->delivered)
+				k = (size_t)(st->limit - st->delivered);
+			*p = st->out.p + st->out_pos;
+			st->out_pos += k;
+			st->delivered += k;
+			return (ssize_t)k;
+		}
+		if (st->ended) {
+			st->finished = 1;
+			if (st->verdict.rc != ARCHIVE_OK)
+				return la_verdict_report(self, &st->verdict);
+			return 0;
+		}
+		/* what the window holds beyond `limit` (with the tail, at most 64 KiB) waits for the next window's verdict */
+		if (st->out_pos < st->out_len) {
+			const size_t k = st->out_len - st->out_pos;
+			if (st->tail_len + k > XZ_OUT_BLOCK) {
+				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "xz filter: held-back bytes exceed one block");
+				st->finished = 1;
+				return ARCHIVE_FATAL;
+			}
+			memcpy(st->tail + st->tail_len, st->out.p + st->out_pos, k);
+			st->tail_len += k;
+			st->out_pos = st->out_len;
+		}
+		const int r = xz_window(self, st);
+		if (r != ARCHIVE_OK) {
+			st->finished = 1;
+			return r;
+		}
+	}
+}
+
+static int xz_filter_close(struct archive_read_filter *self)
+{
+	struct xz_private *st = (struct xz_private *)self->data;
+	if (st == NULL)
+		return ARCHIVE_OK;
+	la_gpu_ctx *gpu = st->w.gpu;
+	(void)la_gpu_sync(gpu);
+	la_buf_release(gpu, &st->d_src);
+	la_buf_release(gpu, &st->d_dst);
+	la_buf_release(gpu, &st->d_tabs);
+	la_buf_release(gpu, &st->out);
+	la_buf_release(gpu, &st->stage);
+	la_gpu_close(gpu);
+	free(st->tab);
+	free(st->res);
+	free(st->tail);
+	free(st);
+	self->data = NULL;
+	return ARCHIVE_OK;
+}

@@ -129,6 +129,7 @@ int archive_read_support_filter_none(struct archive *a) { (void)a; return ARCHIV
 /* The bzip2 filter is one more source file (la_filter_bzip2.c); libraries that list their sources by name and leave it
  * out (the CPU mocks of the tests) still load: the reference is weak, and a filter that is not linked is not registered. */
 extern int archive_read_support_filter_bzip2(struct archive *) __attribute__((weak));
+extern int archive_read_support_filter_xz(struct archive *) __attribute__((weak));	/* la_filter_xz.c, the same way */
 
 int archive_read_support_filter_all(struct archive *a)
 {
@@ -138,6 +139,8 @@ int archive_read_support_filter_all(struct archive *a)
 	archive_read_support_filter_zstd(a);
 	if (archive_read_support_filter_bzip2)
 		archive_read_support_filter_bzip2(a);
+	if (archive_read_support_filter_xz)
+		archive_read_support_filter_xz(a);
 	archive_clear_error(a);
 	return ARCHIVE_OK;
 }

@@ -1,0 +1,64 @@
+"""Device-resident xz block decode through the C ABI (harness for tests / tools).  Plumbing only: torch allocates the
+HBM buffers; the block table is the caller's (the container is walked on the host, host/la_filter_xz.c), all work is
+la_gpu_xz_decode()."""
+import numpy as np
+
+from . import _native as N
+
+XZ_BLOCK_DTYPE, XZ_RESULT_DTYPE, LA_XZ_UNKNOWN = N.XZ_BLOCK_DTYPE, N.XZ_RESULT_DTYPE, N.LA_XZ_UNKNOWN
+LA_ST_XZ_DATA, LA_ST_XZ_LZMA, LA_ST_XZ_TRUNCATED, LA_ST_XZ_SIZE = N.LA_ST_XZ_DATA, N.LA_ST_XZ_LZMA, N.LA_ST_XZ_TRUNCATED, N.LA_ST_XZ_SIZE
+LA_ST_XZ_BAD_CHECK, LA_ST_XZ_PADDING, LA_ST_XZ_OUT_FULL = N.LA_ST_XZ_BAD_CHECK, N.LA_ST_XZ_PADDING, N.LA_ST_XZ_OUT_FULL
+
+
+def block_table(entries):
+    """ndarray of XZ_BLOCK_DTYPE from dicts; fields left out: sizes and check offset unknown, dictionary 8 MiB, no check."""
+    t = np.zeros(len(entries), dtype=XZ_BLOCK_DTYPE)
+    for i, e in enumerate(entries):
+        t[i] = (e["src_off"], e.get("comp_size", LA_XZ_UNKNOWN), e.get("uncomp_size", LA_XZ_UNKNOWN), e.get("dst_off", 0), e["dst_cap"],
+                e.get("check_off", LA_XZ_UNKNOWN), e.get("dict_size", 1 << 23), e.get("check_id", 0))
+    return t
+
+
+class XzDevicePlan:
+    """One call: run() decodes the table; results() / output(i) read back."""
+
+    def __init__(self, ctx, d_src, blocks, dst_cap=None):
+        import torch
+        dev = d_src.device
+        self.ctx, self.n, self.d_src, self.blocks = ctx, len(blocks), d_src, blocks
+        if dst_cap is None:
+            dst_cap = max([int(b["dst_off"] + b["dst_cap"]) for b in blocks], default=0)
+        self.dst_cap = int(dst_cap)
+        self.d_blocks = torch.from_numpy(np.ascontiguousarray(blocks).view(np.uint8).reshape(-1).copy()).to(dev) if self.n else \
+            torch.zeros(16, dtype=torch.uint8, device=dev)
+        self.d_results = torch.zeros(max(self.n, 1) * XZ_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_dst = torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
+        b = N._XzBatchC()
+        b.d_src, b.src_bytes = (d_src.data_ptr() if d_src.numel() else None), d_src.numel()
+        b.d_blocks, b.n = self.d_blocks.data_ptr(), self.n
+        b.d_dst, b.dst_cap, b.d_results = self.d_dst.data_ptr(), self.dst_cap, self.d_results.data_ptr()
+        self.batch = b
+
+    def run(self):
+        self.ctx.xz_decode(self.batch)
+        return self
+
+    def results(self):
+        self.ctx.sync()
+        return self.d_results.cpu().numpy().view(XZ_RESULT_DTYPE)[:self.n].copy()
+
+    def output(self, i=None):
+        res = self.results()
+        if i is None:
+            return b"".join(self.output(k) for k in range(self.n))
+        off, n = int(self.blocks[i]["dst_off"]), int(res[i]["out_len"])
+        return self.d_dst[off:off + n].cpu().numpy().tobytes()
+
+
+def decode_blocks(ctx, image, entries):
+    """Upload a host image, decode the blocks `entries` describe (see block_table).  Returns (results, plan)."""
+    import torch
+    buf = np.frombuffer(bytes(image), dtype=np.uint8)
+    d_src = torch.from_numpy(buf.copy()).cuda() if buf.size else torch.zeros(0, dtype=torch.uint8, device="cuda")
+    plan = XzDevicePlan(ctx, d_src, block_table(entries)).run()
+    return plan.results(), plan

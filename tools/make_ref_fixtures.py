@@ -107,6 +107,36 @@ def make_zip_fixtures():
     json.dump(manifest, open(os.path.join(out, "manifest.json"), "w"), indent=1)
 
 
+# xz (the xz read filter): the reference's own compat sample, and two files made here by the image's /usr/bin/xz -- a
+# threaded writer's (every block header carries both sizes) and a plain one's (one block, no sizes).  The expected
+# payload is what the image's liblzma (Python's lzma) gives; the entry names are the ones test_compat_xz.c walks.
+XZ_NAMES = ["f1", "f2", "f3", "d1/f1", "d1/f2", "d1/f3"]
+
+
+def make_xz_fixtures():
+    import lzma, random, subprocess
+    out = os.path.join(OUT, "xz")
+    os.makedirs(out, exist_ok=True)
+    rel = "libarchive/test/test_compat_xz_1.txz.uu"
+    raw = uudecode(open(os.path.join(REF, rel), "r", errors="replace").read())
+    r = random.Random(0x787A)
+    words = [bytes(r.choice(b"abcdefghijklmnop") for _ in range(2 + i % 9)) for i in range(200)]
+    plain = b" ".join(r.choice(words) for _ in range(40000))[:200000]
+    made = [("threaded.xz", ["/usr/bin/xz", "-T2", "--block-size=65536", "-c"], "xz -T2 --block-size=65536: four blocks, sizes in every header"),
+            ("single.xz", ["/usr/bin/xz", "-c"], "plain xz: one block without sizes")]
+    files = [("test_compat_xz_1.txz", raw, rel, "test_compat_xz.c:40-76: f1 f2 f3 d1/f1 d1/f2 d1/f3", XZ_NAMES)]
+    for name, cmd, note in made:
+        files.append((name, subprocess.run(cmd, input=plain, stdout=subprocess.PIPE, check=True).stdout, "made by " + " ".join(cmd[:-1]), note, None))
+    manifest = []
+    for name, img, source, note, names in files:
+        open(os.path.join(out, name), "wb").write(img)
+        dec = lzma.decompress(img)
+        manifest.append({"file": name, "source": source, "codec": "xz", "decoded_size": len(dec), "decoded_sha256": hashlib.sha256(dec).hexdigest(),
+                         "pins": note, "entries": names, "stream_sha256": hashlib.sha256(img).hexdigest()})
+        print(name, len(img), len(dec))
+    json.dump(manifest, open(os.path.join(out, "manifest.json"), "w"), indent=1)
+
+
 def uudecode(text):
     out = bytearray()
     started = False
@@ -142,6 +172,7 @@ def main():
         print(name, len(raw))
     json.dump(manifest, open(os.path.join(OUT, "manifest.json"), "w"), indent=1)
     make_zip_fixtures()
+    make_xz_fixtures()
 
 
 if __name__ == "__main__":
