@@ -749,6 +749,39 @@ uint64_t la_gpu_bzip2_compress_bound(uint64_t src_bytes, uint32_t level);
 int      la_gpu_bzip2_compress(la_gpu_ctx *ctx, const la_bz2c_batch *batch);
 uint32_t la_gpu_bzip2_compress_sort_rounds(la_gpu_ctx *ctx);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * xz compression -- replaces the lzma_code loop of libarchive/archive_write_add_filter_xz.c (liblzma is the reference's
+ * external dependency for this codec) for the blocks of ONE .xz stream.  d_src[0, src_bytes) is cut every
+ * LA_XZC_BLOCK_BYTES input bytes, at every level; every cut is one complete block: a 16-byte block header with both sizes
+ * and one LZMA2 filter (dictionary 1 MiB), LZMA2 chunks of LA_XZC_CHUNK_BYTES input bytes each, the end marker, zero
+ * padding to four bytes and the CRC64.  The chunk is the parallel unit: each one resets state and properties (control
+ * 0xE0 for a block's first chunk, 0xC0 otherwise; lc 3, lp 0, pb 2), and one whose coding is not smaller than its input is
+ * stored (0x01 / 0x02), so a chunk takes at most its input + 5 bytes.  Levels 0..3 match a chunk against itself; levels
+ * 4..9 also against the up to 64 KiB of the same block in front of it.  csrc/la_xz_enc_dev.h states the rules.
+ * The blocks are written back to back into d_out; LA_XZC_FIRST puts the 12-byte stream header (check CRC64) in front.
+ * Index and footer are the host's (host/la_write_xz.c), which reads the sizes back out of the block headers.
+ * *d_out_bytes is the size needed; nothing is written at or behind out_cap; la_gpu_xz_compress_bound(), exact arithmetic
+ * from the shape above, always fits.  The bytes are not liblzma's; every conforming reader returns the input.
+ * src_bytes is at most LA_XZC_MAX_SRC_BYTES (positions are 32-bit).  The workspace is one slot per chunk, about the size
+ * of the input.  Additions under ABI version 3. */
+#define LA_XZC_BLOCK_BYTES   ((uint32_t)1 << 20)
+#define LA_XZC_CHUNK_BYTES   ((uint32_t)1 << 16)
+#define LA_XZC_MAX_SRC_BYTES ((uint64_t)1 << 30)
+#define LA_XZC_FIRST 1u		/* the stream header goes in front */
+typedef struct la_xzc_batch {
+	const uint8_t *d_src;
+	uint64_t       src_bytes;
+	uint32_t       level;	/* 0..9 */
+	uint32_t       flags;	/* LA_XZC_* */
+	uint8_t       *d_out;
+	uint64_t       out_cap;
+	uint64_t      *d_out_bytes;
+} la_xzc_batch;
+uint64_t la_gpu_xz_compress_block_bytes(uint32_t level);	/* LA_XZC_BLOCK_BYTES; 0 for a level above 9 */
+uint64_t la_gpu_xz_compress_workspace_bytes(uint64_t src_bytes);
+uint64_t la_gpu_xz_compress_bound(uint64_t src_bytes, uint32_t level);
+int      la_gpu_xz_compress(la_gpu_ctx *ctx, const la_xzc_batch *batch);
+
 #ifdef __cplusplus
 }
 #endif

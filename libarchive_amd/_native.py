@@ -126,6 +126,15 @@ class _XzBatchC(C.Structure):
                 ("reserved", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
 
 
+class _XzcBatchC(C.Structure):      # la_xzc_batch
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("level", C.c_uint32), ("flags", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
+
+
+LA_XZC_FIRST = 1
+LA_XZC_BLOCK_BYTES, LA_XZC_CHUNK_BYTES = 1 << 20, 1 << 16
+
+
 class _Bz2StateC(C.Structure):
     _fields_ = [("open", C.c_uint32), ("level", C.c_uint32), ("crc", C.c_uint32), ("stop", C.c_uint32),
                 ("start_bit", C.c_uint64), ("total_out", C.c_uint64), ("n_taken", C.c_uint32), ("stop_entry", C.c_uint32),
@@ -264,6 +273,13 @@ def gpu_lib():
         lib.la_gpu_xz_decode.argtypes = [C.c_void_p, C.POINTER(_XzBatchC)]
         lib.la_gpu_xz_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_xz_workspace_bytes.argtypes = [C.c_uint32]
+        lib.la_gpu_xz_compress.argtypes = [C.c_void_p, C.POINTER(_XzcBatchC)]
+        lib.la_gpu_xz_compress_block_bytes.restype = C.c_uint64
+        lib.la_gpu_xz_compress_block_bytes.argtypes = [C.c_uint32]
+        lib.la_gpu_xz_compress_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_xz_compress_workspace_bytes.argtypes = [C.c_uint64]
+        lib.la_gpu_xz_compress_bound.restype = C.c_uint64
+        lib.la_gpu_xz_compress_bound.argtypes = [C.c_uint64, C.c_uint32]
         lib.la_gpu_bzip2_compress_block_bytes.restype = C.c_uint32
         lib.la_gpu_bzip2_compress_block_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_bzip2_compress_workspace_bytes.restype = C.c_uint64
@@ -498,6 +514,9 @@ class GpuContext:
 
     def xz_decode(self, batch: _XzBatchC):
         self._check(gpu_lib().la_gpu_xz_decode(self._h, C.byref(batch)), "la_gpu_xz_decode")
+
+    def xz_compress(self, batch: _XzcBatchC):
+        self._check(gpu_lib().la_gpu_xz_compress(self._h, C.byref(batch)), "la_gpu_xz_compress")
 
     def gzip_decode(self, batch: _GzBatchC):
         self._check(gpu_lib().la_gpu_gzip_decode(self._h, C.byref(batch)), "la_gpu_gzip_decode")

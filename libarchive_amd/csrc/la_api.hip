@@ -853,4 +853,29 @@ uint32_t la_gpu_bzip2_compress_sort_rounds(la_gpu_ctx *c)
 	return c && c->ws ? la_bzip2_compress_rounds(c->stream, (const uint8_t *)c->ws) : 0u;
 }
 
+uint64_t la_gpu_xz_compress_block_bytes(uint32_t level)
+{
+	return level <= 9u ? LA_XZC_BLOCK_BYTES : 0u;
+}
+uint64_t la_gpu_xz_compress_workspace_bytes(uint64_t src_bytes)
+{
+	return src_bytes <= LA_XZC_MAX_SRC_BYTES ? la_xz_compress_ws_bytes(src_bytes) : 0u;
+}
+uint64_t la_gpu_xz_compress_bound(uint64_t src_bytes, uint32_t level)
+{
+	return level <= 9u ? la_xz_compress_bound(src_bytes) : 0u;
+}
+int la_gpu_xz_compress(la_gpu_ctx *c, const la_xzc_batch *bt)
+{
+	if (!c || !bt || !bt->d_out_bytes || (bt->src_bytes && !bt->d_src) || (bt->out_cap && !bt->d_out))
+		return LA_ERR_ARG;
+	if (bt->level > 9u || (bt->flags & ~LA_XZC_FIRST) || bt->src_bytes > LA_XZC_MAX_SRC_BYTES)
+		return LA_ERR_ARG;
+	return compress_run(c, la_xz_compress_ws_bytes(bt->src_bytes), "xz_compress", [&](uint8_t *ws) {
+		bz2c_prof pr = { c, -1 };
+		const la_stage_hook hook = { bz2c_mark, &pr };
+		la_launch_xz_compress(c->stream, bt, ws, &hook);
+	});
+}
+
 } /* extern "C" */

@@ -578,6 +578,11 @@ uint32_t la_bzip2_compress_rounds(hipStream_t s, const uint8_t *ws);
 struct la_stage_hook { void (*mark)(void *cx, const char *name); void *cx; };
 void la_launch_bzip2_compress(hipStream_t s, const la_bz2c_batch *bt, uint8_t *ws, const la_stage_hook *hook);
 
+/* la_xz_comp.hip */
+uint64_t la_xz_compress_ws_bytes(uint64_t src_bytes);
+uint64_t la_xz_compress_bound(uint64_t src_bytes);
+void la_launch_xz_compress(hipStream_t s, const la_xzc_batch *bt, uint8_t *ws, const la_stage_hook *hook);
+
 /* la_lz4_comp.hip */
 void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);

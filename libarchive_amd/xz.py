@@ -1,6 +1,6 @@
-"""Device-resident xz block decode through the C ABI (harness for tests / tools).  Plumbing only: torch allocates the
-HBM buffers; the block table is the caller's (the container is walked on the host, host/la_filter_xz.c), all work is
-la_gpu_xz_decode()."""
+"""Device-resident xz block decode and compression through the C ABI (harness for tests / tools).  Plumbing only: torch
+allocates the HBM buffers; the block table is the caller's (the container is walked on the host, host/la_filter_xz.c),
+all work is la_gpu_xz_decode() and la_gpu_xz_compress()."""
 import numpy as np
 
 from . import _native as N
@@ -8,6 +8,36 @@ from . import _native as N
 XZ_BLOCK_DTYPE, XZ_RESULT_DTYPE, LA_XZ_UNKNOWN = N.XZ_BLOCK_DTYPE, N.XZ_RESULT_DTYPE, N.LA_XZ_UNKNOWN
 LA_ST_XZ_DATA, LA_ST_XZ_LZMA, LA_ST_XZ_TRUNCATED, LA_ST_XZ_SIZE = N.LA_ST_XZ_DATA, N.LA_ST_XZ_LZMA, N.LA_ST_XZ_TRUNCATED, N.LA_ST_XZ_SIZE
 LA_ST_XZ_BAD_CHECK, LA_ST_XZ_PADDING, LA_ST_XZ_OUT_FULL = N.LA_ST_XZ_BAD_CHECK, N.LA_ST_XZ_PADDING, N.LA_ST_XZ_OUT_FULL
+LA_XZC_FIRST, LA_XZC_BLOCK_BYTES, LA_XZC_CHUNK_BYTES = N.LA_XZC_FIRST, N.LA_XZC_BLOCK_BYTES, N.LA_XZC_CHUNK_BYTES
+
+
+def compress_bound(n, level=6):
+    return int(N.gpu_lib().la_gpu_xz_compress_bound(n, level))
+
+
+def compress_window(ctx, d_plain, level=6, flags=N.LA_XZC_FIRST, out_cap=None, d_out=None):
+    """Device xz compression of one window (la_gpu_xz_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8 CUDA
+    tensor holding the window's blocks back to back, the stream header in front under LA_XZC_FIRST (index and footer are
+    the write filter's).  With `out_cap` (and optionally `d_out`) the call gets that much room only and the needed size
+    is returned beside the tensor."""
+    import torch
+    n = int(d_plain.numel())
+    dev = d_plain.device
+    cap = compress_bound(n, level) if out_cap is None else int(out_cap)
+    if d_out is None:
+        d_out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+    d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    b = N._XzcBatchC()
+    b.d_src, b.src_bytes = (d_plain.data_ptr() if n else None), n
+    b.level, b.flags = level, flags
+    b.d_out, b.out_cap, b.d_out_bytes = d_out.data_ptr(), cap, d_len.data_ptr()
+    ctx.xz_compress(b)
+    ctx.sync()
+    total = int(d_len.cpu()[0])
+    if out_cap is not None:
+        return d_out, total
+    assert total <= cap, (total, cap)
+    return d_out[:total]
 
 
 def block_table(entries):

@@ -1,0 +1,104 @@
+/*
+ * la_gpu_xz_comp_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_xz_compress as include/la_gpu.h words it, so
+ * that the xz write filter's host side (host/la_write_xz.c) and the encoder's rules are tested without a GPU.  "Device"
+ * pointers are host pointers, as in ../mock_gpu/la_gpu_mock.c.
+ *
+ * The rules are NOT restated here: this file compiles libarchive_amd/csrc/la_xz_enc_dev.h, the header the kernels
+ * compile, with the header's defaults: the 64 lanes of a step are walked in a loop, all reads before any write, so the
+ * bytes are the device's.  What the kernels add around the header (who writes which piece of a block, the CRC64 of a
+ * block combined from its chunks') is repeated below in the kernels' order.
+ *
+ * la_xzc_mock_events(out, reset) reads the event counters of the header's hook (LA_XZC_EV_*), for tests/test_xz_encode_rules.py.
+ */
+#include "../../include/la_gpu.h"
+#include <stdlib.h>
+#include <string.h>
+
+static uint64_t xzc_events[32];
+#define LA_XZ_FN static inline
+#define LA_XZC_EVENT(kind) (xzc_events[(kind)]++)
+#include "../../libarchive_amd/csrc/la_xz_enc_dev.h"
+
+uint32_t la_xzc_mock_events(uint64_t *out, int reset)
+{
+	for (int i = 0; i < LA_XZC_EV_COUNT; i++) {
+		if (out)
+			out[i] = xzc_events[i];
+		if (reset)
+			xzc_events[i] = 0;
+	}
+	return LA_XZC_EV_COUNT;
+}
+
+uint64_t la_gpu_xz_compress_block_bytes(uint32_t level) { return level <= 9u ? LA_XZC_BLOCK_BYTES : 0u; }
+uint64_t la_gpu_xz_compress_workspace_bytes(uint64_t src_bytes) { (void)src_bytes; return 0; }
+uint64_t la_gpu_xz_compress_bound(uint64_t src_bytes, uint32_t level) { return level <= 9u ? la_xzc_bound(src_bytes) : 0u; }
+
+struct sink { uint8_t *p; uint64_t cap, n; };
+static void put(struct sink *s, const uint8_t *b, uint64_t n)
+{
+	for (uint64_t i = 0; i < n; i++, s->n++)
+		if (s->n < s->cap)
+			s->p[s->n] = b[i];
+}
+
+int la_gpu_xz_compress(la_gpu_ctx *c, const la_xzc_batch *bt)
+{
+	static uint64_t table[256];
+	if (!c || !bt || !bt->d_out_bytes || (bt->src_bytes && !bt->d_src) || (bt->out_cap && !bt->d_out))
+		return LA_ERR_ARG;
+	if (bt->level > 9u || (bt->flags & ~LA_XZC_FIRST) || bt->src_bytes > LA_XZC_MAX_SRC_BYTES)
+		return LA_ERR_ARG;
+	if (table[1] == 0)
+		for (uint32_t i = 0; i < 256; i++)
+			table[i] = la_xz_crc64_entry(i);
+	const uint32_t per = LA_XZC_BLOCK_BYTES / LA_XZC_CHUNK_BYTES;
+	uint16_t *probs = malloc(sizeof(uint16_t) * LA_XZC_PROBS);
+	uint32_t *tab = malloc(sizeof(uint32_t) * LA_XZC_TAB);
+	uint8_t *slots = malloc((size_t)per * LA_XZC_SLOT_BYTES);
+	if (!probs || !tab || !slots) {
+		free(probs); free(tab); free(slots);
+		return LA_ERR_NOMEM;
+	}
+	struct sink s = { bt->d_out, bt->out_cap, 0 };
+	uint8_t h[LA_XZC_BLOCK_HDR];
+	if (bt->flags & LA_XZC_FIRST) {
+		la_xzc_stream_header(h);
+		put(&s, h, 12);
+	}
+	for (uint64_t boff = 0; boff < bt->src_bytes; boff += LA_XZC_BLOCK_BYTES) {
+		const uint8_t *blk = bt->d_src + boff;
+		const uint32_t blen = bt->src_bytes - boff < LA_XZC_BLOCK_BYTES ? (uint32_t)(bt->src_bytes - boff) : LA_XZC_BLOCK_BYTES;
+		const uint32_t nc = (blen + LA_XZC_CHUNK_BYTES - 1u) / LA_XZC_CHUNK_BYTES;
+		uint32_t payload[LA_XZC_BLOCK_BYTES / LA_XZC_CHUNK_BYTES], m_len[64], m_cand[64];
+		uint64_t comp = 1, crc = 0;
+		for (uint32_t k = 0; k < nc; k++) {
+			const uint32_t cs = k * LA_XZC_CHUNK_BYTES, ce = cs + LA_XZC_CHUNK_BYTES < blen ? cs + LA_XZC_CHUNK_BYTES : blen;
+			payload[k] = la_xzc_chunk(blk, cs, ce, bt->level, probs, tab, m_len, m_cand, slots + (size_t)k * LA_XZC_SLOT_BYTES);
+			comp += la_xzc_chunk_bytes(ce - cs, payload[k]);
+			/* the block's CRC64 from the chunks', by the combine arithmetic of the kernel */
+			const uint64_t cc = la_xz_crc64(table, blk + cs, ce - cs, 0);
+			crc = k ? la_xz_crc64_mul(la_xz_crc64_shift(ce - cs), crc) ^ cc : cc;
+		}
+		la_xzc_block_header(h, comp, blen);
+		put(&s, h, LA_XZC_BLOCK_HDR);
+		for (uint32_t k = 0; k < nc; k++) {
+			const uint32_t cs = k * LA_XZC_CHUNK_BYTES, n = (cs + LA_XZC_CHUNK_BYTES < blen ? cs + LA_XZC_CHUNK_BYTES : blen) - cs;
+			if (payload[k]) {
+				put(&s, slots + (size_t)k * LA_XZC_SLOT_BYTES, 6u + payload[k]);
+			} else {
+				la_xzc_stored_header(h, n, k == 0);
+				put(&s, h, 3);
+				put(&s, blk + cs, n);
+			}
+		}
+		memset(h, 0, sizeof(h));
+		put(&s, h, 1u + (uint32_t)(la_xzc_block_bytes(comp) - LA_XZC_BLOCK_HDR - 8u - comp));
+		for (int i = 0; i < 8; i++)
+			h[i] = (uint8_t)(crc >> (8 * i));
+		put(&s, h, 8);
+	}
+	*bt->d_out_bytes = s.n;
+	free(probs); free(tab); free(slots);
+	return LA_OK;
+}

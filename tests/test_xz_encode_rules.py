@@ -1,0 +1,64 @@
+"""The encoder's rules (libarchive_amd/csrc/la_xz_enc_dev.h) through the ABI entry of the CPU stand-in, which compiles
+that header: about 2 000 small seeded inputs, each decoded by liblzma as raw LZMA2, and over the whole set the header's
+event hook must have seen every symbol kind the encoder can write."""
+import random
+
+import pytest
+
+import xz_parse as XP
+import xz_support as XS
+import xz_write_support as W
+
+
+@pytest.fixture(scope="module")
+def stand_in(tmp_path_factory):
+    return W.StandIn(str(tmp_path_factory.mktemp("mock_xz_write")))
+
+
+def small_inputs():
+    """1 .. 3 000 bytes: letters over alphabets of 2 .. 10, text, noise, runs, repeats of short units"""
+    r = random.Random(2024)
+    for i in range(2000):
+        n = r.choice((1, 2, 3, 5, 17, 64, 65, 300, 1000, 3000)) if i % 4 == 0 else r.randint(1, 3000)
+        kind = i % 6
+        if kind == 0:
+            yield XS.letters(i, n, 2 + i // 6 % 9)
+        elif kind == 1:
+            yield XS.text(i, n)
+        elif kind == 2:
+            yield r.randbytes(n)
+        elif kind == 3:         # runs of random lengths, the longest above 273 and above 546
+            out = bytearray()
+            while len(out) < n:
+                out += bytes([r.randrange(4)]) * r.choice((1, 2, 3, 9, 10, 17, 18, 274, 600))
+            yield bytes(out[:n])
+        elif kind == 4:         # a few units repeated in changing order: the four reps
+            units = [r.randbytes(r.randint(5, 40)) for _ in range(4)]
+            out = bytearray()
+            while len(out) < n:
+                out += r.choice(units) + r.randbytes(r.randint(0, 3))
+            yield bytes(out[:n])
+        else:                   # text with a byte changed here and there: matches broken by one literal
+            b = bytearray(XS.text(i, n) * 2)[:n]
+            for _ in range(n // 50):
+                b[r.randrange(n)] ^= 1
+            yield bytes(b)
+
+
+def test_small_inputs_decode_and_reach_every_rule(stand_in):
+    stand_in.events(reset=True)
+    count = 0
+    for data in small_inputs():
+        for level in (0, 6):
+            out = stand_in.compress(data, level)
+            assert len(out) <= stand_in.bound(len(data), level)
+            hs = (out[12] + 1) * 4
+            comp, _ = XP.vli(out, 12 + 2)
+            assert XP.raw_lzma2(out[12 + hs:12 + hs + comp]) == data, (count, level)
+        count += 1
+    ev = stand_in.events()
+    print(count, "inputs;", ev)
+    assert count == 2000
+    for name in ("carry_long", "stored", "rep0", "rep1", "rep2", "rep3", "short_rep", "len_low", "len_mid", "len_high", "split", "dist_slot",
+                 "dist_special", "dist_align", "matched_literal"):
+        assert ev[name] > 0, name
