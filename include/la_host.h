@@ -17,6 +17,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <sys/types.h>	/* ssize_t */
 #include "la_gpu.h"
 
 #ifdef __cplusplus
@@ -183,14 +184,15 @@ int    la_bid_lz4_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead);
 
-/* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the lz4, gzip and zstd read filters ---- */
+/* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the read filters; the held-back delivery at its
+ * end by the bzip2 and xz ones ---- */
 /* LA_GPU_DEVICE: the device ordinal every filter, the ZIP reader and the hash drop-in open (default 0) */
 int  la_env_device(void);
 
 /* One filter's window: its device, its size (read once, at init) and whether upstream has ended */
 typedef struct la_window {
 	la_gpu_ctx *gpu;
-	const char *name;		/* "lz4", "gzip", "zstd": in the error strings */
+	const char *name;		/* "lz4", "gzip", "zstd", "bzip2", "xz": in the error strings */
 	size_t      batch_bytes;	/* compressed bytes of the next window: min(16 MiB, target), then ramped */
 	size_t      target_bytes;	/* LA_GPU_BATCH_MIB, default 64 */
 	size_t      max_batch_bytes;	/* LA_GPU_MAX_BATCH_MIB, default 2048: how far a window may widen */
@@ -220,6 +222,11 @@ void la_buf_release(la_gpu_ctx *gpu, la_buf *b);
 /* Append upstream bytes to the pinned stage[0..*len) until it holds a window (w->batch_bytes) or upstream
  * ends (w->upstream_eof).  ARCHIVE_FATAL with upstream's error left in place, or after la_window_fail. */
 int  la_window_gather(struct archive_read_filter *self, la_window *w, la_buf *stage, size_t *len);
+/* Drop stage[0, used): the unfinished unit opens the next window.  When that unit needs more bytes (`more`), nothing
+ * was dropped and the window was full, the unit is larger than the window: double it up to max_batch_bytes, or refuse
+ * "<name> <unit> too large for the GPU data plane (more than %llu compressed bytes; LA_GPU_MAX_BATCH_MIB)". */
+int  la_window_carry(struct archive_read_filter *self, la_window *w, la_buf *stage, size_t *len, size_t used, int more,
+         const char *unit);
 
 /* A verdict reported after the bytes in front of it: rc (ARCHIVE_OK = none) and the message to set with it.
  * fmt NULL: no message (upstream already set the error, or the reference returns ARCHIVE_FATAL without one). */
@@ -234,6 +241,34 @@ __attribute__((format(printf, 3, 4)))
 void la_verdict_set(la_verdict *v, int rc, const char *fmt, ...);
 /* sets the message, if any, and returns rc */
 int  la_verdict_report(struct archive_read_filter *self, const la_verdict *v);
+
+/* Decoded bytes held back in front of a possible error (the bzip2 and xz filters).  The reference hands out whole
+ * blocks of LA_OUT_BLOCK bytes and loses the partial block on an error, so with T bytes decoded everything up to the
+ * last block boundary strictly below T is safe to hand out; the rest (at most one block) waits for the next window's
+ * verdict.  Each filter's head comment derives T and which of its errors is early or late. */
+#define LA_OUT_BLOCK ((uint64_t)65536)	/* bzip2.c:186, xz.c:474 */
+typedef struct la_holdback {
+	la_buf   out; size_t out_len, out_pos;	/* pinned: what the current window decoded (the window appends, read takes) */
+	uint8_t *tail; size_t tail_len;		/* held back from earlier windows, at most one block */
+	uint64_t total, delivered;		/* T (the window adds to it), bytes handed out */
+	la_verdict verdict; uint64_t end_limit; int ended;	/* the stream's end is known: reported once end_limit bytes are out */
+	int      finished;
+} la_holdback;
+enum {
+	LA_HB_EARLY,	/* the error arrives in the call that emitted byte T: floor((T-1)/64Ki)*64Ki bytes go out, 0 for T = 0 */
+	LA_HB_LATE,	/* it arrives in a call of its own: floor(T/64Ki)*64Ki */
+	LA_HB_ALL	/* a clean end: T */
+};
+int     la_holdback_open(la_holdback *h);	/* the tail block; -1: no memory */
+/* The stream ends here, T being h->total: rc and msg (NULL: none) are reported behind the bytes `how` lets out.  A
+ * later call replaces an earlier one. */
+void    la_holdback_end(la_holdback *h, int rc, const char *msg, int how);
+/* The filter's read(): hands out what may go, then the verdict once, then 0; runs window(self) -- which appends to
+ * `out`, adds to `total` and may call la_holdback_end -- whenever it needs more.  A window that does not return
+ * ARCHIVE_OK has set its error: that code is returned and the read is over. */
+ssize_t la_holdback_read(struct archive_read_filter *self, const la_window *w, la_holdback *h, const void **p,
+            int (*window)(struct archive_read_filter *));
+void    la_holdback_release(la_gpu_ctx *gpu, la_holdback *h);
 
 /* ---- hash drop-ins (host/la_hash_dropin.c) ----
  * The 4-pointer table of libarchive/archive_xxhash.h:37-46 (defined as `__archive_xxhash` when built

@@ -1,6 +1,7 @@
 /*
- * la_bid_policy.c -- the host code the three read filters (la_filter_lz4.c, la_filter_gzip.c, la_filter_zstd.c)
- * share: the bid policy, and below it the window plumbing.
+ * la_bid_policy.c -- the host code the read filters (la_filter_lz4.c, la_filter_gzip.c, la_filter_zstd.c,
+ * la_filter_bzip2.c, la_filter_xz.c) share: the bid policy, below it the window plumbing, and at the end the held-back
+ * delivery of the bzip2 and xz filters.
  *
  * Bid policy: should the GPU filter take this stream at all?
  *
@@ -176,8 +177,9 @@ int la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead)
 
 /*
  * Window plumbing: the window configuration and its ramp, opening the device, the "GPU data plane" error strings,
- * the buffer growers, the gather loop and the deferred verdict.  What differs between the filters -- the walker,
- * the launch, the stream-order walk of the results -- stays in each filter.
+ * the buffer growers, the gather loop, the carry of the unfinished unit, the deferred verdict and the held-back
+ * delivery.  What differs between the filters -- the walker, the launch, the stream-order walk of the results --
+ * stays in each filter.
  */
 #define MIB ((size_t)1 << 20)
 
@@ -326,6 +328,24 @@ int la_window_gather(struct archive_read_filter *self, la_window *w, la_buf *sta
 	return ARCHIVE_OK;
 }
 
+int la_window_carry(struct archive_read_filter *self, la_window *w, la_buf *stage, size_t *len, size_t used, int more,
+    const char *unit)
+{
+	if (more && used == 0 && *len >= w->batch_bytes) {
+		/* one unit larger than the window: widen it, as the other filters do */
+		if (*len >= w->max_batch_bytes) {
+			archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+			    "%s %s too large for the GPU data plane (more than %llu compressed bytes; LA_GPU_MAX_BATCH_MIB)",
+			    w->name, unit, (unsigned long long)w->max_batch_bytes);
+			return ARCHIVE_FATAL;
+		}
+		w->batch_bytes = *len * 2 < w->max_batch_bytes ? *len * 2 : w->max_batch_bytes;
+	}
+	memmove(stage->p, stage->p + used, *len - used);
+	*len -= used;
+	return ARCHIVE_OK;
+}
+
 void la_verdict_set(la_verdict *v, int rc, const char *fmt, ...)
 {
 	v->rc = rc;
@@ -343,4 +363,87 @@ int la_verdict_report(struct archive_read_filter *self, const la_verdict *v)
 	if (v->has_msg)
 		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "%s", v->msg);
 	return v->rc;
+}
+
+int la_holdback_open(la_holdback *h)
+{
+	return (h->tail = malloc((size_t)LA_OUT_BLOCK)) != NULL ? 0 : -1;
+}
+
+static uint64_t block_floor(uint64_t n)
+{
+	return n / LA_OUT_BLOCK * LA_OUT_BLOCK;
+}
+
+void la_holdback_end(la_holdback *h, int rc, const char *msg, int how)
+{
+	if (msg)
+		la_verdict_set(&h->verdict, rc, "%s", msg);
+	else
+		la_verdict_set(&h->verdict, rc, NULL);
+	h->ended = 1;
+	h->end_limit = how == LA_HB_ALL ? h->total : block_floor(how == LA_HB_EARLY && h->total ? h->total - 1 : h->total);
+}
+
+/* bytes that may be handed out: while the stream goes on, whatever follows is at best an early error */
+static uint64_t holdback_limit(const la_holdback *h)
+{
+	return h->ended ? h->end_limit : block_floor(h->total ? h->total - 1 : 0);
+}
+
+ssize_t la_holdback_read(struct archive_read_filter *self, const la_window *w, la_holdback *h, const void **p,
+    int (*window)(struct archive_read_filter *))
+{
+	*p = NULL;
+	if (h->finished)
+		return 0;
+	for (;;) {
+		const uint64_t limit = holdback_limit(h);
+		if (h->tail_len && h->delivered + h->tail_len <= limit) {
+			const size_t k = h->tail_len;
+			*p = h->tail;
+			h->tail_len = 0;
+			h->delivered += k;
+			return (ssize_t)k;
+		}
+		if (h->tail_len == 0 && h->out_pos < h->out_len && h->delivered < limit) {
+			size_t k = h->out_len - h->out_pos;
+			if (k > limit - h->delivered)
+				k = (size_t)(limit - h->delivered);
+			*p = h->out.p + h->out_pos;
+			h->out_pos += k;
+			h->delivered += k;
+			return (ssize_t)k;
+		}
+		if (h->ended) {
+			h->finished = 1;
+			if (h->verdict.rc != ARCHIVE_OK)
+				return la_verdict_report(self, &h->verdict);
+			return 0;
+		}
+		/* what the window holds beyond `limit` (with the tail, at most one block) waits for the next window's verdict */
+		if (h->out_pos < h->out_len) {
+			const size_t k = h->out_len - h->out_pos;
+			if (h->tail_len + k > LA_OUT_BLOCK) {
+				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "%s filter: held-back bytes exceed one block", w->name);
+				h->finished = 1;
+				return ARCHIVE_FATAL;
+			}
+			memcpy(h->tail + h->tail_len, h->out.p + h->out_pos, k);
+			h->tail_len += k;
+		}
+		h->out_len = h->out_pos = 0;
+		const int r = window(self);
+		if (r != ARCHIVE_OK) {
+			h->finished = 1;
+			return r;
+		}
+	}
+}
+
+void la_holdback_release(la_gpu_ctx *gpu, la_holdback *h)
+{
+	la_buf_release(gpu, &h->out);
+	free(h->tail);
+	h->tail = NULL;
 }

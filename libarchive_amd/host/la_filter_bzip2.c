@@ -20,15 +20,15 @@
  * on to read the next header in the same call even when the output block is full.  With T the bytes libbz2 has emitted
  * when it reports the error (through the block in front of a damaged header, table or symbol; through the block
  * itself for a wrong block CRC; everything for a wrong combined CRC):
- *   - a data error arrives in the call that emitted byte T or later, so the block that holds byte T is not handed out:
- *     64 KiB * floor((T - 1) / 64 KiB) bytes are delivered (0 for T = 0);
- *   - truncated input is found by the NEXT look at upstream (bzip2.c:280-287), after a full block has been returned:
- *     64 KiB * floor(T / 64 KiB) bytes are delivered;
- *   - a clean end (end of input between streams, or bytes behind a stream that fail the bid) delivers all T.
- * So at any time everything up to the last 64 KiB boundary strictly below T is safe to hand out, whatever follows; the
- * filter holds the rest (at most 64 KiB) back until it knows more.  (tests/bzip2_support.py restates the reference's
- * loop over the real libbz2; the rule above is what that emulator gives.  For T a multiple of 64 KiB the first case
- * assumes that upstream hands the reference the damaged unit together with byte T's block, as a memory reader does.)
+ *   - a data error arrives in the call that emitted byte T or later, so the block that holds byte T is not handed out
+ *     (LA_HB_EARLY);
+ *   - truncated input is found by the NEXT look at upstream (bzip2.c:280-287), after a full block has been returned
+ *     (LA_HB_LATE);
+ *   - a clean end (end of input between streams, or bytes behind a stream that fail the bid) hands out all T (LA_HB_ALL).
+ * What each kind lets out, and the holding back until the next window says which it is, is la_holdback's (la_host.h,
+ * la_bid_policy.c).  (tests/bzip2_support.py restates the reference's loop over the real libbz2; the rule above is
+ * what that emulator gives.  For T a multiple of 64 KiB the first case assumes that upstream hands the reference the
+ * damaged unit together with byte T's block, as a memory reader does.)
  */
 #include "la_read_private.h"
 #include "la_host.h"
@@ -37,7 +37,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define BZ_OUT_BLOCK   ((uint64_t)65536)	/* bzip2.c:186 */
 #define BZ_CAND_CAP    ((uint32_t)1 << 16)	/* candidates one scan keeps; a window with more is taken in parts */
 
 struct bzip2_private {
@@ -46,12 +45,8 @@ struct bzip2_private {
 	la_buf stage; size_t stage_len;	/* pinned: the stream from the byte of the next unit on */
 	la_bz2_state st;		/* where the stream stands at stage[0] */
 	la_buf d_src, d_dst, d_tabs;	/* d_tabs: candidates, results, state, count */
-	la_buf out; size_t out_len, out_pos;	/* pinned: the decoded bytes of the current window */
 	la_bz2_result *res;		/* the window's results on the host (4096 entries) */
-	uint8_t *tail; size_t tail_len;	/* held-back bytes of earlier windows (at most 64 KiB) */
-	uint64_t total, delivered, limit;	/* T, bytes handed out, bytes that may be handed out */
-	la_verdict verdict; int ended;	/* the stream's end is known: reported when everything up to limit is out */
-	int finished;
+	la_holdback hb;			/* the decoded bytes, T and the stream's end */
 };
 
 static int bzip2_reader_bid(struct archive_read_filter_bidder *, struct archive_read_filter *);
@@ -98,18 +93,15 @@ static int bzip2_reader_init(struct archive_read_filter *self)
 	self->code = ARCHIVE_FILTER_BZIP2;
 	self->name = "bzip2";
 	struct bzip2_private *st = calloc(1, sizeof(*st));
-	uint8_t *tail = malloc((size_t)BZ_OUT_BLOCK);
-	if (st == NULL || tail == NULL) {
+	if (st == NULL || la_holdback_open(&st->hb) < 0) {
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for bzip2 decompression");
 		free(st);
-		free(tail);
 		return ARCHIVE_FATAL;
 	}
-	st->tail = tail;
 	const char *sc = getenv("LA_BZIP2_SERIAL_CHASE");
 	st->options = (sc && atoi(sc) > 0) ? LA_BZ2_OPT_SERIAL_CHASE : 0u;
 	if (la_window_open(self, &st->w, "bzip2") != ARCHIVE_OK) {
-		free(tail);
+		la_holdback_release(NULL, &st->hb);
 		free(st);
 		return ARCHIVE_FATAL;
 	}
@@ -118,33 +110,18 @@ static int bzip2_reader_init(struct archive_read_filter *self)
 	return ARCHIVE_OK;
 }
 
-static int gpu_fail(struct archive_read_filter *self, struct bzip2_private *st, const char *what)
-{
-	st->finished = 1;
-	return la_window_fail(self, &st->w, what);
-}
-
-/* the stream ends here: rc and message are reported once `limit` bytes are out */
-static void bz_end(struct bzip2_private *st, int rc, const char *msg, uint64_t limit)
-{
-	if (msg)
-		la_verdict_set(&st->verdict, rc, "%s", msg);
-	else
-		la_verdict_set(&st->verdict, rc, NULL);
-	st->ended = 1;
-	st->limit = limit;
-}
+/* the stream ends here, T being hb.total */
 static void bz_end_data(struct bzip2_private *st)
 {
-	bz_end(st, ARCHIVE_FATAL, "bzip decompression failed", st->total ? (st->total - 1) / BZ_OUT_BLOCK * BZ_OUT_BLOCK : 0);
+	la_holdback_end(&st->hb, ARCHIVE_FATAL, "bzip decompression failed", LA_HB_EARLY);
 }
 static void bz_end_truncated(struct bzip2_private *st)
 {
-	bz_end(st, ARCHIVE_FATAL, "truncated bzip2 input", st->total / BZ_OUT_BLOCK * BZ_OUT_BLOCK);
+	la_holdback_end(&st->hb, ARCHIVE_FATAL, "truncated bzip2 input", LA_HB_LATE);
 }
 static void bz_end_clean(struct bzip2_private *st)
 {
-	bz_end(st, ARCHIVE_OK, NULL, st->total);
+	la_holdback_end(&st->hb, ARCHIVE_OK, NULL, LA_HB_ALL);
 }
 
 /* the byte that starts at bit `bit` of p[0, n): caller keeps bit + 8 <= 8 n */
@@ -175,15 +152,15 @@ static int bz_magic_at(const uint8_t *p, size_t n, uint64_t bit)
 	return k == 6;
 }
 
-/* One window: gather, upload, scan, measure, emit, copy back; updates the stream state, T and limit, and says how the
- * stream ends if this window shows it.  ARCHIVE_OK, or a fatal code with the error set. */
-static int bz_window(struct archive_read_filter *self, struct bzip2_private *st)
+/* One window: gather, upload, scan, measure, emit, copy back; updates the stream state and T, and says how the stream
+ * ends if this window shows it.  ARCHIVE_OK, or a fatal code with the error set. */
+static int bz_window(struct archive_read_filter *self)
 {
+	struct bzip2_private *st = (struct bzip2_private *)self->data;
 	la_gpu_ctx *gpu = st->w.gpu;
 	int r = la_window_gather(self, &st->w, &st->stage, &st->stage_len);
 	if (r != ARCHIVE_OK)
 		return r;
-	st->out_len = st->out_pos = 0;
 	if (st->stage_len == 0) {	/* (upstream has ended) */
 		if (st->st.open)
 			bz_end_truncated(st);
@@ -200,7 +177,7 @@ static int bz_window(struct archive_read_filter *self, struct bzip2_private *st)
 	const uint32_t max_n = la_gpu_bzip2_max_blocks(slot_level);
 	const size_t o_res = sizeof(la_bz2_cand) * BZ_CAND_CAP, o_state = o_res + sizeof(la_bz2_result) * 4096, o_count = o_state + 64;
 	if (la_buf_dev(gpu, &st->d_src, len + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o_count + 64) < 0)
-		return gpu_fail(self, st, "la_gpu_malloc");
+		return la_window_fail(self, &st->w, "la_gpu_malloc");
 	if (st->res == NULL && (st->res = malloc(sizeof(la_bz2_result) * 4096)) == NULL) {
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for bzip2 decompression");
 		return ARCHIVE_FATAL;
@@ -210,9 +187,9 @@ static int bz_window(struct archive_read_filter *self, struct bzip2_private *st)
 	la_bz2_state *d_state = (la_bz2_state *)(st->d_tabs.p + o_state);
 	uint32_t *d_count = (uint32_t *)(st->d_tabs.p + o_count);
 	uint32_t count = 0;
-	if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
-	if (la_gpu_bzip2_scan(gpu, st->d_src.p, len, d_cands, BZ_CAND_CAP, d_count) != LA_OK) return gpu_fail(self, st, "la_gpu_bzip2_scan");
-	if (la_gpu_memcpy_d2h(gpu, &count, d_count, 4) != LA_OK || la_gpu_sync(gpu) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+	if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
+	if (la_gpu_bzip2_scan(gpu, st->d_src.p, len, d_cands, BZ_CAND_CAP, d_count) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_bzip2_scan");
+	if (la_gpu_memcpy_d2h(gpu, &count, d_count, 4) != LA_OK || la_gpu_sync(gpu) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
 	uint32_t n = count < BZ_CAND_CAP ? count : BZ_CAND_CAP;
 	if (n > max_n)
 		n = max_n;	/* the table never holds more blocks than the workspace slots: the rest waits for the next window */
@@ -225,10 +202,10 @@ static int bz_window(struct archive_read_filter *self, struct bzip2_private *st)
 	bt.state_in = &st->st; bt.d_state_out = d_state;
 	bt.options = st->options; bt.slot_level = slot_level;
 	bt.phase = LA_BZ2_MEASURE;
-	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return gpu_fail(self, st, "la_gpu_bzip2_decode");
+	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_bzip2_decode");
 	if (la_gpu_memcpy_d2h(gpu, st->res, d_results, sizeof(la_bz2_result) * n) != LA_OK ||
 	    la_gpu_memcpy_d2h(gpu, &ms, d_state, sizeof(ms)) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
 	/* the prefix of confirmed blocks that fits the decoded-bytes budget; one block always goes (at most 46 MB) */
 	uint32_t n_emit = ms.n_taken;
 	uint64_t dst_bytes = 0;
@@ -242,23 +219,22 @@ static int bz_window(struct archive_read_filter *self, struct bzip2_private *st)
 		}
 		dst_bytes += q->out_len;
 	}
-	if (la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0) return gpu_fail(self, st, "la_gpu_malloc");
-	if (la_buf_pinned(gpu, &st->out, (size_t)dst_bytes + 64, 0) < 0) return gpu_fail(self, st, "la_gpu_malloc_host");
+	if (la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc");
+	if (la_buf_pinned(gpu, &st->hb.out, (size_t)dst_bytes + 64, 0) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc_host");
 	bt.phase = LA_BZ2_EMIT;
 	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes; bt.n_emit = n_emit;
-	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return gpu_fail(self, st, "la_gpu_bzip2_decode");
+	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_bzip2_decode");
 	if (la_gpu_memcpy_d2h(gpu, &es, d_state, sizeof(es)) != LA_OK ||
 	    la_gpu_memcpy_d2h(gpu, st->res, d_results, sizeof(la_bz2_result) * n) != LA_OK ||
-	    la_gpu_memcpy_d2h(gpu, st->out.p, st->d_dst.p, dst_bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+	    la_gpu_memcpy_d2h(gpu, st->hb.out.p, st->d_dst.p, dst_bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
+		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
 	la_window_ramp(&st->w);
-	st->out_len = (size_t)es.total_out;	/* (through a block with a wrong CRC: libbz2 emits it before it compares) */
-	st->total += es.total_out;
+	st->hb.out_len = (size_t)es.total_out;	/* (through a block with a wrong CRC: libbz2 emits it before it compares) */
+	st->hb.total += es.total_out;
 	if (es.first_bad != 0xFFFFFFFFu) {
 		bz_end_data(st);
 		return ARCHIVE_OK;
 	}
-	st->limit = st->total ? (st->total - 1) / BZ_OUT_BLOCK * BZ_OUT_BLOCK : 0;
 	const uint64_t stop_bit = es.start_bit;
 	const size_t used = (size_t)(stop_bit >> 3) < len ? (size_t)(stop_bit >> 3) : len;
 	int more = 0;	/* the unit at stop_bit needs bytes the window does not hold */
@@ -290,26 +266,15 @@ static int bz_window(struct archive_read_filter *self, struct bzip2_private *st)
 		else
 			more = 1;
 	}
-	if (st->ended)
+	if (st->hb.ended)
 		return ARCHIVE_OK;
 	if (!more && used == 0 && es.total_out == 0) {
 		/* (cannot be: a window that neither ends the stream nor asks for more input has passed at least one unit) */
 		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "bzip2 GPU data plane: a window made no progress");
 		return ARCHIVE_FATAL;
 	}
-	if (more && used == 0 && len >= st->w.batch_bytes) {
-		/* one unit larger than the window: widen it, as the other filters do */
-		if (len >= st->w.max_batch_bytes) {
-			archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-			    "bzip2 block too large for the GPU data plane (more than %llu compressed bytes; LA_GPU_MAX_BATCH_MIB)",
-			    (unsigned long long)st->w.max_batch_bytes);
-			st->finished = 1;
-			return ARCHIVE_FATAL;
-		}
-		st->w.batch_bytes = len * 2 < st->w.max_batch_bytes ? len * 2 : st->w.max_batch_bytes;
-	}
-	memmove(st->stage.p, st->stage.p + used, len - used);
-	st->stage_len = len - used;
+	if ((r = la_window_carry(self, &st->w, &st->stage, &st->stage_len, used, more, "block")) != ARCHIVE_OK)
+		return r;
 	st->st.open = es.open; st->st.level = es.level; st->st.crc = es.crc;
 	st->st.start_bit = stop_bit - (uint64_t)used * 8;
 	return ARCHIVE_OK;
@@ -318,50 +283,7 @@ static int bz_window(struct archive_read_filter *self, struct bzip2_private *st)
 static ssize_t bzip2_filter_read(struct archive_read_filter *self, const void **p)
 {
 	struct bzip2_private *st = (struct bzip2_private *)self->data;
-	*p = NULL;
-	if (st->finished)
-		return 0;
-	for (;;) {
-		if (st->tail_len && st->delivered + st->tail_len <= st->limit) {
-			const size_t k = st->tail_len;
-			*p = st->tail;
-			st->tail_len = 0;
-			st->delivered += k;
-			return (ssize_t)k;
-		}
-		if (st->tail_len == 0 && st->out_pos < st->out_len && st->delivered < st->limit) {
-			size_t k = st->out_len - st->out_pos;
-			if (k > st->limit - st->delivered)
-				k = (size_t)(st->limit - st->delivered);
-			*p = st->out.p + st->out_pos;
-			st->out_pos += k;
-			st->delivered += k;
-			return (ssize_t)k;
-		}
-		if (st->ended) {
-			st->finished = 1;
-			if (st->verdict.rc != ARCHIVE_OK)
-				return la_verdict_report(self, &st->verdict);
-			return 0;
-		}
-		/* what the window holds beyond `limit` (with the tail, at most 64 KiB) waits for the next window's verdict */
-		if (st->out_pos < st->out_len) {
-			const size_t k = st->out_len - st->out_pos;
-			if (st->tail_len + k > BZ_OUT_BLOCK) {
-				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "bzip2 filter: held-back bytes exceed one block");
-				st->finished = 1;
-				return ARCHIVE_FATAL;
-			}
-			memcpy(st->tail + st->tail_len, st->out.p + st->out_pos, k);
-			st->tail_len += k;
-			st->out_pos = st->out_len;
-		}
-		const int r = bz_window(self, st);
-		if (r != ARCHIVE_OK) {
-			st->finished = 1;
-			return r;
-		}
-	}
+	return la_holdback_read(self, &st->w, &st->hb, p, bz_window);
 }
 
 static int bzip2_filter_close(struct archive_read_filter *self)
@@ -374,11 +296,10 @@ static int bzip2_filter_close(struct archive_read_filter *self)
 	la_buf_release(gpu, &st->d_src);
 	la_buf_release(gpu, &st->d_dst);
 	la_buf_release(gpu, &st->d_tabs);
-	la_buf_release(gpu, &st->out);
+	la_holdback_release(gpu, &st->hb);
 	la_buf_release(gpu, &st->stage);
 	la_gpu_close(gpu);
 	free(st->res);
-	free(st->tail);
 	free(st);
 	self->data = NULL;
 	return ARCHIVE_OK;

@@ -28,16 +28,15 @@
  * it takes the end marker, padding, check, the next header, the index -- but it does not decode another LZMA symbol.
  * With T the bytes liblzma has emitted when it reports:
  *   - an error of the container or at a chunk boundary (every status but LA_ST_XZ_LZMA) arrives in the call that
- *     emitted byte T, so that byte's block is not handed out: 64 KiB * floor((T - 1) / 64 KiB) bytes are delivered;
+ *     emitted byte T, so that byte's block is not handed out (LA_HB_EARLY);
  *   - an error inside an LZMA chunk (LA_ST_XZ_LZMA), and LZMA_BUF_ERROR for input that ends inside a stream (the
  *     reference calls lzma_code twice more without input: "No progress is possible", not "truncated input"), arrive
- *     in a call of their own: 64 KiB * floor(T / 64 KiB) bytes are delivered;
- *   - a clean end (LZMA_STREAM_END at the end of input, the stream padding a multiple of four) delivers all T.
- * So at any time everything up to the last 64 KiB boundary strictly below T is safe to hand out; the filter holds the
- * rest (at most 64 KiB) back until it knows more, as la_filter_bzip2.c does.  (tests/xz_support.py restates the
- * reference's loop over the real liblzma; the rule above is what that emulator gives.  For T a multiple of 64 KiB the
- * first case assumes that upstream hands the reference the damaged bytes together with byte T's block, as a memory
- * reader does.)
+ *     in a call of their own, after a full block has been returned (LA_HB_LATE);
+ *   - a clean end (LZMA_STREAM_END at the end of input, the stream padding a multiple of four) hands out all T (LA_HB_ALL).
+ * What each kind lets out, and the holding back until the next window says which it is, is la_holdback's (la_host.h,
+ * la_bid_policy.c).  (tests/xz_support.py restates the reference's loop over the real liblzma; the rule above is what
+ * that emulator gives.  For T a multiple of 64 KiB the first case assumes that upstream hands the reference the damaged
+ * bytes together with byte T's block, as a memory reader does.)
  */
 #include "la_read_private.h"
 #include "la_host.h"
@@ -47,7 +46,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define XZ_OUT_BLOCK  ((uint64_t)65536)	/* xz.c:474 */
 #define XZ_TAB_CAP    4096u		/* blocks one launch takes; a window with more is taken in parts */
 #define XZ_VLI_MAX    (~(uint64_t)0 >> 1)
 
@@ -69,13 +67,9 @@ struct xz_private {
 	la_window w;
 	la_buf stage; size_t stage_len;	/* pinned: the stream from the first byte of the next unit on */
 	la_buf d_src, d_dst, d_tabs;	/* d_tabs: block table, results */
-	la_buf out; size_t out_len, out_pos;	/* pinned: the decoded bytes of the current window */
 	la_xz_block *tab;		/* host copies of the tables (XZ_TAB_CAP entries) */
 	la_xz_result *res;
-	uint8_t *tail; size_t tail_len;	/* held-back bytes of earlier windows (at most 64 KiB) */
-	uint64_t total, delivered, limit;	/* T, bytes handed out, bytes that may be handed out */
-	la_verdict verdict; int ended;
-	int finished;
+	la_holdback hb;			/* the decoded bytes, T and the stream's end */
 	/* where the container stands at stage[0] */
 	int seq, first_stream;
 	uint32_t check_id;		/* of the stream header: the footer's has to be the same */
@@ -133,16 +127,18 @@ static int xz_reader_init(struct archive_read_filter *self)
 	self->code = ARCHIVE_FILTER_XZ;
 	self->name = "xz";
 	struct xz_private *st = calloc(1, sizeof(*st));
-	uint8_t *tail = malloc((size_t)XZ_OUT_BLOCK);
 	la_xz_block *tab = malloc(sizeof(la_xz_block) * XZ_TAB_CAP);
 	la_xz_result *res = malloc(sizeof(la_xz_result) * XZ_TAB_CAP);
-	if (st == NULL || tail == NULL || tab == NULL || res == NULL || la_window_open(self, &st->w, "xz") != ARCHIVE_OK) {
-		if (st == NULL || tail == NULL || tab == NULL || res == NULL)
+	const int no_mem = st == NULL || tab == NULL || res == NULL || la_holdback_open(&st->hb) < 0;
+	if (no_mem || la_window_open(self, &st->w, "xz") != ARCHIVE_OK) {
+		if (no_mem)
 			archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for xz decompression");	/* xz.c:482-483 */
-		free(st); free(tail); free(tab); free(res);
+		if (st)
+			la_holdback_release(NULL, &st->hb);
+		free(st); free(tab); free(res);
 		return ARCHIVE_FATAL;
 	}
-	st->tail = tail; st->tab = tab; st->res = res;
+	st->tab = tab; st->res = res;
 	st->seq = SEQ_HEADER;
 	st->first_stream = 1;
 	if (st->w.out_budget == 0 || st->w.out_budget > ((uint64_t)4095 << 20))
@@ -152,31 +148,15 @@ static int xz_reader_init(struct archive_read_filter *self)
 	return ARCHIVE_OK;
 }
 
-static int gpu_fail(struct archive_read_filter *self, struct xz_private *st, const char *what)
-{
-	st->finished = 1;
-	return la_window_fail(self, &st->w, what);
-}
-
-/* the stream ends here: rc and message are reported once `limit` bytes are out */
-static void xz_end(struct xz_private *st, int rc, const char *msg, uint64_t limit)
-{
-	if (msg)
-		la_verdict_set(&st->verdict, rc, "%s", msg);
-	else
-		la_verdict_set(&st->verdict, rc, NULL);
-	st->ended = 1;
-	st->limit = limit;
-}
-/* an error reported in the call that emitted byte T */
+/* the stream ends here, T being hb.total: an error reported in the call that emitted byte T ... */
 static void xz_end_early(struct xz_private *st, int e)
 {
-	xz_end(st, ARCHIVE_FATAL, xz_msg[e], st->total ? (st->total - 1) / XZ_OUT_BLOCK * XZ_OUT_BLOCK : 0);
+	la_holdback_end(&st->hb, ARCHIVE_FATAL, xz_msg[e], LA_HB_EARLY);
 }
-/* an error reported in a call of its own */
+/* ... or in a call of its own */
 static void xz_end_late(struct xz_private *st, int e)
 {
-	xz_end(st, ARCHIVE_FATAL, xz_msg[e], st->total / XZ_OUT_BLOCK * XZ_OUT_BLOCK);
+	la_holdback_end(&st->hb, ARCHIVE_FATAL, xz_msg[e], LA_HB_LATE);
 }
 
 /* vli.c, single-call mode: 0 and *pos advanced, or -1 (LZMA_DATA_ERROR: no byte left, a zero byte that is not the first,
@@ -337,17 +317,17 @@ static int xz_launch(struct archive_read_filter *self, struct xz_private *st, ui
 	la_gpu_ctx *gpu = st->w.gpu;
 	const size_t o_res = sizeof(la_xz_block) * XZ_TAB_CAP;
 	if (la_buf_dev(gpu, &st->d_tabs, o_res + sizeof(la_xz_result) * XZ_TAB_CAP) < 0 || la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0)
-		return gpu_fail(self, st, "la_gpu_malloc");
+		return la_window_fail(self, &st->w, "la_gpu_malloc");
 	la_xz_batch bt;
 	memset(&bt, 0, sizeof(bt));
 	bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
 	bt.d_blocks = (const la_xz_block *)st->d_tabs.p; bt.n = n;
 	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes;
 	bt.d_results = (la_xz_result *)(st->d_tabs.p + o_res);
-	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, st->tab, sizeof(la_xz_block) * n) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
-	if (la_gpu_xz_decode(gpu, &bt) != LA_OK) return gpu_fail(self, st, "la_gpu_xz_decode");
+	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, st->tab, sizeof(la_xz_block) * n) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
+	if (la_gpu_xz_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_xz_decode");
 	if (la_gpu_memcpy_d2h(gpu, st->res, bt.d_results, sizeof(la_xz_result) * n) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
 	return ARCHIVE_OK;
 }
 
@@ -373,39 +353,39 @@ static int xz_take_results(struct archive_read_filter *self, struct xz_private *
 		bytes = st->tab[i].dst_off + st->res[i].out_len;	/* (the table is packed: no gaps in front of a failure) */
 	}
 	if (bytes) {
-		if (la_buf_pinned(gpu, &st->out, st->out_len + (size_t)bytes + 64, st->out_len) < 0)
-			return gpu_fail(self, st, "la_gpu_malloc_host");
-		if (la_gpu_memcpy_d2h(gpu, st->out.p + st->out_len, st->d_dst.p, bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-			return gpu_fail(self, st, "la_gpu_memcpy_d2h");
+		if (la_buf_pinned(gpu, &st->hb.out, st->hb.out_len + (size_t)bytes + 64, st->hb.out_len) < 0)
+			return la_window_fail(self, &st->w, "la_gpu_malloc_host");
+		if (la_gpu_memcpy_d2h(gpu, st->hb.out.p + st->hb.out_len, st->d_dst.p, bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
+			return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
 	}
-	st->out_len += (size_t)bytes;
-	st->total += bytes;
+	st->hb.out_len += (size_t)bytes;
+	st->hb.total += bytes;
 	if (bad < n)
 		xz_block_failed(st, st->res[bad].status);
 	return ARCHIVE_OK;
 }
 
-/* One window: gather, upload, walk; updates T and limit, and says how the stream ends if this window shows it.
+/* One window: gather, upload, walk; updates T, and says how the stream ends if this window shows it.
  * ARCHIVE_OK, or a fatal code with the error set. */
-static int xz_window(struct archive_read_filter *self, struct xz_private *st)
+static int xz_window(struct archive_read_filter *self)
 {
+	struct xz_private *st = (struct xz_private *)self->data;
 	la_gpu_ctx *gpu = st->w.gpu;
 	int r = la_window_gather(self, &st->w, &st->stage, &st->stage_len);
 	if (r != ARCHIVE_OK)
 		return r;
-	st->out_len = st->out_pos = 0;
 	const uint8_t *src = st->stage.p;
 	const size_t len = st->stage_len;
 	const int eof = st->w.upstream_eof;
 	if (len) {
-		if (la_buf_dev(gpu, &st->d_src, len + 64) < 0) return gpu_fail(self, st, "la_gpu_malloc");
-		if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return gpu_fail(self, st, "la_gpu_memcpy_h2d");
+		if (la_buf_dev(gpu, &st->d_src, len + 64) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc");
+		if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
 	}
 	size_t pos = 0;		/* the first byte of the unit the walk stands at */
 	int more = 0;		/* that unit needs bytes the window does not hold */
 	uint32_t n = 0;		/* sized blocks collected for one launch */
 	uint64_t dst_bytes = 0;
-	while (!st->ended && !more) {
+	while (!st->hb.ended && !more) {
 		/* the block header at pos, when the walk stands at one and all of it is here: parsed once per turn */
 		xz_block_header bh;
 		size_t hsize = 0;
@@ -476,14 +456,12 @@ static int xz_window(struct archive_read_filter *self, struct xz_private *st)
 			if (bh.unsupported) {
 				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
 				    "xz GPU data plane: unsupported filter %s in a block's filter chain (only LZMA2 is decoded)", bh.unsupported);
-				st->finished = 1;
 				return ARCHIVE_FATAL;
 			}
 			if (too_large) {
 				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
 				    "xz block too large for the GPU data plane (more than %llu compressed or %llu decoded bytes; LA_GPU_MAX_BATCH_MIB, LA_GPU_OUT_BUDGET_MIB)",
 				    (unsigned long long)st->w.max_batch_bytes, (unsigned long long)st->w.out_budget);
-				st->finished = 1;
 				return ARCHIVE_FATAL;
 			}
 			/* a size is missing, or the block is not all here: alone, bounded by the window's end and by a budget that grows
@@ -513,7 +491,6 @@ static int xz_window(struct archive_read_filter *self, struct xz_private *st)
 					archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
 					    "xz block too large for the GPU data plane (more than %llu decoded bytes; LA_GPU_OUT_BUDGET_MIB)",
 					    (unsigned long long)st->w.out_budget);
-					st->finished = 1;
 					return ARCHIVE_FATAL;
 				}
 				st->solo_cap = cap * 2;
@@ -527,8 +504,7 @@ static int xz_window(struct archive_read_filter *self, struct xz_private *st)
 			if ((r = xz_take_results(self, st, 1)) != ARCHIVE_OK)
 				return r;
 			if (q.status == LA_ST_XZ_TRUNCATED) {
-				st->ended = 0;	/* (not a data error: the input ends inside the block) */
-				xz_end_late(st, XZ_E_BUF);
+				xz_end_late(st, XZ_E_BUF);	/* (replaces xz_take_results' data error: the input ends inside the block) */
 			} else if (q.status == LA_ST_OK) {
 				sums_append(&st->blocks, hsize + q.consumed + cs, q.out_len);
 				pos += hsize + (size_t)ceil4(q.consumed) + cs;
@@ -584,7 +560,7 @@ static int xz_window(struct archive_read_filter *self, struct xz_private *st)
 				if (st->pad_mod)
 					xz_end_early(st, XZ_E_DATA);
 				else
-					xz_end(st, ARCHIVE_OK, NULL, st->total);
+					la_holdback_end(&st->hb, ARCHIVE_OK, NULL, LA_HB_ALL);
 			} else {
 				more = 1;
 			}
@@ -593,72 +569,15 @@ static int xz_window(struct archive_read_filter *self, struct xz_private *st)
 		}
 	}
 	la_window_ramp(&st->w);
-	if (st->ended)
+	if (st->hb.ended)
 		return ARCHIVE_OK;
-	st->limit = st->total ? (st->total - 1) / XZ_OUT_BLOCK * XZ_OUT_BLOCK : 0;
-	if (pos == 0 && len >= st->w.batch_bytes) {
-		/* one unit larger than the window: widen it, as the other filters do */
-		if (len >= st->w.max_batch_bytes) {
-			archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-			    "xz block too large for the GPU data plane (more than %llu compressed bytes; LA_GPU_MAX_BATCH_MIB)",
-			    (unsigned long long)st->w.max_batch_bytes);
-			st->finished = 1;
-			return ARCHIVE_FATAL;
-		}
-		st->w.batch_bytes = len * 2 < st->w.max_batch_bytes ? len * 2 : st->w.max_batch_bytes;
-	}
-	memmove(st->stage.p, st->stage.p + pos, len - pos);
-	st->stage_len = len - pos;
-	return ARCHIVE_OK;
+	return la_window_carry(self, &st->w, &st->stage, &st->stage_len, pos, more, "block");
 }
 
 static ssize_t xz_filter_read(struct archive_read_filter *self, const void **p)
 {
 	struct xz_private *st = (struct xz_private *)self->data;
-	*p = NULL;
-	if (st->finished)
-		return 0;
-	for (;;) {
-		if (st->tail_len && st->delivered + st->tail_len <= st->limit) {
-			const size_t k = st->tail_len;
-			*p = st->tail;
-			st->tail_len = 0;
-			st->delivered += k;
-			return (ssize_t)k;
-		}
-		if (st->tail_len == 0 && st->out_pos < st->out_len && st->delivered < st->limit) {
-			size_t k = st->out_len - st->out_pos;
-			if (k > st->limit - st->delivered)
-				k = (size_t)(st->limit - st->delivered);
-			*p = st->out.p + st->out_pos;
-			st->out_pos += k;
-			st->delivered += k;
-			return (ssize_t)k;
-		}
-		if (st->ended) {
-			st->finished = 1;
-			if (st->verdict.rc != ARCHIVE_OK)
-				return la_verdict_report(self, &st->verdict);
-			return 0;
-		}
-		/* what the window holds beyond `limit` (with the tail, at most 64 KiB) waits for the next window's verdict */
-		if (st->out_pos < st->out_len) {
-			const size_t k = st->out_len - st->out_pos;
-			if (st->tail_len + k > XZ_OUT_BLOCK) {
-				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "xz filter: held-back bytes exceed one block");
-				st->finished = 1;
-				return ARCHIVE_FATAL;
-			}
-			memcpy(st->tail + st->tail_len, st->out.p + st->out_pos, k);
-			st->tail_len += k;
-			st->out_pos = st->out_len;
-		}
-		const int r = xz_window(self, st);
-		if (r != ARCHIVE_OK) {
-			st->finished = 1;
-			return r;
-		}
-	}
+	return la_holdback_read(self, &st->w, &st->hb, p, xz_window);
 }
 
 static int xz_filter_close(struct archive_read_filter *self)
@@ -671,12 +590,11 @@ static int xz_filter_close(struct archive_read_filter *self)
 	la_buf_release(gpu, &st->d_src);
 	la_buf_release(gpu, &st->d_dst);
 	la_buf_release(gpu, &st->d_tabs);
-	la_buf_release(gpu, &st->out);
+	la_holdback_release(gpu, &st->hb);
 	la_buf_release(gpu, &st->stage);
 	la_gpu_close(gpu);
 	free(st->tab);
 	free(st->res);
-	free(st->tail);
 	free(st);
 	self->data = NULL;
 	return ARCHIVE_OK;

@@ -85,6 +85,15 @@ def test_small_windows(gpu_ctx, monkeypatch):
         same_as_reference(img[:len(img) - 100000])
 
 
+def test_tail_over_several_windows(gpu_ctx, monkeypatch):
+    """windows of 1 MiB that decode 20 000 bytes each: the held-back tail takes the bytes of three windows before the
+    fourth crosses 64 KiB, and an error in the fourth drops all of them"""
+    monkeypatch.setenv("LA_GPU_BATCH_MIB", "1")
+    for name, img in XS.padded_streams().items():
+        data, _, msg = la_api.as_reference_tuple(same_as_reference(img))
+        assert (len(data), msg) == XS.PADDED_STREAMS_RESULT[name], name
+
+
 @pytest.mark.parametrize("part", range(CUT_PARTS))
 def test_cut_at_every_byte(gpu_ctx, part):
     img = XS.stream3000()

@@ -99,6 +99,16 @@ def test_small_windows(mock, monkeypatch):
         same_as_reference(XS.flip(img, (2 << 20) * 8 + 5))
 
 
+@pytest.mark.parametrize("read_size", [None, 1000])
+def test_tail_over_several_windows(mock, monkeypatch, read_size):
+    """windows of 1 MiB that decode 20 000 bytes each: the held-back tail takes the bytes of three windows before the
+    fourth crosses 64 KiB, and an error in the fourth drops all of them"""
+    monkeypatch.setenv("LA_GPU_BATCH_MIB", "1")
+    for name, img in XS.padded_streams().items():
+        data, _, msg = la_api.as_reference_tuple(same_as_reference(img, read_size))
+        assert (len(data), msg) == XS.PADDED_STREAMS_RESULT[name], name
+
+
 def test_a_block_larger_than_the_window_limit_is_refused_by_name(mock, monkeypatch):
     monkeypatch.setenv("LA_GPU_BATCH_MIB", "1")
     monkeypatch.setenv("LA_GPU_MAX_BATCH_MIB", "1")
@@ -166,19 +176,29 @@ def test_sanitizer_program(mock, tmp_path):
     images += [XS.wrap(raw) for raw, _ in XS.refusals().values()] + [XS.wrap(c[0], dict_byte=c[3]) for c in XS.beyond_cases().values()]
     img = XS.stream3000()
     images += [img[:cut] for cut in range(6, len(img), 5)] + [XS.flip(img, b) for b in XS.flip_cases()[::4]]
-    paths = []
-    for i, im in enumerate(images):
-        paths.append(os.path.join(out, "case%04d.xz" % i))
-        with open(paths[-1], "wb") as f:
-            f.write(im)
     env = dict(os.environ, LA_GPU_BID="all", ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")     # (the environment is otherwise the caller's)
-    for k in range(0, len(paths), 400):
-        run = subprocess.run([os.path.join(out, "xz_read_asan")] + paths[k:k + 400], capture_output=True, text=True, env=env, timeout=600)
-        assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
-        assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
-        lines = run.stdout.splitlines()
-        assert len(lines) == len(paths[k:k + 400])
-        for line, im in zip(lines, images[k:k + 400]):
-            data, rc, msg = XS.reference_cat(im)
-            assert line == ("%d %d %016x %s" % (rc, len(data), fnv1a(data), msg)), (line, len(im))
+
+    def run_over(images, tag, env):
+        paths = []
+        for i, im in enumerate(images):
+            paths.append(os.path.join(out, "%s%04d.xz" % (tag, i)))
+            with open(paths[-1], "wb") as f:
+                f.write(im)
+        for k in range(0, len(paths), 400):
+            run = subprocess.run([os.path.join(out, "xz_read_asan")] + paths[k:k + 400], capture_output=True, text=True, env=env, timeout=600)
+            assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
+            assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
+            lines = run.stdout.splitlines()
+            assert len(lines) == len(paths[k:k + 400])
+            for line, im in zip(lines, images[k:k + 400]):
+                data, rc, msg = XS.reference_cat(im)
+                assert line == ("%d %d %016x %s" % (rc, len(data), fnv1a(data), msg)), (line, len(im))
+        return lines
+
+    run_over(images, "case", env)
+    # the tail that takes several windows' bytes (test_tail_over_several_windows), in a run of its own with windows of 1 MiB
+    held = XS.padded_streams()
+    lines = run_over(list(held.values()), "held", dict(env, LA_GPU_BATCH_MIB="1"))
+    for name, line in zip(held, lines):
+        assert (int(line.split()[1]), line.split(" ", 3)[3]) == XS.PADDED_STREAMS_RESULT[name], (name, line)

@@ -230,6 +230,34 @@ def filter_shapes():
     return shapes
 
 
+@functools.lru_cache(maxsize=None)
+def padded_streams():
+    """name -> image, about 8.4 MB each: eight streams of one 20 000-byte block, 1 MiB of stream padding behind each.
+    Read with LA_GPU_BATCH_MIB=1 every window decodes one stream, so the filter's held-back tail grows over three
+    windows (20 000, 40 000, 60 000 bytes) before the fourth crosses 64 KiB.  PADDED_STREAMS_BYTES: what the reference
+    delivers of each."""
+    pad = bytes(1 << 20)
+    parts = [text(100 + i, 20000) for i in range(8)]
+    streams = [XB.stream([XB.block(XB.lzma2(p), p, XB.CHECK_CRC32)], XB.CHECK_CRC32) for p in parts]
+    start = lambda i: sum(len(s) + len(pad) for s in streams[:i])      # noqa: E731
+    clean = b"".join(s + pad for s in streams)
+    return {
+        "clean": clean,
+        "cut_in_the_seventh_stream": clean[:start(6) + 100],
+        "cut_in_the_fifth_padding": clean[:start(5) - 1000],
+        "padding_of_three_more_behind_five": clean[:start(5)] + bytes(3) + streams[5],
+        "sixth_stream_header_flip": flip(clean, (start(5) + 7) * 8 + 7),
+        "sixth_stream_data_flip": flip(clean, (start(5) + 200) * 8 + 4),
+        "fourth_stream_data_flip": flip(clean, (start(3) + 200) * 8 + 4),      # 60 000 held-back bytes of three windows are dropped
+    }
+
+
+PADDED_STREAMS_RESULT = {       # name -> (bytes delivered, message)
+    "clean": (160000, ""), "cut_in_the_seventh_stream": (65536, BUF_ERROR), "cut_in_the_fifth_padding": (100000, ""),
+    "padding_of_three_more_behind_five": (65536, DATA_ERROR), "sixth_stream_header_flip": (65536, DATA_ERROR),
+    "sixth_stream_data_flip": (65536, DATA_ERROR), "fourth_stream_data_flip": (0, DATA_ERROR)}
+
+
 FIXTURE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_fixtures", "xz")
 
 
