@@ -689,12 +689,30 @@ typedef struct la_xz_result {
 	uint64_t valid;		/* a failed block: the bytes in front of the failure that are valid (they are in d_dst) */
 } la_xz_result;
 
+/* Filter chains (still ABI version 3; no layout above changes).  la_xz_batch.reserved is a flag word: with
+ * LA_XZ_BATCH_CHAINS, d_blocks[n] is followed in the same device buffer by la_xz_chain chains[n], the filters that stand
+ * in front of LZMA2 in each block's chain, in chain order: delta (prop: the distance 1 .. 256) and the BCJ filters x86,
+ * PowerPC, IA-64, ARM, ARM-Thumb, SPARC (prop: start_offset).  csrc/la_xz_filters_dev.h states the transforms.  They are
+ * undone in reverse order over the block's out_len bytes (a failed block: over its valid bytes) between decode and
+ * verify, so the check is taken over the unfiltered bytes.  An entry with a count above LA_XZ_CHAIN_MAX, an id outside
+ * 0x03 .. 0x09 or a start_offset the filter's alignment does not divide is LA_ST_XZ_SIZE for its block.  Any other
+ * non-zero flag word is LA_ERR_ARG.  The filters' scratch (16 bytes per block, 256 per 16 KiB of dst_cap) is reserved
+ * in the context's workspace by the call itself, beside la_gpu_xz_workspace_bytes(n). */
+#define LA_XZ_BATCH_CHAINS 1u
+#define LA_XZ_CHAIN_MAX 3u
+typedef struct la_xz_chain {
+	uint32_t count;			/* 0 .. LA_XZ_CHAIN_MAX filters in front of LZMA2 */
+	uint32_t id[LA_XZ_CHAIN_MAX];
+	uint32_t prop[LA_XZ_CHAIN_MAX];
+	uint32_t reserved;
+} la_xz_chain;
+
 typedef struct la_xz_batch {
 	const uint8_t     *d_src;
 	uint64_t           src_bytes;
 	const la_xz_block *d_blocks;	/* device-resident */
 	uint32_t           n;
-	uint32_t           reserved;
+	uint32_t           reserved;	/* 0, or LA_XZ_BATCH_CHAINS */
 	uint8_t           *d_dst;
 	uint64_t           dst_cap;	/* every block's [dst_off, dst_off + dst_cap) lies inside it */
 	la_xz_result      *d_results;	/* [n] */

@@ -116,6 +116,8 @@ LA_ST_BZ2_DATA, LA_ST_BZ2_TRUNCATED, LA_ST_BZ2_BAD_CRC, LA_ST_BZ2_REFUTED, LA_ST
 XZ_BLOCK_DTYPE = np.dtype([("src_off", "<u8"), ("comp_size", "<u8"), ("uncomp_size", "<u8"), ("dst_off", "<u8"), ("dst_cap", "<u8"),
                            ("check_off", "<u8"), ("dict_size", "<u4"), ("check_id", "<u4")])
 XZ_RESULT_DTYPE = np.dtype([("status", "<u4"), ("reserved", "<u4"), ("out_len", "<u8"), ("consumed", "<u8"), ("valid", "<u8")])
+XZ_CHAIN_DTYPE = np.dtype([("count", "<u4"), ("id", "<u4", (3,)), ("prop", "<u4", (3,)), ("reserved", "<u4")])     # la_xz_chain
+LA_XZ_BATCH_CHAINS = 1          # la_xz_batch.reserved: d_blocks[n] is followed by la_xz_chain chains[n]
 LA_XZ_UNKNOWN = 0xFFFFFFFFFFFFFFFF
 (LA_ST_XZ_DATA, LA_ST_XZ_LZMA, LA_ST_XZ_TRUNCATED, LA_ST_XZ_SIZE, LA_ST_XZ_BAD_CHECK, LA_ST_XZ_PADDING,
  LA_ST_XZ_OUT_FULL) = 25, 26, 27, 28, 29, 30, 31

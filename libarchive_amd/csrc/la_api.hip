@@ -548,11 +548,14 @@ uint64_t la_gpu_xz_workspace_bytes(uint32_t n)
 
 int la_gpu_xz_decode(la_gpu_ctx *c, const la_xz_batch *bt)
 {
-	if (!c || !bt || bt->reserved)
+	if (!c || !bt || (bt->reserved & ~LA_XZ_BATCH_CHAINS))
 		return LA_ERR_ARG;
 	if (bt->n && (!bt->d_blocks || !bt->d_results || !bt->d_dst || (bt->src_bytes && !bt->d_src)))
 		return LA_ERR_ARG;
-	const uint64_t need = la_xz_workspace_bytes(bt->n);
+	const bool chains = (bt->reserved & LA_XZ_BATCH_CHAINS) != 0u;
+	/* the filters' scratch (it grows with dst_cap) lies behind the decoder's */
+	const uint64_t o_filters = (la_xz_workspace_bytes(bt->n) + 255u) & ~(uint64_t)255u;
+	const uint64_t need = o_filters + (chains ? la_xz_unfilter_ws_bytes(bt->n, bt->dst_cap) : 0u);
 	if (need > c->ws_bytes) {
 		int rc = la_gpu_reserve(c, need);
 		if (rc != LA_OK) return rc;
@@ -560,6 +563,8 @@ int la_gpu_xz_decode(la_gpu_ctx *c, const la_xz_batch *bt)
 	prof_begin(c);
 	uint8_t *ws = (uint8_t *)c->ws;
 	prof_range(c, "xz_decode", c->stream, [&] { la_launch_xz_decode(c->stream, bt, ws); });
+	if (chains)
+		prof_range(c, "xz_unfilter", c->stream, [&] { la_launch_xz_unfilter(c->stream, bt, ws, ws + o_filters); });
 	prof_range(c, "xz_verify", c->stream, [&] { la_launch_xz_verify(c->stream, bt, ws); });
 	HIPCHK(c, hipGetLastError());
 	return LA_OK;

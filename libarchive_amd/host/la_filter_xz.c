@@ -15,9 +15,19 @@
  * The index is checked as liblzma checks it, by a running comparison (count, sums of padded sizes, uncompressed sizes
  * and record lengths, and a hash chain over the pairs), not against a stored list.
  *
- * Departures from liblzma.  (1) Only a single LZMA2 filter is decoded: a block that lists delta or a BCJ filter (IDs
- * 0x03 .. 0x0B) ends the read with "xz GPU data plane: unsupported filter <name> in a block's filter chain"; liblzma
- * decodes such chains.  (2) A block has to fit a window: more than LA_GPU_MAX_BATCH_MIB (2048) compressed MiB, or more
+ * Departures from liblzma.  (1) By default only a single LZMA2 filter is decoded: a block that lists delta or a BCJ
+ * filter (IDs 0x03 .. 0x0B) ends the read with "xz GPU data plane: unsupported filter <name> in a block's filter chain";
+ * liblzma decodes such chains.  With LA_XZ_CHAINS=1 in the environment (read once in xz_reader_init; off by default
+ * because two tests pin the refusal -- making it the default is a follow-up that touches them) up to three of delta,
+ * x86, PowerPC, IA-64, ARM, ARM-Thumb and SPARC in front of LZMA2 are judged as liblzma judges them and undone on the
+ * device (csrc/la_xz_filters.hip, the chain table behind the block table, LA_XZ_BATCH_CHAINS); ARM64 (0x0A) and RISC-V
+ * (0x0B) stay refused by name either way.  With a BCJ filter in the chain, liblzma holds back the tail bytes its coder
+ * cannot decide yet (a branch may reach over them: up to 4 for x86, less than a unit otherwise), so at an error inside
+ * a block its T lies up to that much below the LZMA2 level's.  This filter takes the most that could be held off its
+ * own T (xz_chain_hold): where the error falls within those few bytes behind a multiple of 64 KiB, the bytes handed out
+ * are still a prefix of the plain data, with the reference's code and message, but may be one 64 KiB block fewer than
+ * the reference's; everywhere else they are the reference's.
+ * (2) A block has to fit a window: more than LA_GPU_MAX_BATCH_MIB (2048) compressed MiB, or more
  * than min(LA_GPU_OUT_BUDGET_MIB, 4095) decoded MiB (default 4095), is refused by name.  (3) Verdicts inside a block
  * are the device's (csrc/la_xz_dev.h), where liblzma's reading is pinned: dictionary sizes rounded up to 4096 and to a
  * multiple of 16, a non-zero first byte of a chunk's range-coder data refused.
@@ -41,6 +51,7 @@
 #include "la_read_private.h"
 #include "la_host.h"
 #include "../csrc/la_xz_dev.h"	/* la_xz_check_size: the rules header is plain C too */
+#include "../csrc/la_xz_filters_dev.h"	/* la_xz_filter_valid */
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -67,8 +78,10 @@ struct xz_private {
 	la_window w;
 	la_buf stage; size_t stage_len;	/* pinned: the stream from the first byte of the next unit on */
 	la_buf d_src, d_dst, d_tabs;	/* d_tabs: block table, results */
-	la_xz_block *tab;		/* host copies of the tables (XZ_TAB_CAP entries) */
+	la_xz_block *tab;		/* host copies of the tables (XZ_TAB_CAP entries; room for the chains of a launch behind its blocks) */
+	la_xz_chain *chains;		/* tab[i]'s delta / BCJ filters (LA_XZ_CHAINS=1; otherwise all empty) */
 	la_xz_result *res;
+	int chains_on;			/* LA_XZ_CHAINS=1: delta and BCJ filters in front of LZMA2 are run, not refused */
 	la_holdback hb;			/* the decoded bytes, T and the stream's end */
 	/* where the container stands at stage[0] */
 	int seq, first_stream;
@@ -127,18 +140,21 @@ static int xz_reader_init(struct archive_read_filter *self)
 	self->code = ARCHIVE_FILTER_XZ;
 	self->name = "xz";
 	struct xz_private *st = calloc(1, sizeof(*st));
-	la_xz_block *tab = malloc(sizeof(la_xz_block) * XZ_TAB_CAP);
+	la_xz_block *tab = malloc((sizeof(la_xz_block) + sizeof(la_xz_chain)) * XZ_TAB_CAP);
+	la_xz_chain *chains = calloc(XZ_TAB_CAP, sizeof(la_xz_chain));
 	la_xz_result *res = malloc(sizeof(la_xz_result) * XZ_TAB_CAP);
-	const int no_mem = st == NULL || tab == NULL || res == NULL || la_holdback_open(&st->hb) < 0;
+	const int no_mem = st == NULL || tab == NULL || chains == NULL || res == NULL || la_holdback_open(&st->hb) < 0;
 	if (no_mem || la_window_open(self, &st->w, "xz") != ARCHIVE_OK) {
 		if (no_mem)
 			archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for xz decompression");	/* xz.c:482-483 */
 		if (st)
 			la_holdback_release(NULL, &st->hb);
-		free(st); free(tab); free(res);
+		free(st); free(tab); free(chains); free(res);
 		return ARCHIVE_FATAL;
 	}
-	st->tab = tab; st->res = res;
+	st->tab = tab; st->chains = chains; st->res = res;
+	const char *v = getenv("LA_XZ_CHAINS");	/* read once, here */
+	st->chains_on = v != NULL && v[0] == '1';
 	st->seq = SEQ_HEADER;
 	st->first_stream = 1;
 	if (st->w.out_budget == 0 || st->w.out_budget > ((uint64_t)4095 << 20))
@@ -209,10 +225,14 @@ typedef struct xz_block_header {
 	uint64_t comp, uncomp;	/* LA_XZ_UNKNOWN when absent */
 	uint32_t dict_size;
 	const char *unsupported;	/* a filter this data plane does not run */
+	la_xz_chain chain;		/* the filters in front of LZMA2 (chains_on) */
 } xz_block_header;
 
-/* block_header_decoder.c over the whole header h[0, size): -1 or an XZ_E_* */
-static int xz_block_header_parse(const uint8_t *h, size_t size, uint32_t check_id, xz_block_header *bh)
+/* block_header_decoder.c over the whole header h[0, size), then what lzma_raw_decoder_init says about the chain:
+ * -1 or an XZ_E_*.  With chains_on, delta and the BCJ filters 0x04 .. 0x09 are taken into bh->chain, their properties
+ * judged as liblzma's decoders judge them (delta_decoder.c, simple_decoder.c: sizes in lzma_properties_decode, the
+ * offset's alignment and the chain's shape in the init, all LZMA_OPTIONS_ERROR); ARM64 and RISC-V stay unsupported. */
+static int xz_block_header_parse(const uint8_t *h, size_t size, uint32_t check_id, int chains_on, xz_block_header *bh)
 {
 	const size_t n = size - 4;
 	if ((uint32_t)la_crc32(0, h, n) != archive_le32dec(h + n))
@@ -223,6 +243,7 @@ static int xz_block_header_parse(const uint8_t *h, size_t size, uint32_t check_i
 	bh->comp = bh->uncomp = LA_XZ_UNKNOWN;
 	bh->unsupported = NULL;
 	bh->dict_size = 0;
+	memset(&bh->chain, 0, sizeof(bh->chain));
 	if (h[1] & 0x40) {
 		if (xz_vli(h, n, &pos, &bh->comp) != 0)
 			return XZ_E_DATA;
@@ -233,7 +254,7 @@ static int xz_block_header_parse(const uint8_t *h, size_t size, uint32_t check_i
 	if ((h[1] & 0x80) && xz_vli(h, n, &pos, &bh->uncomp) != 0)
 		return XZ_E_DATA;
 	const unsigned nf = (h[1] & 3u) + 1u;
-	int lzma2_last = 0, others = 0;
+	int lzma2_last = 0, others = 0, bad_offset = 0;
 	for (unsigned f = 0; f < nf; f++) {
 		uint64_t id, psize;
 		if (xz_vli(h, n, &pos, &id) != 0 || id >= ((uint64_t)1 << 62))
@@ -246,6 +267,23 @@ static int xz_block_header_parse(const uint8_t *h, size_t size, uint32_t check_i
 			bh->dict_size = h[pos] == 40 ? 0xFFFFFFFFu : (2u | (h[pos] & 1u)) << (h[pos] / 2 + 11);
 			lzma2_last = f == nf - 1;
 			others += f != nf - 1;
+		} else if (chains_on && id >= LA_XZF_DELTA && id <= LA_XZF_SPARC) {
+			uint32_t prop;
+			if (id == LA_XZF_DELTA) {
+				if (psize != 1)
+					return XZ_E_OPTIONS;
+				prop = (uint32_t)h[pos] + 1u;
+			} else {
+				if (psize != 0 && psize != 4)
+					return XZ_E_OPTIONS;
+				prop = psize ? archive_le32dec(h + pos) : 0u;
+			}
+			bad_offset |= !la_xz_filter_valid((uint32_t)id, prop);
+			if (f < LA_XZ_CHAIN_MAX) {	/* (a fourth one stands in LZMA2's place: refused below) */
+				bh->chain.id[f] = (uint32_t)id;
+				bh->chain.prop[f] = prop;
+				bh->chain.count = f + 1u;
+			}
 		} else if (xz_filter_name(id)) {
 			if (bh->unsupported == NULL)
 				bh->unsupported = xz_filter_name(id);
@@ -259,8 +297,8 @@ static int xz_block_header_parse(const uint8_t *h, size_t size, uint32_t check_i
 			return XZ_E_OPTIONS;
 	if (bh->unsupported)
 		return -1;
-	if (!lzma2_last || others)
-		return XZ_E_OPTIONS;	/* lzma_raw_decoder_init: the chain has to end in LZMA2 and hold it once */
+	if (!lzma2_last || others || bad_offset)
+		return XZ_E_OPTIONS;	/* lzma_raw_decoder_init: the chain has to end in LZMA2 and hold it once; a BCJ offset has to be aligned */
 	return -1;
 }
 
@@ -315,7 +353,11 @@ static int64_t xz_index_parse(struct xz_private *st, const uint8_t *p, size_t n)
 static int xz_launch(struct archive_read_filter *self, struct xz_private *st, uint32_t n, uint64_t dst_bytes)
 {
 	la_gpu_ctx *gpu = st->w.gpu;
-	const size_t o_res = sizeof(la_xz_block) * XZ_TAB_CAP;
+	const size_t o_res = (sizeof(la_xz_block) + sizeof(la_xz_chain)) * XZ_TAB_CAP;
+	size_t tab_bytes = sizeof(la_xz_block) * n;
+	int chained = 0;
+	for (uint32_t i = 0; i < n; i++)
+		chained |= st->chains[i].count != 0;
 	if (la_buf_dev(gpu, &st->d_tabs, o_res + sizeof(la_xz_result) * XZ_TAB_CAP) < 0 || la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0)
 		return la_window_fail(self, &st->w, "la_gpu_malloc");
 	la_xz_batch bt;
@@ -324,7 +366,12 @@ static int xz_launch(struct archive_read_filter *self, struct xz_private *st, ui
 	bt.d_blocks = (const la_xz_block *)st->d_tabs.p; bt.n = n;
 	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes;
 	bt.d_results = (la_xz_result *)(st->d_tabs.p + o_res);
-	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, st->tab, sizeof(la_xz_block) * n) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
+	if (chained) {	/* the chain table rides behind the blocks, and only then */
+		memcpy(st->tab + n, st->chains, sizeof(la_xz_chain) * n);
+		tab_bytes += sizeof(la_xz_chain) * n;
+		bt.reserved = LA_XZ_BATCH_CHAINS;
+	}
+	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, st->tab, tab_bytes) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
 	if (la_gpu_xz_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_xz_decode");
 	if (la_gpu_memcpy_d2h(gpu, st->res, bt.d_results, sizeof(la_xz_result) * n) != LA_OK || la_gpu_sync(gpu) != LA_OK)
 		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
@@ -340,6 +387,16 @@ static void xz_block_failed(struct xz_private *st, uint32_t status)
 		xz_end_early(st, XZ_E_DATA);
 }
 
+/* the most bytes at the end of unfinished data that the chain's BCJ filters leave undecided: less than a unit each,
+ * 4 for x86 (liblzma's simple coder holds them back until more data or the end of the LZMA2 data arrives) */
+static uint64_t xz_chain_hold(const la_xz_chain *ch)
+{
+	uint64_t hold = 0;
+	for (uint32_t k = 0; k < ch->count; k++)
+		hold += ch->id[k] == LA_XZF_X86 ? 4u : la_xz_unit_bytes(ch->id[k]) ? la_xz_unit_bytes(ch->id[k]) - 1u : 0u;
+	return hold;
+}
+
 /* Walk the results of tab[0, n) in stream order; the bytes of the blocks in front of the first failure, and the valid
  * bytes of that one, come back from the device. */
 static int xz_take_results(struct archive_read_filter *self, struct xz_private *st, uint32_t n)
@@ -351,6 +408,12 @@ static int xz_take_results(struct archive_read_filter *self, struct xz_private *
 		if (st->res[i].status != LA_ST_OK)
 			bad = i;
 		bytes = st->tab[i].dst_off + st->res[i].out_len;	/* (the table is packed: no gaps in front of a failure) */
+	}
+	if (bad < n && st->res[bad].status != LA_ST_XZ_BAD_CHECK && st->res[bad].status != LA_ST_XZ_PADDING) {
+		/* the data ends inside the block: a BCJ filter could not decide the last bytes (a branch may reach over the end),
+		 * and liblzma's coder keeps such bytes back; they do not count */
+		const uint64_t hold = xz_chain_hold(&st->chains[bad]);
+		bytes -= hold < st->res[bad].out_len ? hold : st->res[bad].out_len;
 	}
 	if (bytes) {
 		if (la_buf_pinned(gpu, &st->hb.out, st->hb.out_len + (size_t)bytes + 64, st->hb.out_len) < 0)
@@ -393,7 +456,7 @@ static int xz_window(struct archive_read_filter *self)
 		const uint32_t cs = la_xz_check_size(st->check_id);
 		memset(&bh, 0, sizeof(bh));
 		if (st->seq == SEQ_BLOCK && len - pos >= 1 && src[pos] != 0 && len - pos >= (hsize = ((size_t)src[pos] + 1) * 4))
-			hdr = xz_block_header_parse(src + pos, hsize, st->check_id, &bh);
+			hdr = xz_block_header_parse(src + pos, hsize, st->check_id, st->chains_on, &bh);
 		const int sound = hdr == -1 && !bh.unsupported;
 		const int too_large = sound && ((bh.comp != LA_XZ_UNKNOWN && bh.comp > st->w.max_batch_bytes) ||
 		    (bh.uncomp != LA_XZ_UNKNOWN && bh.uncomp > st->w.out_budget));
@@ -401,6 +464,7 @@ static int xz_window(struct archive_read_filter *self)
 		const int whole = sound && !too_large && bh.comp != LA_XZ_UNKNOWN && bh.uncomp != LA_XZ_UNKNOWN &&
 		    len - pos - hsize >= ceil4(bh.comp) + cs;
 		if (whole && n < XZ_TAB_CAP && !(n && dst_bytes + bh.uncomp > st->w.out_budget)) {
+			st->chains[n] = bh.chain;
 			la_xz_block *b = &st->tab[n++];
 			b->src_off = pos + hsize; b->comp_size = bh.comp; b->uncomp_size = bh.uncomp;
 			b->dst_off = dst_bytes; b->dst_cap = bh.uncomp;
@@ -479,6 +543,7 @@ static int xz_window(struct archive_read_filter *self)
 					st->solo_cap = st->w.out_budget;
 				cap = st->solo_cap;
 			}
+			st->chains[0] = bh.chain;
 			la_xz_block *b = &st->tab[0];
 			b->src_off = pos + hsize; b->comp_size = bh.comp; b->uncomp_size = bh.uncomp;
 			b->dst_off = 0; b->dst_cap = cap; b->check_off = LA_XZ_UNKNOWN;
@@ -594,6 +659,7 @@ static int xz_filter_close(struct archive_read_filter *self)
 	la_buf_release(gpu, &st->stage);
 	la_gpu_close(gpu);
 	free(st->tab);
+	free(st->chains);
 	free(st->res);
 	free(st);
 	self->data = NULL;

@@ -6,6 +6,7 @@ import numpy as np
 from . import _native as N
 
 XZ_BLOCK_DTYPE, XZ_RESULT_DTYPE, LA_XZ_UNKNOWN = N.XZ_BLOCK_DTYPE, N.XZ_RESULT_DTYPE, N.LA_XZ_UNKNOWN
+XZ_CHAIN_DTYPE, LA_XZ_BATCH_CHAINS = N.XZ_CHAIN_DTYPE, N.LA_XZ_BATCH_CHAINS
 LA_ST_XZ_DATA, LA_ST_XZ_LZMA, LA_ST_XZ_TRUNCATED, LA_ST_XZ_SIZE = N.LA_ST_XZ_DATA, N.LA_ST_XZ_LZMA, N.LA_ST_XZ_TRUNCATED, N.LA_ST_XZ_SIZE
 LA_ST_XZ_BAD_CHECK, LA_ST_XZ_PADDING, LA_ST_XZ_OUT_FULL = N.LA_ST_XZ_BAD_CHECK, N.LA_ST_XZ_PADDING, N.LA_ST_XZ_OUT_FULL
 LA_XZC_FIRST, LA_XZC_BLOCK_BYTES, LA_XZC_CHUNK_BYTES = N.LA_XZC_FIRST, N.LA_XZC_BLOCK_BYTES, N.LA_XZC_CHUNK_BYTES
@@ -49,24 +50,41 @@ def block_table(entries):
     return t
 
 
-class XzDevicePlan:
-    """One call: run() decodes the table; results() / output(i) read back."""
+def chain_table(chains):
+    """ndarray of XZ_CHAIN_DTYPE from one list per block of (filter id, property) pairs in chain order, LZMA2 left out:
+    the property is delta's distance (1 .. 256) or a BCJ filter's start_offset.  (Nothing is checked here: the device
+    call judges the entries.)"""
+    t = np.zeros(len(chains), dtype=XZ_CHAIN_DTYPE)
+    for i, ch in enumerate(chains):
+        t[i]["count"] = len(ch)
+        for k, (fid, prop) in enumerate(ch[:3]):
+            t[i]["id"][k], t[i]["prop"][k] = fid, prop
+    return t
 
-    def __init__(self, ctx, d_src, blocks, dst_cap=None):
+
+class XzDevicePlan:
+    """One call: run() decodes the table; results() / output(i) read back.  With `chains` (see chain_table) the chain
+    table rides behind the blocks and the call is made with LA_XZ_BATCH_CHAINS."""
+
+    def __init__(self, ctx, d_src, blocks, dst_cap=None, chains=None):
         import torch
         dev = d_src.device
         self.ctx, self.n, self.d_src, self.blocks = ctx, len(blocks), d_src, blocks
         if dst_cap is None:
             dst_cap = max([int(b["dst_off"] + b["dst_cap"]) for b in blocks], default=0)
         self.dst_cap = int(dst_cap)
-        self.d_blocks = torch.from_numpy(np.ascontiguousarray(blocks).view(np.uint8).reshape(-1).copy()).to(dev) if self.n else \
-            torch.zeros(16, dtype=torch.uint8, device=dev)
+        table = np.ascontiguousarray(blocks).view(np.uint8).reshape(-1)
+        if chains is not None:
+            assert len(chains) == self.n
+            table = np.concatenate([table, np.ascontiguousarray(chain_table(chains)).view(np.uint8).reshape(-1)])
+        self.d_blocks = torch.from_numpy(table.copy()).to(dev) if self.n else torch.zeros(16, dtype=torch.uint8, device=dev)
         self.d_results = torch.zeros(max(self.n, 1) * XZ_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.d_dst = torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
         b = N._XzBatchC()
         b.d_src, b.src_bytes = (d_src.data_ptr() if d_src.numel() else None), d_src.numel()
         b.d_blocks, b.n = self.d_blocks.data_ptr(), self.n
         b.d_dst, b.dst_cap, b.d_results = self.d_dst.data_ptr(), self.dst_cap, self.d_results.data_ptr()
+        b.reserved = LA_XZ_BATCH_CHAINS if chains is not None else 0
         self.batch = b
 
     def run(self):
@@ -85,10 +103,11 @@ class XzDevicePlan:
         return self.d_dst[off:off + n].cpu().numpy().tobytes()
 
 
-def decode_blocks(ctx, image, entries):
-    """Upload a host image, decode the blocks `entries` describe (see block_table).  Returns (results, plan)."""
+def decode_blocks(ctx, image, entries, chains=None):
+    """Upload a host image, decode the blocks `entries` describe (see block_table), with `chains` (see chain_table)
+    their delta / BCJ filters undone.  Returns (results, plan)."""
     import torch
     buf = np.frombuffer(bytes(image), dtype=np.uint8)
     d_src = torch.from_numpy(buf.copy()).cuda() if buf.size else torch.zeros(0, dtype=torch.uint8, device="cuda")
-    plan = XzDevicePlan(ctx, d_src, block_table(entries)).run()
+    plan = XzDevicePlan(ctx, d_src, block_table(entries), chains=chains).run()
     return plan.results(), plan
