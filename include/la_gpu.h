@@ -313,6 +313,29 @@ typedef struct la_gz_batch {
 					 * [dst_off[0] - hist_len, dst_off[0] + dst_cap) and the workspace is touched, whatever the claims.
 					 *   Workspace: 4 bytes per byte of batch.dst_cap and about 40 bytes per piece (la_gpu_reserve). */
 
+#define LA_GZ_OPT_BLOCK_STARTS 256u	/* with LA_GZ_OPT_PIECES | LA_GZ_OPT_CHAIN and n_members == 1 only (else LA_ERR_ARG, as are the chain's
+					 * own refusals and src_bytes >= 2^29: bit offsets are 32-bit words): d_members[0] is the span from a
+					 * TRUE block boundary of one raw-deflate stream to the end of the window, and the boundary lies at
+					 * bit LA_GZ_OPT_START_BIT(options) of the span's first byte.  The device finds the candidate starts
+					 * of non-final dynamic blocks behind it, decodes a piece from every one of them, confirms in stream
+					 * order those a confirmed piece ended on exactly, and decodes the confirmed pieces as a chain:
+					 * hist_len, the packed output from d_members[0].dst_off and batch.dst_cap are the chain's.
+					 *   d_results has THREE entries.  [0]: status of the chain -- LA_ST_OK (the final block ended),
+					 * LA_ST_GZ_PIECE_END (a non-final block ended on the last bit of the span), LA_ST_GZ_OUT_FULL (the
+					 * next piece does not fit: out_len and consumed stand in front of it), or what the last piece earned
+					 * (LA_ST_GZ_TRUNCATED, LA_ST_GZ_DATA); out_len: the packed bytes, those of the last piece in front
+					 * of its error included; consumed: in BITS from the span's first byte, the bit behind the last block
+					 * that ended (for an error: where the decoder's bit buffer stood); crc32: of the out_len bytes.
+					 * [1]: out_len = candidates found, consumed = pieces confirmed (the first piece included).
+					 * [2]: the chain as far as it stands on a block boundary, for a caller with more input behind the
+					 * span: [0] itself when that is LA_ST_OK, LA_ST_GZ_PIECE_END or LA_ST_GZ_OUT_FULL; else the chain
+					 * without its last piece -- LA_ST_GZ_PIECE_END, out_len and crc32 of the pieces in front of it,
+					 * consumed = the bit that piece starts at (the next call's first byte and start bit).
+					 *   Workspace (la_gpu_reserve), from src_bytes and dst_cap alone: 4 B per byte of dst_cap and about
+					 * 2 B per byte of src_bytes. */
+#define LA_GZ_OPT_START_BIT_SHIFT 16
+#define LA_GZ_OPT_START_BIT(options) (((options) >> LA_GZ_OPT_START_BIT_SHIFT) & 7u)
+
 int la_gpu_gzip_decode(la_gpu_ctx *ctx, const la_gz_batch *batch);
 
 /* =====================================================================

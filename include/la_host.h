@@ -158,6 +158,9 @@ int      la_gz_flush_points_enabled(void);
 int      la_zstd_blocks_enabled(void);	/* LA_ZSTD_BLOCKS=1: one zstd frame decodes block-parallel (LA_ZSTD_OPT_BLOCK_PARALLEL) */
 /* LA_GZIP_FLUSH_POINTS=chain: the pieces may depend on each other, the filter decodes them with LA_GZ_OPT_CHAIN */
 int      la_gz_flush_points_chain(void);
+/* LA_GZIP_BLOCK_STARTS=1: a member without flush points is decoded from the block starts the device finds
+ * (LA_GZ_OPT_BLOCK_STARTS); the bid policy then takes a lone member */
+int      la_gz_block_starts_enabled(void);
 
 /* ---- zstd (host/la_zstd_index.c) ---- */
 typedef struct la_zstd_index_result {

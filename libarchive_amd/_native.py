@@ -39,6 +39,8 @@ LA_ST_GZ_PIECE_END, LA_ST_GZ_NEEDS_HISTORY = 18, 19     # LA_GZ_OPT_PIECES only
 (LA_GZ_OPT_NO_VERIFY, LA_GZ_OPT_WAVE_KERNEL, LA_GZ_OPT_LANE_KERNEL, LA_GZ_OPT_TWO_PHASE, LA_GZ_OPT_RAW,
  LA_GZ_OPT_EXPAND_INORDER, LA_GZ_OPT_PIECES) = 1, 2, 4, 8, 16, 32, 64
 LA_GZ_OPT_CHAIN = 128      # with LA_GZ_OPT_PIECES: the pieces depend on each other, output is packed
+LA_GZ_OPT_BLOCK_STARTS = 256        # with PIECES | CHAIN and one span: the device finds the block starts itself
+LA_GZ_OPT_START_BIT_SHIFT = 16      # the span's first bit, 0..7, in bits 16..18 of the options
 
 (LA_END_EOF, LA_END_TRUNCATED, LA_END_MALFORMED, LA_END_MALFORMED_SKIP, LA_END_EMPTY_FRAME,
  LA_END_NEED_MORE, LA_END_GZ_NO_TRAILER, LA_END_GZ_TOO_LARGE) = range(8)

@@ -649,12 +649,101 @@ static int gzip_decode_chain(la_gpu_ctx *c, const la_gz_batch *bt)
 	return LA_OK;
 }
 
+/* workspace of LA_GZ_OPT_BLOCK_STARTS, a function of src_bytes and dst_cap only: the chain's 4 B of source pointer per byte
+ * of capacity; one bit per bit of the source (the quick test's masks); 12 B per tile of LA_FIND_TILE_BYTES; at most
+ * src_bytes / 32 + 1024 survivors of 16 B; at most src_bytes / 128 + 64 candidates of 56 B */
+struct gz_blocks_ws {
+	la_gz_find_ws f;
+	uint32_t *ptr, *chain_ctl;
+	uint64_t *packed_off;
+};
+static uint64_t gz_blocks_carve(uint8_t *base, uint64_t src_bytes, uint64_t dst_cap, gz_blocks_ws *w)
+{
+	la_carve cv = { base, 0 };
+	la_gz_find_ws &f = w->f;
+	f.tiles = (uint32_t)((src_bytes + LA_FIND_TILE_BYTES - 1) / LA_FIND_TILE_BYTES);
+	if (f.tiles == 0) f.tiles = 1;
+	f.max_surv = (uint32_t)(src_bytes / 32) + 1024u;
+	f.max_cand = (uint32_t)(src_bytes / 128) + 64u;
+	const uint32_t scan_n = f.max_surv > f.tiles ? f.max_surv : f.tiles;	/* (and above max_cand) */
+	f.ctl = cv.take<uint32_t>(LA_FIND_CTL_WORDS, 256);
+	w->chain_ctl = cv.take<uint32_t>(LA_CHAIN_CTL_WORDS, 256);
+	w->ptr = cv.take<uint32_t>(dst_cap, 256);
+	f.mask = cv.take<uint32_t>((uint64_t)f.tiles * (LA_FIND_TILE_BYTES / 4), 256);
+	f.tile_cnt = cv.take<uint32_t>(f.tiles, 256);
+	f.tile_off = cv.take<uint64_t>((uint64_t)f.tiles + 1, 256);
+	f.surv = cv.take<uint32_t>(f.max_surv, 256);
+	f.flag = cv.take<uint32_t>(f.max_surv, 256);
+	f.flag_off = cv.take<uint64_t>((uint64_t)f.max_surv + 1, 256);
+	f.cand = cv.take<uint32_t>(f.max_cand, 256);
+	f.res_all = cv.take<la_gz_result>(f.max_cand, 256);
+	f.startc = cv.take<uint32_t>((uint64_t)f.max_cand + 1, 256);
+	f.resc = cv.take<la_gz_result>(f.max_cand, 256);
+	f.lenc = cv.take<uint32_t>(f.max_cand, 256);
+	f.crc = cv.take<uint32_t>(f.max_cand, 256);
+	w->packed_off = cv.take<uint64_t>((uint64_t)f.max_cand + 1, 256);
+	f.scan = cv.take<uint8_t>(la_scan_scratch_bytes(scan_n), 256);
+	return align_up(cv.off, 256);
+}
+
+/* LA_GZ_OPT_BLOCK_STARTS: find, measure every candidate, walk (la_inflate_find.hip), then the chain path over the
+ * confirmed pieces and the two results (la_hash.hip) */
+static int gzip_decode_block_starts(la_gpu_ctx *c, const la_gz_batch *bt)
+{
+	hipStream_t s = c->stream;
+	const uint32_t start_bit = (bt->options >> LA_GZ_OPT_START_BIT_SHIFT) & 7u;
+	gz_blocks_ws w;
+	const uint64_t need = gz_blocks_carve(NULL, bt->src_bytes, bt->dst_cap, &w);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	gz_blocks_carve((uint8_t *)c->ws, bt->src_bytes, bt->dst_cap, &w);
+	const la_gz_find_ws &f = w.f;
+	const la_inflate_chain all = { w.packed_off, w.ptr, bt->hist_len, f.cand, f.ctl + LA_FIND_N_CAND, f.ctl + LA_FIND_N_CAND };
+	const la_inflate_chain confirmed = { w.packed_off, w.ptr, bt->hist_len, f.startc, f.ctl + LA_FIND_N_CONF, f.ctl + LA_FIND_N_TABLE };
+	prof_begin(c);
+	prof_range(c, "blocks_find", s, [&] {
+		la_launch_gz_find(s, bt->d_src, bt->src_bytes, bt->d_members, start_bit, f);
+	});
+	prof_range(c, "blocks_measure", s, [&] {
+		la_launch_inflate_chain_bits(s, bt->d_src, bt->src_bytes, bt->d_members, f.max_cand, bt->d_dst, bt->dst_cap, f.res_all, all, false);
+	});
+	prof_range(c, "blocks_walk", s, [&] {
+		la_launch_gz_walk(s, bt->dst_cap, f);
+		la_launch_scan_u32(s, f.lenc, f.max_cand, w.packed_off, f.scan);
+	});
+	prof_range(c, "chain_emit", s, [&] {
+		la_launch_inflate_chain_bits(s, bt->d_src, bt->src_bytes, bt->d_members, f.max_cand, bt->d_dst, bt->dst_cap, f.resc, confirmed, true);
+	});
+	prof_range(c, "chain_resolve", s, [&] {
+		la_launch_chain_resolve_dev(s, bt->d_dst, &bt->d_members->dst_off, w.ptr, bt->hist_len, w.packed_off + f.max_cand, bt->dst_cap,
+		    w.chain_ctl);
+	});
+	prof_range(c, "gz_crc32", s, [&] {
+		la_launch_gz_blocks_summary(s, bt->d_dst, bt->d_members, w.packed_off, start_bit, f, bt->d_results);
+	});
+	if (bt->d_summary)
+		la_launch_gz_summary(s, bt->d_results, 1, bt->d_summary);
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
 {
 	if (!c || !bt)
 		return LA_ERR_ARG;
 	if (bt->n_members && (!bt->d_src || !bt->d_members || !bt->d_dst || !bt->d_results))
 		return LA_ERR_ARG;
+	if (bt->options & LA_GZ_OPT_BLOCK_STARTS) {
+		/* one span of one stream, decoded as a chain; bit offsets into the source are 32-bit words */
+		if ((bt->options & (LA_GZ_OPT_PIECES | LA_GZ_OPT_CHAIN)) != (LA_GZ_OPT_PIECES | LA_GZ_OPT_CHAIN) ||
+		    (bt->options & (LA_GZ_OPT_LANE_KERNEL | LA_GZ_OPT_TWO_PHASE | LA_GZ_OPT_EXPAND_INORDER)) ||
+		    bt->n_members != 1 || bt->src_bytes >= (1ull << 29) ||
+		    bt->hist_len > 32768u || bt->dst_cap + bt->hist_len > 0xFFFFFFFFull)
+			return LA_ERR_ARG;
+		return gzip_decode_block_starts(c, bt);
+	}
 	if (bt->options & LA_GZ_OPT_CHAIN) {
 		/* pieces only, the wave kernel only; coordinates of history + range are 32-bit words */
 		if (!(bt->options & LA_GZ_OPT_PIECES) ||

@@ -100,6 +100,21 @@ __device__ __forceinline__ bool dfl_piece_end(int64_t unread_bits)
 {
 	return PIECES && unread_bits == 0;
 }
+/* The end-of-piece rule of a piece that starts at a BIT (LA_GZ_OPT_BLOCK_STARTS; a third template parameter of the wave
+ * kernel), tested at the same place as dfl_piece_end and beside it.  starts[0 .. n) are bit offsets from the span's first
+ * byte, ascending: the candidate block starts (la_deflate_find_dev.h), or the confirmed ones.  cursor is the bit the next
+ * block header would be read from.  The piece is over when a start behind its own lies exactly on the cursor; idx walks up
+ * the table as the cursor advances (it begins one above the piece's own entry), so a start the piece passed in mid-block
+ * is stepped over and never looked at again. */
+template <bool BITS>
+__device__ __forceinline__ bool dfl_piece_end_at(uint32_t cursor, const uint32_t *starts, uint32_t n, uint32_t &idx)
+{
+	if (!BITS)
+		return false;
+	while (idx < n && starts[idx] < cursor)
+		idx++;
+	return idx < n && starts[idx] == cursor;
+}
 /* the verdict on a match distance above the bytes produced so far */
 template <bool PIECES>
 __device__ __forceinline__ uint32_t dfl_far_back() { return PIECES ? LA_ST_GZ_NEEDS_HISTORY : LA_ST_GZ_DATA; }

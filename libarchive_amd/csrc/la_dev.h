@@ -616,9 +616,48 @@ struct la_inflate_chain {
 	const uint64_t *packed_off;	/* [n + 1] exclusive scan of the measured out_len */
 	uint32_t *ptr;			/* one source pointer per packed output byte */
 	uint32_t hist_len;
+	/* LA_GZ_OPT_BLOCK_STARTS only (la_launch_inflate_chain_bits; the other instances do not read them): piece i starts
+	 * at bit starts[i] of the span d_members[0]; *n_starts pieces, a number only the device knows */
+	const uint32_t *starts;
+	const uint32_t *n_starts;
+	const uint32_t *n_table;	/* entries of starts[], *n_starts or one more: where a piece that is not decoded starts */
 };
 void la_launch_inflate_chain(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_gz_member *d_members,
     uint32_t n, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, const la_inflate_chain &C, bool emit);
+/* the same two instances for pieces that start at a bit: d_members is ONE span, n_max bounds *C.n_starts (the grid);
+ * results: consumed is the BIT the piece ended on, counted from the span's first byte, and the measure instance leaves
+ * in crc32 the index of the start a LA_ST_GZ_PIECE_END piece ended on (0xFFFFFFFF: on the end of the span) */
+void la_launch_inflate_chain_bits(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_gz_member *d_span,
+    uint32_t n_max, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, const la_inflate_chain &C, bool emit);
+/* la_inflate_find.hip (LA_GZ_OPT_BLOCK_STARTS): the candidate table, the confirming walk, the summary */
+struct la_gz_find_ws {
+	uint32_t *ctl;		/* LA_FIND_* words */
+	uint32_t *mask;		/* one bit per bit position: passed dfl_find_quick */
+	uint32_t *tile_cnt;	/* survivors per tile */
+	uint64_t *tile_off;	/* [tiles + 1] */
+	uint32_t *surv;		/* [max_surv] survivor bit offsets, ascending */
+	uint32_t *flag;		/* [max_surv] 1: the survivor passed the full rule */
+	uint64_t *flag_off;	/* [max_surv + 1] */
+	uint32_t *cand;		/* [max_cand] cand[0] = the caller's start bit, then the candidates behind it, ascending */
+	la_gz_result *res_all;	/* [max_cand] measured, per candidate */
+	uint32_t *startc;	/* [max_cand + 1] confirmed starts, and behind them the start of the piece that did not fit */
+	la_gz_result *resc;	/* [max_cand] results of the confirmed pieces (measure, then emit) */
+	uint32_t *lenc;		/* [max_cand] their measured lengths, 0 behind the last */
+	uint32_t *crc;		/* [max_cand] CRC32 of each confirmed piece's packed bytes */
+	void *scan;
+	uint32_t tiles, max_surv, max_cand;
+};
+enum { LA_FIND_N_SURV = 0, LA_FIND_N_CAND = 1, LA_FIND_N_CONF = 2, LA_FIND_STOP = 3, LA_FIND_STOP_BIT = 4, LA_FIND_N_TABLE = 5, LA_FIND_CTL_WORDS = 64 };
+#define LA_FIND_TILE_BYTES 1024u
+void la_launch_gz_find(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_gz_member *d_span, uint32_t start_bit,
+    const la_gz_find_ws &W);
+void la_launch_gz_walk(hipStream_t s, uint64_t dst_cap, const la_gz_find_ws &W);
+/* la_hash.hip: CRC32 of every confirmed piece, then results[0] / results[1] of the call */
+void la_launch_gz_blocks_summary(hipStream_t s, const uint8_t *d_dst, const la_gz_member *d_span, const uint64_t *d_packed_off,
+    uint32_t start_bit, const la_gz_find_ws &W, la_gz_result *d_results);
+/* la_inflate_chain.hip: the jump passes and the gather over a range whose length is *d_total (at most dst_cap) */
+void la_launch_chain_resolve_dev(hipStream_t s, uint8_t *d_dst, const uint64_t *d_first_off, uint32_t *d_ptr, uint32_t hist_len,
+    const uint64_t *d_total, uint64_t dst_cap, uint32_t *d_ctl);
 /* la_inflate_chain.hip: between the two instances (measured lengths as the scan's input), and behind them (packed
  * member table for the CRC32 launch, the pointer-jumping passes, the gather) */
 #define LA_CHAIN_JUMP_PASSES 32u

@@ -491,6 +491,110 @@ void la_launch_gz_verify(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes
 	    d_dst, d_results, verify);
 }
 
+/* ------------------------------------------------------------------ LA_GZ_OPT_BLOCK_STARTS: the two results */
+
+/* one wave per confirmed piece: the CRC32 of its packed bytes as the emit pass left them (whatever its status: the last
+ * piece of a chain may be truncated or refused, and its bytes in front of that are delivered) */
+__global__ __launch_bounds__(256) void gz_blocks_crc_kernel(const uint8_t *__restrict__ dst, const la_gz_member *__restrict__ span,
+    const uint64_t *__restrict__ packed_off, const la_gz_find_ws W)
+{
+	__shared__ uint32_t T[4 * 256];
+	crc_build_tables(T);
+	const int lane = threadIdx.x & 63;
+	const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+	const uint32_t n = W.ctl[LA_FIND_N_CONF];
+	for (uint32_t i = wave; i < n; i += nwaves) {
+		const uint32_t c = crc32_wave(T, dst + span[0].dst_off + packed_off[i], W.resc[i].out_len, 0, lane);
+		if (lane == 0)
+			W.crc[i] = c;
+	}
+}
+
+/* One workgroup.  The chain is the confirmed pieces up to and with the first that is not LA_ST_GZ_PIECE_END after the emit
+ * pass (which alone judges distances); its status is the chain's.  When every piece is, the chain stopped in front of a
+ * piece that did not fit (LA_FIND_STOP) or on the end of the span.  CRC32 over pieces A B C is
+ * crc(A) x^(8 (|B| + |C|)) + crc(B) x^(8 |C|) + crc(C): one term per lane, no order. */
+__global__ __launch_bounds__(256) void gz_blocks_fold_kernel(const uint64_t *__restrict__ packed_off, uint32_t start_bit,
+    const la_gz_find_ws W, la_gz_result *results)
+{
+	__shared__ uint32_t first_bad, crc, crc_b;
+	const uint32_t n = W.ctl[LA_FIND_N_CONF];
+	if (threadIdx.x == 0) {
+		first_bad = n;
+		crc = crc_b = 0;
+	}
+	__syncthreads();
+	uint32_t fb = n;
+	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x)
+		if (W.resc[i].status != LA_ST_GZ_PIECE_END && i < fb)
+			fb = i;
+	if (fb < n)
+		atomicMin(&first_bad, fb);
+	__syncthreads();
+	const uint32_t bad = first_bad;
+	la_gz_result r;
+	uint32_t pieces;
+	if (bad < n) {
+		r.status = W.resc[bad].status;
+		r.out_len = (uint32_t)packed_off[bad] + W.resc[bad].out_len;
+		r.consumed = W.resc[bad].consumed;
+		pieces = bad + 1;
+	} else {
+		const uint32_t stop = W.ctl[LA_FIND_STOP];
+		r.status = stop ? stop : LA_ST_GZ_PIECE_END;
+		r.out_len = (uint32_t)packed_off[n];
+		r.consumed = stop ? W.ctl[LA_FIND_STOP_BIT] : n ? W.resc[n - 1].consumed : start_bit;
+		pieces = n;
+	}
+	/* results[2]: the chain as far as it stands on a block boundary -- all of it, or all but a last piece that ran into
+	 * the end of the span or an error: where a caller with more input behind the span goes on from */
+	const bool whole = r.status == LA_ST_OK || r.status == LA_ST_GZ_PIECE_END || r.status == LA_ST_GZ_OUT_FULL;
+	la_gz_result b = r;
+	if (!whole) {
+		b.status = LA_ST_GZ_PIECE_END;
+		b.out_len = (uint32_t)packed_off[pieces - 1];
+		b.consumed = W.startc[pieces - 1];
+	}
+	uint32_t x = 0, xb = 0;
+	for (uint32_t i = threadIdx.x; i < pieces; i += blockDim.x) {
+		const uint32_t end = (uint32_t)packed_off[i] + W.resc[i].out_len;
+		x ^= gf2_mulmod(W.crc[i], gf2_xpow8(r.out_len - end));
+		if (!whole && i + 1 < pieces)
+			xb ^= gf2_mulmod(W.crc[i], gf2_xpow8(b.out_len - end));
+	}
+	for (int d = 32; d >= 1; d >>= 1) {
+		x ^= __shfl_xor(x, d, 64);
+		xb ^= __shfl_xor(xb, d, 64);
+	}
+	if ((threadIdx.x & 63) == 0 && x)
+		atomicXor(&crc, x);
+	if ((threadIdx.x & 63) == 0 && xb)
+		atomicXor(&crc_b, xb);
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		r.crc32 = crc;
+		results[0] = r;
+		b.crc32 = whole ? crc : crc_b;
+		results[2] = b;
+		la_gz_result f;
+		f.status = LA_ST_OK;
+		f.out_len = W.ctl[LA_FIND_N_CAND] - 1;	/* candidates found behind the caller's start */
+		f.consumed = pieces;			/* pieces confirmed */
+		f.crc32 = 0;
+		results[1] = f;
+	}
+}
+
+void la_launch_gz_blocks_summary(hipStream_t s, const uint8_t *d_dst, const la_gz_member *d_span, const uint64_t *d_packed_off,
+    uint32_t start_bit, const la_gz_find_ws &W, la_gz_result *d_results)
+{
+	uint32_t blocks = (W.max_cand + 3) / 4;
+	if (blocks > 256 * 8) blocks = 256 * 8;
+	hipLaunchKernelGGL(gz_blocks_crc_kernel, dim3(blocks), dim3(256), 0, s, d_dst, d_span, d_packed_off, W);
+	hipLaunchKernelGGL(gz_blocks_fold_kernel, dim3(1), dim3(256), 0, s, d_packed_off, start_bit, W, d_results);
+}
+
 __global__ void gz_summary_init(la_batch_summary *sm)
 {
 	sm->total_out = 0; sm->n_bad_units = 0; sm->n_bad_frames = 0;

@@ -388,20 +388,43 @@ struct wave_reader {
 };
 
 /* PIECES: the members are pieces of one raw-deflate stream (LA_GZ_OPT_PIECES; the rules are in la_deflate_dev.h);
- * CHAIN: see above (C is read by the chain instances only) */
-template <bool PIECES, int CHAIN>
+ * CHAIN: see above (C is read by the chain instances only);
+ * BITS (LA_GZ_OPT_BLOCK_STARTS, chain instances only; the other instances do not hold a byte of it): members[0] is ONE
+ * span and piece mi starts at bit C.starts[mi] of it, of *C.n_starts pieces (n bounds that number: the grid was sized
+ * before the device knew it).  The piece ends as dfl_piece_end_at says, and consumed is reported in bits. */
+template <bool PIECES, int CHAIN, bool BITS = false>
 __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const uint8_t *__restrict__ src,
     uint64_t src_bytes, const la_gz_member *__restrict__ members, uint32_t n, uint8_t *dst,
     uint64_t dst_cap, la_gz_result *__restrict__ results, la_inflate_chain C)
 {
+	static_assert(!BITS || (PIECES && CHAIN != LA_CHAIN_OFF), "bit-granular pieces exist in chain mode only");
 	__shared__ inf_tables tabs[INF_WAVES_PER_WG];
 	const int lane = threadIdx.x & 63;
 	const int wv = threadIdx.x >> 6;
 	const uint32_t mi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * INF_WAVES_PER_WG + wv));
 	if (mi >= n)
 		return;
+	uint32_t n_starts = 0, next_start = 0, start_bit = 0;
+	if constexpr (BITS) {
+		const uint32_t n_pieces = (uint32_t)__builtin_amdgcn_readfirstlane((int)*C.n_starts);
+		if (mi >= n_pieces)
+			return;
+		/* (the table may name one start more than there are pieces: the piece the walk stopped in front of) */
+		n_starts = (uint32_t)__builtin_amdgcn_readfirstlane((int)*C.n_table);
+		if (n_starts > n + 1)
+			n_starts = n + 1;
+		start_bit = (uint32_t)__builtin_amdgcn_readfirstlane((int)C.starts[mi]);
+		next_start = mi + 1;
+	}
 	inf_tables *T = &tabs[wv];
-	const la_gz_member m = members[mi];
+	la_gz_member m = members[BITS ? 0 : mi];
+	/* (the first byte of the span; m becomes the piece: the span from the byte that holds its first bit) */
+	const uint64_t span_off = m.src_off;
+	if constexpr (BITS) {
+		const uint32_t skip = start_bit >> 3 < m.src_len ? start_bit >> 3 : m.src_len;
+		m.src_off += skip;
+		m.src_len -= skip;
+	}
 	uint32_t status = LA_ST_OK;
 	DIAG_DECL;
 #ifdef LA_DIAG
@@ -445,6 +468,11 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 	}
 
 	wave_reader R = { B, T, lane, 0 };
+	if constexpr (BITS) {
+		/* the bits of the first byte in front of the piece belong to the block before it */
+		if (br_need(B, (int)(start_bit & 7u), lane))
+			br_take(B, (int)(start_bit & 7u));
+	}
 	for (;;) {
 		if (!br_need(B, 3, lane)) { status = LA_ST_GZ_TRUNCATED; break; }
 		int last = (int)br_take(B, 1);
@@ -505,7 +533,17 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 		 * with the cursor stepped back: both counts are exact here) */
 		if (dfl_piece_end<PIECES>((int64_t)B.bits + 8 * (int64_t)(B.iend - B.ip))) {
 			status = LA_ST_GZ_PIECE_END;
+			if constexpr (BITS)
+				next_start = 0xFFFFFFFFu;
 			break;
+		}
+		if constexpr (BITS) {
+			/* (below 2^32: la_api.hip refuses a source of 2^29 bytes or more) */
+			const uint32_t cursor = (uint32_t)(8 * (int64_t)(B.ip - (src + span_off)) - (int64_t)B.bits);
+			if (dfl_piece_end_at<BITS>(cursor, C.starts, n_starts, next_start)) {
+				status = LA_ST_GZ_PIECE_END;
+				break;
+			}
 		}
 	}
 	/* what zlib would have emitted before noticing: whole symbols, stored data bytewise */
@@ -534,6 +572,10 @@ __global__ __launch_bounds__(64 * INF_WAVES_PER_WG) void inflate_kernel(const ui
 		r.out_len = O.op;
 		r.consumed = consumed;
 		r.crc32 = 0;
+		if constexpr (BITS) {
+			r.consumed = (uint32_t)(8 * (int64_t)(B.ip - (src + span_off)) - (int64_t)B.bits);
+			r.crc32 = next_start;
+		}
 		results[mi] = r;
 	}
 }
@@ -557,3 +599,12 @@ void la_launch_inflate_chain(hipStream_t s, const uint8_t *d_src, uint64_t src_b
 	    dim3(64 * INF_WAVES_PER_WG), 0, s, d_src, src_bytes, d_members, n, d_dst, dst_cap, d_results, C);
 }
 
+/* the chain instances for pieces that start at a bit (LA_GZ_OPT_BLOCK_STARTS): n_max waves, of which *C.n_starts work */
+void la_launch_inflate_chain_bits(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, const la_gz_member *d_span,
+    uint32_t n_max, uint8_t *d_dst, uint64_t dst_cap, la_gz_result *d_results, const la_inflate_chain &C, bool emit)
+{
+	if (n_max == 0) return;
+	const auto kernel = emit ? inflate_kernel<true, LA_CHAIN_EMIT, true> : inflate_kernel<true, LA_CHAIN_MEASURE, true>;
+	hipLaunchKernelGGL(kernel, dim3((n_max + INF_WAVES_PER_WG - 1) / INF_WAVES_PER_WG),
+	    dim3(64 * INF_WAVES_PER_WG), 0, s, d_src, src_bytes, d_span, n_max, d_dst, dst_cap, d_results, C);
+}

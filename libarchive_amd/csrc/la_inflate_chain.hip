@@ -123,6 +123,26 @@ void la_launch_chain_resolve(hipStream_t s, const la_gz_member *d_members, const
 	    &d_members->dst_off, d_dst);
 }
 
+/* the length of the packed range from the device (LA_GZ_OPT_BLOCK_STARTS: the end of the scan over the confirmed pieces);
+ * a value above the capacity -- there is none: the walk stops in front of the piece that would pass it -- resolves nothing */
+__global__ void chain_total_dev_kernel(uint32_t *ctl, const uint64_t *total, uint64_t dst_cap)
+{
+	ctl[LA_CHAIN_JUMP_PASSES] = *total <= dst_cap ? (uint32_t)*total : 0u;
+}
+
+void la_launch_chain_resolve_dev(hipStream_t s, uint8_t *d_dst, const uint64_t *d_first_off, uint32_t *d_ptr, uint32_t hist_len,
+    const uint64_t *d_total, uint64_t dst_cap, uint32_t *d_ctl)
+{
+	(void)hipMemsetAsync(d_ctl, 0, LA_CHAIN_CTL_WORDS * sizeof(uint32_t), s);
+	hipLaunchKernelGGL(chain_total_dev_kernel, dim3(1), dim3(1), 0, s, d_ctl, d_total, dst_cap);
+	uint64_t blocks = (dst_cap + 4 * CHAIN_TPB - 1) / (4 * CHAIN_TPB);
+	if (blocks < 1) blocks = 1;
+	if (blocks > 4096) blocks = 4096;
+	for (uint32_t pass = 0; pass < LA_CHAIN_JUMP_PASSES; pass++)
+		hipLaunchKernelGGL(chain_jump_kernel, dim3((uint32_t)blocks), dim3(CHAIN_TPB), 0, s, d_ptr, hist_len, d_ctl, pass);
+	hipLaunchKernelGGL(chain_gather_kernel, dim3((uint32_t)blocks), dim3(CHAIN_TPB), 0, s, d_ptr, hist_len, d_ctl, d_first_off, d_dst);
+}
+
 __global__ void chain_total_kernel(uint32_t *ctl, uint32_t total) { ctl[LA_CHAIN_JUMP_PASSES] = total; }
 
 /* the jump passes and the gather for a caller that has the pointers of d_dst[0, total) in d_ptr (coordinate = index,

@@ -51,6 +51,53 @@ def decode_pieces(ctx, d_src, pieces, options=0):
     return plan, plan.results()
 
 
+class BlockStartsRun:
+    """what decode_block_starts returns: status, out_len, consumed_bits, crc32 of the confirmed chain; candidates found and
+    pieces confirmed; boundary = the third result; out = the d_dst tensor (the packed bytes start at lead)"""
+
+
+def decode_block_starts(ctx, d_src, src_off, src_len, dst_cap, start_bit=0, hist=b"", lead=32768 + 64, guard=0xA5, src_bytes=None,
+                        options=None, expect_rc=0):
+    """la_gpu_gzip_decode with LA_GZ_OPT_PIECES | LA_GZ_OPT_CHAIN | LA_GZ_OPT_BLOCK_STARTS over ONE span of d_src that starts
+    on a true block boundary of a raw-deflate stream, at bit start_bit of its first byte.  hist: the stream's earlier output
+    (at most 32 KiB), placed in front of the packed bytes.  The destination is lead + dst_cap + 64 bytes prefilled with
+    `guard`.  Returns a BlockStartsRun, or None when the call was refused with expect_rc."""
+    import ctypes as C
+    import torch
+    dev = d_src.device
+    assert len(hist) <= lead
+    mem = np.zeros(1, dtype=N.GZ_MEMBER_DTYPE)
+    mem[0] = (src_off, src_len, min(dst_cap, 0xFFFFFFFF), lead)
+    host_dst = np.full(lead + dst_cap + 64, guard, dtype=np.uint8)
+    host_dst[lead - len(hist):lead] = np.frombuffer(hist, dtype=np.uint8)
+    d_mem = torch.from_numpy(mem.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_dst = torch.from_numpy(host_dst).to(dev)
+    d_res = torch.full((3 * N.GZ_RESULT_DTYPE.itemsize,), 0xEE, dtype=torch.uint8, device=dev)
+    b = N._GzBatchC()
+    b.d_src = d_src.data_ptr(); b.src_bytes = d_src.numel() if src_bytes is None else src_bytes
+    b.d_members = d_mem.data_ptr(); b.n_members = 1
+    b.d_dst = d_dst.data_ptr(); b.dst_cap = dst_cap
+    b.d_results = d_res.data_ptr(); b.d_summary = None
+    if options is None:
+        options = N.LA_GZ_OPT_PIECES | N.LA_GZ_OPT_CHAIN | N.LA_GZ_OPT_BLOCK_STARTS
+    b.options = options | (start_bit << N.LA_GZ_OPT_START_BIT_SHIFT)
+    b.hist_len = len(hist)
+    rc = N.gpu_lib().la_gpu_gzip_decode(ctx._h, C.byref(b))
+    ctx.sync()
+    assert rc == expect_rc, (rc, expect_rc)
+    if rc != 0:
+        assert bool((d_res == 0xEE).all()) and bool((d_dst.cpu() == torch.from_numpy(host_dst)).all()), "a refused call wrote something"
+        return None
+    res = d_res.cpu().numpy().view(N.GZ_RESULT_DTYPE)
+    r = BlockStartsRun()
+    r.status, r.out_len, r.consumed_bits, r.crc32 = (int(res[0][k]) for k in ("status", "out_len", "consumed", "crc32"))
+    r.candidates, r.pieces = int(res[1]["out_len"]), int(res[1]["consumed"])
+    # (status, out_len, consumed_bits, crc32) of the chain as far as it stands on a block boundary
+    r.boundary = tuple(int(res[2][k]) for k in ("status", "out_len", "consumed", "crc32"))
+    r.out, r.lead, r.dst_cap, r.hist, r.guard = d_dst, lead, dst_cap, hist, guard
+    return r
+
+
 def compress_to_members(ctx, d_plain, chunk_bytes=49152, mtime=0, options=0, framing=0):
     """Device gzip compression (la_gpu_gzip_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8 CUDA
     tensor holding the concatenated gzip members (harness for the tests).  options: 0 fixed Huffman, 1 the smallest of

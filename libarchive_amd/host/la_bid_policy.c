@@ -87,6 +87,15 @@ int la_gz_flush_points_chain(void)
 	return v != NULL && strcmp(v, "chain") == 0;
 }
 
+/* LA_GZIP_BLOCK_STARTS=1: ONE ordinary member -- no flush point, no second header -- is no serial unit any more: the
+ * filter lets the device find its block starts and decodes it as a chain of pieces (LA_GZ_OPT_BLOCK_STARTS), so the
+ * bidder takes it.  Read at every call, as la_gz_flush_points_enabled is. */
+int la_gz_block_starts_enabled(void)
+{
+	const char *v = getenv("LA_GZIP_BLOCK_STARTS");
+	return v != NULL && v[0] == '1';
+}
+
 /* LA_GZIP_FLUSH_POINTS=1: ONE member whose body is a chain of flush points (00 00 FF FF, la_gz_pieces_build) decodes a
  * piece per lane.  Evidence inside the look-ahead: at least LA_BID_GZ_MARKERS markers behind the header, none further
  * than LA_BID_GZ_GAP from the one before (the first: from the header) -- the pieces of zlib's Z_FULL_FLUSH writers,
@@ -109,11 +118,14 @@ static int gzip_flush_points(const unsigned char *p, size_t n, size_t hdr_len)
 /* gzip: p[0..n) starts with a member whose header (hdr_len bytes, parsed by the caller) carries no BGZF size.
  * 1 = take it.  A second member header inside the look-ahead counts as evidence of a many-member stream; the
  * candidate test is the strict one of the boundary search (XFL / OS bytes that real writers emit).  With
- * LA_GZIP_FLUSH_POINTS=1 a chain of flush points counts too. */
+ * LA_GZIP_FLUSH_POINTS=1 a chain of flush points counts too; with LA_GZIP_BLOCK_STARTS=1 a lone member needs no
+ * evidence at all. */
 int la_bid_gzip_parallel(const unsigned char *p, size_t n, size_t hdr_len, size_t lookahead)
 {
 	if (n < lookahead)
 		return 1;	/* the whole stream is smaller than the look-ahead */
+	if (la_gz_block_starts_enabled())
+		return 1;
 	if (la_gz_flush_points_enabled() && gzip_flush_points(p, n, hdr_len))
 		return 1;
 	for (size_t i = hdr_len + 1; i + 10 <= n; i++) {

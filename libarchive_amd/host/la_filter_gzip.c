@@ -21,7 +21,7 @@
  *     first 64 KiB were produced (gzip.c:160-163, :196-201, :280-296).
  * There is no CPU decode path: without a usable GPU, init() fails the open.
  *
- * Environment: LA_GPU_DEVICE, LA_GPU_BATCH_MIB (as for lz4), LA_GZIP_STRICT, LA_GZIP_FLUSH_POINTS.
+ * Environment: LA_GPU_DEVICE, LA_GPU_BATCH_MIB (as for lz4), LA_GZIP_STRICT, LA_GZIP_FLUSH_POINTS, LA_GZIP_BLOCK_STARTS.
  */
 #include "la_read_private.h"
 #include "../../include/la_gpu.h"
@@ -40,13 +40,14 @@ static double gz_now(void)
 
 #define OUT_BLOCK 65536u	/* gzip.c:314 */
 #define LA_GZ_HIST 32768u	/* the deflate window: as far as a distance reaches */
+#define LA_GZ_BLOCKS_SPAN_MAX (((size_t)1 << 29) - 65536)	/* LA_GZ_OPT_BLOCK_STARTS: a source below 2^29 bytes, header included */
 
 /* What a walk asks of the next window's first unit, because a decode refuted the table: pass over `skip` candidate
  * boundaries (1f 8b 08 guesses, 00 00 FF FF markers) and give it an output slot of `cap` bytes at least. */
 struct gz_hint { uint32_t skip, cap; };
 
 /* which table the window in flight was queued from */
-enum gz_inflight { GZ_NONE = 0, GZ_MEMBERS, GZ_PIECES };
+enum gz_inflight { GZ_NONE = 0, GZ_MEMBERS, GZ_PIECES, GZ_BLOCKS };
 
 struct gzip_private {
 	la_window w;
@@ -104,6 +105,19 @@ struct gzip_private {
 	int fp_chain;
 	la_buf hist;		/* pinned, LA_GZ_HIST bytes */
 	size_t hist_len;
+	/* Block-start mode (LA_GZIP_BLOCK_STARTS=1): the FIRST member of the stream, when it carries no BGZF size, is decoded
+	 * from the block starts the device finds in it (LA_GZ_OPT_BLOCK_STARTS): one span per window, from a true block
+	 * boundary -- behind the header, or where the window before stopped -- to the end of the window.  What is carried
+	 * from window to window is what the chain of pieces carries (st->pm, st->hist) and one thing more: the bit of the
+	 * span's first byte the boundary lies at.  Members behind the first go the ordinary way. */
+	int bs_on;
+	int bs_done;		/* the first member is behind us, or it left this mode before anything of it was out */
+	uint32_t bs_bit;	/* 0..7 */
+	uint32_t bs_cap;	/* a larger output capacity asked for by a window that could not place one piece */
+	size_t bs_span_limit;	/* bytes of the window given to one call: below 2^29 (32-bit bit offsets on the device); grows when
+				 * a span confirms nothing; LA_GZ_TEST_BLOCKS_WINDOW lowers where it starts, for tests */
+	size_t bs_from, bs_len;	/* the span of the window in flight */
+	la_gz_member bs_span;
 };
 
 static int gzip_bidder_bid(struct archive_read_filter_bidder *, struct archive_read_filter *);
@@ -206,6 +220,13 @@ static int gzip_bidder_init(struct archive_read_filter *self)
 	}
 	st->fp_on = la_gz_flush_points_enabled();
 	st->fp_chain = la_gz_flush_points_chain();
+	st->bs_on = la_gz_block_starts_enabled();
+	st->bs_span_limit = LA_GZ_BLOCKS_SPAN_MAX;
+	{
+		const char *v = getenv("LA_GZ_TEST_BLOCKS_WINDOW");
+		if (v != NULL && strtoull(v, NULL, 10) >= 1024 && strtoull(v, NULL, 10) < st->bs_span_limit)
+			st->bs_span_limit = (size_t)strtoull(v, NULL, 10);
+	}
 	st->trace = getenv("LA_GPU_TRACE") != NULL && atoi(getenv("LA_GPU_TRACE")) != 0;
 	st->no_ahead = getenv("LA_GZ_NO_COPY_AHEAD") != NULL && atoi(getenv("LA_GZ_NO_COPY_AHEAD")) != 0;
 	if (la_window_open(self, &st->w, "gzip") != ARCHIVE_OK) {
@@ -235,6 +256,7 @@ struct gz_units {
 	enum gz_inflight kind;
 	const la_gz_member *tab;
 	uint32_t n;
+	uint32_t n_res;		/* results the device writes: one per unit, three for the one span of block-start mode */
 	uint64_t consumed;	/* bytes of the window the table covers */
 	uint64_t max_out;	/* sum of the slots */
 	int end_kind;		/* LA_END_*: what follows the last unit */
@@ -247,9 +269,12 @@ static struct gz_units gz_units_of(const struct gzip_private *st, enum gz_inflig
 	const la_gz_pieces *p = &st->pcs;
 	const la_gz_index *x = &st->idx;
 	if (kind == GZ_PIECES)
-		return (struct gz_units){ kind, p->pieces, p->n, p->consumed, p->max_out, p->end_kind,
+		return (struct gz_units){ kind, p->pieces, p->n, p->n, p->consumed, p->max_out, p->end_kind,
 		    st->fp_chain ? LA_GZ_HIST : 0, st->fp_chain };
-	return (struct gz_units){ kind, x->members, x->n, x->consumed, x->max_out, x->end_kind, 0, 0 };
+	if (kind == GZ_BLOCKS)
+		return (struct gz_units){ kind, &st->bs_span, 1, 3, st->bs_from + st->bs_len, st->bs_span.dst_cap, LA_END_NEED_MORE,
+		    LA_GZ_HIST, 1 };
+	return (struct gz_units){ kind, x->members, x->n, x->n, x->consumed, x->max_out, x->end_kind, 0, 0 };
 }
 
 /* the window's table is done with (the one that is not in use is empty: freeing it changes nothing) */
@@ -357,10 +382,11 @@ static void gz_take_metadata(struct gzip_private *st, const struct gz_walk *w, c
 static int gz_launch(struct archive_read_filter *self, struct gzip_private *st, const struct gz_units *u)
 {
 	la_gpu_ctx *gpu = st->w.gpu;
-	const int pieces = u->kind == GZ_PIECES;
+	const int blocks = u->kind == GZ_BLOCKS;
+	const int pieces = u->kind == GZ_PIECES || blocks;
 	size_t o = 0;
 	const size_t o_mem = o; o += ALIGN256((size_t)u->n * sizeof(la_gz_member));
-	const size_t o_res = o; o += ALIGN256((size_t)u->n * sizeof(la_gz_result));	/* (st->o_res once the window is in flight) */
+	const size_t o_res = o; o += ALIGN256((size_t)u->n_res * sizeof(la_gz_result));	/* (st->o_res once the window is in flight) */
 	const size_t o_sum = o; o += 256;
 	if (la_buf_dev(gpu, &st->d_dst, u->lead + (size_t)u->max_out + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o) < 0)
 		return la_window_fail(self, &st->w, "device allocation");
@@ -368,7 +394,7 @@ static int gz_launch(struct archive_read_filter *self, struct gzip_private *st, 
 	if (la_gpu_memcpy_h2d(gpu, T + o_mem, u->tab, (size_t)u->n * sizeof(la_gz_member)) != LA_OK)
 		return la_window_fail(self, &st->w, "host to device copy");
 	la_gz_batch bt = {
-		.d_src = st->d_src.p, .src_bytes = pieces ? st->stage_len : (size_t)u->consumed,
+		.d_src = st->d_src.p, .src_bytes = blocks ? (size_t)u->consumed : pieces ? st->stage_len : (size_t)u->consumed,
 		.d_members = (const la_gz_member *)(T + o_mem), .n_members = u->n,
 		.d_dst = st->d_dst.p + u->lead, .dst_cap = u->max_out, .d_results = (la_gz_result *)(T + o_res),
 		.d_summary = pieces ? NULL : (la_batch_summary *)(T + o_sum), .options = pieces ? LA_GZ_OPT_PIECES : 0,
@@ -384,6 +410,8 @@ static int gz_launch(struct archive_read_filter *self, struct gzip_private *st, 
 		bt.options |= LA_GZ_OPT_CHAIN;
 		bt.hist_len = (uint32_t)st->hist_len;
 	}
+	if (blocks)
+		bt.options |= LA_GZ_OPT_BLOCK_STARTS | st->bs_bit << LA_GZ_OPT_START_BIT_SHIFT;
 	if (la_gpu_gzip_decode(gpu, &bt) != LA_OK)
 		return la_window_fail(self, &st->w, "la_gpu_gzip_decode");
 	st->o_res = o_res;
@@ -687,6 +715,112 @@ static void gzip_walk_pieces(struct gzip_private *st, const la_gz_result *res, s
 }
 
 /*
+ * Block-start mode: the one span of the window, judged by the three results of LA_GZ_OPT_BLOCK_STARTS (la_gpu.h).  The
+ * device has confirmed the chain itself; what is left to the host is where the chain stands on a block boundary (res[2]),
+ * whether more input lies behind the span, and the member's trailer.
+ */
+static void gzip_walk_blocks(struct gzip_private *st, const la_gz_result *res, struct gz_walk *w)
+{
+	const la_gz_result *r = &res[0], *b = &res[2];
+	const size_t from = st->bs_from, span_end = from + st->bs_len;
+	const int more_behind = span_end < st->stage_len || !st->w.upstream_eof;
+	const uint32_t start_bit = st->bs_bit;
+	if (!st->pm.in_member) {
+		la_gz_header h;
+		la_gz_header_parse(st->stage.p, st->stage_len, &h);
+		gz_take_metadata(st, w, &h);
+	}
+	w->used = 0;
+	if (r->status == LA_ST_OK) {
+		/* the final block ended: the member's trailer follows on the next byte boundary */
+		const uint64_t tr = from + (((uint64_t)r->consumed + 7) >> 3);
+		if (tr + 8 > st->stage_len && !st->w.upstream_eof) {
+			/* the trailer lies beyond this window: the same bytes again once more of them are here (a span that was
+			 * cut short of the window reaches further next time) */
+			if (span_end < st->stage_len) {
+				st->bs_span_limit *= 2;
+				w->again = 1;
+			}
+			return;
+		}
+		if (tr + 8 > st->stage_len) {
+			gz_failed_after(st, w, 1, r->out_len, GZ_NO_TRAILER);
+			return;
+		}
+		const uint8_t *t = st->stage.p + tr;
+		const uint32_t crc = la_crc32_combine(st->pm.crc, r->crc32, r->out_len);
+		const uint32_t isize = (uint32_t)(st->pm.bytes + r->out_len);
+		const uint32_t t_crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+		const uint32_t t_len = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+		if (st->strict && (t_crc != crc || t_len != isize)) {
+			gz_fail_in_front(st, w, la_status_message(t_crc != crc ? LA_ST_GZ_BAD_CRC : LA_ST_GZ_BAD_ISIZE));
+			return;
+		}
+		w->take = 1;
+		w->total += r->out_len;
+		/* the member is over: what follows is indexed the ordinary way */
+		memset(&st->pm, 0, sizeof(st->pm));
+		st->bs_done = 1;
+		st->bs_bit = 0;
+		w->used = (size_t)(tr + 8);
+		return;
+	}
+	if (r->status == LA_ST_GZ_DATA) {
+		/* (the failing piece starts on a confirmed boundary and read nothing but the stream's own bits: the error is the
+		 * stream's) */
+		gz_failed_after(st, w, 1, r->out_len, GZ_DATA_ERROR);
+		return;
+	}
+	if (r->status == LA_ST_GZ_TRUNCATED && !more_behind) {
+		gz_truncated(st, w, 1, r->out_len);
+		return;
+	}
+	if (r->status != LA_ST_GZ_TRUNCATED && r->status != LA_ST_GZ_PIECE_END && r->status != LA_ST_GZ_OUT_FULL) {
+		gz_fail_in_front(st, w, GZ_DATA_ERROR);
+		return;
+	}
+	/* the member goes on behind what stands on a block boundary */
+	if (b->status == LA_ST_GZ_PIECE_END && (uint64_t)b->consumed > start_bit) {
+		st->pm.crc = la_crc32_combine(st->pm.crc, b->crc32, b->out_len);
+		st->pm.bytes += b->out_len;
+		st->pm.in_member = 1;
+		w->take = 1;
+		w->total += b->out_len;
+		w->used = from + (size_t)(b->consumed >> 3);
+		st->bs_bit = b->consumed & 7u;
+		if (!more_behind && w->used >= st->stage_len)
+			/* a non-final block ended on the last bit of the input */
+			gz_truncated(st, w, 1, 0);
+		return;
+	}
+	/* nothing confirmed: not one piece of the span ended on a block boundary inside it */
+	if (r->status == LA_ST_GZ_OUT_FULL) {
+		/* ... because the first piece does not fit */
+		const struct gz_hint prev = { 0, st->bs_cap };
+		struct gz_hint h = prev;
+		gz_grow_slot(st, w, &h, prev, 0, st->bs_span.dst_cap, 0);
+		st->bs_cap = h.cap;
+		return;
+	}
+	if (span_end < st->stage_len) {		/* the span was cut short of the window: a longer one */
+		st->bs_span_limit = st->bs_span_limit * 2 < LA_GZ_BLOCKS_SPAN_MAX ? st->bs_span_limit * 2 : LA_GZ_BLOCKS_SPAN_MAX;
+		if (st->bs_len < LA_GZ_BLOCKS_SPAN_MAX - from) {
+			w->again = 1;
+			return;
+		}
+	}
+	if (st->stage_len < st->w.max_batch_bytes && st->bs_len < LA_GZ_BLOCKS_SPAN_MAX - from)
+		return;		/* (no progress and nothing asked again: the window grows, gzip_filter_read) */
+	/* one run of fixed and stored blocks as long as the window may get */
+	if (!st->pm.in_member) {
+		st->bs_done = 1;	/* nothing of the member is out: it goes the ordinary way, on one wave */
+		w->again = 1;
+		return;
+	}
+	gz_refuse(st, w, "gzip member holds no dynamic block start within LA_GPU_MAX_BATCH_MIB (read it without LA_GZIP_BLOCK_STARTS)");
+}
+
+/*
  * The window in flight: results, stream-order walk, slab.  On return the slab holds carry + newly decoded bytes
  * (st->carry_len updated to the total now waiting) and st->last_ret says how many of them go out now.
  */
@@ -695,17 +829,20 @@ static int gz_finish(struct archive_read_filter *self, struct gzip_private *st, 
 	const struct gz_units u = gz_units_of(st, st->inflight);
 	*w = (struct gz_walk){ .total = st->total_out, .cutoff = UINT64_MAX, .contiguous = 1, .used = (size_t)u.consumed,
 	    .b0 = st->trace ? gz_now() : 0 };
-	if (la_buf_host(&st->h_res, (size_t)u.n * sizeof(la_gz_result)) < 0) {
+	if (la_buf_host(&st->h_res, (size_t)u.n_res * sizeof(la_gz_result)) < 0) {
 		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for gzip decompression");
 		return ARCHIVE_FATAL;
 	}
 	const la_gz_result *res = (const la_gz_result *)st->h_res.p;
-	if (la_gpu_memcpy_d2h(st->w.gpu, st->h_res.p, st->d_tabs.p + st->o_res, (size_t)u.n * sizeof(la_gz_result)) != LA_OK ||
+	if (la_gpu_memcpy_d2h(st->w.gpu, st->h_res.p, st->d_tabs.p + st->o_res, (size_t)u.n_res * sizeof(la_gz_result)) != LA_OK ||
 	    la_gpu_sync(st->w.gpu) != LA_OK)
 		return la_window_fail(self, &st->w, "result copy");
 	w->b1 = st->trace ? gz_now() : 0;
 	if (u.kind == GZ_PIECES) {
 		gzip_walk_pieces(st, res, w);
+		st->ahead_ok = 0;
+	} else if (u.kind == GZ_BLOCKS) {
+		gzip_walk_blocks(st, res, w);
 		st->ahead_ok = 0;
 	} else
 		gzip_walk_members(st, res, w);
@@ -789,6 +926,50 @@ static int gz_prepare_pieces(struct archive_read_filter *self, struct gzip_priva
 }
 
 /*
+ * gz_prepare's block-start branch, behind the gather and the upload.  2: the window is not one for this mode (go on the
+ * ordinary way); otherwise as gz_prepare.
+ */
+static int gz_prepare_blocks(struct archive_read_filter *self, struct gzip_private *st)
+{
+	size_t from = 0;
+	if (!st->pm.in_member) {
+		/* the stream's first member, when its header carries no BGZF size */
+		la_gz_header h;
+		const size_t hlen = la_gz_header_parse(st->stage.p, st->stage_len, &h);
+		if (hlen == 0 || h.bgzf_size || hlen >= st->stage_len) {
+			/* (a header that is not all here yet is looked at again with the next window) */
+			if ((hlen != 0 && h.bgzf_size) || st->w.upstream_eof)
+				st->bs_done = 1;
+			return 2;
+		}
+		from = hlen;
+		st->bs_bit = 0;
+	}
+	size_t len = st->stage_len - from;
+	if (len > st->bs_span_limit)
+		len = st->bs_span_limit;
+	if (len > LA_GZ_BLOCKS_SPAN_MAX - from)
+		len = LA_GZ_BLOCKS_SPAN_MAX - from;
+	/* the capacity: eight times the span (as the piece walker's slots), more when a window asked for it */
+	uint64_t cap = (uint64_t)len * 8 < 65536 ? 65536 : (uint64_t)len * 8;
+	if (cap < st->bs_cap)
+		cap = st->bs_cap;
+	if (cap > st->slot_limit)
+		cap = st->slot_limit;
+	st->bs_from = from;
+	st->bs_len = len;
+	st->bs_span = (la_gz_member){ .src_off = from, .src_len = (uint32_t)len, .dst_cap = (uint32_t)cap, .dst_off = 0 };
+	const int rc = gz_queue(self, st, GZ_BLOCKS);
+	if (rc <= 0)
+		return rc;
+	st->ahead_ok = 0;
+	la_window_ramp(&st->w);
+	if (st->trace)
+		fprintf(stderr, "la_gzip: window %zu bytes, block starts of %zu bytes from %zu, bit %u\n", st->stage_len, len, from, st->bs_bit);
+	return 1;
+}
+
+/*
  * Gather one window, start its upload, find the member boundaries and queue the decode: nothing is
  * waited for.  Returns 1 when a window is in flight (st->inflight), 0 when the state changed
  * instead (end of stream, pending error, wider window, looser boundary search: the caller looks again),
@@ -809,6 +990,11 @@ static int gz_prepare(struct archive_read_filter *self, struct gzip_private *st)
 		return la_window_fail(self, &st->w, "host to device copy");
 	if (st->fp_on && !st->pm_declined) {
 		const int pr = gz_prepare_pieces(self, st);
+		if (pr != 2)
+			return pr;
+	}
+	if (st->bs_on && !st->bs_done && !st->fp_on) {
+		const int pr = gz_prepare_blocks(self, st);
 		if (pr != 2)
 			return pr;
 	}

@@ -1,0 +1,114 @@
+/* TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_gzip_decode with LA_GZ_OPT_BLOCK_STARTS, as include/la_gpu.h words it,
+ * so that the host side of the gzip read filter's block-start mode runs without a GPU.  The candidates are the rules
+ * header's (la_deflate_find_dev.h, compiled for the host); the decode is zlib's raw inflate walked with Z_BLOCK, which says
+ * where every block ends: a piece ends where a block ends on a candidate.  Every other call goes to ../mock_gpu, whose
+ * la_gpu_gzip_decode is compiled under the name la_gpu_gzip_decode_base (Makefile).  Not part of the product. */
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+#include <zlib.h>
+#include "../../libarchive_amd/csrc/la_deflate_find_dev.h"
+
+extern "C" int la_gpu_gzip_decode_base(la_gpu_ctx *c, const la_gz_batch *bt);
+
+struct boundary { uint64_t bits, out; };
+
+static int blocks_decode(const la_gz_batch *bt)
+{
+	const la_gz_member m = bt->d_members[0];
+	const uint32_t start_bit = LA_GZ_OPT_START_BIT(bt->options);
+	uint64_t len = m.src_off < bt->src_bytes ? bt->src_bytes - m.src_off : 0;
+	if (len > m.src_len) len = m.src_len;
+	const uint8_t *base = bt->d_src + m.src_off;
+	uint8_t *out = bt->d_dst + m.dst_off;
+	uint64_t cap = bt->dst_cap < m.dst_cap ? bt->dst_cap : m.dst_cap;
+
+	std::vector<uint64_t> cand;
+	for (uint64_t p = (uint64_t)start_bit + 1; p < 8 * len; p++)
+		if (dfl_find_full(base, p, 8 * len))
+			cand.push_back(p);
+
+	z_stream s;
+	memset(&s, 0, sizeof(s));
+	if (inflateInit2(&s, -15) != Z_OK)
+		return LA_ERR_ARG;
+	if (bt->hist_len)
+		inflateSetDictionary(&s, out - bt->hist_len, bt->hist_len);
+	uint64_t skipped = 0;		/* whole bytes of the span that zlib does not count in total_in */
+	if (start_bit && len) {
+		inflatePrime(&s, 8 - (int)start_bit, base[0] >> start_bit);
+		skipped = 1;
+	}
+	s.next_in = (Bytef *)(base + skipped);
+	s.avail_in = (uInt)(len - skipped);
+	s.next_out = out;
+	s.avail_out = (uInt)cap;
+	uint8_t sink;
+	uint32_t status = LA_ST_GZ_TRUNCATED, pieces = 1;
+	boundary last = { start_bit, 0 };	/* where the last piece starts */
+	size_t ci = 0;
+	uint64_t cursor = start_bit;
+	bool full = false, sinking = false;
+	for (;;) {
+		if (s.avail_out == 0 && !sinking) {	/* one byte more would not fit: is there one? */
+			s.next_out = &sink;
+			s.avail_out = 1;
+			sinking = true;
+		}
+		const int rc = inflate(&s, Z_BLOCK);
+		if (sinking && s.avail_out == 0) { full = true; break; }
+		if (rc == Z_STREAM_END) { status = LA_ST_OK; break; }
+		if (rc == Z_BUF_ERROR) { status = LA_ST_GZ_TRUNCATED; break; }	/* (no input left: there is always room for output) */
+		if (rc != Z_OK) { status = LA_ST_GZ_DATA; break; }
+		if ((s.data_type & 128) && !(s.data_type & 64)) {
+			/* behind the end-of-block code of a block without BFINAL */
+			cursor = 8 * (skipped + (uint64_t)s.total_in) - (uint64_t)(s.data_type & 63);
+			if (cursor == 8 * len && cursor > start_bit) { status = LA_ST_GZ_PIECE_END; break; }
+			while (ci < cand.size() && cand[ci] < cursor) ci++;
+			if (ci < cand.size() && cand[ci] == cursor && cursor > last.bits) {
+				last.bits = cursor;
+				last.out = s.total_out;
+				pieces++;
+			}
+		}
+	}
+	const uint64_t produced = s.total_out > cap ? cap : s.total_out;
+	const uint64_t end_bits = 8 * (skipped + (uint64_t)s.total_in) - (uint64_t)(s.data_type & 63);
+	inflateEnd(&s);
+
+	la_gz_result r0, r1, r2;
+	if (full) {
+		/* the last piece does not fit: the chain stops in front of it */
+		pieces--;
+		r0.status = LA_ST_GZ_OUT_FULL; r0.out_len = (uint32_t)last.out; r0.consumed = (uint32_t)last.bits;
+	} else {
+		r0.status = status; r0.out_len = (uint32_t)produced;
+		r0.consumed = (uint32_t)(status == LA_ST_GZ_PIECE_END ? cursor : end_bits);
+	}
+	r0.crc32 = (uint32_t)crc32(0, out, r0.out_len);
+	r1.status = LA_ST_OK; r1.out_len = (uint32_t)cand.size(); r1.consumed = pieces; r1.crc32 = 0;
+	r2 = r0;
+	if (r0.status != LA_ST_OK && r0.status != LA_ST_GZ_PIECE_END && r0.status != LA_ST_GZ_OUT_FULL) {
+		r2.status = LA_ST_GZ_PIECE_END; r2.out_len = (uint32_t)last.out; r2.consumed = (uint32_t)last.bits;
+		r2.crc32 = (uint32_t)crc32(0, out, r2.out_len);
+	}
+	bt->d_results[0] = r0; bt->d_results[1] = r1; bt->d_results[2] = r2;
+	return LA_OK;
+}
+
+extern "C" int la_gpu_gzip_decode(la_gpu_ctx *c, const la_gz_batch *bt)
+{
+	if (!c || !bt)
+		return LA_ERR_ARG;
+	if (!(bt->options & LA_GZ_OPT_BLOCK_STARTS))
+		return la_gpu_gzip_decode_base(c, bt);
+	if (!bt->d_src || !bt->d_members || !bt->d_dst || !bt->d_results)
+		return LA_ERR_ARG;
+	if ((bt->options & (LA_GZ_OPT_PIECES | LA_GZ_OPT_CHAIN)) != (LA_GZ_OPT_PIECES | LA_GZ_OPT_CHAIN) ||
+	    (bt->options & (LA_GZ_OPT_LANE_KERNEL | LA_GZ_OPT_TWO_PHASE | LA_GZ_OPT_EXPAND_INORDER)) ||
+	    bt->n_members != 1 || bt->src_bytes >= (1ull << 29) ||
+	    bt->hist_len > 32768u || bt->dst_cap + bt->hist_len > 0xFFFFFFFFull)
+		return LA_ERR_ARG;
+	return blocks_decode(bt);
+}
