@@ -124,7 +124,18 @@ enum {
 	LA_ST_XZ_SIZE             = 28,	/* the data disagrees with a size of the block header */
 	LA_ST_XZ_BAD_CHECK        = 29,	/* the check field is not the CRC32 / CRC64 / SHA-256 of the block's bytes */
 	LA_ST_XZ_PADDING          = 30,	/* a non-zero byte in the block padding */
-	LA_ST_XZ_OUT_FULL         = 31	/* a block of unknown size produces more than dst_cap bytes: the host retries with more */
+	LA_ST_XZ_OUT_FULL         = 31,	/* a block of unknown size produces more than dst_cap bytes: the host retries with more */
+	/* lzip (xz.c:443-451 for the first, :605-632 "Lzip: ..." for the last two; the others are questions to the host) */
+	LA_ST_LZIP_DATA           = 32,	/* refused inside the LZMA stream: a distance beyond the data or the dictionary, a code that
+					 * is not 0 behind the end-of-payload marker */
+	LA_ST_LZIP_SRC_END        = 33,	/* the stream asks for a byte at or behind the member's tentative end (src_end) */
+	LA_ST_LZIP_TRUNCATED      = 34,	/* no tentative end, and the stream asks for a byte behind d_src */
+	LA_ST_LZIP_EARLY_END      = 35,	/* the marker ends the stream in front of the tentative end */
+	LA_ST_LZIP_SIZE_OVER      = 36,	/* the stream produces more than the tentative data size */
+	LA_ST_LZIP_OUT_FULL       = 37,	/* no tentative size, and the stream produces more than dst_cap: the host retries with more */
+	LA_ST_LZIP_BAD_SIZE       = 38,	/* the stream ended with fewer bytes than the tentative data size */
+	LA_ST_LZIP_BAD_CRC        = 39,	/* the bytes do not give the trailer's CRC32 */
+	LA_ST_LZIP_REFUSED        = 40	/* the entry points outside d_src or d_dst, or its dst_cap is above LA_XZ_DST_CAP_MAX: not decoded */
 };
 
 /* =====================================================================
@@ -743,6 +754,64 @@ typedef struct la_xz_batch {
 
 uint64_t la_gpu_xz_workspace_bytes(uint32_t n);
 int      la_gpu_xz_decode(la_gpu_ctx *ctx, const la_xz_batch *batch);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * lzip -- replaces, for a table of members per call, what lzma_code does for xz_filter_read on a .lz stream
+ * (libarchive/archive_read_support_filter_xz.c:533-646, :651-735: lzma_raw_decoder with one LZMA1 filter, lc 3, lp 0,
+ * pb 2).  A member is "LZIP", a version byte (0, 1), a dictionary byte, ONE LZMA stream that ends at its end-of-payload
+ * marker, and a trailer: CRC32, data size, and (version 1) member size.  Members are independent: one workgroup per
+ * member, the probability model in LDS, the dictionary is the member's own output.  csrc/la_lzip_dev.h states the rules
+ * (through csrc/la_xz_dev.h's symbol loop).
+ *
+ * la_gpu_lzip_scan finds every offset of d_src[0, src_bytes) at which a member header can stand: "LZIP", a version of 0
+ * or 1, a dictionary byte b with 12 <= (b & 31) <= 29 (xz.c:343-374), all six bytes inside the source.  The offsets go in
+ * ascending order to d_offs[0, min(count, cap)); *d_count is the number found.  A match is a CANDIDATE: the host chains
+ * members by their trailers' member sizes (host/la_filter_lzip.c).
+ *
+ * la_gpu_lzip_decode decodes a table of members.  Either end of a member may be unknown (LA_LZIP_UNKNOWN): the source is
+ * then bounded by src_bytes (LA_ST_LZIP_TRUNCATED) instead of src_end (LA_ST_LZIP_SRC_END), the output by dst_cap
+ * (LA_ST_LZIP_OUT_FULL) instead of data_size (LA_ST_LZIP_SIZE_OVER).  A stream that ends elsewhere than a tentative end
+ * says is LA_ST_LZIP_EARLY_END / LA_ST_LZIP_BAD_SIZE.  With LA_LZIP_HAS_CRC the CRC32 of the bytes is compared with
+ * `crc32` (LA_ST_LZIP_BAD_CRC); the computed value is in the result either way.  On every failure out_len (= valid)
+ * bytes in front of it are in d_dst.  A tentative end or size that proves wrong is no verdict on the stream: the host
+ * decodes that member again with both unknown.  dst_cap is at most LA_XZ_DST_CAP_MAX, as for an xz block and for the same
+ * reason; such an entry, or one that points outside d_src or d_dst, is LA_ST_LZIP_REFUSED.  Additions under ABI version 3. */
+#define LA_LZIP_UNKNOWN (~(uint64_t)0)
+#define LA_LZIP_HAS_CRC 1u
+typedef struct la_lzip_member {
+	uint64_t src_off;	/* first byte of the LZMA stream inside d_src (behind the 6-byte header) */
+	uint64_t src_end;	/* tentative: the offset of the trailer (the byte behind the marker), or LA_LZIP_UNKNOWN */
+	uint64_t data_size;	/* tentative: the trailer's data size, or LA_LZIP_UNKNOWN */
+	uint64_t dst_off;	/* where the member's bytes go inside d_dst */
+	uint64_t dst_cap;	/* the member's output budget (at least data_size when that is given) */
+	uint32_t dict_size;	/* from the header's dictionary byte (la_lzip_dict_size) */
+	uint32_t crc32;		/* LA_LZIP_HAS_CRC: the trailer's CRC32 */
+	uint32_t flags;		/* LA_LZIP_HAS_CRC */
+	uint32_t reserved;
+} la_lzip_member;
+
+typedef struct la_lzip_result {
+	uint32_t status;	/* LA_ST_OK or LA_ST_LZIP_* */
+	uint32_t crc32;		/* CRC32 of the out_len bytes (0 for an entry that was refused) */
+	uint64_t out_len;	/* bytes produced */
+	uint64_t consumed;	/* source bytes of the LZMA stream through the marker; what was read so far on a failure */
+	uint64_t valid;		/* = out_len: the bytes in front of a failure are valid */
+} la_lzip_result;
+
+typedef struct la_lzip_batch {
+	const uint8_t        *d_src;
+	uint64_t              src_bytes;
+	const la_lzip_member *d_members;	/* device-resident */
+	uint32_t              n;
+	uint32_t              reserved;	/* 0 */
+	uint8_t              *d_dst;
+	uint64_t              dst_cap;		/* every member's [dst_off, dst_off + dst_cap) lies inside it */
+	la_lzip_result       *d_results;	/* [n] */
+} la_lzip_batch;
+
+uint64_t la_gpu_lzip_workspace_bytes(uint32_t n);
+int      la_gpu_lzip_scan(la_gpu_ctx *ctx, const uint8_t *d_src, uint64_t src_bytes, uint64_t *d_offs, uint32_t cap, uint32_t *d_count);
+int      la_gpu_lzip_decode(la_gpu_ctx *ctx, const la_lzip_batch *batch);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * bzip2 compression -- replaces the BZ2_bzCompress loop of libarchive/archive_write_add_filter_bzip2.c (libbz2 is the

@@ -186,6 +186,7 @@ int    la_bid_gzip_parallel(const unsigned char *p, size_t n, size_t hdr_len, si
 int    la_bid_lz4_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead);
+int    la_bid_lzip_parallel(const unsigned char *p, size_t n, size_t lookahead);
 
 /* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the read filters; the held-back delivery at its
  * end by the bzip2 and xz ones ---- */
@@ -195,7 +196,7 @@ int  la_env_device(void);
 /* One filter's window: its device, its size (read once, at init) and whether upstream has ended */
 typedef struct la_window {
 	la_gpu_ctx *gpu;
-	const char *name;		/* "lz4", "gzip", "zstd", "bzip2", "xz": in the error strings */
+	const char *name;		/* "lz4", "gzip", "zstd", "bzip2", "xz", "lzip": in the error strings */
 	size_t      batch_bytes;	/* compressed bytes of the next window: min(16 MiB, target), then ramped */
 	size_t      target_bytes;	/* LA_GPU_BATCH_MIB, default 64 */
 	size_t      max_batch_bytes;	/* LA_GPU_MAX_BATCH_MIB, default 2048: how far a window may widen */
@@ -245,7 +246,7 @@ void la_verdict_set(la_verdict *v, int rc, const char *fmt, ...);
 /* sets the message, if any, and returns rc */
 int  la_verdict_report(struct archive_read_filter *self, const la_verdict *v);
 
-/* Decoded bytes held back in front of a possible error (the bzip2 and xz filters).  The reference hands out whole
+/* Decoded bytes held back in front of a possible error (the bzip2, xz and lzip filters).  The reference hands out whole
  * blocks of LA_OUT_BLOCK bytes and loses the partial block on an error, so with T bytes decoded everything up to the
  * last block boundary strictly below T is safe to hand out; the rest (at most one block) waits for the next window's
  * verdict.  Each filter's head comment derives T and which of its errors is early or late. */
@@ -256,6 +257,7 @@ typedef struct la_holdback {
 	uint64_t total, delivered;		/* T (the window adds to it), bytes handed out */
 	la_verdict verdict; uint64_t end_limit; int ended;	/* the stream's end is known: reported once end_limit bytes are out */
 	int      finished;
+	uint64_t base;				/* where the grid of output blocks starts: 0, or the last la_holdback_rebase */
 } la_holdback;
 enum {
 	LA_HB_EARLY,	/* the error arrives in the call that emitted byte T: floor((T-1)/64Ki)*64Ki bytes go out, 0 for T = 0 */
@@ -266,6 +268,10 @@ int     la_holdback_open(la_holdback *h);	/* the tail block; -1: no memory */
 /* The stream ends here, T being h->total: rc and msg (NULL: none) are reported behind the bytes `how` lets out.  A
  * later call replaces an earlier one. */
 void    la_holdback_end(la_holdback *h, int rc, const char *msg, int how);
+/* The reference's output block starts afresh here, T being h->total (the lzip filter, at every member's confirmed end:
+ * xz.c:693-734 hands out the partial block there).  All T bytes may go out; the early / late arithmetic counts from
+ * here on.  A filter that never calls it keeps one grid from byte 0. */
+void    la_holdback_rebase(la_holdback *h);
 /* The filter's read(): hands out what may go, then the verdict once, then 0; runs window(self) -- which appends to
  * `out`, adds to `total` and may call la_holdback_end -- whenever it needs more.  A window that does not return
  * ARCHIVE_OK has set its error: that code is returned and the read is over. */

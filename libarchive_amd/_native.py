@@ -138,6 +138,20 @@ class _XzcBatchC(C.Structure):      # la_xzc_batch
 LA_XZC_FIRST = 1
 LA_XZC_BLOCK_BYTES, LA_XZC_CHUNK_BYTES = 1 << 20, 1 << 16
 
+# lzip (la_lzip_member, la_lzip_result, la_lzip_batch)
+LZIP_MEMBER_DTYPE = np.dtype([("src_off", "<u8"), ("src_end", "<u8"), ("data_size", "<u8"), ("dst_off", "<u8"), ("dst_cap", "<u8"),
+                              ("dict_size", "<u4"), ("crc32", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+LZIP_RESULT_DTYPE = np.dtype([("status", "<u4"), ("crc32", "<u4"), ("out_len", "<u8"), ("consumed", "<u8"), ("valid", "<u8")])
+LA_LZIP_UNKNOWN = 0xFFFFFFFFFFFFFFFF
+LA_LZIP_HAS_CRC = 1
+(LA_ST_LZIP_DATA, LA_ST_LZIP_SRC_END, LA_ST_LZIP_TRUNCATED, LA_ST_LZIP_EARLY_END, LA_ST_LZIP_SIZE_OVER, LA_ST_LZIP_OUT_FULL,
+ LA_ST_LZIP_BAD_SIZE, LA_ST_LZIP_BAD_CRC, LA_ST_LZIP_REFUSED) = 32, 33, 34, 35, 36, 37, 38, 39, 40
+
+
+class _LzipBatchC(C.Structure):     # la_lzip_batch
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("d_members", C.c_void_p), ("n", C.c_uint32),
+                ("reserved", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
+
 
 class _Bz2StateC(C.Structure):
     _fields_ = [("open", C.c_uint32), ("level", C.c_uint32), ("crc", C.c_uint32), ("stop", C.c_uint32),
@@ -278,6 +292,10 @@ def gpu_lib():
         lib.la_gpu_xz_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_xz_workspace_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_xz_compress.argtypes = [C.c_void_p, C.POINTER(_XzcBatchC)]
+        lib.la_gpu_lzip_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.la_gpu_lzip_decode.argtypes = [C.c_void_p, C.POINTER(_LzipBatchC)]
+        lib.la_gpu_lzip_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_lzip_workspace_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_xz_compress_block_bytes.restype = C.c_uint64
         lib.la_gpu_xz_compress_block_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_xz_compress_workspace_bytes.restype = C.c_uint64
@@ -521,6 +539,12 @@ class GpuContext:
 
     def xz_compress(self, batch: _XzcBatchC):
         self._check(gpu_lib().la_gpu_xz_compress(self._h, C.byref(batch)), "la_gpu_xz_compress")
+
+    def lzip_scan(self, d_src_ptr, src_bytes, d_offs_ptr, cap, d_count_ptr):
+        self._check(gpu_lib().la_gpu_lzip_scan(self._h, d_src_ptr, src_bytes, d_offs_ptr, cap, d_count_ptr), "la_gpu_lzip_scan")
+
+    def lzip_decode(self, batch: _LzipBatchC):
+        self._check(gpu_lib().la_gpu_lzip_decode(self._h, C.byref(batch)), "la_gpu_lzip_decode")
 
     def gzip_decode(self, batch: _GzBatchC):
         self._check(gpu_lib().la_gpu_gzip_decode(self._h, C.byref(batch)), "la_gpu_gzip_decode")

@@ -570,6 +570,45 @@ int la_gpu_xz_decode(la_gpu_ctx *c, const la_xz_batch *bt)
 	return LA_OK;
 }
 
+uint64_t la_gpu_lzip_workspace_bytes(uint32_t n)
+{
+	return la_lzip_workspace_bytes(n);
+}
+
+int la_gpu_lzip_scan(la_gpu_ctx *c, const uint8_t *d_src, uint64_t src_bytes, uint64_t *d_offs, uint32_t cap, uint32_t *d_count)
+{
+	if (!c || !d_count || (src_bytes && !d_src) || (cap && !d_offs) || src_bytes >= ((uint64_t)1 << 35))
+		return LA_ERR_ARG;
+	const uint64_t need = la_lzip_scan_ws_bytes(src_bytes);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	prof_range(c, "lzip_scan", c->stream, [&] {
+		la_launch_lzip_scan(c->stream, d_src, src_bytes, d_offs, cap, d_count, (uint8_t *)c->ws);
+	});
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
+int la_gpu_lzip_decode(la_gpu_ctx *c, const la_lzip_batch *bt)
+{
+	if (!c || !bt || bt->reserved)
+		return LA_ERR_ARG;
+	if (bt->n && (!bt->d_members || !bt->d_results || !bt->d_dst || (bt->src_bytes && !bt->d_src)))
+		return LA_ERR_ARG;
+	const uint64_t need = la_lzip_workspace_bytes(bt->n);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	prof_range(c, "lzip_decode", c->stream, [&] { la_launch_lzip_decode(c->stream, bt, (uint8_t *)c->ws); });
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 /* workspace of a gzip batch on the lane kernels: their scratch, then (two phases) E and the SEG launch's list; returns its size */
 static uint64_t gz_ws_carve(uint8_t *base, uint32_t n, bool two_phase, la_inflate_emit *E, uint32_t **big)
 {

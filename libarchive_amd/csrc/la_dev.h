@@ -568,6 +568,12 @@ void la_launch_bzip2_verify(hipStream_t s, const la_bz2_batch *bt, uint8_t *ws);
 uint64_t la_xz_workspace_bytes(uint32_t n);
 void la_launch_xz_decode(hipStream_t s, const la_xz_batch *bt, uint8_t *ws);
 void la_launch_xz_verify(hipStream_t s, const la_xz_batch *bt, uint8_t *ws);
+/* la_lzip.hip */
+uint64_t la_lzip_scan_ws_bytes(uint64_t src_bytes);
+void la_launch_lzip_scan(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint64_t *d_offs, uint32_t cap, uint32_t *d_count,
+    uint8_t *ws);
+uint64_t la_lzip_workspace_bytes(uint32_t n);
+void la_launch_lzip_decode(hipStream_t s, const la_lzip_batch *bt, uint8_t *ws);
 /* la_xz_filters.hip: the chains behind d_blocks[n] (LA_XZ_BATCH_CHAINS) undone over the decoded bytes; jobs_ws is
  * la_launch_xz_decode's workspace, ws a 256-byte aligned scratch of la_xz_unfilter_ws_bytes() of its own */
 uint64_t la_xz_unfilter_ws_bytes(uint32_t n, uint64_t dst_cap);

@@ -98,12 +98,19 @@ LA_XZ_FN uint32_t la_xz_props(la_xz_lzma *s, uint32_t byte)
 		if (code < bd_) { range = bd_; probs[i_] = (uint16_t)(pr_ + ((2048u - pr_) >> 5)); bit = 0; } \
 		else { range -= bd_; code -= bd_; probs[i_] = (uint16_t)(pr_ - (pr_ >> 5)); bit = 1; } } } while (0)
 
-/* One LZMA chunk: src[*pp, lim) into dst[*ppos, stop), stop <= chunk_out_end.  chunk_end is the chunk's last compressed
- * byte + 1; lim = min(chunk_end, what the source holds) and lim_status is what asking for src[lim] means.  Returns
- * LA_ST_OK with *ppos == stop: the chunk is complete and checked when stop == chunk_out_end, otherwise the output limit
- * cut it.  The last dictionary reset lies at dst[dict_start]. */
-LA_XZ_FN uint32_t la_xz_lzma_chunk(la_xz_lzma *s, uint16_t *probs, const uint8_t *src, uint64_t *pp, uint64_t lim, uint64_t chunk_end,
-    uint32_t lim_status, uint8_t *dst, uint64_t *ppos, uint64_t stop, uint64_t chunk_out_end, uint64_t dict_start, uint32_t dict_cap)
+/* The LZMA symbol loop, stated once for its two callers: an LZMA2 chunk (la_xz_lzma_chunk below, marker == 0) and an
+ * lzip member (la_lzip_dev.h, marker == 1).  src[*pp, lim) into dst[*ppos, stop); lim_status is what asking for src[lim]
+ * means.  The last dictionary reset lies at dst[dict_start].
+ *   marker == 0: the chunk's ends are known.  stop <= chunk_out_end; chunk_end is the chunk's last compressed byte + 1.
+ * Returns LA_ST_OK with *ppos == stop: the chunk is complete and checked when stop == chunk_out_end, otherwise the output
+ * limit cut it.  The end-of-payload marker is refused as the distance it is.
+ *   marker == 1: neither end is known (chunk_end and chunk_out_end are not read).  The stream goes on until the
+ * end-of-payload marker: behind it liblzma normalises once more and asks for code == 0 (else LA_ST_XZ_DATA); then
+ * *ended = 1 and *pp stands behind the marker.  A symbol that does not fit in front of `stop` is over_status (a match is
+ * copied up to stop first); nothing is decoded behind the marker. */
+LA_XZ_FN uint32_t la_xz_lzma_run(la_xz_lzma *s, uint16_t *probs, const uint8_t *src, uint64_t *pp, uint64_t lim, uint64_t chunk_end,
+    uint32_t lim_status, uint8_t *dst, uint64_t *ppos, uint64_t stop, uint64_t chunk_out_end, uint64_t dict_start, uint32_t dict_cap,
+    const int marker, uint32_t over_status, uint32_t *ended)
 {
 	uint64_t p = *pp, pos = *ppos;
 	uint32_t range = 0xFFFFFFFFu, code = 0, st = LA_ST_OK;
@@ -115,11 +122,12 @@ LA_XZ_FN uint32_t la_xz_lzma_chunk(la_xz_lzma *s, uint16_t *probs, const uint8_t
 		code = (code << 8) | src[p];
 		p++;
 	}
-	while (pos < stop) {
+	while (marker || pos < stop) {
 		const uint32_t pos_state = (uint32_t)pos & pb_mask;
 		uint32_t bit;
 		LA_XZ_BIT(LA_XZ_P_IS_MATCH + state * 16u + pos_state, bit);
 		if (bit == 0) {
+			if (marker && pos >= stop) { st = over_status; goto out; }
 			const uint32_t prev = pos == dict_start ? 0u : dst[pos - 1];
 			const uint32_t lit = LA_XZ_P_LITERAL + 768u * ((((uint32_t)pos & lp_mask) << lc) + (prev >> (8u - lc)));
 			uint32_t sym = 1;
@@ -156,6 +164,7 @@ LA_XZ_FN uint32_t la_xz_lzma_chunk(la_xz_lzma *s, uint16_t *probs, const uint8_t
 				LA_XZ_BIT(LA_XZ_P_IS_REP0_LONG + state * 16u + pos_state, bit);
 				if (bit == 0) {
 					if (rep0 >= avail) { st = LA_ST_XZ_LZMA; goto out; }
+					if (marker && pos >= stop) { st = over_status; goto out; }
 					dst[pos] = dst[pos - rep0 - 1];
 					pos++;
 					state = state < 7u ? 9u : 11u;
@@ -240,6 +249,14 @@ LA_XZ_FN uint32_t la_xz_lzma_chunk(la_xz_lzma *s, uint16_t *probs, const uint8_t
 				}
 			}
 		}
+		if (marker && lenp == LA_XZ_P_LEN && rep0 == 0xFFFFFFFFu) {	/* the end-of-payload marker, whatever its length */
+			LA_XZ_NORM();
+			if (code != 0)
+				st = LA_ST_XZ_DATA;
+			else
+				*ended = 1;
+			goto out;
+		}
 		if (rep0 >= avail) { st = LA_ST_XZ_LZMA; goto out; }
 		{
 			const uint64_t room = stop - pos;
@@ -249,13 +266,15 @@ LA_XZ_FN uint32_t la_xz_lzma_chunk(la_xz_lzma *s, uint16_t *probs, const uint8_t
 				dst[pos + i] = dst[from + i];
 			pos += n;
 			if (n < len) {	/* the output ends inside the match */
-				if (stop == chunk_out_end)
+				if (marker)
+					st = over_status;
+				else if (stop == chunk_out_end)
 					st = LA_ST_XZ_DATA;
 				goto out;
 			}
 		}
 	}
-	if (pos == chunk_out_end) {
+	if (!marker && pos == chunk_out_end) {
 		LA_XZ_NORM();
 		if (code != 0 || p != chunk_end)
 			st = LA_ST_XZ_DATA;
@@ -264,6 +283,14 @@ out:
 	s->state = state; s->rep0 = rep0; s->rep1 = rep1; s->rep2 = rep2; s->rep3 = rep3;
 	*pp = p; *ppos = pos;
 	return st;
+}
+
+/* One LZMA chunk of an LZMA2 block: see la_xz_lzma_run, marker == 0 */
+LA_XZ_FN uint32_t la_xz_lzma_chunk(la_xz_lzma *s, uint16_t *probs, const uint8_t *src, uint64_t *pp, uint64_t lim, uint64_t chunk_end,
+    uint32_t lim_status, uint8_t *dst, uint64_t *ppos, uint64_t stop, uint64_t chunk_out_end, uint64_t dict_start, uint32_t dict_cap)
+{
+	return la_xz_lzma_run(s, probs, src, pp, lim, chunk_end, lim_status, dst, ppos, stop, chunk_out_end, dict_start, dict_cap, 0, LA_ST_OK,
+	    (uint32_t *)0);
 }
 
 #ifndef LA_XZ_COPY

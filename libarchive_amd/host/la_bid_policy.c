@@ -1,7 +1,7 @@
 /*
  * la_bid_policy.c -- the host code the read filters (la_filter_lz4.c, la_filter_gzip.c, la_filter_zstd.c,
- * la_filter_bzip2.c, la_filter_xz.c) share: the bid policy, below it the window plumbing, and at the end the held-back
- * delivery of the bzip2 and xz filters.
+ * la_filter_bzip2.c, la_filter_xz.c, la_filter_lzip.c) share: the bid policy, below it the window plumbing, and at the end
+ * the held-back delivery of the bzip2, xz and lzip filters.
  *
  * Bid policy: should the GPU filter take this stream at all?
  *
@@ -17,6 +17,8 @@
  *   - evidence of many units inside the look-ahead (a BGZF size subfield, a second member header, a frame that
  *     ends inside it): taken;
  *   - otherwise the first unit is larger than the look-ahead: declined (bid 0).
+ * An .lz stream (la_filter_lzip.c) is taken when the look-ahead shows a second member header that the member size in
+ * front of it confirms: a first member longer than the look-ahead is one serial chain.
  * An .xz stream (la_filter_xz.c) is taken when its first block header carries a compressed size (xz -T, pixz: the
  * host hops from header to header); a block without one is a serial chain of unknown extent.
  * LA_ZSTD_BLOCKS=1 makes one long zstd frame a parallel unit (its blocks), and the zstd bidder takes it.
@@ -185,6 +187,29 @@ int la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead)
 	if (n < lookahead || n < 14)
 		return 1;
 	return p[12] == 0 || (p[13] & 0x40) != 0;
+}
+
+/* lzip: 1 = take it: the look-ahead holds the whole stream, or it shows a confirmed second member -- the first header
+ * shape at an offset o whose preceding 8 bytes, the member size of a version 1 trailer, say o (la_filter_lzip.c chains
+ * members by the same rule).  A first member longer than the look-ahead is one serial chain. */
+int la_bid_lzip_parallel(const unsigned char *p, size_t n, size_t lookahead)
+{
+	if (n < lookahead)
+		return 1;
+	for (size_t o = 6 + 5 + 20; o + 6 <= n; o++) {
+		const unsigned char *q = memchr(p + o, 'L', n - 6 - o + 1);
+		if (q == NULL)
+			break;
+		o = (size_t)(q - p);
+		if (memcmp(q, "LZIP", 4) != 0 || q[4] > 1 || (q[5] & 31) < 12 || (q[5] & 31) > 29)
+			continue;
+		uint64_t msize = 0;
+		for (unsigned k = 0; k < 8; k++)
+			msize |= (uint64_t)(q - 8)[k] << (8 * k);
+		if (msize == o)
+			return 1;
+	}
+	return 0;
 }
 
 /*
@@ -394,13 +419,19 @@ void la_holdback_end(la_holdback *h, int rc, const char *msg, int how)
 	else
 		la_verdict_set(&h->verdict, rc, NULL);
 	h->ended = 1;
-	h->end_limit = how == LA_HB_ALL ? h->total : block_floor(how == LA_HB_EARLY && h->total ? h->total - 1 : h->total);
+	const uint64_t t = h->total - h->base;	/* (base is 0 unless the filter moved it: la_holdback_rebase) */
+	h->end_limit = how == LA_HB_ALL ? h->total : h->base + block_floor(how == LA_HB_EARLY && t ? t - 1 : t);
+}
+
+void la_holdback_rebase(la_holdback *h)
+{
+	h->base = h->total;
 }
 
 /* bytes that may be handed out: while the stream goes on, whatever follows is at best an early error */
 static uint64_t holdback_limit(const la_holdback *h)
 {
-	return h->ended ? h->end_limit : block_floor(h->total ? h->total - 1 : 0);
+	return h->ended ? h->end_limit : h->base + block_floor(h->total > h->base ? h->total - h->base - 1 : 0);
 }
 
 ssize_t la_holdback_read(struct archive_read_filter *self, const la_window *w, la_holdback *h, const void **p,

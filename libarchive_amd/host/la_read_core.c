@@ -130,6 +130,7 @@ int archive_read_support_filter_none(struct archive *a) { (void)a; return ARCHIV
  * out (the CPU mocks of the tests) still load: the reference is weak, and a filter that is not linked is not registered. */
 extern int archive_read_support_filter_bzip2(struct archive *) __attribute__((weak));
 extern int archive_read_support_filter_xz(struct archive *) __attribute__((weak));	/* la_filter_xz.c, the same way */
+extern int archive_read_support_filter_lzip(struct archive *) __attribute__((weak));	/* la_filter_lzip.c */
 
 int archive_read_support_filter_all(struct archive *a)
 {
@@ -141,6 +142,8 @@ int archive_read_support_filter_all(struct archive *a)
 		archive_read_support_filter_bzip2(a);
 	if (archive_read_support_filter_xz)
 		archive_read_support_filter_xz(a);
+	if (archive_read_support_filter_lzip)
+		archive_read_support_filter_lzip(a);
 	archive_clear_error(a);
 	return ARCHIVE_OK;
 }
