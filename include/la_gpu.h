@@ -892,6 +892,36 @@ uint64_t la_gpu_xz_compress_workspace_bytes(uint64_t src_bytes);
 uint64_t la_gpu_xz_compress_bound(uint64_t src_bytes, uint32_t level);
 int      la_gpu_xz_compress(la_gpu_ctx *ctx, const la_xzc_batch *batch);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * lzip compression -- replaces the lzma_code loop of libarchive/archive_write_add_filter_xz.c for its lzip filter
+ * (liblzma's raw LZMA1 encoder is the reference's external dependency for this codec).  d_src[0, src_bytes) is cut every
+ * la_gpu_lzip_compress_member_bytes(level) input bytes: 64 KiB at levels 0..6 (dictionary byte 0x10), 256 KiB at levels
+ * 7..9 (0x12).  Every cut is one complete MEMBER: "LZIP", version 1, the dictionary byte; one raw LZMA1 stream (lc 3,
+ * lp 0, pb 2) that ends with the end marker; CRC32, data size and member size.  The members are written back to back into
+ * d_out, which is a whole lzip stream (the shape plzip writes) and may be followed by the next call's; src_bytes == 0
+ * writes one member of no data.  The member is the parallel unit and is coded without knowing its neighbours; within a
+ * level group every level writes the same bytes.  csrc/la_lzip_enc_dev.h states the rules.
+ * lzip has no uncompressed member, so la_gpu_lzip_compress_bound() is arithmetic from the coder's worst case and not from
+ * a stored fallback: 7 * m + 64 stream bytes and 26 of framing per member of m input bytes, about SEVEN times the input
+ * (measured expansion on noise: 1.4 %).  The workspace is one slot of that size per member, so workspace and d_out are
+ * about 448 MiB each for a 64 MiB window.  *d_out_bytes is the size needed; nothing is written at or behind out_cap.
+ * The bytes are not liblzma's; every conforming reader returns the input.  src_bytes is at most LA_LZC_MAX_SRC_BYTES;
+ * level is 0..9 and flags 0, anything else is LA_ERR_ARG.  Additions under ABI version 3. */
+#define LA_LZC_MAX_SRC_BYTES ((uint64_t)1 << 30)
+typedef struct la_lzc_batch {
+	const uint8_t *d_src;
+	uint64_t       src_bytes;
+	uint32_t       level;	/* 0..9 */
+	uint32_t       flags;	/* 0 */
+	uint8_t       *d_out;
+	uint64_t       out_cap;
+	uint64_t      *d_out_bytes;
+} la_lzc_batch;
+uint64_t la_gpu_lzip_compress_member_bytes(uint32_t level);	/* 0 for a level above 9 */
+uint64_t la_gpu_lzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t level);	/* 0 above the limit or for a level above 9 */
+uint64_t la_gpu_lzip_compress_bound(uint64_t src_bytes, uint32_t level);	/* 0 for a level above 9 */
+int      la_gpu_lzip_compress(la_gpu_ctx *ctx, const la_lzc_batch *batch);
+
 #ifdef __cplusplus
 }
 #endif

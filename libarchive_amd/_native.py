@@ -153,6 +153,11 @@ class _LzipBatchC(C.Structure):     # la_lzip_batch
                 ("reserved", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
 
 
+class _LzcBatchC(C.Structure):      # la_lzc_batch
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("level", C.c_uint32), ("flags", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
+
+
 class _Bz2StateC(C.Structure):
     _fields_ = [("open", C.c_uint32), ("level", C.c_uint32), ("crc", C.c_uint32), ("stop", C.c_uint32),
                 ("start_bit", C.c_uint64), ("total_out", C.c_uint64), ("n_taken", C.c_uint32), ("stop_entry", C.c_uint32),
@@ -292,6 +297,13 @@ def gpu_lib():
         lib.la_gpu_xz_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_xz_workspace_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_xz_compress.argtypes = [C.c_void_p, C.POINTER(_XzcBatchC)]
+        lib.la_gpu_lzip_compress.argtypes = [C.c_void_p, C.POINTER(_LzcBatchC)]
+        lib.la_gpu_lzip_compress_member_bytes.restype = C.c_uint64
+        lib.la_gpu_lzip_compress_member_bytes.argtypes = [C.c_uint32]
+        lib.la_gpu_lzip_compress_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_lzip_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        lib.la_gpu_lzip_compress_bound.restype = C.c_uint64
+        lib.la_gpu_lzip_compress_bound.argtypes = [C.c_uint64, C.c_uint32]
         lib.la_gpu_lzip_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.la_gpu_lzip_decode.argtypes = [C.c_void_p, C.POINTER(_LzipBatchC)]
         lib.la_gpu_lzip_workspace_bytes.restype = C.c_uint64
@@ -545,6 +557,9 @@ class GpuContext:
 
     def lzip_decode(self, batch: _LzipBatchC):
         self._check(gpu_lib().la_gpu_lzip_decode(self._h, C.byref(batch)), "la_gpu_lzip_decode")
+
+    def lzip_compress(self, batch: _LzcBatchC):
+        self._check(gpu_lib().la_gpu_lzip_compress(self._h, C.byref(batch)), "la_gpu_lzip_compress")
 
     def gzip_decode(self, batch: _GzBatchC):
         self._check(gpu_lib().la_gpu_gzip_decode(self._h, C.byref(batch)), "la_gpu_gzip_decode")

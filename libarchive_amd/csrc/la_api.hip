@@ -1011,4 +1011,29 @@ int la_gpu_xz_compress(la_gpu_ctx *c, const la_xzc_batch *bt)
 	});
 }
 
+uint64_t la_gpu_lzip_compress_member_bytes(uint32_t level)
+{
+	return level <= 9u ? la_lzip_compress_member_bytes(level) : 0u;
+}
+uint64_t la_gpu_lzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t level)
+{
+	return level <= 9u && src_bytes <= LA_LZC_MAX_SRC_BYTES ? la_lzip_compress_ws_bytes(src_bytes, level) : 0u;
+}
+uint64_t la_gpu_lzip_compress_bound(uint64_t src_bytes, uint32_t level)
+{
+	return level <= 9u ? la_lzip_compress_bound(src_bytes, level) : 0u;
+}
+int la_gpu_lzip_compress(la_gpu_ctx *c, const la_lzc_batch *bt)
+{
+	if (!c || !bt || !bt->d_out_bytes || (bt->src_bytes && !bt->d_src) || (bt->out_cap && !bt->d_out))
+		return LA_ERR_ARG;
+	if (bt->level > 9u || bt->flags != 0u || bt->src_bytes > LA_LZC_MAX_SRC_BYTES)
+		return LA_ERR_ARG;
+	return compress_run(c, la_lzip_compress_ws_bytes(bt->src_bytes, bt->level), "lzip_compress", [&](uint8_t *ws) {
+		bz2c_prof pr = { c, -1 };
+		const la_stage_hook hook = { bz2c_mark, &pr };
+		la_launch_lzip_compress(c->stream, bt, ws, &hook);
+	});
+}
+
 } /* extern "C" */

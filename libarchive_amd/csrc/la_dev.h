@@ -593,6 +593,12 @@ uint64_t la_xz_compress_ws_bytes(uint64_t src_bytes);
 uint64_t la_xz_compress_bound(uint64_t src_bytes);
 void la_launch_xz_compress(hipStream_t s, const la_xzc_batch *bt, uint8_t *ws, const la_stage_hook *hook);
 
+/* la_lzip_comp.hip */
+uint32_t la_lzip_compress_member_bytes(uint32_t level);
+uint64_t la_lzip_compress_ws_bytes(uint64_t src_bytes, uint32_t level);
+uint64_t la_lzip_compress_bound(uint64_t src_bytes, uint32_t level);
+void la_launch_lzip_compress(hipStream_t s, const la_lzc_batch *bt, uint8_t *ws, const la_stage_hook *hook);
+
 /* la_lz4_comp.hip */
 void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);

@@ -16,7 +16,8 @@
  * sizes (zero padding up to the declared size keeps the header's length fixed), one LZMA2 filter, dictionary 1 MiB.  The
  * body is chunks of LA_XZC_CHUNK_BYTES of input, the end marker, zero padding to four bytes, CRC64.
  *
- * One chunk (la_xzc_chunk), three phases per step of 64 positions:
+ * One chunk (la_xzc_chunk: la_xzc_chain_init, la_xzc_chain_steps, then LZMA2's own tail), three phases per step of 64
+ * positions:
  *   MATCH    every lane hashes the four bytes at its position, reads the table's candidate, then (behind LA_XZC_SYNC)
  *            enters its own position and extends the candidate.  Matches end at or before the chunk's end.  Levels 0..3
  *            start from an empty table; levels 4..9 first enter the up to 64 KiB of the same block in front of the chunk,
@@ -395,20 +396,17 @@ LA_XZ_FN uint32_t la_xzc_hash(uint32_t v)
 	return (v * 2654435761u) >> (32u - LA_XZC_HASH_BITS);
 }
 
-/* One chunk: blk[cs, ce) of the block that starts at blk (ce - cs <= LA_XZC_CHUNK_BYTES, ce <= the block's bytes) into
- * slot[0, LA_XZC_SLOT_BYTES): the six header bytes and the payload.  probs holds LA_XZC_PROBS entries, tab LA_XZC_TAB,
- * m_len and m_cand 64 each (the kernel keeps all four in LDS).  Returns the payload's bytes, or 0: the chunk is stored
- * and the slot's content means nothing. */
-LA_XZ_FN uint32_t la_xzc_chunk(const uint8_t *blk, uint32_t cs, uint32_t ce, uint32_t level, uint16_t *probs, uint32_t *tab, uint32_t *m_len,
-    uint32_t *m_cand, uint8_t *slot)
+/* ---- one chain: la_xzc_chunk below and la_lzc_member (la_lzip_enc_dev.h) are callers of the same two pieces ---- */
+
+/* The chain's start: a fresh range coder that stores into out[0, lim) and counts beyond, state and reps, the model and
+ * the match table reset; then the table is warmed with blk[lo, cs), nothing emitted (lo == cs: no warm-up).  The table
+ * holds position + 1, 0 for none. */
+LA_XZ_FN void la_xzc_chain_init(la_xzc_enc *e, const uint8_t *blk, uint32_t lo, uint32_t cs, uint32_t ce, uint16_t *probs, uint32_t *tab,
+    uint8_t *out, uint32_t lim)
 {
-	const uint32_t n = ce - cs;
-	/* the lowest position a distance may reach */
-	const uint32_t lo = level < LA_XZC_WARM_LEVEL ? cs : cs > LA_XZC_CHUNK_BYTES ? cs - LA_XZC_CHUNK_BYTES : 0u;
-	la_xzc_enc e;
-	e.rc.low = 0; e.rc.range = 0xFFFFFFFFu; e.rc.cache = 0; e.rc.cache_size = 1;
-	e.rc.pos = 0; e.rc.lim = n - 1u; e.rc.out = slot + 6;
-	e.state = 0; e.rep0 = e.rep1 = e.rep2 = e.rep3 = 0;
+	e->rc.low = 0; e->rc.range = 0xFFFFFFFFu; e->rc.cache = 0; e->rc.cache_size = 1;
+	e->rc.pos = 0; e->rc.lim = lim; e->rc.out = out;
+	e->state = 0; e->rep0 = e->rep1 = e->rep2 = e->rep3 = 0;
 	LA_XZC_LANE_LOOP(l) {
 		for (uint32_t i = l; i < LA_XZC_PROBS; i += 64u)
 			probs[i] = 1024;
@@ -416,13 +414,20 @@ LA_XZ_FN uint32_t la_xzc_chunk(const uint8_t *blk, uint32_t cs, uint32_t ce, uin
 			tab[i] = 0;
 	}
 	LA_XZC_SYNC();
-	/* the table holds position + 1, 0 for none: warmed with the bytes in front of the chunk, nothing emitted */
 	LA_XZC_LANE_LOOP(l) {
 		for (uint32_t p = lo + l; p < cs && p + 4u <= ce; p += 64u)
 			LA_XZC_TAB_MAX(&tab[la_xzc_hash(la_xzc_ld4(blk + p))], p + 1u);
 	}
+}
+
+/* The steps of 64 positions over blk[cs, ce): MATCH, SYMBOLS, CODE.  lo is the lowest position a distance may reach;
+ * pos_state and the literal's previous byte come from the position behind blk.  The walk ends early once more than
+ * `stop` bytes are out (a caller with a stored form gives up there; 0xFFFFFFFF: never). */
+LA_XZ_FN void la_xzc_chain_steps(la_xzc_enc *e, const uint8_t *blk, uint32_t lo, uint32_t cs, uint32_t ce, uint32_t stop, uint16_t *probs,
+    uint32_t *tab, uint32_t *m_len, uint32_t *m_cand)
+{
 	uint32_t base = cs, anchor = cs;
-	while (base < ce && e.rc.pos <= e.rc.lim) {
+	while (base < ce && e->rc.pos <= stop) {
 		/* MATCH: all reads of the table, then all writes */
 		LA_XZC_SYNC();
 		LA_XZC_LANE_LOOP(l) {
@@ -449,7 +454,7 @@ LA_XZ_FN uint32_t la_xzc_chunk(const uint8_t *blk, uint32_t cs, uint32_t ce, uin
 		/* SYMBOLS and CODE: the step's positions in order, the same values in every lane */
 		const uint32_t end = base + 64u < ce ? base + 64u : ce;
 		uint32_t p = anchor > base ? anchor : base;
-		while (p < end && e.rc.pos <= e.rc.lim) {
+		while (p < end && e->rc.pos <= stop) {
 			const uint32_t f = p - base;
 			uint32_t len = m_len[f];
 			const uint32_t dist = len ? p - m_cand[f] : 0u;	/* distance - 1: the table holds position + 1 */
@@ -458,26 +463,41 @@ LA_XZ_FN uint32_t la_xzc_chunk(const uint8_t *blk, uint32_t cs, uint32_t ce, uin
 			if (len) {
 				if (m_cand[f] <= cs)
 					LA_XZC_EVENT(LA_XZC_EV_ACROSS_CHUNKS);
-				la_xzc_match_any(&e, probs, p, len, dist);
+				la_xzc_match_any(e, probs, p, len, dist);
 				p += len;
-			} else if (p - lo > e.rep0 && blk[p - e.rep0 - 1u] == blk[p]) {
-				const uint8_t *q = blk + p - e.rep0 - 1u;
+			} else if (p - lo > e->rep0 && blk[p - e->rep0 - 1u] == blk[p]) {
+				const uint8_t *q = blk + p - e->rep0 - 1u;
 				uint32_t rl = 1;
 				while (rl < 273u && p + rl < ce && q[rl] == blk[p + rl])
 					rl++;
 				if (rl >= 2u)
-					la_xzc_rep(&e, probs, p, rl, 0);
+					la_xzc_rep(e, probs, p, rl, 0);
 				else
-					la_xzc_short_rep(&e, probs, p);
+					la_xzc_short_rep(e, probs, p);
 				p += rl;
 			} else {
-				la_xzc_literal(&e, probs, blk, p);
+				la_xzc_literal(e, probs, blk, p);
 				p++;
 			}
 		}
 		anchor = p;
 		base = base + 64u > anchor ? base + 64u : anchor;
 	}
+}
+
+/* One chunk: blk[cs, ce) of the block that starts at blk (ce - cs <= LA_XZC_CHUNK_BYTES, ce <= the block's bytes) into
+ * slot[0, LA_XZC_SLOT_BYTES): the six header bytes and the payload.  probs holds LA_XZC_PROBS entries, tab LA_XZC_TAB,
+ * m_len and m_cand 64 each (the kernel keeps all four in LDS).  Returns the payload's bytes, or 0: the chunk is stored
+ * and the slot's content means nothing.  What is LZMA2's own is here: five flush bytes, the stored decision, the header. */
+LA_XZ_FN uint32_t la_xzc_chunk(const uint8_t *blk, uint32_t cs, uint32_t ce, uint32_t level, uint16_t *probs, uint32_t *tab, uint32_t *m_len,
+    uint32_t *m_cand, uint8_t *slot)
+{
+	const uint32_t n = ce - cs;
+	/* the lowest position a distance may reach */
+	const uint32_t lo = level < LA_XZC_WARM_LEVEL ? cs : cs > LA_XZC_CHUNK_BYTES ? cs - LA_XZC_CHUNK_BYTES : 0u;
+	la_xzc_enc e;
+	la_xzc_chain_init(&e, blk, lo, cs, ce, probs, tab, slot + 6, n - 1u);
+	la_xzc_chain_steps(&e, blk, lo, cs, ce, e.rc.lim, probs, tab, m_len, m_cand);
 	for (int i = 0; i < 5; i++)
 		la_xzc_rc_shift(&e.rc);
 	if (e.rc.pos > e.rc.lim) {

@@ -17,8 +17,7 @@
  *   - the index is kept on the host: the patch hook walks the block headers of the bytes that came back and appends
  *     (unpadded size, uncompressed size) to a list; close() writes index and footer from it;
  *   - an archive without data is the 32-byte stream without a block, written without a device call;
- *   - lzma-alone and lzip write filters, which the reference serves from the same file, are not built (lzip is READ:
- *     la_filter_lzip.c).
+ *   - the lzip write filter, which the reference serves from the same file, is la_write_lzip.c.
  */
 #include <errno.h>
 #include <stdint.h>

@@ -1,6 +1,6 @@
-"""Device-resident lzip member scan and decode through the C ABI (harness for tests / tools).  Plumbing only: torch
-allocates the HBM buffers; the member table is the caller's (members are chained on the host, host/la_filter_lzip.c),
-all work is la_gpu_lzip_scan() and la_gpu_lzip_decode()."""
+"""Device-resident lzip member scan, decode and compression through the C ABI (harness for tests / tools).  Plumbing
+only: torch allocates the HBM buffers; the member table is the caller's (members are chained on the host,
+host/la_filter_lzip.c), all work is la_gpu_lzip_scan(), la_gpu_lzip_decode() and la_gpu_lzip_compress()."""
 import numpy as np
 
 from . import _native as N
@@ -17,6 +17,39 @@ def dict_size(b):
     if (b & 0x1F) > 12:
         size -= (size // 16) * (b >> 5)
     return size
+
+
+def member_bytes(level=6):
+    """input bytes per member at `level` (0 above 9)"""
+    return int(N.gpu_lib().la_gpu_lzip_compress_member_bytes(level))
+
+
+def compress_bound(n, level=6):
+    return int(N.gpu_lib().la_gpu_lzip_compress_bound(n, level))
+
+
+def compress_window(ctx, d_plain, level=6, out_cap=None, d_out=None):
+    """Device lzip compression of one window (la_gpu_lzip_compress): d_plain is a 1-D uint8 CUDA tensor; returns a uint8
+    CUDA tensor holding the window's members back to back, a whole lzip stream.  With `out_cap` (and optionally `d_out`)
+    the call gets that much room only and the needed size is returned beside the tensor."""
+    import torch
+    n = int(d_plain.numel())
+    dev = d_plain.device
+    cap = compress_bound(n, level) if out_cap is None else int(out_cap)
+    if d_out is None:
+        d_out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+    d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    b = N._LzcBatchC()
+    b.d_src, b.src_bytes = (d_plain.data_ptr() if n else None), n
+    b.level, b.flags = level, 0
+    b.d_out, b.out_cap, b.d_out_bytes = d_out.data_ptr(), cap, d_len.data_ptr()
+    ctx.lzip_compress(b)
+    ctx.sync()
+    total = int(d_len.cpu()[0])
+    if out_cap is not None:
+        return d_out, total
+    assert total <= cap, (total, cap)
+    return d_out[:total]
 
 
 def to_device(image):
