@@ -220,6 +220,10 @@ typedef struct la_batch_summary {
 					 * behind it; no per-sequence flags, no polling in the match phase); same results, kept as the
 					 * cross-check of the default kernel (la_lz4_fast.hip), which is still the faster one */
 
+#define LA_LZ4_OPT_SEARCH_IN_EXPAND 16u	/* the default LDS-window kernel finds what each match has to wait for by itself, in
+					 * front of its match phase, as it did before the dependency kernel (la_lz4_deps.hip) took
+					 * that search out of it; same results, kept as the cross-check of the dependency words */
+
 typedef struct la_lz4_batch {
 	const uint8_t      *d_src;	/* compressed image (or batch window) in HBM */
 	uint64_t            src_bytes;
@@ -249,6 +253,17 @@ typedef struct la_lz4_batch {
 uint64_t la_gpu_lz4_workspace_bytes(uint32_t n_blocks, uint64_t src_bytes);
 
 int la_gpu_lz4_decode(la_gpu_ctx *ctx, const la_lz4_batch *batch);
+
+/* Debugging aid: after la_gpu_lz4_decode(ctx, batch) and before the next call on ctx, copies the sequence-table
+ * entries of block `block` (lit_src | lit_len << 16 | dst << 32 | off << 48) and the dependency words the dependency
+ * kernel wrote for them (first sequence to wait for | number of sequences << 16) to the host, `cap` of each at most.
+ * Synchronises.  Returns the block's sequence count (0: the block has no table), or LA_ERR_ARG when that decode
+ * computed no words (LA_LZ4_OPT_GENERAL_ONLY, _SEARCH_IN_EXPAND, _EXPAND_INORDER).  The words mean something only for a
+ * block the LDS-window kernel took in one piece: not stored, not failed, at most 4096 sequences, not routed to the general
+ * kernel for its long sequences; the others' are never written.  A word that waits for too little shows in the
+ * decoded bytes only as a race; here it can be compared with the rule. */
+int la_gpu_lz4_debug_deps(la_gpu_ctx *ctx, const la_lz4_batch *batch, uint32_t block, uint64_t *seq_out,
+    uint32_t *deps_out, uint32_t cap);
 
 /* =====================================================================
  * gzip / DEFLATE -- replaces the inflate() loop of gzip_filter_read

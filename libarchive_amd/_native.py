@@ -33,6 +33,7 @@ assert HASH_JOB_DTYPE.itemsize == 16 and SUMMARY_DTYPE.itemsize == 32
 LA_LZ4B_STORED, LA_LZ4B_CHECKSUM, LA_LZ4B_DEPENDENT, LA_LZ4B_FIRST = 1, 2, 4, 8
 LA_LZ4F_CONTENT_SUM, LA_LZ4F_HEADER_SUM, LA_LZ4F_CONT, LA_LZ4F_OPEN, LA_LZ4F_HASHED = 1, 2, 4, 8, 16
 LA_LZ4_OPT_GENERAL_ONLY, LA_LZ4_OPT_NO_VERIFY, LA_LZ4_OPT_PARSE_V1, LA_LZ4_OPT_EXPAND_INORDER = 1, 2, 4, 8
+LA_LZ4_OPT_SEARCH_IN_EXPAND = 16
 LA_GPU_ABI_VERSION = 3
 LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED, LA_ST_GZ_OUT_FULL, LA_ST_GZ_NO_TRAILER = 0, 5, 6, 9, 10
 LA_ST_GZ_PIECE_END, LA_ST_GZ_NEEDS_HISTORY = 18, 19     # LA_GZ_OPT_PIECES only
@@ -269,6 +270,8 @@ def gpu_lib():
         lib.la_gpu_lz4_workspace_bytes.argtypes = [C.c_uint32, C.c_uint64]
         lib.la_gpu_lz4_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_lz4_decode.argtypes = [C.c_void_p, C.POINTER(_Lz4BatchC)]
+        lib.la_gpu_lz4_debug_deps.argtypes = [C.c_void_p, C.POINTER(_Lz4BatchC), C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_uint32]
         lib.la_gpu_lz4_compress.argtypes = [C.c_void_p, C.POINTER(_Lz4cBatchC)]
         lib.la_gpu_gzip_compress.argtypes = [C.c_void_p, C.POINTER(_GzcBatchC)]
         lib.la_gpu_gzip_compress_bound.restype = C.c_uint64
@@ -520,6 +523,15 @@ class GpuContext:
 
     def lz4_decode(self, batch: _Lz4BatchC):
         self._check(gpu_lib().la_gpu_lz4_decode(self._h, C.byref(batch)), "la_gpu_lz4_decode")
+
+    def lz4_debug_deps(self, batch: _Lz4BatchC, block: int, cap: int = 4096):
+        """(table entries as uint64, dependency words as uint32) of one block of the decode that just ran with `batch`;
+        cut to the block's sequence count, at most cap (la_gpu_lz4_debug_deps)."""
+        seq, deps = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
+        n = gpu_lib().la_gpu_lz4_debug_deps(self._h, C.byref(batch), block, seq.ctypes.data, deps.ctypes.data, cap)
+        if n < 0:
+            self._check(n, "la_gpu_lz4_debug_deps")
+        return seq[:min(n, cap)], deps[:min(n, cap)]
 
     def lz4_compress(self, batch: _Lz4cBatchC):
         self._check(gpu_lib().la_gpu_lz4_compress(self._h, C.byref(batch)), "la_gpu_lz4_compress")

@@ -24,6 +24,11 @@ struct la_gpu_ctx {
 	hipEvent_t mark;
 	void *ws;
 	uint64_t ws_bytes;
+	/* dependency words of the lz4 window blocks (la_lz4_deps.hip), one per sequence-table slot: a buffer of its
+	 * own beside the workspace, grown by the decode that needs it (la_gpu_lz4_workspace_bytes is a recorded
+	 * public figure and keeps describing ws alone) */
+	uint32_t *lz4_deps;
+	uint64_t lz4_deps_cap;	/* words */
 	/* second stream + events: block checksums / parse of later slices run beside the
 	 * expand kernels of earlier ones */
 	hipStream_t aux_stream;
@@ -123,6 +128,7 @@ void la_gpu_close(la_gpu_ctx *c)
 	(void)hipSetDevice(c->device);
 	(void)hipStreamSynchronize(c->stream);
 	if (c->ws) (void)hipFree(c->ws);
+	if (c->lz4_deps) (void)hipFree(c->lz4_deps);
 	(void)hipEventDestroy(c->ev0);
 	(void)hipEventDestroy(c->ev1);
 	(void)hipEventDestroy(c->mark);
@@ -337,6 +343,30 @@ uint64_t la_gpu_lz4_workspace_bytes(uint32_t n_blocks, uint64_t src_bytes)
 	return w.total;
 }
 
+/* Room for one dependency word per table slot (4 B beside the slot's 8: on the 16 GiB bench shape the table is
+ * 20 GB and the words 10 GB; a filter's 64 MiB window asks for 90 MB).  Grown like the workspace, never shrunk. */
+static int lz4_deps_reserve(la_gpu_ctx *c, uint64_t words)
+{
+	if (words <= c->lz4_deps_cap)
+		return LA_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->aux_stream));
+	if (c->lz4_deps) { HIPCHK(c, hipFree(c->lz4_deps)); c->lz4_deps = NULL; c->lz4_deps_cap = 0; }
+	words = (words + 0x3FFFFull) & ~0x3FFFFull;
+	HIPCHK(c, hipMalloc((void **)&c->lz4_deps, words * sizeof(uint32_t)));
+	c->lz4_deps_cap = words;
+	return LA_OK;
+}
+
+/* does a decode of this batch hand the polling kernel dependency words?  (not without tables, not under the
+ * cross-check option, not when the in-order kernel expands) */
+static bool lz4_uses_deps(const la_lz4_batch *bt)
+{
+	return !(bt->options & (LA_LZ4_OPT_GENERAL_ONLY | LA_LZ4_OPT_SEARCH_IN_EXPAND)) && bt->n_blocks &&
+	    ((bt->options & LA_LZ4_OPT_EXPAND_INORDER) == 0 || !la_lz4_expand_inorder_takes(bt->src_bytes));
+}
+
 int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 {
 	if (!c || !bt)
@@ -358,13 +388,19 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 		if (rc != LA_OK) return rc;
 	}
 	lz4_ws_carve(&w, (uint8_t *)c->ws, bt->n_blocks, bt->src_bytes, fast);
+	const bool with_deps = lz4_uses_deps(bt);
+	if (with_deps) {
+		int rc = lz4_deps_reserve(c, w.table_cap);
+		if (rc != LA_OK) return rc;
+	}
 	hipStream_t sx = c->stream;		/* main stream (the caller's): checksums, expand, summary */
 	hipStream_t sp = c->aux_stream;		/* second stream: parse beside the block checksums, frame
 						 * checksums beside the expand kernel */
 	const uint32_t n = bt->n_blocks;
 	const la_expand_job xj = {	/* every expand launch below is this job, or a slice of it */ bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_dst, bt->dst_cap, bt->d_dst_off,
 	    bt->d_out_len, bt->d_block_status, w.nseq, fast ? w.table : NULL, w.table_off,
-	    LA_LZ4_LONG_SEQ_BYTES };	/* blocks of few long sequences go to the general kernel (la_dev.h) */
+	    LA_LZ4_LONG_SEQ_BYTES,	/* blocks of few long sequences go to the general kernel (la_dev.h) */
+	    with_deps ? c->lz4_deps : NULL };
 
 	prof_begin(c);
 	/* the second stream starts after whatever the caller queued on its stream */
@@ -405,6 +441,13 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 
 	HIPCHK(c, hipStreamWaitEvent(sx, c->slice_ev[0], 0));
 	prof_range(c, "scan", sx, [&] { la_launch_scan_u32(sx, bt->d_out_len, n, bt->d_dst_off, w.scan); });
+	/* what each match of a window block waits for, once over the whole table, at eight workgroups per CU (the
+	 * window kernel, at two, used to search for it).  In front of the slices, not beside them: with slice i + 1's
+	 * share on the second stream beside expand slice i the step took 25.48 ms against 25.37 (three runs each,
+	 * profiles/r25_lz4_deps.md) -- two window workgroups leave 3 KiB of a CU's LDS, so the dependency kernel only
+	 * ever gets in where an expand workgroup has just left */
+	if (with_deps)
+		prof_range(c, "lz4_deps", sx, [&] { la_launch_lz4_deps(sx, xj, c->lz4_deps); });
 
 	/* blocks the LDS-window kernel does not take (any size, stored, chains of dependent
 	 * blocks) first, over the whole table; then the LDS-window kernel in slices, each
@@ -446,6 +489,35 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 		});
 	HIPCHK(c, hipGetLastError());
 	return LA_OK;
+}
+
+int la_gpu_lz4_debug_deps(la_gpu_ctx *c, const la_lz4_batch *bt, uint32_t block, uint64_t *seq_out, uint32_t *deps_out,
+    uint32_t cap)
+{
+	if (!c || !bt || block >= bt->n_blocks || (cap && (!seq_out || !deps_out)) || !lz4_uses_deps(bt))
+		return LA_ERR_ARG;
+	/* the layout the decode carved: the same call on the same shape */
+	lz4_ws w;
+	lz4_ws_carve(&w, (uint8_t *)c->ws, bt->n_blocks, bt->src_bytes, true);
+	if (!c->ws || w.total > c->ws_bytes || w.table_cap > c->lz4_deps_cap)
+		return LA_ERR_ARG;
+	uint32_t ns = 0;
+	uint64_t toff = 0;
+	HIPCHK(c, hipMemcpyAsync(&ns, w.nseq + block, sizeof(ns), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(&toff, w.table_off + block, sizeof(toff), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (ns == 0xFFFFFFFFu)
+		return 0;
+	if (ns > 0x7FFFFFFFu || toff > w.table_cap || ns > w.table_cap - toff)
+		return LA_ERR_ARG;
+	const uint32_t m = ns < cap ? ns : cap;
+	if (m) {
+		static_assert(sizeof(la_lz4_seq) == sizeof(uint64_t), "a table entry travels as one 64-bit value");
+		HIPCHK(c, hipMemcpyAsync(seq_out, w.table + toff, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipMemcpyAsync(deps_out, c->lz4_deps + toff, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+	}
+	return (int)ns;
 }
 
 uint64_t la_gpu_zstd_workspace_bytes(uint32_t n_frames)

@@ -494,6 +494,33 @@ __host__ __device__ __forceinline__ la_expand_route la_lz4_route(const la_lz4_bl
 	return nseq <= LA_LZ4_FAST_MAXSEQ ? LA_XR_WINDOW : LA_XR_WINDOW_SEG;
 }
 
+/* What a match of the LDS-window kernel has to wait for: THE place where that is decided.  Literals are all in the window
+ * before the first match is copied, so sequence k (output position d, match at mdst = d + lit_len, offset off, mlen match
+ * bytes) waits only for earlier MATCHES under its source.  The source is the span min(mlen, off) from mdst - off (an
+ * overlapping match reads its own bytes behind that), clipped below d: from d on the bytes are the sequence's own.
+ * la_lz4_dep_source: false when nothing in front of the sequence is read (empty match, or a source inside its own literals);
+ * else *hi_byte is the last byte that is.  With q the last sequence that starts at or before the source and qe the last
+ * one that starts at or before hi_byte, the wait is for the matches of q .. qe, and la_lz4_dep_drops_last says that qe
+ * falls out again: a sequence is literals first and match second, so a source that ends before qe's match start
+ * (last_mstart = its d + lit_len) touches its literals only.  The word handed to the poll loop is q | count << 16.
+ * Asked by the dependency kernel (la_lz4_deps.hip) and by the search inside lz4_expand_fast_kernel. */
+__device__ __forceinline__ bool la_lz4_dep_source(uint32_t d, uint32_t mdst, uint32_t off, uint32_t mlen, uint32_t *hi_byte)
+{
+	const uint32_t s0 = mdst - off;
+	if (mlen == 0 || s0 >= d)
+		return false;
+	const uint32_t span = mlen < off ? mlen : off;
+	uint32_t hi = s0 + span - 1;
+	if (hi >= d)
+		hi = d - 1;
+	*hi_byte = hi;
+	return true;
+}
+__device__ __forceinline__ bool la_lz4_dep_drops_last(uint32_t hi_byte, uint32_t last_mstart)
+{
+	return hi_byte < last_mstart;
+}
+
 /* One expand step over a table of blocks: what every expand launch is given.  Host side only: the launchers unpack
  * it into their kernels' (restrict-qualified) arguments. */
 struct la_expand_job {
@@ -510,12 +537,14 @@ struct la_expand_job {
 	const la_lz4_seq *table;	/* NULL: no sequence tables, the general kernel takes every block */
 	const uint64_t *table_off;
 	uint32_t long_thr;		/* la_lz4_long_sequences */
+	const uint32_t *deps;		/* one word per table entry, written by la_launch_lz4_deps for the LA_XR_WINDOW blocks
+					 * (la_lz4_dep_source); NULL: the window kernel searches for itself */
 
-	/* blocks first .. first + count - 1: the per-block arrays move; image, slab and table (absolute offsets) stay */
+	/* blocks first .. first + count - 1: the per-block arrays move; image, slab, table and deps (absolute offsets) stay */
 	la_expand_job slice(uint32_t first, uint32_t count) const
 	{
 		return la_expand_job{ src, src_bytes, blocks + first, count, dst, dst_cap, dst_off + first, out_len + first,
-		    status + first, nseq + first, table, table_off + first, long_thr };
+		    status + first, nseq + first, table, table_off + first, long_thr, deps };
 	}
 };
 
@@ -533,6 +562,9 @@ void la_launch_lz4_parse_staged(hipStream_t s, const uint8_t *d_src, uint64_t sr
 void la_launch_lz4_expand_general(hipStream_t s, const la_expand_job &j, uint32_t hist_len);
 void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j);
 void la_launch_lz4_expand_fast_big(hipStream_t s, const la_expand_job &j, uint32_t *d_big /* n + 1 words */);
+/* la_lz4_deps.hip: the dependency words of the job's LA_XR_WINDOW blocks, for a later la_launch_lz4_expand_fast whose
+ * job carries d_deps (same table offsets) */
+void la_launch_lz4_deps(hipStream_t s, const la_expand_job &j, uint32_t *d_deps);
 
 /* la_lz4_inorder.hip: the in-order expand step, run on request as the cross-check of the polling kernel (in-order
  * matcher wave + literal wave + flush wave per 64 KiB LDS window); the same contract, blocks of any sequence count

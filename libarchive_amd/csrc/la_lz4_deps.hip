@@ -1,0 +1,158 @@
+/*
+ * la_lz4_deps.hip -- what every match of an LDS-window block has to wait for, found ahead of the
+ * window kernel (la_lz4_fast.hip) in a kernel of its own.
+ *
+ * The window kernel holds one block per workgroup in a 64 KiB window, two workgroups per CU, and
+ * used to open its match phase with a search: for every sequence the earlier sequences under its
+ * match source (chunk map, two walks over the output positions, one look at the last touched
+ * sequence's table entry in global memory).  That search needs no payload and no window, only the
+ * block's sequence table, and it was paid at the worst occupancy on the chip.  Here it runs with
+ * 20 KiB of LDS per workgroup, eight workgroups per CU:
+ *
+ *   pass 1   the block's table entries, all loads of a thread in flight together and the entries
+ *            kept in registers: output position and match start (dst + lit_len) go to LDS
+ *   pass 2   the chunk map: for every 32-byte chunk of the output the sequence that holds the
+ *            chunk's first byte (from the output positions in LDS)
+ *   pass 3   per sequence: the source's last byte by la_lz4_dep_source (la_dev.h), the map
+ *            entries under the source's first and last byte, two short walks forward to q and
+ *            to the last sequence under the source, that sequence's match start from LDS (la_lz4_dep_drops_last), and the
+ *            word  q | count << 16  to deps[table_off + k]
+ *
+ * The word is the one the window kernel's own search hands its poll loop (same rule, same
+ * functions), so the kernel given the words (DEPS = true) skips the search and nothing else
+ * changes.  A word that waited for too little would show in the decoded bytes only as a race:
+ * la_gpu_lz4_debug_deps fetches the words, tests/test_gpu_lz4_deps.py compares them with the rule.
+ *
+ * Blocks: exactly those la_lz4_route sends to LA_XR_WINDOW (asked with the window kernel's
+ * arguments); stored, failed, general and segmented blocks are left alone -- the segmented launch
+ * numbers its sequences per segment and keeps its own search.  Every loop is bounded by the
+ * block's sequence count or its chunk count; nothing here waits for another thread.
+ *
+ * Every index is inside its array whatever the table holds: positions are 16-bit, so a map index
+ * is below 2048; q and qe stay below k < ns <= LA_LZ4_FAST_MAXSEQ; deps is written at
+ * table_off + k with k < ns, inside the block's table slot.
+ */
+#include "la_dev.h"
+
+#define DEPS_THREADS 256
+#define DEPS_SLOTS   (LA_LZ4_FAST_MAXSEQ / DEPS_THREADS)	/* sequences per thread */
+
+__global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_block *__restrict__ blocks, uint32_t n,
+    uint64_t dst_cap, const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ out_len,
+    const uint32_t *__restrict__ status, const uint32_t *__restrict__ nseq, const la_lz4_seq *__restrict__ table,
+    const uint64_t *__restrict__ table_off, uint32_t long_thr, uint32_t *__restrict__ deps)
+{
+	__shared__ uint16_t dstpos[LA_LZ4_FAST_MAXSEQ];		/* output position per sequence (20 KiB in all: eight workgroups per CU) */
+	__shared__ uint16_t mstart[LA_LZ4_FAST_MAXSEQ];		/* dst + lit_len: where the sequence's match starts */
+	__shared__ uint16_t cmap[2048];				/* per 32-byte output chunk: the sequence that holds its first byte */
+
+	const uint32_t bi = blockIdx.x;
+	if (bi >= n)
+		return;
+	const uint32_t olen = out_len[bi], ns = nseq[bi];
+	if (la_lz4_route(blocks[bi], status[bi], olen, ns, dst_off[bi], dst_cap, true, long_thr) != LA_XR_WINDOW)
+		return;
+	const uint32_t tid = threadIdx.x;
+	const uint64_t *const tab = (const uint64_t *)(const void *)(table + table_off[bi]);	/* lit_src | lit_len << 16 | dst << 32 | off << 48 */
+	uint32_t *const out = deps + table_off[bi];
+
+	/* the thread's entries (sequences tid, tid + 256, ...), all requested before the first one is used and kept in
+	 * registers for pass 3: the table is read from memory once, with one latency and not one per 256 sequences */
+	uint64_t ent[DEPS_SLOTS];
+#pragma unroll
+	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
+		const uint32_t k = r * DEPS_THREADS + tid;
+		ent[r] = k < ns ? tab[k] : 0;
+	}
+#pragma unroll
+	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
+		if (r * DEPS_THREADS >= ns)
+			break;
+		const uint32_t k = r * DEPS_THREADS + tid;
+		if (k < ns) {
+			const uint32_t d = (uint32_t)(ent[r] >> 32) & 0xFFFFu;
+			dstpos[k] = (uint16_t)d;
+			mstart[k] = (uint16_t)(d + ((uint32_t)(ent[r] >> 16) & 0xFFFFu));	/* (65536 reads 0: only behind a last, empty sequence, which nobody waits for) */
+		}
+	}
+	__syncthreads();
+	/* pass 2.  Where sequence k's match ends is the next sequence's position, the block's end behind the last one
+	 * (positions are 16-bit: an end at 65536 reads 0).  It replaces lit_src in the entry's low 16 bits, which
+	 * nothing here reads: pass 3 has the match length without another look at LDS. */
+#pragma unroll
+	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
+		if (r * DEPS_THREADS >= ns)
+			break;
+		const uint32_t k = r * DEPS_THREADS + tid;
+		const uint32_t after = k + 1 < ns ? (uint32_t)dstpos[k + 1] : (olen & 0xFFFFu);
+		ent[r] = (ent[r] & ~0xFFFFull) | after;
+	}
+#pragma unroll
+	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
+		if (r * DEPS_THREADS >= ns)
+			break;
+		const uint32_t k = r * DEPS_THREADS + tid;
+		if (k < ns) {
+			const uint32_t d = (uint32_t)(ent[r] >> 32) & 0xFFFFu;
+			uint32_t nxt = (uint32_t)ent[r] & 0xFFFFu;
+			if (nxt < d)
+				nxt = 65536u;
+			if (k == 0)
+				for (uint32_t c = 0; (c << 5) < d; c++)
+					cmap[c] = 0;
+			for (uint32_t c = (d + 31) >> 5; (c << 5) < nxt; c++)
+				cmap[c] = (uint16_t)k;
+		}
+	}
+	__syncthreads();
+
+	/* pass 3.  q is the largest index below k whose sequence starts at or before the source's first byte, qe the
+	 * same for its last byte (la_lz4_dep_source).  Both start from the map -- the sequence that holds the first
+	 * byte of the 32-byte chunk -- and walk up; a chunk holds at most eight sequence starts.  One sequence and
+	 * one walk at a time: the kernel is bound by instruction issue, not by the LDS round trips (eight waves per
+	 * SIMD cover those), and a loop over several sequences at once runs as long as the longest walk of all of them. */
+#pragma unroll
+	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
+		if (r * DEPS_THREADS >= ns)
+			break;
+		const uint32_t k = r * DEPS_THREADS + tid;
+		const uint64_t e = ent[r];
+		const uint32_t d = (uint32_t)(e >> 32) & 0xFFFFu, mdst = d + ((uint32_t)(e >> 16) & 0xFFFFu), off = (uint32_t)(e >> 48);
+		const bool valid = k > 0 && k < ns;	/* (sequence 0 waits for nobody: its word is 0) */
+		const uint32_t mlen = valid ? (((uint32_t)e & 0xFFFFu) - mdst) & 0xFFFFu : 0;
+		const uint32_t s0 = mdst - off;
+		uint32_t hi = 0;
+		const bool waits = valid && la_lz4_dep_source(d, mdst, off, mlen, &hi) && dstpos[0] <= hi;
+		const uint32_t kq = valid ? k : 0, ke = waits ? k : 0;	/* the walks' bounds: 0 stops them at once */
+		uint32_t q = 0;
+		if (valid) {
+			const uint32_t q0 = cmap[(s0 < 65535u ? s0 : 65535u) >> 5];
+			q = q0 < k - 1 ? q0 : k - 1;
+		}
+		uint32_t qe = q;
+		if (waits) {	/* hi < d <= 65535: inside the map, and at or behind s0 */
+			const uint32_t e0 = cmap[hi >> 5];
+			const uint32_t e1 = e0 < k - 1 ? e0 : k - 1;
+			qe = e1 > q ? e1 : q;
+		}
+		while (q + 1 < kq && dstpos[q + 1] <= s0)
+			q++;
+		if (qe < q)
+			qe = q;
+		while (qe + 1 < ke && dstpos[qe + 1] <= hi)
+			qe++;
+		if (k < ns) {
+			uint32_t cnt = 0;
+			if (waits)
+				cnt = qe - q + 1 - (la_lz4_dep_drops_last(hi, mstart[qe]) ? 1u : 0u);
+			out[k] = q | (cnt << 16);
+		}
+	}
+}
+
+void la_launch_lz4_deps(hipStream_t s, const la_expand_job &j, uint32_t *d_deps)
+{
+	if (j.n == 0) return;
+	hipLaunchKernelGGL(lz4_deps_kernel, dim3(j.n), dim3(DEPS_THREADS), 0, s, j.blocks, j.n, j.dst_cap, j.dst_off,
+	    j.out_len, j.status, j.nseq, j.table, j.table_off, j.long_thr, d_deps);
+}

@@ -78,6 +78,14 @@
  * -3 %; expand 5.34 -> 5.18 ms per C2 launch, 25.7 -> 24.7 ms for gzip C3.  The per-slot register picks were
  * already outside the loop (hoisted by the compiler), so the iteration did not halve: a level's time is the
  * LDS round trips in series, not issue.  s_sleep 0 instead of 1: no change beyond noise.
+ *
+ * The search out of the kernel (profiles/r25_lz4_deps.md): which earlier matches a match waits for -- the chunk
+ * map over the output, the two walks, the look at the last touched sequence's entry in global memory, 16.6 k of a
+ * block's 95 k cycles here at two blocks per CU -- needs only the sequence table.  The lz4 path now finds it in
+ * la_lz4_deps.hip at eight workgroups per CU and hands this kernel one word per sequence (DEPS = true): the four C2
+ * launches 20.8 -> 18.0 ms, the dependency kernel 1.9 ms in front of them.  The rule itself is la_lz4_dep_source /
+ * la_lz4_dep_drops_last (la_dev.h), asked by both.  DEPS = false is the kernel as it was: the segmented launch, the
+ * deflate front end (inflate_expand) and LA_LZ4_OPT_SEARCH_IN_EXPAND run it.
  */
 #include "la_dev.h"
 
@@ -142,15 +150,20 @@ __device__ __forceinline__ seq_t seq_load(const la_lz4_seq *t, uint32_t k)
 /* SEG = false: one workgroup per block of the table, blocks of at most MAXSEQ sequences (the
  * usual case).  SEG = true: the workgroups share out the few blocks with MORE sequences, listed
  * by lz4_classify_kernel, and run them in segments of MAXSEQ sequences. */
-template <uint32_t MAXSEQ, bool SEG>
+/* DEPS = true: every sequence's dependency word comes from the dependency kernel (la_lz4_deps.hip, one word per table
+ * entry) and the search in front of the match phase is compiled out; DEPS = false: the kernel searches for itself
+ * (the segmented launch, whose sequence numbers are segment-local, the deflate front end, and the cross-check
+ * LA_LZ4_OPT_SEARCH_IN_EXPAND). */
+template <uint32_t MAXSEQ, bool SEG, bool DEPS>
 __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_kernel(
     const uint8_t *__restrict__ src, uint64_t src_bytes, const la_lz4_block *__restrict__ blocks,
     uint32_t n, uint8_t *__restrict__ dst, uint64_t dst_cap, const uint64_t *__restrict__ dst_off,
     const uint32_t *__restrict__ out_len, uint32_t *status_out,
     const uint32_t *__restrict__ nseq, const la_lz4_seq *__restrict__ table,
     const uint64_t *__restrict__ table_off, const uint32_t *__restrict__ big_list,
-    const uint32_t *__restrict__ big_count, uint32_t long_thr)
+    const uint32_t *__restrict__ big_count, uint32_t long_thr, const uint32_t *__restrict__ deps)
 {
+	static_assert(!(SEG && DEPS), "the dependency words number a block's sequences from its first one");
 	const uint32_t *status = status_out;
 	__shared__ __attribute__((aligned(16))) uint8_t win[16 + 65536 + 96];	/* 16 headroom (literal stores may start 3 bytes early) + 16 alignment shift + slack for over-reads */
 	__shared__ uint16_t dstpos[MAXSEQ + 4];
@@ -222,10 +235,12 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	}
 	seq_t ent[MAXSTEPS];
 	uint32_t prev_end[MAXSTEPS];
+	uint32_t dw[MAXSTEPS];	/* DEPS: the dependency word of the slot's sequence (la_lz4_deps.hip), loaded at the end of phase L */
 #pragma unroll
 	for (uint32_t r = 0; r < MAXSTEPS; r++) {
 		ent[r] = 0;
 		prev_end[r] = 0;
+		dw[r] = 0;
 	}
 	/* (slot r holds sequences r * FAST_THREADS and up: slots beyond the segment's last sequence
 	 * are skipped wave-uniformly in every pass below -- the kernel is bound by instruction issue) */
@@ -354,6 +369,16 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 				fin = put(seq_load(tab, k), false);
 		}
 	}
+	/* DEPS: the slots' dependency words are requested here, in front of the barrier that ends phase L: the wait for
+	 * the slowest wave covers their latency.  Requested in the prepass, beside the table entries, they hold eight
+	 * registers through phase L (97 VGPRs instead of 90) and the four C2 launches took 18.4 ms instead of 18.0. */
+	if (DEPS) {
+#pragma unroll
+		for (uint32_t r = 0; r < MAXSTEPS; r++) {
+			const uint32_t k = fast_seq_index(r, wave, lane);
+			dw[r] = (r * FAST_THREADS < ns && k < ns) ? deps[table_off[bi] + k] : 0;
+		}
+	}
 	STAMP(1);
 	__syncthreads();
 	STAMP(2);
@@ -362,6 +387,14 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	 * First every step's dependency range [q, qend] (branch-free binary searches over
 	 * the output positions, interleaved across steps), then the steps in order. */
 	uint32_t qcur[MAXSTEPS];	/* search cursor, then (first dependency | count << 16) */
+	if constexpr (DEPS) {
+#pragma unroll
+		for (uint32_t r = 0; r < MAXSTEPS; r++)
+			qcur[r] = dw[r];
+#ifdef LA_DIAG_M
+		STAMP(6);	/* (no search: stamps 6 and 7 sit right behind the barrier) */
+#endif
+	} else {
 #ifndef FAST_BSEARCH
 	/* The sequence under a source position comes from a MAP, not from a binary search over the output
 	 * positions (twelve dependent LDS reads per sequence: a third of the kernel's LDS cycles, PMC + count
@@ -452,16 +485,12 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 			continue;
 		const uint32_t k = fast_seq_index(r, wave, lane);
 		const uint32_t d = SEQ_DST(ent[r]), mdst = d + SEQ_LIT_LEN(ent[r]), off = SEQ_OFF(ent[r]);
-		const uint32_t s0 = mdst - off;
 		const uint32_t next = k < ns ? dstpos[k + 1] : 0;	/* dstpos[ns] = where the segment's output ends */
 		const uint32_t mlen = k < ns ? (next - mdst) & 0xFFFFu : 0;	/* (positions are 16-bit: an end at 65536 reads 0) */
 		uint32_t cnt = 0;	/* number of earlier sequences (of this segment) to wait for */
+		uint32_t hi_byte = 0;
 		qlh[r] = 0xFFFFFFFFu;
-		if (mlen != 0 && s0 < d) {
-			const uint32_t span = mlen < off ? mlen : off;
-			uint32_t hi_byte = s0 + span - 1;
-			if (hi_byte >= d)
-				hi_byte = d - 1;
+		if (la_lz4_dep_source(d, mdst, off, mlen, &hi_byte)) {
 			/* sources that end before this segment's first output byte need nothing here:
 			 * earlier segments are complete */
 			if (k > 0 && dstpos[0] <= hi_byte) {
@@ -487,9 +516,10 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 			le[r] = qlh[h + r] != 0xFFFFFFFFu ? seq_load(tab, qlh[h + r] & 0xFFFFu) : 0;
 #pragma unroll
 		for (uint32_t r = 0; r < 4; r++)
-			if (qlh[h + r] != 0xFFFFFFFFu && (qlh[h + r] >> 16) < SEQ_DST(le[r]) + SEQ_LIT_LEN(le[r]))
+			if (qlh[h + r] != 0xFFFFFFFFu && la_lz4_dep_drops_last(qlh[h + r] >> 16, SEQ_DST(le[r]) + SEQ_LIT_LEN(le[r])))
 				qcur[h + r] -= 1u << 16;	/* source ends inside the literals of the last sequence: its match is not needed */
 	}
+	}	/* !DEPS */
 
 #ifdef LA_DIAG_M
 	STAMP(7);	/* the last touched sequence's entry looked up (global memory) */
@@ -709,9 +739,14 @@ extern "C" int la_diag_set_stamps(void *d_buf)
 void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j)
 {
 	if (j.n == 0) return;
-	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false>), dim3(j.n), dim3(FAST_THREADS), 0, s,
-	    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
-	    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr);
+	if (j.deps)
+		hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false, true>), dim3(j.n), dim3(FAST_THREADS), 0, s,
+		    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
+		    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr, j.deps);
+	else
+		hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false, false>), dim3(j.n), dim3(FAST_THREADS), 0, s,
+		    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
+		    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr, (const uint32_t *)nullptr);
 }
 
 /* blocks with more than LA_LZ4_FAST_MAXSEQ sequences, over the WHOLE table: classify + a small
@@ -723,7 +758,7 @@ void la_launch_lz4_expand_fast_big(hipStream_t s, const la_expand_job &j, uint32
 	hipLaunchKernelGGL(lz4_classify_kernel, dim3((j.n + 255) / 256), dim3(256), 0, s, j.blocks, j.n, j.status, j.nseq,
 	    d_big + 1, d_big, j.out_len, j.long_thr);
 	const uint32_t grid = j.n < 1024u ? j.n : 1024u;
-	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, true>), dim3(grid), dim3(FAST_THREADS), 0, s,
+	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, true, false>), dim3(grid), dim3(FAST_THREADS), 0, s,
 	    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
-	    j.table, j.table_off, (const uint32_t *)(d_big + 1), (const uint32_t *)d_big, j.long_thr);
+	    j.table, j.table_off, (const uint32_t *)(d_big + 1), (const uint32_t *)d_big, j.long_thr, (const uint32_t *)nullptr);
 }
