@@ -29,6 +29,21 @@
  *             which evens out lanes whose sequences are short or long).
  *   checksum  XXH32 stripes of chunk r, four accumulators per lane, from the same
  *             staged bytes: the image is read from HBM exactly once for both jobs.
+ *   table     a sequence's entry waits in a per-lane LDS stage and leaves in aligned groups,
+ *             all lanes that hold a group together every few trips.  No lane ever waits
+ *             for room in its stage (see PS_STAGE / PS_GROUP / PS_CAD below).
+ *
+ * Where the time goes (16 GiB workload, 4 096 waves, profiles/r26_lz4_parse.md): 4.36 ms as
+ * it was; 4.18 without the checksum stripes, 3.90 without the table, 2.80 without either --
+ * the parts overlap, and at eight waves per CU the walk alone is nowhere near one instruction
+ * per cycle and SIMD.  Measured forms of the stage and the ring, same session, parse alone:
+ *   four entries, a full lane sits out a trip and flushes behind it (as it was)       4.36
+ *   four entries, flushed right behind the commit that fills them                     4.16 - 4.40
+ *   eight entries, groups of four every fourth trip, ring rows masked (kept)          3.96 - 4.05
+ *   eight entries, groups of eight right behind the filling commit                    4.28 - 4.39
+ *   the kept form with rounds of 64 bytes over a ring of four chunks (6 % fewer trips
+ *   in a replay of the loop, a round's fixed cost twice as often)                     +0.48 on it
+ *   the kept form's table stores non-temporal                                         12.9
  *
  * (Tried without effect: branch-free chunk loads -- as written the compiler waits for each
  * 16-byte load right behind it, because the byte-wise image-tail path defines the same
@@ -42,21 +57,28 @@
 
 #define LZ4_MFLIMIT 12
 #define LZ4_LASTLIT 5
+#define PS_DONE_IP  (-256)
 
-/* The kernel's two LDS sizes are template parameters (spelt like the macros derived from them):
+/* The kernel's LDS shape is a set of template parameters (spelt like the macros derived from them):
  *   PS_CH     bytes of every block staged per round (multiple of 16).  Measured on the 16 GiB
  *             workload, whole table in one launch on an empty chip: 32 -> 9.9 ms, 64 -> 6.0,
  *             128 -> 5.2, 256 -> 8.4 (a larger ring lets lanes drift further apart before they
  *             wait for each other, but LDS per wave sets how many waves a CU holds)
- *   PS_STAGE  staged table entries per lane (a power of two; they leave in groups of
- *             min(PS_STAGE, 8))
- * la_launch_lz4_parse_staged() picks the pair by the rounds of waves a launch needs (below). */
+ *   PS_STAGE  staged table entries per lane (a power of two)
+ *   PS_GROUP  entries per store burst: one aligned piece of 8 * PS_GROUP bytes per lane
+ *   PS_CAD    trips between two flushes.  A lane adds one entry per trip at most and keeps fewer
+ *             than PS_GROUP behind a flush, so PS_GROUP - 1 + PS_CAD <= PS_STAGE means that no
+ *             lane is ever full, and PS_CAD <= PS_GROUP that a flush finds one group at most
+ *   PS_WRAP   four more ring rows that repeat rows 0 .. 3, so that only the first row index of a
+ *             read is masked; without them (they do not fit beside an eight-entry stage at eight
+ *             waves per CU) every row index is
+ * la_launch_lz4_parse_staged() picks the shape by the rounds of waves a launch needs (below). */
 #ifndef PS_THREADS
 #define PS_THREADS 64u		/* waves of a workgroup share nothing: the size only sets the LDS granule */
 #endif
 #define PS_WAVES   (PS_THREADS / 64u)
-#define PS_GROUP   (PS_STAGE < 8u ? PS_STAGE : 8u)	/* table entries per store burst */
 #define PS_RINGW   (2u * PS_CH / 4u)	/* ring = two chunks, in dwords (power of two) */
+#define PS_RBMASK  ((PS_RINGW - 1u) << 8)	/* the row bits of a byte address in a wave's ring: row << 8 | lane << 2 */
 #define PS_PIECES  (PS_CH / 16u)	/* 16-byte pieces per chunk = load instructions per round */
 #define PS_BPI     (64u / PS_PIECES)	/* blocks covered by one load instruction */
 
@@ -92,19 +114,24 @@ __device__ __forceinline__ void ps_load_chunk(const uint8_t *__restrict__ src, c
 	}
 }
 
-template <uint32_t PS_CH, uint32_t PS_STAGE, bool EMIT, bool SUMS>
+template <uint32_t PS_CH, uint32_t PS_STAGE, uint32_t PS_GROUP, uint32_t PS_CAD, bool PS_WRAP, bool EMIT, bool SUMS>
 __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint8_t *__restrict__ src,
     uint64_t src_bytes, const la_lz4_block *__restrict__ blocks, uint32_t n,
     uint32_t *__restrict__ out_len, uint32_t *__restrict__ nseq_out, uint32_t *__restrict__ status,
     uint32_t *__restrict__ sum_status, la_lz4_seq *__restrict__ table,
     const uint64_t *__restrict__ table_off, uint64_t table_cap)
 {
-	__shared__ uint32_t ring[PS_WAVES][PS_RINGW + 4u][64];	/* last rows = copies of rows 0..3: up to five consecutive dwords never wrap */
+	/* PS_WRAP: four more rows = copies of rows 0..3, so that up to five consecutive dwords never wrap; without
+	 * them every row index behind the first is masked */
+	__shared__ uint32_t ring[PS_WAVES][PS_RINGW + (PS_WRAP ? 4u : 0u)][64];
 	/* table entries wait here (transposed: conflict free) and leave in groups of PS_GROUP (eight = one
-	 * aligned 64-byte burst per lane, see la_lz4.hip), at the START of a round: the stores
-	 * then have a whole round of LDS-only work to complete in before the wave next waits on
-	 * its memory counter (gfx950 counts loads and stores in one in-order counter, so a store
-	 * issued just before the wait for the next chunk would put its full latency on the path) */
+	 * aligned 64-byte burst per lane, see la_lz4.hip) every PS_CAD trips of the parse loop, whichever
+	 * round those fall in.  (They used to leave at the START of a round, and a lane that filled its stage
+	 * inside a round sat out the next trip and flushed behind it: with four entries a lane idled one
+	 * trip in five, and some lane of the 64 was full on 40 % of all trips.  The start of a round was chosen
+	 * because gfx950 counts loads and stores in one in-order counter, so a store issued just in front of the
+	 * wait for the next chunk puts its latency on the path.  A cadence flush can now fall there; that is
+	 * accepted: the form as a whole is 0.35 ms faster, the placement alone was not measured.) */
 	__shared__ uint64_t stage[PS_STAGE][PS_THREADS];
 
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -156,7 +183,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 			const uint32_t slot_ = k_ * PS_BPI + lane / PS_PIECES;                    \
 			const uint32_t j_ = (((c_) * (PS_CH / 4u)) + 4u * piece) & (PS_RINGW - 1u); \
 			R[j_ + 0][slot_] = fl[k_].x;                                              \
-			if (j_ == 0) {                                                            \
+			if (PS_WRAP && j_ == 0) {                                                 \
 				R[PS_RINGW + 0][slot_] = fl[k_].x;                                \
 				R[PS_RINGW + 1][slot_] = fl[k_].y;                                \
 				R[PS_RINGW + 2][slot_] = fl[k_].z;                                \
@@ -186,10 +213,12 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 	const bool eligible = EMIT && have && la_lz4_fast_eligible(b);
 	const bool emit = eligible && do_parse && table_off[i + 1] <= table_cap;
 	uint64_t *tab = emit ? (uint64_t *)(table + table_off[i]) : nullptr;	/* slot is 64-byte aligned */
-	int ip = 0, op = 0;
 	uint32_t nseq = 0;
 	bool ok = iend > 0;
 	uint32_t done = (!do_parse || !ok) ? 1u : 0u;
+	/* a lane that is through parks its position behind every chunk there can be (staged positions stay below
+	 * 2^31 + PS_CH): the trip loop then needs no look at `done` */
+	int ip = done ? PS_DONE_IP : 0, op = 0;
 	/* checksum state */
 	uint32_t v1 = XXH_P1 + XXH_P2, v2 = XXH_P2, v3 = 0, v4 = 0u - XXH_P1;
 	uint32_t hp = 0;	/* payload offset of the next stripe */
@@ -202,29 +231,36 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 		    ((uint64_t)(uint16_t)(off_) << 48);                                            \
 	} while (0)
 	uint32_t nfl = 0;	/* entries already written to the table (multiple of PS_GROUP) */
-	/* write every complete group of staged entries */
-	auto flush_groups = [&]() {
-		while (__ballot(emit && nseq - nfl >= PS_GROUP) != 0) {
-			if (emit && nseq - nfl >= PS_GROUP) {
-				const uint32_t g = nfl & (PS_STAGE - 1u);	/* a multiple of PS_GROUP */
-				uint4 *o4 = (uint4 *)(tab + nfl);
+	/* write the complete group of staged entries of every lane that has one (never two: see the trip loop) */
+	auto flush_group = [&]() {
+		if (emit && nseq - nfl >= PS_GROUP) {
+			const uint32_t g = nfl & (PS_STAGE - 1u);	/* a multiple of PS_GROUP */
+			uint4 *o4 = (uint4 *)(tab + nfl);
 #pragma unroll
-				for (uint32_t j = 0; j < PS_GROUP / 2u; j++) {
-					const uint64_t a_ = stage[g + 2 * j][threadIdx.x], b_ = stage[g + 2 * j + 1][threadIdx.x];
-					o4[j] = make_uint4((uint32_t)a_, (uint32_t)(a_ >> 32), (uint32_t)b_, (uint32_t)(b_ >> 32));
-				}
-				nfl += PS_GROUP;
+			for (uint32_t j = 0; j < PS_GROUP / 2u; j++) {
+				const uint64_t a_ = stage[g + 2 * j][threadIdx.x], b_ = stage[g + 2 * j + 1][threadIdx.x];
+				o4[j] = make_uint4((uint32_t)a_, (uint32_t)(a_ >> 32), (uint32_t)b_, (uint32_t)(b_ >> 32));
 			}
+			nfl += PS_GROUP;
 		}
 	};
+	uint32_t trip = 0;	/* trips of the parse loop so far, over all rounds */
 
-	uint32_t *const Rw = &R[0][0];	/* row stride 64 dwords; row PS_RINGW repeats row 0 */
+	/* The lane's dword k rows behind the one that holds staged position sp.  Rows are 256 bytes apart; the address
+	 * is put together in bytes (shift, add, and-or), which is two instructions less per read than masking a
+	 * dword index.  With PS_WRAP rows PS_RINGW .. PS_RINGW + 3 repeat rows 0 .. 3 and only the first row is masked. */
+	const uint8_t *const Rb = (const uint8_t *)&R[0][0];
+	const uint32_t lane4 = lane << 2;
+	auto ring_dw = [&](uint32_t sp, uint32_t k) -> uint32_t {
+		const uint32_t a = PS_WRAP ? (((sp << 6) & PS_RBMASK) | lane4) + 256u * k : ((((sp << 6) + 256u * k) & PS_RBMASK) | lane4);
+		return *(const uint32_t *)(Rb + a);
+	};
+	/* the four bytes at staged position sp */
+	auto ring_u32 = [&](uint32_t sp) -> uint32_t { return __builtin_amdgcn_alignbit(ring_dw(sp, 1), ring_dw(sp, 0), sp << 3); };
 	for (uint32_t r = 0; r < nrounds; r++) {
 		const uint32_t base = r * PS_CH;
 		const uint32_t rend = base + PS_CH;
 		const uint32_t se32 = base + 2u * PS_CH;	/* ring holds [base, se32); no wrap: payloads stay below 2^31 */
-		if (EMIT)
-			flush_groups();
 
 		/* one payload byte at offset p >= base: ring, or (length-extension runs and
 		 * literal runs longer than the ring) the image itself */
@@ -303,21 +339,24 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 
 		/* ---- parse: a lane takes one whole sequence per trip while its token is staged
 		 * (it may run up to a chunk ahead); the round lasts until no lane is left inside
-		 * chunk r.  This kernel is bound by instruction issue, so the trip is branch-free
+		 * chunk r.  A wave's time is the length of its trips (at six waves per CU; at eight
+		 * something else binds as well, see the head of the file), so the trip is branch-free
 		 * straight-line code on integer registers for the common sequence (no run of
 		 * length-extension bytes beyond the first, offset staged, not the last of the
 		 * block): two LDS round trips of two dwords each, every rule evaluated as a
-		 * predicate, state committed with selects.  Lanes the predicates turn away take
-		 * the careful step instead. ---- */
+		 * predicate, state committed under one mask.  Lanes the predicates turn away take
+		 * the careful step instead.  What the ISA showed and took out of the trip (62 -> 54
+		 * vector instructions; 1.77 -> 1.63 ms for 1 536 waves of the wide shape): a finished
+		 * lane is parked at PS_DONE_IP instead of being asked `done` twice per trip, the
+		 * staging bounds are compared as se32 - 8 and se32 - 4 (scalars) instead of adding to
+		 * the lane's position, and no ballot stands in front of the careful step (a ballot of
+		 * a compound condition costs a select and a compare). ---- */
 		for (;;) {
-			const bool live = done == 0;
-			if (__ballot(live && (uint32_t)ip + sk < rend) == 0)
-				break;
-			const bool full = EMIT && emit && nseq - nfl >= PS_STAGE;
 			const uint32_t uip = (uint32_t)ip, uop = (uint32_t)op, sip = uip + sk;	/* sip: staged position of the token */
-			const bool act = live && sip + 8u <= se32 && !full;
-			const uint32_t row = (((sip >> 2) & (PS_RINGW - 1u)) << 6) | lane;
-			const uint32_t w0 = __builtin_amdgcn_alignbit(Rw[row + 64], Rw[row], sip << 3);
+			if (__builtin_amdgcn_ballot_w64(sip < rend) == 0)
+				break;
+			const bool act = sip <= se32 - 8u;
+			const uint32_t w0 = ring_u32(sip);
 			const uint32_t nib_l = (w0 >> 4) & 15u, nib_m = w0 & 15u, x1 = (w0 >> 8) & 0xffu;
 			const bool ext1 = nib_l == 15u;
 			const uint32_t ll = nib_l + (ext1 ? x1 : 0u);
@@ -326,8 +365,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 			const uint32_t opl = uop + ll, q = p + ll;
 			const bool lastseq = (int)opl > oend - LZ4_MFLIMIT || (int)q > iend - (2 + 1 + LZ4_LASTLIT);
 			const uint32_t sq = q + sk;
-			const uint32_t row2 = (((sq >> 2) & (PS_RINGW - 1u)) << 6) | lane;
-			const uint32_t o3 = __builtin_amdgcn_alignbit(Rw[row2 + 64], Rw[row2], sq << 3);
+			const uint32_t o3 = ring_u32(sq);
 			const uint32_t off = o3 & 0xffffu, x2 = (o3 >> 16) & 0xffu;
 			const bool ext2 = nib_m == 15u;
 			const uint32_t ml = nib_m + 4u + (ext2 ? x2 : 0u);
@@ -337,22 +375,26 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 			/* offset not staged yet: a lane that runs ahead of the round simply waits for
 			 * the next chunk; one still inside chunk r has a literal run longer than the
 			 * ring and lets the careful step fetch the three bytes from the image */
-			const bool far = sq + 4u > se32;
+			const bool far = sq > se32 - 4u;
 			const bool hold = far && sip >= rend;
 			const bool slow = act && !hold && (s1 || lastseq || far || s2 || bad);
-			const bool commit = act && !hold && !slow;
-			if (EMIT && commit && emit)
-				stage[nseq & (PS_STAGE - 1u)][threadIdx.x] =
-				    (uint64_t)(p | (ll << 16)) | ((uint64_t)(uop | (o3 << 16)) << 32);
-			nseq += commit ? 1u : 0u;
-			op = commit ? (int)(opl + ml) : op;
-			ip = commit ? (int)p2 : ip;
-			if (__ballot(slow || (live && full)) != 0) {
-				if (EMIT && __ballot(live && full) != 0)
-					flush_groups();
-				if (slow)
-					careful_step();
+			if (act && !hold && !slow) {	/* commit */
+				if (EMIT && emit)
+					stage[nseq & (PS_STAGE - 1u)][threadIdx.x] =
+					    (uint64_t)(p | (ll << 16)) | ((uint64_t)(uop | (o3 << 16)) << 32);
+				nseq++;
+				op = (int)(opl + ml);
+				ip = (int)p2;
 			}
+			if (slow) {
+				careful_step();
+				ip = done ? PS_DONE_IP : ip;
+			}
+			/* Every PS_CAD trips the lanes that hold a whole group write it out.  A lane adds one entry per
+			 * trip at most and keeps fewer than PS_GROUP behind a flush, so it never holds more than
+			 * PS_GROUP - 1 + PS_CAD <= PS_STAGE: no lane ever waits for room in its stage. */
+			if (EMIT && ++trip % PS_CAD == 0)
+				flush_group();
 		}
 
 		/* ---- block checksum: the XXH32 stripes that START in chunk r (a stripe is 16 payload
@@ -362,8 +404,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 			for (uint32_t sidx = 0; sidx < PS_PIECES; sidx++) {
 				const uint32_t sp = hp + sk;
 				if (hp + 16u <= b.src_len && sp < rend) {
-					const uint32_t rowh = (((sp >> 2) & (PS_RINGW - 1u)) << 6) | lane;
-					const uint32_t d0 = Rw[rowh], d1 = Rw[rowh + 64], d2 = Rw[rowh + 128], d3 = Rw[rowh + 192], d4 = Rw[rowh + 256];
+					const uint32_t d0 = ring_dw(sp, 0), d1 = ring_dw(sp, 1), d2 = ring_dw(sp, 2), d3 = ring_dw(sp, 3), d4 = ring_dw(sp, 4);
 					const uint32_t sh = sp << 3;
 					v1 = xxh_round(v1, __builtin_amdgcn_alignbit(d1, d0, sh));
 					v2 = xxh_round(v2, __builtin_amdgcn_alignbit(d2, d1, sh));
@@ -379,8 +420,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 				h += b.src_len;
 				uint32_t p = hp;
 				for (; p + 4 <= b.src_len; p += 4) {
-					const uint32_t sp = p + sk, rowh = (((sp >> 2) & (PS_RINGW - 1u)) << 6) | lane;
-					h = rotl32(h + __builtin_amdgcn_alignbit(Rw[rowh + 64], Rw[rowh], sp << 3) * XXH_P3, 17) * XXH_P4;
+					h = rotl32(h + ring_u32(p + sk) * XXH_P3, 17) * XXH_P4;
 				}
 				for (; p < b.src_len; p++) {
 					const uint32_t sp = p + sk;
@@ -417,7 +457,7 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 	if (done == 0)
 		ok = false;	/* cannot happen: every chain ends inside its payload */
 	if (EMIT)
-		flush_groups();
+		flush_group();
 	if (emit && ok)
 		for (uint32_t j = nfl; j < nseq; j++)	/* the last, incomplete group */
 			tab[j] = stage[j & (PS_STAGE - 1u)][threadIdx.x];
@@ -430,34 +470,34 @@ __global__ __launch_bounds__(PS_THREADS) void lz4_parse_staged_kernel(const uint
 		status[i] = LA_ST_LZ4_DECODE;
 }
 
-template <uint32_t PS_CH, uint32_t PS_STAGE>
+template <uint32_t PS_CH, uint32_t PS_STAGE, uint32_t PS_GROUP, uint32_t PS_CAD, bool PS_WRAP>
 static void ps_launch(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_lz4_block *d_blocks, uint32_t n, uint32_t *d_out_len, uint32_t *d_nseq,
     uint32_t *d_status, uint32_t *d_sum_status, la_lz4_seq *d_table, const uint64_t *d_table_off,
     uint64_t table_cap)
 {
-	static_assert(PS_STAGE >= 2u && (PS_STAGE & (PS_STAGE - 1u)) == 0, "table entries leave in pairs at least");
+	static_assert(PS_GROUP >= 2u && (PS_STAGE & (PS_STAGE - 1u)) == 0 && PS_STAGE % PS_GROUP == 0, "table entries leave in pairs at least");
+	static_assert(PS_CAD <= PS_GROUP && PS_GROUP - 1u + PS_CAD <= PS_STAGE, "a lane is never full, and never holds two groups");
 	const dim3 grid((n + PS_THREADS - 1) / PS_THREADS), wg(PS_THREADS);
+#define PS_GO(emit_, sums_) hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, PS_GROUP, PS_CAD, PS_WRAP, emit_, sums_>), \
+	grid, wg, 0, s, d_src, src_bytes, d_blocks, n, d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap)
 	if (d_table && d_sum_status)
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, true, true>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+		PS_GO(true, true);
 	else if (d_table)
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, true, false>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+		PS_GO(true, false);
 	else if (d_sum_status)
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, false, true>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+		PS_GO(false, true);
 	else
-		hipLaunchKernelGGL((lz4_parse_staged_kernel<PS_CH, PS_STAGE, false, false>), grid, wg, 0, s, d_src, src_bytes, d_blocks, n,
-		    d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+		PS_GO(false, false);
+#undef PS_GO
 }
 
 /* Waves the chip holds of the two shapes the launcher knows: LDS per wave (ring + stage) sets how many fit on
  * a CU's 160 KiB, gfx950 has 256 CUs.  A lane walks its whole block, so a launch runs in rounds of that many
  * waves and a round lasts as long as the serial walk of a block whatever the number of waves in it. */
 #define PS_CHIP_CUS       256u
-#define PS_WAVES_WIDE     (PS_CHIP_CUS * 6u)	/* <128, 16>: 25 600 B per wave */
-#define PS_WAVES_NARROW   (PS_CHIP_CUS * 8u)	/* <128, 4>:  19 456 B per wave */
+#define PS_WAVES_WIDE     (PS_CHIP_CUS * 6u)	/* 25 600 B per wave: ring + wrap rows 17 408, stage 8 192 */
+#define PS_WAVES_NARROW   (PS_CHIP_CUS * 8u)	/* 20 480 B per wave: ring 16 384, stage 4 096 */
 
 void la_launch_lz4_parse_staged(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes,
     const la_lz4_block *d_blocks, uint32_t n, uint32_t *d_out_len, uint32_t *d_nseq,
@@ -465,14 +505,16 @@ void la_launch_lz4_parse_staged(hipStream_t s, const uint8_t *d_src, uint64_t sr
     uint64_t table_cap)
 {
 	if (n == 0) return;
-	/* The sixteen-entry stage (two bursts of 64 bytes per lane) is the faster wave; the four-entry one puts
-	 * eight waves on a CU instead of six.  It is taken where that saves a round: the 16 GiB workload's 4 096
-	 * waves are three rounds of 1 536 (the last one two thirds full) or two full rounds of 2 048, 5.2 -> 4.5 ms. */
+	/* Two shapes, still.  The wide one (sixteen entries, bursts of 64 bytes every eighth trip, wrap rows) is the
+	 * faster wave: 1 536 waves, one round of either, take 1.63 ms against 1.73 in the narrow one (eight entries,
+	 * 32 bytes every fourth trip, masked rows), which puts eight waves on a CU instead of six.  The narrow one is
+	 * taken where that saves a round: the 16 GiB workload's 4 096 waves are three rounds of 1 536 (the last one
+	 * two thirds full) or two full rounds of 2 048. */
 	const uint32_t waves = (n + 63u) / 64u;
 	const uint32_t rounds_wide = (waves + PS_WAVES_WIDE - 1u) / PS_WAVES_WIDE;
 	const uint32_t rounds_narrow = (waves + PS_WAVES_NARROW - 1u) / PS_WAVES_NARROW;
 	if (rounds_narrow < rounds_wide)
-		ps_launch<128u, 4u>(s, d_src, src_bytes, d_blocks, n, d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+		ps_launch<128u, 8u, 4u, 4u, false>(s, d_src, src_bytes, d_blocks, n, d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
 	else
-		ps_launch<128u, 16u>(s, d_src, src_bytes, d_blocks, n, d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
+		ps_launch<128u, 16u, 8u, 8u, true>(s, d_src, src_bytes, d_blocks, n, d_out_len, d_nseq, d_status, d_sum_status, d_table, d_table_off, table_cap);
 }
