@@ -265,6 +265,16 @@ int la_gpu_lz4_decode(la_gpu_ctx *ctx, const la_lz4_batch *batch);
 int la_gpu_lz4_debug_deps(la_gpu_ctx *ctx, const la_lz4_batch *batch, uint32_t block, uint64_t *seq_out,
     uint32_t *deps_out, uint32_t cap);
 
+/* Debugging aid, the same contract: the LITERAL PLAN the dependency kernel wrote for block `block`, `cap` entries at
+ * most.  Entry c, for c < ceil(src_len / 32), is the first sequence of the block whose literals end beyond payload
+ * offset 32 c, or 0xFFFF when no literal byte lies at or behind that offset; one more entry behind them holds the number
+ * of chunks that hold literals.  The LDS-window kernel starts each payload chunk's literal placement from its entry.
+ * Synchronises.  Returns the number of entries, ceil(src_len / 32) + 1; 0 for a block the window kernel did not take
+ * in one piece (stored, failed, no table, more than 4096 sequences, routed to the general kernel): nothing was
+ * written for it; LA_ERR_ARG when that decode computed no plan (the options named above). */
+int la_gpu_lz4_debug_literal_plan(la_gpu_ctx *ctx, const la_lz4_batch *batch, uint32_t block, uint16_t *plan_out,
+    uint32_t cap);
+
 /* =====================================================================
  * gzip / DEFLATE -- replaces the inflate() loop of gzip_filter_read
  * (libarchive/archive_read_support_filter_gzip.c:431-511; zlib inflate with

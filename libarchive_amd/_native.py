@@ -272,6 +272,7 @@ def gpu_lib():
         lib.la_gpu_lz4_decode.argtypes = [C.c_void_p, C.POINTER(_Lz4BatchC)]
         lib.la_gpu_lz4_debug_deps.argtypes = [C.c_void_p, C.POINTER(_Lz4BatchC), C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.c_uint32]
+        lib.la_gpu_lz4_debug_literal_plan.argtypes = [C.c_void_p, C.POINTER(_Lz4BatchC), C.c_uint32, C.c_void_p, C.c_uint32]
         lib.la_gpu_lz4_compress.argtypes = [C.c_void_p, C.POINTER(_Lz4cBatchC)]
         lib.la_gpu_gzip_compress.argtypes = [C.c_void_p, C.POINTER(_GzcBatchC)]
         lib.la_gpu_gzip_compress_bound.restype = C.c_uint64
@@ -532,6 +533,16 @@ class GpuContext:
         if n < 0:
             self._check(n, "la_gpu_lz4_debug_deps")
         return seq[:min(n, cap)], deps[:min(n, cap)]
+
+    def lz4_debug_literal_plan(self, batch: _Lz4BatchC, block: int, cap: int = 2049):
+        """The literal plan of one window block of the decode that just ran with `batch` (la_gpu_lz4_debug_literal_plan):
+        per 32-byte payload chunk the first sequence with literals in or behind it (0xFFFF: none), then the number of
+        chunks that hold literals; uint16, empty for a block without a plan."""
+        plan = np.zeros(cap, dtype=np.uint16)
+        n = gpu_lib().la_gpu_lz4_debug_literal_plan(self._h, C.byref(batch), block, plan.ctypes.data, cap)
+        if n < 0:
+            self._check(n, "la_gpu_lz4_debug_literal_plan")
+        return plan[:min(n, cap)]
 
     def lz4_compress(self, batch: _Lz4cBatchC):
         self._check(gpu_lib().la_gpu_lz4_compress(self._h, C.byref(batch)), "la_gpu_lz4_compress")

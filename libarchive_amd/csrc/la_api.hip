@@ -29,6 +29,9 @@ struct la_gpu_ctx {
 	 * public figure and keeps describing ws alone) */
 	uint32_t *lz4_deps;
 	uint64_t lz4_deps_cap;	/* words */
+	/* literal plans of the same blocks, written by the same kernel (la_lz4_lit_chunk_edge): one byte per table slot
+	 * entry, lz4_deps_cap bytes, reserved with the words */
+	uint8_t *lz4_plan;
 	/* second stream + events: block checksums / parse of later slices run beside the
 	 * expand kernels of earlier ones */
 	hipStream_t aux_stream;
@@ -129,6 +132,7 @@ void la_gpu_close(la_gpu_ctx *c)
 	(void)hipStreamSynchronize(c->stream);
 	if (c->ws) (void)hipFree(c->ws);
 	if (c->lz4_deps) (void)hipFree(c->lz4_deps);
+	if (c->lz4_plan) (void)hipFree(c->lz4_plan);
 	(void)hipEventDestroy(c->ev0);
 	(void)hipEventDestroy(c->ev1);
 	(void)hipEventDestroy(c->mark);
@@ -343,8 +347,9 @@ uint64_t la_gpu_lz4_workspace_bytes(uint32_t n_blocks, uint64_t src_bytes)
 	return w.total;
 }
 
-/* Room for one dependency word per table slot (4 B beside the slot's 8: on the 16 GiB bench shape the table is
- * 20 GB and the words 10 GB; a filter's 64 MiB window asks for 90 MB).  Grown like the workspace, never shrunk. */
+/* Room for one dependency word and one byte of literal plan per table slot entry (5 B beside the entry's 8: on the
+ * 16 GiB bench shape the table is 20 GB, the words 10 GB and the plans 2.5 GB; a filter's 64 MiB window asks for 90 MB
+ * and 22 MB).  Grown like the workspace, never shrunk. */
 static int lz4_deps_reserve(la_gpu_ctx *c, uint64_t words)
 {
 	if (words <= c->lz4_deps_cap)
@@ -352,9 +357,12 @@ static int lz4_deps_reserve(la_gpu_ctx *c, uint64_t words)
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->aux_stream));
-	if (c->lz4_deps) { HIPCHK(c, hipFree(c->lz4_deps)); c->lz4_deps = NULL; c->lz4_deps_cap = 0; }
+	c->lz4_deps_cap = 0;
+	if (c->lz4_deps) { HIPCHK(c, hipFree(c->lz4_deps)); c->lz4_deps = NULL; }
+	if (c->lz4_plan) { HIPCHK(c, hipFree(c->lz4_plan)); c->lz4_plan = NULL; }
 	words = (words + 0x3FFFFull) & ~0x3FFFFull;
 	HIPCHK(c, hipMalloc((void **)&c->lz4_deps, words * sizeof(uint32_t)));
+	HIPCHK(c, hipMalloc((void **)&c->lz4_plan, words));
 	c->lz4_deps_cap = words;
 	return LA_OK;
 }
@@ -400,7 +408,7 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 	const la_expand_job xj = {	/* every expand launch below is this job, or a slice of it */ bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_dst, bt->dst_cap, bt->d_dst_off,
 	    bt->d_out_len, bt->d_block_status, w.nseq, fast ? w.table : NULL, w.table_off,
 	    LA_LZ4_LONG_SEQ_BYTES,	/* blocks of few long sequences go to the general kernel (la_dev.h) */
-	    with_deps ? c->lz4_deps : NULL };
+	    with_deps ? c->lz4_deps : NULL, with_deps ? c->lz4_plan : NULL };
 
 	prof_begin(c);
 	/* the second stream starts after whatever the caller queued on its stream */
@@ -447,7 +455,7 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 	 * profiles/r25_lz4_deps.md) -- two window workgroups leave 3 KiB of a CU's LDS, so the dependency kernel only
 	 * ever gets in where an expand workgroup has just left */
 	if (with_deps)
-		prof_range(c, "lz4_deps", sx, [&] { la_launch_lz4_deps(sx, xj, c->lz4_deps); });
+		prof_range(c, "lz4_deps", sx, [&] { la_launch_lz4_deps(sx, xj, c->lz4_deps, c->lz4_plan); });
 
 	/* blocks the LDS-window kernel does not take (any size, stored, chains of dependent
 	 * blocks) first, over the whole table; then the LDS-window kernel in slices, each
@@ -518,6 +526,39 @@ int la_gpu_lz4_debug_deps(la_gpu_ctx *c, const la_lz4_batch *bt, uint32_t block,
 		HIPCHK(c, hipStreamSynchronize(c->stream));
 	}
 	return (int)ns;
+}
+
+int la_gpu_lz4_debug_literal_plan(la_gpu_ctx *c, const la_lz4_batch *bt, uint32_t block, uint16_t *plan_out, uint32_t cap)
+{
+	if (!c || !bt || block >= bt->n_blocks || (cap && !plan_out) || !lz4_uses_deps(bt))
+		return LA_ERR_ARG;
+	lz4_ws w;
+	lz4_ws_carve(&w, (uint8_t *)c->ws, bt->n_blocks, bt->src_bytes, true);
+	if (!c->ws || w.total > c->ws_bytes || w.table_cap > c->lz4_deps_cap || !c->lz4_plan)
+		return LA_ERR_ARG;
+	la_lz4_block b;
+	uint32_t ns = 0, st = 0, olen = 0;
+	uint64_t toff[2] = { 0, 0 }, doff = 0;
+	HIPCHK(c, hipMemcpyAsync(&b, bt->d_blocks + block, sizeof(b), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(&ns, w.nseq + block, sizeof(ns), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(&st, bt->d_block_status + block, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(&olen, bt->d_out_len + block, sizeof(olen), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(&doff, bt->d_dst_off + block, sizeof(doff), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(toff, w.table_off + block, sizeof(toff), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	/* the dependency kernel's own question.  (The status is the decode's final one: a block that failed behind the
+	 * dependency kernel -- a wrong checksum -- had its plan written and answers 0 here all the same.) */
+	if (la_lz4_route(b, st, olen, ns, doff, bt->dst_cap, true, LA_LZ4_LONG_SEQ_BYTES) != LA_XR_WINDOW)
+		return 0;
+	const uint32_t m = la_lz4_plan_entries(b.src_len);
+	if (toff[0] > toff[1] || toff[1] > w.table_cap || 2ull * m > toff[1] - toff[0])
+		return LA_ERR_ARG;
+	const uint32_t take = m < cap ? m : cap;
+	if (take) {
+		HIPCHK(c, hipMemcpyAsync(plan_out, c->lz4_plan + toff[0], (size_t)take * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+	}
+	return (int)m;
 }
 
 uint64_t la_gpu_zstd_workspace_bytes(uint32_t n_frames)

@@ -521,6 +521,32 @@ __device__ __forceinline__ bool la_lz4_dep_drops_last(uint32_t hi_byte, uint32_t
 	return hi_byte < last_mstart;
 }
 
+/* Where phase L of the LDS-window kernel starts in the sequence table: THE place where that is decided.  Phase L gives
+ * every 32-byte chunk of a block's payload to one thread, which has to know the first sequence with literal bytes in or
+ * behind its chunk.  Positions are relative to the payload's first byte.  With le(k) = lit_src + lit_len the end of
+ * sequence k's literal run (le(-1) = 0), the LITERAL PLAN of a block is a chunk index:
+ *   entry c, c < ceil(src_len / 32):  the first sequence whose literals end beyond payload offset 32 c, that is the k
+ *       with la_lz4_lit_chunk_edge(le(k - 1)) <= c < la_lz4_lit_chunk_edge(le(k)); LA_LZ4_PLAN_NONE when there is none
+ *       (chunks behind the last literal byte: a thread there has nothing to place);
+ *   one entry behind them:  the number of chunks that hold literals, la_lz4_lit_chunk_edge(le(ns - 1)).
+ * A sequence whose run ends in front of the same chunk edge as the run before it is no chunk's entry; one without
+ * literals counts with lit_len = 0, its le the place where they would stand.
+ * A sequence number is below LA_LZ4_FAST_MAXSEQ = 4096, so 0xFFFF is free for "none".  The entries are 16-bit and lie
+ * in a byte buffer of one byte per table slot entry, the block's first one at byte table_off[block] (slots are
+ * multiples of eight entries, so that is even): 2 (ceil(src_len / 32) + 1) <= (src_len / 3 + 8) & ~7 for every
+ * src_len, checked in tests/test_lz4_literal_plan_rule.py.
+ * Asked by the dependency kernel (la_lz4_deps.hip), which writes the plan, and by the window kernel's own chunk index
+ * (DEPS = false, la_lz4_fast.hip). */
+#define LA_LZ4_PLAN_NONE 0xFFFFu
+__host__ __device__ __forceinline__ uint32_t la_lz4_lit_chunk_edge(uint32_t lit_end)
+{
+	return (lit_end + 31u) >> 5;	/* the chunks [0, edge) begin in front of lit_end */
+}
+__host__ __device__ __forceinline__ uint32_t la_lz4_plan_entries(uint32_t src_len)
+{
+	return la_lz4_lit_chunk_edge(src_len) + 1u;
+}
+
 /* One expand step over a table of blocks: what every expand launch is given.  Host side only: the launchers unpack
  * it into their kernels' (restrict-qualified) arguments. */
 struct la_expand_job {
@@ -539,12 +565,14 @@ struct la_expand_job {
 	uint32_t long_thr;		/* la_lz4_long_sequences */
 	const uint32_t *deps;		/* one word per table entry, written by la_launch_lz4_deps for the LA_XR_WINDOW blocks
 					 * (la_lz4_dep_source); NULL: the window kernel searches for itself */
+	const uint8_t *lit_plan;	/* with deps, by the same launch: the blocks' literal plans (la_lz4_lit_chunk_edge), one byte
+					 * per table entry */
 
-	/* blocks first .. first + count - 1: the per-block arrays move; image, slab, table and deps (absolute offsets) stay */
+	/* blocks first .. first + count - 1: the per-block arrays move; image, slab, table, deps and plan (absolute offsets) stay */
 	la_expand_job slice(uint32_t first, uint32_t count) const
 	{
 		return la_expand_job{ src, src_bytes, blocks + first, count, dst, dst_cap, dst_off + first, out_len + first,
-		    status + first, nseq + first, table, table_off + first, long_thr, deps };
+		    status + first, nseq + first, table, table_off + first, long_thr, deps, lit_plan };
 	}
 };
 
@@ -562,9 +590,9 @@ void la_launch_lz4_parse_staged(hipStream_t s, const uint8_t *d_src, uint64_t sr
 void la_launch_lz4_expand_general(hipStream_t s, const la_expand_job &j, uint32_t hist_len);
 void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j);
 void la_launch_lz4_expand_fast_big(hipStream_t s, const la_expand_job &j, uint32_t *d_big /* n + 1 words */);
-/* la_lz4_deps.hip: the dependency words of the job's LA_XR_WINDOW blocks, for a later la_launch_lz4_expand_fast whose
- * job carries d_deps (same table offsets) */
-void la_launch_lz4_deps(hipStream_t s, const la_expand_job &j, uint32_t *d_deps);
+/* la_lz4_deps.hip: the dependency words and the literal plans of the job's LA_XR_WINDOW blocks, for a later
+ * la_launch_lz4_expand_fast whose job carries d_deps and d_plan (same table offsets) */
+void la_launch_lz4_deps(hipStream_t s, const la_expand_job &j, uint32_t *d_deps, uint8_t *d_plan);
 
 /* la_lz4_inorder.hip: the in-order expand step, run on request as the cross-check of the polling kernel (in-order
  * matcher wave + literal wave + flush wave per 64 KiB LDS window); the same contract, blocks of any sequence count

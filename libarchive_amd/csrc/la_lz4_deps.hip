@@ -10,9 +10,18 @@
  * 20 KiB of LDS per workgroup, eight workgroups per CU:
  *
  *   pass 1   the block's table entries, all loads of a thread in flight together and the entries
- *            kept in registers: output position and match start (dst + lit_len) go to LDS
- *   pass 2   the chunk map: for every 32-byte chunk of the output the sequence that holds the
- *            chunk's first byte (from the output positions in LDS)
+ *            kept in registers: output position and literal end (lit_src + lit_len) go to LDS
+ *   plan     the block's LITERAL PLAN (la_lz4_lit_chunk_edge, la_dev.h): for every 32-byte chunk
+ *            of the payload the first sequence with literals in or behind it, from each sequence's
+ *            own literal end and the one before it; 16-bit entries to lit_plan + table_off.  The
+ *            window kernel's literal phase starts from them: it used to load every sequence's
+ *            predecessor, build this index in LDS and stand at a barrier before its first literal
+ *            load (profiles/r27_lz4_literal_plan.md).  Every entry of the block's
+ *            ceil(src_len / 32) chunks and the count behind them is written in every launch:
+ *            the buffer is never cleared.
+ *   pass 2   match starts (dst + lit_len) take the literal ends' place behind a barrier; the chunk
+ *            map: for every 32-byte chunk of the output the sequence that holds the chunk's first
+ *            byte (from the output positions in LDS)
  *   pass 3   per sequence: the source's last byte by la_lz4_dep_source (la_dev.h), the map
  *            entries under the source's first and last byte, two short walks forward to q and
  *            to the last sequence under the source, that sequence's match start from LDS (la_lz4_dep_drops_last), and the
@@ -30,7 +39,8 @@
  *
  * Every index is inside its array whatever the table holds: positions are 16-bit, so a map index
  * is below 2048; q and qe stay below k < ns <= LA_LZ4_FAST_MAXSEQ; deps is written at
- * table_off + k with k < ns, inside the block's table slot.
+ * table_off + k with k < ns, inside the block's table slot; plan entries are written at
+ * c <= ceil(src_len / 32), two bytes each from byte table_off on, inside one byte per slot entry.
  */
 #include "la_dev.h"
 
@@ -40,10 +50,11 @@
 __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_block *__restrict__ blocks, uint32_t n,
     uint64_t dst_cap, const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ out_len,
     const uint32_t *__restrict__ status, const uint32_t *__restrict__ nseq, const la_lz4_seq *__restrict__ table,
-    const uint64_t *__restrict__ table_off, uint32_t long_thr, uint32_t *__restrict__ deps)
+    const uint64_t *__restrict__ table_off, uint32_t long_thr, uint32_t *__restrict__ deps, uint8_t *__restrict__ lit_plan)
 {
 	__shared__ uint16_t dstpos[LA_LZ4_FAST_MAXSEQ];		/* output position per sequence (20 KiB in all: eight workgroups per CU) */
-	__shared__ uint16_t mstart[LA_LZ4_FAST_MAXSEQ];		/* dst + lit_len: where the sequence's match starts */
+	__shared__ uint16_t mstart[LA_LZ4_FAST_MAXSEQ];		/* dst + lit_len: where the sequence's match starts; until the literal
+								 * plan is out, lit_src + lit_len: where its literals end in the payload */
 	__shared__ uint16_t cmap[2048];				/* per 32-byte output chunk: the sequence that holds its first byte */
 
 	const uint32_t bi = blockIdx.x;
@@ -55,6 +66,8 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
 	const uint32_t tid = threadIdx.x;
 	const uint64_t *const tab = (const uint64_t *)(const void *)(table + table_off[bi]);	/* lit_src | lit_len << 16 | dst << 32 | off << 48 */
 	uint32_t *const out = deps + table_off[bi];
+	uint16_t *const plan = (uint16_t *)(void *)(lit_plan + table_off[bi]);	/* (slots are multiples of eight entries: even) */
+	const uint32_t nchunks = la_lz4_lit_chunk_edge(blocks[bi].src_len);	/* <= 2048: an eligible block has src_len <= 65536 */
 
 	/* the thread's entries (sequences tid, tid + 256, ...), all requested before the first one is used and kept in
 	 * registers for pass 3: the table is read from memory once, with one latency and not one per 256 sequences */
@@ -70,12 +83,36 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
 			break;
 		const uint32_t k = r * DEPS_THREADS + tid;
 		if (k < ns) {
-			const uint32_t d = (uint32_t)(ent[r] >> 32) & 0xFFFFu;
-			dstpos[k] = (uint16_t)d;
-			mstart[k] = (uint16_t)(d + ((uint32_t)(ent[r] >> 16) & 0xFFFFu));	/* (65536 reads 0: only behind a last, empty sequence, which nobody waits for) */
+			dstpos[k] = (uint16_t)((uint32_t)(ent[r] >> 32) & 0xFFFFu);
+			mstart[k] = (uint16_t)(((uint32_t)ent[r] & 0xFFFFu) + ((uint32_t)(ent[r] >> 16) & 0xFFFFu));	/* literal end, for now */
 		}
 	}
 	__syncthreads();
+	/* the literal plan (la_lz4_lit_chunk_edge): sequence k is the entry of the payload chunks between the edge of the
+	 * literal end before it and its own, the last sequence closes the plan with "none" up to the payload's last chunk
+	 * and the count behind that.  The parse kernels keep literals inside the payload; a table that did not would
+	 * still write inside the slot (c < nchunks).  Only the end of the run BEFORE a sequence is read back from the
+	 * 16-bit array, and that run has its match offset behind it: it ends below 65536. */
+#pragma unroll
+	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
+		if (r * DEPS_THREADS >= ns)
+			break;
+		const uint32_t k = r * DEPS_THREADS + tid;
+		if (k < ns) {
+			const uint32_t le = ((uint32_t)ent[r] & 0xFFFFu) + ((uint32_t)(ent[r] >> 16) & 0xFFFFu);
+			const uint32_t pe = k ? (uint32_t)mstart[k - 1] : 0u;
+			uint32_t cend = la_lz4_lit_chunk_edge(le);
+			if (cend > nchunks)
+				cend = nchunks;
+			for (uint32_t c = la_lz4_lit_chunk_edge(pe); c < cend; c++)
+				plan[c] = (uint16_t)k;
+			if (k + 1 == ns) {
+				for (uint32_t c = cend; c < nchunks; c++)
+					plan[c] = (uint16_t)LA_LZ4_PLAN_NONE;
+				plan[nchunks] = (uint16_t)cend;
+			}
+		}
+	}
 	/* pass 2.  Where sequence k's match ends is the next sequence's position, the block's end behind the last one
 	 * (positions are 16-bit: an end at 65536 reads 0).  It replaces lit_src in the entry's low 16 bits, which
 	 * nothing here reads: pass 3 has the match length without another look at LDS. */
@@ -87,6 +124,7 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
 		const uint32_t after = k + 1 < ns ? (uint32_t)dstpos[k + 1] : (olen & 0xFFFFu);
 		ent[r] = (ent[r] & ~0xFFFFull) | after;
 	}
+	__syncthreads();	/* every literal end has been read: the array takes the match starts */
 #pragma unroll
 	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
 		if (r * DEPS_THREADS >= ns)
@@ -97,6 +135,7 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
 			uint32_t nxt = (uint32_t)ent[r] & 0xFFFFu;
 			if (nxt < d)
 				nxt = 65536u;
+			mstart[k] = (uint16_t)(d + ((uint32_t)(ent[r] >> 16) & 0xFFFFu));	/* (65536 reads 0: only behind a last, empty sequence, which nobody waits for) */
 			if (k == 0)
 				for (uint32_t c = 0; (c << 5) < d; c++)
 					cmap[c] = 0;
@@ -150,9 +189,9 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
 	}
 }
 
-void la_launch_lz4_deps(hipStream_t s, const la_expand_job &j, uint32_t *d_deps)
+void la_launch_lz4_deps(hipStream_t s, const la_expand_job &j, uint32_t *d_deps, uint8_t *d_plan)
 {
 	if (j.n == 0) return;
 	hipLaunchKernelGGL(lz4_deps_kernel, dim3(j.n), dim3(DEPS_THREADS), 0, s, j.blocks, j.n, j.dst_cap, j.dst_off,
-	    j.out_len, j.status, j.nseq, j.table, j.table_off, j.long_thr, d_deps);
+	    j.out_len, j.status, j.nseq, j.table, j.table_off, j.long_thr, d_deps, d_plan);
 }

@@ -86,6 +86,16 @@
  * launches 20.8 -> 18.0 ms, the dependency kernel 1.9 ms in front of them.  The rule itself is la_lz4_dep_source /
  * la_lz4_dep_drops_last (la_dev.h), asked by both.  DEPS = false is the kernel as it was: the segmented launch, the
  * deflate front end (inflate_expand) and LA_LZ4_OPT_SEARCH_IN_EXPAND run it.
+ *
+ * The chunk index out of the kernel (profiles/r27_lz4_literal_plan.md): where a payload chunk's literals start in the
+ * table follows from the table alone too (la_lz4_lit_chunk_edge, la_dev.h).  With DEPS = true the prepass above no
+ * longer loads every sequence's predecessor, builds no index in LDS and has no barrier in front of phase L: a thread
+ * asks for its chunks' entries of the block's literal plan (written by the dependency kernel, 16 bits per chunk) with
+ * the chunks themselves, ahead of the table entries, and the output positions and the cleared flags go to LDS behind
+ * the literal stores, where only the barrier that ends phase L waits for them.  Of a block's 79.4 k cycles the
+ * stretch in front of the first literal store went from 13.7 k to 8.9 k, the block to 75.1 k; the four C2 launches
+ * 17.97 -> 17.05 ms, the dependency kernel 1.91 -> 2.32 ms.  84 VGPRs and 74 368 B of LDS against 90 and 78 480.
+ * DEPS = false builds the index here as before, by the same rule.
  */
 #include "la_dev.h"
 
@@ -161,14 +171,16 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
     const uint32_t *__restrict__ out_len, uint32_t *status_out,
     const uint32_t *__restrict__ nseq, const la_lz4_seq *__restrict__ table,
     const uint64_t *__restrict__ table_off, const uint32_t *__restrict__ big_list,
-    const uint32_t *__restrict__ big_count, uint32_t long_thr, const uint32_t *__restrict__ deps)
+    const uint32_t *__restrict__ big_count, uint32_t long_thr, const uint32_t *__restrict__ deps,
+    const uint8_t *__restrict__ lit_plan)
 {
 	static_assert(!(SEG && DEPS), "the dependency words number a block's sequences from its first one");
 	const uint32_t *status = status_out;
 	__shared__ __attribute__((aligned(16))) uint8_t win[16 + 65536 + 96];	/* 16 headroom (literal stores may start 3 bytes early) + 16 alignment shift + slack for over-reads */
 	__shared__ uint16_t dstpos[MAXSEQ + 4];
 	__shared__ uint32_t donebits[MAXSEQ / 32];	/* one bit per sequence: its match is in the window */
-	__shared__ uint16_t chunk_first[2048 + 8];	/* per 32-byte payload chunk: first sequence with literals in or after it */
+	__shared__ uint16_t chunk_first[DEPS ? 8 : 2048 + 8];	/* per 32-byte payload chunk: first sequence with literals in or after it
+								 * (DEPS: the index comes from the dependency kernel, nothing is kept here) */
 
 	auto do_block = [&](const uint32_t bi) __attribute__((always_inline)) {
 	if (bi >= n)
@@ -217,6 +229,22 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 			}
 		}
 	}
+	/* DEPS: where each of those chunks starts in the table is the block's literal plan (la_lz4_lit_chunk_edge), written
+	 * by the dependency kernel: requested with the chunks, in front of the table entries, so that the chunk's sequences
+	 * can be asked for as soon as it is back.  No predecessor entries, no index built in LDS, no barrier in front of
+	 * phase L (profiles/r27_lz4_literal_plan.md). */
+	const uint16_t *const plan = DEPS ? (const uint16_t *)(const void *)(lit_plan + table_off[bi]) : nullptr;
+	const uint32_t plan_chunks = la_lz4_lit_chunk_edge(b.src_len);	/* the plan has an entry for every chunk of the payload */
+	uint32_t kk0[LBATCH];
+#pragma unroll
+	for (int u = 0; u < LBATCH; u++) {
+		kk0[u] = LA_LZ4_PLAN_NONE;
+		if constexpr (DEPS) {
+			const uint32_t c = u * FAST_THREADS + tid;
+			if (c < plan_chunks)
+				kk0[u] = plan[c];
+		}
+	}
 	/* Blocks with more sequences than the LDS arrays hold are done in SEGMENTS of MAXSEQ
 	 * sequences: prepass, literals and matches per segment, a barrier between segments.
 	 * Sequences of earlier segments are complete by then, so a segment only ever waits on
@@ -250,50 +278,72 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 			break;
 		const uint32_t k = fast_seq_index(r, wave, lane);
 		ent[r] = k < ns ? seq_load(tab, k) : 0;
-		const seq_t pv = ((k > 0 || kb > 0) && k < ns) ? seq_load(tab_all, kb + k - 1) : 0;
-		prev_end[r] = SEQ_LIT_SRC(pv) + SEQ_LIT_LEN(pv);
-	}
-	if (tid < MAXSEQ / 32)
-		donebits[tid] = 0;
-	if (tid == 0) {
-		/* output position where the segment ends: the match length of its last sequence */
-		dstpos[ns] = kb + ns < ns_all ? (uint16_t)SEQ_DST(seq_load(tab_all, kb + ns)) : (uint16_t)olen;
-		if ((cb << 5) < seg_prev_end)
-			chunk_first[0] = 0;	/* chunk shared with the previous segment: this side starts with its first sequence */
-	}
-	/* chunk_first[c] = first sequence whose literals end beyond payload offset 32c */
-#pragma unroll
-	for (uint32_t r = 0; r < MAXSTEPS; r++) {
-		if (r * FAST_THREADS >= ns)
-			break;
-		const uint32_t k = fast_seq_index(r, wave, lane);
-		if (k < ns) {
-			const uint32_t le = SEQ_LIT_SRC(ent[r]) + SEQ_LIT_LEN(ent[r]);
-			for (uint32_t c = (prev_end[r] + 31) >> 5; (c << 5) < le; c++)
-				chunk_first[c - cb] = (uint16_t)k;
-			dstpos[k] = (uint16_t)SEQ_DST(ent[r]);
-			if (k + 1 == ns)
-				chunk_first[2048] = (uint16_t)(((le + 31) >> 5) - cb);	/* chunks from here on hold no literals of this segment */
+		if constexpr (!DEPS) {
+			const seq_t pv = ((k > 0 || kb > 0) && k < ns) ? seq_load(tab_all, kb + k - 1) : 0;
+			prev_end[r] = SEQ_LIT_SRC(pv) + SEQ_LIT_LEN(pv);
 		}
 	}
-	__syncthreads();
+	/* what the match phase finds in LDS: the flags cleared, every sequence's output position, and behind the last one
+	 * the position where the segment ends (the match length of its last sequence).  Without the plan it goes out with
+	 * the chunk index, in front of phase L's barrier; with it, behind phase L's stores. */
+	auto publish = [&]() __attribute__((always_inline)) {
+		if (tid < MAXSEQ / 32)
+			donebits[tid] = 0;
+		if (tid == 0)
+			dstpos[ns] = kb + ns < ns_all ? (uint16_t)SEQ_DST(seq_load(tab_all, kb + ns)) : (uint16_t)olen;
+#pragma unroll
+		for (uint32_t r = 0; r < MAXSTEPS; r++) {
+			if (r * FAST_THREADS >= ns)
+				break;
+			const uint32_t k = fast_seq_index(r, wave, lane);
+			if (k < ns)
+				dstpos[k] = (uint16_t)SEQ_DST(ent[r]);
+		}
+	};
+	if constexpr (!DEPS) {
+		publish();
+		if (tid == 0 && (cb << 5) < seg_prev_end)
+			chunk_first[0] = 0;	/* chunk shared with the previous segment: this side starts with its first sequence */
+		/* chunk_first[c] = first sequence whose literals end beyond payload offset 32c (la_lz4_lit_chunk_edge) */
+#pragma unroll
+		for (uint32_t r = 0; r < MAXSTEPS; r++) {
+			if (r * FAST_THREADS >= ns)
+				break;
+			const uint32_t k = fast_seq_index(r, wave, lane);
+			if (k < ns) {
+				const uint32_t le = SEQ_LIT_SRC(ent[r]) + SEQ_LIT_LEN(ent[r]);
+				for (uint32_t c = la_lz4_lit_chunk_edge(prev_end[r]); c < la_lz4_lit_chunk_edge(le); c++)
+					chunk_first[c - cb] = (uint16_t)k;
+				if (k + 1 == ns)
+					chunk_first[2048] = (uint16_t)(la_lz4_lit_chunk_edge(le) - cb);	/* chunks from here on hold no literals of this segment */
+			}
+		}
+		__syncthreads();
+	}
 #ifdef LA_DIAG_L
 	STAMP(6);
 #endif
 
 	/* ---- phase L: literals, one thread per 32-byte payload chunk ----
 	 * Two coalesced 16-byte loads of the compressed stream per chunk; the chunk's
-	 * sequences come from chunk_first (LDS) and six table entries fetched together;
+	 * sequences come from chunk_first (LDS; DEPS: from the literal plan) and six table entries fetched together;
 	 * literal bytes go to the window with unaligned 8-byte LDS stores.  Work is balanced
 	 * by payload bytes, and every payload byte is read once. */
-	const uint32_t nlit_chunks = chunk_first[2048];
+	uint32_t nlit_chunks = plan_chunks;	/* DEPS: every chunk of the payload has a plan entry, "none" behind the last literal */
+	if constexpr (!DEPS)
+		nlit_chunks = chunk_first[2048];
 	for (uint32_t base = 0; base < nlit_chunks; base += LBATCH * FAST_THREADS) {
 		uint32_t kk[LBATCH];
 		seq_t pe[LBATCH][6];
 #pragma unroll
 		for (int u = 0; u < LBATCH; u++) {
 			const uint32_t c = base + u * FAST_THREADS + tid;	/* chunk number inside the segment */
-			kk[u] = c < nlit_chunks ? (uint32_t)chunk_first[c] : 0xFFFFFFFFu;
+			if constexpr (DEPS) {
+				const uint32_t e = base == 0 ? kk0[u] : c < nlit_chunks ? (uint32_t)plan[c] : (uint32_t)LA_LZ4_PLAN_NONE;
+				kk[u] = e == LA_LZ4_PLAN_NONE ? 0xFFFFFFFFu : e;
+			} else {
+				kk[u] = c < nlit_chunks ? (uint32_t)chunk_first[c] : 0xFFFFFFFFu;
+			}
 			if (base != 0 || kb != 0) {	/* payloads beyond 32 KiB, later segments: chunks are loaded here */
 				vv[u][0] = vv[u][1] = vv[u][2] = vv[u][3] = 0;
 				const uint32_t c0 = (cb + c) << 5;
@@ -378,6 +428,7 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 			const uint32_t k = fast_seq_index(r, wave, lane);
 			dw[r] = (r * FAST_THREADS < ns && k < ns) ? deps[table_off[bi] + k] : 0;
 		}
+		publish();
 	}
 	STAMP(1);
 	__syncthreads();
@@ -739,14 +790,15 @@ extern "C" int la_diag_set_stamps(void *d_buf)
 void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j)
 {
 	if (j.n == 0) return;
-	if (j.deps)
+	if (j.deps && j.lit_plan)
 		hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false, true>), dim3(j.n), dim3(FAST_THREADS), 0, s,
 		    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
-		    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr, j.deps);
+		    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr, j.deps, j.lit_plan);
 	else
 		hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false, false>), dim3(j.n), dim3(FAST_THREADS), 0, s,
 		    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
-		    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr, (const uint32_t *)nullptr);
+		    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr, (const uint32_t *)nullptr,
+		    (const uint8_t *)nullptr);
 }
 
 /* blocks with more than LA_LZ4_FAST_MAXSEQ sequences, over the WHOLE table: classify + a small
@@ -760,5 +812,6 @@ void la_launch_lz4_expand_fast_big(hipStream_t s, const la_expand_job &j, uint32
 	const uint32_t grid = j.n < 1024u ? j.n : 1024u;
 	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, true, false>), dim3(grid), dim3(FAST_THREADS), 0, s,
 	    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
-	    j.table, j.table_off, (const uint32_t *)(d_big + 1), (const uint32_t *)d_big, j.long_thr, (const uint32_t *)nullptr);
+	    j.table, j.table_off, (const uint32_t *)(d_big + 1), (const uint32_t *)d_big, j.long_thr, (const uint32_t *)nullptr,
+	    (const uint8_t *)nullptr);
 }
