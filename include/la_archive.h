@@ -34,6 +34,7 @@ extern "C" {
 #define ARCHIVE_FILTER_BZIP2 2
 #define ARCHIVE_FILTER_XZ   6
 #define ARCHIVE_FILTER_LZIP 9
+#define ARCHIVE_FILTER_LZOP 11
 #define ARCHIVE_FILTER_LZ4  13
 #define ARCHIVE_FILTER_ZSTD 14
 
@@ -59,6 +60,7 @@ int  archive_read_support_filter_gzip(struct archive *);			/* archive.h:466 */
 int  archive_read_support_compression_gzip(struct archive *);			/* deprecated alias, gzip.c:85-92 */
 int  archive_read_support_filter_lz4(struct archive *);				/* archive.h:469 */
 int  archive_read_support_filter_lzip(struct archive *);			/* archive.h:470 (host/la_filter_lzip.c) */
+int  archive_read_support_filter_lzop(struct archive *);			/* archive.h:472 (host/la_filter_lzop.c) */
 int  archive_read_support_filter_zstd(struct archive *);			/* archive.h:482 */
 int  archive_read_support_filter_xz(struct archive *);				/* archive.h:481 (host/la_filter_xz.c) */
 int  archive_read_support_filter_none(struct archive *);

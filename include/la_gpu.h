@@ -135,7 +135,18 @@ enum {
 	LA_ST_LZIP_OUT_FULL       = 37,	/* no tentative size, and the stream produces more than dst_cap: the host retries with more */
 	LA_ST_LZIP_BAD_SIZE       = 38,	/* the stream ended with fewer bytes than the tentative data size */
 	LA_ST_LZIP_BAD_CRC        = 39,	/* the bytes do not give the trailer's CRC32 */
-	LA_ST_LZIP_REFUSED        = 40	/* the entry points outside d_src or d_dst, or its dst_cap is above LA_XZ_DST_CAP_MAX: not decoded */
+	LA_ST_LZIP_REFUSED        = 40,	/* the entry points outside d_src or d_dst, or its dst_cap is above LA_XZ_DST_CAP_MAX: not decoded */
+	/* lzop (archive_read_support_filter_lzop.c; the numbers in brackets are liblzo2's lzo1x_decompress_safe codes, which
+	 * the reference prints) */
+	LA_ST_LZOP_BAD_SUM_C      = 41,	/* lzop.c:425-429 -> "Corrupted data": the compressed bytes do not give the block's sum; not decoded */
+	LA_ST_LZOP_INPUT_OVERRUN  = 42,	/* lzop.c:459-462 -> "lzop decompression failed: -4": the stream asks for a byte behind src_len */
+	LA_ST_LZOP_OUTPUT_OVERRUN = 43,	/* lzop.c:459-462 -> "lzop decompression failed: -5": a literal run or match passes dst_len */
+	LA_ST_LZOP_LOOKBEHIND     = 44,	/* lzop.c:459-462 -> "lzop decompression failed: -6": a match starts in front of the block */
+	LA_ST_LZOP_NOT_CONSUMED   = 45,	/* lzop.c:459-462 -> "lzop decompression failed: -8": the end marker stands in front of src_len */
+	LA_ST_LZOP_SHORT_OUTPUT   = 46,	/* lzop.c:449-454 -> "Corrupted data": the stream ends well with fewer than dst_len bytes */
+	LA_ST_LZOP_BAD_SUM_U      = 47,	/* lzop.c:473-477 -> "Corrupted data": the decoded bytes do not give the block's sum */
+	LA_ST_LZOP_REFUSED        = 48	/* the entry points outside d_src or d_dst, src_len > dst_len (lzop.c:332-333 "Corrupted lzop
+					 * header" is the host's) or dst_len is above LA_LZOP_MAX_BLOCK (lzop.c:324-325): not touched */
 };
 
 /* =====================================================================
@@ -157,6 +168,14 @@ int la_gpu_xxh32_many(la_gpu_ctx *ctx, const uint8_t *d_base,
  * `seed` of a job is the running crc to continue from (0 for a fresh one).
  * ===================================================================== */
 int la_gpu_crc32_many(la_gpu_ctx *ctx, const uint8_t *d_base,
+    const la_hash_job *d_jobs, uint32_t n_jobs, uint32_t *d_out);
+
+/* =====================================================================
+ * Adler-32 -- replaces adler32() (zlib's, as archive_read_support_filter_lzop.c:51, :282, :422, :469 calls it) for many
+ * ranges; each range is cut into lane chunks whose (a, b) pairs are combined.  `seed` of a job is the running value to
+ * continue from (1 for a fresh one).  Addition under ABI version 3.
+ * ===================================================================== */
+int la_gpu_adler32_many(la_gpu_ctx *ctx, const uint8_t *d_base,
     const la_hash_job *d_jobs, uint32_t n_jobs, uint32_t *d_out);
 
 /* =====================================================================
@@ -837,6 +856,56 @@ typedef struct la_lzip_batch {
 uint64_t la_gpu_lzip_workspace_bytes(uint32_t n);
 int      la_gpu_lzip_scan(la_gpu_ctx *ctx, const uint8_t *d_src, uint64_t src_bytes, uint64_t *d_offs, uint32_t cap, uint32_t *d_count);
 int      la_gpu_lzip_decode(la_gpu_ctx *ctx, const la_lzip_batch *batch);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * lzop -- replaces, for a table of blocks per call, what lzop_filter_read does with one block
+ * (libarchive/archive_read_support_filter_lzop.c:412-482): the sum over the compressed bytes, lzo1x_decompress_safe (or
+ * the plain copy of a stored block, src_len == dst_len), the sum over the decoded bytes.  Blocks are independent and
+ * both of their sizes stand in the block header, so the host hops from header to header (host/la_filter_lzop.c) and the
+ * device decodes one block per wave in ONE pass.  csrc/la_lzo_dev.h states the LZO1X rules.
+ *
+ * A block whose compressed sum fails is not decoded (LA_ST_LZOP_BAD_SUM_C, out_len 0).  The host hands over sum_c and
+ * sum_u as the reference would hold them when it compares (a stale value included, lzop.c:335-350); without a flag for
+ * a side nothing is computed or compared for it and the result's field is 0.  On every failure out_len bytes in front of
+ * it are in d_dst.  An entry that points outside d_src or d_dst, with src_len > dst_len or dst_len above
+ * LA_LZOP_MAX_BLOCK, is LA_ST_LZOP_REFUSED and not touched.  Additions under ABI version 3. */
+#define LA_LZOP_C_ADLER32 1u	/* sum_c is the Adler-32 of the compressed bytes (ADLER32_COMPRESSED) */
+#define LA_LZOP_C_CRC32   2u	/* sum_c is their CRC32 (CRC32_COMPRESSED); wins over LA_LZOP_C_ADLER32 */
+#define LA_LZOP_U_ADLER32 4u	/* sum_u is the Adler-32 of the decoded bytes (ADLER32_UNCOMPRESSED) */
+#define LA_LZOP_U_CRC32   8u	/* sum_u is their CRC32 (CRC32_UNCOMPRESSED); wins over LA_LZOP_U_ADLER32 */
+#define LA_LZOP_MAX_BLOCK ((uint32_t)64 << 20)	/* MAX_BLOCK_SIZE, lzop.c:92 */
+typedef struct la_lzop_block {
+	uint64_t src_off;	/* first byte of the block's data inside d_src (behind its header words) */
+	uint64_t dst_off;	/* where the block's bytes go inside d_dst */
+	uint32_t src_len;	/* the header's compressed size */
+	uint32_t dst_len;	/* the header's uncompressed size; equal to src_len: a stored block */
+	uint32_t flags;		/* LA_LZOP_* */
+	uint32_t sum_c;
+	uint32_t sum_u;		/* (not looked at for a stored block, lzop.c:435-440) */
+	uint32_t reserved;
+} la_lzop_block;
+
+typedef struct la_lzop_result {
+	uint32_t status;	/* LA_ST_OK or LA_ST_LZOP_* */
+	uint32_t sum_c;		/* the computed sums (0 where no flag asks for one, or the block was not decoded) */
+	uint32_t sum_u;
+	uint32_t out_len;	/* bytes produced: the bytes in front of a failure are valid */
+	uint32_t consumed;	/* source bytes read, through the end marker when one was found */
+} la_lzop_result;
+
+typedef struct la_lzop_batch {
+	const uint8_t       *d_src;
+	uint64_t             src_bytes;
+	const la_lzop_block *d_blocks;	/* device-resident */
+	uint32_t             n;
+	uint32_t             reserved;	/* 0 */
+	uint8_t             *d_dst;
+	uint64_t             dst_cap;		/* every block's [dst_off, dst_off + dst_len) lies inside it */
+	la_lzop_result      *d_results;	/* [n] */
+} la_lzop_batch;
+
+uint64_t la_gpu_lzop_workspace_bytes(uint32_t n);
+int      la_gpu_lzop_decode(la_gpu_ctx *ctx, const la_lzop_batch *batch);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * bzip2 compression -- replaces the BZ2_bzCompress loop of libarchive/archive_write_add_filter_bzip2.c (libbz2 is the

@@ -187,6 +187,7 @@ int    la_bid_lz4_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_zstd_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_lzip_parallel(const unsigned char *p, size_t n, size_t lookahead);
+int    la_bid_lzop_parallel(const unsigned char *p, size_t n, size_t lookahead);
 
 /* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the read filters; the held-back delivery at its
  * end by the bzip2 and xz ones ---- */
@@ -196,7 +197,7 @@ int  la_env_device(void);
 /* One filter's window: its device, its size (read once, at init) and whether upstream has ended */
 typedef struct la_window {
 	la_gpu_ctx *gpu;
-	const char *name;		/* "lz4", "gzip", "zstd", "bzip2", "xz", "lzip": in the error strings */
+	const char *name;		/* "lz4", "gzip", "zstd", "bzip2", "xz", "lzip", "lzop": in the error strings */
 	size_t      batch_bytes;	/* compressed bytes of the next window: min(16 MiB, target), then ramped */
 	size_t      target_bytes;	/* LA_GPU_BATCH_MIB, default 64 */
 	size_t      max_batch_bytes;	/* LA_GPU_MAX_BATCH_MIB, default 2048: how far a window may widen */

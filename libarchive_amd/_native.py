@@ -154,6 +154,21 @@ class _LzipBatchC(C.Structure):     # la_lzip_batch
                 ("reserved", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
 
 
+# lzop (la_lzop_block, la_lzop_result, la_lzop_batch)
+LZOP_BLOCK_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u4"), ("dst_len", "<u4"), ("flags", "<u4"),
+                             ("sum_c", "<u4"), ("sum_u", "<u4"), ("reserved", "<u4")])
+LZOP_RESULT_DTYPE = np.dtype([("status", "<u4"), ("sum_c", "<u4"), ("sum_u", "<u4"), ("out_len", "<u4"), ("consumed", "<u4")])
+LA_LZOP_C_ADLER32, LA_LZOP_C_CRC32, LA_LZOP_U_ADLER32, LA_LZOP_U_CRC32 = 1, 2, 4, 8
+LA_LZOP_MAX_BLOCK = 64 << 20
+(LA_ST_LZOP_BAD_SUM_C, LA_ST_LZOP_INPUT_OVERRUN, LA_ST_LZOP_OUTPUT_OVERRUN, LA_ST_LZOP_LOOKBEHIND, LA_ST_LZOP_NOT_CONSUMED,
+ LA_ST_LZOP_SHORT_OUTPUT, LA_ST_LZOP_BAD_SUM_U, LA_ST_LZOP_REFUSED) = 41, 42, 43, 44, 45, 46, 47, 48
+
+
+class _LzopBatchC(C.Structure):     # la_lzop_batch
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("d_blocks", C.c_void_p), ("n", C.c_uint32),
+                ("reserved", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
+
+
 class _LzcBatchC(C.Structure):      # la_lzc_batch
     _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("level", C.c_uint32), ("flags", C.c_uint32),
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
@@ -312,6 +327,10 @@ def gpu_lib():
         lib.la_gpu_lzip_decode.argtypes = [C.c_void_p, C.POINTER(_LzipBatchC)]
         lib.la_gpu_lzip_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_lzip_workspace_bytes.argtypes = [C.c_uint32]
+        lib.la_gpu_adler32_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.la_gpu_lzop_decode.argtypes = [C.c_void_p, C.POINTER(_LzopBatchC)]
+        lib.la_gpu_lzop_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_lzop_workspace_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_xz_compress_block_bytes.restype = C.c_uint64
         lib.la_gpu_xz_compress_block_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_xz_compress_workspace_bytes.restype = C.c_uint64
@@ -580,6 +599,12 @@ class GpuContext:
 
     def lzip_decode(self, batch: _LzipBatchC):
         self._check(gpu_lib().la_gpu_lzip_decode(self._h, C.byref(batch)), "la_gpu_lzip_decode")
+
+    def adler32_many(self, d_base_ptr, d_jobs_ptr, n, d_out_ptr):
+        self._check(gpu_lib().la_gpu_adler32_many(self._h, d_base_ptr, d_jobs_ptr, n, d_out_ptr), "la_gpu_adler32_many")
+
+    def lzop_decode(self, batch: _LzopBatchC):
+        self._check(gpu_lib().la_gpu_lzop_decode(self._h, C.byref(batch)), "la_gpu_lzop_decode")
 
     def lzip_compress(self, batch: _LzcBatchC):
         self._check(gpu_lib().la_gpu_lzip_compress(self._h, C.byref(batch)), "la_gpu_lzip_compress")

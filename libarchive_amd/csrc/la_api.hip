@@ -306,6 +306,15 @@ int la_gpu_crc32_many(la_gpu_ctx *c, const uint8_t *d_base, const la_hash_job *d
 	return LA_OK;
 }
 
+int la_gpu_adler32_many(la_gpu_ctx *c, const uint8_t *d_base, const la_hash_job *d_jobs,
+    uint32_t n, uint32_t *d_out)
+{
+	if (!c || (n && (!d_base || !d_jobs || !d_out))) return LA_ERR_ARG;
+	la_launch_adler32_many(c->stream, d_base, d_jobs, n, d_out);
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 /* ------------------------------------------------------------------ lz4 */
 
 static uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) & ~(a - 1); }
@@ -718,6 +727,28 @@ int la_gpu_lzip_decode(la_gpu_ctx *c, const la_lzip_batch *bt)
 	}
 	prof_begin(c);
 	prof_range(c, "lzip_decode", c->stream, [&] { la_launch_lzip_decode(c->stream, bt, (uint8_t *)c->ws); });
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
+uint64_t la_gpu_lzop_workspace_bytes(uint32_t n)
+{
+	return la_lzop_workspace_bytes(n);
+}
+
+int la_gpu_lzop_decode(la_gpu_ctx *c, const la_lzop_batch *bt)
+{
+	if (!c || !bt || bt->reserved)
+		return LA_ERR_ARG;
+	if (bt->n && (!bt->d_blocks || !bt->d_results || !bt->d_dst || (bt->src_bytes && !bt->d_src)))
+		return LA_ERR_ARG;
+	const uint64_t need = la_lzop_workspace_bytes(bt->n);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	prof_begin(c);
+	prof_range(c, "lzop_decode", c->stream, [&] { la_launch_lzop_decode(c->stream, bt, (uint8_t *)c->ws); });
 	HIPCHK(c, hipGetLastError());
 	return LA_OK;
 }

@@ -436,6 +436,8 @@ void la_launch_xxh32_many(hipStream_t s, const uint8_t *d_base, const la_hash_jo
     uint32_t n, uint32_t *d_out);
 void la_launch_crc32_many(hipStream_t s, const uint8_t *d_base, const la_hash_job *d_jobs,
     uint32_t n, uint32_t *d_out);
+void la_launch_adler32_many(hipStream_t s, const uint8_t *d_base, const la_hash_job *d_jobs,
+    uint32_t n, uint32_t *d_out);
 void la_launch_lz4_block_sums(hipStream_t s, const uint8_t *d_src, const la_lz4_block *d_blocks,
     uint32_t n, uint32_t *d_status);
 void la_launch_lz4_frame_sums(hipStream_t s, const uint8_t *d_src, const uint8_t *d_dst,
@@ -634,6 +636,10 @@ void la_launch_lzip_scan(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes
     uint8_t *ws);
 uint64_t la_lzip_workspace_bytes(uint32_t n);
 void la_launch_lzip_decode(hipStream_t s, const la_lzip_batch *bt, uint8_t *ws);
+
+/* la_lzo.hip */
+uint64_t la_lzop_workspace_bytes(uint32_t n);
+void la_launch_lzop_decode(hipStream_t s, const la_lzop_batch *bt, uint8_t *ws);
 /* la_xz_filters.hip: the chains behind d_blocks[n] (LA_XZ_BATCH_CHAINS) undone over the decoded bytes; jobs_ws is
  * la_launch_xz_decode's workspace, ws a 256-byte aligned scratch of la_xz_unfilter_ws_bytes() of its own */
 uint64_t la_xz_unfilter_ws_bytes(uint32_t n, uint64_t dst_cap);

@@ -1,5 +1,5 @@
 /*
- * la_hash.hip -- many-hash XXH32 and wave-reduced CRC32 kernels (gfx950).
+ * la_hash.hip -- many-hash XXH32 and wave-reduced CRC32 and Adler-32 kernels (gfx950).
  *
  * Replaces, for whole batches, the per-call hashing of
  *   libarchive/xxhash.c:234-319        (XXH32 one shot; call sites lz4.c:446, :518, :652)
@@ -13,6 +13,9 @@
  * (contiguous chunks, slicing-by-4 tables in LDS) and the lane values are
  * merged with a log2(64)-step shuffle tree of carry-less multiplications by
  * x^(8*chunk*2^k) mod P.
+ * Adler-32 (zlib's adler32(), the lzop filter's block check, lzop.c:422, :469) splits a
+ * range the same way: the (a, b) pair of two ranges in a row is a function of their pairs
+ * and the second one's length, so the same tree joins the lanes.
  */
 #include "la_dev.h"
 
@@ -434,6 +437,107 @@ void la_launch_crc32_many(hipStream_t s, const uint8_t *d_base, const la_hash_jo
 	uint32_t blocks = (n + 3) / 4;
 	if (blocks > 256 * 8) blocks = 256 * 8;
 	hipLaunchKernelGGL(crc32_many_kernel, dim3(blocks), dim3(256), 0, s, d_base, d_jobs, n, d_out);
+}
+
+/* ------------------------------------------------------------------ Adler-32, many ranges */
+
+#define ADLER_MOD  65521u
+#define ADLER_NMAX 5552u	/* zlib's: the most bytes after which a and b, both below ADLER_MOD before, still fit 32 bits */
+
+/* (a, b) of n bytes hashed by one lane from the fresh state (1, 0); both below ADLER_MOD */
+__device__ __forceinline__ void adler_run(const uint8_t *p, uint32_t n, uint32_t &a_out, uint32_t &b_out)
+{
+	uint32_t a = 1, b = 0;
+	while (n) {
+		uint32_t k = n < ADLER_NMAX ? n : ADLER_NMAX;
+		n -= k;
+		while (k && ((uintptr_t)p & 3)) {
+			a += *p++; b += a;
+			k--;
+		}
+		for (; k >= 16; k -= 16, p += 16) {
+			const uint4 v = *(const uint4 *)__builtin_assume_aligned(p, 4);
+			const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+			for (int i = 0; i < 4; i++) {
+				a += w[i] & 0xffu; b += a;
+				a += (w[i] >> 8) & 0xffu; b += a;
+				a += (w[i] >> 16) & 0xffu; b += a;
+				a += w[i] >> 24; b += a;
+			}
+		}
+		for (; k; k--) {
+			a += *p++; b += a;
+		}
+		a %= ADLER_MOD;
+		b %= ADLER_MOD;
+	}
+	a_out = a;
+	b_out = b;
+}
+
+/* the pair of a range followed by a second one of len2 bytes: a = a1 + a2 - 1, b = b1 + b2 + len2 * (a1 - 1), all mod
+ * ADLER_MOD.  Every operand is below ADLER_MOD, so the product stays below 2^32 and is reduced before anything is added */
+__device__ __forceinline__ void adler_combine(uint32_t &a1, uint32_t &b1, uint32_t a2, uint32_t b2, uint32_t len2_mod)
+{
+	const uint32_t a1m = (a1 + ADLER_MOD - 1u) % ADLER_MOD;
+	b1 = ((b1 + b2) % ADLER_MOD + (len2_mod * a1m) % ADLER_MOD) % ADLER_MOD;
+	a1 = (a1m + a2) % ADLER_MOD;
+}
+
+/*
+ * One wave per range, laid out as crc32_wave lays it out: right-aligned in 64 virtual chunks of S bytes, lane i owns
+ * chunk i, lanes in front of the first real byte hold the empty pair (1, 0).  The shuffle tree joins a lane's group with
+ * the group of 2^k chunks to its right; whenever the left group holds a byte the right one is full, and an empty left
+ * group has a - 1 == 0, so len2 = S * 2^k serves every lane that lane 0's value comes from.
+ */
+__device__ __forceinline__ uint32_t adler32_wave(const uint8_t *p, uint32_t len, uint32_t seed, int lane)
+{
+	if (len == 0)
+		return seed;
+	const uint32_t S = ((len + 63) / 64 + 15) & ~15u;
+	const uint64_t pad = 64ull * S - len;
+	const uint64_t vbeg = (uint64_t)lane * S, vend = vbeg + S;
+	uint32_t a = 1, b = 0;
+	if (vend > pad) {
+		const uint64_t lo = vbeg < pad ? pad : vbeg;
+		adler_run(p + (lo - pad), (uint32_t)(vend - lo), a, b);
+	}
+	uint32_t l2 = S % ADLER_MOD;
+#pragma unroll
+	for (int k = 0; k < 6; k++) {
+		const uint32_t ra = __shfl_down(a, 1 << k, 64), rb = __shfl_down(b, 1 << k, 64);
+		adler_combine(a, b, ra, rb, l2);
+		l2 = (l2 * 2u) % ADLER_MOD;
+	}
+	/* the running value in front of the whole range */
+	uint32_t sa = seed & 0xffffu, sb = seed >> 16;
+	sa %= ADLER_MOD; sb %= ADLER_MOD;
+	adler_combine(sa, sb, a, b, len % ADLER_MOD);
+	return (sb << 16) | sa;	/* valid in lane 0 */
+}
+
+__global__ __launch_bounds__(256) void adler32_many_kernel(const uint8_t *__restrict__ base,
+    const la_hash_job *__restrict__ jobs, uint32_t n, uint32_t *__restrict__ out)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+	for (uint32_t i = wave; i < n; i += nwaves) {
+		const la_hash_job j = jobs[i];
+		const uint32_t c = adler32_wave(base + j.off, j.len, j.seed, lane);
+		if (lane == 0)
+			out[i] = c;
+	}
+}
+
+void la_launch_adler32_many(hipStream_t s, const uint8_t *d_base, const la_hash_job *d_jobs,
+    uint32_t n, uint32_t *d_out)
+{
+	if (n == 0) return;
+	uint32_t blocks = (n + 3) / 4;
+	if (blocks > 256 * 8) blocks = 256 * 8;
+	hipLaunchKernelGGL(adler32_many_kernel, dim3(blocks), dim3(256), 0, s, d_base, d_jobs, n, d_out);
 }
 
 /* ------------------------------------------------------------------ gzip trailer */

@@ -1,7 +1,7 @@
 /*
  * la_bid_policy.c -- the host code the read filters (la_filter_lz4.c, la_filter_gzip.c, la_filter_zstd.c,
- * la_filter_bzip2.c, la_filter_xz.c, la_filter_lzip.c) share: the bid policy, below it the window plumbing, and at the end
- * the held-back delivery of the bzip2, xz and lzip filters.
+ * la_filter_bzip2.c, la_filter_xz.c, la_filter_lzip.c, la_filter_lzop.c) share: the bid policy, below it the window
+ * plumbing, and at the end the held-back delivery of the bzip2, xz, lzip and lzop filters.
  *
  * Bid policy: should the GPU filter take this stream at all?
  *
@@ -19,6 +19,8 @@
  *   - otherwise the first unit is larger than the look-ahead: declined (bid 0).
  * An .lz stream (la_filter_lzip.c) is taken when the look-ahead shows a second member header that the member size in
  * front of it confirms: a first member longer than the look-ahead is one serial chain.
+ * An .lzo stream (la_filter_lzop.c) is taken when its first block ends inside the look-ahead: every block header carries
+ * both of its sizes, and a block longer than the look-ahead is one serial chain.
  * An .xz stream (la_filter_xz.c) is taken when its first block header carries a compressed size (xz -T, pixz: the
  * host hops from header to header); a block without one is a serial chain of unknown extent.
  * LA_ZSTD_BLOCKS=1 makes one long zstd frame a parallel unit (its blocks), and the zstd bidder takes it.
@@ -210,6 +212,47 @@ int la_bid_lzip_parallel(const unsigned char *p, size_t n, size_t lookahead)
 			return 1;
 	}
 	return 0;
+}
+
+/* lzop: 1 = take it: the look-ahead holds the whole stream, or the first block ends inside it (`lzop` writes blocks of
+ * 256 KiB, and a stream is then thousands of them).  A first block longer than the look-ahead is one serial chain: the
+ * format allows blocks of up to 64 MiB.  p[0, 9) is the magic.  The header's fields are walked as la_filter_lzop.c walks
+ * them (lzop.c:221-296), its checksum and refusals left to the filter: a header the walk cannot follow is taken, so
+ * that the filter says what is wrong with it. */
+int la_bid_lzop_parallel(const unsigned char *p, size_t n, size_t lookahead)
+{
+	if (n < lookahead || n < 9 + 29)
+		return 1;
+	size_t at = 9;
+	const unsigned version = ((unsigned)p[at] << 8) | p[at + 1];
+	at += 4;
+	if (version >= 0x940)
+		at += 2;
+	at += 1;
+	if (version >= 0x940)
+		at += 1;
+	const uint32_t flags = (uint32_t)p[at] << 24 | (uint32_t)p[at + 1] << 16 | (uint32_t)p[at + 2] << 8 | p[at + 3];
+	at += 4;
+	if (flags & 0x0800u)
+		at += 4;
+	at += 4 + (version >= 0x940 ? 8 : 4);
+	at += 1 + (size_t)p[at] + 4;	/* the name and the header's checksum */
+	if (flags & 0x0040u) {
+		if (at > n || n - at < 4)
+			return 0;
+		const uint64_t skip = ((uint64_t)p[at] << 24 | (uint64_t)p[at + 1] << 16 | (uint64_t)p[at + 2] << 8 | p[at + 3]) + 8;
+		if (skip > n - at)
+			return 0;
+		at += (size_t)skip;
+	}
+	if (at > n || n - at < 8)
+		return 0;
+	const uint32_t usize = (uint32_t)p[at] << 24 | (uint32_t)p[at + 1] << 16 | (uint32_t)p[at + 2] << 8 | p[at + 3];
+	const uint32_t csize = (uint32_t)p[at + 4] << 24 | (uint32_t)p[at + 5] << 16 | (uint32_t)p[at + 6] << 8 | p[at + 7];
+	if (usize == 0 || usize > ((uint32_t)64 << 20) || csize > usize)
+		return 1;	/* an empty part, or a header the filter refuses */
+	/* (at most two checksum words stand between the sizes and the data) */
+	return (uint64_t)csize + 16 <= n - at;
 }
 
 /*

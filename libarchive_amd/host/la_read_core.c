@@ -131,6 +131,7 @@ int archive_read_support_filter_none(struct archive *a) { (void)a; return ARCHIV
 extern int archive_read_support_filter_bzip2(struct archive *) __attribute__((weak));
 extern int archive_read_support_filter_xz(struct archive *) __attribute__((weak));	/* la_filter_xz.c, the same way */
 extern int archive_read_support_filter_lzip(struct archive *) __attribute__((weak));	/* la_filter_lzip.c */
+extern int archive_read_support_filter_lzop(struct archive *) __attribute__((weak));	/* la_filter_lzop.c */
 
 int archive_read_support_filter_all(struct archive *a)
 {
@@ -144,6 +145,8 @@ int archive_read_support_filter_all(struct archive *a)
 		archive_read_support_filter_xz(a);
 	if (archive_read_support_filter_lzip)
 		archive_read_support_filter_lzip(a);
+	if (archive_read_support_filter_lzop)
+		archive_read_support_filter_lzop(a);
 	archive_clear_error(a);
 	return ARCHIVE_OK;
 }

@@ -164,6 +164,16 @@ static inline uint32_t archive_le32dec(const void *pp)	/* archive_endian.h */
 	const unsigned char *p = (const unsigned char *)pp;
 	return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
+static inline uint16_t archive_be16dec(const void *pp)
+{
+	const unsigned char *p = (const unsigned char *)pp;
+	return (uint16_t)(((unsigned)p[0] << 8) | p[1]);
+}
+static inline uint32_t archive_be32dec(const void *pp)
+{
+	const unsigned char *p = (const unsigned char *)pp;
+	return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+}
 
 #endif /* !LA_IN_LIBARCHIVE */
 #endif

@@ -1,0 +1,846 @@
+"""Support for the lzop tests: the LZO1X rules in Python, an instruction emitter, a small greedy compressor over it, lzop
+container builders, and the reference's read loop restated over the Python decoder.
+
+No liblzo2, no lzop and no python-lzo stand behind this file.  decode() is written from the format description that
+libarchive_amd/csrc/la_lzo_dev.h states too; what pins it is independent: every block of the reference's seven lzop
+fixtures carries the Adler-32 of its decoded bytes, and tests/test_lzo_rules.py holds decode() to all of them.  The
+fixtures exercise only part of the format (FIXTURE_FORMS below, asserted by the same test); for a first byte above 17,
+both M1 forms and M4 the oracle rests on the description alone.
+
+reference_read() is lzop_filter_read + consume_header + consume_block_info
+(libarchive/archive_read_support_filter_lzop.c:201-483) in Python, statement for statement, with decode() where the
+reference calls lzo1x_decompress_safe.  It returns (bytes in front of the error or all of them, the filter's return
+code: 0, -25 ARCHIVE_FAILED or -30 ARCHIVE_FATAL, message)."""
+import ctypes as C
+import functools
+import json
+import os
+import struct
+import zlib
+
+import xz_support as XS
+
+ARCHIVE_FAILED, ARCHIVE_FATAL = -25, -30
+ARCHIVE_FILTER_LZOP = 11
+MAGIC = b"\x89\x4c\x5a\x4f\x00\x0d\x0a\x1a\x0a"
+FILTER, CRC32_HEADER, EXTRA_FIELD = 0x0800, 0x1000, 0x0040
+ADLER32_UNCOMPRESSED, ADLER32_COMPRESSED, CRC32_UNCOMPRESSED, CRC32_COMPRESSED = 0x0001, 0x0002, 0x0100, 0x0200
+MAX_BLOCK_SIZE = 64 * 1024 * 1024
+E_TRUNCATED, E_HEADER, E_VERSION, E_METHOD, E_LEVEL, E_DATA = ("Truncated lzop data", "Corrupted lzop header", "Invalid required version",
+                                                               "Unsupported method", "Invalid level", "Corrupted data")
+E_LZO = "lzop decompression failed: %d"
+# liblzo2's codes for the verdicts of decode()
+LZO_CODE = {"INPUT_OVERRUN": -4, "OUTPUT_OVERRUN": -5, "LOOKBEHIND": -6, "NOT_CONSUMED": -8}
+
+text, noise, letters, flip = XS.text, XS.noise, XS.letters, XS.flip
+
+
+# ---- the LZO1X rules ---------------------------------------------------------------------------------------------------
+
+def decode(src, dst_len, forms=None):
+    """One block's stream: (verdict, bytes, consumed).  verdict is "OK", "INPUT_OVERRUN", "OUTPUT_OVERRUN", "LOOKBEHIND",
+    "NOT_CONSUMED" or "SHORT_OUTPUT"; the bytes in front of a failure are valid.  `forms`, a set, collects the names of
+    the instruction forms met."""
+    src = bytes(src)
+    n_src = len(src)
+    out = bytearray()
+    forms = forms if forms is not None else set()
+    ip = 0
+    state = 0
+
+    def run(base):
+        """a zero-run length from `base`, or None when it runs off the input"""
+        nonlocal ip
+        n = base
+        zeros = 0
+        while True:
+            if ip >= n_src:
+                return None
+            b = src[ip]
+            ip += 1
+            if b:
+                if zeros:
+                    forms.add("zero_bytes")
+                return n + b
+            n += 255
+            zeros += 1
+
+    def literals(n):
+        """None, or the verdict that stops them"""
+        nonlocal ip
+        if n > dst_len - len(out):
+            return "OUTPUT_OVERRUN"
+        if n > n_src - ip:
+            return "INPUT_OVERRUN"
+        out.extend(src[ip:ip + n])
+        ip += n
+        return None
+
+    def done(verdict):
+        return verdict, bytes(out), ip
+
+    if n_src and src[0] > 17:
+        n = src[0] - 17
+        ip = 1
+        forms.add("first_byte_short" if n < 4 else "first_byte_long")
+        v = literals(n)
+        if v:
+            return done(v)
+        state = min(n, 4)
+    while True:
+        if ip >= n_src:
+            return done("INPUT_OVERRUN")
+        t = src[ip]
+        ip += 1
+        if t < 16 and state == 0:
+            n = t
+            if n == 0:
+                n = run(15)
+                if n is None:
+                    return done("INPUT_OVERRUN")
+                forms.add("literals_long")
+            else:
+                forms.add("literals_short")
+            v = literals(n + 3)
+            if v:
+                return done(v)
+            state = 4
+            continue
+        if t < 16:
+            if ip >= n_src:
+                return done("INPUT_OVERRUN")
+            dist = (src[ip] << 2) + (t >> 2) + (2049 if state == 4 else 1)
+            ip += 1
+            mlen = 3 if state == 4 else 2
+            forms.add("m1_3byte" if state == 4 else "m1_2byte")
+            trail = t & 3
+        elif t >= 64:
+            if ip >= n_src:
+                return done("INPUT_OVERRUN")
+            dist = (src[ip] << 3) + ((t >> 2) & 7) + 1
+            ip += 1
+            mlen = (t >> 5) + 1
+            forms.add("m2")
+            trail = t & 3
+        else:
+            m3 = t >= 32
+            mlen = t & (31 if m3 else 7)
+            if mlen == 0:
+                mlen = run(31 if m3 else 7)
+                if mlen is None:
+                    return done("INPUT_OVERRUN")
+                form = "m3_long" if m3 else "m4_long"
+            else:
+                form = "m3_short" if m3 else "m4_short"
+            mlen += 2
+            if n_src - ip < 2:
+                return done("INPUT_OVERRUN")
+            w = src[ip] | (src[ip + 1] << 8)
+            ip += 2
+            trail = w & 3
+            if m3:
+                dist = (w >> 2) + 1
+            else:
+                d = ((t & 8) << 11) + (w >> 2)
+                if d == 0:
+                    forms.add("end")
+                    return done("NOT_CONSUMED" if ip != n_src else "SHORT_OUTPUT" if len(out) != dst_len else "OK")
+                dist = d + 16384
+            forms.add(form)
+        if dist > len(out):
+            return done("LOOKBEHIND")
+        if mlen > dst_len - len(out):
+            return done("OUTPUT_OVERRUN")
+        if dist < mlen:
+            forms.add("overlap")
+        start = len(out) - dist
+        if dist >= mlen:
+            out.extend(out[start:start + mlen])
+        else:
+            for i in range(mlen):
+                out.append(out[start + i])
+        forms.add("trail_%d" % trail)
+        if trail:
+            v = literals(trail)
+            if v:
+                return done(v)
+        state = trail
+
+
+# ---- an instruction emitter ------------------------------------------------------------------------------------------------
+
+def _run(v):
+    """the bytes of a zero-run that adds v (>= 1) to its base"""
+    zeros = (v - 1) // 255
+    return bytes(zeros) + bytes([v - 255 * zeros])
+
+
+class Emitter:
+    """Writes instructions and keeps the bytes they stand for.  Every method checks that the form may stand here (the
+    state rule) and that its fields are in range; `check=False` lets a test write a match that reaches in front of
+    the block."""
+
+    def __init__(self):
+        self.out = bytearray()      # the stream
+        self.plain = bytearray()    # what it decodes to
+        self.state = 0
+        self.marker = b""
+
+    def _lit(self, data):
+        self.out += data
+        self.plain += data
+
+    def first_literals(self, data):
+        assert not self.out and 1 <= len(data) <= 238
+        self.out.append(17 + len(data))
+        self._lit(data)
+        self.state = min(len(data), 4)
+        return self
+
+    def literals(self, data):
+        n = len(data)
+        assert self.state == 0 and n >= 4
+        self.out += bytes([n - 3]) if n <= 18 else b"\x00" + _run(n - 3 - 15)
+        self._lit(data)
+        self.state = 4
+        return self
+
+    def _match(self, dist, mlen, trail, check):
+        if check:
+            assert dist <= len(self.plain), "the match starts in front of the block"
+        start = len(self.plain) - dist
+        for i in range(mlen):
+            self.plain.append(self.plain[start + i] if start + i >= 0 else 0)
+        assert len(trail) <= 3
+        self._lit(trail)
+        self.state = len(trail)
+
+    def m1(self, dist, trail=b"", check=True):
+        """2 bytes behind 1..3 literals (length 2, distance 1..1024), 3 bytes behind a literal run (length 3, 2049..3072)"""
+        assert self.state != 0
+        base, mlen = (2049, 3) if self.state == 4 else (1, 2)
+        d = dist - base
+        assert 0 <= d < 1024
+        self.out += bytes([((d & 3) << 2) | len(trail), d >> 2])
+        self._match(dist, mlen, trail, check)
+        return self
+
+    def m2(self, dist, mlen, trail=b"", check=True):
+        assert 3 <= mlen <= 8 and 1 <= dist <= 2048
+        d = dist - 1
+        self.out += bytes([((mlen - 1) << 5) | ((d & 7) << 2) | len(trail), d >> 3])
+        self._match(dist, mlen, trail, check)
+        return self
+
+    def m3(self, dist, mlen, trail=b"", check=True):
+        assert mlen >= 3 and 1 <= dist <= 16384
+        self.out += bytes([32 | (mlen - 2)]) if mlen - 2 <= 31 else bytes([32]) + _run(mlen - 2 - 31)
+        self.out += struct.pack("<H", ((dist - 1) << 2) | len(trail))
+        self._match(dist, mlen, trail, check)
+        return self
+
+    def m4(self, dist, mlen, trail=b"", check=True):
+        assert mlen >= 3 and 16385 <= dist <= 49151
+        d = dist - 16384
+        t = 16 | ((d >> 14) << 3)
+        self.out += bytes([t | (mlen - 2)]) if mlen - 2 <= 7 else bytes([t]) + _run(mlen - 2 - 7)
+        self.out += struct.pack("<H", ((d & 0x3FFF) << 2) | len(trail))
+        self._match(dist, mlen, trail, check)
+        return self
+
+    def end(self, marker=b"\x11\x00\x00"):
+        self.marker = marker
+        return self
+
+    def stream(self):
+        return bytes(self.out) + self.marker
+
+
+# ---- a small greedy compressor over the emitter ---------------------------------------------------------------------------------
+
+def compress(plain):
+    """an LZO1X stream of `plain`: greedy, a table of the last position of every four bytes, M2 / M3 / M4 by distance"""
+    plain = bytes(plain)
+    n = len(plain)
+    e = Emitter()
+    table = {}
+    lit_from = 0        # literals plain[lit_from, i) wait for the next match
+    pending = None      # the match in front of them: (dist, mlen)
+
+    def flush(upto):
+        """the pending match with up to 3 of the literals as its trail, then the rest as a run"""
+        nonlocal pending, lit_from
+        lits = plain[lit_from:upto]
+        if pending is None:
+            if not lits:
+                return
+            if len(lits) <= 238:
+                e.first_literals(lits)
+            else:
+                e.literals(lits)
+        else:
+            dist, mlen = pending
+            trail = lits if len(lits) <= 3 else b""
+            if dist <= 2048 and mlen <= 8:
+                e.m2(dist, mlen, trail)
+            elif dist <= 16384:
+                e.m3(dist, mlen, trail)
+            else:
+                e.m4(dist, mlen, trail)
+            if len(lits) > 3:
+                e.literals(lits)
+        pending = None
+        lit_from = upto
+
+    i = 0
+    while i + 4 <= n:
+        key = plain[i:i + 4]
+        cand = table.get(key)
+        table[key] = i
+        if cand is None or i - cand > 49151 or (pending is None and i == 0):
+            i += 1
+            continue
+        mlen = 4
+        while i + mlen < n and plain[cand + mlen] == plain[i + mlen]:
+            mlen += 1
+        flush(i)
+        pending = (i - cand, mlen)
+        i += mlen
+        lit_from = i
+    flush(n)
+    if pending is not None:
+        flush(n)
+    e.end()
+    assert bytes(e.plain) == plain
+    return e.stream()
+
+
+# ---- lzop containers ---------------------------------------------------------------------------------------------------
+
+def _sum(data, crc):
+    return zlib.crc32(data) if crc else zlib.adler32(data)
+
+
+def header(version=0x1030, flags=ADLER32_UNCOMPRESSED, method=1, level=5, name=b"", reqversion=0x0940, filter_word=0, extra=None,
+           checksum=None, lib_version=0x2060):
+    """magic and header of one part; `checksum` overrides the header's own"""
+    h = struct.pack(">HH", version, lib_version)
+    if version >= 0x940:
+        h += struct.pack(">H", reqversion)
+    h += bytes([method])
+    if version >= 0x940:
+        h += bytes([level])
+    h += struct.pack(">I", flags)
+    if flags & FILTER:
+        h += struct.pack(">I", filter_word)
+    h += struct.pack(">I", 0o100644)
+    h += struct.pack(">II", 0x5F000000, 0) if version >= 0x940 else struct.pack(">I", 0x5F000000)
+    h += bytes([len(name)]) + name
+    h += struct.pack(">I", _sum(h, flags & CRC32_HEADER) if checksum is None else checksum)
+    if flags & EXTRA_FIELD:
+        x = b"extra" if extra is None else extra
+        h += struct.pack(">I", len(x)) + x + struct.pack(">I", _sum(x, flags & CRC32_HEADER))
+    return MAGIC + h
+
+
+def block(plain, flags=ADLER32_UNCOMPRESSED, stored=None, comp=None, sum_u=None, sum_c=None):
+    """one block: its info words and data.  stored None: as lzop does, stored when compression does not shrink it"""
+    plain = bytes(plain)
+    if comp is None:
+        comp = compress(plain) if stored is not True else plain
+    if stored is True or (stored is None and len(comp) >= len(plain)):
+        comp = plain
+    b = struct.pack(">II", len(plain), len(comp))
+    if flags & (CRC32_UNCOMPRESSED | ADLER32_UNCOMPRESSED):
+        b += struct.pack(">I", _sum(plain, flags & CRC32_UNCOMPRESSED) if sum_u is None else sum_u)
+    if flags & (CRC32_COMPRESSED | ADLER32_COMPRESSED) and len(comp) < len(plain):
+        b += struct.pack(">I", _sum(comp, flags & CRC32_COMPRESSED) if sum_c is None else sum_c)
+    return b + comp
+
+
+def part(plain, block_size=4096, flags=ADLER32_UNCOMPRESSED, **kw):
+    """one part: header, the blocks of `plain`, the closing size word"""
+    plain = bytes(plain)
+    blocks = b"".join(block(plain[i:i + block_size], flags) for i in range(0, len(plain), block_size))
+    return header(flags=flags, **kw) + blocks + bytes(4)
+
+
+def bid(image):
+    return 72 if bytes(image[:9]) == MAGIC else 0
+
+
+def reference_read(image, read_size=None, forms=None, on_block=None):
+    """read_size is taken for the signature's sake: the reference asks upstream for whole headers and blocks, and a memory
+    reader answers those the same whatever its block size.  on_block(decoded bytes, flags, stored checksum word) sees
+    every block that decoded."""
+    image = bytes(image)
+    if not bid(image):
+        raise ValueError("the bidder would not take this image: no lzop filter is created")
+    S = {"pos": 0, "flags": 0, "ccksum": 0, "ucksum": 0, "in_stream": False}
+    out = bytearray()
+
+    def ahead(n):
+        return S["pos"] if len(image) - S["pos"] >= n else None
+
+    def be16(o):
+        return struct.unpack_from(">H", image, o)[0]
+
+    def be32(o):
+        return struct.unpack_from(">I", image, o)[0]
+
+    def consume_header():
+        p = ahead(9)
+        if p is None or image[p:p + 9] != MAGIC:
+            return "eof", ""
+        S["pos"] += 9
+        p = ahead(29)
+        if p is None:
+            return ARCHIVE_FAILED, E_TRUNCATED
+        _p = p
+        version = be16(p)
+        p += 4
+        if version >= 0x940:
+            if be16(p) < 0x900:
+                return ARCHIVE_FAILED, E_VERSION
+            p += 2
+        method = image[p]
+        p += 1
+        if method < 1 or method > 3:
+            return ARCHIVE_FAILED, E_METHOD
+        if version >= 0x940:
+            level = image[p]
+            p += 1
+            if level > 9:
+                return ARCHIVE_FAILED, E_LEVEL
+        flags = be32(p)
+        p += 4
+        if flags & FILTER:
+            p += 4
+        p += 4
+        p += 8 if version >= 0x940 else 4
+        ln = image[p]
+        p += 1
+        ln += p - _p
+        p = ahead(ln + 4)
+        if p is None:
+            return ARCHIVE_FAILED, E_TRUNCATED
+        if be32(p + ln) != _sum(image[p:p + ln], flags & CRC32_HEADER):
+            return ARCHIVE_FAILED, E_HEADER
+        S["pos"] += ln + 4
+        if flags & EXTRA_FIELD:
+            p = ahead(4)
+            if p is None:
+                return ARCHIVE_FAILED, E_TRUNCATED
+            S["pos"] = min(S["pos"] + be32(p) + 4 + 4, len(image))    # (a consume past the end, its answer ignored)
+        S["flags"] = flags
+        S["in_stream"] = True
+        return 0, ""
+
+    def consume_block_info():
+        flags = S["flags"]
+        p = ahead(4)
+        if p is None:
+            return ARCHIVE_FAILED, E_TRUNCATED
+        S["usize"] = be32(p)
+        S["pos"] += 4
+        if S["usize"] == 0:
+            return "eof", ""
+        if S["usize"] > MAX_BLOCK_SIZE:
+            return ARCHIVE_FAILED, E_HEADER
+        p = ahead(4)
+        if p is None:
+            return ARCHIVE_FAILED, E_TRUNCATED
+        S["csize"] = be32(p)
+        S["pos"] += 4
+        if S["csize"] > S["usize"]:
+            return ARCHIVE_FAILED, E_HEADER
+        if flags & (CRC32_UNCOMPRESSED | ADLER32_UNCOMPRESSED):
+            p = ahead(4)
+            if p is None:
+                return ARCHIVE_FAILED, E_TRUNCATED
+            S["ccksum"] = S["ucksum"] = be32(p)
+            S["pos"] += 4
+        if flags & (CRC32_COMPRESSED | ADLER32_COMPRESSED) and S["csize"] < S["usize"]:
+            p = ahead(4)
+            if p is None:
+                return ARCHIVE_FAILED, E_TRUNCATED
+            S["ccksum"] = be32(p)
+            S["pos"] += 4
+        return 0, ""
+
+    while True:                     # one lzop_filter_read per turn
+        while True:
+            if not S["in_stream"]:
+                rc, msg = consume_header()
+                if rc == "eof":
+                    return bytes(out), 0, ""
+                if rc:
+                    return bytes(out), rc, msg
+            rc, msg = consume_block_info()
+            if rc == "eof":
+                S["in_stream"] = False
+                continue
+            if rc:
+                return bytes(out), rc, msg
+            break
+        flags, csize, usize = S["flags"], S["csize"], S["usize"]
+        b = ahead(csize)
+        if b is None:
+            return bytes(out), ARCHIVE_FATAL, E_TRUNCATED
+        data = image[b:b + csize]
+        if flags & CRC32_COMPRESSED:
+            cksum = zlib.crc32(data)
+        elif flags & ADLER32_COMPRESSED:
+            cksum = zlib.adler32(data)
+        else:
+            cksum = S["ccksum"]
+        if cksum != S["ccksum"]:
+            return bytes(out), ARCHIVE_FATAL, E_DATA
+        if usize == csize:
+            out += data
+            S["pos"] += csize
+            continue
+        verdict, plain, _ = decode(data, usize, forms)
+        if verdict == "SHORT_OUTPUT":
+            return bytes(out), ARCHIVE_FATAL, E_DATA
+        if verdict != "OK":
+            return bytes(out), ARCHIVE_FATAL, E_LZO % LZO_CODE[verdict]
+        if on_block:
+            on_block(plain, flags, S["ucksum"])
+        if flags & CRC32_UNCOMPRESSED:
+            cksum = zlib.crc32(plain)
+        elif flags & ADLER32_UNCOMPRESSED:
+            cksum = zlib.adler32(plain)
+        else:
+            cksum = S["ucksum"]
+        if cksum != S["ucksum"]:
+            return bytes(out), ARCHIVE_FATAL, E_DATA
+        S["pos"] += csize
+        out += plain
+
+
+def reference_cat(image, read_size=None):
+    """What the whole read stack gives: a filter is put on a filter's output as long as a bidder takes it; every failed
+    read is fatal to the read core"""
+    data, rc, msg = reference_read(image, read_size)
+    while rc == 0 and bid(data):
+        data, rc, msg = reference_read(data)
+    return data, (ARCHIVE_FATAL if rc else 0), msg
+
+
+FIXTURE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_fixtures", "lzop")
+
+
+def fixtures():
+    """[(manifest entry, image bytes)]"""
+    with open(os.path.join(FIXTURE_DIR, "manifest.json")) as f:
+        man = json.load(f)
+    return [(m, open(os.path.join(FIXTURE_DIR, m["file"]), "rb").read()) for m in man]
+
+
+# the instruction forms the seven fixtures exercise (tests/test_lzo_rules.py asserts the list), and all that decode() names
+FIXTURE_FORMS = {"literals_short", "literals_long", "m2", "m3_short", "m3_long", "zero_bytes", "trail_0", "trail_1", "trail_2", "trail_3",
+                 "overlap", "end"}
+ALL_FORMS = FIXTURE_FORMS | {"first_byte_short", "first_byte_long", "m1_2byte", "m1_3byte", "m4_short", "m4_long"}
+
+
+# ---- the rules cases: hand-built streams of the rules test and the device test ------------------------------------------------
+
+LIT_RUNS = (18, 19, 273, 274, 528)
+M3_LENS = (33, 34, 288, 289)
+M4_LENS = (9, 10, 264, 265)
+DISTANCES = (1, 2, 63, 64, 65, 2048, 2049, 3072, 16384, 16385, 32768, 49151)
+
+
+def _filled(n, seed=1):
+    """an emitter with n bytes of noise in front (first byte form for up to 238 bytes, else a literal run)"""
+    e = Emitter()
+    data = noise(seed, n, 200)
+    return e.first_literals(data) if n <= 238 else e.literals(data)
+
+
+def _match_at(e, dist, mlen=6, trail=b"", check=True):
+    """a match of the form the distance asks for"""
+    if dist <= 2048 and mlen <= 8:
+        return e.m2(dist, mlen, trail, check)
+    if dist <= 16384:
+        return e.m3(dist, mlen, trail, check)
+    return e.m4(dist, mlen, trail, check)
+
+
+@functools.lru_cache(maxsize=None)
+def rules_cases():
+    """name -> (stream, dst_len, expected verdict, expected bytes).  The expected bytes come from the EMITTER's own
+    book-keeping, not from decode(): the two are held against each other."""
+    out = {}
+
+    def put(name, e, verdict="OK", dst_len=None, stream=None, valid=None):
+        # the device ABI refuses a block whose stream is longer than its bytes and copies one that is as long (the container
+        # holds such a block stored), so a stream that ends well is made to grow: a run of its last byte behind everything
+        # the case is about
+        while verdict == "OK" and e.plain and len(e.stream()) >= len(e.plain):
+            e.m3(1, len(e.stream()) - len(e.plain) + 8)
+        plain = bytes(e.plain)
+        out[name] = (e.stream() if stream is None else stream, len(plain) if dst_len is None else dst_len, verdict,
+                     plain if valid is None else plain[:valid])
+
+    # every instruction form
+    put("empty", Emitter().end())
+    for n in (1, 2, 3, 4, 5, 238):
+        put("first_byte_%d" % n, Emitter().first_literals(noise(n, n)).m2(1, 3).end() if n < 4 else Emitter().first_literals(noise(n, n)).end())
+    put("first_byte_17_is_m4", Emitter().end(b"\x11\x00\x00"))
+    for n in (4, 5, 17, 18) + LIT_RUNS:
+        put("literals_%d" % n, Emitter().literals(noise(n, n)).end())
+    for k in (1, 2, 3):
+        for dist in (1, 2, 3, 4, 5, 1024):
+            put("m1_2byte_after_%d_dist_%d" % (k, dist), _filled(1100).m2(7, 3, noise(k, k)).m1(dist, noise(9, k % 3)).end())
+    put("m1_2byte_after_first_byte", Emitter().first_literals(b"abc").m1(2, b"z").m1(1).end())
+    for dist in (2049, 2050, 2052, 3072):
+        put("m1_3byte_dist_%d" % dist, _filled(3100).m1(dist, b"q").m2(5, 4).literals(b"wxyz").m1(dist).end())
+    put("m1_3byte_after_first_byte_run", _filled(3100).m2(5, 4).literals(noise(3, 9)).m1(2100, b"ab").end())
+    for mlen in range(3, 9):
+        for trail in range(4):
+            put("m2_len_%d_trail_%d" % (mlen, trail), _filled(300).m2(17 * mlen, mlen, noise(mlen, trail)).end())
+    for mlen in (3, 4, 32) + M3_LENS:
+        put("m3_len_%d" % mlen, _filled(300).m3(100, mlen, b"t").m3(7, mlen).end())
+    for mlen in (3, 4, 8) + M4_LENS:
+        put("m4_len_%d" % mlen, _filled(17000).m4(16500, mlen, b"tt").m4(16385, mlen).end())
+    put("m4_high_bit", _filled(40000).m4(32768, 5).m4(32767, 5).m4(32769, 300, b"abc").end())
+    for dist in DISTANCES:
+        for mlen in (3, 6, 70, 200):
+            put("dist_%d_len_%d" % (dist, mlen), _match_at(_filled(dist + 10, dist), dist, mlen, b"x").end())
+    put("overlap_chain", _filled(5).m2(1, 8).m3(2, 100).m3(3, 129, b"ab").m3(64, 500).m3(63, 500).m3(65, 500).end())
+    # the end marker whatever its length field and w's low bits say
+    for name, marker in (("len_field", b"\x13\x00\x00"), ("low_bits", b"\x11\x03\x00"), ("zero_run", b"\x10\x00\x05\x00\x00"), ("both", b"\x17\x02\x00")):
+        put("end_marker_" + name, _filled(20).end(marker))
+    # a match that reaches output byte 0, and one byte in front of it
+    put("reaches_byte_0", _filled(100).m2(100, 8).end())
+    put("lookbehind_by_one", _filled(100).m2(101, 8, check=False).end(), "LOOKBEHIND", dst_len=4096, valid=100)
+    put("lookbehind_far", _filled(5000).m4(20000, 8, check=False).end(), "LOOKBEHIND", dst_len=65536, valid=5000)
+    put("lookbehind_at_start", Emitter().m4(16385, 3, check=False).end(), "LOOKBEHIND", dst_len=64, valid=0)
+    # the other pinned verdicts, one violation per stream, far from every other limit
+    e = _filled(300).m3(100, 400).literals(noise(5, 50))
+    put("output_overrun_match", _filled(300).m3(100, 400).end(), "OUTPUT_OVERRUN", dst_len=500, valid=300)
+    put("output_overrun_literals", e.end(), "OUTPUT_OVERRUN", dst_len=720, valid=700)
+    put("output_overrun_trail", _filled(300).m3(1, 100).m2(9, 4, b"abc").end(), "OUTPUT_OVERRUN", dst_len=406, valid=404)
+    e = _filled(300).m3(100, 400, b"ab").end()
+    put("input_overrun_no_marker", e, "INPUT_OVERRUN", dst_len=4096, stream=e.stream()[:-3])
+    put("input_overrun_in_literals", _filled(300), "INPUT_OVERRUN", dst_len=4096, stream=_filled(300).stream()[:-100], valid=0)
+    put("input_overrun_in_run", Emitter(), "INPUT_OVERRUN", dst_len=4096, stream=b"\x00\x00\x00\x00")
+    put("input_overrun_in_m3", _filled(300), "INPUT_OVERRUN", dst_len=4096, stream=_filled(300).stream() + b"\x25\x01")
+    put("input_overrun_empty", Emitter(), "INPUT_OVERRUN", dst_len=16, stream=b"")
+    e = _filled(300).m3(100, 400).end()
+    put("not_consumed", e, "NOT_CONSUMED", stream=e.stream() + b"\x00" * 40)
+    put("not_consumed_one", e, "NOT_CONSUMED", stream=e.stream() + b"\x11")
+    put("short_output", e, "SHORT_OUTPUT", dst_len=len(e.plain) + 100)
+    put("short_output_one", e, "SHORT_OUTPUT", dst_len=len(e.plain) + 1)
+    # literal runs and matches laid across the payload register window's refills (256 and 512 bytes into the stream)
+    for n in (511, 512, 513):
+        for lead in (0, 1, 250, 255, 256):
+            e = _filled(lead, n) if lead else Emitter()
+            if lead:
+                e.m2(1, 3)
+            put("window_literals_%d_lead_%d" % (n, lead), e.literals(noise(n + lead, n)).m3(n, n).literals(noise(7, n)).m3(5, n, b"xyz").end())
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def cut_stream():
+    """a 2 KB stream of many forms, for the cut at every byte"""
+    e = Emitter().first_literals(b"ab")
+    k = 0
+    while len(e.out) < 2048:
+        k += 1
+        e.m1(1 + k % 2, noise(k, k % 4))
+        if e.state == 0:
+            e.literals(noise(k, 4 + k % 40))
+            e.m1(2049 + k % 7 if len(e.plain) > 2100 else 2049, b"") if len(e.plain) >= 2049 + 7 else e.m2(3, 4)
+        e.m3(1 + k % 50, 3 + (k * 37) % 300, noise(k, 1 + k % 3))
+        if len(e.plain) > 16500:
+            e.m4(16385 + k % 100, 3 + k % 20, b"z")
+        else:
+            e.m2(1 + k % 9, 3 + k % 6, b"q")
+    e.m2(1, 3).end()
+    return e.stream(), bytes(e.plain)
+
+
+# ---- the device ABI through ctypes (the mock library takes host pointers, the device library device pointers) ----------
+
+C_ADLER32, C_CRC32, U_ADLER32, U_CRC32 = 1, 2, 4, 8
+ST = {"OK": 0, "BAD_SUM_C": 41, "INPUT_OVERRUN": 42, "OUTPUT_OVERRUN": 43, "LOOKBEHIND": 44, "NOT_CONSUMED": 45, "SHORT_OUTPUT": 46,
+      "BAD_SUM_U": 47, "REFUSED": 48}
+
+
+class Block(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("dst_off", C.c_uint64), ("src_len", C.c_uint32), ("dst_len", C.c_uint32), ("flags", C.c_uint32),
+                ("sum_c", C.c_uint32), ("sum_u", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Result(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("sum_c", C.c_uint32), ("sum_u", C.c_uint32), ("out_len", C.c_uint32), ("consumed", C.c_uint32)]
+
+
+class Batch(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("d_blocks", C.c_void_p), ("n", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
+
+
+def pack_table(streams):
+    """[(stream, dst_len)] packed back to back: (source image, [Block], total output bytes).  Odd gaps keep the blocks
+    off every alignment."""
+    src = bytearray()
+    blocks = []
+    dst = 0
+    for i, (s, dst_len) in enumerate(streams):
+        src += bytes(i % 3)
+        blocks.append(Block(len(src), dst, len(s), dst_len, 0, 0, 0, 0))
+        src += s
+        dst += dst_len + i % 5
+    return bytes(src), blocks, dst
+
+
+def mock_decode(lib, src, blocks, dst_cap):
+    """la_gpu_lzop_decode of a library that takes host pointers: [(Result, bytes of the block's slot)]"""
+    src = bytes(src)
+    sbuf = C.create_string_buffer(src, max(len(src), 1))
+    tab = (Block * max(len(blocks), 1))(*blocks)
+    res = (Result * max(len(blocks), 1))()
+    dst = C.create_string_buffer(max(dst_cap, 1))
+    bt = Batch(C.addressof(sbuf), len(src), C.addressof(tab), len(blocks), 0, C.addressof(dst), dst_cap, C.addressof(res))
+    lib.la_gpu_lzop_decode.argtypes = [C.c_void_p, C.POINTER(Batch)]
+    assert lib.la_gpu_lzop_decode(None, C.byref(bt)) == 0
+    return [(res[i], dst.raw[b.dst_off:b.dst_off + res[i].out_len]) for i, b in enumerate(blocks)]
+
+
+def rules_decode(lib, stream, dst_len):
+    """la_lzo_dev.h's decoder alone, as tests/mock_lzop exports it: (status name, bytes, consumed)"""
+    names = {v: k for k, v in ST.items()}
+    dst = C.create_string_buffer(max(dst_len, 1))
+    out_len, consumed = C.c_uint32(), C.c_uint32()
+    lib.la_lzo_rules_decode.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.la_lzo_rules_decode.restype = C.c_uint32
+    st = lib.la_lzo_rules_decode(bytes(stream), len(stream), dst, dst_len, C.byref(out_len), C.byref(consumed))
+    return names[st], dst.raw[:out_len.value], consumed.value
+
+
+# ---- stream shapes ---------------------------------------------------------------------------------------------------------
+
+AU, AC, CU, CC = ADLER32_UNCOMPRESSED, ADLER32_COMPRESSED, CRC32_UNCOMPRESSED, CRC32_COMPRESSED
+SUM_FLAGS = (0, AU, AC, CU, CC, AU | AC, CU | CC, AU | CU, AC | CC, AU | CC, CU | AC, AU | AC | CU | CC)
+
+
+def adler_forge(prefix, target, k=700):
+    """prefix + k bytes whose Adler-32 is `target`: the bytes are chosen for the sum a, then units are moved between
+    positions, which keeps a and shifts b by the distance moved"""
+    M = 65521
+    a0, b0 = zlib.adler32(prefix) & 0xFFFF, zlib.adler32(prefix) >> 16
+    need_a = ((target & 0xFFFF) - a0) % M
+    while need_a < 100 * k:
+        need_a += M
+    x = [need_a // k] * k
+    for i in range(need_a - sum(x)):
+        x[i] += 1
+    assert all(0 < v < 255 for v in x)
+    need_b = ((target >> 16) - b0 - k * a0 - sum((k - i) * v for i, v in enumerate(x))) % M
+    i = 0
+    while need_b:
+        step = min(need_b, k - 1 - 2 * i) if k - 1 - 2 * i > 0 else 0
+        assert step > 0
+        x[i] += 1                   # a unit moved from position i + step to i adds `step` to b
+        x[i + step] -= 1
+        need_b -= step
+        i += 1
+    out = bytes(prefix) + bytes(x)
+    assert zlib.adler32(out) == target
+    return out
+
+
+def _handbuilt_block(name, flags=AU):
+    """a block around a rules case that fails inside the stream: the sizes are the case's, the checksum word is beside the point"""
+    stream, dst_len, _, _ = rules_cases()[name]
+    return block(bytes(dst_len), flags, comp=stream, stored=False)
+
+
+@functools.lru_cache(maxsize=None)
+def filter_shapes():
+    """name -> image: the shapes of the filter tests"""
+    t = text(5, 20000)
+    a, b, c = text(1, 5000), noise(2, 700, 16), text(3, 4000)
+    sh = {}
+    sh["one_part"] = part(t)
+    sh["empty_part"] = header() + bytes(4)
+    sh["empty_part_short"] = header(version=0x0930) + bytes(4)        # (fewer than 29 bytes behind the magic: truncated, as the reference says)
+    sh["one_byte"] = part(b"x")
+    for v in (0x0900, 0x0930, 0x0940, 0x1030):
+        sh["version_%04x" % v] = part(a, version=v, name=b"name.txt")
+    for f in SUM_FLAGS:
+        sh["flags_%04x" % f] = part(a + b + c, block_size=1500, flags=f)
+        sh["flags_%04x_crc32_header" % f] = part(a, flags=f | CRC32_HEADER)
+    sh["filter_word"] = part(a, flags=AU | FILTER, filter_word=3)
+    sh["extra_field"] = part(a, flags=AU | EXTRA_FIELD, extra=b"some extra bytes")
+    sh["extra_field_empty_and_filter"] = part(a, flags=AC | EXTRA_FIELD | FILTER, extra=b"", version=0x0930)
+    sh["extra_field_runs_off_the_stream"] = header(flags=AU | EXTRA_FIELD, extra=b"xy")[:-3]
+    sh["long_name"] = part(a, name=b"n" * 255)
+    # the refusals of consume_header and consume_block_info
+    sh["required_version_08ff"] = part(a, reqversion=0x08FF)
+    sh["required_version_0900"] = part(a, reqversion=0x0900)
+    for m in (0, 2, 3, 4):
+        sh["method_%d" % m] = part(a, method=m)
+    for lv in (0, 9, 10):
+        sh["level_%d" % lv] = part(a, level=lv)
+    sh["level_10_old_version"] = part(a, level=10, version=0x0930)    # (no level byte below 0x940)
+    sh["bad_header_checksum"] = part(a, checksum=0x12345678)
+    sh["bad_header_crc32"] = part(a, flags=AU | CRC32_HEADER, checksum=0x12345678)
+    sh["bad_second_header"] = part(a) + part(b, checksum=1) + part(c)
+    sh["block_above_64_mib"] = header() + struct.pack(">II", MAX_BLOCK_SIZE + 1, 5) + bytes(20)
+    sh["block_of_64_mib_truncated"] = header() + struct.pack(">III", MAX_BLOCK_SIZE, 5, 0) + bytes(3)
+    sh["compressed_above_uncompressed"] = header() + block(a[:1000]) + struct.pack(">II", 100, 101) + bytes(200)
+    # parts and junk
+    sh["three_parts"] = part(a) + part(b, flags=CC | CU, version=0x0930) + part(c, flags=0)
+    sh["empty_parts_between"] = part(a) + part(b"") + part(b"") + part(c)
+    sh["junk_behind"] = part(t) + b"junk behind the last part, more than twenty-nine bytes of it, to be ignored"
+    sh["junk_zeros"] = part(a) + bytes(51)
+    sh["junk_short"] = part(a) + b"xyz"
+    sh["junk_is_a_bare_magic"] = part(a) + MAGIC
+    sh["junk_is_most_of_a_magic"] = part(a) + MAGIC[:8]
+    sh["junk_begins_with_a_magic"] = part(a) + MAGIC + b"not a header at all, just some text that follows the nine bytes"
+    sh["junk_inside_a_part_is_a_block"] = header() + block(a) + b"\x00\x00\x00\x05junk"
+    # stored blocks
+    sh["stored_noise"] = part(noise(7, 9000), block_size=2000)
+    for n in (1, 63, 64, 65):
+        sh["stored_%d_between" % n] = header() + block(a) + block(noise(n, n), stored=True) + block(c) + bytes(4)
+    for f in SUM_FLAGS:
+        sh["stored_flags_%04x" % f] = header(flags=f) + block(a[:900], f) + block(noise(8, 500), f, stored=True) + block(c[:900], f) + bytes(4)
+    # the stale checksum: only a *_COMPRESSED flag, so a stored block reads no word and is compared with what is left over
+    first = block(a[:900], AC)
+    left_over = struct.unpack_from(">I", first, 8)[0]
+    sh["stale_sum_fails"] = header(flags=AC) + first + block(noise(8, 500), AC, stored=True) + block(c[:900], AC) + bytes(4)
+    sh["stale_sum_of_the_block_in_front_passes"] = header(flags=AC) + first + block(adler_forge(noise(8, 50), left_over), AC, stored=True) + block(c[:900], AC) + bytes(4)
+    sh["stale_sum_first_block_is_compared_with_0"] = header(flags=AC) + block(noise(8, 500), AC, stored=True) + bytes(4)
+    sh["stale_sum_crc32_fails"] = header(flags=CC) + block(a[:900], CC) + block(noise(8, 500), CC, stored=True) + bytes(4)
+    sh["stale_sum_carries_over_a_part"] = part(a[:900], flags=AC) + header(flags=AC) + block(adler_forge(b"", left_over), AC, stored=True) + bytes(4)
+    # damaged blocks between good ones
+    for k in range(3):
+        parts = [a[:1500], b, c[:1500]]
+        for f, kw in ((AU, {"sum_u": 1}), (AC | AU, {"sum_c": 1}), (CU, {"sum_u": 1}), (CC, {"sum_c": 1}), (AU | AC | CU | CC, {"sum_u": 2})):
+            if k == 1 and "sum_c" in kw:
+                continue        # (a stored block carries no such word)
+            sh["bad_%s_flags_%04x_block_%d" % (list(kw)[0], f, k)] = header(flags=f) + b"".join(block(p, f, **(kw if i == k else {})) for i, p in enumerate(parts)) + bytes(4)
+    for name in ("lookbehind_by_one", "lookbehind_far", "output_overrun_match", "output_overrun_literals", "input_overrun_no_marker", "input_overrun_in_run",
+                 "not_consumed", "not_consumed_one", "short_output", "short_output_one"):
+        sh["handbuilt_" + name] = header() + block(a) + _handbuilt_block(name) + block(c) + bytes(4)
+        sh["handbuilt_first_" + name] = header(flags=0) + _handbuilt_block(name, 0) + block(c, 0) + bytes(4)
+    sh["block_truncated"] = (header() + block(a) + block(c))[:-10]
+    sh["no_closing_word"] = header() + block(a) + block(c)
+    sh["nested"] = part(part(a), block_size=100000)
+    return sh
+
+
+def flip_cases(image, head):
+    """bit positions: every bit of the first `head` bytes behind the magic, every 7th of the rest"""
+    return list(range(9 * 8, (9 + head) * 8)) + list(range((9 + head) * 8, len(image) * 8, 7))
+
+
+def randbytes(seed, n):
+    import random
+    return random.Random(seed).randbytes(n)
