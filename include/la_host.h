@@ -177,8 +177,10 @@ int la_zstd_index_build(const uint8_t *img, uint64_t len, int at_eof, uint64_t o
         uint32_t cap, la_zstd_index_result *res);
 
 /* ---- bid policy (host/la_bid_policy.c): does the stream hold many independent units, or ONE serial one that the
- * reference's own filter decodes faster on a host core?  Used by the three bidders; LA_GPU_BID=all switches it off. ---- */
+ * reference's own filter decodes faster on a host core?  Used by the bidders; LA_GPU_BID=all switches it off. ---- */
 struct archive_read_filter;
+/* 1: the policy is on and a look-ahead of 1024 KiB shows one serial unit (`parallel`, a la_bid_*_parallel below, says 0) */
+int    la_bid_declines(struct archive_read_filter *filter, int (*parallel)(const unsigned char *, size_t, size_t));
 int    la_bid_take_all(void);
 size_t la_bid_lookahead(size_t default_kib);
 const unsigned char *la_bid_peek(struct archive_read_filter *filter, size_t want, size_t *got);
@@ -189,8 +191,8 @@ int    la_bid_xz_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_lzip_parallel(const unsigned char *p, size_t n, size_t lookahead);
 int    la_bid_lzop_parallel(const unsigned char *p, size_t n, size_t lookahead);
 
-/* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the read filters; the held-back delivery at its
- * end by the bzip2 and xz ones ---- */
+/* ---- read-filter window plumbing (host/la_bid_policy.c), shared by the read filters; the held-back delivery and the
+ * reader base at its end by the bzip2, xz, lzip and lzop ones ---- */
 /* LA_GPU_DEVICE: the device ordinal every filter, the ZIP reader and the hash drop-in open (default 0) */
 int  la_env_device(void);
 
@@ -247,7 +249,7 @@ void la_verdict_set(la_verdict *v, int rc, const char *fmt, ...);
 /* sets the message, if any, and returns rc */
 int  la_verdict_report(struct archive_read_filter *self, const la_verdict *v);
 
-/* Decoded bytes held back in front of a possible error (the bzip2, xz and lzip filters).  The reference hands out whole
+/* Decoded bytes held back in front of a possible error (the bzip2, xz, lzip and lzop filters).  The reference hands out whole
  * blocks of LA_OUT_BLOCK bytes and loses the partial block on an error, so with T bytes decoded everything up to the
  * last block boundary strictly below T is safe to hand out; the rest (at most one block) waits for the next window's
  * verdict.  Each filter's head comment derives T and which of its errors is early or late. */
@@ -279,6 +281,37 @@ void    la_holdback_rebase(la_holdback *h);
 ssize_t la_holdback_read(struct archive_read_filter *self, const la_window *w, la_holdback *h, const void **p,
             int (*window)(struct archive_read_filter *));
 void    la_holdback_release(la_gpu_ctx *gpu, la_holdback *h);
+
+/* What a filter that decodes a window of units in one launch and hands the bytes out through la_holdback keeps: each
+ * of the four embeds one as the first member of its private struct.  The walker, the launch and the walk of its
+ * results stay in the filter. */
+typedef struct la_reader {
+	la_window w;
+	la_buf stage; size_t stage_len;	/* pinned: the stream from the first byte of the unfinished unit on */
+	la_buf d_src, d_dst, d_tabs;	/* the window on the device, the decoded bytes, the filter's tables */
+	la_buf h_tabs;			/* the filter's host tables, one zeroed block of the size it asked for */
+	la_holdback hb;
+} la_reader;
+/* The host block, the holdback, the window and its device; out_budget is clamped to max_out_budget (0: left alone).
+ * r NULL (the filter had no memory for its struct) or no memory here: ENOMEM with nomem_msg; no device: la_window_open's
+ * message.  Either way everything is released again and ARCHIVE_FATAL returned. */
+int     la_reader_open(struct archive_read_filter *self, la_reader *r, const char *name, size_t host_tab_bytes,
+            uint64_t max_out_budget, const char *nomem_msg);
+/* la_window_gather, then stage[0, stage_len) uploaded to d_src */
+int     la_reader_gather(struct archive_read_filter *self, la_reader *r);
+/* Append d_dst[0, bytes) to hb.out; T grows by as much */
+int     la_reader_take(struct archive_read_filter *self, la_reader *r, uint64_t bytes);
+/* The window's end: ramp, then nothing more when the stream has ended, else la_window_carry */
+int     la_reader_finish(struct archive_read_filter *self, la_reader *r, size_t used, int more, const char *unit);
+ssize_t la_reader_read(struct archive_read_filter *self, la_reader *r, const void **p, int (*window)(struct archive_read_filter *));
+/* Everything la_reader_open and the windows allocated, and the device; the filter's struct is the filter's to free */
+void    la_reader_close(la_reader *r);
+/* A unit whose decoded size nothing states is given *solo_cap bytes of output: max(8 x the `have` compressed bytes at
+ * hand, 1 MiB) when it is 0, at most out_budget.  la_reader_solo_full, when `cap` proved too small ("output full"):
+ * *solo_cap = 2 x cap, or at the budget "<name> <unit> too large for the GPU data plane (more than %llu decoded bytes;
+ * LA_GPU_OUT_BUDGET_MIB)" and ARCHIVE_FATAL. */
+uint64_t la_reader_solo_cap(const la_reader *r, uint64_t *solo_cap, uint64_t have);
+int     la_reader_solo_full(struct archive_read_filter *self, const la_reader *r, uint64_t *solo_cap, uint64_t cap, const char *unit);
 
 /* ---- hash drop-ins (host/la_hash_dropin.c) ----
  * The 4-pointer table of libarchive/archive_xxhash.h:37-46 (defined as `__archive_xxhash` when built

@@ -1,7 +1,7 @@
 /*
  * la_bid_policy.c -- the host code the read filters (la_filter_lz4.c, la_filter_gzip.c, la_filter_zstd.c,
  * la_filter_bzip2.c, la_filter_xz.c, la_filter_lzip.c, la_filter_lzop.c) share: the bid policy, below it the window
- * plumbing, and at the end the held-back delivery of the bzip2, xz, lzip and lzop filters.
+ * plumbing, and at the end the held-back delivery and the reader base (la_reader) of the bzip2, xz, lzip and lzop filters.
  *
  * Bid policy: should the GPU filter take this stream at all?
  *
@@ -29,6 +29,7 @@
  */
 #include "la_read_private.h"
 #include "la_host.h"
+#include <errno.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -64,6 +65,16 @@ const unsigned char *la_bid_peek(struct archive_read_filter *filter, size_t want
 	}
 	*got = (size_t)avail < want ? (size_t)avail : want;
 	return p;
+}
+
+int la_bid_declines(struct archive_read_filter *filter, int (*parallel)(const unsigned char *, size_t, size_t))
+{
+	if (la_bid_take_all())
+		return 0;
+	const size_t la = la_bid_lookahead(1024);
+	size_t got = 0;
+	const unsigned char *w = la_bid_peek(filter, la, &got);
+	return w != NULL && !parallel(w, got, la);
 }
 
 int la_gz_flush_points_enabled(void)
@@ -532,4 +543,94 @@ void la_holdback_release(la_gpu_ctx *gpu, la_holdback *h)
 	la_buf_release(gpu, &h->out);
 	free(h->tail);
 	h->tail = NULL;
+}
+
+int la_reader_open(struct archive_read_filter *self, la_reader *r, const char *name, size_t host_tab_bytes,
+    uint64_t max_out_budget, const char *nomem_msg)
+{
+	if (r == NULL || (r->h_tabs.p = calloc(1, host_tab_bytes)) == NULL || la_holdback_open(&r->hb) < 0)
+		archive_set_error(&self->archive->archive, ENOMEM, "%s", nomem_msg);
+	else if (la_window_open(self, &r->w, name) == ARCHIVE_OK) {
+		if (max_out_budget && (r->w.out_budget == 0 || r->w.out_budget > max_out_budget))
+			r->w.out_budget = max_out_budget;
+		return ARCHIVE_OK;
+	}
+	if (r) {
+		la_holdback_release(NULL, &r->hb);
+		la_buf_release(NULL, &r->h_tabs);
+	}
+	return ARCHIVE_FATAL;
+}
+
+int la_reader_gather(struct archive_read_filter *self, la_reader *r)
+{
+	const int rc = la_window_gather(self, &r->w, &r->stage, &r->stage_len);
+	if (rc != ARCHIVE_OK || r->stage_len == 0)
+		return rc;
+	if (la_buf_dev(r->w.gpu, &r->d_src, r->stage_len + 64) < 0)
+		return la_window_fail(self, &r->w, "la_gpu_malloc");
+	if (la_gpu_memcpy_h2d(r->w.gpu, r->d_src.p, r->stage.p, r->stage_len) != LA_OK)
+		return la_window_fail(self, &r->w, "la_gpu_memcpy_h2d");
+	return ARCHIVE_OK;
+}
+
+int la_reader_take(struct archive_read_filter *self, la_reader *r, uint64_t bytes)
+{
+	la_holdback *h = &r->hb;
+	if (bytes) {
+		if (la_buf_pinned(r->w.gpu, &h->out, h->out_len + (size_t)bytes + 64, h->out_len) < 0)
+			return la_window_fail(self, &r->w, "la_gpu_malloc_host");
+		if (la_gpu_memcpy_d2h(r->w.gpu, h->out.p + h->out_len, r->d_dst.p, bytes) != LA_OK || la_gpu_sync(r->w.gpu) != LA_OK)
+			return la_window_fail(self, &r->w, "la_gpu_memcpy_d2h");
+	}
+	h->out_len += (size_t)bytes;
+	h->total += bytes;
+	return ARCHIVE_OK;
+}
+
+int la_reader_finish(struct archive_read_filter *self, la_reader *r, size_t used, int more, const char *unit)
+{
+	la_window_ramp(&r->w);
+	if (r->hb.ended)
+		return ARCHIVE_OK;
+	return la_window_carry(self, &r->w, &r->stage, &r->stage_len, used, more, unit);
+}
+
+ssize_t la_reader_read(struct archive_read_filter *self, la_reader *r, const void **p, int (*window)(struct archive_read_filter *))
+{
+	return la_holdback_read(self, &r->w, &r->hb, p, window);
+}
+
+void la_reader_close(la_reader *r)
+{
+	la_gpu_ctx *gpu = r->w.gpu;
+	(void)la_gpu_sync(gpu);
+	la_buf_release(gpu, &r->d_src);
+	la_buf_release(gpu, &r->d_dst);
+	la_buf_release(gpu, &r->d_tabs);
+	la_holdback_release(gpu, &r->hb);
+	la_buf_release(gpu, &r->stage);
+	la_gpu_close(gpu);
+	la_buf_release(NULL, &r->h_tabs);
+}
+
+uint64_t la_reader_solo_cap(const la_reader *r, uint64_t *solo_cap, uint64_t have)
+{
+	if (*solo_cap == 0)
+		*solo_cap = have * 8 > MIB ? have * 8 : MIB;
+	if (*solo_cap > r->w.out_budget)
+		*solo_cap = r->w.out_budget;
+	return *solo_cap;
+}
+
+int la_reader_solo_full(struct archive_read_filter *self, const la_reader *r, uint64_t *solo_cap, uint64_t cap, const char *unit)
+{
+	if (cap >= r->w.out_budget) {
+		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
+		    "%s %s too large for the GPU data plane (more than %llu decoded bytes; LA_GPU_OUT_BUDGET_MIB)",
+		    r->w.name, unit, (unsigned long long)r->w.out_budget);
+		return ARCHIVE_FATAL;
+	}
+	*solo_cap = cap * 2;
+	return ARCHIVE_OK;
 }

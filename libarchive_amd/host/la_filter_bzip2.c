@@ -32,7 +32,6 @@
  */
 #include "la_read_private.h"
 #include "la_host.h"
-#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -40,13 +39,10 @@
 #define BZ_CAND_CAP    ((uint32_t)1 << 16)	/* candidates one scan keeps; a window with more is taken in parts */
 
 struct bzip2_private {
-	la_window w;
+	la_reader r;			/* stage: from the byte of the next unit on; d_tabs: candidates, results, state, count */
 	uint32_t options;		/* LA_BZIP2_SERIAL_CHASE=1: LA_BZ2_OPT_SERIAL_CHASE */
-	la_buf stage; size_t stage_len;	/* pinned: the stream from the byte of the next unit on */
 	la_bz2_state st;		/* where the stream stands at stage[0] */
-	la_buf d_src, d_dst, d_tabs;	/* d_tabs: candidates, results, state, count */
-	la_bz2_result *res;		/* the window's results on the host (4096 entries) */
-	la_holdback hb;			/* the decoded bytes, T and the stream's end */
+	la_bz2_result *res;		/* the window's results on the host (4096 entries), r.h_tabs */
 };
 
 static int bzip2_reader_bid(struct archive_read_filter_bidder *, struct archive_read_filter *);
@@ -93,18 +89,14 @@ static int bzip2_reader_init(struct archive_read_filter *self)
 	self->code = ARCHIVE_FILTER_BZIP2;
 	self->name = "bzip2";
 	struct bzip2_private *st = calloc(1, sizeof(*st));
-	if (st == NULL || la_holdback_open(&st->hb) < 0) {
-		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for bzip2 decompression");
+	if (la_reader_open(self, st ? &st->r : NULL, "bzip2", sizeof(la_bz2_result) * 4096, 0,
+	    "Can't allocate data for bzip2 decompression") != ARCHIVE_OK) {
 		free(st);
 		return ARCHIVE_FATAL;
 	}
+	st->res = (la_bz2_result *)st->r.h_tabs.p;
 	const char *sc = getenv("LA_BZIP2_SERIAL_CHASE");
 	st->options = (sc && atoi(sc) > 0) ? LA_BZ2_OPT_SERIAL_CHASE : 0u;
-	if (la_window_open(self, &st->w, "bzip2") != ARCHIVE_OK) {
-		la_holdback_release(NULL, &st->hb);
-		free(st);
-		return ARCHIVE_FATAL;
-	}
 	self->data = st;
 	self->vtable = &bzip2_reader_vtable;
 	return ARCHIVE_OK;
@@ -113,15 +105,15 @@ static int bzip2_reader_init(struct archive_read_filter *self)
 /* the stream ends here, T being hb.total */
 static void bz_end_data(struct bzip2_private *st)
 {
-	la_holdback_end(&st->hb, ARCHIVE_FATAL, "bzip decompression failed", LA_HB_EARLY);
+	la_holdback_end(&st->r.hb, ARCHIVE_FATAL, "bzip decompression failed", LA_HB_EARLY);
 }
 static void bz_end_truncated(struct bzip2_private *st)
 {
-	la_holdback_end(&st->hb, ARCHIVE_FATAL, "truncated bzip2 input", LA_HB_LATE);
+	la_holdback_end(&st->r.hb, ARCHIVE_FATAL, "truncated bzip2 input", LA_HB_LATE);
 }
 static void bz_end_clean(struct bzip2_private *st)
 {
-	la_holdback_end(&st->hb, ARCHIVE_OK, NULL, LA_HB_ALL);
+	la_holdback_end(&st->r.hb, ARCHIVE_OK, NULL, LA_HB_ALL);
 }
 
 /* the byte that starts at bit `bit` of p[0, n): caller keeps bit + 8 <= 8 n */
@@ -157,55 +149,51 @@ static int bz_magic_at(const uint8_t *p, size_t n, uint64_t bit)
 static int bz_window(struct archive_read_filter *self)
 {
 	struct bzip2_private *st = (struct bzip2_private *)self->data;
-	la_gpu_ctx *gpu = st->w.gpu;
-	int r = la_window_gather(self, &st->w, &st->stage, &st->stage_len);
+	la_reader *rd = &st->r;
+	la_gpu_ctx *gpu = rd->w.gpu;
+	int r = la_reader_gather(self, rd);
 	if (r != ARCHIVE_OK)
 		return r;
-	if (st->stage_len == 0) {	/* (upstream has ended) */
+	if (rd->stage_len == 0) {	/* (upstream has ended) */
 		if (st->st.open)
 			bz_end_truncated(st);
 		else
 			bz_end_clean(st);
 		return ARCHIVE_OK;
 	}
-	const uint8_t *src = st->stage.p;
-	const size_t len = st->stage_len;
+	const uint8_t *src = rd->stage.p;
+	const size_t len = rd->stage_len;
 	/* every block of the window gets a slot for the largest block its stream may hold */
 	uint32_t slot_level = st->st.open ? st->st.level : 9;
 	if (!st->st.open && len >= 4 && src[3] >= '1' && src[3] <= '9')
 		slot_level = (uint32_t)(src[3] - '0');
 	const uint32_t max_n = la_gpu_bzip2_max_blocks(slot_level);
 	const size_t o_res = sizeof(la_bz2_cand) * BZ_CAND_CAP, o_state = o_res + sizeof(la_bz2_result) * 4096, o_count = o_state + 64;
-	if (la_buf_dev(gpu, &st->d_src, len + 64) < 0 || la_buf_dev(gpu, &st->d_tabs, o_count + 64) < 0)
-		return la_window_fail(self, &st->w, "la_gpu_malloc");
-	if (st->res == NULL && (st->res = malloc(sizeof(la_bz2_result) * 4096)) == NULL) {
-		archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for bzip2 decompression");
-		return ARCHIVE_FATAL;
-	}
-	la_bz2_cand *d_cands = (la_bz2_cand *)st->d_tabs.p;
-	la_bz2_result *d_results = (la_bz2_result *)(st->d_tabs.p + o_res);
-	la_bz2_state *d_state = (la_bz2_state *)(st->d_tabs.p + o_state);
-	uint32_t *d_count = (uint32_t *)(st->d_tabs.p + o_count);
+	if (la_buf_dev(gpu, &rd->d_tabs, o_count + 64) < 0)
+		return la_window_fail(self, &rd->w, "la_gpu_malloc");
+	la_bz2_cand *d_cands = (la_bz2_cand *)rd->d_tabs.p;
+	la_bz2_result *d_results = (la_bz2_result *)(rd->d_tabs.p + o_res);
+	la_bz2_state *d_state = (la_bz2_state *)(rd->d_tabs.p + o_state);
+	uint32_t *d_count = (uint32_t *)(rd->d_tabs.p + o_count);
 	uint32_t count = 0;
-	if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
-	if (la_gpu_bzip2_scan(gpu, st->d_src.p, len, d_cands, BZ_CAND_CAP, d_count) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_bzip2_scan");
-	if (la_gpu_memcpy_d2h(gpu, &count, d_count, 4) != LA_OK || la_gpu_sync(gpu) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
+	if (la_gpu_bzip2_scan(gpu, rd->d_src.p, len, d_cands, BZ_CAND_CAP, d_count) != LA_OK) return la_window_fail(self, &rd->w, "la_gpu_bzip2_scan");
+	if (la_gpu_memcpy_d2h(gpu, &count, d_count, 4) != LA_OK || la_gpu_sync(gpu) != LA_OK) return la_window_fail(self, &rd->w, "la_gpu_memcpy_d2h");
 	uint32_t n = count < BZ_CAND_CAP ? count : BZ_CAND_CAP;
 	if (n > max_n)
 		n = max_n;	/* the table never holds more blocks than the workspace slots: the rest waits for the next window */
 	la_bz2_batch bt;
 	la_bz2_state ms, es;
 	memset(&bt, 0, sizeof(bt));
-	bt.d_src = st->d_src.p; bt.src_bytes = len;
+	bt.d_src = rd->d_src.p; bt.src_bytes = len;
 	bt.d_cands = d_cands; bt.n = n;
 	bt.d_results = d_results;
 	bt.state_in = &st->st; bt.d_state_out = d_state;
 	bt.options = st->options; bt.slot_level = slot_level;
 	bt.phase = LA_BZ2_MEASURE;
-	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_bzip2_decode");
+	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &rd->w, "la_gpu_bzip2_decode");
 	if (la_gpu_memcpy_d2h(gpu, st->res, d_results, sizeof(la_bz2_result) * n) != LA_OK ||
 	    la_gpu_memcpy_d2h(gpu, &ms, d_state, sizeof(ms)) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
+		return la_window_fail(self, &rd->w, "la_gpu_memcpy_d2h");
 	/* the prefix of confirmed blocks that fits the decoded-bytes budget; one block always goes (at most 46 MB) */
 	uint32_t n_emit = ms.n_taken;
 	uint64_t dst_bytes = 0;
@@ -213,37 +201,34 @@ static int bz_window(struct archive_read_filter *self)
 		const la_bz2_result *q = &st->res[i];
 		if (q->status != LA_ST_OK || q->out_len == 0)
 			continue;
-		if (dst_bytes && st->w.out_budget && dst_bytes + q->out_len > st->w.out_budget) {
+		if (dst_bytes && rd->w.out_budget && dst_bytes + q->out_len > rd->w.out_budget) {
 			n_emit = i;
 			break;
 		}
 		dst_bytes += q->out_len;
 	}
-	if (la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc");
-	if (la_buf_pinned(gpu, &st->hb.out, (size_t)dst_bytes + 64, 0) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc_host");
+	if (la_buf_dev(gpu, &rd->d_dst, (size_t)dst_bytes + 64) < 0) return la_window_fail(self, &rd->w, "la_gpu_malloc");
+	if (la_buf_pinned(gpu, &rd->hb.out, (size_t)dst_bytes + 64, 0) < 0) return la_window_fail(self, &rd->w, "la_gpu_malloc_host");
 	bt.phase = LA_BZ2_EMIT;
-	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes; bt.n_emit = n_emit;
-	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_bzip2_decode");
+	bt.d_dst = rd->d_dst.p; bt.dst_cap = dst_bytes; bt.n_emit = n_emit;
+	if (la_gpu_bzip2_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &rd->w, "la_gpu_bzip2_decode");
 	if (la_gpu_memcpy_d2h(gpu, &es, d_state, sizeof(es)) != LA_OK ||
 	    la_gpu_memcpy_d2h(gpu, st->res, d_results, sizeof(la_bz2_result) * n) != LA_OK ||
-	    la_gpu_memcpy_d2h(gpu, st->hb.out.p, st->d_dst.p, dst_bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
-	la_window_ramp(&st->w);
-	st->hb.out_len = (size_t)es.total_out;	/* (through a block with a wrong CRC: libbz2 emits it before it compares) */
-	st->hb.total += es.total_out;
-	if (es.first_bad != 0xFFFFFFFFu) {
-		bz_end_data(st);
-		return ARCHIVE_OK;
-	}
+	    la_gpu_memcpy_d2h(gpu, rd->hb.out.p, rd->d_dst.p, dst_bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
+		return la_window_fail(self, &rd->w, "la_gpu_memcpy_d2h");
+	rd->hb.out_len = (size_t)es.total_out;	/* (through a block with a wrong CRC: libbz2 emits it before it compares) */
+	rd->hb.total += es.total_out;
 	const uint64_t stop_bit = es.start_bit;
 	const size_t used = (size_t)(stop_bit >> 3) < len ? (size_t)(stop_bit >> 3) : len;
 	int more = 0;	/* the unit at stop_bit needs bytes the window does not hold */
-	if (es.n_taken < ms.n_taken || es.stop == LA_BZ2_STOP_LEVEL) {
+	if (es.first_bad != 0xFFFFFFFFu) {
+		bz_end_data(st);
+	} else if (es.n_taken < ms.n_taken || es.stop == LA_BZ2_STOP_LEVEL) {
 		;	/* the budget, or a stream of a higher level, ends the window: on from there */
 	} else if (es.stop == LA_BZ2_STOP_ENTRY) {
 		if (st->res[es.stop_entry].status != LA_ST_BZ2_TRUNCATED)
 			bz_end_data(st);	/* LA_ST_BZ2_DATA, LA_ST_BZ2_RANDOMISED */
-		else if (st->w.upstream_eof)
+		else if (rd->w.upstream_eof)
 			bz_end_truncated(st);
 		else
 			more = 1;
@@ -252,7 +237,7 @@ static int bz_window(struct archive_read_filter *self)
 		if (m < 0)
 			bz_end_data(st);
 		else if (m == 0) {
-			if (st->w.upstream_eof)
+			if (rd->w.upstream_eof)
 				bz_end_truncated(st);
 			else
 				more = 1;
@@ -261,19 +246,17 @@ static int bz_window(struct archive_read_filter *self)
 	} else if (es.stop == LA_BZ2_STOP_BID) {
 		bz_end_clean(st);	/* bzip2.c:236-241: what follows the stream fails the bid */
 	} else {	/* LA_BZ2_STOP_SHORT: fewer than 14 bytes behind a stream */
-		if (st->w.upstream_eof)
+		if (rd->w.upstream_eof)
 			bz_end_clean(st);
 		else
 			more = 1;
 	}
-	if (st->hb.ended)
-		return ARCHIVE_OK;
-	if (!more && used == 0 && es.total_out == 0) {
+	if (!rd->hb.ended && !more && used == 0 && es.total_out == 0) {
 		/* (cannot be: a window that neither ends the stream nor asks for more input has passed at least one unit) */
 		archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC, "bzip2 GPU data plane: a window made no progress");
 		return ARCHIVE_FATAL;
 	}
-	if ((r = la_window_carry(self, &st->w, &st->stage, &st->stage_len, used, more, "block")) != ARCHIVE_OK)
+	if ((r = la_reader_finish(self, rd, used, more, "block")) != ARCHIVE_OK || rd->hb.ended)
 		return r;
 	st->st.open = es.open; st->st.level = es.level; st->st.crc = es.crc;
 	st->st.start_bit = stop_bit - (uint64_t)used * 8;
@@ -282,8 +265,7 @@ static int bz_window(struct archive_read_filter *self)
 
 static ssize_t bzip2_filter_read(struct archive_read_filter *self, const void **p)
 {
-	struct bzip2_private *st = (struct bzip2_private *)self->data;
-	return la_holdback_read(self, &st->w, &st->hb, p, bz_window);
+	return la_reader_read(self, &((struct bzip2_private *)self->data)->r, p, bz_window);
 }
 
 static int bzip2_filter_close(struct archive_read_filter *self)
@@ -291,15 +273,7 @@ static int bzip2_filter_close(struct archive_read_filter *self)
 	struct bzip2_private *st = (struct bzip2_private *)self->data;
 	if (st == NULL)
 		return ARCHIVE_OK;
-	la_gpu_ctx *gpu = st->w.gpu;
-	(void)la_gpu_sync(gpu);
-	la_buf_release(gpu, &st->d_src);
-	la_buf_release(gpu, &st->d_dst);
-	la_buf_release(gpu, &st->d_tabs);
-	la_holdback_release(gpu, &st->hb);
-	la_buf_release(gpu, &st->stage);
-	la_gpu_close(gpu);
-	free(st->res);
+	la_reader_close(&st->r);
 	free(st);
 	self->data = NULL;
 	return ARCHIVE_OK;

@@ -54,14 +54,11 @@ static const char LZ_MSG_DATA[] = "Lzma library error: Corrupted input data";
 static const char LZ_MSG_BUF[] = "Lzma library error:  No progress is possible";
 
 struct lzip_private {
-	la_window w;
-	la_buf stage; size_t stage_len;	/* pinned: the stream from the first byte of the next member on */
-	la_buf d_src, d_dst, d_tabs;	/* d_tabs: candidates, count, member table, results */
+	la_reader r;			/* stage: from the first byte of the next member on; d_tabs: candidates, count, member table, results */
 	uint64_t *cands; size_t n_cands, cands_cap;	/* the window's header shapes, ascending */
-	la_lzip_member *tab;		/* host copies of the tables (LZ_TAB_CAP entries) */
+	la_lzip_member *tab;		/* host copies of the tables (LZ_TAB_CAP entries each), in r.h_tabs */
 	la_lzip_result *res;
 	size_t *ends;			/* tab[i]'s member ends inside the window */
-	la_holdback hb;			/* the decoded bytes, T and the stream's end */
 	int force_solo;			/* the member at stage[0 ...] was refuted as chained: decode it alone */
 	uint64_t solo_cap;		/* output budget of the next member decoded alone (grows on LA_ST_LZIP_OUT_FULL) */
 };
@@ -100,13 +97,8 @@ static int lzip_reader_bid(struct archive_read_filter_bidder *self, struct archi
 		return 0;
 	/* Default policy (la_bid_policy.c): one member is one serial chain; a stream whose first member does not end inside
 	 * the look-ahead is left to liblzma on a host core. */
-	if (!la_bid_take_all()) {
-		const size_t la = la_bid_lookahead(1024);
-		size_t got = 0;
-		const unsigned char *w = la_bid_peek(filter, la, &got);
-		if (w != NULL && !la_bid_lzip_parallel(w, got, la))
-			return 0;
-	}
+	if (la_bid_declines(filter, la_bid_lzip_parallel))
+		return 0;
 	return 32 + 8 + 8;
 }
 
@@ -115,21 +107,15 @@ static int lzip_reader_init(struct archive_read_filter *self)
 	self->code = ARCHIVE_FILTER_LZIP;
 	self->name = "lzip";
 	struct lzip_private *st = calloc(1, sizeof(*st));
-	la_lzip_member *tab = malloc(sizeof(la_lzip_member) * LZ_TAB_CAP);
-	la_lzip_result *res = malloc(sizeof(la_lzip_result) * LZ_TAB_CAP);
-	size_t *ends = malloc(sizeof(size_t) * LZ_TAB_CAP);
-	const int no_mem = st == NULL || tab == NULL || res == NULL || ends == NULL || la_holdback_open(&st->hb) < 0;
-	if (no_mem || la_window_open(self, &st->w, "lzip") != ARCHIVE_OK) {
-		if (no_mem)
-			archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for xz decompression");	/* xz.c:482-483 */
-		if (st)
-			la_holdback_release(NULL, &st->hb);
-		free(st); free(tab); free(res); free(ends);
+	/* (a member's dst_cap is at most LA_XZ_DST_CAP_MAX: 4095 MiB) */
+	if (la_reader_open(self, st ? &st->r : NULL, "lzip", (sizeof(la_lzip_member) + sizeof(la_lzip_result) + sizeof(size_t)) * LZ_TAB_CAP,
+	    (uint64_t)4095 << 20, "Can't allocate data for xz decompression") != ARCHIVE_OK) {	/* xz.c:482-483 */
+		free(st);
 		return ARCHIVE_FATAL;
 	}
-	st->tab = tab; st->res = res; st->ends = ends;
-	if (st->w.out_budget == 0 || st->w.out_budget > ((uint64_t)4095 << 20))
-		st->w.out_budget = (uint64_t)4095 << 20;	/* a member's dst_cap is at most LA_XZ_DST_CAP_MAX */
+	st->tab = (la_lzip_member *)st->r.h_tabs.p;
+	st->res = (la_lzip_result *)(st->tab + LZ_TAB_CAP);
+	st->ends = (size_t *)(st->res + LZ_TAB_CAP);
 	self->data = st;
 	self->vtable = &lzip_reader_vtable;
 	return ARCHIVE_OK;
@@ -146,17 +132,18 @@ static uint64_t le64(const uint8_t *p)
 /* The header shapes of the window, in parts of LZ_CAND_CAP: st->cands[0, n_cands). */
 static int lz_scan(struct archive_read_filter *self, struct lzip_private *st, size_t len)
 {
-	la_gpu_ctx *gpu = st->w.gpu;
-	uint64_t *d_offs = (uint64_t *)st->d_tabs.p;
-	uint32_t *d_count = (uint32_t *)(st->d_tabs.p + sizeof(uint64_t) * LZ_CAND_CAP);
+	la_reader *r = &st->r;
+	la_gpu_ctx *gpu = r->w.gpu;
+	uint64_t *d_offs = (uint64_t *)r->d_tabs.p;
+	uint32_t *d_count = (uint32_t *)(r->d_tabs.p + sizeof(uint64_t) * LZ_CAND_CAP);
 	size_t from = 0;
 	st->n_cands = 0;
 	for (;;) {
 		uint32_t count = 0;
-		if (la_gpu_lzip_scan(gpu, st->d_src.p + from, len - from, d_offs, LZ_CAND_CAP, d_count) != LA_OK)
-			return la_window_fail(self, &st->w, "la_gpu_lzip_scan");
+		if (la_gpu_lzip_scan(gpu, r->d_src.p + from, len - from, d_offs, LZ_CAND_CAP, d_count) != LA_OK)
+			return la_window_fail(self, &r->w, "la_gpu_lzip_scan");
 		if (la_gpu_memcpy_d2h(gpu, &count, d_count, 4) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-			return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
+			return la_window_fail(self, &r->w, "la_gpu_memcpy_d2h");
 		const uint32_t k = count < LZ_CAND_CAP ? count : LZ_CAND_CAP;
 		if (st->n_cands + k > st->cands_cap) {
 			const size_t nc = (st->n_cands + k) * 2;
@@ -169,7 +156,7 @@ static int lz_scan(struct archive_read_filter *self, struct lzip_private *st, si
 			st->cands_cap = nc;
 		}
 		if (k && (la_gpu_memcpy_d2h(gpu, st->cands + st->n_cands, d_offs, sizeof(uint64_t) * k) != LA_OK || la_gpu_sync(gpu) != LA_OK))
-			return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
+			return la_window_fail(self, &r->w, "la_gpu_memcpy_d2h");
 		for (uint32_t i = 0; i < k; i++)
 			st->cands[st->n_cands + i] += from;
 		st->n_cands += k;
@@ -198,41 +185,27 @@ static size_t lz_chain_end(const struct lzip_private *st, const uint8_t *src, si
 /* Decode tab[0, n) in one call; the results are in st->res. */
 static int lz_launch(struct archive_read_filter *self, struct lzip_private *st, uint32_t n, uint64_t dst_bytes)
 {
-	la_gpu_ctx *gpu = st->w.gpu;
+	la_reader *r = &st->r;
+	la_gpu_ctx *gpu = r->w.gpu;
 	const size_t o_tab = sizeof(uint64_t) * LZ_CAND_CAP + 256, o_res = o_tab + sizeof(la_lzip_member) * LZ_TAB_CAP;
-	if (la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0)
-		return la_window_fail(self, &st->w, "la_gpu_malloc");
+	if (la_buf_dev(gpu, &r->d_dst, (size_t)dst_bytes + 64) < 0)
+		return la_window_fail(self, &r->w, "la_gpu_malloc");
 	la_lzip_batch bt;
 	memset(&bt, 0, sizeof(bt));
-	bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
-	bt.d_members = (const la_lzip_member *)(st->d_tabs.p + o_tab); bt.n = n;
-	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes;
-	bt.d_results = (la_lzip_result *)(st->d_tabs.p + o_res);
-	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p + o_tab, st->tab, sizeof(la_lzip_member) * n) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
-	if (la_gpu_lzip_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_lzip_decode");
+	bt.d_src = r->d_src.p; bt.src_bytes = r->stage_len;
+	bt.d_members = (const la_lzip_member *)(r->d_tabs.p + o_tab); bt.n = n;
+	bt.d_dst = r->d_dst.p; bt.dst_cap = dst_bytes;
+	bt.d_results = (la_lzip_result *)(r->d_tabs.p + o_res);
+	if (la_gpu_memcpy_h2d(gpu, r->d_tabs.p + o_tab, st->tab, sizeof(la_lzip_member) * n) != LA_OK) return la_window_fail(self, &r->w, "la_gpu_memcpy_h2d");
+	if (la_gpu_lzip_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &r->w, "la_gpu_lzip_decode");
 	if (la_gpu_memcpy_d2h(gpu, st->res, bt.d_results, sizeof(la_lzip_result) * n) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
-	return ARCHIVE_OK;
-}
-
-/* Append d_dst[0, bytes) to the window's output; T grows by as much. */
-static int lz_take_bytes(struct archive_read_filter *self, struct lzip_private *st, uint64_t bytes)
-{
-	la_gpu_ctx *gpu = st->w.gpu;
-	if (bytes) {
-		if (la_buf_pinned(gpu, &st->hb.out, st->hb.out_len + (size_t)bytes + 64, st->hb.out_len) < 0)
-			return la_window_fail(self, &st->w, "la_gpu_malloc_host");
-		if (la_gpu_memcpy_d2h(gpu, st->hb.out.p + st->hb.out_len, st->d_dst.p, bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-			return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
-	}
-	st->hb.out_len += (size_t)bytes;
-	st->hb.total += bytes;
+		return la_window_fail(self, &r->w, "la_gpu_memcpy_d2h");
 	return ARCHIVE_OK;
 }
 
 static void lz_end_failed(struct lzip_private *st, const char *msg)
 {
-	la_holdback_end(&st->hb, ARCHIVE_FAILED, msg, LA_HB_EARLY);
+	la_holdback_end(&st->r.hb, ARCHIVE_FAILED, msg, LA_HB_EARLY);
 }
 
 /* One window: gather, upload, scan, walk; updates T, and says how the stream ends if this window shows it.
@@ -240,32 +213,29 @@ static void lz_end_failed(struct lzip_private *st, const char *msg)
 static int lz_window(struct archive_read_filter *self)
 {
 	struct lzip_private *st = (struct lzip_private *)self->data;
-	la_gpu_ctx *gpu = st->w.gpu;
-	int r = la_window_gather(self, &st->w, &st->stage, &st->stage_len);
+	la_holdback *hb = &st->r.hb;
+	const uint64_t out_budget = st->r.w.out_budget;
+	int r = la_reader_gather(self, &st->r);
 	if (r != ARCHIVE_OK)
 		return r;
-	const uint8_t *src = st->stage.p;
-	const size_t len = st->stage_len;
-	const int eof = st->w.upstream_eof;
+	const uint8_t *src = st->r.stage.p;
+	const size_t len = st->r.stage_len;
+	const int eof = st->r.w.upstream_eof;
 	const size_t tabs_bytes = sizeof(uint64_t) * LZ_CAND_CAP + 256 + (sizeof(la_lzip_member) + sizeof(la_lzip_result)) * LZ_TAB_CAP;
-	if (la_buf_dev(gpu, &st->d_tabs, tabs_bytes) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc");
+	if (la_buf_dev(st->r.w.gpu, &st->r.d_tabs, tabs_bytes) < 0) return la_window_fail(self, &st->r.w, "la_gpu_malloc");
 	st->n_cands = 0;
-	if (len) {
-		if (la_buf_dev(gpu, &st->d_src, len + 64) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc");
-		if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
-		if ((r = lz_scan(self, st, len)) != ARCHIVE_OK)
-			return r;
-	}
+	if (len && (r = lz_scan(self, st, len)) != ARCHIVE_OK)
+		return r;
 	size_t pos = 0;		/* the first byte of the member the walk stands at */
 	size_t ci = 0;		/* the first candidate that may lie behind pos */
 	int more = 0;		/* that member needs bytes the window does not hold */
-	while (!st->hb.ended && !more) {
+	while (!hb->ended && !more) {
 		if (len - pos < 6) {	/* xz.c:350-352: no six bytes, no member */
-			if (eof) la_holdback_end(&st->hb, ARCHIVE_OK, NULL, LA_HB_ALL); else more = 1;
+			if (eof) la_holdback_end(hb, ARCHIVE_OK, NULL, LA_HB_ALL); else more = 1;
 			break;
 		}
 		if (!la_lzip_header_shape(src + pos)) {	/* junk behind a member is ignored (xz.c:636-645) */
-			la_holdback_end(&st->hb, ARCHIVE_OK, NULL, LA_HB_ALL);
+			la_holdback_end(hb, ARCHIVE_OK, NULL, LA_HB_ALL);
 			break;
 		}
 		/* the run of members that chain from here, each with a trailer whose sizes fit a launch */
@@ -277,7 +247,7 @@ static int lz_window(struct archive_read_filter *self)
 			if (o == 0)
 				break;
 			const uint64_t data_size = le64(src + o - 16);
-			if (data_size > st->w.out_budget || (n && dst_bytes + data_size > st->w.out_budget))
+			if (data_size > out_budget || (n && dst_bytes + data_size > out_budget))
 				break;
 			la_lzip_member *m = &st->tab[n];
 			m->src_off = at + 6; m->src_end = o - 20; m->data_size = data_size;
@@ -296,9 +266,9 @@ static int lz_window(struct archive_read_filter *self)
 				good++;
 			if (good) {
 				/* every one of them ends where its trailer says, with that size and CRC: lzip_tail would pass them */
-				if ((r = lz_take_bytes(self, st, st->tab[good - 1].dst_off + st->res[good - 1].out_len)) != ARCHIVE_OK)
+				if ((r = la_reader_take(self, &st->r, st->tab[good - 1].dst_off + st->res[good - 1].out_len)) != ARCHIVE_OK)
 					return r;
-				la_holdback_rebase(&st->hb);
+				la_holdback_rebase(hb);
 				pos = st->ends[good - 1];
 			}
 			st->force_solo = good < n;	/* a tentative end, size or CRC did not hold: that member alone says what is wrong */
@@ -310,12 +280,7 @@ static int lz_window(struct archive_read_filter *self)
 			break;
 		}
 		const unsigned tail = src[pos + 4] == 0 ? 12 : 20;
-		const uint64_t have = len - pos - 6;
-		if (st->solo_cap == 0)
-			st->solo_cap = have * 8 > ((uint64_t)1 << 20) ? have * 8 : (uint64_t)1 << 20;
-		if (st->solo_cap > st->w.out_budget)
-			st->solo_cap = st->w.out_budget;
-		const uint64_t cap = st->solo_cap;
+		const uint64_t cap = la_reader_solo_cap(&st->r, &st->solo_cap, len - pos - 6);
 		la_lzip_member *m = &st->tab[0];
 		m->src_off = pos + 6; m->src_end = LA_LZIP_UNKNOWN; m->data_size = LA_LZIP_UNKNOWN;
 		m->dst_off = 0; m->dst_cap = cap;
@@ -325,13 +290,8 @@ static int lz_window(struct archive_read_filter *self)
 			return r;
 		const la_lzip_result q = st->res[0];
 		if (q.status == LA_ST_LZIP_OUT_FULL) {
-			if (cap >= st->w.out_budget) {
-				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-				    "lzip member too large for the GPU data plane (more than %llu decoded bytes; LA_GPU_OUT_BUDGET_MIB)",
-				    (unsigned long long)st->w.out_budget);
-				return ARCHIVE_FATAL;
-			}
-			st->solo_cap = cap * 2;
+			if ((r = la_reader_solo_full(self, &st->r, &st->solo_cap, cap, "member")) != ARCHIVE_OK)
+				return r;
 			continue;	/* again, with twice the room */
 		}
 		const size_t trailer = pos + 6 + (size_t)q.consumed;
@@ -341,12 +301,12 @@ static int lz_window(struct archive_read_filter *self)
 		}
 		st->solo_cap = 0;
 		st->force_solo = 0;
-		if ((r = lz_take_bytes(self, st, q.out_len)) != ARCHIVE_OK)
+		if ((r = la_reader_take(self, &st->r, q.out_len)) != ARCHIVE_OK)
 			return r;
 		if (q.status == LA_ST_LZIP_TRUNCATED)
-			la_holdback_end(&st->hb, ARCHIVE_FATAL, LZ_MSG_BUF, LA_HB_LATE);
+			la_holdback_end(hb, ARCHIVE_FATAL, LZ_MSG_BUF, LA_HB_LATE);
 		else if (q.status != LA_ST_OK)
-			la_holdback_end(&st->hb, ARCHIVE_FATAL, LZ_MSG_DATA, LA_HB_EARLY);
+			la_holdback_end(hb, ARCHIVE_FATAL, LZ_MSG_DATA, LA_HB_EARLY);
 		/* lzip_tail, xz.c:589-646 */
 		else if (len - trailer < tail)
 			lz_end_failed(st, "Lzip: Remaining data is less bytes");
@@ -357,20 +317,16 @@ static int lz_window(struct archive_read_filter *self)
 		else if (tail == 20 && 6 + q.consumed + 20 != le64(src + trailer + 12))
 			lz_end_failed(st, "Lzip: Member size error");
 		else {
-			la_holdback_rebase(&st->hb);
+			la_holdback_rebase(hb);
 			pos = trailer + tail;
 		}
 	}
-	la_window_ramp(&st->w);
-	if (st->hb.ended)
-		return ARCHIVE_OK;
-	return la_window_carry(self, &st->w, &st->stage, &st->stage_len, pos, more, "member");
+	return la_reader_finish(self, &st->r, pos, more, "member");
 }
 
 static ssize_t lzip_filter_read(struct archive_read_filter *self, const void **p)
 {
-	struct lzip_private *st = (struct lzip_private *)self->data;
-	return la_holdback_read(self, &st->w, &st->hb, p, lz_window);
+	return la_reader_read(self, &((struct lzip_private *)self->data)->r, p, lz_window);
 }
 
 static int lzip_filter_close(struct archive_read_filter *self)
@@ -378,18 +334,8 @@ static int lzip_filter_close(struct archive_read_filter *self)
 	struct lzip_private *st = (struct lzip_private *)self->data;
 	if (st == NULL)
 		return ARCHIVE_OK;
-	la_gpu_ctx *gpu = st->w.gpu;
-	(void)la_gpu_sync(gpu);
-	la_buf_release(gpu, &st->d_src);
-	la_buf_release(gpu, &st->d_dst);
-	la_buf_release(gpu, &st->d_tabs);
-	la_holdback_release(gpu, &st->hb);
-	la_buf_release(gpu, &st->stage);
-	la_gpu_close(gpu);
+	la_reader_close(&st->r);
 	free(st->cands);
-	free(st->tab);
-	free(st->res);
-	free(st->ends);
 	free(st);
 	self->data = NULL;
 	return ARCHIVE_OK;

@@ -29,7 +29,6 @@
  */
 #include "la_read_private.h"
 #include "la_host.h"
-#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -50,12 +49,9 @@
 #define LZO_TAB_CAP 4096u	/* blocks one launch takes; a window with more is taken in parts */
 
 struct lzop_private {
-	la_window w;
-	la_buf stage; size_t stage_len;	/* pinned: the stream from the first byte of the unfinished header or block on */
-	la_buf d_src, d_dst, d_tabs;	/* d_tabs: block table, results */
-	la_lzop_block *tab;		/* host copies of the tables (LZO_TAB_CAP entries) */
+	la_reader r;			/* stage: from the first byte of the unfinished header or block on; d_tabs: block table, results */
+	la_lzop_block *tab;		/* host copies of the tables (LZO_TAB_CAP entries each), in r.h_tabs */
 	la_lzop_result *res;
-	la_holdback hb;
 	/* struct read_lzop's fields (lzop.c:71-83) at the walk's position */
 	char in_stream;
 	unsigned flags;
@@ -99,13 +95,8 @@ static int lzop_bidder_bid(struct archive_read_filter_bidder *self, struct archi
 		return 0;
 	/* Default policy (la_bid_policy.c): one block is one serial chain; a stream whose first block does not end inside the
 	 * look-ahead is left to liblzo2 on a host core. */
-	if (!la_bid_take_all()) {
-		const size_t la = la_bid_lookahead(1024);
-		size_t got = 0;
-		const unsigned char *w = la_bid_peek(filter, la, &got);
-		if (w != NULL && !la_bid_lzop_parallel(w, got, la))
-			return 0;
-	}
+	if (la_bid_declines(filter, la_bid_lzop_parallel))
+		return 0;
 	return LZOP_HEADER_MAGIC_LEN * 8;
 }
 
@@ -114,18 +105,13 @@ static int lzop_bidder_init(struct archive_read_filter *self)
 	self->code = ARCHIVE_FILTER_LZOP;
 	self->name = "lzop";
 	struct lzop_private *st = calloc(1, sizeof(*st));
-	la_lzop_block *tab = malloc(sizeof(la_lzop_block) * LZO_TAB_CAP);
-	la_lzop_result *res = malloc(sizeof(la_lzop_result) * LZO_TAB_CAP);
-	const int no_mem = st == NULL || tab == NULL || res == NULL || la_holdback_open(&st->hb) < 0;
-	if (no_mem || la_window_open(self, &st->w, "lzop") != ARCHIVE_OK) {
-		if (no_mem)
-			archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for lzop decompression");	/* lzop.c:190-191 */
-		if (st)
-			la_holdback_release(NULL, &st->hb);
-		free(st); free(tab); free(res);
+	if (la_reader_open(self, st ? &st->r : NULL, "lzop", (sizeof(la_lzop_block) + sizeof(la_lzop_result)) * LZO_TAB_CAP, 0,
+	    "Can't allocate data for lzop decompression") != ARCHIVE_OK) {	/* lzop.c:190-191 */
+		free(st);
 		return ARCHIVE_FATAL;
 	}
-	st->tab = tab; st->res = res;
+	st->tab = (la_lzop_block *)st->r.h_tabs.p;
+	st->res = (la_lzop_result *)(st->tab + LZO_TAB_CAP);
 	self->data = st;
 	self->vtable = &lzop_reader_vtable;
 	return ARCHIVE_OK;
@@ -280,36 +266,21 @@ static int wk_block(struct lzop_private *st, const uint8_t *src, size_t len, int
 /* Decode tab[0, n) in one call; the results are in st->res. */
 static int lzo_launch(struct archive_read_filter *self, struct lzop_private *st, uint32_t n, uint64_t dst_bytes)
 {
-	la_gpu_ctx *gpu = st->w.gpu;
+	la_reader *r = &st->r;
+	la_gpu_ctx *gpu = r->w.gpu;
 	const size_t o_res = sizeof(la_lzop_block) * LZO_TAB_CAP;
-	if (la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0)
-		return la_window_fail(self, &st->w, "la_gpu_malloc");
+	if (la_buf_dev(gpu, &r->d_dst, (size_t)dst_bytes + 64) < 0)
+		return la_window_fail(self, &r->w, "la_gpu_malloc");
 	la_lzop_batch bt;
 	memset(&bt, 0, sizeof(bt));
-	bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
-	bt.d_blocks = (const la_lzop_block *)st->d_tabs.p; bt.n = n;
-	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes;
-	bt.d_results = (la_lzop_result *)(st->d_tabs.p + o_res);
-	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, st->tab, sizeof(la_lzop_block) * n) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
-	if (la_gpu_lzop_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_lzop_decode");
+	bt.d_src = r->d_src.p; bt.src_bytes = r->stage_len;
+	bt.d_blocks = (const la_lzop_block *)r->d_tabs.p; bt.n = n;
+	bt.d_dst = r->d_dst.p; bt.dst_cap = dst_bytes;
+	bt.d_results = (la_lzop_result *)(r->d_tabs.p + o_res);
+	if (la_gpu_memcpy_h2d(gpu, r->d_tabs.p, st->tab, sizeof(la_lzop_block) * n) != LA_OK) return la_window_fail(self, &r->w, "la_gpu_memcpy_h2d");
+	if (la_gpu_lzop_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &r->w, "la_gpu_lzop_decode");
 	if (la_gpu_memcpy_d2h(gpu, st->res, bt.d_results, sizeof(la_lzop_result) * n) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
-	return ARCHIVE_OK;
-}
-
-/* Append d_dst[0, bytes) to the window's output; every block of it is out before the next one is read */
-static int lzo_take_bytes(struct archive_read_filter *self, struct lzop_private *st, uint64_t bytes)
-{
-	la_gpu_ctx *gpu = st->w.gpu;
-	if (bytes) {
-		if (la_buf_pinned(gpu, &st->hb.out, st->hb.out_len + (size_t)bytes + 64, st->hb.out_len) < 0)
-			return la_window_fail(self, &st->w, "la_gpu_malloc_host");
-		if (la_gpu_memcpy_d2h(gpu, st->hb.out.p + st->hb.out_len, st->d_dst.p, bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-			return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
-	}
-	st->hb.out_len += (size_t)bytes;
-	st->hb.total += bytes;
-	la_holdback_rebase(&st->hb);
+		return la_window_fail(self, &r->w, "la_gpu_memcpy_d2h");
 	return ARCHIVE_OK;
 }
 
@@ -336,19 +307,14 @@ static void lzo_block_failed(struct lzop_private *st, uint32_t status)
 static int lzo_window(struct archive_read_filter *self)
 {
 	struct lzop_private *st = (struct lzop_private *)self->data;
-	la_gpu_ctx *gpu = st->w.gpu;
-	int r = la_window_gather(self, &st->w, &st->stage, &st->stage_len);
+	int r = la_reader_gather(self, &st->r);
 	if (r != ARCHIVE_OK)
 		return r;
-	const uint8_t *src = st->stage.p;
-	const size_t len = st->stage_len;
-	const int eof = st->w.upstream_eof;
-	if (la_buf_dev(gpu, &st->d_tabs, (sizeof(la_lzop_block) + sizeof(la_lzop_result)) * LZO_TAB_CAP) < 0)
-		return la_window_fail(self, &st->w, "la_gpu_malloc");
-	if (len) {
-		if (la_buf_dev(gpu, &st->d_src, len + 64) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc");
-		if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
-	}
+	const uint8_t *src = st->r.stage.p;
+	const size_t len = st->r.stage_len;
+	const int eof = st->r.w.upstream_eof;
+	if (la_buf_dev(st->r.w.gpu, &st->r.d_tabs, (sizeof(la_lzop_block) + sizeof(la_lzop_result)) * LZO_TAB_CAP) < 0)
+		return la_window_fail(self, &st->r.w, "la_gpu_malloc");
 	size_t pos = 0;		/* the first byte of the header or block info the walk stands at */
 	int wk = WK_OK;
 	while (wk == WK_OK) {
@@ -361,7 +327,7 @@ static int lzo_window(struct archive_read_filter *self)
 					break;
 			}
 			la_lzop_block *b = &st->tab[n];
-			if (n && dst_bytes + MAX_BLOCK_SIZE > st->w.out_budget)
+			if (n && dst_bytes + MAX_BLOCK_SIZE > st->r.w.out_budget)
 				break;
 			if ((wk = wk_block(st, src, len, eof, &pos, b)) != WK_OK)
 				break;
@@ -378,25 +344,22 @@ static int lzo_window(struct archive_read_filter *self)
 		uint32_t good = 0;
 		while (good < n && st->res[good].status == LA_ST_OK)
 			good++;
-		if ((r = lzo_take_bytes(self, st, good < n ? st->tab[good].dst_off : dst_bytes)) != ARCHIVE_OK)
+		if ((r = la_reader_take(self, &st->r, good < n ? st->tab[good].dst_off : dst_bytes)) != ARCHIVE_OK)
 			return r;
+		la_holdback_rebase(&st->r.hb);	/* every block of them is out before the next one is read */
 		if (good < n) {
 			lzo_block_failed(st, st->res[good].status);	/* (replaces a verdict the walk met behind it) */
 			wk = WK_END;
 		}
 	}
-	la_window_ramp(&st->w);
-	if (wk == WK_END) {
-		la_holdback_end(&st->hb, st->end_rc, st->end_rc != ARCHIVE_OK ? st->end_msg : NULL, LA_HB_ALL);
-		return ARCHIVE_OK;
-	}
-	return la_window_carry(self, &st->w, &st->stage, &st->stage_len, pos, wk == WK_MORE, "block");
+	if (wk == WK_END)
+		la_holdback_end(&st->r.hb, st->end_rc, st->end_rc != ARCHIVE_OK ? st->end_msg : NULL, LA_HB_ALL);
+	return la_reader_finish(self, &st->r, pos, wk == WK_MORE, "block");
 }
 
 static ssize_t lzop_filter_read(struct archive_read_filter *self, const void **p)
 {
-	struct lzop_private *st = (struct lzop_private *)self->data;
-	return la_holdback_read(self, &st->w, &st->hb, p, lzo_window);
+	return la_reader_read(self, &((struct lzop_private *)self->data)->r, p, lzo_window);
 }
 
 static int lzop_filter_close(struct archive_read_filter *self)
@@ -404,16 +367,7 @@ static int lzop_filter_close(struct archive_read_filter *self)
 	struct lzop_private *st = (struct lzop_private *)self->data;
 	if (st == NULL)
 		return ARCHIVE_OK;
-	la_gpu_ctx *gpu = st->w.gpu;
-	(void)la_gpu_sync(gpu);
-	la_buf_release(gpu, &st->d_src);
-	la_buf_release(gpu, &st->d_dst);
-	la_buf_release(gpu, &st->d_tabs);
-	la_holdback_release(gpu, &st->hb);
-	la_buf_release(gpu, &st->stage);
-	la_gpu_close(gpu);
-	free(st->tab);
-	free(st->res);
+	la_reader_close(&st->r);
 	free(st);
 	self->data = NULL;
 	return ARCHIVE_OK;

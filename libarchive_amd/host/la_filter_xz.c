@@ -52,7 +52,6 @@
 #include "la_host.h"
 #include "../csrc/la_xz_dev.h"	/* la_xz_check_size: the rules header is plain C too */
 #include "../csrc/la_xz_filters_dev.h"	/* la_xz_filter_valid */
-#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -75,14 +74,11 @@ typedef struct xz_sums {
 } xz_sums;
 
 struct xz_private {
-	la_window w;
-	la_buf stage; size_t stage_len;	/* pinned: the stream from the first byte of the next unit on */
-	la_buf d_src, d_dst, d_tabs;	/* d_tabs: block table, results */
-	la_xz_block *tab;		/* host copies of the tables (XZ_TAB_CAP entries; room for the chains of a launch behind its blocks) */
+	la_reader r;			/* stage: from the first byte of the next unit on; d_tabs: block table, results */
+	la_xz_block *tab;		/* host copies of the tables, in r.h_tabs (XZ_TAB_CAP entries; room for the chains of a launch behind its blocks) */
 	la_xz_chain *chains;		/* tab[i]'s delta / BCJ filters (LA_XZ_CHAINS=1; otherwise all empty) */
 	la_xz_result *res;
 	int chains_on;			/* LA_XZ_CHAINS=1: delta and BCJ filters in front of LZMA2 are run, not refused */
-	la_holdback hb;			/* the decoded bytes, T and the stream's end */
 	/* where the container stands at stage[0] */
 	int seq, first_stream;
 	uint32_t check_id;		/* of the stream header: the footer's has to be the same */
@@ -125,13 +121,8 @@ static int xz_reader_bid(struct archive_read_filter_bidder *self, struct archive
 		return 0;
 	/* Default policy (la_bid_policy.c): a block without a compressed size is one serial chain of unknown extent; a
 	 * stream that opens with one and does not end inside the look-ahead is left to liblzma on a host core. */
-	if (!la_bid_take_all()) {
-		const size_t la = la_bid_lookahead(1024);
-		size_t got = 0;
-		const unsigned char *w = la_bid_peek(filter, la, &got);
-		if (w != NULL && !la_bid_xz_parallel(w, got, la))
-			return 0;
-	}
+	if (la_bid_declines(filter, la_bid_xz_parallel))
+		return 0;
 	return 48;
 }
 
@@ -140,25 +131,19 @@ static int xz_reader_init(struct archive_read_filter *self)
 	self->code = ARCHIVE_FILTER_XZ;
 	self->name = "xz";
 	struct xz_private *st = calloc(1, sizeof(*st));
-	la_xz_block *tab = malloc((sizeof(la_xz_block) + sizeof(la_xz_chain)) * XZ_TAB_CAP);
-	la_xz_chain *chains = calloc(XZ_TAB_CAP, sizeof(la_xz_chain));
-	la_xz_result *res = malloc(sizeof(la_xz_result) * XZ_TAB_CAP);
-	const int no_mem = st == NULL || tab == NULL || chains == NULL || res == NULL || la_holdback_open(&st->hb) < 0;
-	if (no_mem || la_window_open(self, &st->w, "xz") != ARCHIVE_OK) {
-		if (no_mem)
-			archive_set_error(&self->archive->archive, ENOMEM, "Can't allocate data for xz decompression");	/* xz.c:482-483 */
-		if (st)
-			la_holdback_release(NULL, &st->hb);
-		free(st); free(tab); free(chains); free(res);
+	/* (a block's dst_cap is at most LA_XZ_DST_CAP_MAX: 4095 MiB) */
+	if (la_reader_open(self, st ? &st->r : NULL, "xz", (sizeof(la_xz_block) + 2 * sizeof(la_xz_chain) + sizeof(la_xz_result)) * XZ_TAB_CAP,
+	    (uint64_t)4095 << 20, "Can't allocate data for xz decompression") != ARCHIVE_OK) {	/* xz.c:482-483 */
+		free(st);
 		return ARCHIVE_FATAL;
 	}
-	st->tab = tab; st->chains = chains; st->res = res;
+	st->tab = (la_xz_block *)st->r.h_tabs.p;
+	st->chains = (la_xz_chain *)((uint8_t *)st->tab + (sizeof(la_xz_block) + sizeof(la_xz_chain)) * XZ_TAB_CAP);	/* (zeroed) */
+	st->res = (la_xz_result *)(st->chains + XZ_TAB_CAP);
 	const char *v = getenv("LA_XZ_CHAINS");	/* read once, here */
 	st->chains_on = v != NULL && v[0] == '1';
 	st->seq = SEQ_HEADER;
 	st->first_stream = 1;
-	if (st->w.out_budget == 0 || st->w.out_budget > ((uint64_t)4095 << 20))
-		st->w.out_budget = (uint64_t)4095 << 20;	/* a block's dst_cap is at most LA_XZ_DST_CAP_MAX */
 	self->data = st;
 	self->vtable = &xz_reader_vtable;
 	return ARCHIVE_OK;
@@ -167,12 +152,12 @@ static int xz_reader_init(struct archive_read_filter *self)
 /* the stream ends here, T being hb.total: an error reported in the call that emitted byte T ... */
 static void xz_end_early(struct xz_private *st, int e)
 {
-	la_holdback_end(&st->hb, ARCHIVE_FATAL, xz_msg[e], LA_HB_EARLY);
+	la_holdback_end(&st->r.hb, ARCHIVE_FATAL, xz_msg[e], LA_HB_EARLY);
 }
 /* ... or in a call of its own */
 static void xz_end_late(struct xz_private *st, int e)
 {
-	la_holdback_end(&st->hb, ARCHIVE_FATAL, xz_msg[e], LA_HB_LATE);
+	la_holdback_end(&st->r.hb, ARCHIVE_FATAL, xz_msg[e], LA_HB_LATE);
 }
 
 /* vli.c, single-call mode: 0 and *pos advanced, or -1 (LZMA_DATA_ERROR: no byte left, a zero byte that is not the first,
@@ -352,29 +337,30 @@ static int64_t xz_index_parse(struct xz_private *st, const uint8_t *p, size_t n)
 /* Decode tab[0, n) in one call and append the bytes to the window's output; the results are in st->res. */
 static int xz_launch(struct archive_read_filter *self, struct xz_private *st, uint32_t n, uint64_t dst_bytes)
 {
-	la_gpu_ctx *gpu = st->w.gpu;
+	la_reader *r = &st->r;
+	la_gpu_ctx *gpu = r->w.gpu;
 	const size_t o_res = (sizeof(la_xz_block) + sizeof(la_xz_chain)) * XZ_TAB_CAP;
 	size_t tab_bytes = sizeof(la_xz_block) * n;
 	int chained = 0;
 	for (uint32_t i = 0; i < n; i++)
 		chained |= st->chains[i].count != 0;
-	if (la_buf_dev(gpu, &st->d_tabs, o_res + sizeof(la_xz_result) * XZ_TAB_CAP) < 0 || la_buf_dev(gpu, &st->d_dst, (size_t)dst_bytes + 64) < 0)
-		return la_window_fail(self, &st->w, "la_gpu_malloc");
+	if (la_buf_dev(gpu, &r->d_tabs, o_res + sizeof(la_xz_result) * XZ_TAB_CAP) < 0 || la_buf_dev(gpu, &r->d_dst, (size_t)dst_bytes + 64) < 0)
+		return la_window_fail(self, &r->w, "la_gpu_malloc");
 	la_xz_batch bt;
 	memset(&bt, 0, sizeof(bt));
-	bt.d_src = st->d_src.p; bt.src_bytes = st->stage_len;
-	bt.d_blocks = (const la_xz_block *)st->d_tabs.p; bt.n = n;
-	bt.d_dst = st->d_dst.p; bt.dst_cap = dst_bytes;
-	bt.d_results = (la_xz_result *)(st->d_tabs.p + o_res);
+	bt.d_src = r->d_src.p; bt.src_bytes = r->stage_len;
+	bt.d_blocks = (const la_xz_block *)r->d_tabs.p; bt.n = n;
+	bt.d_dst = r->d_dst.p; bt.dst_cap = dst_bytes;
+	bt.d_results = (la_xz_result *)(r->d_tabs.p + o_res);
 	if (chained) {	/* the chain table rides behind the blocks, and only then */
 		memcpy(st->tab + n, st->chains, sizeof(la_xz_chain) * n);
 		tab_bytes += sizeof(la_xz_chain) * n;
 		bt.reserved = LA_XZ_BATCH_CHAINS;
 	}
-	if (la_gpu_memcpy_h2d(gpu, st->d_tabs.p, st->tab, tab_bytes) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
-	if (la_gpu_xz_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_xz_decode");
+	if (la_gpu_memcpy_h2d(gpu, r->d_tabs.p, st->tab, tab_bytes) != LA_OK) return la_window_fail(self, &r->w, "la_gpu_memcpy_h2d");
+	if (la_gpu_xz_decode(gpu, &bt) != LA_OK) return la_window_fail(self, &r->w, "la_gpu_xz_decode");
 	if (la_gpu_memcpy_d2h(gpu, st->res, bt.d_results, sizeof(la_xz_result) * n) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-		return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
+		return la_window_fail(self, &r->w, "la_gpu_memcpy_d2h");
 	return ARCHIVE_OK;
 }
 
@@ -401,7 +387,6 @@ static uint64_t xz_chain_hold(const la_xz_chain *ch)
  * bytes of that one, come back from the device. */
 static int xz_take_results(struct archive_read_filter *self, struct xz_private *st, uint32_t n)
 {
-	la_gpu_ctx *gpu = st->w.gpu;
 	uint64_t bytes = 0;
 	uint32_t bad = n;
 	for (uint32_t i = 0; i < n && bad == n; i++) {
@@ -415,17 +400,10 @@ static int xz_take_results(struct archive_read_filter *self, struct xz_private *
 		const uint64_t hold = xz_chain_hold(&st->chains[bad]);
 		bytes -= hold < st->res[bad].out_len ? hold : st->res[bad].out_len;
 	}
-	if (bytes) {
-		if (la_buf_pinned(gpu, &st->hb.out, st->hb.out_len + (size_t)bytes + 64, st->hb.out_len) < 0)
-			return la_window_fail(self, &st->w, "la_gpu_malloc_host");
-		if (la_gpu_memcpy_d2h(gpu, st->hb.out.p + st->hb.out_len, st->d_dst.p, bytes) != LA_OK || la_gpu_sync(gpu) != LA_OK)
-			return la_window_fail(self, &st->w, "la_gpu_memcpy_d2h");
-	}
-	st->hb.out_len += (size_t)bytes;
-	st->hb.total += bytes;
-	if (bad < n)
+	const int rc = la_reader_take(self, &st->r, bytes);
+	if (rc == ARCHIVE_OK && bad < n)
 		xz_block_failed(st, st->res[bad].status);
-	return ARCHIVE_OK;
+	return rc;
 }
 
 /* One window: gather, upload, walk; updates T, and says how the stream ends if this window shows it.
@@ -433,22 +411,18 @@ static int xz_take_results(struct archive_read_filter *self, struct xz_private *
 static int xz_window(struct archive_read_filter *self)
 {
 	struct xz_private *st = (struct xz_private *)self->data;
-	la_gpu_ctx *gpu = st->w.gpu;
-	int r = la_window_gather(self, &st->w, &st->stage, &st->stage_len);
+	const la_window *w = &st->r.w;
+	int r = la_reader_gather(self, &st->r);
 	if (r != ARCHIVE_OK)
 		return r;
-	const uint8_t *src = st->stage.p;
-	const size_t len = st->stage_len;
-	const int eof = st->w.upstream_eof;
-	if (len) {
-		if (la_buf_dev(gpu, &st->d_src, len + 64) < 0) return la_window_fail(self, &st->w, "la_gpu_malloc");
-		if (la_gpu_memcpy_h2d(gpu, st->d_src.p, src, len) != LA_OK) return la_window_fail(self, &st->w, "la_gpu_memcpy_h2d");
-	}
+	const uint8_t *src = st->r.stage.p;
+	const size_t len = st->r.stage_len;
+	const int eof = w->upstream_eof;
 	size_t pos = 0;		/* the first byte of the unit the walk stands at */
 	int more = 0;		/* that unit needs bytes the window does not hold */
 	uint32_t n = 0;		/* sized blocks collected for one launch */
 	uint64_t dst_bytes = 0;
-	while (!st->hb.ended && !more) {
+	while (!st->r.hb.ended && !more) {
 		/* the block header at pos, when the walk stands at one and all of it is here: parsed once per turn */
 		xz_block_header bh;
 		size_t hsize = 0;
@@ -458,12 +432,12 @@ static int xz_window(struct archive_read_filter *self)
 		if (st->seq == SEQ_BLOCK && len - pos >= 1 && src[pos] != 0 && len - pos >= (hsize = ((size_t)src[pos] + 1) * 4))
 			hdr = xz_block_header_parse(src + pos, hsize, st->check_id, st->chains_on, &bh);
 		const int sound = hdr == -1 && !bh.unsupported;
-		const int too_large = sound && ((bh.comp != LA_XZ_UNKNOWN && bh.comp > st->w.max_batch_bytes) ||
-		    (bh.uncomp != LA_XZ_UNKNOWN && bh.uncomp > st->w.out_budget));
+		const int too_large = sound && ((bh.comp != LA_XZ_UNKNOWN && bh.comp > w->max_batch_bytes) ||
+		    (bh.uncomp != LA_XZ_UNKNOWN && bh.uncomp > w->out_budget));
 		/* both sizes in the header and the whole block in the window: hopped over, decoded with its neighbours */
 		const int whole = sound && !too_large && bh.comp != LA_XZ_UNKNOWN && bh.uncomp != LA_XZ_UNKNOWN &&
 		    len - pos - hsize >= ceil4(bh.comp) + cs;
-		if (whole && n < XZ_TAB_CAP && !(n && dst_bytes + bh.uncomp > st->w.out_budget)) {
+		if (whole && n < XZ_TAB_CAP && !(n && dst_bytes + bh.uncomp > w->out_budget)) {
 			st->chains[n] = bh.chain;
 			la_xz_block *b = &st->tab[n++];
 			b->src_off = pos + hsize; b->comp_size = bh.comp; b->uncomp_size = bh.uncomp;
@@ -525,7 +499,7 @@ static int xz_window(struct archive_read_filter *self)
 			if (too_large) {
 				archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
 				    "xz block too large for the GPU data plane (more than %llu compressed or %llu decoded bytes; LA_GPU_MAX_BATCH_MIB, LA_GPU_OUT_BUDGET_MIB)",
-				    (unsigned long long)st->w.max_batch_bytes, (unsigned long long)st->w.out_budget);
+				    (unsigned long long)w->max_batch_bytes, (unsigned long long)w->out_budget);
 				return ARCHIVE_FATAL;
 			}
 			/* a size is missing, or the block is not all here: alone, bounded by the window's end and by a budget that grows
@@ -535,14 +509,7 @@ static int xz_window(struct archive_read_filter *self)
 				more = 1;	/* the header says how much is missing */
 				break;
 			}
-			uint64_t cap = bh.uncomp;
-			if (cap == LA_XZ_UNKNOWN) {
-				if (st->solo_cap == 0)
-					st->solo_cap = have * 8 > ((uint64_t)1 << 20) ? have * 8 : (uint64_t)1 << 20;
-				if (st->solo_cap > st->w.out_budget)
-					st->solo_cap = st->w.out_budget;
-				cap = st->solo_cap;
-			}
+			const uint64_t cap = bh.uncomp != LA_XZ_UNKNOWN ? bh.uncomp : la_reader_solo_cap(&st->r, &st->solo_cap, have);
 			st->chains[0] = bh.chain;
 			la_xz_block *b = &st->tab[0];
 			b->src_off = pos + hsize; b->comp_size = bh.comp; b->uncomp_size = bh.uncomp;
@@ -552,13 +519,8 @@ static int xz_window(struct archive_read_filter *self)
 				return r;
 			const la_xz_result q = st->res[0];
 			if (q.status == LA_ST_XZ_OUT_FULL) {
-				if (cap >= st->w.out_budget) {
-					archive_set_error(&self->archive->archive, ARCHIVE_ERRNO_MISC,
-					    "xz block too large for the GPU data plane (more than %llu decoded bytes; LA_GPU_OUT_BUDGET_MIB)",
-					    (unsigned long long)st->w.out_budget);
-					return ARCHIVE_FATAL;
-				}
-				st->solo_cap = cap * 2;
+				if ((r = la_reader_solo_full(self, &st->r, &st->solo_cap, cap, "block")) != ARCHIVE_OK)
+					return r;
 				break;	/* again, with twice the room */
 			}
 			if (q.status == LA_ST_XZ_TRUNCATED && !eof) {
@@ -625,7 +587,7 @@ static int xz_window(struct archive_read_filter *self)
 				if (st->pad_mod)
 					xz_end_early(st, XZ_E_DATA);
 				else
-					la_holdback_end(&st->hb, ARCHIVE_OK, NULL, LA_HB_ALL);
+					la_holdback_end(&st->r.hb, ARCHIVE_OK, NULL, LA_HB_ALL);
 			} else {
 				more = 1;
 			}
@@ -633,16 +595,12 @@ static int xz_window(struct archive_read_filter *self)
 		}
 		}
 	}
-	la_window_ramp(&st->w);
-	if (st->hb.ended)
-		return ARCHIVE_OK;
-	return la_window_carry(self, &st->w, &st->stage, &st->stage_len, pos, more, "block");
+	return la_reader_finish(self, &st->r, pos, more, "block");
 }
 
 static ssize_t xz_filter_read(struct archive_read_filter *self, const void **p)
 {
-	struct xz_private *st = (struct xz_private *)self->data;
-	return la_holdback_read(self, &st->w, &st->hb, p, xz_window);
+	return la_reader_read(self, &((struct xz_private *)self->data)->r, p, xz_window);
 }
 
 static int xz_filter_close(struct archive_read_filter *self)
@@ -650,17 +608,7 @@ static int xz_filter_close(struct archive_read_filter *self)
 	struct xz_private *st = (struct xz_private *)self->data;
 	if (st == NULL)
 		return ARCHIVE_OK;
-	la_gpu_ctx *gpu = st->w.gpu;
-	(void)la_gpu_sync(gpu);
-	la_buf_release(gpu, &st->d_src);
-	la_buf_release(gpu, &st->d_dst);
-	la_buf_release(gpu, &st->d_tabs);
-	la_holdback_release(gpu, &st->hb);
-	la_buf_release(gpu, &st->stage);
-	la_gpu_close(gpu);
-	free(st->tab);
-	free(st->chains);
-	free(st->res);
+	la_reader_close(&st->r);
 	free(st);
 	self->data = NULL;
 	return ARCHIVE_OK;

@@ -81,13 +81,8 @@ static int zstd_reader_bid(struct archive_read_filter_bidder *self, struct archi
 	const int bits = la_zstd_bid_bytes(p, 4);
 	/* Default policy (la_bid_policy.c): a frame is one serial chain (one wave); a stream whose first frame does not
 	 * end inside the look-ahead is left to libzstd on a host core. */
-	if (bits > 0 && !la_bid_take_all()) {
-		const size_t la = la_bid_lookahead(1024);
-		size_t got = 0;
-		const unsigned char *w = la_bid_peek(filter, la, &got);
-		if (w != NULL && !la_bid_zstd_parallel(w, got, la))
-			return 0;
-	}
+	if (bits > 0 && la_bid_declines(filter, la_bid_zstd_parallel))
+		return 0;
 	return bits;
 }
 

@@ -9,6 +9,7 @@
  */
 #include "../../include/la_gpu.h"
 #include "../../oracle/la_oracle.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <zlib.h>	/* LA_GZ_OPT_PIECES: Z_BLOCK and inflateSetDictionary */
@@ -20,11 +21,37 @@ unsigned long la_gpu_mock_hist_blocks(void) { return mock_hist_blocks; }
 struct la_gpu_ctx { char err[64]; };
 _Static_assert(sizeof(orc_xxh32_state) <= LA_XXH_CARRY_BYTES, "carry buffer too small for the oracle's state");
 
+/* test hook: LA_MOCK_FAIL=<call>:<k>, read by la_gpu_open (which also starts the count afresh), makes the k-th call of
+ * <call> behind it fail with "mock failure" as the context's error text; la_gpu_open:1 fails the open itself.  <call>:
+ * la_gpu_open, la_gpu_malloc, la_gpu_malloc_host, la_gpu_memcpy_h2d, la_gpu_memcpy_d2h.  Unset: nothing fails.
+ * la_gpu_mock_failed: how many calls the hook has failed in this process. */
+static char fail_call[32];
+static unsigned long fail_k, fail_seen, mock_failed;
+unsigned long la_gpu_mock_failed(void) { return mock_failed; }
+static int mock_fails(la_gpu_ctx *c, const char *call)
+{
+	if (fail_k == 0 || strcmp(call, fail_call) != 0 || ++fail_seen != fail_k)
+		return 0;
+	mock_failed++;
+	if (c)
+		snprintf(c->err, sizeof(c->err), "mock failure");
+	return 1;
+}
+
 int la_gpu_abi_version(void) { return LA_GPU_ABI_VERSION; }
 int la_gpu_device_count(void) { return 1; }
 int la_gpu_open(int device, la_gpu_ctx **out)
 {
 	(void)device;
+	const char *v = getenv("LA_MOCK_FAIL"), *colon = v ? strchr(v, ':') : NULL;
+	fail_k = fail_seen = 0;
+	if (colon != NULL && (size_t)(colon - v) < sizeof(fail_call)) {
+		snprintf(fail_call, sizeof(fail_call), "%.*s", (int)(colon - v), v);
+		fail_k = strtoul(colon + 1, NULL, 10);
+	}
+	*out = NULL;
+	if (mock_fails(NULL, "la_gpu_open"))
+		return LA_ERR_NO_DEVICE;
 	*out = calloc(1, sizeof(**out));
 	return *out ? LA_OK : LA_ERR_NOMEM;
 }
@@ -35,12 +62,25 @@ int la_gpu_mark(la_gpu_ctx *c) { (void)c; return LA_OK; }
 int la_gpu_wait_mark(la_gpu_ctx *c) { (void)c; return LA_OK; }
 const char *la_gpu_last_error(const la_gpu_ctx *c) { return c ? c->err : "no context"; }
 int la_gpu_reserve(la_gpu_ctx *c, uint64_t b) { (void)c; (void)b; return LA_OK; }
-int la_gpu_malloc(la_gpu_ctx *c, void **p, uint64_t n) { (void)c; *p = malloc(n ? n : 1); return *p ? LA_OK : LA_ERR_NOMEM; }
+static int mock_alloc(void **p, uint64_t n) { *p = malloc(n ? n : 1); return *p ? LA_OK : LA_ERR_NOMEM; }
+int la_gpu_malloc(la_gpu_ctx *c, void **p, uint64_t n) { return mock_fails(c, "la_gpu_malloc") ? LA_ERR_NOMEM : mock_alloc(p, n); }
 int la_gpu_free(la_gpu_ctx *c, void *p) { (void)c; free(p); return LA_OK; }
-int la_gpu_malloc_host(la_gpu_ctx *c, void **p, uint64_t n) { return la_gpu_malloc(c, p, n); }
+int la_gpu_malloc_host(la_gpu_ctx *c, void **p, uint64_t n) { return mock_fails(c, "la_gpu_malloc_host") ? LA_ERR_NOMEM : mock_alloc(p, n); }
 int la_gpu_free_host(la_gpu_ctx *c, void *p) { return la_gpu_free(c, p); }
-int la_gpu_memcpy_h2d(la_gpu_ctx *c, void *d, const void *h, uint64_t n) { (void)c; if (n) memcpy(d, h, n); return LA_OK; }
-int la_gpu_memcpy_d2h(la_gpu_ctx *c, void *h, const void *d, uint64_t n) { (void)c; if (n) memcpy(h, d, n); return LA_OK; }
+int la_gpu_memcpy_h2d(la_gpu_ctx *c, void *d, const void *h, uint64_t n)
+{
+	if (mock_fails(c, "la_gpu_memcpy_h2d"))
+		return LA_ERR_HIP;
+	if (n) memcpy(d, h, n);
+	return LA_OK;
+}
+int la_gpu_memcpy_d2h(la_gpu_ctx *c, void *h, const void *d, uint64_t n)
+{
+	if (mock_fails(c, "la_gpu_memcpy_d2h"))
+		return LA_ERR_HIP;
+	if (n) memcpy(h, d, n);
+	return LA_OK;
+}
 int la_gpu_memcpy_d2d(la_gpu_ctx *c, void *d, const void *s, uint64_t n) { (void)c; if (n) memmove(d, s, n); return LA_OK; }
 
 static void summary_init(la_batch_summary *sm)
