@@ -1,16 +1,16 @@
 """Support for the lzip write tests: the named inputs of the device tests (shared with the recorded digests of
 tests/golden/lzip_write_digests.json), the checks every written image has to pass, and the CPU stand-in of
-tests/mock_lzip_write, which compiles the kernels' own rules header and therefore writes the device's bytes."""
+tests/mock_gpu/la_gpu_lzip_comp_mock.c, which compiles the kernels' own rules header and therefore writes the device's bytes."""
 import ctypes as C
 import functools
 import hashlib
 import json
 import os
 import struct
-import subprocess
 import zlib
 
 import lzip_support as LS
+import mock_build
 import xz_write_support as XW
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -108,16 +108,11 @@ class _Batch(C.Structure):      # la_lzc_batch
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
 
 
-def build_mock(out_dir, target=None):
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzip_write"), "OUT=" + out_dir] + ([target] if target else []))
-
-
 class StandIn:
-    """la_gpu_lzip_compress of tests/mock_lzip_write through its ABI entry ("device" pointers are host pointers)"""
+    """la_gpu_lzip_compress of tests/mock_gpu through its ABI entry ("device" pointers are host pointers)"""
 
-    def __init__(self, out_dir):
-        build_mock(out_dir)
-        lib = C.CDLL(os.path.join(out_dir, "libla_gpu_lzwmock.so"))
+    def __init__(self):
+        lib = mock_build.gpu_lib()
         lib.la_gpu_lzip_compress.argtypes = [C.c_void_p, C.POINTER(_Batch)]
         lib.la_gpu_lzip_compress_bound.restype = C.c_uint64
         lib.la_gpu_lzip_compress_bound.argtypes = [C.c_uint64, C.c_uint32]

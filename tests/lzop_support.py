@@ -713,7 +713,7 @@ def mock_decode(lib, src, blocks, dst_cap):
 
 
 def rules_decode(lib, stream, dst_len):
-    """la_lzo_dev.h's decoder alone, as tests/mock_lzop exports it: (status name, bytes, consumed)"""
+    """la_lzo_dev.h's decoder alone, as tests/mock_gpu/la_gpu_lzop_mock.c exports it: (status name, bytes, consumed)"""
     names = {v: k for k, v in ST.items()}
     dst = C.create_string_buffer(max(dst_len, 1))
     out_len, consumed = C.c_uint32(), C.c_uint32()

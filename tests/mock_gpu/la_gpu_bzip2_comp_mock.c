@@ -1,7 +1,7 @@
 /*
  * la_gpu_bzip2_comp_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_bzip2_compress over the real libbz2, so
  * that the bzip2 write filter's host side (windows, FIRST / LAST, the state carried between calls, the empty stream)
- * is tested without a device.  "Device" pointers are host pointers, as in ../mock_gpu/la_gpu_mock.c.
+ * is tested without a device.  "Device" pointers are host pointers, as in la_gpu_mock.c.
  *
  * The same contract as the device: the input is cut every la_gpu_bzip2_compress_block_bytes(level) bytes; per cut ONE
  * BZ2_bzCompressInit(level) / BZ_FINISH stream, which holds exactly one block because the cut fits libbz2's block

@@ -1,7 +1,7 @@
 /*
  * la_gpu_bzip2_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_bzip2_scan / la_gpu_bzip2_decode as
  * include/la_gpu.h words them, over the image's real libbz2, so that the host side (la_filter_bzip2.c: windows, carry,
- * budget, held-back bytes, verdicts) is tested without a GPU.  Linked beside ../mock_gpu/la_gpu_mock.c as it is.
+ * budget, held-back bytes, verdicts) is tested without a GPU.  Linked beside la_gpu_mock.c.
  *
  * The walk is the ABI's (confirm candidates in stream order from state_in).  A block the walk reaches is decoded by
  * libbz2: its bits are re-aligned behind a "BZh<level>" header and fed to BZ2_bzDecompress one byte at a time.  libbz2

@@ -1,7 +1,7 @@
 /* TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_gzip_decode with LA_GZ_OPT_BLOCK_STARTS, as include/la_gpu.h words it,
  * so that the host side of the gzip read filter's block-start mode runs without a GPU.  The candidates are the rules
  * header's (la_deflate_find_dev.h, compiled for the host); the decode is zlib's raw inflate walked with Z_BLOCK, which says
- * where every block ends: a piece ends where a block ends on a candidate.  Every other call goes to ../mock_gpu, whose
+ * where every block ends: a piece ends where a block ends on a candidate.  Every other call goes to la_gpu_mock.c, whose
  * la_gpu_gzip_decode is compiled under the name la_gpu_gzip_decode_base (Makefile).  Not part of the product. */
 #include <stdint.h>
 #include <stdlib.h>

@@ -1,7 +1,7 @@
 /*
  * la_gpu_lzip_comp_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_lzip_compress as include/la_gpu.h words it,
  * so that the lzip write filter's host side (host/la_write_lzip.c) and the encoder's rules are tested without a GPU.
- * "Device" pointers are host pointers, as in ../mock_gpu/la_gpu_mock.c.
+ * "Device" pointers are host pointers, as in la_gpu_mock.c.
  *
  * The rules are NOT restated here: this file compiles libarchive_amd/csrc/la_lzip_enc_dev.h (over la_xz_enc_dev.h), the
  * header the kernels compile, with the header's defaults: the 64 lanes of a step are walked in a loop, all reads before

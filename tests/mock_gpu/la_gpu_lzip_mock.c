@@ -1,7 +1,7 @@
 /*
  * la_gpu_lzip_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_lzip_scan and la_gpu_lzip_decode as
  * include/la_gpu.h words them, so that the host side (la_filter_lzip.c: the chain of members, windows, held-back bytes,
- * verdicts) is tested without a GPU.  Linked beside ../mock_gpu/la_gpu_mock.c as it is.
+ * verdicts) is tested without a GPU.  Linked beside la_gpu_mock.c.
  *
  * The decode rules are NOT restated here: this file compiles libarchive_amd/csrc/la_lzip_dev.h (and through it
  * la_xz_dev.h's symbol loop), the headers the kernel compiles, one member after the other.  What the kernel adds around

@@ -1,7 +1,7 @@
 /*
  * la_gpu_lzop_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_lzop_decode and la_gpu_adler32_many as
  * include/la_gpu.h words them, so that the host side (la_filter_lzop.c: the walk over headers and block infos, windows,
- * verdicts) is tested without a GPU.  Linked beside ../mock_gpu/la_gpu_mock.c as it is.
+ * verdicts) is tested without a GPU.  Linked beside la_gpu_mock.c.
  *
  * The LZO1X rules are NOT restated here: this file compiles libarchive_amd/csrc/la_lzo_dev.h, the header the kernel
  * compiles, with its plain hooks, one block after the other.  What the kernel adds around the header (the refused

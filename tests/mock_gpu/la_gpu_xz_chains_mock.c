@@ -1,11 +1,11 @@
 /*
- * la_gpu_xz_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_xz_decode as include/la_gpu.h words it, so that the
- * host side (la_filter_xz.c: the container walk, windows, held-back bytes, verdicts) is tested without a GPU.  Linked
- * beside ../mock_gpu/la_gpu_mock.c as it is.
+ * la_gpu_xz_chains_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_xz_decode as include/la_gpu.h words it,
+ * the chain table (LA_XZ_BATCH_CHAINS) included, so that the host side (la_filter_xz.c, with and without LA_XZ_CHAINS=1)
+ * is tested without a GPU: a batch without the table is decoded as it stands.  Linked beside la_gpu_mock.c.
  *
- * The decode rules are NOT restated here: this file compiles libarchive_amd/csrc/la_xz_dev.h, the header the kernel
- * compiles, one block after the other.  What the kernel adds around the header (which bound is which, the size
- * comparison, the check values) is repeated below in the kernel's order.  CRC32 is zlib's.
+ * Neither the decode rules nor the filters are restated here: this file compiles libarchive_amd/csrc/la_xz_dev.h and
+ * la_xz_filters_dev.h, the headers the kernels compile, one block after the other, in the kernels' order: decode, the
+ * chain undone over the bytes there are (out_len, which on a failure counts the valid bytes), then sizes and check.
  */
 #include "../../include/la_gpu.h"
 #include <stdlib.h>
@@ -14,6 +14,7 @@
 
 #define LA_XZ_FN static inline
 #include "../../libarchive_amd/csrc/la_xz_dev.h"
+#include "../../libarchive_amd/csrc/la_xz_filters_dev.h"
 
 uint64_t la_gpu_xz_workspace_bytes(uint32_t n) { (void)n; return 0; }
 
@@ -21,8 +22,9 @@ int la_gpu_xz_decode(la_gpu_ctx *c, const la_xz_batch *bt)
 {
 	static uint64_t table[256];
 	(void)c;
-	if (!bt || bt->reserved || (bt->n && (!bt->d_blocks || !bt->d_results || !bt->d_dst || (bt->src_bytes && !bt->d_src))))
+	if (!bt || (bt->reserved & ~LA_XZ_BATCH_CHAINS) || (bt->n && (!bt->d_blocks || !bt->d_results || !bt->d_dst || (bt->src_bytes && !bt->d_src))))
 		return LA_ERR_ARG;
+	const la_xz_chain *chains = (bt->reserved & LA_XZ_BATCH_CHAINS) ? (const la_xz_chain *)(bt->d_blocks + bt->n) : NULL;
 	if (table[1] == 0)
 		for (uint32_t i = 0; i < 256; i++)
 			table[i] = la_xz_crc64_entry(i);
@@ -35,7 +37,8 @@ int la_gpu_xz_decode(la_gpu_ctx *c, const la_xz_batch *bt)
 		la_xz_lzma lz;
 		memset(&r, 0, sizeof(r));
 		if (blk.src_off > bt->src_bytes || blk.dst_off > bt->dst_cap || blk.dst_cap > bt->dst_cap - blk.dst_off ||
-		    blk.dst_cap > LA_XZ_DST_CAP_MAX || (blk.uncomp_size != LA_XZ_UNKNOWN && blk.uncomp_size > blk.dst_cap)) {
+		    blk.dst_cap > LA_XZ_DST_CAP_MAX || (blk.uncomp_size != LA_XZ_UNKNOWN && blk.uncomp_size > blk.dst_cap) ||
+		    (chains && !la_xz_chain_valid(&chains[b]))) {
 			r.status = LA_ST_XZ_SIZE;
 			bt->d_results[b] = r;
 			continue;
@@ -52,6 +55,8 @@ int la_gpu_xz_decode(la_gpu_ctx *c, const la_xz_batch *bt)
 		    sized ? (uint32_t)LA_ST_XZ_SIZE : (uint32_t)LA_ST_XZ_OUT_FULL, blk.dict_size, probs, &lz, &r);
 		if (r.status == LA_ST_OK && !la_xz_sizes_agree(&blk, &r))
 			r.status = LA_ST_XZ_SIZE;
+		if (chains)
+			la_xz_unchain_serial(&chains[b], out, r.status == LA_ST_OK ? r.out_len : r.valid);
 		if (r.status == LA_ST_OK) {
 			uint8_t have[64];
 			int supported = 1;

@@ -1,7 +1,7 @@
 /*
  * la_gpu_xz_comp_mock.c -- TEST INFRASTRUCTURE: a CPU stand-in for la_gpu_xz_compress as include/la_gpu.h words it, so
  * that the xz write filter's host side (host/la_write_xz.c) and the encoder's rules are tested without a GPU.  "Device"
- * pointers are host pointers, as in ../mock_gpu/la_gpu_mock.c.
+ * pointers are host pointers, as in la_gpu_mock.c.
  *
  * The rules are NOT restated here: this file compiles libarchive_amd/csrc/la_xz_enc_dev.h, the header the kernels
  * compile, with the header's defaults: the 64 lanes of a step are walked in a loop, all reads before any write, so the

@@ -1,6 +1,6 @@
 /*
  * la_gpu_zip_mock.c -- TEST INFRASTRUCTURE: la_gpu_zip_compress of include/la_gpu.h on the CPU, through zlib, beside
- * ../mock_gpu/la_gpu_mock.c (which has the rest of the ABI; "device" memory is host memory there).  It keeps the
+ * la_gpu_mock.c (which has the rest of the ABI; "device" memory is host memory there).  It keeps the
  * call's contract -- layout, gaps left alone, results, errors -- not the device's bytes: a deflated segment is one
  * raw-deflate stream with a Z_SYNC_FLUSH behind every chunk and 03 00 where the entry ends, so matches may cross
  * chunks and a chunk may cost a few bytes more than on the device.  Its bound is its own.

@@ -1,8 +1,8 @@
 /*
- * lzip_read_main.c -- TEST INFRASTRUCTURE: a program of its own that reads lzip images through the host side
- * (read core, la_filter_lzip.c) over the CPU mock of the device ABI, for the sanitizer build of the Makefile.
+ * la_read_main.c -- TEST INFRASTRUCTURE: a program of its own that reads compressed images of any format through the
+ * host side (read core, every read filter) over the CPU mock of the device ABI, for the sanitizer build of the Makefile.
  *
- *   lzip_read_asan FILE...      every file is one image; prints "rc bytes fnv1a message" per file
+ *   la_read_asan FILE...      every file is one image; prints "rc bytes fnv1a message" per file
  *
  * Each image is read three ways: in one piece, 1000 bytes at a time and 1 byte at a time (the last only below 64 KiB),
  * and the three must agree.
@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+void la_gpu_bzip2_mock_release(void);
 
 static int read_image(const unsigned char *img, size_t n, size_t read_size, unsigned long long *bytes, unsigned long long *hash, char *msg, size_t msg_cap)
 {
@@ -67,5 +68,6 @@ int main(int argc, char **argv)
 		}
 		free(img);
 	}
+	la_gpu_bzip2_mock_release();
 	return bad;
 }

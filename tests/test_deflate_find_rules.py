@@ -1,34 +1,24 @@
 """The candidate rule of the block-start finder (libarchive_amd/csrc/la_deflate_find_dev.h), compiled for the host
-(tests/mock_gz_blocks/deflate_find_shim.cpp), against the plain-Python model of tests/deflate_find_support.py at EVERY bit
+(tests/mock_gpu/deflate_find_shim.cpp), against the plain-Python model of tests/deflate_find_support.py at EVERY bit
 of its inputs, and against zlib's own list of block starts (inflate with Z_BLOCK): the rule may call a false position a
 candidate, it may never miss a true non-final dynamic block start.  The quick form (what the first kernel pass tests) must
 hold wherever the full rule does."""
 import ctypes as C
-import os
 import random
 import subprocess
-import zlib
 
 import pytest
 
 import deflate_build as B
 import deflate_find_support as F
+import mock_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 NOISE_SEED = 20261019
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("deflate_find"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_gz_blocks"), "OUT=" + out,
-                           os.path.join(out, "libdeflate_find_rules.so"), os.path.join(out, "deflate_find_asan")])
-    return out
-
-
-@pytest.fixture(scope="module")
-def rules(built):
-    lib = C.CDLL(os.path.join(built, "libdeflate_find_rules.so"))
+def rules():
+    lib = C.CDLL(mock_build.rules("libdeflate_find_rules.so"))
     lib.deflate_find_scan.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p]
     lib.deflate_find_scan.restype = C.c_uint64
     return lib
@@ -131,7 +121,7 @@ def test_hand_built_headers(rules, lead):
         assert (verdict != "data") == (want or name == "final"), (name, verdict)
 
 
-def test_sanitizer_program(built, inputs, tmp_path):
+def test_sanitizer_program(inputs, tmp_path):
     """the same header over the same inputs in a program of its own under AddressSanitizer and UBSan, every input in a heap
     buffer of exactly its size"""
     names = sorted(inputs)
@@ -140,7 +130,7 @@ def test_sanitizer_program(built, inputs, tmp_path):
         p = tmp_path / (n + ".bin")
         p.write_bytes(inputs[n][0])
         paths.append(str(p))
-    r = subprocess.run([os.path.join(built, "deflate_find_asan")] + paths, capture_output=True, text=True)
+    r = subprocess.run([mock_build.program("deflate_find_asan")] + paths, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     for n, line in zip(names, r.stdout.splitlines()):
         size, quick, cands, possum = (int(x) for x in line.split())

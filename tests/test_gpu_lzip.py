@@ -1,27 +1,23 @@
 """The device ABI of the lzip kernels (la_lzip.hip through la_gpu_lzip_scan / la_gpu_lzip_decode) against liblzma's raw
 LZMA1 decoder (lzip_support.expected_stream_result), Python's lzma, and the CPU stand-in that compiles the same rules
-headers (tests/mock_lzip): status, bytes, consumed and CRC32 per member."""
+headers (tests/mock_gpu/la_gpu_lzip_mock.c): status, bytes, consumed and CRC32 per member."""
 import ctypes as C
-import os
 import random
-import subprocess
 import zlib
 
 import pytest
 
 import lzip_support as LS
+import mock_build
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 TILE = 4096
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_lzip"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzip"), "OUT=" + out, os.path.join(out, "libla_gpu_lzipmock.so")])
-    return C.CDLL(os.path.join(out, "libla_gpu_lzipmock.so"))
+def mock():
+    return C.CDLL(mock_build.rules("liblzip_rules.so"))
 
 
 def host_scan(buf):

@@ -1,27 +1,22 @@
 """The bzip2 read filter's HOST side (la_filter_bzip2.c: windows, carry of the unfinished unit and the stream state, the
 decoded-bytes budget, the bytes held back in front of an error, verdicts and strings) over a CPU stand-in for
-la_gpu_bzip2_scan / la_gpu_bzip2_decode (tests/mock_bzip2: the real libbz2, one block at a time).  la_api.cat through
+la_gpu_bzip2_scan / la_gpu_bzip2_decode (tests/mock_gpu/la_gpu_bzip2_mock.c: the real libbz2, one block at a time).  la_api.cat through
 the mock library must equal the reference's read loop over libbz2 (bzip2_support.reference_read) on bytes, return
 code, error string and filter code / name."""
-import ctypes as C
-import os
 import random
-import subprocess
 
 import pytest
 
 import bzip2_support as BS
 import la_api
+import mock_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ARCHIVE_FILTER_BZIP2 = 2
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_bzip2"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_bzip2"), "OUT=" + out])
-    lib = C.CDLL(os.path.join(out, "libla_host_bz2mock.so"))      # (finds libla_gpu_bz2mock.so beside itself)
+def mock():
+    lib = mock_build.host_lib()
     la_api.use_library(lib)
     yield lib
     la_api.use_library(None)

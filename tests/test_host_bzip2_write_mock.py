@@ -1,6 +1,6 @@
 """The bzip2 write filter's HOST side (host/la_write_bzip2.c: options, windows of whole blocks, FIRST on the first
 window, LAST on close()'s flush only, the device-resident stream state, the empty stream) over a CPU stand-in for
-la_gpu_bzip2_compress (tests/mock_bzip2_write: the real libbz2, one block per cut).  Every image must be ONE stream that
+la_gpu_bzip2_compress (tests/mock_gpu/la_gpu_bzip2_comp_mock.c: the real libbz2, one block per cut).  Every image must be ONE stream that
 libbz2 (bz2.decompress) and the reference's read loop over libbz2 (bzip2_support.reference_read) decode to the input.
 A stand-alone program writes the same shapes under the address and undefined-behaviour sanitizers."""
 import bz2
@@ -11,23 +11,17 @@ import subprocess
 import pytest
 
 import bzip2_support as BS
+import mock_build
 from test_gpu_lz4_write import _lib_setup
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ARCHIVE_OK, ARCHIVE_FAILED, ARCHIVE_FATAL = 0, -25, -30
 BLOCK1 = 4 * ((100000 - 19) // 5)
 WINDOW1 = (1 << 20) // BLOCK1 * BLOCK1        # LA_GPU_WRITE_WINDOW_MIB=1 at level 1: 13 whole blocks
 
 
 @pytest.fixture(scope="module")
-def build_dir(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("mock_bzip2_write"))
-
-
-@pytest.fixture(scope="module")
-def lib(build_dir):
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_bzip2_write"), "OUT=" + build_dir])
-    lib = _lib_setup(C.CDLL(os.path.join(build_dir, "libla_host_bz2wmock.so")))    # (finds libla_gpu_bz2wmock.so beside itself)
+def lib():
+    lib = _lib_setup(mock_build.host_lib())
     lib.archive_write_add_filter_bzip2.argtypes = [C.c_void_p]
     return lib
 
@@ -118,10 +112,9 @@ def test_client_buffer_too_small(lib):
     assert rc == ARCHIVE_FATAL and err == "Buffer exhausted"
 
 
-def test_sanitizer_program(build_dir):
+def test_sanitizer_program():
     """host sources, mocks and a main of its own in one link under -fsanitize=address,undefined; nothing is preloaded"""
-    exe = os.path.join(build_dir, "bzip2_write_asan")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_bzip2_write"), "OUT=" + build_dir, exe])
+    exe = mock_build.program("bzip2_write_asan")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")     # (the environment is otherwise the caller's)
     r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

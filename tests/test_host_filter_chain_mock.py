@@ -1,22 +1,17 @@
 """CPU-only: the gzip read filter's chain mode (LA_GZIP_FLUSH_POINTS=chain) END TO END against tests/mock_gpu, whose
 LA_GZ_OPT_PIECES | LA_GZ_OPT_CHAIN answers come from zlib -- the test functions of tests/test_gpu_filter_chain.py, as
 tests/test_host_filters_mock.py runs those of the other filter tests."""
-import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import la_api
-
-MOCK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mock_gpu")
+import mock_build
 
 
 @pytest.fixture(scope="module")
 def gpu_ctx():
     """Same name as the GPU fixture on purpose: the imported tests ask for it."""
-    subprocess.check_call(["make", "-s", "-C", MOCK_DIR])
-    la_api.use_library(C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so")))
+    la_api.use_library(mock_build.host_lib())
     yield None
     la_api.use_library(None)
 

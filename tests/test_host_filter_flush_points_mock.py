@@ -2,22 +2,17 @@
 LA_GZ_OPT_PIECES answers come from zlib -- the test functions of tests/test_gpu_filter_flush_points.py, as
 tests/test_host_filters_mock.py runs those of the other filter tests.  (test_own_writer_single_member_over_several_windows
 stays with the device: the mock's gzip writer stores one member per chunk and cannot write a flush-pointed member.)"""
-import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import la_api
-
-MOCK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mock_gpu")
+import mock_build
 
 
 @pytest.fixture(scope="module")
 def gpu_ctx():
     """Same name as the GPU fixture on purpose: the imported tests ask for it."""
-    subprocess.check_call(["make", "-s", "-C", MOCK_DIR])
-    la_api.use_library(C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so")))
+    la_api.use_library(mock_build.host_lib())
     yield None
     la_api.use_library(None)
 

@@ -5,24 +5,18 @@ tests/test_gpu_filters.py, but linked against tests/mock_gpu (a CPU stand-in for
 C ABI built from the oracle; test infrastructure, never part of the product).  The very
 same test functions run on the GPU box against the real device library."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import la_api
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-MOCK_DIR = os.path.join(HERE, "mock_gpu")
+import mock_build
 
 
 @pytest.fixture(scope="module")
 def gpu_ctx():
     """Same name as the GPU fixture on purpose: the imported tests ask for it.  Here it
     builds the mock-linked host library and routes the API harness to it."""
-    subprocess.check_call(["make", "-s", "-C", MOCK_DIR])
-    lib = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
-    la_api.use_library(lib)
+    la_api.use_library(mock_build.host_lib())
     yield None
     la_api.use_library(None)
 
@@ -91,11 +85,10 @@ from test_gpu_zip import (  # noqa: E402,F401
 def test_write_filter_host_logic_on_the_mock(gpu_ctx, monkeypatch):
     """The write filters' host side (windows, options, frame hand-off, empty stream, client errors) against the
     mock device (which stores every block): what they write reads back through the read path."""
-    import ctypes as C
     import random
     import test_gpu_lz4_write as W
     import test_gpu_zstd_write as ZW
-    mock = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
+    mock = mock_build.host_lib()
     monkeypatch.setattr(W, "_lib", lambda: W._lib_setup(mock))
     monkeypatch.setenv("LA_GPU_WRITE_WINDOW_MIB", "1")
     rnd = random.Random(31)
@@ -188,11 +181,10 @@ def test_gzip_window_fuzz(gpu_ctx, monkeypatch):
             assert got == want, (t, how, rs, len(got[0]), len(want[0]), got[1:], want[1:])
 
 
-
 def test_dependent_frame_really_used_the_carried_history(gpu_ctx, monkeypatch):
     """The imported dependent-frame test passes trivially if the filter widened its window to hold
     the whole frame; the mock counts the blocks it decoded against a carried history."""
-    lib = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
+    lib = mock_build.host_lib()
     lib.la_gpu_mock_hist_blocks.restype = C.c_ulong
     before = lib.la_gpu_mock_hist_blocks()
     test_lz4_dependent_frame_across_windows(gpu_ctx, monkeypatch)

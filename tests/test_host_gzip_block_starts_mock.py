@@ -1,29 +1,24 @@
 """The gzip read filter's block-start mode (LA_GZIP_BLOCK_STARTS=1, la_filter_gzip.c) over a CPU stand-in for
-la_gpu_gzip_decode with LA_GZ_OPT_BLOCK_STARTS (tests/mock_gz_blocks: the kernels' rules header for the candidates, zlib
+la_gpu_gzip_decode with LA_GZ_OPT_BLOCK_STARTS (tests/mock_gpu/la_gpu_gz_blocks_mock.cpp: the kernels' rules header for the candidates, zlib
 walked with Z_BLOCK for the pieces).  la_api.cat through the mock library must equal the reference filter over zlib
 (oracle_lib.gzip_stream_decode) on bytes, return code and error string, at read sizes None, 1000 and 1, with the span of one
 device call held to 40 000 bytes so that a stream takes several windows, windows begin in mid-byte, the history is carried
 and spans that confirm nothing have to grow.  Without the switch the same streams go the way they went before."""
-import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import deflate_find_support as F
 import la_api
+import mock_build
 import oracle_lib as O
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ARCHIVE_FILTER_GZIP = 1
 STREAMS = sorted(F.filter_streams())
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_gz_blocks"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_gz_blocks"), "OUT=" + out])
-    lib = C.CDLL(os.path.join(out, "libla_host_gzblocks.so"))      # (finds libla_gpu_gzblocks.so beside itself)
+def mock():
+    lib = mock_build.host_lib()
     la_api.use_library(lib)
     yield lib
     la_api.use_library(None)

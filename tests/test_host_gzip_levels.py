@@ -12,10 +12,10 @@ import subprocess
 import pytest
 
 import la_api
+import mock_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-MOCK_DIR = os.path.join(HERE, "mock_gpu")
 ARCHIVE_OK, ARCHIVE_WARN, ARCHIVE_FAILED = 0, -20, -25
 
 
@@ -37,8 +37,7 @@ def test_batch_struct_layout_matches_ctypes(tmp_path):
 @pytest.fixture(scope="module")
 def mock_writer():
     import test_gpu_lz4_write as W
-    subprocess.check_call(["make", "-s", "-C", MOCK_DIR])
-    mock = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
+    mock = mock_build.host_lib()
     la_api.use_library(mock)
     saved = W._lib
     W._lib = lambda: W._lib_setup(mock)

@@ -2,27 +2,22 @@
 la_gzc_batch.framing (it writes a member per chunk whatever the field says), so nothing here writes data in that mode:
 the option table and the empty stream are what the host code decides alone.  The data path is
 tests/test_gpu_gzip_stream.py."""
-import ctypes as C
 import gzip
-import os
 import struct
-import subprocess
 import time
 
 import pytest
 
 import la_api
+import mock_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-MOCK_DIR = os.path.join(HERE, "mock_gpu")
 ARCHIVE_OK, ARCHIVE_FAILED = 0, -25
 
 
 @pytest.fixture(scope="module")
 def mock_writer():
     import test_gpu_lz4_write as W
-    subprocess.check_call(["make", "-s", "-C", MOCK_DIR])
-    mock = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
+    mock = mock_build.host_lib()
     la_api.use_library(mock)
     saved = W._lib
     W._lib = lambda: W._lib_setup(mock)

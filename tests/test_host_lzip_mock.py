@@ -1,26 +1,21 @@
 """The lzip read filter's HOST side (la_filter_lzip.c: the chain of members by their trailers, members decoded alone,
 windows, the carry of the unfinished member, the bytes held back in front of an error, lzip_tail's verdicts) over CPU
-stand-ins for la_gpu_lzip_scan / la_gpu_lzip_decode (tests/mock_lzip: the kernel's own rules headers, compiled for the
+stand-ins for la_gpu_lzip_scan / la_gpu_lzip_decode (tests/mock_gpu/la_gpu_lzip_mock.c: the kernel's own rules headers, compiled for the
 host).  la_api.cat through the mock library must equal the reference's read loop over liblzma
 (lzip_support.reference_read) on bytes, error string and filter code / name."""
-import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import la_api
+import mock_build
 import lzip_support as LS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 LZIP = (LS.ARCHIVE_FILTER_LZIP, "lzip")
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_lzip"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzip"), "OUT=" + out])
-    lib = C.CDLL(os.path.join(out, "libla_host_lzipmock.so"))      # (finds libla_gpu_lzipmock.so beside itself)
+def mock():
+    lib = mock_build.host_lib()
     la_api.use_library(lib)
     yield lib
     la_api.use_library(None)

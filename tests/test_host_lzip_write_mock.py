@@ -1,6 +1,6 @@
 """The lzip write filter's HOST side (host/la_write_lzip.c: options, windows of whole members, nothing kept between
 windows, the empty archive as one member of no data from the compress call) over the CPU stand-in for
-la_gpu_lzip_compress (tests/mock_lzip_write, which compiles the kernels' rules header).  Every image has to pass
+la_gpu_lzip_compress (tests/mock_gpu/la_gpu_lzip_comp_mock.c, which compiles the kernels' rules header).  Every image has to pass
 lzip_write_support.accept and comes back through the project's own lzip read filter over the decode stand-in, where
 archive_filter_code and archive_filter_name name it.  A stand-alone program writes the same shapes under the address
 and undefined-behaviour sanitizers."""
@@ -13,6 +13,7 @@ import pytest
 import la_api
 import lzip_support as LS
 import lzip_write_support as W
+import mock_build
 from test_gpu_lz4_write import _lib_setup
 
 ARCHIVE_OK, ARCHIVE_FAILED, ARCHIVE_FATAL = 0, -25, -30
@@ -20,14 +21,8 @@ WINDOW = 1 << 20        # LA_GPU_WRITE_WINDOW_MIB=1: sixteen members, or four la
 
 
 @pytest.fixture(scope="module")
-def build_dir(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("mock_lzip_write"))
-
-
-@pytest.fixture(scope="module")
-def lib(build_dir):
-    W.build_mock(build_dir)
-    lib = _lib_setup(C.CDLL(os.path.join(build_dir, "libla_host_lzwmock.so")))    # (finds libla_gpu_lzwmock.so beside itself)
+def lib():
+    lib = _lib_setup(mock_build.host_lib())
     lib.archive_write_add_filter_lzip.argtypes = [C.c_void_p]
     la_api.use_library(lib)
     yield lib
@@ -130,10 +125,9 @@ def test_client_buffer_too_small(lib):
     assert rc == ARCHIVE_FATAL and err == "Buffer exhausted"
 
 
-def test_sanitizer_program(build_dir):
+def test_sanitizer_program():
     """host sources, mocks and a main of its own in one link under -fsanitize=address,undefined; nothing is preloaded"""
-    exe = os.path.join(build_dir, "lzip_write_asan")
-    W.build_mock(build_dir, exe)
+    exe = mock_build.program("lzip_write_asan")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")     # (the environment is otherwise the caller's)
     r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

@@ -1,26 +1,21 @@
 """The lzop read filter's HOST side (la_filter_lzop.c: consume_header and consume_block_info restated, parts and junk,
 the stale checksum, windows, the carry of the unfinished block, the blocks handed out in front of an error) over a CPU
-stand-in for la_gpu_lzop_decode (tests/mock_lzop: the kernel's own rules header, compiled for the host).  la_api.cat
+stand-in for la_gpu_lzop_decode (tests/mock_gpu/la_gpu_lzop_mock.c: the kernel's own rules header, compiled for the host).  la_api.cat
 through the mock library must equal the reference's read loop over the Python decoder (lzop_support.reference_read) on
 bytes, return code, error string and filter code / name."""
-import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import la_api
+import mock_build
 import lzop_support as L
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 LZOP = (L.ARCHIVE_FILTER_LZOP, "lzop")
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_lzop"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzop"), "OUT=" + out])
-    lib = C.CDLL(os.path.join(out, "libla_host_lzopmock.so"))      # (finds libla_gpu_lzopmock.so beside itself)
+def mock():
+    lib = mock_build.host_lib()
     la_api.use_library(lib)
     yield lib
     la_api.use_library(None)

@@ -2,9 +2,9 @@
 the device ABI (tests/mock_gpu/la_gpu_mock.c) fails the k-th call of one kind when LA_MOCK_FAIL=<call>:<k> is set; for
 every filter and every kind of call, k runs from 1 until a read completes with no call failed.  A failed read has to end
 with ARCHIVE_FATAL and the data plane's own words for that call, hand out nothing but a prefix of the plain data, and
-leave the process able to read the same stream in full.  The same cases run in each filter's stand-alone ASan / UBSan
-program (tests/mock_*/..._read_main.c), where a leak or a double free in the cleanup would show: the sanitizer runtimes
-are linked into those programs statically, and nothing is loaded into Python."""
+leave the process able to read the same stream in full.  The same cases run in the stand-alone ASan / UBSan program of
+the readers (tests/mock_gpu/la_read_main.c), where a leak or a double free in the cleanup would show: the sanitizer runtimes
+are linked into that program statically, and nothing is loaded into Python."""
 import bz2
 import ctypes as C
 import os
@@ -15,12 +15,12 @@ import pytest
 
 import bzip2_support as BS
 import la_api
+import mock_build
 import lzip_support as LS
 import lzop_support as L
 import xz_build as XB
 import xz_support as XS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 CALLS = ("la_gpu_open", "la_gpu_malloc", "la_gpu_malloc_host", "la_gpu_memcpy_h2d", "la_gpu_memcpy_d2h")
 # the label la_window_fail is given for each call; a pinned allocation is the stage's (the gather) or the output's
 LABELS = {"la_gpu_malloc": ("la_gpu_malloc",), "la_gpu_malloc_host": ("la_gpu_malloc_host", "pinned staging allocation"),
@@ -49,23 +49,17 @@ def lzop_stream():
     return L.part(L.text(9, 9000), block_size=1)
 
 
-# filter name -> (mock directory, host library, sanitizer program, stream)
-FILTERS = {
-    "bzip2": ("mock_bzip2", "libla_host_bz2mock.so", "bzip2_read_asan", bzip2_stream),
-    "xz": ("mock_xz", "libla_host_xzmock.so", "xz_read_asan", xz_stream),
-    "lzip": ("mock_lzip", "libla_host_lzipmock.so", "lzip_read_asan", lzip_stream),
-    "lzop": ("mock_lzop", "libla_host_lzopmock.so", "lzop_read_asan", lzop_stream),
-}
+# filter name -> stream
+FILTERS = {"bzip2": bzip2_stream, "xz": xz_stream, "lzip": lzip_stream, "lzop": lzop_stream}
 
 
 @pytest.fixture(scope="module", params=sorted(FILTERS))
 def reader(request, tmp_path_factory):
-    """(filter name, build directory, stream, its plain bytes) with la_api routed to that filter's mock library"""
+    """(filter name, mock library, directory for files, stream, its plain bytes) with la_api routed to the mock library"""
     name = request.param
-    mock_dir, lib_name, _, stream = FILTERS[name]
+    stream = FILTERS[name]
     out = str(tmp_path_factory.mktemp("fail_" + name))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, mock_dir), "OUT=" + out])
-    lib = C.CDLL(os.path.join(out, lib_name))
+    lib = mock_build.host_lib()
     lib.la_gpu_mock_failed.restype = C.c_ulong
     la_api.use_library(lib)
     env = {"LA_GPU_BATCH_MIB": "1", "LA_GPU_BID": "all"}
@@ -120,18 +114,17 @@ def test_failing_calls_under_asan_ubsan(reader):
     """each call's first three failures in the filter's sanitizer program: exit status 0 (the three read sizes agree),
     nothing reported, no leak"""
     name, _, out, image, plain = reader
-    mock_dir, _, prog, _ = FILTERS[name]
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, mock_dir), "OUT=" + out, os.path.join(out, prog)])
+    prog = mock_build.program("la_read_asan")
     path = os.path.join(out, "stream." + name)
     with open(path, "wb") as f:
         f.write(image)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
     env.pop("LA_MOCK_FAIL", None)
-    run = subprocess.run([os.path.join(out, prog), path], env=env, capture_output=True, text=True, timeout=600)
+    run = subprocess.run([prog, path], env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0 and re.match(r"0 %d [0-9a-f]{16} $" % len(plain), run.stdout), run.stdout + run.stderr[-3000:]
     for call in CALLS:
         for k in (1, 2, 3):
-            run = subprocess.run([os.path.join(out, prog), path], env=dict(env, LA_MOCK_FAIL="%s:%d" % (call, k)),
+            run = subprocess.run([prog, path], env=dict(env, LA_MOCK_FAIL="%s:%d" % (call, k)),
                                  capture_output=True, text=True, timeout=600)
             assert run.returncode == 0, (call, k, (run.stdout + run.stderr)[-3000:])
             assert "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, (call, k, run.stderr[-3000:])

@@ -1,28 +1,25 @@
 """The xz read filter's host side with LA_XZ_CHAINS=1 (la_filter_xz.c: chains parsed and judged as liblzma judges them,
 the chain table carried to the device call) over a CPU stand-in for la_gpu_xz_decode that compiles both rules headers
-of the kernels (tests/mock_xz_chains).  la_api.cat through the mock library must equal the reference's read loop over
+of the kernels (tests/mock_gpu/la_gpu_xz_chains_mock.c).  la_api.cat through the mock library must equal the reference's read loop over
 liblzma (xz_support.reference_cat) on bytes, return code and error string.  Without the variable the same streams end
 in today's refusal.  The same shapes go through a stand-alone ASan/UBSan program of the same sources."""
-import ctypes as C
 import os
 import subprocess
 
 import pytest
 
 import la_api
+import mock_build
 import xz_build as XB
 import xz_chains_support as XC
 import xz_support as XS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ARCHIVE_FILTER_XZ = 6
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_xz_chains"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_xz_chains"), "OUT=" + out])
-    lib = C.CDLL(os.path.join(out, "libla_host_xzchains.so"))      # (finds libla_gpu_xzchains.so beside itself)
+def mock():
+    lib = mock_build.host_lib()
     la_api.use_library(lib)
     yield lib
     la_api.use_library(None)
@@ -118,7 +115,7 @@ def test_without_the_variable_chains_are_refused_as_before(mock, monkeypatch):
 def test_sanitizer_program(mock, tmp_path):
     """the C filter and the stand-in as one ASan/UBSan program of their own over the same streams"""
     out = str(tmp_path)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_xz_chains"), "OUT=" + out, os.path.join(out, "xz_chains_asan")])
+    exe = mock_build.program("la_read_asan")
     images = list(XC.good_streams().values()) + list(XC.bad_streams().values())
     img = XC.good_streams()["sized_and_bare"]
     images += [img[:cut] for cut in range(6, len(img), 211)]
@@ -129,7 +126,7 @@ def test_sanitizer_program(mock, tmp_path):
         paths.append(os.path.join(out, "case%04d.xz" % i))
         with open(paths[-1], "wb") as f:
             f.write(im)
-    run = subprocess.run([os.path.join(out, "xz_chains_asan")] + paths, capture_output=True, text=True, env=env, timeout=600)
+    run = subprocess.run([exe] + paths, capture_output=True, text=True, env=env, timeout=600)
     assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
     lines = run.stdout.splitlines()

@@ -1,9 +1,8 @@
 """The xz read filter's HOST side (la_filter_xz.c: the container walk, windows, the carry of the unfinished unit, blocks
 with and without sizes, the bytes held back in front of an error, verdicts and strings) over a CPU stand-in for
-la_gpu_xz_decode (tests/mock_xz: the kernel's own rules header, compiled for the host).  la_api.cat through the mock
+la_gpu_xz_decode (tests/mock_gpu/la_gpu_xz_chains_mock.c: the kernel's own rules header, compiled for the host).  la_api.cat through the mock
 library must equal the reference's read loop over liblzma (xz_support.reference_read) on bytes, return code, error
 string and filter code / name.  The same shapes go through a stand-alone ASan/UBSan program of the same sources."""
-import ctypes as C
 import lzma
 import os
 import subprocess
@@ -11,18 +10,16 @@ import subprocess
 import pytest
 
 import la_api
+import mock_build
 import xz_build as XB
 import xz_support as XS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ARCHIVE_FILTER_XZ = 6
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_xz"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_xz"), "OUT=" + out])
-    lib = C.CDLL(os.path.join(out, "libla_host_xzmock.so"))      # (finds libla_gpu_xzmock.so beside itself)
+def mock():
+    lib = mock_build.host_lib()
     la_api.use_library(lib)
     yield lib
     la_api.use_library(None)
@@ -170,7 +167,7 @@ def test_tar_walk_over_the_fixture(mock):
 def test_sanitizer_program(mock, tmp_path):
     """the C filter and the mock as one ASan/UBSan program of their own, over the shapes, the hand-built data, cuts and flips"""
     out = str(tmp_path)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_xz"), "OUT=" + out, os.path.join(out, "xz_read_asan")])
+    exe = mock_build.program("la_read_asan")
     images = list(XS.filter_shapes().values()) + [img for _, img in XS.fixtures()]
     images += [XS.wrap(raw, plain, XB.CHECK_CRC64) for raw, plain in list(XS.packet_cases().values()) + list(XS.chunk_plans().values())]
     images += [XS.wrap(raw) for raw, _ in XS.refusals().values()] + [XS.wrap(c[0], dict_byte=c[3]) for c in XS.beyond_cases().values()]
@@ -186,7 +183,7 @@ def test_sanitizer_program(mock, tmp_path):
             with open(paths[-1], "wb") as f:
                 f.write(im)
         for k in range(0, len(paths), 400):
-            run = subprocess.run([os.path.join(out, "xz_read_asan")] + paths[k:k + 400], capture_output=True, text=True, env=env, timeout=600)
+            run = subprocess.run([exe] + paths[k:k + 400], capture_output=True, text=True, env=env, timeout=600)
             assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
             assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
             lines = run.stdout.splitlines()

@@ -1,6 +1,6 @@
 """The xz write filter's HOST side (host/la_write_xz.c: options, windows of whole blocks, the stream header on the first
 window only, the index kept from the block headers that come back, index and footer at close(), the empty stream) over
-the CPU stand-in for la_gpu_xz_compress (tests/mock_xz_write, which compiles the kernels' rules header).  Every image has
+the CPU stand-in for la_gpu_xz_compress (tests/mock_gpu/la_gpu_xz_comp_mock.c, which compiles the kernels' rules header).  Every image has
 to pass xz_write_support.accept.  A stand-alone program writes the same shapes under the address and
 undefined-behaviour sanitizers."""
 import ctypes as C
@@ -10,23 +10,17 @@ import subprocess
 import pytest
 
 import xz_write_support as W
+import mock_build
 from test_gpu_lz4_write import _lib_setup
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ARCHIVE_OK, ARCHIVE_FAILED, ARCHIVE_FATAL = 0, -25, -30
 EMPTY = bytes.fromhex("fd377a585a000004e6d6b446" "000000001cdf4421" "1fb6f37d010000000004595a")
 WINDOW = 1 << 20        # LA_GPU_WRITE_WINDOW_MIB=1: one block
 
 
 @pytest.fixture(scope="module")
-def build_dir(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("mock_xz_write"))
-
-
-@pytest.fixture(scope="module")
-def lib(build_dir):
-    W.build_mock(build_dir)
-    lib = _lib_setup(C.CDLL(os.path.join(build_dir, "libla_host_xzwmock.so")))    # (finds libla_gpu_xzwmock.so beside itself)
+def lib():
+    lib = _lib_setup(mock_build.host_lib())
     lib.archive_write_add_filter_xz.argtypes = [C.c_void_p]
     return lib
 
@@ -106,10 +100,9 @@ def test_client_buffer_too_small(lib):
     assert rc == ARCHIVE_FATAL and err == "Buffer exhausted"
 
 
-def test_sanitizer_program(build_dir):
+def test_sanitizer_program():
     """host sources, mocks and a main of its own in one link under -fsanitize=address,undefined; nothing is preloaded"""
-    exe = os.path.join(build_dir, "xz_write_asan")
-    W.build_mock(build_dir, exe)
+    exe = mock_build.program("xz_write_asan")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")     # (the environment is otherwise the caller's)
     r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

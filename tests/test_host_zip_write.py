@@ -1,5 +1,5 @@
 """CPU-only: the ZIP write format (host/la_write_zip.c) and the format hooks of the write core, against a CPU stand-in
-for la_gpu_zip_compress (tests/mock_zip: zlib, one Z_SYNC_FLUSH per chunk, then 03 00).  Everything the host decides
+for la_gpu_zip_compress (tests/mock_gpu/la_gpu_zip_mock.c: zlib, one Z_SYNC_FLUSH per chunk, then 03 00).  Everything the host decides
 -- segments and gaps per window, headers and descriptors patched into the gaps, entries chained over windows, the
 central directory and the end records, the options, the failure paths -- is what is checked here, field by field
 against the lines of libarchive/archive_write_set_format_zip.c that la_write_zip.c restates.  The device's side of the
@@ -8,23 +8,18 @@ import ctypes as C
 import gzip
 import os
 import random
-import subprocess
 
 import pytest
 
 import la_api
+import mock_build
 import zip_write_support as Z
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_zip"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_zip"), "OUT=" + out])
-    mock = C.CDLL(os.path.join(out, "libla_host_zipmock.so"))
-    gpu = C.CDLL(os.path.join(out, "libla_gpu_zipmock.so"))
-    mock._gpu_mock = gpu
+def lib():
+    mock = mock_build.host_lib()
+    mock._gpu_mock = mock_build.gpu_lib()
     saved = os.environ.get("LA_GPU_WRITE_WINDOW_MIB")
     os.environ["LA_GPU_WRITE_WINDOW_MIB"] = "1"     # entries split across windows
     la_api.use_library(mock)

@@ -10,17 +10,16 @@ import subprocess
 import pytest
 
 import la_api
+import mock_build
 from test_gpu_bid_policy import ARCHIVE_FILTER_ZSTD, _codes, _zstd_raw_frame
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-MOCK_DIR = os.path.join(HERE, "mock_gpu")
 
 
 @pytest.fixture(scope="module")
 def mock():
-    subprocess.check_call(["make", "-s", "-C", MOCK_DIR])
-    lib = C.CDLL(os.path.join(MOCK_DIR, "libla_host_mock.so"))
+    lib = mock_build.host_lib()
     la_api.use_library(lib)
     yield lib
     la_api.use_library(None)

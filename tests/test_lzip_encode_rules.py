@@ -9,8 +9,8 @@ import lzip_write_support as W
 
 
 @pytest.fixture(scope="module")
-def stand_in(tmp_path_factory):
-    return W.StandIn(str(tmp_path_factory.mktemp("mock_lzip_write")))
+def stand_in():
+    return W.StandIn()
 
 
 @pytest.fixture(scope="module")

@@ -1,24 +1,19 @@
 """The lzip decode rules (libarchive_amd/csrc/la_lzip_dev.h over la_xz_dev.h's symbol loop, compiled for the host by
-tests/mock_lzip) against liblzma's raw LZMA1 decoder on hand-built streams: bytes, verdict and the bytes consumed
+tests/mock_gpu/la_gpu_lzip_mock.c) against liblzma's raw LZMA1 decoder on hand-built streams: bytes, verdict and the bytes consumed
 through the marker.  Then what the entry's tentative ends add: each has its own status."""
-import ctypes as C
-import os
-import subprocess
 import zlib
 
 import pytest
 
 import lzip_support as LS
+import mock_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 NAMES = {v: k for k, v in LS.ST.items()}
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_lzip"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzip"), "OUT=" + out, os.path.join(out, "libla_gpu_lzipmock.so")])
-    return C.CDLL(os.path.join(out, "libla_gpu_lzipmock.so"))
+def lib():
+    return mock_build.gpu_lib()
 
 
 def entry(raw, db, cap, src_end=LS.UNKNOWN, data_size=LS.UNKNOWN, crc=None, src_off=0, dst_off=0):

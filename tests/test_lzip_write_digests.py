@@ -1,4 +1,4 @@
-"""The CPU stand-in of tests/mock_lzip_write reproduces tests/golden/lzip_write_digests.json (recorded from it by
+"""The CPU stand-in of tests/mock_gpu/la_gpu_lzip_comp_mock.c reproduces tests/golden/lzip_write_digests.json (recorded from it by
 tools/record_lzip_write_digests.py); tests/test_gpu_lzip_compress.py holds the device to the same file, which pins kernel
 and stand-in to the same bytes."""
 import pytest
@@ -7,8 +7,8 @@ import lzip_write_support as W
 
 
 @pytest.fixture(scope="module")
-def stand_in(tmp_path_factory):
-    return W.StandIn(str(tmp_path_factory.mktemp("mock_lzip_write")))
+def stand_in():
+    return W.StandIn()
 
 
 def test_every_input_is_recorded():

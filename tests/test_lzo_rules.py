@@ -1,27 +1,21 @@
 """The LZO1X rules.  Two statements of them exist, both written from the format description and neither from liblzo2:
 lzop_support.decode() in Python and libarchive_amd/csrc/la_lzo_dev.h, which the kernel and the CPU stand-in
-(tests/mock_lzop) compile.  What pins the Python one is independent of both: every block of the reference's seven lzop
+(tests/mock_gpu/la_gpu_lzop_mock.c) compile.  What pins the Python one is independent of both: every block of the reference's seven lzop
 fixtures carries the Adler-32 of its decoded bytes.  The header then has to equal the Python decoder in bytes and
 verdict on every instruction form, every length-run edge, the distances at which a form or a copy path changes, and the
 four pinned verdicts; the expected bytes of the hand-built streams come from the emitter's own book-keeping."""
-import ctypes as C
 import hashlib
-import os
-import subprocess
 import zlib
 
 import pytest
 
 import lzop_support as L
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+import mock_build
 
 
 @pytest.fixture(scope="module")
-def mock(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mock_lzop"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzop"), "OUT=" + out])
-    return C.CDLL(os.path.join(out, "libla_gpu_lzopmock.so"))
+def mock():
+    return mock_build.gpu_lib()
 
 
 def header_decode(mock, streams):

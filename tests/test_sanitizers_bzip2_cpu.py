@@ -1,4 +1,4 @@
-"""ASan + UBSan over the bzip2 read path on the CPU: tests/mock_bzip2/bzip2_read_main.c is a program of its own that
+"""ASan + UBSan over the bzip2 read path on the CPU: tests/mock_gpu/la_read_main.c is a program of its own that
 links the host sources (read core, la_filter_bzip2.c), the CPU mock of the device ABI and the libbz2 stand-in for
 la_gpu_bzip2_scan / la_gpu_bzip2_decode, all compiled with -fsanitize=address,undefined.  It reads valid, concatenated,
 cut and damaged streams, each in one piece, 1000 bytes and 1 byte at a time, and has to exit 0 with nothing reported
@@ -9,8 +9,7 @@ import random
 import subprocess
 
 import bzip2_support as BS
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+import mock_build
 
 
 def fnv1a(data):
@@ -22,7 +21,7 @@ def fnv1a(data):
 
 def test_bzip2_reader_under_asan_ubsan(tmp_path):
     out = str(tmp_path)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_bzip2"), "OUT=" + out, os.path.join(out, "bzip2_read_asan")])
+    exe = mock_build.program("la_read_asan")
     big, small = BS.stream350k(), BS.stream3000()
     r = random.Random(77)
     images = list(BS.filter_shapes().values()) + [img for _, img in BS.fixtures()]
@@ -35,7 +34,7 @@ def test_bzip2_reader_under_asan_ubsan(tmp_path):
         with open(paths[-1], "wb") as f:
             f.write(img)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")     # (the environment is otherwise the caller's)
-    run = subprocess.run([os.path.join(out, "bzip2_read_asan")] + paths, env=env, capture_output=True, text=True, timeout=600)
+    run = subprocess.run([exe] + paths, env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
     lines = run.stdout.splitlines()

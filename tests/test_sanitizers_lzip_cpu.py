@@ -1,4 +1,4 @@
-"""ASan + UBSan over the lzip read path on the CPU: tests/mock_lzip/lzip_read_main.c is a program of its own that links
+"""ASan + UBSan over the lzip read path on the CPU: tests/mock_gpu/la_read_main.c is a program of its own that links
 the host sources (read core, la_filter_lzip.c, la_bid_policy.c), the CPU mock of the device ABI and the stand-ins for
 la_gpu_lzip_scan / la_gpu_lzip_decode (the kernel's rules headers), all compiled with -fsanitize=address,undefined.  It
 reads valid, multi-member, cut and damaged streams, each in one piece, 1000 bytes and 1 byte at a time, and has to exit
@@ -8,8 +8,8 @@ import os
 import subprocess
 
 import lzip_support as LS
+import mock_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 # (read 1 byte at a time the reference meets these errors in a call of its own: la_filter_lzip.c's head comment)
 WHOLE_READS_ONLY = {"bad_crc_at_64k", "bad_crc_at_128k"}
 
@@ -23,7 +23,7 @@ def fnv1a(data):
 
 def test_lzip_reader_under_asan_ubsan(tmp_path):
     out = str(tmp_path)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzip"), "OUT=" + out, os.path.join(out, "lzip_read_asan")])
+    exe = mock_build.program("la_read_asan")
     images = [img for name, img in sorted(LS.filter_shapes().items()) if name not in WHOLE_READS_ONLY and len(img) < 1 << 17]
     images += [img for _, img in LS.fixtures()]
     two = LS.member(LS.text(1, 5000)) + LS.member(LS.noise(2, 700, 16))
@@ -37,7 +37,7 @@ def test_lzip_reader_under_asan_ubsan(tmp_path):
     env = dict(os.environ, LA_GPU_BID="all", ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")     # (the environment is otherwise the caller's)
     for k in range(0, len(paths), 400):
-        run = subprocess.run([os.path.join(out, "lzip_read_asan")] + paths[k:k + 400], env=env, capture_output=True, text=True, timeout=600)
+        run = subprocess.run([exe] + paths[k:k + 400], env=env, capture_output=True, text=True, timeout=600)
         assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
         assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
         lines = run.stdout.splitlines()
@@ -46,6 +46,6 @@ def test_lzip_reader_under_asan_ubsan(tmp_path):
             data, rc, msg = LS.reference_cat(img)
             assert line == ("%d %d %016x %s" % (rc, len(data), fnv1a(data), msg)), (line, len(img))
     # the bid policy's look-ahead walk under the sanitizers too: a look-ahead of 4 KiB over streams longer than that
-    run = subprocess.run([os.path.join(out, "lzip_read_asan")] + paths[:40], env=dict(env, LA_GPU_BID="auto", LA_GPU_BID_LOOKAHEAD_KIB="4"),
+    run = subprocess.run([exe] + paths[:40], env=dict(env, LA_GPU_BID="auto", LA_GPU_BID_LOOKAHEAD_KIB="4"),
                          capture_output=True, text=True, timeout=600)
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]

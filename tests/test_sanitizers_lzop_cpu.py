@@ -1,4 +1,4 @@
-"""ASan + UBSan over the lzop read path on the CPU: tests/mock_lzop/lzop_read_main.c is a program of its own that links
+"""ASan + UBSan over the lzop read path on the CPU: tests/mock_gpu/la_read_main.c is a program of its own that links
 the host sources (read core, la_filter_lzop.c, la_bid_policy.c), the CPU mock of the device ABI and the stand-in for
 la_gpu_lzop_decode (the kernel's rules header), all compiled with -fsanitize=address,undefined.  It reads valid,
 multi-part, cut and damaged streams, each in one piece, 1000 bytes and 1 byte at a time, and has to exit 0 with nothing
@@ -8,8 +8,7 @@ import os
 import subprocess
 
 import lzop_support as L
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+import mock_build
 
 
 def fnv1a(data):
@@ -21,7 +20,7 @@ def fnv1a(data):
 
 def test_lzop_reader_under_asan_ubsan(tmp_path):
     out = str(tmp_path)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_lzop"), "OUT=" + out, os.path.join(out, "lzop_read_asan")])
+    exe = mock_build.program("la_read_asan")
     images = [img for _, img in sorted(L.filter_shapes().items())]
     images += [img for _, img in L.fixtures()]
     two = L.part(L.text(1, 3000), block_size=1200, flags=L.AU | L.AC, name=b"a name") + L.part(L.noise(2, 300, 16), flags=L.CC | L.EXTRA_FIELD)
@@ -38,7 +37,7 @@ def test_lzop_reader_under_asan_ubsan(tmp_path):
     env = dict(os.environ, LA_GPU_BID="all", ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")     # (the environment is otherwise the caller's)
     for k in range(0, len(paths), 400):
-        run = subprocess.run([os.path.join(out, "lzop_read_asan")] + paths[k:k + 400], env=env, capture_output=True, text=True, timeout=600)
+        run = subprocess.run([exe] + paths[k:k + 400], env=env, capture_output=True, text=True, timeout=600)
         assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
         assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
         lines = run.stdout.splitlines()
@@ -47,6 +46,6 @@ def test_lzop_reader_under_asan_ubsan(tmp_path):
             data, rc, msg = L.reference_cat(img)
             assert line == ("%d %d %016x %s" % (rc, len(data), fnv1a(data), msg)), (line, len(img))
     # the bid policy's header walk under the sanitizers too: a look-ahead of 4 KiB over streams longer than that
-    run = subprocess.run([os.path.join(out, "lzop_read_asan")] + paths[:60], env=dict(env, LA_GPU_BID="auto", LA_GPU_BID_LOOKAHEAD_KIB="4"),
+    run = subprocess.run([exe] + paths[:60], env=dict(env, LA_GPU_BID="auto", LA_GPU_BID_LOOKAHEAD_KIB="4"),
                          capture_output=True, text=True, timeout=600)
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]

@@ -11,8 +11,8 @@ import xz_write_support as W
 
 
 @pytest.fixture(scope="module")
-def stand_in(tmp_path_factory):
-    return W.StandIn(str(tmp_path_factory.mktemp("mock_xz_write")))
+def stand_in():
+    return W.StandIn()
 
 
 def small_inputs():

@@ -1,29 +1,25 @@
 """The inverse delta / BCJ transforms of libarchive_amd/csrc/la_xz_filters_dev.h, compiled for the host
-(tests/mock_xz_chains/xz_rules_shim.c), against liblzma's raw decoder.  For a buffer X and a filter F, liblzma's verdict
+(tests/mock_gpu/xz_rules_shim.c), against liblzma's raw decoder.  For a buffer X and a filter F, liblzma's verdict
 is lzma.decompress(LZMA2(X), FORMAT_RAW, [F, LZMA2]): the F decoder run over X, whatever X holds.  Both the header's
 serial routine and the kernels' parallel formulation (tiles and row groups for delta, segment cutting for x86, a map
 for the others; the independent pieces in descending order) must give those bytes."""
 import ctypes as C
 import lzma
-import os
 import random
-import subprocess
 
 import pytest
 
+import mock_build
 import xz_chains_support as XC
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 LZMA2, spec = XC.LZMA2, XC.spec
 DELTA, X86, POWERPC, IA64, ARM, ARMTHUMB, SPARC = XC.DELTA, XC.X86, XC.POWERPC, XC.IA64, XC.ARM, XC.ARMTHUMB, XC.SPARC
 TILE, SUB = XC.TILE, XC.SUB
 
 
 @pytest.fixture(scope="module")
-def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("xz_rules"))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_xz_chains"), "OUT=" + out, os.path.join(out, "libxz_rules.so")])
-    lib = C.CDLL(os.path.join(out, "libxz_rules.so"))
+def rules():
+    lib = C.CDLL(mock_build.rules("libxz_rules.so"))
     lib.rules_serial.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64]
     lib.rules_serial.restype = None
     lib.rules_parallel.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]

@@ -1,4 +1,4 @@
-"""The CPU stand-in of tests/mock_xz_write reproduces tests/golden/xz_write_digests.json (recorded from it by
+"""The CPU stand-in of tests/mock_gpu/la_gpu_xz_comp_mock.c reproduces tests/golden/xz_write_digests.json (recorded from it by
 tools/record_xz_write_digests.py); tests/test_gpu_xz_compress.py holds the device to the same file, which pins kernel
 and stand-in to the same bytes.  Every recorded image also passes the checks of a written stream."""
 import pytest
@@ -8,8 +8,8 @@ import xz_write_support as W
 
 
 @pytest.fixture(scope="module")
-def stand_in(tmp_path_factory):
-    return W.StandIn(str(tmp_path_factory.mktemp("mock_xz_write")))
+def stand_in():
+    return W.StandIn()
 
 
 def test_every_input_is_recorded():

@@ -1,6 +1,6 @@
 """Support for the xz write tests: the named inputs of the device tests (shared with the recorded digests of
 tests/golden/xz_write_digests.json), the checks every written image has to pass, and the CPU stand-in of
-tests/mock_xz_write, which compiles the kernels' own rules header and therefore writes the device's bytes."""
+tests/mock_gpu/la_gpu_xz_comp_mock.c, which compiles the kernels' own rules header and therefore writes the device's bytes."""
 import ctypes as C
 import functools
 import hashlib
@@ -8,8 +8,8 @@ import json
 import lzma
 import os
 import random
-import subprocess
 
+import mock_build
 import xz_parse as XP
 import xz_support as XS
 
@@ -139,16 +139,11 @@ class _Batch(C.Structure):      # la_xzc_batch
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
 
 
-def build_mock(out_dir, target=None):
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "mock_xz_write"), "OUT=" + out_dir] + ([target] if target else []))
-
-
 class StandIn:
-    """la_gpu_xz_compress of tests/mock_xz_write through its ABI entry ("device" pointers are host pointers)"""
+    """la_gpu_xz_compress of tests/mock_gpu through its ABI entry ("device" pointers are host pointers)"""
 
-    def __init__(self, out_dir):
-        build_mock(out_dir)
-        lib = C.CDLL(os.path.join(out_dir, "libla_gpu_xzwmock.so"))
+    def __init__(self):
+        lib = mock_build.gpu_lib()
         lib.la_gpu_xz_compress.argtypes = [C.c_void_p, C.POINTER(_Batch)]
         lib.la_gpu_xz_compress_bound.restype = C.c_uint64
         lib.la_gpu_xz_compress_bound.argtypes = [C.c_uint64, C.c_uint32]

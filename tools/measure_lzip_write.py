@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """lzip write side.  Two parts:
 
-  --sizes     no GPU: the CPU stand-in of tests/mock_lzip_write (the kernels' rules header, so the device's bytes) over the
+  --sizes     no GPU: the CPU stand-in of tests/mock_gpu (the kernels' rules header, so the device's bytes) over the
               first `baseline-mib` MiB of each input at levels 6 and 9, against liblzma's raw LZMA1 (preset 0 and 6, one
               stream with the end marker) and against the same coded per 64 KiB piece; the expansion on noise.
   (default)   on the device: la_gpu_lzip_compress on a window resident in HBM at levels 6 and 9 (median of three calls
@@ -15,7 +15,6 @@ import argparse
 import lzma
 import os
 import sys
-import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,23 +34,22 @@ def raw_lzma1(data, preset, piece=None):
 
 def sizes(args, say):
     import lzip_write_support as W
-    with tempfile.TemporaryDirectory() as d:
-        s = W.StandIn(d)
-        for name, gen in (("text", text_like), ("noise", noise), ("c2_like", c2_like)):
-            sample = gen(args.baseline_mib)
-            n = len(sample)
-            ours = {lv: len(s.compress(sample, lv)) for lv in (6, 9)}
-            members = {lv: -(-n // W.member_bytes(lv)) for lv in (6, 9)}
-            say("%s, %d MiB: level 6 %d bytes (ratio %.3f), level 9 %d bytes (ratio %.3f): the 256 KiB member is %.4f of the 64 KiB one"
-                % (name, args.baseline_mib, ours[6], n / ours[6], ours[9], n / ours[9], ours[9] / ours[6]))
-            for preset in (0, 6):
-                one, per64, per256 = raw_lzma1(sample, preset), raw_lzma1(sample, preset, 1 << 16), raw_lzma1(sample, preset, 1 << 18)
-                say("  liblzma raw LZMA1 preset %d: one stream %d bytes, per 64 KiB %d, per 256 KiB %d; streams alone (framing of 26 bytes taken off): "
-                    "level 6 is %.3f of per-64-KiB, level 9 %.3f of per-256-KiB, %.3f and %.3f of one stream"
-                    % (preset, one, per64, per256, (ours[6] - 26 * members[6]) / per64, (ours[9] - 26 * members[9]) / per256,
-                       (ours[6] - 26 * members[6]) / one, (ours[9] - 26 * members[9]) / one))
-            if name == "noise":
-                say("  expansion on noise: level 6 %.4f, level 9 %.4f of the input (the bound is 7.00)" % (ours[6] / n, ours[9] / n))
+    s = W.StandIn()
+    for name, gen in (("text", text_like), ("noise", noise), ("c2_like", c2_like)):
+        sample = gen(args.baseline_mib)
+        n = len(sample)
+        ours = {lv: len(s.compress(sample, lv)) for lv in (6, 9)}
+        members = {lv: -(-n // W.member_bytes(lv)) for lv in (6, 9)}
+        say("%s, %d MiB: level 6 %d bytes (ratio %.3f), level 9 %d bytes (ratio %.3f): the 256 KiB member is %.4f of the 64 KiB one"
+            % (name, args.baseline_mib, ours[6], n / ours[6], ours[9], n / ours[9], ours[9] / ours[6]))
+        for preset in (0, 6):
+            one, per64, per256 = raw_lzma1(sample, preset), raw_lzma1(sample, preset, 1 << 16), raw_lzma1(sample, preset, 1 << 18)
+            say("  liblzma raw LZMA1 preset %d: one stream %d bytes, per 64 KiB %d, per 256 KiB %d; streams alone (framing of 26 bytes taken off): "
+                "level 6 is %.3f of per-64-KiB, level 9 %.3f of per-256-KiB, %.3f and %.3f of one stream"
+                % (preset, one, per64, per256, (ours[6] - 26 * members[6]) / per64, (ours[9] - 26 * members[9]) / per256,
+                   (ours[6] - 26 * members[6]) / one, (ours[9] - 26 * members[9]) / one))
+        if name == "noise":
+            say("  expansion on noise: level 6 %.4f, level 9 %.4f of the input (the bound is 7.00)" % (ours[6] / n, ours[9] / n))
 
 
 def device(args, say):

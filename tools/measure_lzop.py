@@ -36,9 +36,8 @@ def inputs(mib):
 
 def host_baseline(tmp, blocks, reps):
     """(bytes, seconds) of the rules header on one host core: best of `reps` passes over the unit's blocks"""
-    exe = os.path.join(tmp, "lzo_rules_bench")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "mock_lzop"), "OUT=" + tmp, exe])
+    import mock_build
+    exe = mock_build.program("lzo_rules_bench")
     path = os.path.join(tmp, "blocks.bin")
     with open(path, "wb") as f:
         f.write(struct.pack("<I", len(blocks)))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Records tests/golden/xz_write_digests.json: size and SHA-256 of what la_gpu_xz_compress (LA_XZC_FIRST) writes for every
 named input of tests/xz_write_support.inputs() at levels 0 and 6.  The bytes come from the CPU stand-in of
-tests/mock_xz_write, which compiles libarchive_amd/csrc/la_xz_enc_dev.h as the kernels do; no GPU is needed.
+tests/mock_gpu/la_gpu_xz_comp_mock.c, which compiles libarchive_amd/csrc/la_xz_enc_dev.h as the kernels do; no GPU is needed.
 tests/test_xz_write_digests.py holds the stand-in to the file, tests/test_gpu_xz_compress.py the device.
 
     python3 tools/record_xz_write_digests.py
@@ -9,7 +9,6 @@ tests/test_xz_write_digests.py holds the stand-in to the file, tests/test_gpu_xz
 import json
 import os
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -17,9 +16,8 @@ import xz_write_support as W     # noqa: E402
 
 
 def main():
-    with tempfile.TemporaryDirectory() as d:
-        s = W.StandIn(d)
-        out = {"%s/%d" % (name, level): W.digest(s.compress(data, level)) for name, data in sorted(W.inputs().items()) for level in (0, 6)}
+    s = W.StandIn()
+    out = {"%s/%d" % (name, level): W.digest(s.compress(data, level)) for name, data in sorted(W.inputs().items()) for level in (0, 6)}
     with open(W.GOLDEN, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
