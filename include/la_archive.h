@@ -92,6 +92,7 @@ int  archive_write_add_filter_zstd(struct archive *);				/* archive.h:837; archi
 int  archive_write_add_filter_bzip2(struct archive *);				/* archive.h:813; archive_write_add_filter_bzip2.c:79 (host/la_write_bzip2.c): one stream, blocks sorted and coded on the device */
 int  archive_write_add_filter_xz(struct archive *);				/* archive.h:836; archive_write_add_filter_xz.c:238 (host/la_write_xz.c): one stream of 1 MiB blocks, LZMA2 chunks coded on the device */
 int  archive_write_add_filter_lzip(struct archive *);				/* archive.h:829; archive_write_add_filter_xz.c:202 (host/la_write_lzip.c): members of 64 KiB (levels 7..9: 256 KiB) coded on the device, back to back */
+int  archive_write_add_filter_lzop(struct archive *);				/* archive.h:831; archive_write_add_filter_lzop.c:136 (host/la_write_lzop.c): one part, LZO1X blocks of 64 KiB coded on the device */
 int  archive_write_set_format_raw(struct archive *);				/* one entry, data passed through */
 int  archive_write_set_format_zip(struct archive *);				/* archive.h:867; archive_write_set_format_zip.c:720 (host/la_write_zip.c): deflate + CRC32 of a window of entries per device call */
 int  archive_write_set_format_option(struct archive *, const char *m, const char *o, const char *v);	/* archive.h:927; "zip", "compression", "store" ... */

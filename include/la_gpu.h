@@ -1016,6 +1016,32 @@ uint64_t la_gpu_lzip_compress_workspace_bytes(uint64_t src_bytes, uint32_t level
 uint64_t la_gpu_lzip_compress_bound(uint64_t src_bytes, uint32_t level);	/* 0 for a level above 9 */
 int      la_gpu_lzip_compress(la_gpu_ctx *ctx, const la_lzc_batch *batch);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * lzop compression -- replaces, for a window per call, what drive_compressor of
+ * libarchive/archive_write_add_filter_lzop.c:314-386 does per block (liblzo2's lzo1x_1_compress is the reference's external
+ * dependency for this codec).  d_src[0, src_bytes) is cut every block_size bytes; every cut is one complete lzop BLOCK:
+ * BE32 uncompressed size, BE32 compressed size, BE32 Adler-32 of the uncompressed bytes, then one LZO1X stream -- or the
+ * input itself, with both sizes equal, where the stream is not shorter than the block (:364-381).  The output is
+ * d_out[0, lead_bytes), left untouched for the caller (the filter writes the part's header there), then the blocks back to
+ * back.  No header and no closing size word are written: those are the host's.  src_bytes == 0 writes nothing behind the gap.
+ * The block is the parallel unit; csrc/la_lzo_enc_dev.h states how its sequences become bytes.  There is one coder: the
+ * method and level bytes of a part's header do not reach this call.  The bytes are not liblzo2's; every conforming reader
+ * returns the input.  *d_out_bytes is the size needed, the gap counted; nothing is written at or behind out_cap.
+ * block_size is 1 .. LA_LZOPC_BLOCK_BYTES, anything else is LA_ERR_ARG.  Additions under ABI version 3. */
+#define LA_LZOPC_BLOCK_BYTES 65536u
+typedef struct la_lzopc_batch {
+	const uint8_t *d_src;
+	uint64_t       src_bytes;
+	uint32_t       block_size;	/* 1 .. 65536; the filter passes LA_LZOPC_BLOCK_BYTES */
+	uint32_t       lead_bytes;	/* d_out[0, lead_bytes) is left untouched for the caller (the header); counted in *d_out_bytes */
+	uint8_t       *d_out;
+	uint64_t       out_cap;
+	uint64_t      *d_out_bytes;
+} la_lzopc_batch;
+uint64_t la_gpu_lzop_compress_workspace_bytes(uint64_t src_bytes, uint32_t block_size);	/* 0 for a bad block_size */
+uint64_t la_gpu_lzop_compress_bound(uint64_t src_bytes, uint32_t block_size);	/* src_bytes + 12 per block; 0 for block_size 0 */
+int      la_gpu_lzop_compress(la_gpu_ctx *ctx, const la_lzopc_batch *batch);
+
 #ifdef __cplusplus
 }
 #endif

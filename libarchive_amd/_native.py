@@ -174,6 +174,14 @@ class _LzcBatchC(C.Structure):      # la_lzc_batch
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
 
 
+LA_LZOPC_BLOCK_BYTES = 65536
+
+
+class _LzopcBatchC(C.Structure):    # la_lzopc_batch
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("block_size", C.c_uint32), ("lead_bytes", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
+
+
 class _Bz2StateC(C.Structure):
     _fields_ = [("open", C.c_uint32), ("level", C.c_uint32), ("crc", C.c_uint32), ("stop", C.c_uint32),
                 ("start_bit", C.c_uint64), ("total_out", C.c_uint64), ("n_taken", C.c_uint32), ("stop_entry", C.c_uint32),
@@ -331,6 +339,11 @@ def gpu_lib():
         lib.la_gpu_lzop_decode.argtypes = [C.c_void_p, C.POINTER(_LzopBatchC)]
         lib.la_gpu_lzop_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_lzop_workspace_bytes.argtypes = [C.c_uint32]
+        lib.la_gpu_lzop_compress.argtypes = [C.c_void_p, C.POINTER(_LzopcBatchC)]
+        lib.la_gpu_lzop_compress_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_lzop_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        lib.la_gpu_lzop_compress_bound.restype = C.c_uint64
+        lib.la_gpu_lzop_compress_bound.argtypes = [C.c_uint64, C.c_uint32]
         lib.la_gpu_xz_compress_block_bytes.restype = C.c_uint64
         lib.la_gpu_xz_compress_block_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_xz_compress_workspace_bytes.restype = C.c_uint64
@@ -605,6 +618,9 @@ class GpuContext:
 
     def lzop_decode(self, batch: _LzopBatchC):
         self._check(gpu_lib().la_gpu_lzop_decode(self._h, C.byref(batch)), "la_gpu_lzop_decode")
+
+    def lzop_compress(self, batch: _LzopcBatchC):
+        self._check(gpu_lib().la_gpu_lzop_compress(self._h, C.byref(batch)), "la_gpu_lzop_compress")
 
     def lzip_compress(self, batch: _LzcBatchC):
         self._check(gpu_lib().la_gpu_lzip_compress(self._h, C.byref(batch)), "la_gpu_lzip_compress")

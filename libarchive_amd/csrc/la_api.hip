@@ -1180,4 +1180,27 @@ int la_gpu_lzip_compress(la_gpu_ctx *c, const la_lzc_batch *bt)
 	});
 }
 
+static bool lzopc_block_size_ok(uint64_t src_bytes, uint32_t block_size)
+{
+	return block_size >= 1u && block_size <= LA_LZOPC_BLOCK_BYTES && (src_bytes + block_size - 1) / block_size <= 0x7FFFFFFEull;
+}
+uint64_t la_gpu_lzop_compress_workspace_bytes(uint64_t src_bytes, uint32_t block_size)
+{
+	return lzopc_block_size_ok(src_bytes, block_size) ? la_lzop_compress_ws_bytes(src_bytes, block_size) : 0u;
+}
+uint64_t la_gpu_lzop_compress_bound(uint64_t src_bytes, uint32_t block_size)
+{
+	return block_size ? src_bytes + 12u * ((src_bytes + block_size - 1) / block_size) : 0u;
+}
+int la_gpu_lzop_compress(la_gpu_ctx *c, const la_lzopc_batch *bt)
+{
+	if (!c || !bt || !bt->d_out_bytes || (bt->src_bytes && !bt->d_src) || (bt->out_cap && !bt->d_out))
+		return LA_ERR_ARG;
+	if (!lzopc_block_size_ok(bt->src_bytes, bt->block_size))
+		return LA_ERR_ARG;
+	return compress_run(c, la_lzop_compress_ws_bytes(bt->src_bytes, bt->block_size), "lzop_compress", [&](uint8_t *ws) {
+		la_launch_lzop_compress(c->stream, bt, ws);
+	});
+}
+
 } /* extern "C" */

@@ -1,6 +1,6 @@
 /*
- * la_comp_common.h -- device code the three compressors share (la_lz4_comp.hip, la_deflate_comp.hip,
- * la_zstd_comp.hip): small load / copy / store helpers, wave reductions, the LZ77 window matcher of the lz4 and zstd block kernels,
+ * la_comp_common.h -- device code the compressors share (la_lz4_comp.hip, la_deflate_comp.hip, la_zstd_comp.hip,
+ * la_lzo_comp.hip): small load / copy / store helpers, wave reductions, the LZ77 window matcher of the lz4, zstd and lzop block kernels,
  * the wave bit-stream appender of the deflate and Huffman encoders and the per-frame checksum kernel.  (The launchers'
  * workspace carver, la_carve, comes with la_dev.h.)
  */
@@ -52,11 +52,12 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v)
  * candidate and extends the match eight bytes at a time, then byte by byte.  The wave then takes the matches in
  * position order (ballot + first set bit), skipping the ones an earlier match has covered, and calls
  * emit(pf, mf, cf, anchor) for each: match position, length, candidate position and the first position not yet
- * emitted.  Matches start at or before `plast` and end at or before `mend`.  `tab` holds 2^LZ77_HASH_BITS positions
- * (T: uint16_t or uint32_t), zeroed.  Returns the first position no match covers. */
+ * emitted.  Matches start at or before `plast` and end at or before `mend`; a candidate further back than `max_dist`
+ * (the format's longest distance, where a block is longer than that) is not taken.  `tab` holds 2^LZ77_HASH_BITS
+ * positions (T: uint16_t or uint32_t), zeroed.  Returns the first position no match covers. */
 template <typename T, typename Emit>
 __device__ __forceinline__ uint32_t lz77_match(T *tab, const uint8_t *in, uint32_t plast, uint32_t mend, uint32_t lane,
-    Emit emit)
+    Emit emit, uint32_t max_dist = 0xFFFFFFFFu)
 {
 	uint32_t anchor = 0, base = 0;	/* wave-uniform */
 	while (base <= plast) {
@@ -74,7 +75,7 @@ __device__ __forceinline__ uint32_t lz77_match(T *tab, const uint8_t *in, uint32
 			const uint32_t h = (v * 2654435761u) >> (32 - LZ77_HASH_BITS);
 			tab[h] = (T)p;
 			/* (position 0 doubles as "empty": a candidate is only taken if its bytes match) */
-			ok = cand < p && ld_u32(in + cand) == v;
+			ok = cand < p && p - cand <= max_dist && ld_u32(in + cand) == v;
 			if (ok) {
 				mlen = 4;
 				while (p + mlen + 8u <= mend && ld_u64(in + p + mlen) == ld_u64(in + cand + mlen))

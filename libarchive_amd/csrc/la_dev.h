@@ -665,6 +665,10 @@ uint64_t la_lzip_compress_ws_bytes(uint64_t src_bytes, uint32_t level);
 uint64_t la_lzip_compress_bound(uint64_t src_bytes, uint32_t level);
 void la_launch_lzip_compress(hipStream_t s, const la_lzc_batch *bt, uint8_t *ws, const la_stage_hook *hook);
 
+/* la_lzo_comp.hip */
+uint64_t la_lzop_compress_ws_bytes(uint64_t src_bytes, uint32_t block_size);
+void la_launch_lzop_compress(hipStream_t s, const la_lzopc_batch *bt, uint8_t *ws);
+
 /* la_lz4_comp.hip */
 void la_launch_lz4_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_bytes, uint32_t block_size,
     uint32_t bpf, uint32_t flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_bytes, uint8_t *ws);

@@ -1,6 +1,7 @@
-"""Device-resident lzop block decode and many-range Adler-32 through the C ABI (harness for tests / tools).  Plumbing
-only: torch allocates the HBM buffers; the block table is the caller's (the host hops from block header to block header,
-host/la_filter_lzop.c), all work is la_gpu_lzop_decode() and la_gpu_adler32_many()."""
+"""Device-resident lzop block decode, block compression and many-range Adler-32 through the C ABI (harness for tests /
+tools).  Plumbing only: torch allocates the HBM buffers; the block table is the caller's (the host hops from block header
+to block header, host/la_filter_lzop.c), all work is la_gpu_lzop_decode(), la_gpu_lzop_compress() and
+la_gpu_adler32_many()."""
 import numpy as np
 
 from . import _native as N
@@ -10,6 +11,39 @@ C_ADLER32, C_CRC32, U_ADLER32, U_CRC32 = N.LA_LZOP_C_ADLER32, N.LA_LZOP_C_CRC32,
 STATUS = {0: "OK", N.LA_ST_LZOP_BAD_SUM_C: "BAD_SUM_C", N.LA_ST_LZOP_INPUT_OVERRUN: "INPUT_OVERRUN", N.LA_ST_LZOP_OUTPUT_OVERRUN: "OUTPUT_OVERRUN",
           N.LA_ST_LZOP_LOOKBEHIND: "LOOKBEHIND", N.LA_ST_LZOP_NOT_CONSUMED: "NOT_CONSUMED", N.LA_ST_LZOP_SHORT_OUTPUT: "SHORT_OUTPUT",
           N.LA_ST_LZOP_BAD_SUM_U: "BAD_SUM_U", N.LA_ST_LZOP_REFUSED: "REFUSED"}
+
+
+BLOCK_BYTES = N.LA_LZOPC_BLOCK_BYTES
+
+
+def compress_bound(n, block_size=BLOCK_BYTES):
+    """bytes the blocks of n input bytes can take (0 for block_size 0); a lead is the caller's to add"""
+    return int(N.gpu_lib().la_gpu_lzop_compress_bound(n, block_size))
+
+
+def compress_window(ctx, d_src, block_size=BLOCK_BYTES, lead_bytes=0, out_cap=None, d_out=None):
+    """Device lzop compression of one window (la_gpu_lzop_compress): d_src is a 1-D uint8 CUDA tensor; returns a uint8
+    CUDA tensor holding `lead_bytes` of untouched gap and the window's blocks back to back (no header, no closing word).
+    With `out_cap` (and optionally `d_out`) the call gets that much room only and the needed size is returned beside the
+    tensor."""
+    import torch
+    n = int(d_src.numel())
+    dev = d_src.device
+    cap = lead_bytes + compress_bound(n, block_size) if out_cap is None else int(out_cap)
+    if d_out is None:
+        d_out = torch.zeros(max(cap, 16), dtype=torch.uint8, device=dev)
+    d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    b = N._LzopcBatchC()
+    b.d_src, b.src_bytes = (d_src.data_ptr() if n else None), n
+    b.block_size, b.lead_bytes = block_size, lead_bytes
+    b.d_out, b.out_cap, b.d_out_bytes = d_out.data_ptr(), cap, d_len.data_ptr()
+    ctx.lzop_compress(b)
+    ctx.sync()
+    total = int(d_len.cpu()[0])
+    if out_cap is not None:
+        return d_out, total
+    assert total <= cap, (total, cap)
+    return d_out[:total]
 
 
 def to_device(image):
