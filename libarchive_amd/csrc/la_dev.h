@@ -549,6 +549,35 @@ __host__ __device__ __forceinline__ uint32_t la_lz4_plan_entries(uint32_t src_le
 	return la_lz4_lit_chunk_edge(src_len) + 1u;
 }
 
+/* Which dwords of a payload chunk a literal run stores: THE place where that is decided.  Phase L moves a 32-byte chunk
+ * of the payload (from payload offset c0, a multiple of 32) to the window as whole dwords on the chunk's own grid.  A run
+ * [ls, le) of a sequence with output position dst stores the dwords [*m0, *mend) of the chunk, the ones that hold at
+ * least one of its bytes, and dword m goes to  *w0 + 4 m,  *w0 = w + dst + c0 - ls  with w the window's first byte: a
+ * pointer, or an offset (then modulo 2^32: dst + c0 - ls lies up to 31 below zero for a run that starts inside the chunk;
+ * a dword the run stores is at most three bytes in front of dst).  False, and nothing written, when no byte of the run
+ * lies in the chunk.  The first and the last dword may spill up to three bytes over the run's ends: into the match in
+ * front of it or behind it, which is at least four bytes long and is copied later, or into the window's headroom and
+ * slack.
+ * In a table the lz4 parse kernels wrote two literal runs are at least three payload bytes apart (the match offset and
+ * the next token stand between them), so a dword of the grid holds bytes of at most one run: the ranges of a chunk's
+ * runs are disjoint and increasing, and a dword has one owner or none.  That is what lets the window kernel pick an
+ * owner per dword (DEPS = true) instead of walking the dwords once per run (put(), the other instantiations); both ask
+ * here, and tests/lz4_literal_dword_rule.py restates it. */
+template <class W>
+__host__ __device__ __forceinline__ bool la_lz4_lit_run_dwords(uint32_t ls, uint32_t le, uint32_t dst, uint32_t c0, W w,
+    uint32_t *m0, uint32_t *mend, W *w0)
+{
+	const uint32_t c1 = c0 + 32u;
+	const uint32_t lo = ls > c0 ? ls : c0, hi = le < c1 ? le : c1;
+	if (hi > lo) {
+		*m0 = (lo - c0) >> 2;
+		*mend = (hi - c0 + 3) >> 2;
+		*w0 = w + dst + c0 - ls;
+		return true;
+	}
+	return false;
+}
+
 /* One expand step over a table of blocks: what every expand launch is given.  Host side only: the launchers unpack
  * it into their kernels' (restrict-qualified) arguments. */
 struct la_expand_job {

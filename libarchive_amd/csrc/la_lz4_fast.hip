@@ -96,6 +96,19 @@
  * stretch in front of the first literal store went from 13.7 k to 8.9 k, the block to 75.1 k; the four C2 launches
  * 17.97 -> 17.05 ms, the dependency kernel 1.91 -> 2.32 ms.  84 VGPRs and 74 368 B of LDS against 90 and 78 480.
  * DEPS = false builds the index here as before, by the same rule.
+ *
+ * Phase L dword by dword (profiles/r30_lz4_literal_dwords.md): put() walks a chunk's eight dwords once per run, 96
+ * predicated stores per thread for sixteen dwords to place, and 2 069 of the kernel's 2 449 static instructions stood
+ * in front of the barrier that ends phase L.  Which dwords of a chunk a run stores is stated once, la_lz4_lit_run_dwords
+ * (la_dev.h); two runs of a parsed table are at least three payload bytes apart, so a dword of the chunk's grid has one
+ * owner or none.  With DEPS = true the six runs a chunk fetches leave their window offset under the bits of their 8-bit
+ * range mask (one bit extract and one and-or per run and dword), and each dword goes out with one store under one
+ * predicate: the same (address, dword) stores as before.  1 818 instructions in front of the barrier, 33 ds_write_b32
+ * where there were 113, 114 s_and_saveexec where there were 206; 87 VGPRs (84), no scratch, 74 368 B of LDS.  The
+ * literal stores of a block 17.0 k -> 12.5 k cycles, the block 74.9 k -> 71.7 k; the four C2 launches 17.06 -> 16.35 ms.
+ * Picking the owner with ordered thresholds (compare and select: 1 950 instructions) gave 16.54 ms and was not kept.
+ * DEPS = false and SEG keep put(), now over the same function; their device code is the parent's, instruction for
+ * instruction.
  */
 #include "la_dev.h"
 
@@ -391,11 +404,10 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 				const uint32_t ls = SEQ_LIT_SRC(e), le = ls + SEQ_LIT_LEN(e);
 				if (ls >= c1)
 					return true;
-				const uint32_t lo = ls > c0 ? ls : c0, hi = le < c1 ? le : c1;
-				if (hi > lo) {
-					uint32_t m0 = (lo - c0) >> 2;
-					const uint32_t mend = (hi - c0 + 3) >> 2;
-					uint8_t *wb = W + SEQ_DST(e) + c0 - ls;	/* wb[p - c0] <-> payload[p]; W has 16 bytes of headroom */
+				uint32_t m0, mend;	/* the chunk's dwords [m0, mend) are the run's, dword m at wb + 4 m */
+				uint8_t *wb;		/* wb[p - c0] <-> payload[p]; W has 16 bytes of headroom */
+				if (la_lz4_lit_run_dwords(ls, le, SEQ_DST(e), c0, W, &m0, &mend, &wb)) {
+					const uint32_t lo = ls > c0 ? ls : c0, hi = le < c1 ? le : c1;	/* the run's bytes inside the chunk */
 					if (exact_head && lo == ls && ((lo - c0) & 3u)) {
 						const uint32_t stop = hi < c0 + 4 * m0 + 4 ? hi : c0 + 4 * m0 + 4;
 						for (uint32_t pp = lo; pp < stop; pp++)	/* (once per segment: straight from the image) */
@@ -411,10 +423,41 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 				return le >= c1;
 			};
 			bool fin = false;
+			if constexpr (DEPS) {
+				/* The six runs at once, dword by dword (profiles/r30_lz4_literal_dwords.md).  put() tests each of a
+				 * chunk's eight dwords once per run, 48 predicated stores for eight dwords to place.  The runs'
+				 * dword ranges are disjoint (la_lz4_lit_run_dwords), so each dword has one owner or none: every run
+				 * leaves its window offset in the dwords of its 8-bit range mask, and each dword goes out with ONE
+				 * store under one predicate, to the same address with the same value as put() would send it.  An
+				 * entry behind the table's last one is zero and owns nothing, like a run outside the chunk; the
+				 * chunk is finished when the table is, or a run reaches the chunk's end.  A run slot that no lane
+				 * of the wave has is skipped wave-uniformly. */
+				uint32_t wo[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, any = 0;
+				fin = kk[u] + 5 >= ns;
 #pragma unroll
-			for (int t = 0; t < 6; t++)
-				if (!fin)
-					fin = (kk[u] + t >= ns) || put(pe[u][t], kb != 0 && kk[u] + t == 0);
+				for (int t = 0; t < 6; t++) {
+					const uint32_t ls = SEQ_LIT_SRC(pe[u][t]), le = ls + SEQ_LIT_LEN(pe[u][t]);
+					uint32_t m0 = 0, mend = 0, w0 = 0;
+					la_lz4_lit_run_dwords(ls, le, SEQ_DST(pe[u][t]), c0, (uint32_t)(W - win), &m0, &mend, &w0);	/* (offsets from win: 13 and up) */
+					const uint32_t own = (((1u << (mend - m0)) - 1u) << m0) & ~any;	/* (one owner whatever the table holds) */
+					fin = fin || le >= c1;
+					if (__ballot(own != 0) == 0)
+						continue;
+					any |= own;
+#pragma unroll
+					for (uint32_t m = 0; m < 8; m++)
+						wo[m] |= w0 & (0u - ((own >> m) & 1u));	/* (one bit extract, one and-or) */
+				}
+#pragma unroll
+				for (uint32_t m = 0; m < 8; m++)
+					if ((any >> m) & 1u)
+						lds_st4(win + wo[m] + 4 * m, dd[m]);
+			} else {
+#pragma unroll
+				for (int t = 0; t < 6; t++)
+					if (!fin)
+						fin = (kk[u] + t >= ns) || put(pe[u][t], kb != 0 && kk[u] + t == 0);
+			}
 			for (uint32_t k = kk[u] + 6; !fin && k < ns; k++)	/* more than six sequences touch this chunk: rare */
 				fin = put(seq_load(tab, k), false);
 		}

@@ -1,9 +1,11 @@
 #!/bin/bash
 # HBM traffic counters of the lz4 kernels at full size (separate --pmc passes, MI355X_MICROARCH.md HBM section)
 out=$1
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out.fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out.write.log 2>&1
+root=$(cd "$(dirname "$0")/.." && pwd)	# the repository: bench.py runs from there, $out is relative to it
+cd /tmp && export TMPDIR=/tmp && cd "$root"
+# (each pass under its own time limit; nothing more is started behind one that failed)
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out.fetch.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out.write.log 2>&1 || exit 1
 python - <<PY
 import csv,glob,collections,json
 res=collections.defaultdict(dict)
