@@ -496,6 +496,85 @@ __host__ __device__ __forceinline__ la_expand_route la_lz4_route(const la_lz4_bl
 	return nseq <= LA_LZ4_FAST_MAXSEQ ? LA_XR_WINDOW : LA_XR_WINDOW_SEG;
 }
 
+/* A block's words, fetched once: what la_lz4_route is asked with, and where the block's payload, output and table slot
+ * lie.  The expand kernels (window, in-order, general) open with la_lz4_load_block_words and route on what it returns
+ * (la_lz4_route_words); the dependency kernel, at eight workgroups per CU, gained 0.03 ms of 2.17 from it, short of the
+ * margin, and reads its words as before.  Read word by word where la_lz4_route first needs them, every array is a scalar
+ * load of its own behind its own wait and branch -- the compiler sinks a load to the test that first asks for it and does not lift it
+ * back over a branch: six memory round trips in a row before a kernel has asked for its first payload byte
+ * (profiles/r31_lz4_block_words.md).  Here all of them are requested together, and the pin -- an empty asm that takes
+ * every word in a scalar register -- keeps them live at one point, so they form one clause behind one wait.
+ * The block index must be wave-uniform (a scalar register: blockIdx, or through readfirstlane) and below n: then every
+ * index is inside its array, table_off having n + 1 entries (lz4_ws_carve in la_api.hip, la_inflate_emit).  All the
+ * arrays are read whatever the block's state, so a launch passes only arrays it was given: TABLE_OFF = false for a
+ * kernel that has no table offsets (the general kernel; its nseq words are carved for every batch, and routed on only
+ * with have_tables). */
+struct la_lz4_block_words {
+	uint64_t src_off;
+	uint32_t src_len, dst_cap, flags;
+	uint32_t block_sum;	/* (nobody asks for it here.  It lies in the 16 bytes that one load fetches with the three words
+				 * in front of it; left out of the pin, its register is handed to the next load at once, which then
+				 * has to wait for this one: a second round trip) */
+	uint32_t status, out_len, nseq;
+	uint64_t dst_off, table_off;
+};
+/* (device only: the host has no scalar registers to pin) */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LA_PIN_SCALARS(...) asm volatile("" :: __VA_ARGS__)
+__device__ __forceinline__ void la_lz4_pin_block_words(la_lz4_block_words &w)
+{
+	asm volatile("" : "+s"(w.src_off), "+s"(w.src_len), "+s"(w.dst_cap), "+s"(w.flags), "+s"(w.block_sum), "+s"(w.status), "+s"(w.out_len),
+	    "+s"(w.nseq), "+s"(w.dst_off), "+s"(w.table_off));
+}
+#else
+#define LA_PIN_SCALARS(...) do { } while (0)
+__device__ __forceinline__ void la_lz4_pin_block_words(la_lz4_block_words &) { }
+#endif
+/* the value of lane 0 in a scalar register (a no-op on a value that is in one already) */
+__device__ __forceinline__ uint32_t la_first_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t la_first_lane(uint64_t v)
+{
+	return ((uint64_t)la_first_lane((uint32_t)(v >> 32)) << 32) | la_first_lane((uint32_t)v);
+}
+/* VECTOR_LOADS: the kernel asks again behind its own stores (a loop over blocks), where the compiler loads through the
+ * vector path, every lane the same address: the words move to scalar registers by hand, so that the pin holds */
+template <bool TABLE_OFF = true, bool VECTOR_LOADS = false>
+__device__ __forceinline__ la_lz4_block_words la_lz4_load_block_words(uint32_t bi, const la_lz4_block *blocks,
+    const uint32_t *status, const uint32_t *out_len, const uint32_t *nseq, const uint64_t *dst_off, const uint64_t *table_off)
+{
+	la_lz4_block_words w;
+	w.src_off = blocks[bi].src_off;
+	w.src_len = blocks[bi].src_len;
+	w.dst_cap = blocks[bi].dst_cap;
+	w.flags = blocks[bi].flags;
+	w.block_sum = blocks[bi].block_sum;
+	w.status = status[bi];
+	w.out_len = out_len[bi];
+	w.nseq = nseq[bi];
+	w.dst_off = dst_off[bi];
+	w.table_off = TABLE_OFF ? table_off[bi] : 0;
+	if (VECTOR_LOADS) {
+		w.src_off = la_first_lane(w.src_off); w.src_len = la_first_lane(w.src_len); w.dst_cap = la_first_lane(w.dst_cap);
+		w.flags = la_first_lane(w.flags); w.block_sum = la_first_lane(w.block_sum); w.status = la_first_lane(w.status);
+		w.out_len = la_first_lane(w.out_len); w.nseq = la_first_lane(w.nseq); w.dst_off = la_first_lane(w.dst_off);
+		w.table_off = la_first_lane(w.table_off);
+	}
+	la_lz4_pin_block_words(w);
+	return w;
+}
+/* la_lz4_route asked with the fetched words (slab_cap: the decoded slab's size, la_lz4_route's dst_cap) */
+__device__ __forceinline__ la_expand_route la_lz4_route_words(const la_lz4_block_words &w, uint64_t slab_cap, bool have_tables,
+    uint32_t long_thr)
+{
+	la_lz4_block b;
+	b.src_off = w.src_off;
+	b.src_len = w.src_len;
+	b.dst_cap = w.dst_cap;
+	b.flags = w.flags;
+	b.block_sum = w.block_sum;
+	return la_lz4_route(b, w.status, w.out_len, w.nseq, w.dst_off, slab_cap, have_tables, long_thr);
+}
+
 /* What a match of the LDS-window kernel has to wait for: THE place where that is decided.  Literals are all in the window
  * before the first match is copied, so sequence k (output position d, match at mdst = d + lit_len, offset off, mlen match
  * bytes) waits only for earlier MATCHES under its source.  The source is the span min(mlen, off) from mdst - off (an

@@ -359,7 +359,11 @@ __global__ __launch_bounds__(256) void lz4_expand_general_kernel(const uint8_t *
 	uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
 	if (i >= n)
 		return;
-	uint32_t fl = blocks[i].flags;
+	/* the block's words in one round trip (la_lz4_load_block_words, la_dev.h; no table offsets here).  A chain asks
+	 * again per block, behind its own stores: through the vector path, i being the same in every lane */
+	la_lz4_block_words b = la_lz4_load_block_words<false, true>(i, blocks, status, out_len, nseq, dst_off, nullptr);
+	LA_PIN_SCALARS("s"(src), "s"(src_bytes), "s"(dst), "s"(dst_cap), "s"(have_tables), "s"(hist_len), "s"(long_thr));
+	uint32_t fl = b.flags;
 	/* a dependent block that is not the first of its frame belongs to the
 	 * chain of the wave that owns the frame's first block */
 	if ((fl & LA_LZ4B_DEPENDENT) && !(fl & (LA_LZ4B_FIRST | LA_LZ4B_HIST)))
@@ -369,11 +373,10 @@ __global__ __launch_bounds__(256) void lz4_expand_general_kernel(const uint8_t *
 	 * block as its dictionary: the caller has put those bytes in front of the slab */
 	uint32_t prev_len = (fl & LA_LZ4B_HIST) ? hist_len : 0;
 	for (;;) {
-		la_lz4_block b = blocks[i];
-		uint8_t *d = dst + dst_off[i];
-		uint32_t olen = out_len[i];
+		uint8_t *d = dst + b.dst_off;
+		uint32_t olen = b.out_len;
 		/* blocks the LDS-window kernels take, and blocks nobody may write, are passed over */
-		if (la_lz4_route(b, status[i], olen, nseq[i], dst_off[i], dst_cap, have_tables != 0, long_thr) == LA_XR_GENERAL) {
+		if (la_lz4_route_words(b, dst_cap, have_tables != 0, long_thr) == LA_XR_GENERAL) {
 			const uint8_t *s = src + b.src_off;
 			if (b.flags & LA_LZ4B_STORED) {
 				/* stored block (lz4.c:530-552): bytes up to the slab's 16-byte grid one by one,
@@ -401,7 +404,8 @@ __global__ __launch_bounds__(256) void lz4_expand_general_kernel(const uint8_t *
 		i++;
 		if (i >= n)
 			break;
-		uint32_t nf = blocks[i].flags;
+		b = la_lz4_load_block_words<false, true>(i, blocks, status, out_len, nseq, dst_off, nullptr);
+		uint32_t nf = b.flags;
 		if (!(nf & LA_LZ4B_DEPENDENT) || (nf & (LA_LZ4B_FIRST | LA_LZ4B_HIST)))
 			break;
 		wave_mem_fence();	/* previous block's bytes become the dictionary */

@@ -109,6 +109,16 @@
  * Picking the owner with ordered thresholds (compare and select: 1 950 instructions) gave 16.54 ms and was not kept.
  * DEPS = false and SEG keep put(), now over the same function; their device code is the parent's, instruction for
  * instruction.
+ *
+ * A block's words in one round trip (profiles/r31_lz4_block_words.md): la_lz4_route is a chain of ||, and each word it is
+ * asked with used to be loaded where the chain first needs it -- six scalar loads one behind another, each with its own
+ * wait and branch, kernel arguments fetched one or two at a time between them, and table_off[bi] read again for every
+ * slot's dependency words.  The kernel now opens with la_lz4_load_block_words (la_dev.h): one clause of arguments, one
+ * clause with the block's words and the late arguments (table, deps, lit_plan, src, dst) behind one wait, then the routing
+ * test; no scalar load between the first payload load and the barrier that ends phase L.  Registers, LDS and occupancy
+ * of all three instantiations are unchanged.  The four C2 launches 16.31 -> 16.02 ms.  The stretch the stamps call "up to
+ * the loads requested" fell by 0.7 k cycles only: the first stamp stands behind the routing test, most of the removed
+ * trips were in front of it, and what is left there is the payload chunks' own round trip.
  */
 #include "la_dev.h"
 
@@ -198,18 +208,22 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	auto do_block = [&](const uint32_t bi) __attribute__((always_inline)) {
 	if (bi >= n)
 		return;
-	const la_lz4_block b = blocks[bi];
-	const uint32_t olen = out_len[bi];
-	const uint32_t ns_all = nseq[bi];
-	const uint64_t doff = dst_off[bi];
+	/* the block's words in one round trip (la_lz4_load_block_words, la_dev.h) */
+	const la_lz4_block_words b = la_lz4_load_block_words<true, SEG>(bi, blocks, status, out_len, nseq, dst_off, table_off);
+	/* and with them every argument the block needs later: no round trip of its own in front of the plan, the table
+	 * entries or the dependency words */
+	LA_PIN_SCALARS("s"(src), "s"(src_bytes), "s"(dst), "s"(dst_cap), "s"(table), "s"(long_thr), "s"(deps), "s"(lit_plan));
+	const uint32_t olen = b.out_len;
+	const uint32_t ns_all = b.nseq;
+	const uint64_t doff = b.dst_off;
 	/* this launch's share of the table: blocks of one LDS segment, or (SEG) of more */
 	static_assert(MAXSEQ == LA_LZ4_FAST_MAXSEQ, "la_lz4_route splits the window kernels' blocks at LA_LZ4_FAST_MAXSEQ");
-	if (la_lz4_route(b, status[bi], olen, ns_all, doff, dst_cap, true, long_thr) != (SEG ? LA_XR_WINDOW_SEG : LA_XR_WINDOW))
+	if (la_lz4_route_words(b, dst_cap, true, long_thr) != (SEG ? LA_XR_WINDOW_SEG : LA_XR_WINDOW))
 		return;
 
 	STAMP(0);
 	const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const la_lz4_seq *const tab_all = table + table_off[bi];
+	const la_lz4_seq *const tab_all = table + b.table_off;
 	const uint8_t *s = src + b.src_off;
 	const uint64_t s_room = src_bytes - b.src_off;	/* bytes of the image from s on */
 	uint8_t *g_out = dst + doff;
@@ -246,7 +260,7 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 	 * by the dependency kernel: requested with the chunks, in front of the table entries, so that the chunk's sequences
 	 * can be asked for as soon as it is back.  No predecessor entries, no index built in LDS, no barrier in front of
 	 * phase L (profiles/r27_lz4_literal_plan.md). */
-	const uint16_t *const plan = DEPS ? (const uint16_t *)(const void *)(lit_plan + table_off[bi]) : nullptr;
+	const uint16_t *const plan = DEPS ? (const uint16_t *)(const void *)(lit_plan + b.table_off) : nullptr;
 	const uint32_t plan_chunks = la_lz4_lit_chunk_edge(b.src_len);	/* the plan has an entry for every chunk of the payload */
 	uint32_t kk0[LBATCH];
 #pragma unroll
@@ -469,7 +483,7 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 #pragma unroll
 		for (uint32_t r = 0; r < MAXSTEPS; r++) {
 			const uint32_t k = fast_seq_index(r, wave, lane);
-			dw[r] = (r * FAST_THREADS < ns && k < ns) ? deps[table_off[bi] + k] : 0;
+			dw[r] = (r * FAST_THREADS < ns && k < ns) ? deps[b.table_off + k] : 0;
 		}
 		publish();
 	}

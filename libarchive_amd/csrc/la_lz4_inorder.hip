@@ -153,17 +153,19 @@ __device__ __forceinline__ io_blk io_load_blk(uint32_t bi, uint32_t n, const uin
 	r.tab = nullptr; r.s = nullptr; r.s_room = 0; r.g_out = nullptr;
 	if (bi >= n)
 		return r;
-	const la_lz4_block b = blocks[bi];
-	const uint32_t olen = out_len[bi], ns = nseq[bi];
-	const uint64_t doff = dst_off[bi];
+	/* the block's words in one round trip (la_lz4_load_block_words, la_dev.h).  Every wave asks once per block, behind
+	 * the workgroup's own stores: the loads go through the vector path, bi being the same in every lane */
+	const la_lz4_block_words b = la_lz4_load_block_words<true, true>(bi, blocks, status, out_len, nseq, dst_off, table_off);
+	const uint32_t olen = b.out_len, ns = b.nseq;
+	const uint64_t doff = b.dst_off;
 	/* blocks of any sequence count: this kernel runs in place of both launches of the polling kernel */
-	const la_expand_route xr = la_lz4_route(b, status[bi], olen, ns, doff, dst_cap, true, long_thr);
+	const la_expand_route xr = la_lz4_route_words(b, dst_cap, true, long_thr);
 	if (xr != LA_XR_WINDOW && xr != LA_XR_WINDOW_SEG)
 		return r;
 	r.take = true;
 	r.ns = ns;
 	r.olen = olen;
-	r.tab = table + table_off[bi];
+	r.tab = table + b.table_off;
 	r.s = src + b.src_off;
 	r.s_room = src_bytes - b.src_off;
 	r.g_out = dst + doff;
