@@ -243,6 +243,11 @@ typedef struct la_batch_summary {
 					 * front of its match phase, as it did before the dependency kernel (la_lz4_deps.hip) took
 					 * that search out of it; same results, kept as the cross-check of the dependency words */
 
+#define LA_LZ4_OPT_SPLIT_SMALL 32u	/* a batch below the slicing threshold takes the split form of the last expand slice
+					 * (la_lz4_slices.h: launches by position in the frame, frame checksums advancing between
+					 * them) with the whole batch as that slice, wherever a batch at size would split its last
+					 * quarter; same results, so that tests reach the path with a few dozen blocks */
+
 typedef struct la_lz4_batch {
 	const uint8_t      *d_src;	/* compressed image (or batch window) in HBM */
 	uint64_t            src_bytes;

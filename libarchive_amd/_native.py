@@ -34,6 +34,7 @@ LA_LZ4B_STORED, LA_LZ4B_CHECKSUM, LA_LZ4B_DEPENDENT, LA_LZ4B_FIRST = 1, 2, 4, 8
 LA_LZ4F_CONTENT_SUM, LA_LZ4F_HEADER_SUM, LA_LZ4F_CONT, LA_LZ4F_OPEN, LA_LZ4F_HASHED = 1, 2, 4, 8, 16
 LA_LZ4_OPT_GENERAL_ONLY, LA_LZ4_OPT_NO_VERIFY, LA_LZ4_OPT_PARSE_V1, LA_LZ4_OPT_EXPAND_INORDER = 1, 2, 4, 8
 LA_LZ4_OPT_SEARCH_IN_EXPAND = 16
+LA_LZ4_OPT_SPLIT_SMALL = 32
 LA_GPU_ABI_VERSION = 3
 LA_ST_OK, LA_ST_GZ_DATA, LA_ST_GZ_TRUNCATED, LA_ST_GZ_OUT_FULL, LA_ST_GZ_NO_TRAILER = 0, 5, 6, 9, 10
 LA_ST_GZ_PIECE_END, LA_ST_GZ_NEEDS_HISTORY = 18, 19     # LA_GZ_OPT_PIECES only

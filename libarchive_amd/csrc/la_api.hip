@@ -36,6 +36,11 @@ struct la_gpu_ctx {
 	 * expand kernels of earlier ones */
 	hipStream_t aux_stream;
 	hipEvent_t slice_ev[LA_MAX_SLICES + 1];
+	/* a split last slice (la_lz4_slices.h): one event behind each group's launch, and the frames' hash states between
+	 * the passes, one LA_XXH_CARRY_BYTES record per block of the slice; grown like lz4_deps, never cleared */
+	hipEvent_t split_ev[LA_LZ4_SPLIT_MAX_GROUPS];
+	void *lz4_carry;
+	uint64_t lz4_carry_cap;	/* records */
 	/* optional timing of the last batch: one (start, stop) event pair per kernel range,
 	 * recorded on the stream the kernels run on, summed by name when read */
 	int prof_on;
@@ -119,6 +124,8 @@ int la_gpu_open(int device, la_gpu_ctx **out)
 	(void)hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking);
 	for (int i = 0; i <= LA_MAX_SLICES; i++)
 		(void)hipEventCreateWithFlags(&c->slice_ev[i], hipEventDisableTiming);
+	for (uint32_t i = 0; i < LA_LZ4_SPLIT_MAX_GROUPS; i++)
+		(void)hipEventCreateWithFlags(&c->split_ev[i], hipEventDisableTiming);
 	c->stream = c->own_stream;
 	*out = c;
 	return LA_OK;
@@ -133,6 +140,7 @@ void la_gpu_close(la_gpu_ctx *c)
 	if (c->ws) (void)hipFree(c->ws);
 	if (c->lz4_deps) (void)hipFree(c->lz4_deps);
 	if (c->lz4_plan) (void)hipFree(c->lz4_plan);
+	if (c->lz4_carry) (void)hipFree(c->lz4_carry);
 	(void)hipEventDestroy(c->ev0);
 	(void)hipEventDestroy(c->ev1);
 	(void)hipEventDestroy(c->mark);
@@ -142,6 +150,8 @@ void la_gpu_close(la_gpu_ctx *c)
 	}
 	for (int i = 0; i <= LA_MAX_SLICES; i++)
 		(void)hipEventDestroy(c->slice_ev[i]);
+	for (uint32_t i = 0; i < LA_LZ4_SPLIT_MAX_GROUPS; i++)
+		(void)hipEventDestroy(c->split_ev[i]);
 	(void)hipStreamSynchronize(c->aux_stream);
 	(void)hipStreamDestroy(c->aux_stream);
 	(void)hipStreamDestroy(c->own_stream);
@@ -376,6 +386,30 @@ static int lz4_deps_reserve(la_gpu_ctx *c, uint64_t words)
 	return LA_OK;
 }
 
+/* Room for the hash states of a split last slice (la_lz4_slices.h): 64 B per block of the slice, 4 MiB on the bench
+ * shape.  A buffer of its own for the reason lz4_deps has one. */
+static int lz4_carry_reserve(la_gpu_ctx *c, uint64_t records)
+{
+	if (records <= c->lz4_carry_cap)
+		return LA_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->aux_stream));
+	c->lz4_carry_cap = 0;
+	if (c->lz4_carry) { HIPCHK(c, hipFree(c->lz4_carry)); c->lz4_carry = NULL; }
+	records = (records + 0xFFFull) & ~0xFFFull;
+	HIPCHK(c, hipMalloc(&c->lz4_carry, records * LA_XXH_CARRY_BYTES));
+	c->lz4_carry_cap = records;
+	return LA_OK;
+}
+
+/* Group bounds of a split last slice in sixteenths of the period, and whether the passes that run beside a later
+ * group use the sixteen-lane form (the last pass always does).  Kept by the step time among (8, 13), (8, 14), (10, 15)
+ * and (12), each with both forms: profiles/r32_lz4_last_slice.md, section 5. */
+static const uint32_t lz4_split_sixteenths[] = { 8, 13, 16 };
+static_assert(sizeof(lz4_split_sixteenths) / sizeof(lz4_split_sixteenths[0]) <= LA_LZ4_SPLIT_MAX_GROUPS, "too many groups");
+static const bool lz4_split_row_hidden = false;
+
 /* does a decode of this batch hand the polling kernel dependency words?  (not without tables, not under the
  * cross-check option, not when the in-order kernel expands) */
 static bool lz4_uses_deps(const la_lz4_batch *bt)
@@ -410,10 +444,25 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 		int rc = lz4_deps_reserve(c, w.table_cap);
 		if (rc != LA_OK) return rc;
 	}
+	const uint32_t n = bt->n_blocks;
+	const uint32_t nsl = (fast && n >= 4u * 8192u) ? 4u : 1u;	/* expand slices */
+	/* The last slice by position in the frame (la_lz4_slices.h), where the default window kernel runs and frames are
+	 * checked: the frames' chains advance between its launches, and the step waits for the last group's bytes only.
+	 * Decided here, from the batch's shape alone, so that the carries are reserved before anything is queued. */
+	la_lz4_split split = { 0, 0, 0, 0, { 0 } };
+	if (fast && poll && with_deps && verify && bt->n_frames && (nsl == 4 || (bt->options & LA_LZ4_OPT_SPLIT_SMALL))) {
+		const uint32_t P = la_lz4_split_period(n, bt->n_frames);
+		if (P) {
+			const uint32_t first = nsl == 4 ? (uint32_t)((uint64_t)n * 3 / 4) / P * P : 0u;
+			la_lz4_split_init(&split, first, n, P, lz4_split_sixteenths,
+			    sizeof(lz4_split_sixteenths) / sizeof(lz4_split_sixteenths[0]));
+			int rc = lz4_carry_reserve(c, n - first);
+			if (rc != LA_OK) return rc;
+		}
+	}
 	hipStream_t sx = c->stream;		/* main stream (the caller's): checksums, expand, summary */
 	hipStream_t sp = c->aux_stream;		/* second stream: parse beside the block checksums, frame
 						 * checksums beside the expand kernel */
-	const uint32_t n = bt->n_blocks;
 	const la_expand_job xj = {	/* every expand launch below is this job, or a slice of it */ bt->d_src, bt->src_bytes, bt->d_blocks, n, bt->d_dst, bt->dst_cap, bt->d_dst_off,
 	    bt->d_out_len, bt->d_block_status, w.nseq, fast ? w.table : NULL, w.table_off,
 	    LA_LZ4_LONG_SEQ_BYTES,	/* blocks of few long sequences go to the general kernel (la_dev.h) */
@@ -468,17 +517,43 @@ int la_gpu_lz4_decode(la_gpu_ctx *c, const la_lz4_batch *bt)
 
 	/* blocks the LDS-window kernel does not take (any size, stored, chains of dependent
 	 * blocks) first, over the whole table; then the LDS-window kernel in slices, each
-	 * slice's frames hashed on the second stream while the next slice expands */
+	 * slice's frames hashed on the second stream while the next slice expands.  The last
+	 * slice has no next one: where it can (below) it goes out in groups of period positions,
+	 *     main stream:    slice 1 | slice 2 | slice 3 | group 0    | group 1 | group 2 | join, merge, summary
+	 *     second stream:            hash 1  | hash 2  | hash 3     | pass 0  | pass 1  | pass 2 (lz4_frame_sums_tail)
+	 * pass g taking every frame of the slice over the blocks that groups 0 .. g completed, so that the step waits for
+	 * the chain over the last group's blocks only.  Every ordering is an event between launches.
+	 * (The two launches in front of the slices were also tried on the second stream beside lz4_deps, the merge in
+	 * front of the join: 0.08 ms per step, inside the spread of three runs, not kept; profiles/r32_lz4_last_slice.md.) */
 	prof_range(c, fast ? "lz4_expand_general" : "lz4_expand", sx, [&] { la_launch_lz4_expand_general(sx, xj, bt->hist_len); });
 	if (fast && poll)
 		/* eligible blocks with more sequences than one LDS segment: classified on the device, shared out over a
 		 * small grid (a no-op launch when there are none).  (The in-order kernel takes blocks of any sequence count.) */
 		prof_range(c, "lz4_expand_big", sx, [&] { la_launch_lz4_expand_fast_big(sx, xj, w.big); });
-	const uint32_t nsl = (fast && n >= 4u * 8192u) ? 4u : 1u;
 	if (bt->n_frames && !verify)
 		HIPCHK(c, hipMemsetAsync(bt->d_frame_status, 0, (size_t)bt->n_frames * sizeof(uint32_t), sx));
 	for (uint32_t i = 0; i < nsl; i++) {
-		const uint32_t first = (uint32_t)((uint64_t)n * i / nsl), last = (uint32_t)((uint64_t)n * (i + 1) / nsl);
+		uint32_t first = (uint32_t)((uint64_t)n * i / nsl), last = (uint32_t)((uint64_t)n * (i + 1) / nsl);
+		if (split.n_groups) {	/* the split slice starts on a multiple of its period */
+			if (i + 2 == nsl)
+				last = split.first;
+			if (i + 1 == nsl) {
+				for (uint32_t g = 0; g < split.n_groups; g++) {
+					prof_range(c, "lz4_expand", sx, [&] { la_launch_lz4_expand_fast_group(sx, xj, split, g); });
+					HIPCHK(c, hipEventRecord(c->split_ev[g], sx));
+					HIPCHK(c, hipStreamWaitEvent(sp, c->split_ev[g], 0));
+					const bool tail = g + 1 == split.n_groups;
+					/* pass g: every frame over the blocks that groups 0 .. g made ready; the last one is the
+					 * stretch the step waits for */
+					prof_range(c, tail ? "lz4_frame_sums_tail" : "lz4_frame_sums", sp, [&] {
+						la_launch_lz4_frame_sums_split(sp, bt->d_src, bt->d_dst, bt->d_frames, bt->n_frames,
+						    bt->d_dst_off, bt->dst_cap, bt->d_frame_status, split, g, c->lz4_carry,
+						    bt->d_carry_in, bt->d_carry_out, tail || lz4_split_row_hidden);
+					});
+				}
+				break;
+			}
+		}
 		const la_expand_job sj = xj.slice(first, last - first);
 		if (fast)
 			prof_range(c, "lz4_expand", sx, [&] { (poll ? la_launch_lz4_expand_fast : la_launch_lz4_expand_inorder)(sx, sj); });

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/la_gpu.h"
+#include "la_lz4_slices.h"
 
 #define LA_WAVE 64
 
@@ -444,6 +445,11 @@ void la_launch_lz4_frame_sums(hipStream_t s, const uint8_t *d_src, const uint8_t
     const la_lz4_frame *d_frames, uint32_t n_frames, const uint64_t *d_dst_off,
     uint64_t dst_cap, uint32_t *d_frame_status, uint32_t end_lo, uint32_t end_hi,
     const void *d_carry_in, void *d_carry_out, int row /* 16 lanes per frame: latency over throughput */);
+/* hash pass g of a split last slice (la_lz4_slices.h); d_carries: one LA_XXH_CARRY_BYTES record per block of the slice */
+void la_launch_lz4_frame_sums_split(hipStream_t s, const uint8_t *d_src, const uint8_t *d_dst,
+    const la_lz4_frame *d_frames, uint32_t n_frames, const uint64_t *d_dst_off, uint64_t dst_cap,
+    uint32_t *d_frame_status, const la_lz4_split &sp, uint32_t g, void *d_carries, const void *d_carry_in,
+    void *d_carry_out, int row);
 void la_launch_lz4_merge_status(hipStream_t s, const uint32_t *d_sum_status, uint32_t n, uint32_t *d_status);
 
 /* la_lz4.hip, la_lz4_fast.hip */
@@ -700,6 +706,8 @@ void la_launch_lz4_parse_staged(hipStream_t s, const uint8_t *d_src, uint64_t sr
 void la_launch_lz4_expand_general(hipStream_t s, const la_expand_job &j, uint32_t hist_len);
 void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j);
 void la_launch_lz4_expand_fast_big(hipStream_t s, const la_expand_job &j, uint32_t *d_big /* n + 1 words */);
+/* group g of a split last slice (la_lz4_slices.h): j is the whole batch's job and carries deps and lit_plan */
+void la_launch_lz4_expand_fast_group(hipStream_t s, const la_expand_job &j, const la_lz4_split &sp, uint32_t g);
 /* la_lz4_deps.hip: the dependency words and the literal plans of the job's LA_XR_WINDOW blocks, for a later
  * la_launch_lz4_expand_fast whose job carries d_deps and d_plan (same table offsets) */
 void la_launch_lz4_deps(hipStream_t s, const la_expand_job &j, uint32_t *d_deps, uint8_t *d_plan);

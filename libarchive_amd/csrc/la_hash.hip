@@ -16,6 +16,13 @@
  * Adler-32 (zlib's adler32(), the lzop filter's block check, lzop.c:422, :469) splits a
  * range the same way: the (a, b) pair of two ranges in a row is a function of their pairs
  * and the second one's length, so the same tree joins the lanes.
+ *
+ * The lz4 frames' content checksums run on a second stream beside the expand slices, each slice's frames behind the
+ * slice.  A chain costs about 31 cycles per 16-byte stripe whatever runs beside it (three dependent vector instructions
+ * of a lone wave), so the frames of the LAST slice, with nothing left to hide behind, used to hold the step for a whole
+ * frame's chain.  lz4_frame_sums_kernel's SPLIT form goes with a last slice that is expanded by position in the frame
+ * (la_lz4_slices.h): one pass behind each group of positions, every frame advancing from its carry (xxh32_quad_stream)
+ * over the blocks that are in the slab by then, and only the chain over the last group's blocks is left for the end.
  */
 #include "la_dev.h"
 
@@ -204,14 +211,31 @@ __device__ uint32_t xxh32_quad_stream(const la_xxh_carry *cin, la_xxh_carry *cou
 	return xxh_avalanche(h);
 }
 
+/* One hash pass of a split last slice (la_lz4_slices.h), behind the launch of group g: the frames advance over the
+ * blocks that became ready between the bounds h_lo = h[g] and h_hi = h[g + 1].  carries: one record per block of the
+ * slice, a frame's at la_lz4_split_carry_index(); never cleared, because a frame's first piece starts from the seed. */
+template <bool SPLIT> struct frame_sums_pass { };
+template <> struct frame_sums_pass<true> {
+	uint32_t first, period;
+	uint32_t h_lo, h_hi;
+	uint32_t last_pass;	/* digest, compare, write fstatus; and every frame the passes do not stream, whole */
+	la_xxh_carry *carries;
+};
+
 /* ROW = false: four lanes per frame (xxh32_quad; bulk).  ROW = true: sixteen lanes per frame
  * (xxh32_row; half the latency per hash, a quarter of the hashes per instruction) for launches
- * whose duration nothing hides. */
-template <bool ROW>
+ * whose duration nothing hides.
+ * SPLIT = true: the frames that end in a split last slice, one launch per group.  A frame is STREAMED when it has blocks,
+ * a content checksum, no state coming in or going out (LA_LZ4F_CONT / _OPEN) and its bytes inside the slab: its chain
+ * advances pass by pass through its carry, and only the last pass digests it, compares and reports.  Every other frame
+ * that ends in the slice is left to the last pass, which handles it as the unsplit form does.  The descriptor check byte
+ * belongs to the last pass. */
+template <bool ROW, bool SPLIT = false>
 __global__ __launch_bounds__(64) void lz4_frame_sums_kernel(const uint8_t *__restrict__ src,
     const uint8_t *__restrict__ dst, const la_lz4_frame *__restrict__ frames, uint32_t n,
     const uint64_t *__restrict__ dst_off, uint64_t dst_cap, uint32_t *__restrict__ fstatus,
-    uint32_t end_lo, uint32_t end_hi, const la_xxh_carry *carry_in, la_xxh_carry *carry_out)
+    uint32_t end_lo, uint32_t end_hi, const la_xxh_carry *carry_in, la_xxh_carry *carry_out,
+    const frame_sums_pass<SPLIT> pass)
 {
 	uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	uint32_t i = ROW ? t >> 4 : t >> 2;
@@ -225,13 +249,42 @@ __global__ __launch_bounds__(64) void lz4_frame_sums_kernel(const uint8_t *__res
 	const uint32_t fend = f.first_block + f.n_blocks;
 	if (fend < end_lo || fend > end_hi)
 		return;
+	bool streamed = false;
+	uint32_t lo = 0, hi = 0;	/* a streamed frame's blocks [lo, hi) are this pass's */
+	la_xxh_carry *carry = nullptr;
+	if constexpr (SPLIT) {
+		if (f.n_blocks && (f.flags & (LA_LZ4F_CONTENT_SUM | LA_LZ4F_CONT | LA_LZ4F_OPEN)) == LA_LZ4F_CONTENT_SUM) {
+			const uint64_t a = dst_off[f.first_block], e = dst_off[fend];
+			/* (xxhash.c:234, below: a one-shot length is an unsigned int; a longer frame stays with that form) */
+			streamed = e <= dst_cap && e - a <= 0xFFFFFFFFull;
+		}
+		if (streamed) {
+			lo = la_lz4_split_pass_lo(pass.first, pass.period, pass.h_lo, f.first_block, f.n_blocks);
+			hi = la_lz4_split_ready(pass.first, pass.period, pass.h_hi, f.first_block, f.n_blocks);
+			carry = pass.carries + la_lz4_split_carry_index(pass.first, f.first_block, f.n_blocks);
+		}
+		if (!pass.last_pass) {
+			if (hi > lo) {
+				const uint64_t a = dst_off[f.first_block + lo], e = dst_off[f.first_block + hi];
+				(void)xxh32_quad_stream<ROW>(lo ? carry : nullptr, carry, dst + a, e - a, l);
+			}
+			return;
+		}
+	}
 	uint32_t st = LA_ST_OK;
 	if (f.flags & LA_LZ4F_HEADER_SUM) {
 		uint32_t h = xxh32_quad(src + f.desc_off, f.desc_len - 1, 0, j);
 		if (((h >> 8) & 0xff) != src[f.desc_off + f.desc_len - 1])
 			st = LA_ST_LZ4_BAD_HEADER_SUM;
 	}
-	if (st == LA_ST_OK && (f.flags & (LA_LZ4F_CONT | LA_LZ4F_OPEN))) {
+	if (SPLIT && streamed) {
+		if (st == LA_ST_OK) {
+			/* the last piece (it may be empty) and the digest */
+			const uint64_t a = dst_off[f.first_block + lo], e = dst_off[f.first_block + hi];
+			if (xxh32_quad_stream<ROW>(lo ? carry : nullptr, nullptr, dst + a, e - a, l) != f.content_sum)
+				st = LA_ST_LZ4_BAD_CONTENT_SUM;
+		}
+	} else if (st == LA_ST_OK && (f.flags & (LA_LZ4F_CONT | LA_LZ4F_OPEN))) {
 		/* a frame larger than one batch: its content hash comes in and / or goes out as state */
 		if ((f.flags & LA_LZ4F_HASHED) && carry_in && carry_out) {
 			uint64_t a = dst_off[f.first_block], e = dst_off[f.first_block + f.n_blocks];
@@ -276,13 +329,34 @@ void la_launch_lz4_frame_sums(hipStream_t s, const uint8_t *d_src, const uint8_t
 {
 	if (n_frames == 0) return;
 	if (row)
-		hipLaunchKernelGGL(lz4_frame_sums_kernel<true>, dim3((n_frames + 3) / 4), dim3(64), 0, s,
+		hipLaunchKernelGGL((lz4_frame_sums_kernel<true, false>), dim3((n_frames + 3) / 4), dim3(64), 0, s,
 		    d_src, d_dst, d_frames, n_frames, d_dst_off, dst_cap, d_frame_status, end_lo, end_hi,
-		    (const la_xxh_carry *)d_carry_in, (la_xxh_carry *)d_carry_out);
+		    (const la_xxh_carry *)d_carry_in, (la_xxh_carry *)d_carry_out, frame_sums_pass<false>{});
 	else
-		hipLaunchKernelGGL(lz4_frame_sums_kernel<false>, dim3((n_frames + 15) / 16), dim3(64), 0, s,
+		hipLaunchKernelGGL((lz4_frame_sums_kernel<false, false>), dim3((n_frames + 15) / 16), dim3(64), 0, s,
 		    d_src, d_dst, d_frames, n_frames, d_dst_off, dst_cap, d_frame_status, end_lo, end_hi,
-		    (const la_xxh_carry *)d_carry_in, (la_xxh_carry *)d_carry_out);
+		    (const la_xxh_carry *)d_carry_in, (la_xxh_carry *)d_carry_out, frame_sums_pass<false>{});
+}
+
+/* Hash pass g of a split last slice, queued behind the launch of group g: the frames that end in (sp.first, sp.last]
+ * -- from 0 when the slice is the whole batch.  d_carries: sp.last - sp.first records of LA_XXH_CARRY_BYTES. */
+void la_launch_lz4_frame_sums_split(hipStream_t s, const uint8_t *d_src, const uint8_t *d_dst,
+    const la_lz4_frame *d_frames, uint32_t n_frames, const uint64_t *d_dst_off, uint64_t dst_cap,
+    uint32_t *d_frame_status, const la_lz4_split &sp, uint32_t g, void *d_carries, const void *d_carry_in,
+    void *d_carry_out, int row)
+{
+	if (n_frames == 0) return;
+	const frame_sums_pass<true> pass = { sp.first, sp.period, sp.bound[g], sp.bound[g + 1], g + 1 == sp.n_groups,
+	    (la_xxh_carry *)d_carries };
+	const uint32_t end_lo = sp.first ? sp.first + 1 : 0u;
+	if (row)
+		hipLaunchKernelGGL((lz4_frame_sums_kernel<true, true>), dim3((n_frames + 3) / 4), dim3(64), 0, s,
+		    d_src, d_dst, d_frames, n_frames, d_dst_off, dst_cap, d_frame_status, end_lo, sp.last,
+		    (const la_xxh_carry *)d_carry_in, (la_xxh_carry *)d_carry_out, pass);
+	else
+		hipLaunchKernelGGL((lz4_frame_sums_kernel<false, true>), dim3((n_frames + 15) / 16), dim3(64), 0, s,
+		    d_src, d_dst, d_frames, n_frames, d_dst_off, dst_cap, d_frame_status, end_lo, sp.last,
+		    (const la_xxh_carry *)d_carry_in, (la_xxh_carry *)d_carry_out, pass);
 }
 
 /* ------------------------------------------------------------------ CRC32 */

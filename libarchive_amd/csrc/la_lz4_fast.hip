@@ -119,6 +119,18 @@
  * of all three instantiations are unchanged.  The four C2 launches 16.31 -> 16.02 ms.  The stretch the stamps call "up to
  * the loads requested" fell by 0.7 k cycles only: the first stamp stands behind the routing test, most of the removed
  * trips were in front of it, and what is left there is the payload chunks' own round trip.
+ *
+ * The last slice by position in the frame (profiles/r32_lz4_last_slice.md): the step used to end with the content checksums
+ * of the last slice's frames, one serial chain per frame that could only start when the slice's launch had ended (0.86 ms
+ * in the sixteen-lane form, bound by the chain, not by the number of frames).  The last slice is now launched in groups of
+ * period positions (la_lz4_slices.h: positions 0..7 of every frame of sixteen, then 8..12, then 13..15), and behind each
+ * group the frames' chains advance over the blocks that exist by then (la_hash.hip).  For this kernel that is one more
+ * instantiation, STRIDED, which differs in how the workgroup finds its block and in nothing else: a two-dimensional grid,
+ * bi = base + blockIdx.x * period + blockIdx.y, still a scalar value at kernel entry, in front of the same two clauses.
+ * Registers, LDS and occupancy are the contiguous instantiation's (87 VGPRs, 74 368 B, no scratch, 4 waves per SIMD), and
+ * the three older instantiations' device code is the parent's, instruction for instruction.  The window launches of the
+ * last slice take together what the contiguous one took; what they lose is what every slice beside a hash launch loses
+ * (about 0.28 ms per slice), now that the last slice has its own frames hashed beside it instead of behind it.
  */
 #include "la_dev.h"
 
@@ -187,17 +199,28 @@ __device__ __forceinline__ seq_t seq_load(const la_lz4_seq *t, uint32_t k)
  * entry) and the search in front of the match phase is compiled out; DEPS = false: the kernel searches for itself
  * (the segmented launch, whose sequence numbers are segment-local, the deflate front end, and the cross-check
  * LA_LZ4_OPT_SEARCH_IN_EXPAND). */
-template <uint32_t MAXSEQ, bool SEG, bool DEPS>
+/* STRIDED = true: one group of a split last slice (la_lz4_slices.h).  The grid is two-dimensional, periods in x and the
+ * positions inside the group in y; the workgroup's block is la_lz4_split_block(), n is the slice's end in the batch's own
+ * numbering and every array is the whole batch's.  Nothing else differs: the block index is still a scalar value known at
+ * kernel entry.  Such a launch has no list of blocks, and the stride travels in the list's place among the arguments
+ * (same size, same offset), so the other instantiations' arguments, and with them their code, are what they were. */
+struct fast_stride { uint32_t base, period; };	/* first + h[g], P */
+template <bool STRIDED> struct fast_list_arg { typedef const uint32_t *__restrict__ type; };
+template <> struct fast_list_arg<true> { typedef fast_stride type; };
+static_assert(sizeof(fast_stride) == sizeof(const uint32_t *), "the stride takes the list's place");
+
+template <uint32_t MAXSEQ, bool SEG, bool DEPS, bool STRIDED = false>
 __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_kernel(
     const uint8_t *__restrict__ src, uint64_t src_bytes, const la_lz4_block *__restrict__ blocks,
     uint32_t n, uint8_t *__restrict__ dst, uint64_t dst_cap, const uint64_t *__restrict__ dst_off,
     const uint32_t *__restrict__ out_len, uint32_t *status_out,
     const uint32_t *__restrict__ nseq, const la_lz4_seq *__restrict__ table,
-    const uint64_t *__restrict__ table_off, const uint32_t *__restrict__ big_list,
+    const uint64_t *__restrict__ table_off, typename fast_list_arg<STRIDED>::type big_list /* STRIDED: the stride */,
     const uint32_t *__restrict__ big_count, uint32_t long_thr, const uint32_t *__restrict__ deps,
     const uint8_t *__restrict__ lit_plan)
 {
 	static_assert(!(SEG && DEPS), "the dependency words number a block's sequences from its first one");
+	static_assert(!(SEG && STRIDED), "the segmented launch takes its blocks from a list");
 	const uint32_t *status = status_out;
 	__shared__ __attribute__((aligned(16))) uint8_t win[16 + 65536 + 96];	/* 16 headroom (literal stores may start 3 bytes early) + 16 alignment shift + slack for over-reads */
 	__shared__ uint16_t dstpos[MAXSEQ + 4];
@@ -812,7 +835,9 @@ __global__ __launch_bounds__(FAST_THREADS, FAST_MIN_WAVES) void lz4_expand_fast_
 		g_out[tail0 + tid] = W[tail0 + tid];
 	STAMP(5);
 	};	/* do_block */
-	if (!SEG) {
+	if constexpr (STRIDED) {
+		do_block(la_lz4_split_block(big_list.base, big_list.period, blockIdx.x, blockIdx.y));
+	} else if constexpr (!SEG) {
 		do_block(blockIdx.x);
 	} else {
 		const uint32_t cnt = *big_count;
@@ -856,6 +881,19 @@ void la_launch_lz4_expand_fast(hipStream_t s, const la_expand_job &j)
 		    j.src, j.src_bytes, j.blocks, j.n, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
 		    j.table, j.table_off, (const uint32_t *)nullptr, (const uint32_t *)nullptr, j.long_thr, (const uint32_t *)nullptr,
 		    (const uint8_t *)nullptr);
+}
+
+/* Group g of a split last slice: j is the WHOLE batch's job (with dependency words and literal plans), sp the slice's
+ * schedule.  One workgroup per position of the group in every period that has one; a block at or behind sp.last leaves
+ * at the kernel's `bi >= n` test. */
+void la_launch_lz4_expand_fast_group(hipStream_t s, const la_expand_job &j, const la_lz4_split &sp, uint32_t g)
+{
+	const uint32_t gx = la_lz4_split_grid_x(&sp, g), gy = la_lz4_split_grid_y(&sp, g);
+	if (gx == 0 || gy == 0) return;
+	const fast_stride st = { sp.first + sp.bound[g], sp.period };
+	hipLaunchKernelGGL((lz4_expand_fast_kernel<LA_LZ4_FAST_MAXSEQ, false, true, true>), dim3(gx, gy), dim3(FAST_THREADS), 0, s,
+	    j.src, j.src_bytes, j.blocks, sp.last, j.dst, j.dst_cap, j.dst_off, j.out_len, j.status, j.nseq,
+	    j.table, j.table_off, st, (const uint32_t *)nullptr, j.long_thr, j.deps, j.lit_plan);
 }
 
 /* blocks with more than LA_LZ4_FAST_MAXSEQ sequences, over the WHOLE table: classify + a small

@@ -24,7 +24,14 @@ res["library_sha16"]=hashlib.sha256(open(lib,"rb").read()).hexdigest()[:16]	# th
 k=[x for x in res if "lz4_expand_fast_kernel" in x and "false" in x]
 if k:
     r=res[k[0]]
-    # FETCH_SIZE counts half the bytes of wide coalesced reads on gfx950 (MI355X_MICROARCH.md, HBM): doubled; units KiB
-    res["lz4_expand_fast_kernel"]={"hbm_bytes_per_launch": (2*r.get("fetch_kb_per_launch",0)+r.get("write_kb_per_launch",0))*1024, "launches": r.get("launches")}
+    # FETCH_SIZE counts half the bytes of wide coalesced reads on gfx950 (MI355X_MICROARCH.md, HBM): doubled; units KiB.
+    # The window kernel's launches of a step are three contiguous slices and the groups of the split last slice
+    # (la_lz4_slices.h), of unequal size, under one truncated name here: the figure is the kernel's bytes per STEP divided
+    # by four, a quarter of the step like bench.py's algorithmic_bytes and launch_ms (launches_per_step: 4), so that it
+    # stays comparable with the rounds that had four equal launches.  A step has one lz4_deps_kernel launch.
+    steps=res.get("lz4_deps_kernel",{}).get("launches") or r.get("launches")/4
+    per_launch=(2*r.get("fetch_kb_per_launch",0)+r.get("write_kb_per_launch",0))*1024
+    res["lz4_expand_fast_kernel"]={"hbm_bytes_per_launch": per_launch*r.get("launches")/steps/4, "launches": r.get("launches"), "steps": steps,
+        "note": "bytes per step / 4: the step's window launches are unequal since the last slice is split"}
 print(json.dumps(res, indent=1))
 PY
