@@ -24,8 +24,17 @@
  *            byte (from the output positions in LDS)
  *   pass 3   per sequence: the source's last byte by la_lz4_dep_source (la_dev.h), the map
  *            entries under the source's first and last byte, two short walks forward to q and
- *            to the last sequence under the source, that sequence's match start from LDS (la_lz4_dep_drops_last), and the
- *            word  q | count << 16  to deps[table_off + k]
+ *            to the last sequence under the source (la_lz4_dep_walk.h: by looks at four positions
+ *            at once, not step by step), that sequence's match start from LDS
+ *            (la_lz4_dep_drops_last), and the word  q | count << 16  to deps[table_off + k]
+ *
+ * Pass 3 has no branch per sequence but the one to the rare second look of a walk and the one around
+ * the store: both map entries and the block's first position are read by every lane, whatever its
+ * flags say, behind one wait; each walk's first look is four reads behind one wait; the last
+ * sequence's match start is read by every lane.  Step by step and with a branch per flag it was seven
+ * to eight round trips per sequence, each walk's with a trip through the loop's exec bookkeeping
+ * (profiles/r33_lz4_deps_looks.md; requesting the first looks of both walks together was measured too
+ * and gave nothing more).
  *
  * The word is the one the window kernel's own search hands its poll loop (same rule, same
  * functions), so the kernel given the words (DEPS = true) skips the search and nothing else
@@ -43,11 +52,16 @@
  * block's sequence count or its chunk count; nothing here waits for another thread.
  *
  * Every index is inside its array whatever the table holds: positions are 16-bit, so a map index
- * is below 2048; q and qe stay below k < ns <= LA_LZ4_FAST_MAXSEQ; deps is written at
- * table_off + k with k < ns, inside the block's table slot; plan entries are written at
+ * is below 2048; q and qe stay below k < ns <= LA_LZ4_FAST_MAXSEQ, and a look reads the positions
+ * up to index q + LA_LZ4_WALK_LOOK, at most four entries into the match starts of the same array;
+ * deps is written at table_off + k with k < ns, inside the block's table slot; plan entries are written at
  * c <= ceil(src_len / 32), two bytes each from byte table_off on, inside one byte per slot entry.
  */
 #include "la_dev.h"
+#include "la_lz4_dep_walk.h"
+
+static_assert(LA_LZ4_WALK_CAP == LA_LZ4_FAST_MAXSEQ && LA_LZ4_WALK_LOOK <= LA_LZ4_FAST_MAXSEQ,
+    "the walk's array is the kernel's positions; a look's entries behind them lie in the match starts");
 
 #define DEPS_THREADS 256
 #define DEPS_SLOTS   (LA_LZ4_FAST_MAXSEQ / DEPS_THREADS)	/* sequences per thread */
@@ -57,9 +71,13 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
     const uint32_t *__restrict__ status, const uint32_t *__restrict__ nseq, const la_lz4_seq *__restrict__ table,
     const uint64_t *__restrict__ table_off, uint32_t long_thr, uint32_t *__restrict__ deps, uint8_t *__restrict__ lit_plan)
 {
-	__shared__ uint16_t dstpos[LA_LZ4_FAST_MAXSEQ];		/* output position per sequence (20 KiB in all: eight workgroups per CU) */
-	__shared__ uint16_t mstart[LA_LZ4_FAST_MAXSEQ];		/* dst + lit_len: where the sequence's match starts; until the literal
-								 * plan is out, lit_src + lit_len: where its literals end in the payload */
+	__shared__ uint16_t posm[2 * LA_LZ4_FAST_MAXSEQ];	/* (20 KiB in all with the map: eight workgroups per CU) */
+	uint16_t *const dstpos = posm;				/* output position per sequence */
+	uint16_t *const mstart = posm + LA_LZ4_FAST_MAXSEQ;	/* dst + lit_len: where the sequence's match starts; until the literal
+								 * plan is out, lit_src + lit_len: where its literals end in the payload.
+								 * One array with the positions in front: a look from the last positions
+								 * (la_lz4_dep_walk.h) reads up to LA_LZ4_WALK_LOOK entries into this half,
+								 * which decide nothing */
 	__shared__ uint16_t cmap[2048];				/* per 32-byte output chunk: the sequence that holds its first byte */
 
 	const uint32_t bi = blockIdx.x;
@@ -156,9 +174,8 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
 
 	/* pass 3.  q is the largest index below k whose sequence starts at or before the source's first byte, qe the
 	 * same for its last byte (la_lz4_dep_source).  Both start from the map -- the sequence that holds the first
-	 * byte of the 32-byte chunk -- and walk up; a chunk holds at most eight sequence starts.  One sequence and
-	 * one walk at a time: the kernel is bound by instruction issue, not by the LDS round trips (eight waves per
-	 * SIMD cover those), and a loop over several sequences at once runs as long as the longest walk of all of them. */
+	 * byte of the 32-byte chunk -- and walk up; a chunk holds at most eight sequence starts, one on average.  One
+	 * sequence at a time: a loop over several sequences at once runs as long as the longest walk of all of them. */
 #pragma unroll
 	for (uint32_t r = 0; r < DEPS_SLOTS; r++) {
 		if (r * DEPS_THREADS >= ns)
@@ -170,29 +187,24 @@ __global__ __launch_bounds__(DEPS_THREADS) void lz4_deps_kernel(const la_lz4_blo
 		const uint32_t mlen = valid ? (((uint32_t)e & 0xFFFFu) - mdst) & 0xFFFFu : 0;
 		const uint32_t s0 = mdst - off;
 		uint32_t hi = 0;
-		const bool waits = valid && la_lz4_dep_source(d, mdst, off, mlen, &hi) && dstpos[0] <= hi;
+		const bool src = la_lz4_dep_source(d, mdst, off, mlen, &hi);	/* (false where valid is: mlen is 0 then) */
+		/* the map entries under the source's first and last byte and the block's first position, requested together and
+		 * whatever the flags say: s0 is cut to the map, hi < d <= 65535 (0 without a source), and a value that is not
+		 * wanted is not used */
+		const uint32_t q0 = cmap[(s0 < 65535u ? s0 : 65535u) >> 5], e0 = cmap[hi >> 5], first = dstpos[0];
+		const bool waits = src && first <= hi;
 		const uint32_t kq = valid ? k : 0, ke = waits ? k : 0;	/* the walks' bounds: 0 stops them at once */
-		uint32_t q = 0;
-		if (valid) {
-			const uint32_t q0 = cmap[(s0 < 65535u ? s0 : 65535u) >> 5];
-			q = q0 < k - 1 ? q0 : k - 1;
-		}
-		uint32_t qe = q;
-		if (waits) {	/* hi < d <= 65535: inside the map, and at or behind s0 */
-			const uint32_t e0 = cmap[hi >> 5];
-			const uint32_t e1 = e0 < k - 1 ? e0 : k - 1;
-			qe = e1 > q ? e1 : q;
-		}
-		while (q + 1 < kq && dstpos[q + 1] <= s0)
-			q++;
+		const uint32_t km1 = valid ? k - 1 : 0;
+		uint32_t q = q0 < km1 ? q0 : km1;
+		const uint32_t e1 = e0 < km1 ? e0 : km1;
+		uint32_t qe = waits && e1 > q ? e1 : q;
+		q = la_lz4_dep_walk(dstpos, q, kq, s0);
 		if (qe < q)
 			qe = q;
-		while (qe + 1 < ke && dstpos[qe + 1] <= hi)
-			qe++;
+		qe = la_lz4_dep_walk(dstpos, qe, ke, hi);
+		const uint32_t last = mstart[qe];	/* (qe < LA_LZ4_FAST_MAXSEQ; read by every lane, used where the sequence waits) */
 		if (k < ns) {
-			uint32_t cnt = 0;
-			if (waits)
-				cnt = qe - q + 1 - (la_lz4_dep_drops_last(hi, mstart[qe]) ? 1u : 0u);
+			const uint32_t cnt = waits ? qe - q + 1 - (la_lz4_dep_drops_last(hi, last) ? 1u : 0u) : 0u;
 			out[k] = q | (cnt << 16);
 		}
 	}
