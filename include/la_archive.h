@@ -33,6 +33,7 @@ extern "C" {
 #define ARCHIVE_FILTER_GZIP 1
 #define ARCHIVE_FILTER_BZIP2 2
 #define ARCHIVE_FILTER_XZ   6
+#define ARCHIVE_FILTER_UU   7
 #define ARCHIVE_FILTER_LZIP 9
 #define ARCHIVE_FILTER_LZOP 11
 #define ARCHIVE_FILTER_LZ4  13
@@ -62,6 +63,8 @@ int  archive_read_support_filter_lz4(struct archive *);				/* archive.h:469 */
 int  archive_read_support_filter_lzip(struct archive *);			/* archive.h:470 (host/la_filter_lzip.c) */
 int  archive_read_support_filter_lzop(struct archive *);			/* archive.h:472 (host/la_filter_lzop.c) */
 int  archive_read_support_filter_zstd(struct archive *);			/* archive.h:482 */
+int  archive_read_support_filter_uu(struct archive *);				/* archive.h:480 (host/la_filter_uu.c): uuencode and base64 lines decoded on the device */
+int  archive_read_support_compression_uu(struct archive *);			/* deprecated alias, uu.c:77-84 */
 int  archive_read_support_filter_xz(struct archive *);				/* archive.h:481 (host/la_filter_xz.c) */
 int  archive_read_support_filter_none(struct archive *);
 int  archive_read_support_format_raw(struct archive *);
@@ -135,6 +138,7 @@ void        archive_entry_set_size(struct archive_entry *, int64_t);
 void        archive_entry_unset_size(struct archive_entry *);
 void        archive_entry_set_filetype(struct archive_entry *, unsigned);	/* AE_IFREG, AE_IFDIR ... */
 void        archive_entry_set_perm(struct archive_entry *, unsigned);
+void        archive_entry_set_mode(struct archive_entry *, unsigned);	/* file type and permission bits in one word */
 
 #define ARCHIVE_ERRNO_MISC (-1)			/* archive_platform.h:213 */
 #define ARCHIVE_ERRNO_FILE_FORMAT 84		/* EILSEQ-like, archive_platform.h */

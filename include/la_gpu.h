@@ -145,8 +145,17 @@ enum {
 	LA_ST_LZOP_NOT_CONSUMED   = 45,	/* lzop.c:459-462 -> "lzop decompression failed: -8": the end marker stands in front of src_len */
 	LA_ST_LZOP_SHORT_OUTPUT   = 46,	/* lzop.c:449-454 -> "Corrupted data": the stream ends well with fewer than dst_len bytes */
 	LA_ST_LZOP_BAD_SUM_U      = 47,	/* lzop.c:473-477 -> "Corrupted data": the decoded bytes do not give the block's sum */
-	LA_ST_LZOP_REFUSED        = 48	/* the entry points outside d_src or d_dst, src_len > dst_len (lzop.c:332-333 "Corrupted lzop
+	LA_ST_LZOP_REFUSED        = 48,	/* the entry points outside d_src or d_dst, src_len > dst_len (lzop.c:332-333 "Corrupted lzop
 					 * header" is the host's) or dst_len is above LA_LZOP_MAX_BLOCK (lzop.c:324-325): not touched */
+	/* uu (archive_read_support_filter_uu.c): why the walk over a window's lines stopped at result.stop_off */
+	LA_ST_UU_IGNORED          = 49,	/* uu.c:515-519: a bad byte while looking for a head, behind decoded bytes: the rest of the
+					 * stream is ignored (ST_IGNORE) and the stream ends without an error */
+	LA_ST_UU_BAD_BYTE_HEAD    = 50,	/* uu.c:521-524 -> "Insufficient compressed data": the same with nothing decoded so far */
+	LA_ST_UU_BAD_BYTE         = 51,	/* uu.c:521-524 -> "Insufficient compressed data": a bad byte in a data line or an `end` line */
+	LA_ST_UU_BAD_LINE         = 52,	/* uu.c:607-656, :706-711 -> "Insufficient compressed data": a data line breaks its rules */
+	LA_ST_UU_BAD_END          = 53,	/* uu.c:659-666 -> "Insufficient compressed data": the line behind the zero-length line is not `end` */
+	LA_ST_UU_TOO_LONG         = 54,	/* uu.c:559-563 -> "Invalid format data": a line over LA_UU_MAX_HEAD_LINE / LA_UU_MAX_DATA_LINE */
+	LA_ST_UU_UNTERMINATED     = 55	/* uu.c:527-533 -> "Missing format data": the stream ends inside a line that is not `end` */
 };
 
 /* =====================================================================
@@ -911,6 +920,62 @@ typedef struct la_lzop_batch {
 
 uint64_t la_gpu_lzop_workspace_bytes(uint32_t n);
 int      la_gpu_lzop_decode(la_gpu_ctx *ctx, const la_lzop_batch *batch);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * uu -- replaces, for a window of the stream per call, the line loop of uudecode_filter_read
+ * (libarchive/archive_read_support_filter_uu.c:508-714): get_line, the four states and the two decoders.  A line decodes
+ * on its own once its start and the state in front of it are known, so the device finds the line starts, gives every
+ * line its transition function over the five states, resolves the states by a scan under composition from the state in
+ * front of the window, and decodes all lines at once.  csrc/la_uu_dev.h states the per-line rules.
+ *
+ * The call takes whole lines only.  In a window that is not `final`, a last line without its line end -- or whose only
+ * line end so far is a '\r' in the window's last byte -- is left to the next window: `consumed` stops in front of it.
+ * In a `final` window such a line is a line (uu.c:527-533: only `end` may stand there).  The walk stops at the first
+ * line that its state refuses; the bytes of the lines in front of it are in d_dst, `consumed` and `stop_off` are that
+ * line's offset and `state` is LA_UU_STOP.  Without a stop, status is LA_ST_OK and stop_off == consumed.
+ * The host parses mode and name from its own copy of d_src[head_off, head_off + head_len), the last header line the
+ * walk accepted.  src_bytes is at most LA_UU_MAX_SRC_BYTES; dst_cap >= src_bytes always suffices and is required.
+ * The workspace holds a line table sized for a window of '\n' alone, about 12 bytes per source byte.
+ * Additions under ABI version 3. */
+#define LA_UU_FIND_HEAD   0u	/* ST_FIND_HEAD, uu.c:57 */
+#define LA_UU_READ_UU     1u	/* ST_READ_UU */
+#define LA_UU_UUEND       2u	/* ST_UUEND */
+#define LA_UU_READ_BASE64 3u	/* ST_READ_BASE64 */
+#define LA_UU_STOP        4u	/* absorbing: the walk ended (ST_IGNORE, or one of the reference's errors) */
+#define LA_UU_MAX_HEAD_LINE 131072u	/* a line of this many bytes or more, line end included, while looking for a head (uu.c:559) */
+#define LA_UU_MAX_DATA_LINE 32768u	/* a data line of more bytes than this, line end included (uu.c:604, :669) */
+#define LA_UU_MAX_SRC_BYTES ((uint64_t)1 << 31)
+typedef struct la_uu_state {
+	uint32_t state;		/* LA_UU_FIND_HEAD .. LA_UU_READ_BASE64 */
+	uint32_t decoded;	/* nonzero: the stream has produced bytes in front of this window (uudecode->total > 0) */
+} la_uu_state;
+
+typedef struct la_uu_result {
+	uint32_t status;	/* LA_ST_OK or LA_ST_UU_* */
+	uint32_t state;		/* behind the lines taken; LA_UU_STOP with every status but LA_ST_OK */
+	uint32_t decoded;	/* in.decoded, or out_len > 0 */
+	uint32_t n_headers;	/* header lines accepted in this window */
+	uint64_t out_len;	/* bytes in d_dst */
+	uint64_t consumed;	/* source bytes of the whole lines taken */
+	uint64_t stop_off;	/* first byte of the line that stopped the walk (== consumed) */
+	uint64_t head_off;	/* the last accepted header line, line end included; 0, 0 when n_headers == 0 */
+	uint32_t head_len;
+	uint32_t reserved;
+} la_uu_result;
+
+typedef struct la_uu_batch {
+	const uint8_t *d_src;
+	uint64_t       src_bytes;
+	uint32_t       final;		/* nonzero: the window ends the stream */
+	uint32_t       reserved;	/* 0 */
+	la_uu_state    in;		/* the state in front of the window (host memory, read by the call) */
+	uint8_t       *d_dst;
+	uint64_t       dst_cap;		/* >= src_bytes */
+	la_uu_result  *d_result;	/* one record, device-resident */
+} la_uu_batch;
+
+uint64_t la_gpu_uu_workspace_bytes(uint64_t src_bytes);
+int      la_gpu_uu_decode(la_gpu_ctx *ctx, const la_uu_batch *batch);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * bzip2 compression -- replaces the BZ2_bzCompress loop of libarchive/archive_write_add_filter_bzip2.c (libbz2 is the

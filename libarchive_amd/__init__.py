@@ -38,6 +38,7 @@ from . import xz  # noqa: F401
 from .xz import compress_window as xz_compress_window  # noqa: F401
 from . import lzip  # noqa: F401
 from . import lzop  # noqa: F401
+from . import uu  # noqa: F401
 from .lzip import compress_window as lzip_compress_window  # noqa: F401
 from .lzop import compress_window as lzop_compress_window  # noqa: F401
 
@@ -46,5 +47,5 @@ __all__ = [
     "LZ4_BLOCK_DTYPE", "LZ4_FRAME_DTYPE", "HASH_JOB_DTYPE", "SUMMARY_DTYPE", "lz4",
     "status_message", "end_message", "bzip2", "BZ2_CAND_DTYPE", "BZ2_RESULT_DTYPE", "BZ2_STATE_DTYPE",
     "xz", "XZ_BLOCK_DTYPE", "XZ_RESULT_DTYPE", "xz_compress_window",
-    "lzip", "lzip_compress_window", "lzop", "lzop_compress_window",
+    "lzip", "lzip_compress_window", "lzop", "lzop_compress_window", "uu",
 ]

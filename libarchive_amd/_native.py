@@ -170,6 +170,24 @@ class _LzopBatchC(C.Structure):     # la_lzop_batch
                 ("reserved", C.c_uint32), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_results", C.c_void_p)]
 
 
+# uu (la_uu_state, la_uu_result, la_uu_batch)
+UU_RESULT_DTYPE = np.dtype([("status", "<u4"), ("state", "<u4"), ("decoded", "<u4"), ("n_headers", "<u4"), ("out_len", "<u8"),
+                            ("consumed", "<u8"), ("stop_off", "<u8"), ("head_off", "<u8"), ("head_len", "<u4"), ("reserved", "<u4")])
+LA_UU_FIND_HEAD, LA_UU_READ_UU, LA_UU_UUEND, LA_UU_READ_BASE64, LA_UU_STOP = 0, 1, 2, 3, 4
+LA_UU_MAX_HEAD_LINE, LA_UU_MAX_DATA_LINE, LA_UU_MAX_SRC_BYTES = 131072, 32768, 1 << 31
+(LA_ST_UU_IGNORED, LA_ST_UU_BAD_BYTE_HEAD, LA_ST_UU_BAD_BYTE, LA_ST_UU_BAD_LINE, LA_ST_UU_BAD_END, LA_ST_UU_TOO_LONG,
+ LA_ST_UU_UNTERMINATED) = 49, 50, 51, 52, 53, 54, 55
+
+
+class _UuStateC(C.Structure):       # la_uu_state
+    _fields_ = [("state", C.c_uint32), ("decoded", C.c_uint32)]
+
+
+class _UuBatchC(C.Structure):       # la_uu_batch
+    _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("final", C.c_uint32), ("reserved", C.c_uint32),
+                ("state_in", _UuStateC), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("d_result", C.c_void_p)]
+
+
 class _LzcBatchC(C.Structure):      # la_lzc_batch
     _fields_ = [("d_src", C.c_void_p), ("src_bytes", C.c_uint64), ("level", C.c_uint32), ("flags", C.c_uint32),
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_out_bytes", C.c_void_p)]
@@ -341,6 +359,9 @@ def gpu_lib():
         lib.la_gpu_lzop_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_lzop_workspace_bytes.argtypes = [C.c_uint32]
         lib.la_gpu_lzop_compress.argtypes = [C.c_void_p, C.POINTER(_LzopcBatchC)]
+        lib.la_gpu_uu_decode.argtypes = [C.c_void_p, C.POINTER(_UuBatchC)]
+        lib.la_gpu_uu_workspace_bytes.restype = C.c_uint64
+        lib.la_gpu_uu_workspace_bytes.argtypes = [C.c_uint64]
         lib.la_gpu_lzop_compress_workspace_bytes.restype = C.c_uint64
         lib.la_gpu_lzop_compress_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32]
         lib.la_gpu_lzop_compress_bound.restype = C.c_uint64
@@ -619,6 +640,9 @@ class GpuContext:
 
     def lzop_decode(self, batch: _LzopBatchC):
         self._check(gpu_lib().la_gpu_lzop_decode(self._h, C.byref(batch)), "la_gpu_lzop_decode")
+
+    def uu_decode(self, batch: _UuBatchC):
+        self._check(gpu_lib().la_gpu_uu_decode(self._h, C.byref(batch)), "la_gpu_uu_decode")
 
     def lzop_compress(self, batch: _LzopcBatchC):
         self._check(gpu_lib().la_gpu_lzop_compress(self._h, C.byref(batch)), "la_gpu_lzop_compress")

@@ -828,6 +828,32 @@ int la_gpu_lzop_decode(la_gpu_ctx *c, const la_lzop_batch *bt)
 	return LA_OK;
 }
 
+uint64_t la_gpu_uu_workspace_bytes(uint64_t src_bytes)
+{
+	return src_bytes <= LA_UU_MAX_SRC_BYTES ? la_uu_workspace_bytes(src_bytes) : 0u;
+}
+
+int la_gpu_uu_decode(la_gpu_ctx *c, const la_uu_batch *bt)
+{
+	if (!c || !bt || bt->reserved || !bt->d_result || bt->src_bytes > LA_UU_MAX_SRC_BYTES || bt->in.state > LA_UU_READ_BASE64)
+		return LA_ERR_ARG;
+	if (bt->src_bytes && (!bt->d_src || !bt->d_dst || bt->dst_cap < bt->src_bytes))
+		return LA_ERR_ARG;
+	const uint64_t need = la_uu_workspace_bytes(bt->src_bytes);
+	if (need > c->ws_bytes) {
+		int rc = la_gpu_reserve(c, need);
+		if (rc != LA_OK) return rc;
+	}
+	uint8_t *ws = (uint8_t *)c->ws;
+	prof_begin(c);
+	prof_range(c, "uu_lines", c->stream, [&] { la_launch_uu_lines(c->stream, bt, ws); });
+	prof_range(c, "uu_records", c->stream, [&] { la_launch_uu_records(c->stream, bt, ws); });
+	prof_range(c, "uu_states", c->stream, [&] { la_launch_uu_states(c->stream, bt, ws); });
+	prof_range(c, "uu_decode", c->stream, [&] { la_launch_uu_decode(c->stream, bt, ws); });
+	HIPCHK(c, hipGetLastError());
+	return LA_OK;
+}
+
 /* workspace of a gzip batch on the lane kernels: their scratch, then (two phases) E and the SEG launch's list; returns its size */
 static uint64_t gz_ws_carve(uint8_t *base, uint32_t n, bool two_phase, la_inflate_emit *E, uint32_t **big)
 {

@@ -756,6 +756,12 @@ void la_launch_lzip_decode(hipStream_t s, const la_lzip_batch *bt, uint8_t *ws);
 /* la_lzo.hip */
 uint64_t la_lzop_workspace_bytes(uint32_t n);
 void la_launch_lzop_decode(hipStream_t s, const la_lzop_batch *bt, uint8_t *ws);
+/* la_uu.hip: the four phases of la_gpu_uu_decode, in this order, over one workspace carved from src_bytes */
+uint64_t la_uu_workspace_bytes(uint64_t src_bytes);
+void la_launch_uu_lines(hipStream_t s, const la_uu_batch *bt, uint8_t *ws);
+void la_launch_uu_records(hipStream_t s, const la_uu_batch *bt, uint8_t *ws);
+void la_launch_uu_states(hipStream_t s, const la_uu_batch *bt, uint8_t *ws);
+void la_launch_uu_decode(hipStream_t s, const la_uu_batch *bt, uint8_t *ws);
 /* la_xz_filters.hip: the chains behind d_blocks[n] (LA_XZ_BATCH_CHAINS) undone over the decoded bytes; jobs_ws is
  * la_launch_xz_decode's workspace, ws a 256-byte aligned scratch of la_xz_unfilter_ws_bytes() of its own */
 uint64_t la_xz_unfilter_ws_bytes(uint32_t n, uint64_t dst_cap);

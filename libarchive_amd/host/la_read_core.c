@@ -85,6 +85,7 @@ void archive_entry_set_size(struct archive_entry *e, int64_t s) { e->size = s; e
 void archive_entry_unset_size(struct archive_entry *e) { e->size = 0; e->size_set = 0; }
 void archive_entry_set_filetype(struct archive_entry *e, unsigned type) { e->filetype = type & AE_IFMT; }
 void archive_entry_set_perm(struct archive_entry *e, unsigned perm) { e->mode = perm & 07777u; }
+void archive_entry_set_mode(struct archive_entry *e, unsigned mode) { e->filetype = mode & AE_IFMT; e->mode = mode & 07777u; }
 
 /* ------------------------------------------------------------------ object */
 
@@ -132,6 +133,7 @@ extern int archive_read_support_filter_bzip2(struct archive *) __attribute__((we
 extern int archive_read_support_filter_xz(struct archive *) __attribute__((weak));	/* la_filter_xz.c, the same way */
 extern int archive_read_support_filter_lzip(struct archive *) __attribute__((weak));	/* la_filter_lzip.c */
 extern int archive_read_support_filter_lzop(struct archive *) __attribute__((weak));	/* la_filter_lzop.c */
+extern int archive_read_support_filter_uu(struct archive *) __attribute__((weak));	/* la_filter_uu.c */
 
 int archive_read_support_filter_all(struct archive *a)
 {
@@ -147,6 +149,8 @@ int archive_read_support_filter_all(struct archive *a)
 		archive_read_support_filter_lzip(a);
 	if (archive_read_support_filter_lzop)
 		archive_read_support_filter_lzop(a);
+	if (archive_read_support_filter_uu)
+		archive_read_support_filter_uu(a);
 	archive_clear_error(a);
 	return ARCHIVE_OK;
 }
