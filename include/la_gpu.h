@@ -787,7 +787,8 @@ typedef struct la_xz_result {
  * PowerPC, IA-64, ARM, ARM-Thumb, SPARC (prop: start_offset).  csrc/la_xz_filters_dev.h states the transforms.  They are
  * undone in reverse order over the block's out_len bytes (a failed block: over its valid bytes) between decode and
  * verify, so the check is taken over the unfiltered bytes.  An entry with a count above LA_XZ_CHAIN_MAX, an id outside
- * 0x03 .. 0x09 or a start_offset the filter's alignment does not divide is LA_ST_XZ_SIZE for its block.  Any other
+ * 0x03 .. 0x09 or a start_offset the filter's alignment does not divide is LA_ST_XZ_SIZE for its block, which is not
+ * decoded (its bytes of d_dst are not touched, as for an entry that points outside a buffer).  Any other
  * non-zero flag word is LA_ERR_ARG.  The filters' scratch (16 bytes per block, 256 per 16 KiB of dst_cap) is reserved
  * in the context's workspace by the call itself, beside la_gpu_xz_workspace_bytes(n). */
 #define LA_XZ_BATCH_CHAINS 1u

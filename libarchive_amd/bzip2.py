@@ -97,12 +97,15 @@ class Bz2DevicePlan:
         self.ctx.bzip2_decode(self.batch)
         return self.state()
 
-    def emit(self, n_emit=None, dst_cap=None):
+    def emit(self, n_emit=None, dst_cap=None, d_dst=None):
+        """`d_dst`: the caller's destination (a 1-D uint8 tensor of at least dst_cap bytes, a view at any offset) instead
+        of one of the plan's own"""
         import torch
         st = self.state()
         if dst_cap is None:
             dst_cap = int(st["total_out"])
-        self.d_dst = torch.empty(max(int(dst_cap), 16), dtype=torch.uint8, device=self.d_src.device)
+        self.d_dst = d_dst if d_dst is not None else torch.empty(max(int(dst_cap), 16), dtype=torch.uint8, device=self.d_src.device)
+        assert self.d_dst.numel() >= int(dst_cap)
         self.batch.phase = N.LA_BZ2_EMIT
         self.batch.d_dst, self.batch.dst_cap = self.d_dst.data_ptr(), int(dst_cap)
         self.batch.n_emit = self.n if n_emit is None else n_emit

@@ -22,9 +22,11 @@
 		__syncthreads(); \
 	} while (0)
 #include "la_xz_dev.h"
+#include "la_xz_filters_dev.h"	/* la_xz_chain_valid */
 
-__global__ __launch_bounds__(64) void xz_decode_kernel(const uint8_t *d_src, uint64_t src_bytes, const la_xz_block *d_blocks, uint32_t n,
-    uint8_t *d_dst, uint64_t dst_total, la_xz_result *d_results, la_hash_job *d_jobs)
+/* d_chains: the chain table of a batch with LA_XZ_BATCH_CHAINS, else null */
+__global__ __launch_bounds__(64) void xz_decode_kernel(const uint8_t *d_src, uint64_t src_bytes, const la_xz_block *d_blocks,
+    const la_xz_chain *d_chains, uint32_t n, uint8_t *d_dst, uint64_t dst_total, la_xz_result *d_results, la_hash_job *d_jobs)
 {
 	__shared__ uint16_t probs[LA_XZ_PROBS_MAX];
 	__shared__ la_xz_lzma lz;
@@ -34,9 +36,14 @@ __global__ __launch_bounds__(64) void xz_decode_kernel(const uint8_t *d_src, uin
 		return;
 	const la_xz_block blk = d_blocks[b];
 	la_hash_job job = { blk.dst_off, 0u, 0u };
-	/* a table entry that points outside the two buffers is not decoded at all */
-	if (blk.src_off > src_bytes || blk.dst_off > dst_total || blk.dst_cap > dst_total - blk.dst_off || blk.dst_cap > LA_XZ_DST_CAP_MAX ||
-	    (blk.uncomp_size != LA_XZ_UNKNOWN && blk.uncomp_size > blk.dst_cap)) {
+	/* a table entry that points outside the two buffers, or whose chain cannot be undone, is not decoded at all */
+	bool refused = blk.src_off > src_bytes || blk.dst_off > dst_total || blk.dst_cap > dst_total - blk.dst_off || blk.dst_cap > LA_XZ_DST_CAP_MAX ||
+	    (blk.uncomp_size != LA_XZ_UNKNOWN && blk.uncomp_size > blk.dst_cap);
+	if (!refused && d_chains) {
+		const la_xz_chain ch = d_chains[b];
+		refused = !la_xz_chain_valid(&ch);
+	}
+	if (refused) {
 		if (threadIdx.x == 0) {
 			const la_xz_result bad = { LA_ST_XZ_SIZE, 0u, 0u, 0u, 0u };
 			d_results[b] = bad;
@@ -130,8 +137,9 @@ void la_launch_xz_decode(hipStream_t s, const la_xz_batch *bt, uint8_t *ws)
 	if (bt->n == 0)
 		return;
 	la_hash_job *jobs = (la_hash_job *)ws;
-	hipLaunchKernelGGL(xz_decode_kernel, dim3(bt->n), dim3(64), 0, s, bt->d_src, bt->src_bytes, bt->d_blocks, bt->n, bt->d_dst, bt->dst_cap,
-	    bt->d_results, jobs);
+	const la_xz_chain *chains = (bt->reserved & LA_XZ_BATCH_CHAINS) ? (const la_xz_chain *)(bt->d_blocks + bt->n) : nullptr;
+	hipLaunchKernelGGL(xz_decode_kernel, dim3(bt->n), dim3(64), 0, s, bt->d_src, bt->src_bytes, bt->d_blocks, chains, bt->n, bt->d_dst,
+	    bt->dst_cap, bt->d_results, jobs);
 }
 
 void la_launch_xz_verify(hipStream_t s, const la_xz_batch *bt, uint8_t *ws)

@@ -80,9 +80,10 @@ def member_table(entries):
 
 
 class LzipDevicePlan:
-    """One call: run() decodes the table; results() / output(i) read back."""
+    """One call: run() decodes the table; results() / output(i) read back.  `d_dst` is the caller's destination (a 1-D
+    uint8 tensor of at least dst_cap bytes, a view at any offset) instead of a zeroed one of the plan's own."""
 
-    def __init__(self, ctx, d_src, members, dst_cap=None):
+    def __init__(self, ctx, d_src, members, dst_cap=None, d_dst=None):
         import torch
         dev = d_src.device
         self.ctx, self.n, self.d_src, self.members = ctx, len(members), d_src, members
@@ -92,7 +93,8 @@ class LzipDevicePlan:
         table = np.ascontiguousarray(members).view(np.uint8).reshape(-1)
         self.d_members = torch.from_numpy(table.copy()).to(dev) if self.n else torch.zeros(16, dtype=torch.uint8, device=dev)
         self.d_results = torch.zeros(max(self.n, 1) * LZIP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.d_dst = torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
+        self.d_dst = d_dst if d_dst is not None else torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
+        assert self.d_dst.numel() >= self.dst_cap
         b = N._LzipBatchC()
         b.d_src, b.src_bytes = (d_src.data_ptr() if d_src.numel() else None), d_src.numel()
         b.d_members, b.n = self.d_members.data_ptr(), self.n

@@ -75,9 +75,10 @@ def block_table(entries):
 
 
 class LzopDevicePlan:
-    """One call: run() decodes the table; results() / output(i) read back."""
+    """One call: run() decodes the table; results() / slab() read back.  `d_dst` is the caller's destination (a 1-D uint8
+    tensor of at least dst_cap bytes, a view at any offset) instead of a zeroed one of the plan's own."""
 
-    def __init__(self, ctx, d_src, blocks, dst_cap=None):
+    def __init__(self, ctx, d_src, blocks, dst_cap=None, d_dst=None):
         import torch
         dev = d_src.device
         self.ctx, self.n, self.d_src, self.blocks = ctx, len(blocks), d_src, blocks
@@ -87,7 +88,8 @@ class LzopDevicePlan:
         table = np.ascontiguousarray(blocks).view(np.uint8).reshape(-1)
         self.d_blocks = torch.from_numpy(table.copy()).to(dev) if self.n else torch.zeros(16, dtype=torch.uint8, device=dev)
         self.d_results = torch.zeros(max(self.n, 1) * LZOP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.d_dst = torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
+        self.d_dst = d_dst if d_dst is not None else torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
+        assert self.d_dst.numel() >= self.dst_cap
         b = N._LzopBatchC()
         b.d_src, b.src_bytes = (d_src.data_ptr() if d_src.numel() else None), d_src.numel()
         b.d_blocks, b.n = self.d_blocks.data_ptr(), self.n

@@ -64,9 +64,10 @@ def chain_table(chains):
 
 class XzDevicePlan:
     """One call: run() decodes the table; results() / output(i) read back.  With `chains` (see chain_table) the chain
-    table rides behind the blocks and the call is made with LA_XZ_BATCH_CHAINS."""
+    table rides behind the blocks and the call is made with LA_XZ_BATCH_CHAINS.  `d_dst` is the caller's destination (a
+    1-D uint8 tensor of at least dst_cap bytes, a view at any offset) instead of a zeroed one of the plan's own."""
 
-    def __init__(self, ctx, d_src, blocks, dst_cap=None, chains=None):
+    def __init__(self, ctx, d_src, blocks, dst_cap=None, chains=None, d_dst=None):
         import torch
         dev = d_src.device
         self.ctx, self.n, self.d_src, self.blocks = ctx, len(blocks), d_src, blocks
@@ -79,7 +80,8 @@ class XzDevicePlan:
             table = np.concatenate([table, np.ascontiguousarray(chain_table(chains)).view(np.uint8).reshape(-1)])
         self.d_blocks = torch.from_numpy(table.copy()).to(dev) if self.n else torch.zeros(16, dtype=torch.uint8, device=dev)
         self.d_results = torch.zeros(max(self.n, 1) * XZ_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.d_dst = torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
+        self.d_dst = d_dst if d_dst is not None else torch.zeros(max(self.dst_cap, 16), dtype=torch.uint8, device=dev)
+        assert self.d_dst.numel() >= self.dst_cap
         b = N._XzBatchC()
         b.d_src, b.src_bytes = (d_src.data_ptr() if d_src.numel() else None), d_src.numel()
         b.d_blocks, b.n = self.d_blocks.data_ptr(), self.n

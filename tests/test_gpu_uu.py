@@ -98,26 +98,9 @@ def test_long_base64_lines(dev):
     assert dev.check(b"j" * 70000 + b"\x80" + b"j" * 70000 + b"\n", decoded=True).status == U.ST_IGNORED
 
 
-def residue_stream(style, seed):
-    """base64 lines whose lengths (line end included) cycle through 1 .. 62: more than three tiles, more than three
-    groups of lines; a body of 4k + 1 characters ends in '='"""
-    r = random.Random(seed)
-    out = bytearray()
-    alphabet = U.B64_ALPHABET
-    for i in range(1000):
-        nl = style if style != b"mixed" else r.choice([b"\n", b"\r\n", b"\r"])
-        length = 1 + i % 62
-        n = max(length - len(nl), 0)
-        body = bytes(r.choice(alphabet) for _ in range(n))
-        if n % 4 == 1:
-            body = body[:-1] + b"="
-        out += body + nl
-    return bytes(out)
-
-
 @pytest.mark.parametrize("style", [b"\n", b"\r\n", b"\r", b"mixed"])
 def test_line_starts_at_every_residue(dev, style):
-    s = residue_stream(style, 5)
+    s = U.residue_stream(style, 5)
     assert len(s) > 3 * TILE and len(U.lines_of(s)) > 3 * LINES_PER_GROUP
     w = dev.check(s, U.READ_BASE64)
     assert w.status == U.ST_OK and len(w.out) > 15000

@@ -334,6 +334,23 @@ def b64_section(data, name=b"file.bin", mode=0o644, nl=b"\n", per_line=57, end=b
     return bytes(out)
 
 
+def residue_stream(style, seed):
+    """base64 lines whose lengths (line end included) cycle through 1 .. 62: more than three tiles, more than three
+    groups of lines; a body of 4k + 1 characters ends in '='"""
+    r = random.Random(seed)
+    out = bytearray()
+    alphabet = B64_ALPHABET
+    for i in range(1000):
+        nl = style if style != b"mixed" else r.choice([b"\n", b"\r\n", b"\r"])
+        length = 1 + i % 62
+        n = max(length - len(nl), 0)
+        body = bytes(r.choice(alphabet) for _ in range(n))
+        if n % 4 == 1:
+            body = body[:-1] + b"="
+        out += body + nl
+    return bytes(out)
+
+
 def junk(seed, n_lines, nl=b"\n", width=72):
     """mail-style lines of printable characters; none of them is a header line"""
     r = random.Random(seed)
